@@ -366,6 +366,33 @@ def respawn_under_torchrun(n):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, records, pcap, seed=0):
+    """--dump-outputs DIR: what the timed path handed its caller in its last step -- the (all-gathered) keypoint records
+    (kpts [N, pcap, J, D], count [N], scores [N, pcap]) -- as float32 DIR/<name>.npy, so that two builds can be compared
+    output for output.  Slots past an image's person count are not part of the result (the buffer set keeps whatever it
+    held there) and are written as zeros.  Above 64 MB in all a fixed, seeded sample of images is written, and their
+    indices as image_index.npy."""
+    kpts, count, scores = [t.cpu() for t in records]
+    N, P = kpts.shape[0], kpts.shape[1]
+    valid = torch.arange(P)[None, :] < count.to(torch.int64).clamp(max=pcap)[:, None]
+    kpts = torch.where(valid[:, :, None, None], kpts, torch.zeros((), dtype=kpts.dtype))
+    scores = torch.where(valid, scores, torch.zeros((), dtype=scores.dtype))
+    arrays = {'kpts': kpts.numpy().astype(np.float32), 'count': count.numpy().astype(np.float32),
+              'scores': scores.numpy().astype(np.float32)}
+    per_image = sum(a[0].nbytes for a in arrays.values()) + 4
+    if N * per_image > DUMP_CAP_BYTES:
+        keep = np.sort(np.random.default_rng(seed).choice(N, DUMP_CAP_BYTES // per_image, replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays['image_index'] = keep.astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def parity_check(eng, arch, sd, cfg, R, x, offs_np, records, sample, tol=2e-5):
     """Outside the timed region: the last batch's device maps and records against the oracle on a
     sample of images.  (i) merged heatmaps / tags vs the full CPU pipeline, <= 2e-5; (ii) the
@@ -446,7 +473,11 @@ def main():
     ap.add_argument('--no-io-leg', action='store_true', help='skip the I/O-inclusive leg (value_with_io)')
     ap.add_argument('--shard-seed', type=int, default=-1, help='data seed offset (default: the rank)')
     ap.add_argument('--dump', default='', help='rank 0 saves the gathered records of the last step (npz)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='rank 0 writes the records of the last timed step as float32 DIR/<name>.npy (dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     default_run = not (args.config or args.arch or args.size or args.batch or args.storage)
     preset = CONFIGS.get(args.config, {})
     args.arch = args.arch or preset.get('arch', 'search-XS')
@@ -565,6 +596,10 @@ def main():
     total_images = B * world * args.steps
     value = total_images / dt
     _log('timed run: %.4f ms/step' % ms_per_step)
+    if rank == 0 and args.dump_outputs:
+        # `out` is the last timed step's result: its buffer set is not written again before the next submit
+        dumped = dump_outputs(args.dump_outputs, out, pcap)
+        _log('outputs of the last timed step written to %s: %s' % (args.dump_outputs, ', '.join(dumped)))
     # a second, longer region: the same loop for --long-steps steps, bracketed the same way, max over
     # ranks -- a low-variance number beside the driver's K-step one, never instead of it
     ms_long = None

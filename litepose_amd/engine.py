@@ -452,7 +452,7 @@ class PoseEngine(object):
                     tensors = ent['out']
                     self._stats['graph_replays'] += 1
                 elif self._use_graphs and key in lane['seen'] and self._may_capture():
-                    tensors = self._capture_lane(lane, key, images, offsets, center, scale)
+                    tensors = self._capture_lane(lane, key, fork, images, offsets, center, scale)
                 else:
                     tensors = lane['eng']._infer_one(images, offsets, center, scale)
                     self._stats['eager_stages'] += 1
@@ -576,7 +576,10 @@ class PoseEngine(object):
                     ent['bufs'] = eng._buffers(images.shape[0], images.shape[2], images.shape[3])
                     ctx = ent['ctx']
             if not replay and not capture:
-                ctx = eng._stage_net(images, offsets, early)
+                if lane['stream'] is not ns:         # the capture failed and moved the lane to a fresh stream
+                    ns = _rejoin(lane['stream'], fork, lane['ae_done'])
+                with torch.cuda.stream(ns):
+                    ctx = eng._stage_net(images, offsets, early)
             net_done = torch.cuda.Event()
             net_done.record(ns)
         with torch.cuda.stream(aes):
@@ -593,7 +596,10 @@ class PoseEngine(object):
                     _remember(lane['graphs'], key, ent)
                     self._stats['graph_captures'] += 1
                 else:                                # first sight of the key, or a capture failed: eager
-                    tensors = eng._stage_ae(ctx, center, scale)
+                    if lane['ae_stream'] is not aes:     # the capture failed and moved the lane to a fresh stream
+                        aes = _rejoin(lane['ae_stream'], net_done, lane['consumed'])
+                    with torch.cuda.stream(aes):
+                        tensors = eng._stage_ae(ctx, center, scale)
                     _remember(lane['seen'], key)
                     self._stats['eager_stages'] += 1
             done = torch.cuda.Event()
@@ -619,7 +625,7 @@ class PoseEngine(object):
             self._capture_failed(e, stream)
             return None
 
-    def _capture_lane(self, lane, key, images, offsets, center, scale):
+    def _capture_lane(self, lane, key, fork, images, offsets, center, scale):
         """Capture one batch of this lane into a hipGraph (buffers exist already: the lane ran eagerly
         once) and launch it.  Any failure falls back to eager launches for good."""
         try:
@@ -634,11 +640,15 @@ class PoseEngine(object):
             return tensors
         except Exception as e:                           # capture is an optimisation, never a requirement
             self._capture_failed(e, lane['stream'])
-            return lane['eng']._infer_one(images, offsets, center, scale)
+            with torch.cuda.stream(_rejoin(lane['stream'], fork, lane['consumed'])):
+                return lane['eng']._infer_one(images, offsets, center, scale)
 
     def _capture_failed(self, exc, stream):
         """A capture raised (typically: another host thread made a HIP call while it was open).  Leave capture mode
-        if the stream is still in it, clear the sticky error, drop every graph and stay with eager launches."""
+        if the stream is still in it, clear the sticky error, drop every graph and stay with eager launches.  A stream
+        whose capture was invalidated keeps refusing launches after hipStreamEndCapture ("operation failed due to a
+        previous error during capture", ROCm 7.2 under capture_error_mode='global': tests/capture_probe.py), so every
+        lane on it moves to a fresh stream of the same priority; the caller re-joins its batch there."""
         import warnings
         warnings.warn('hipGraph capture failed (%s); staying with eager launches' % (exc,))
         self._use_graphs = False
@@ -647,8 +657,14 @@ class PoseEngine(object):
             self._lib.lp_stream_abort_capture(C.c_void_p(stream.cuda_stream))
         except Exception:
             pass
+        fresh = torch.cuda.Stream(device=stream.device, priority=stream.priority)
+        while fresh.cuda_stream == stream.cuda_stream:          # torch hands out pooled streams round-robin
+            fresh = torch.cuda.Stream(device=stream.device, priority=stream.priority)
         for ln in self._lanes:
             ln['graphs'].clear()
+            for k in ('stream', 'ae_stream'):
+                if ln[k] is not None and ln[k].cuda_stream == stream.cuda_stream:
+                    ln[k] = fresh
         try:
             torch.cuda.synchronize()
         except Exception:
@@ -661,6 +677,14 @@ def _dist_world():
         return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     except Exception:
         return 1
+
+
+def _rejoin(stream, *events):
+    """``stream`` made to wait for the events a stage depends on (None entries skipped); returns it."""
+    for ev in events:
+        if ev is not None:
+            stream.wait_event(ev)
+    return stream
 
 
 def _remember(d, key, value=True):

@@ -256,3 +256,42 @@ def test_cus_occupied_and_the_second_flop_yardstick(bench):
     b = bench.price_flops(fl, fv, ms, 'f32', mfma_peak=bench.BF16X3_EQUIV_TFLOPS)
     assert abs(a['frac_flops'] - 0.487) < 2e-3 and abs(b['frac_flops'] - 0.294) < 2e-3     # VERDICT r05's two numbers
     assert b['flops_valu'] == a['flops_valu'] and b['mfma_peak_tflops'] < a['mfma_peak_tflops'] * 3
+
+
+def test_dump_outputs_writes_the_records_as_float32(bench, tmp_path):
+    """--dump-outputs DIR: the records of the last timed step as float32 .npy files; slots past an image's person count
+    (not part of the result) are zeros, so two runs on the same inputs compare file for file."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(3)
+    kpts, scores = torch.randn(4, 30, 14, 5, generator=g), torch.randn(4, 30, generator=g)
+    count = torch.tensor([0, 2, 30, 41], dtype=torch.int32)                 # 41: more persons than the record holds
+    names = bench.dump_outputs(str(tmp_path / 'a'), (kpts, count, scores), 30)
+    assert names == ['count', 'kpts', 'scores']
+    d = {n: np.load(str(tmp_path / 'a' / (n + '.npy'))) for n in names}
+    assert all(a.dtype == np.float32 for a in d.values())
+    assert d['count'].tolist() == [0.0, 2.0, 30.0, 41.0] and d['kpts'].shape == (4, 30, 14, 5)
+    for n, k in enumerate((0, 2, 30, 30)):
+        assert np.array_equal(d['kpts'][n, :k], kpts[n, :k].numpy()) and not d['kpts'][n, k:].any()
+        assert np.array_equal(d['scores'][n, :k], scores[n, :k].numpy()) and not d['scores'][n, k:].any()
+    kpts[0] = 7.0                                                           # the tail of an image is not compared
+    bench.dump_outputs(str(tmp_path / 'b'), (kpts, count, scores), 30)
+    assert all(np.array_equal(d[n], np.load(str(tmp_path / 'b' / (n + '.npy')))) for n in names)
+
+
+def test_dump_outputs_samples_a_fixed_subset_above_64_mb(bench, tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, 'DUMP_CAP_BYTES', 10 * (30 * 14 * 5 + 30 + 1) * 4 + 4 * 10)
+    kpts = torch.arange(40 * 30 * 14 * 5, dtype=torch.float32).reshape(40, 30, 14, 5)
+    count = torch.full((40,), 30, dtype=torch.int32)
+    scores = torch.arange(40 * 30, dtype=torch.float32).reshape(40, 30)
+    names = bench.dump_outputs(str(tmp_path / 'a'), (kpts, count, scores), 30)
+    assert names == ['count', 'image_index', 'kpts', 'scores']
+    idx = np.load(str(tmp_path / 'a' / 'image_index.npy')).astype(np.int64)
+    assert len(idx) == 10 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'kpts.npy')), kpts.numpy()[idx])
+    total = sum(os.path.getsize(str(tmp_path / 'a' / (n + '.npy'))) - 128 for n in names)
+    assert total <= bench.DUMP_CAP_BYTES
+    bench.dump_outputs(str(tmp_path / 'b'), (kpts, count, scores), 30)
+    assert np.array_equal(idx, np.load(str(tmp_path / 'b' / 'image_index.npy')).astype(np.int64))

@@ -348,11 +348,44 @@ int lp_preprocess_batch(const uint8_t* d_images, int N, int H, int W, const doub
                         const float* h_mean, const float* h_std, uint8_t* d_resized_u8, float* d_tensor,
                         void* stream);
 
+/* cv::warpAffine's inversion of the 2x3 src->dst matrix h_trans into the dst->src matrix h_minv, in fp64 (host only;
+ * lp_preprocess_batch applies it before its launch; a singular matrix gives the zero-determinant form cv2 uses).   */
+int lp_warp_invert(const double* h_trans, double* h_minv);
+
+/* Per-image source and transform of lp_preprocess_batch_v: 64 bytes, no implicit padding (8 + 4 + 4 + 6 * 8), the
+ * layout of a row of a [N,8]-int64 / [N,16]-int32 table a loader fills.
+ *   src_offset  byte offset of the image's [H,W,3] uint8 pixels in the packed source buffer
+ *   H, W        its size (1..32767)
+ *   minv        the INVERTED (dst -> src) 2x3 matrix, lp_warp_invert of get_affine_transform's                       */
+typedef struct lp_warp_desc {
+    int64_t src_offset;
+    int32_t H, W;
+    double minv[6];
+} lp_warp_desc;
+
+/* The batch form of lp_preprocess for images of DIFFERENT sizes and transforms (a validation set's bucket: every image
+ * warped to the bucket's (Wd, Hd) with its own get_affine_transform, lib/utils/transforms.py:155-192): ONE launch.
+ *   d_src [src_bytes]  the N source images packed back to back (any offsets), uint8 HWC
+ *   d_desc [N]         DEVICE table of lp_warp_desc, read when the launch runs (refill it in place between batches)
+ *   outputs as lp_preprocess_batch: d_resized_u8 [N,Hd,Wd,3] and/or d_tensor [N,3,Hd,Wd]
+ * Bit-identical per image to lp_preprocess with that image's transform.  A descriptor whose image does not lie inside
+ * [0, src_bytes) or whose H or W is outside 1..32767 yields zeros for that image and reads nothing.                 */
+int lp_preprocess_batch_v(const uint8_t* d_src, size_t src_bytes, const lp_warp_desc* d_desc, int N, int Hd, int Wd,
+                          const float* h_mean, const float* h_std, uint8_t* d_resized_u8, float* d_tensor,
+                          void* stream);
+
 /* utils.transforms.get_final_preds (lib/utils/transforms.py:195-202,50-56): inverse
  * affine (rot 0) heatmap -> image coordinates, in place on x,y of d_ans.
  * h_center [2], h_scale [2] as returned by get_multi_scale_size, heatmap size (Wp,Hp).  */
 int lp_final_preds(float* d_ans, const int32_t* d_count, int N, int pcap, int J, int T,
                    const double* h_center, const double* h_scale, int Wp, int Hp, void* stream);
+/* The host arithmetic of lp_final_preds: h_coef4 = (sx, tx, sy, ty) with x' = sx * x + tx, y' = sy * y + ty (fp64) for
+ * one image's centre / scale and heatmap size (Wp, Hp in 1..32767).                                                 */
+int lp_final_preds_coef(const double* h_center, const double* h_scale, int Wp, int Hp, double* h_coef4);
+/* lp_final_preds with a transform per image: d_coef [N,4] fp64 DEVICE table of lp_final_preds_coef rows, read when the
+ * launch runs.  Bit-identical per image to lp_final_preds with that image's centre / scale.  J 1..32, T 1..2.      */
+int lp_final_preds_v(float* d_ans, const int32_t* d_count, int N, int pcap, int J, int T, const double* d_coef,
+                     void* stream);
 
 /* Recovery after a failed hipGraph capture (another host thread's HIP call can invalidate a capture in progress,
  * e.g. the RCCL watchdog of torch.distributed polling events): if `stream` is still in capture mode, end the capture,

@@ -41,6 +41,11 @@ class LpParseParams(C.Structure):
     ]
 
 
+class LpWarpDesc(C.Structure):
+    """lp_warp_desc: one row (64 bytes) of the device descriptor table of lp_preprocess_batch_v."""
+    _fields_ = [('src_offset', C.c_int64), ('H', C.c_int32), ('W', C.c_int32), ('minv', C.c_double * 6)]
+
+
 class LitePoseNativeError(RuntimeError):
     pass
 
@@ -98,9 +103,14 @@ _SIGS = {
                             C.POINTER(C.c_float), vp, vp, vp]),
     'lp_preprocess_batch': (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), i32, i32, C.POINTER(C.c_float),
                                   C.POINTER(C.c_float), vp, vp, vp]),
+    'lp_warp_invert': (i32, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    'lp_preprocess_batch_v': (i32, [vp, sz, vp, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp,
+                                    vp]),
     'lp_stream_abort_capture': (i32, [vp]),
     'lp_final_preds': (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                              i32, i32, vp]),
+    'lp_final_preds_coef': (i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), i32, i32, C.POINTER(C.c_double)]),
+    'lp_final_preds_v': (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
 }
 EXPORTS = sorted(_SIGS)
 

@@ -285,6 +285,22 @@ int lp_parse_dm(const float* d_det, const float* d_mid, int N, int J, int h1, in
     return LP_OK;
 }
 
+int lp_warp_invert(const double* h_trans, double* h_minv) {
+    if (!h_trans || !h_minv) return fail(LP_ERR_INVALID_ARG, "null argument");
+    // cv::warpAffine without WARP_INVERSE_MAP inverts the 2x3 matrix first (fp64)
+    double M[6] = {h_trans[0], h_trans[1], h_trans[2], h_trans[3], h_trans[4], h_trans[5]};
+    double D = M[0] * M[4] - M[1] * M[3];
+    D = D != 0.0 ? 1.0 / D : 0.0;
+    const double A11 = M[4] * D, A22 = M[0] * D;
+    M[0] = A11; M[1] *= -D;
+    M[3] *= -D; M[4] = A22;
+    const double b1 = -M[0] * M[2] - M[1] * M[5];
+    const double b2 = -M[3] * M[2] - M[4] * M[5];
+    M[2] = b1; M[5] = b2;
+    for (int i = 0; i < 6; ++i) h_minv[i] = M[i];
+    return LP_OK;
+}
+
 int lp_preprocess(const uint8_t* d_image, int H, int W, const double* h_trans, int Hd, int Wd,
                   const float* h_mean, const float* h_std, uint8_t* d_resized_u8, float* d_tensor,
                   void* stream) {
@@ -301,19 +317,27 @@ int lp_preprocess_batch(const uint8_t* d_image, int N, int H, int W, const doubl
         return fail(LP_ERR_INVALID_ARG, "image sizes must be 1..32767");
     for (int c = 0; c < 3; ++c)
         if (!(h_std[c] > 0.f)) return fail(LP_ERR_INVALID_ARG, "std must be positive");
-    // cv::warpAffine without WARP_INVERSE_MAP inverts the 2x3 matrix first (fp64)
-    double M[6] = {h_trans[0], h_trans[1], h_trans[2], h_trans[3], h_trans[4], h_trans[5]};
-    double D = M[0] * M[4] - M[1] * M[3];
-    D = D != 0.0 ? 1.0 / D : 0.0;
-    const double A11 = M[4] * D, A22 = M[0] * D;
-    M[0] = A11; M[1] *= -D;
-    M[3] *= -D; M[4] = A22;
-    const double b1 = -M[0] * M[2] - M[1] * M[5];
-    const double b2 = -M[3] * M[2] - M[4] * M[5];
-    M[2] = b1; M[5] = b2;
+    double M[6];
+    lp_warp_invert(h_trans, M);
     lp::launch_warp_affine_norm(d_image, H, W, Hd, Wd, M, h_mean, h_std, d_resized_u8, d_tensor,
                                 (hipStream_t)stream, N);
     if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "preprocess launch failed");
+    return LP_OK;
+}
+
+int lp_preprocess_batch_v(const uint8_t* d_src, size_t src_bytes, const lp_warp_desc* d_desc, int N, int Hd, int Wd,
+                          const float* h_mean, const float* h_std, uint8_t* d_resized_u8, float* d_tensor,
+                          void* stream) {
+    if (!d_src || !d_desc || !h_mean || !h_std) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (N < 1 || N > 65535) return fail(LP_ERR_INVALID_ARG, "N must be 1..65535");
+    if (!d_resized_u8 && !d_tensor) return fail(LP_ERR_INVALID_ARG, "no output requested");
+    if (src_bytes < 1 || src_bytes > (size_t)INT64_MAX) return fail(LP_ERR_INVALID_ARG, "src_bytes must be 1..INT64_MAX");
+    if (Hd < 1 || Wd < 1 || Hd > 32767 || Wd > 32767) return fail(LP_ERR_INVALID_ARG, "image sizes must be 1..32767");
+    for (int c = 0; c < 3; ++c)
+        if (!(h_std[c] > 0.f)) return fail(LP_ERR_INVALID_ARG, "std must be positive");
+    lp::launch_warp_affine_norm_v(d_src, (long long)src_bytes, reinterpret_cast<const lp::WarpDesc*>(d_desc), N, Hd, Wd,
+                                  h_mean, h_std, d_resized_u8, d_tensor, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "preprocess_v launch failed");
     return LP_OK;
 }
 
@@ -334,14 +358,45 @@ int lp_stream_abort_capture(void* stream) {
     return ended;
 }
 
+}  // extern "C"
+
+namespace {
+// get_affine_transform(center, scale, rot=0, output_size, inv=1): uniform scale src_w/dst_w -> (sx, tx, sy, ty)
+void final_preds_coef(const double* h_center, const double* h_scale, int Wp, int Hp, double* c) {
+    const double s = h_scale[0] * 200.0 / (double)Wp;
+    const double tx = h_center[0] - s * Wp * 0.5, ty = h_center[1] - s * Hp * 0.5;
+    c[0] = s; c[1] = tx;
+    c[2] = s; c[3] = ty;
+}
+}  // namespace
+
+extern "C" {
+
+int lp_final_preds_coef(const double* h_center, const double* h_scale, int Wp, int Hp, double* h_coef4) {
+    if (!h_center || !h_scale || !h_coef4) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (Wp < 1 || Hp < 1 || Wp > 32767 || Hp > 32767) return fail(LP_ERR_INVALID_ARG, "heatmap sizes must be 1..32767");
+    final_preds_coef(h_center, h_scale, Wp, Hp, h_coef4);
+    return LP_OK;
+}
+
 int lp_final_preds(float* d_ans, const int32_t* d_count, int N, int pcap, int J, int T,
                    const double* h_center, const double* h_scale, int Wp, int Hp, void* stream) {
     if (!d_ans || !d_count || !h_center || !h_scale) return fail(LP_ERR_INVALID_ARG, "null argument");
-    // get_affine_transform(center, scale, rot=0, output_size, inv=1): uniform scale src_w/dst_w
-    const double s = h_scale[0] * 200.0 / (double)Wp;
-    const double tx = h_center[0] - s * Wp * 0.5, ty = h_center[1] - s * Hp * 0.5;
-    lp::launch_final_preds(d_ans, d_count, N, pcap, J, T, s, tx, s, ty, (hipStream_t)stream);
+    double c[4];
+    final_preds_coef(h_center, h_scale, Wp, Hp, c);
+    lp::launch_final_preds(d_ans, d_count, N, pcap, J, T, c[0], c[1], c[2], c[3], (hipStream_t)stream);
     if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "final_preds launch failed");
+    return LP_OK;
+}
+
+int lp_final_preds_v(float* d_ans, const int32_t* d_count, int N, int pcap, int J, int T, const double* d_coef,
+                     void* stream) {
+    if (!d_ans || !d_count || !d_coef) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (N < 1 || N > 65535) return fail(LP_ERR_INVALID_ARG, "N must be 1..65535");
+    if (pcap < 1 || J < 1 || J > 32 || T < 1 || T > 2)
+        return fail(LP_ERR_INVALID_ARG, "need pcap >= 1, J 1..32, T 1..2");
+    lp::launch_final_preds_v(d_ans, d_count, N, pcap, J, T, d_coef, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "final_preds_v launch failed");
     return LP_OK;
 }
 

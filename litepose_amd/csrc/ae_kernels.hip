@@ -1993,16 +1993,31 @@ void launch_refine(const float* det, const float* tag, int N, int J, int H, int 
                        count, prev, miss);
 }
 
+// get_final_preds on one joint row: x, y of `jt` through sx * x + tx, sy * y + ty in fp64 (shared by the one-transform
+// and the per-image kernel, so both round alike by construction)
+__device__ __forceinline__ void final_preds_row(float* __restrict__ jt, double sx, double tx, double sy, double ty) {
+    const double x = (double)jt[0], y = (double)jt[1];
+    jt[0] = (float)(sx * x + tx);
+    jt[1] = (float)(sy * y + ty);
+}
+
 __global__ void final_preds_kernel(float* __restrict__ ans, const int* __restrict__ count, int pcap,
                                    int J, int D, double sx, double tx, double sy, double ty) {
     const int n = blockIdx.x;
     const int P = min(max(count[n], 0), pcap);
-    for (int e = threadIdx.x; e < P * J; e += blockDim.x) {
-        float* jt = ans + ((long)n * pcap * J + e) * D;
-        const double x = (double)jt[0], y = (double)jt[1];
-        jt[0] = (float)(sx * x + tx);
-        jt[1] = (float)(sy * y + ty);
-    }
+    for (int e = threadIdx.x; e < P * J; e += blockDim.x)
+        final_preds_row(ans + ((long)n * pcap * J + e) * D, sx, tx, sy, ty);
+}
+
+// per image n: (sx, tx, sy, ty) = coef[4n .. 4n+3] from a device table (lp_final_preds_coef of the image's own centre and
+// scale), read wave-uniformly
+__global__ void final_preds_v_kernel(float* __restrict__ ans, const int* __restrict__ count, int pcap, int J, int D,
+                                     const double* __restrict__ coef) {
+    const int n = blockIdx.x;
+    const int P = min(max(count[n], 0), pcap);
+    const double sx = coef[4 * n], tx = coef[4 * n + 1], sy = coef[4 * n + 2], ty = coef[4 * n + 3];
+    for (int e = threadIdx.x; e < P * J; e += blockDim.x)
+        final_preds_row(ans + ((long)n * pcap * J + e) * D, sx, tx, sy, ty);
 }
 
 // ====================================================================================
@@ -2021,17 +2036,12 @@ __device__ __forceinline__ int sat_int_rint(double v) {
     return r >= 2147483647.0 ? 2147483647 : (r <= -2147483648.0 ? (int)-2147483648LL : (int)r);
 }
 
-__global__ __launch_bounds__(256) void warp_affine_norm_kernel(
-    const unsigned char* __restrict__ src, int H, int W, int Hd, int Wd, double m0, double m1, double m2,
-    double m3, double m4, double m5, float mean0, float mean1, float mean2, float std0, float std1,
-    float std2, unsigned char* __restrict__ dst_u8, float* __restrict__ dst_f32) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    if (x >= Wd) return;
-    // blockIdx.z = image of the batch (same size and transform for all of them)
-    src += (long)blockIdx.z * H * W * 3;
-    if (dst_u8) dst_u8 += (long)blockIdx.z * Hd * Wd * 3;
-    if (dst_f32) dst_f32 += (long)blockIdx.z * 3 * Hd * Wd;
+// One destination pixel (x, y) of one image: the fixed-point warp of `src` [H,W,3] through the inverted matrix m0..m5, then
+// ToTensor + Normalize.  Shared by the one-transform and the per-image kernel, so both compute the same bits by construction.
+__device__ __forceinline__ void warp_norm_pixel(const unsigned char* __restrict__ src, int H, int W, int Hd, int Wd,
+                                                int x, int y, double m0, double m1, double m2, double m3, double m4,
+                                                double m5, const float (&mean)[3], const float (&sd)[3],
+                                                unsigned char* __restrict__ dst_u8, float* __restrict__ dst_f32) {
     const int adelta = sat_int_rint(m0 * (double)x * 1024.0), bdelta = sat_int_rint(m3 * (double)x * 1024.0);
     const int X0 = sat_int_rint((m1 * (double)y + m2) * 1024.0) + 16;
     const int Y0 = sat_int_rint((m4 * (double)y + m5) * 1024.0) + 16;
@@ -2043,7 +2053,6 @@ __global__ __launch_bounds__(256) void warp_affine_norm_kernel(
     const int w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
     const bool x0 = sx >= 0 && sx < W, x1 = sx + 1 >= 0 && sx + 1 < W;
     const bool y0 = sy >= 0 && sy < H, y1 = sy + 1 >= 0 && sy + 1 < H;
-    const float mean[3] = {mean0, mean1, mean2}, sd[3] = {std0, std1, std2};
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const int p00 = (y0 && x0) ? src[((long)sy * W + sx) * 3 + c] : 0;
@@ -2055,6 +2064,54 @@ __global__ __launch_bounds__(256) void warp_affine_norm_kernel(
         if (dst_u8) dst_u8[((long)y * Wd + x) * 3 + c] = (unsigned char)v;
         if (dst_f32) dst_f32[((long)c * Hd + y) * Wd + x] = ((float)v / 255.0f - mean[c]) / sd[c];
     }
+}
+
+__global__ __launch_bounds__(256) void warp_affine_norm_kernel(
+    const unsigned char* __restrict__ src, int H, int W, int Hd, int Wd, double m0, double m1, double m2,
+    double m3, double m4, double m5, float mean0, float mean1, float mean2, float std0, float std1,
+    float std2, unsigned char* __restrict__ dst_u8, float* __restrict__ dst_f32) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= Wd) return;
+    // blockIdx.z = image of the batch (same size and transform for all of them)
+    src += (long)blockIdx.z * H * W * 3;
+    if (dst_u8) dst_u8 += (long)blockIdx.z * Hd * Wd * 3;
+    if (dst_f32) dst_f32 += (long)blockIdx.z * 3 * Hd * Wd;
+    const float mean[3] = {mean0, mean1, mean2}, sd[3] = {std0, std1, std2};
+    warp_norm_pixel(src, H, W, Hd, Wd, x, y, m0, m1, m2, m3, m4, m5, mean, sd, dst_u8, dst_f32);
+}
+
+// Per-image sources and transforms (lp_preprocess_batch_v): blockIdx.z = image n, whose source lies at byte
+// desc[n].src_offset of the packed buffer `src` (src_bytes long) with its own H, W and inverted matrix.  The table is
+// read at run time from device memory (wave-uniform: scalar loads), so a loader can refill it in place under a
+// captured graph.  A descriptor whose image does not lie inside the buffer, or with H or W outside 1..32767, writes
+// zeros and reads nothing.
+__global__ __launch_bounds__(256) void warp_affine_norm_v_kernel(
+    const unsigned char* __restrict__ src, long long src_bytes, const WarpDesc* __restrict__ desc, int Hd, int Wd,
+    float mean0, float mean1, float mean2, float std0, float std1, float std2, unsigned char* __restrict__ dst_u8,
+    float* __restrict__ dst_f32) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= Wd) return;
+    const WarpDesc& d = desc[blockIdx.z];
+    const long long off = d.src_offset;
+    const int H = d.H, W = d.W;
+    if (dst_u8) dst_u8 += (long)blockIdx.z * Hd * Wd * 3;
+    if (dst_f32) dst_f32 += (long)blockIdx.z * 3 * Hd * Wd;
+    // H, W <= 32767: H * W * 3 < 2^32 cannot overflow the 64-bit products below
+    const bool ok = H >= 1 && W >= 1 && H <= 32767 && W <= 32767 && off >= 0 && off <= src_bytes &&
+                    (long long)H * W * 3 <= src_bytes - off;
+    if (!ok) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (dst_u8) dst_u8[((long)y * Wd + x) * 3 + c] = 0;
+            if (dst_f32) dst_f32[((long)c * Hd + y) * Wd + x] = 0.f;
+        }
+        return;
+    }
+    const float mean[3] = {mean0, mean1, mean2}, sd[3] = {std0, std1, std2};
+    warp_norm_pixel(src + off, H, W, Hd, Wd, x, y, d.minv[0], d.minv[1], d.minv[2], d.minv[3], d.minv[4], d.minv[5],
+                    mean, sd, dst_u8, dst_f32);
 }
 
 void launch_warp_affine_norm(const unsigned char* src, int H, int W, int Hd, int Wd, const double* minv,
@@ -2069,6 +2126,18 @@ void launch_final_preds(float* ans, const int* count, int N, int pcap, int J, in
                         double tx, double sy, double ty, hipStream_t s) {
     hipLaunchKernelGGL(final_preds_kernel, dim3(N), dim3(256), 0, s, ans, count, pcap, J, 3 + T, sx,
                        tx, sy, ty);
+}
+
+void launch_warp_affine_norm_v(const unsigned char* src, long long src_bytes, const WarpDesc* desc, int N, int Hd,
+                               int Wd, const float* mean, const float* sd, unsigned char* dst_u8, float* dst_f32,
+                               hipStream_t s) {
+    hipLaunchKernelGGL(warp_affine_norm_v_kernel, dim3((Wd + 255) / 256, Hd, N), dim3(256), 0, s, src, src_bytes, desc,
+                       Hd, Wd, mean[0], mean[1], mean[2], sd[0], sd[1], sd[2], dst_u8, dst_f32);
+}
+
+void launch_final_preds_v(float* ans, const int* count, int N, int pcap, int J, int T, const double* coef,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(final_preds_v_kernel, dim3(N), dim3(256), 0, s, ans, count, pcap, J, 3 + T, coef);
 }
 
 }  // namespace lp

@@ -251,5 +251,17 @@ void launch_warp_affine_norm(const unsigned char* src, int H, int W, int Hd, int
                              hipStream_t s, int nimg = 1);      // nimg images [nimg,H,W,3] -> [nimg,...], one transform
 void launch_final_preds(float* ans, const int* count, int N, int pcap, int J, int T,
                         double sx, double tx, double sy, double ty, hipStream_t s);
+// per-image source / transform of launch_warp_affine_norm_v: the layout of lp_warp_desc (include/litepose_amd.h)
+struct WarpDesc {
+    long long src_offset;   // byte offset of the [H,W,3] uint8 source in the packed buffer
+    int H, W;
+    double minv[6];         // inverted (dst -> src) 2x3 matrix
+};
+static_assert(sizeof(WarpDesc) == 64, "WarpDesc must match lp_warp_desc (64 bytes)");
+void launch_warp_affine_norm_v(const unsigned char* src, long long src_bytes, const WarpDesc* desc, int N, int Hd,
+                               int Wd, const float* mean, const float* sd, unsigned char* dst_u8, float* dst_f32,
+                               hipStream_t s);      // N images of their own sizes / transforms -> [N,...] at (Hd, Wd)
+void launch_final_preds_v(float* ans, const int* count, int N, int pcap, int J, int T, const double* coef,
+                          hipStream_t s);           // coef [N,4] = (sx, tx, sy, ty) per image, device
 
 }  // namespace lp

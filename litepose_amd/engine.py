@@ -323,9 +323,9 @@ class PoseEngine(object):
             _inference.tta_project(mid, N, J, h1, w1, (W, H), T, det=b['det'], det_only=True)
         return (path, N, H, W, mid, J, h1, w1, T)
 
-    def _stage_ae(self, ctx, center, scale):
+    def _stage_ae(self, ctx, center, scale, coef=None):
         """Second half: the AE post-process (NMS/top-k, grouping, adjust, refine, back-projection) -- latency-bound
-        launches that fill a fraction of the chip."""
+        launches that fill a fraction of the chip.  ``coef``: per-image back-projection table (see submit)."""
         path, N, H, W = ctx[:4]
         if isinstance(ctx[4], (list, tuple)):                 # early split: the merge runs here
             ctx = self._stage_merge(path, N, H, W, ctx[4], ctx[5], ctx[6])
@@ -336,22 +336,39 @@ class PoseEngine(object):
         else:
             b = self._buffers(N, H, W)
             ans, count, scores = self.parse_dm(b['det'], ctx[4], N, *ctx[5:])
+        if coef is not None:
+            _tf.final_preds_device_v(ans, count, coef)
+            return ans, count, scores
         if center is None:
             # square network input of side INPUT_SIZE: get_multi_scale_size gives the identity
             (_, _), center, scale = _tf.get_multi_scale_size((H, W), min(H, W), 1.0, 1.0)
         _tf.final_preds_device(ans, count, center, scale, (W, H))
         return ans, count, scores
 
-    def _infer_one(self, images, offsets, center, scale):
-        return self._stage_ae(self._stage_net(images, offsets), center, scale)
+    def _infer_one(self, images, offsets, center, scale, coef=None):
+        return self._stage_ae(self._stage_net(images, offsets), center, scale, coef)
 
-    def infer_batch(self, images, offsets=None, center=None, scale=None):
+    @staticmethod
+    def _check_coef(preds_coef, N, center, scale):
+        if preds_coef is None:
+            return
+        if center is not None or scale is not None:
+            raise ValueError('preds_coef replaces center / scale: pass one or the other')
+        if (not torch.is_tensor(preds_coef) or not preds_coef.is_cuda or preds_coef.dtype != torch.float64
+                or tuple(preds_coef.shape) != (N, 4) or not preds_coef.is_contiguous()):
+            raise ValueError('preds_coef must be a contiguous float64 [N,4] device tensor')
+
+    def infer_batch(self, images, offsets=None, center=None, scale=None, preds_coef=None):
         """images [N,3,H,W] float32 (normalised) on the GPU ->
-        (kpts [N,pcap,J,3+T], count [N] int32, scores [N,pcap]); no host sync."""
+        (kpts [N,pcap,J,3+T], count [N] int32, scores [N,pcap]); no host sync.
+        ``preds_coef``: optional [N,4] float64 device table, one back-projection (sx, tx, sy, ty) per image
+        (``utils.transforms.final_preds_coef`` of the image's own centre / scale), instead of one ``center`` /
+        ``scale`` for the whole batch."""
         N = images.shape[0]
+        self._check_coef(preds_coef, N, center, scale)
         if not self.pipeline_halves or N < 2 or N % 2:
             nv.check(self._lib.lp_net_set_streams(self.model._h, 2))
-            return self._infer_one(images, offsets, center, scale)
+            return self._infer_one(images, offsets, center, scale, preds_coef)
         if self._side is None:
             self._side = [torch.cuda.Stream(device=self.device) for _ in range(2)]
             self._half = [PoseEngine.__new__(PoseEngine) for _ in range(2)]
@@ -387,7 +404,8 @@ class PoseEngine(object):
                     t.record_stream(self._side[h])
             with torch.cuda.stream(self._side[h]):
                 self._side[h].wait_event(fork)
-                a, c, s = self._half[h]._infer_one(images[sl], offs, center, scale)
+                a, c, s = self._half[h]._infer_one(images[sl], offs, center, scale,
+                                                   None if preds_coef is None else preds_coef[sl])
                 full[0][sl].copy_(a, non_blocking=True)
                 full[1][sl].copy_(c, non_blocking=True)
                 full[2][sl].copy_(s, non_blocking=True)
@@ -398,9 +416,11 @@ class PoseEngine(object):
         return full
 
 
-    def submit(self, images, offsets=None, center=None, scale=None):
+    def submit(self, images, offsets=None, center=None, scale=None, preds_coef=None):
         """Software-pipelined serving.  Returns a ``PendingBatch``; inputs must stay alive/unchanged until
-        ``result()`` has been waited on.
+        ``result()`` has been waited on.  ``preds_coef``: per-image back-projection table as in ``infer_batch``
+        (part of the graph key by pointer and shape, like ``images``: a graph replays against a table refilled in
+        place).
 
         Schedule (option sched='split', default): a batch is two stages, NET (network on image + mirror, stage merge,
         projection: chip-filling launches) and AE (NMS/top-k, grouping, adjust, refine: latency-bound launches on
@@ -430,6 +450,7 @@ class PoseEngine(object):
         nst = self.options['streams']
         nv.check(self._lib.lp_net_set_streams(self.model._h, int(nst) if nst else (1 if self._split else 2)))
         N, _, H, W = images.shape
+        self._check_coef(preds_coef, N, center, scale)
         cfg = self.cfg
         early = self._split and self.options['split'] == 'early'
         key = (images.data_ptr(), tuple(images.shape),
@@ -438,8 +459,10 @@ class PoseEngine(object):
                None if scale is None else tuple(float(v) for v in scale),
                lane['eng']._buffers(N, H, W)['serial'], lane['eng']._ae_path(H, W), early,
                bool(cfg.TEST.ADJUST), bool(cfg.TEST.REFINE), bool(cfg.TEST.FLIP_TEST))
+        if preds_coef is not None:
+            key = key + ((preds_coef.data_ptr(), tuple(preds_coef.shape)),)
         if self._split:
-            tensors, done = self._submit_split(lane, key, fork, images, offsets, center, scale, early)
+            tensors, done = self._submit_split(lane, key, fork, images, offsets, center, scale, early, preds_coef)
         else:
             with torch.cuda.stream(lane['stream']):
                 lane['stream'].wait_event(fork)
@@ -452,9 +475,9 @@ class PoseEngine(object):
                     tensors = ent['out']
                     self._stats['graph_replays'] += 1
                 elif self._use_graphs and key in lane['seen'] and self._may_capture():
-                    tensors = self._capture_lane(lane, key, fork, images, offsets, center, scale)
+                    tensors = self._capture_lane(lane, key, fork, images, offsets, center, scale, preds_coef)
                 else:
-                    tensors = lane['eng']._infer_one(images, offsets, center, scale)
+                    tensors = lane['eng']._infer_one(images, offsets, center, scale, preds_coef)
                     self._stats['eager_stages'] += 1
                     _remember(lane['seen'], key)
                 done = torch.cuda.Event()
@@ -535,6 +558,24 @@ class PoseEngine(object):
             ln['graphs'].clear()
             ln['seen'].clear()
 
+    def evaluate(self, images, image_ids=None, batch_size=64, num_joints=None, stats=None):
+        """A whole validation set of HxWx3 uint8 images of any sizes -> result dicts in input order
+        (``litepose_amd.evaluate.evaluate``)."""
+        from . import evaluate as _ev
+        return _ev.evaluate(self, images, image_ids, batch_size, num_joints, stats)
+
+    def release_shape(self, N, H, W):
+        """Drop the buffers and captured graphs of input shape [N,3,H,W] in every buffer set (``evaluate``: a bucket that
+        is done -- otherwise its sets keep up to 2 x _MAX_SHAPES shapes resident, buffers plus graphs).  Synchronises
+        first: nothing in flight may still use them."""
+        torch.cuda.synchronize()
+        for eng in [self] + [ln['eng'] for ln in (self._lanes or [])]:
+            eng._bufs.pop((N, H, W), None)
+        for ln in (self._lanes or []):
+            for d in (ln['graphs'], ln['seen']):
+                for k in [k for k in d if k[1] == (N, 3, H, W)]:
+                    d.pop(k)
+
     def graph_stats(self):
         """{'use_graphs', 'captured_sets', 'graph_replays', 'graph_captures', 'eager_stages', 'capture_failures',
         'capture_mode'}: whether the serving loop really runs as graph replays (a failed capture drops the engine
@@ -554,7 +595,7 @@ class PoseEngine(object):
         self._ensure_lanes()
         return max(1, len(self._lanes) - 2) if self._split else 1
 
-    def _submit_split(self, lane, key, fork, images, offsets, center, scale, early):
+    def _submit_split(self, lane, key, fork, images, offsets, center, scale, early, coef=None):
         eng, ns, aes = lane['eng'], lane['stream'], lane['ae_stream']
         ent = lane['graphs'].get(key) if self._use_graphs else None
         replay = ent is not None
@@ -591,7 +632,8 @@ class PoseEngine(object):
                 tensors = ent['out']
                 self._stats['graph_replays'] += 1
             else:
-                if capture and self._capture_stage(ent, 1, aes, lambda: eng._stage_ae(ctx, center, scale)) is not None:
+                if capture and self._capture_stage(ent, 1, aes,
+                                                   lambda: eng._stage_ae(ctx, center, scale, coef)) is not None:
                     tensors = ent['out']
                     _remember(lane['graphs'], key, ent)
                     self._stats['graph_captures'] += 1
@@ -599,7 +641,7 @@ class PoseEngine(object):
                     if lane['ae_stream'] is not aes:     # the capture failed and moved the lane to a fresh stream
                         aes = _rejoin(lane['ae_stream'], net_done, lane['consumed'])
                     with torch.cuda.stream(aes):
-                        tensors = eng._stage_ae(ctx, center, scale)
+                        tensors = eng._stage_ae(ctx, center, scale, coef)
                     _remember(lane['seen'], key)
                     self._stats['eager_stages'] += 1
             done = torch.cuda.Event()
@@ -625,13 +667,13 @@ class PoseEngine(object):
             self._capture_failed(e, stream)
             return None
 
-    def _capture_lane(self, lane, key, fork, images, offsets, center, scale):
+    def _capture_lane(self, lane, key, fork, images, offsets, center, scale, coef=None):
         """Capture one batch of this lane into a hipGraph (buffers exist already: the lane ran eagerly
         once) and launch it.  Any failure falls back to eager launches for good."""
         try:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=lane['stream'], capture_error_mode=self.options['capture_mode']):
-                tensors = lane['eng']._infer_one(images, offsets, center, scale)
+                tensors = lane['eng']._infer_one(images, offsets, center, scale, coef)
             _remember(lane['graphs'], key, {'g': [g], 'out': tensors, 'ctx': None,
                                             'bufs': lane['eng']._buffers(images.shape[0], images.shape[2],
                                                                          images.shape[3])})
@@ -641,7 +683,7 @@ class PoseEngine(object):
         except Exception as e:                           # capture is an optimisation, never a requirement
             self._capture_failed(e, lane['stream'])
             with torch.cuda.stream(_rejoin(lane['stream'], fork, lane['consumed'])):
-                return lane['eng']._infer_one(images, offsets, center, scale)
+                return lane['eng']._infer_one(images, offsets, center, scale, coef)
 
     def _capture_failed(self, exc, stream):
         """A capture raised (typically: another host thread made a HIP call while it was open).  Leave capture mode

@@ -38,6 +38,27 @@ def final_preds_device(ans, count, center, scale, heatmap_size):
     return ans
 
 
+def final_preds_coef(center, scale, heatmap_size):
+    """(sx, tx, sy, ty) float64 of ``lp_final_preds_coef``: the back-projection of one image's records (its row of the
+    ``preds_coef`` table of ``PoseEngine.submit`` / ``infer_batch``)."""
+    c = (C.c_double * 2)(float(center[0]), float(center[1]))
+    s = (C.c_double * 2)(float(scale[0]), float(scale[1]))
+    out = (C.c_double * 4)()
+    nv.check(nv.lib().lp_final_preds_coef(c, s, int(heatmap_size[0]), int(heatmap_size[1]), out), 'lp_final_preds_coef')
+    return np.array(out[:], np.float64)
+
+
+def final_preds_device_v(ans, count, coef):
+    """In place on device records ans [N,pcap,J,3+T] / count [N] with a transform per image: ``coef`` [N,4] float64
+    device table of ``final_preds_coef`` rows (``lp_final_preds_v``)."""
+    N, pcap, J, D = ans.shape
+    if coef.dtype != torch.float64 or tuple(coef.shape) != (N, 4):
+        raise ValueError('coef must be a float64 [N,4] device tensor')
+    nv.check(nv.lib().lp_final_preds_v(nv.dptr(ans), nv.dptr(count), N, pcap, J, D - 3, nv.dptr(coef),
+                                       nv.stream_ptr()), 'lp_final_preds_v')
+    return ans
+
+
 def get_final_preds(grouped_joints, center, scale, heatmap_size):
     """transforms.py:195-202: list of per-person [J, 3+T] arrays in image coordinates."""
     persons = grouped_joints[0]
@@ -145,6 +166,44 @@ def normalize_batch_device(images_u8, out=None, trans=None, size=None, mean=IMAG
     std_c = (C.c_float * 3)(*[float(v) for v in std])
     nv.check(nv.lib().lp_preprocess_batch(nv.dptr(images_u8), N, H, W, m, Hd, Wd, mean_c, std_c, None, nv.dptr(out),
                                           nv.stream_ptr()), 'lp_preprocess_batch')
+    return out
+
+
+# one row of the descriptor table of lp_preprocess_batch_v (lp_warp_desc, 64 bytes)
+WARP_DESC_DTYPE = np.dtype([('src_offset', '<i8'), ('H', '<i4'), ('W', '<i4'), ('minv', '<f8', (6,))])
+assert WARP_DESC_DTYPE.itemsize == 64
+
+
+def warp_invert(trans):
+    """The dst->src matrix (6 float64) cv2.warpAffine applies for the src->dst ``trans`` (``lp_warp_invert``)."""
+    m = (C.c_double * 6)(*[float(v) for v in np.asarray(trans, np.float64).reshape(-1)])
+    out = (C.c_double * 6)()
+    nv.check(nv.lib().lp_warp_invert(m, out), 'lp_warp_invert')
+    return np.array(out[:], np.float64)
+
+
+def preprocess_batch_v_device(src, desc, size, out=None, out_u8=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """Images of different sizes and transforms -> one bucket's network input, ONE launch (``lp_preprocess_batch_v``).
+    ``src``: uint8 device tensor holding the [H,W,3] sources back to back; ``desc``: device tensor whose bytes are N
+    rows of WARP_DESC_DTYPE (uint8 [N,64] or int64 [N,8]); ``size`` = (Wd, Hd).  Writes ``out`` float32 [N,3,Hd,Wd]
+    (allocated when None) and, if given, ``out_u8`` uint8 [N,Hd,Wd,3]; returns ``out``."""
+    if src.dtype != torch.uint8 or not src.is_cuda:
+        raise ValueError('src must be a uint8 device tensor')
+    nbytes = desc.numel() * desc.element_size()
+    if nbytes % WARP_DESC_DTYPE.itemsize or nbytes == 0:
+        raise ValueError('desc must hold whole %d-byte descriptors' % WARP_DESC_DTYPE.itemsize)
+    N = nbytes // WARP_DESC_DTYPE.itemsize
+    Wd, Hd = int(size[0]), int(size[1])
+    if out is None:
+        out = torch.empty((N, 3, Hd, Wd), dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != (N, 3, Hd, Wd) or out.dtype != torch.float32:
+        raise ValueError('out must be float32 [N,3,Hd,Wd]')
+    if out_u8 is not None and (tuple(out_u8.shape) != (N, Hd, Wd, 3) or out_u8.dtype != torch.uint8):
+        raise ValueError('out_u8 must be uint8 [N,Hd,Wd,3]')
+    mean_c = (C.c_float * 3)(*[float(v) for v in mean])
+    std_c = (C.c_float * 3)(*[float(v) for v in std])
+    nv.check(nv.lib().lp_preprocess_batch_v(nv.dptr(src), src.numel(), nv.dptr(desc), N, Hd, Wd, mean_c, std_c,
+                                            nv.dptr(out_u8), nv.dptr(out), nv.stream_ptr()), 'lp_preprocess_batch_v')
     return out
 
 

@@ -258,6 +258,28 @@ int lp_tta_project(const float* d_mid, int N, int J, int h1, int w1, int Hp, int
  * the caller as in valid.py:224.  Pointers 16-byte aligned.                                    */
 int lp_maps_accumulate(float* d_acc, const float* d_src, int64_t count, void* stream);
 
+/* The whole multi-scale aggregation of valid.py:207-224 (inference.py:176-208) in ONE launch, from the stage merges of
+ * every scale (lp_tta_stage) instead of their full-resolution maps.  One scale, 16 bytes:                        */
+#define LP_MAX_SCALES 8
+typedef struct lp_scale_mid {
+    const float* mid;       /* DEVICE [N][4][J][h1][w1] of lp_tta_stage (lp_tta_workspace_bytes(N,J,h1,w1))       */
+    int32_t h1, w1;         /* its stage-1 size                                                                  */
+} lp_scale_mid;
+/* scales [S] (host, 1 <= S <= LP_MAX_SCALES) in DESCENDING scale-factor order; the table is copied into the launch's
+ * arguments, so a captured launch needs no device table.  first_unit: index of scale factor 1 (the scale whose tags
+ * are kept; 0 for a single scale).  T = 2 with flip (maps 1 and 3 of every mid read), 1 without.
+ *   project2image = 1: (Hf, Wf) is the base size; every scale is projected to it with the flip average of
+ *                      lp_tta_project, the scales are summed in order and multiplied by 1.0f / S (what a
+ *                      torch device tensor divided by a host scalar computes); tags: the
+ *                      projection of scale first_unit's tag maps.
+ *   project2image = 0: (Hf, Wf) must be scales[0]'s stage-1 size.  A later scale of another size: its flip-averaged
+ *                      map at its own size, then resized as resize_maps does (inference.py:201-206); the tags of
+ *                      first_unit likewise when their size differs (:180-189).
+ * d_det [N,J,Hf,Wf], d_tag [N,J,Hf,Wf,T] (8-byte aligned with T = 2): bit-identical to the batch-1 chain --
+ * lp_tta_project per scale, aggregate_results (lp_maps_accumulate, resize_maps), then / len(SCALE_FACTOR).     */
+int lp_tta_merge_scales(const lp_scale_mid* scales, int S, int first_unit, int N, int J, int T, int project2image,
+                        int Hf, int Wf, float* d_det, float* d_tag, void* stream);
+
 /* ------------------------------------------------------------ AE parser ----------
  * Replaces core.group.HeatmapParser (lib/core/group.py:123-291).                      */
 typedef struct lp_parse_params {          /* group.py:100-120 Params + mobile.yaml TEST.*  */

@@ -46,6 +46,11 @@ class LpWarpDesc(C.Structure):
     _fields_ = [('src_offset', C.c_int64), ('H', C.c_int32), ('W', C.c_int32), ('minv', C.c_double * 6)]
 
 
+class LpScaleMid(C.Structure):
+    """lp_scale_mid: one scale (16 bytes) of lp_tta_merge_scales."""
+    _fields_ = [('mid', C.c_void_p), ('h1', C.c_int32), ('w1', C.c_int32)]
+
+
 class LitePoseNativeError(RuntimeError):
     pass
 
@@ -84,6 +89,7 @@ _SIGS = {
     'lp_tta_merge_ex': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp,
                               sz, vp]),
     'lp_maps_accumulate': (i32, [vp, vp, i64, vp]),
+    'lp_tta_merge_scales': (i32, [C.POINTER(LpScaleMid), i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     'lp_tta_stage': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
     'lp_tta_stage_add': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz,
                                vp]),

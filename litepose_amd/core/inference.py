@@ -151,6 +151,66 @@ def tta_project(mid, N, J, h1, w1, size_projected, T, det=None, tag=None, det_on
     return det, (None if det_only else tag)
 
 
+MAX_SCALES = 8            # LP_MAX_SCALES of lp_tta_merge_scales
+
+
+def scale_order(cfg):
+    """TEST.SCALE_FACTOR in the order valid.py visits it (sorted, descending) and the index of the scale whose tags
+    are kept (factor 1; 0 for a single scale).  Raises ValueError for lists the reference loop cannot run."""
+    sf = [float(s) for s in cfg.TEST.SCALE_FACTOR]
+    if not sf:
+        raise ValueError('TEST.SCALE_FACTOR is empty')
+    if len(sf) > MAX_SCALES:
+        raise ValueError('at most %d entries in TEST.SCALE_FACTOR' % MAX_SCALES)
+    order = sorted(sf, reverse=True)
+    if len(order) == 1:
+        return order, 0
+    if len(set(order)) != len(order):
+        raise ValueError('TEST.SCALE_FACTOR %s has duplicates: aggregate_results would append the scale-1 tags '
+                         'more than once' % (list(cfg.TEST.SCALE_FACTOR),))
+    if 1.0 not in order:
+        raise ValueError('TEST.SCALE_FACTOR %s has no entry 1: the tags are taken from scale 1 only, and the '
+                         "reference's torch.cat of an empty tag list fails" % (list(cfg.TEST.SCALE_FACTOR),))
+    return order, order.index(1.0)
+
+
+def tta_merge_scales(cfg, mids, N, J, T, size_projected=None, det=None, tag=None):
+    """The aggregation of every scale (``lp_tta_merge_scales``): ``mids`` = one (mid, h1, w1) per TEST.SCALE_FACTOR
+    entry in ``scale_order`` order, each mid an ``tta_stage`` buffer.  Returns (final_heatmaps [N,J,Hf,Wf],
+    tags [N,J,Hf,Wf,T]) -- bit for bit ``tta_project`` per scale + ``aggregate_results`` + the division by
+    len(SCALE_FACTOR) of valid.py:224.  TEST.PROJECT2IMAGE: (Hf, Wf) = ``size_projected`` (W, H), the base size;
+    otherwise the first scale's stage-1 size."""
+    _, first_unit = scale_order(cfg)
+    S = len(mids)
+    if S != len(cfg.TEST.SCALE_FACTOR):
+        raise ValueError('one mid per TEST.SCALE_FACTOR entry is required')
+    p2i = bool(cfg.TEST.PROJECT2IMAGE)
+    if p2i:
+        if not size_projected:
+            raise ValueError('TEST.PROJECT2IMAGE: size_projected (the base size) is required')
+        Wf, Hf = int(size_projected[0]), int(size_projected[1])
+    else:
+        Hf, Wf = int(mids[0][1]), int(mids[0][2])
+    lib = nv.lib()
+    tab = (nv.LpScaleMid * S)()
+    for s, (mid, h1, w1) in enumerate(mids):
+        need = int(lib.lp_tta_workspace_bytes(N, J, int(h1), int(w1)))
+        if mid.numel() * mid.element_size() < need or not mid.is_cuda:
+            raise ValueError('tta_merge_scales: mid %d too small (%d < %d bytes)' % (s, mid.numel(), need))
+        tab[s].mid, tab[s].h1, tab[s].w1 = nv.dptr(mid).value, int(h1), int(w1)
+    dev = mids[0][0].device
+    if det is None:
+        det = torch.empty((N, J, Hf, Wf), dtype=torch.float32, device=dev)
+    if tag is None:
+        tag = torch.empty((N, J, Hf, Wf, T), dtype=torch.float32, device=dev)
+    if tuple(det.shape) != (N, J, Hf, Wf) or tuple(tag.shape) != (N, J, Hf, Wf, T) \
+            or det.dtype != torch.float32 or tag.dtype != torch.float32:
+        raise ValueError('tta_merge_scales: det / tag must be float32 [N,J,Hf,Wf] / [N,J,Hf,Wf,T]')
+    nv.check(lib.lp_tta_merge_scales(tab, S, first_unit, N, J, T, int(p2i), Hf, Wf, nv.dptr(det), nv.dptr(tag),
+                                     nv.stream_ptr()), 'lp_tta_merge_scales')
+    return det, tag
+
+
 class _Merged(list):
     """What get_multi_stage_outputs hands to aggregate_results: the reference passes two
     lists of per-flip maps; here the merge has already been done natively."""

@@ -135,6 +135,31 @@ int lp_tta_merge(const float* d_out0, const float* d_out1, const float* d_out0f,
                            h_flip_index, d_det, d_tag, ws, ws_bytes, stream);
 }
 
+int lp_tta_merge_scales(const lp_scale_mid* scales, int S, int first_unit, int N, int J, int T, int project2image,
+                        int Hf, int Wf, float* d_det, float* d_tag, void* stream) {
+    if (!scales || !d_det || !d_tag) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (S < 1 || S > LP_MAX_SCALES) return fail(LP_ERR_INVALID_ARG, "S must be 1..LP_MAX_SCALES (8)");
+    if (first_unit < 0 || first_unit >= S) return fail(LP_ERR_INVALID_ARG, "first_unit must index a scale");
+    if (N < 1 || J < 1 || J > 32 || T < 1 || T > 2) return fail(LP_ERR_INVALID_ARG, "need N >= 1, J 1..32, T 1..2");
+    if (Hf < 1 || Wf < 1 || Hf > 32767 || Wf > 32767) return fail(LP_ERR_INVALID_ARG, "map sizes must be 1..32767");
+    lp::ScaleTable t;
+    for (int s = 0; s < lp::MAX_SCALES; ++s) t.s[s] = {nullptr, 0, 0};
+    for (int s = 0; s < S; ++s) {
+        if (!scales[s].mid) return fail(LP_ERR_INVALID_ARG, "null mid");
+        if (scales[s].h1 < 1 || scales[s].w1 < 1 || scales[s].h1 > 32767 || scales[s].w1 > 32767)
+            return fail(LP_ERR_INVALID_ARG, "stage-1 sizes must be 1..32767");
+        t.s[s] = {scales[s].mid, scales[s].h1, scales[s].w1};
+    }
+    if (!project2image && (Hf != scales[0].h1 || Wf != scales[0].w1))
+        return fail(LP_ERR_INVALID_ARG, "without project2image (Hf, Wf) is the first scale's stage-1 size");
+    if (T == 2 && ((uintptr_t)d_tag & 7)) return fail(LP_ERR_INVALID_ARG, "d_tag must be 8-byte aligned");
+    if ((int64_t)N * 4 * J > 0x7fffffff) return fail(LP_ERR_UNSUPPORTED, "N * J too large");
+    lp::launch_tta_merge_scales(t, S, first_unit, N, J, T, project2image ? 1 : 0, Hf, Wf, d_det, d_tag,
+                                (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "tta_merge_scales launch failed");
+    return LP_OK;
+}
+
 int lp_maps_accumulate(float* d_acc, const float* d_src, int64_t count, void* stream) {
     if (!d_acc || !d_src) return fail(LP_ERR_INVALID_ARG, "null argument");
     if (count < 0) return fail(LP_ERR_INVALID_ARG, "negative count");

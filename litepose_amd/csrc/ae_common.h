@@ -31,11 +31,15 @@ __device__ __forceinline__ Lerp lerp_coord(int dst, int in, int out) {
     r.l0 = 1.f - r.l1;
     return r;
 }
+// the weighting of four taps a = (i0, i0), b = (i0, i1), c = (i1, i0), d = (i1, i1) [row, column]
+__device__ __forceinline__ float bilerp_taps(float a, float b, float c, float d, const Lerp& ly, const Lerp& lx) {
+    return ly.l0 * (lx.l0 * a + lx.l1 * b) + ly.l1 * (lx.l0 * c + lx.l1 * d);
+}
 __device__ __forceinline__ float bilerp(const float* __restrict__ plane, int w, const Lerp& ly,
                                         const Lerp& lx) {
     const float a = plane[(long)ly.i0 * w + lx.i0], b = plane[(long)ly.i0 * w + lx.i1];
     const float c = plane[(long)ly.i1 * w + lx.i0], d = plane[(long)ly.i1 * w + lx.i1];
-    return ly.l0 * (lx.l0 * a + lx.l1 * b) + ly.l1 * (lx.l0 * c + lx.l1 * d);
+    return bilerp_taps(a, b, c, d, ly, lx);
 }
 
 // ------------------------------------------------------------------------------------

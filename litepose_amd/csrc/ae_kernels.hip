@@ -290,10 +290,15 @@ __global__ __launch_bounds__(256) void tta_project2x_kernel(const float* __restr
     }
 }
 
+// launch_tta_project runs tta_project2x_kernel for this projection (launch_tta_merge_scales follows the same choice)
+static bool tta_project_is_x2(int N, int J, int h1, int w1, int Hp, int Wp) {
+    constexpr int fast2x = 1;        // the exact x2 form wherever the shape admits it
+    return fast2x && Hp == 2 * h1 && Wp == 2 * w1 && h1 >= 2 && w1 >= 2 && (long)N * J <= 65535;
+}
+
 bool launch_tta_project(const float* mid, int N, int J, int h1, int w1, int Hp, int Wp, int T,
                         float* det, float* tag, hipStream_t s) {
-    constexpr int fast2x = 1;        // the exact x2 form wherever the shape admits it
-    if (fast2x && Hp == 2 * h1 && Wp == 2 * w1 && h1 >= 2 && w1 >= 2 && (long)N * J <= 65535) {
+    if (tta_project_is_x2(N, J, h1, w1, Hp, Wp)) {
         const int cg = (w1 % P2_COLS) == 0 ? tta_col_groups(w1) : 1;
         const dim3 grid((w1 + P2_COLS * cg - 1) / (P2_COLS * cg), (h1 + P2_ROWS - 1) / P2_ROWS, N * J);
 #define LP_TP(CGV) hipLaunchKernelGGL(tta_project2x_kernel<CGV>, grid, dim3(256), 0, s, mid, J, h1, w1, T, det, tag)
@@ -309,6 +314,105 @@ bool launch_tta_project(const float* mid, int N, int J, int h1, int w1, int Hp, 
     hipLaunchKernelGGL(tta_project_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, mid,
                        N, J, h1, w1, Hp, Wp, T, det, tag);
     return true;
+}
+
+// Multi-scale aggregation in one pass (valid.py:207-224 with inference.py:176-208), the operation sequence of the
+// batch-1 chain restated per output element, so the bits are the chain's:
+//   chain                                          here
+//   lp_tta_merge per scale (tta_project_kernel)    d_s = merged_at(): bilerp of heat (+ heat_flip, then / 2)
+//   aggregate_results: lp_maps_accumulate          acc = d_0; acc = acc + d_s
+//   valid.py:224 final_heatmaps / len(SCALE_FACTOR)  det = acc * inv_s, inv_s = 1.0f / (float)S on the host: PyTorch
+//                                                  divides a device tensor by a host scalar as a multiplication by
+//                                                  the fp32 reciprocal (its div_true kernel), not as a correctly
+//                                                  rounded division -- the last bit differs for S = 3
+//   a projection the chain runs as tta_project2x_kernel (tta_project_is_x2; bit s of x2_mask): that kernel's
+//   replicate-clamped halo takes the weight-0 tap of output row / column 0 from index 0 where lerp_coord names index
+//   1 -- the same value unless a cell is -0.0 or a neighbour is not finite; x2_first() takes the same tap
+// PROJECT2IMAGE = False: a later scale whose stage-1 size differs from the first one's is resized by resize_maps, i.e.
+// tta_project of a mid whose heat == heat_flip == that scale's merged map: r = bilerp of the four merged taps, then
+// (r + r) / 2 with flip.  The scale-1 tags take the same two steps when their size differs.  No identity shortcut:
+// lerp_coord at equal sizes weights (1, 0), which is not x for -0.0 or a non-finite neighbour.
+__device__ __forceinline__ Lerp x2_first(Lerp l, int dst, bool x2) {
+    if (x2 && dst == 0) l.i1 = 0;
+    return l;
+}
+__device__ __forceinline__ float merged_at(const float* __restrict__ heat, const float* __restrict__ heat_f, int w,
+                                           int T, const Lerp& ly, const Lerp& lx) {
+    const float hm = bilerp(heat, w, ly, lx);
+    if (T != 2) return hm;
+    const float hf = bilerp(heat_f, w, ly, lx);
+    return (hm + hf) / 2.0f;
+}
+// the (Y, X) value of the map a scale contributes: merged_at projected to (Hf, Wf), or with `resize` merged_at at the
+// scale's own size, then resized (inference.py:201-206; with T == 1 the tag path, heat_f unused)
+__device__ __forceinline__ float scale_value(const float* __restrict__ heat, const float* __restrict__ heat_f, int h1,
+                                             int w1, int T, bool resize, bool x2, int Hf, int Wf, int Y, int X) {
+    const Lerp ly = x2_first(lerp_coord(Y, h1, Hf), Y, x2), lx = x2_first(lerp_coord(X, w1, Wf), X, x2);
+    if (!resize) return merged_at(heat, heat_f, w1, T, ly, lx);
+    const Lerp y0 = lerp_coord(ly.i0, h1, h1), y1 = lerp_coord(ly.i1, h1, h1);
+    const Lerp x0 = lerp_coord(lx.i0, w1, w1), x1 = lerp_coord(lx.i1, w1, w1);
+    const float r = bilerp_taps(merged_at(heat, heat_f, w1, T, y0, x0), merged_at(heat, heat_f, w1, T, y0, x1),
+                                merged_at(heat, heat_f, w1, T, y1, x0), merged_at(heat, heat_f, w1, T, y1, x1), ly, lx);
+    return T == 2 ? (r + r) / 2.0f : r;
+}
+
+__device__ __forceinline__ void merge_scales_at(const ScaleTable& tab, int S, int first_unit, int J, int T,
+                                                int project2image, int x2_mask, float inv_s, int Hf, int Wf, int n,
+                                                int j, int Y, int X, long g, float* __restrict__ det,
+                                                float* __restrict__ tag) {
+    float acc = 0.f;
+    for (int s = 0; s < S; ++s) {
+        const ScaleMid sm = tab.s[s];
+        const int plane1 = sm.h1 * sm.w1;
+        const bool resize = !project2image && (sm.h1 != Hf || sm.w1 != Wf);
+        const float d = scale_value(mid_plane(sm.mid, n, 0, j, J, plane1), mid_plane(sm.mid, n, 1, j, J, plane1),
+                                    sm.h1, sm.w1, T, resize, (x2_mask >> s) & 1, Hf, Wf, Y, X);
+        acc = s == 0 ? d : acc + d;
+    }
+    det[g] = acc * inv_s;
+    const ScaleMid su = tab.s[first_unit];
+    const int plane1 = su.h1 * su.w1;
+    const bool resize = !project2image && (su.h1 != Hf || su.w1 != Wf);
+    // a tag plane alone: T = 1 in scale_value (no flip average; resize_maps projects each tag plane by itself)
+    const bool x2 = (x2_mask >> first_unit) & 1;
+    const float t0 =
+        scale_value(mid_plane(su.mid, n, 2, j, J, plane1), nullptr, su.h1, su.w1, 1, resize, x2, Hf, Wf, Y, X);
+    if (T == 2) {
+        const float t1 =
+            scale_value(mid_plane(su.mid, n, 3, j, J, plane1), nullptr, su.h1, su.w1, 1, resize, x2, Hf, Wf, Y, X);
+        *reinterpret_cast<float2*>(tag + g * 2) = float2{t0, t1};
+    } else {
+        tag[g] = t0;
+    }
+}
+
+__global__ __launch_bounds__(256) void tta_merge_scales_kernel(const ScaleTable tab, int S, int first_unit, int J,
+                                                               int T, int project2image, int x2_mask, float inv_s,
+                                                               int Hf, int Wf, int NJ, float* __restrict__ det,
+                                                               float* __restrict__ tag) {
+    // x: pixels of one (image, joint) plane, y: planes (a grid-stride loop past 65535 planes)
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= Hf * Wf) return;
+    const int X = pix % Wf, Y = pix / Wf;
+    for (int nj = blockIdx.y; nj < NJ; nj += gridDim.y) {
+        const int n = nj / J, j = nj - n * J;
+        const long g = (long)nj * Hf * Wf + pix;
+        merge_scales_at(tab, S, first_unit, J, T, project2image, x2_mask, inv_s, Hf, Wf, n, j, Y, X, g, det, tag);
+    }
+}
+
+void launch_tta_merge_scales(const ScaleTable& t, int S, int first_unit, int N, int J, int T, int project2image,
+                             int Hf, int Wf, float* det, float* tag, hipStream_t s) {
+    // every scale's projection in the chain goes from its (h1, w1) to (Hf, Wf): directly, or (PROJECT2IMAGE = False,
+    // another size) as the resize of its merged map; equal sizes are never x2
+    int x2_mask = 0;
+    for (int i = 0; i < S; ++i)
+        if (tta_project_is_x2(N, J, t.s[i].h1, t.s[i].w1, Hf, Wf)) x2_mask |= 1 << i;
+    const float inv_s = 1.0f / (float)S;
+    const int NJ = N * J;
+    const dim3 grid((unsigned)((Hf * Wf + 255) / 256), (unsigned)(NJ < 65535 ? NJ : 65535));
+    hipLaunchKernelGGL(tta_merge_scales_kernel, grid, dim3(256), 0, s, t, S, first_unit, J, T, project2image, x2_mask,
+                       inv_s, Hf, Wf, NJ, det, tag);
 }
 
 // Multi-scale aggregation (inference.py:199-201, PROJECT2IMAGE): final_heatmaps += heatmaps_avg.

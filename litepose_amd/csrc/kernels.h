@@ -217,6 +217,17 @@ void launch_maps_accumulate(float* acc, const float* src, long count, hipStream_
 // tag == nullptr: det only (exact x2 projection only; false = not available for this shape)
 bool launch_tta_project(const float* mid, int N, int J, int h1, int w1, int Hp, int Wp, int T,
                         float* det, float* tag, hipStream_t s);
+// one scale of launch_tta_merge_scales: the layout of lp_scale_mid (include/litepose_amd.h)
+constexpr int MAX_SCALES = 8;
+struct ScaleMid {
+    const float* mid;       // [N][4][J][h1][w1] of lp_tta_stage
+    int h1, w1;
+};
+static_assert(sizeof(ScaleMid) == 16, "ScaleMid must match lp_scale_mid (16 bytes)");
+struct ScaleTable { ScaleMid s[MAX_SCALES]; };      // passed by value: a captured launch holds the table itself
+// multi-scale aggregation of S stage merges (descending scale order) into det [N,J,Hf,Wf] / tag [N,J,Hf,Wf,T]
+void launch_tta_merge_scales(const ScaleTable& t, int S, int first_unit, int N, int J, int T, int project2image,
+                             int Hf, int Wf, float* det, float* tag, hipStream_t s);
 
 // tag == nullptr: the winners' tags are the exact x2 projection of `mid` (lp_parse_dm); false = not available
 bool launch_peaks_topk(const float* det, const float* tag, int N, int J, int H, int W, int T,

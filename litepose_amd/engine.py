@@ -111,7 +111,8 @@ class PoseEngine(object):
         self._prepared = False
         self._in_prepare = False
 
-    def _buffers(self, N, H, W):
+    def _buffers(self, N, H, W, keep=_MAX_SHAPES):
+        """``keep``: shapes that stay resident (a multi-scale batch uses S shapes at once: keep >= S + 1)."""
         key = (N, H, W)
         b = self._bufs.get(key)
         if b is None:
@@ -141,19 +142,19 @@ class PoseEngine(object):
             PoseEngine._buf_serial += 1
             b['serial'] = PoseEngine._buf_serial
             shapes = [k for k in self._bufs if isinstance(k, tuple) and len(k) == 3]
-            while len(shapes) >= _MAX_SHAPES:
+            while len(shapes) >= keep:
                 self._bufs.pop(shapes.pop(0))
             self._bufs[key] = b
         elif list(self._bufs)[-1] != key:
             self._bufs[key] = self._bufs.pop(key)            # most recently used last
         return b
 
-    def _forward_net(self, images, offsets=None, defer_offsets=False):
+    def _forward_net(self, images, offsets=None, defer_offsets=False, keep=_MAX_SHAPES):
         """``defer_offsets``: do not add ``offsets`` here -- the caller hands them to the stage merge, which adds them
         as it reads the outputs (lp_tta_stage_add: bit-identical, one pass over the outputs less)."""
         cfg = self.cfg
         N, _, H, W = images.shape
-        b = self._buffers(N, H, W)
+        b = self._buffers(N, H, W, keep)
         flip = 2 if cfg.TEST.FLIP_TEST else 0
         m = self.model
         nv.check(self._lib.lp_net_forward(m._h, nv.dptr(images), N, H, W, flip, nv.dptr(b['out0']),
@@ -174,6 +175,88 @@ class PoseEngine(object):
             b['tag'] = torch.empty((N, self.J, H, W, self.T), dtype=torch.float32, device=self.device)
         return b['det'], b['tag']
 
+    def _ms_buffers(self, N, shapes):
+        """Buffers of a multi-scale batch beside the per-shape ones (network outputs, workspace, mid of each scale): the
+        merged maps, the parser's records and workspace, and a mid for every scale whose shape an earlier scale of the
+        tuple already uses.  Keyed by the whole tuple of input shapes ((H, W) per scale): no per-shape dict aliases
+        them.  (Hf, Wf): the base size (the scale-1 input) with TEST.PROJECT2IMAGE, else the first scale's stage-1
+        size."""
+        key = ('ms', N, shapes, bool(self.cfg.TEST.PROJECT2IMAGE))
+        b = self._bufs.get(key)
+        if b is None:
+            dev, J, T, pcap = self.device, self.J, self.T, self.pcap
+            _, unit = _inference.scale_order(self.cfg)
+            Hf, Wf = shapes[unit] if self.cfg.TEST.PROJECT2IMAGE else (shapes[0][0] // 2, shapes[0][1] // 2)
+            b = {
+                'Hf': Hf, 'Wf': Wf,
+                'det': torch.empty((N, J, Hf, Wf), dtype=torch.float32, device=dev),
+                'tag': torch.empty((N, J, Hf, Wf, T), dtype=torch.float32, device=dev),
+                'ans': torch.empty((N, pcap, J, 3 + T), dtype=torch.float32, device=dev),
+                'count': torch.empty((N,), dtype=torch.int32, device=dev),
+                'scores': torch.empty((N, pcap), dtype=torch.float32, device=dev),
+                'mids': {},
+            }
+            need_p = int(self._lib.lp_parse_workspace_bytes(N, J, self.parser.params.max_num_people, T, pcap))
+            b['parse_ws'] = torch.empty(max(need_p, 256), dtype=torch.uint8, device=dev)
+            for s, (H, W) in enumerate(shapes):
+                if (H, W) in shapes[:s]:         # the per-shape mid holds the earlier scale's stage merge
+                    need_t = int(self._lib.lp_tta_workspace_bytes(N, J, H // 2, W // 2))
+                    b['mids'][s] = torch.empty(max(need_t, 256), dtype=torch.uint8, device=dev)
+            PoseEngine._buf_serial += 1
+            b['serial'] = PoseEngine._buf_serial
+            old = [k for k in self._bufs if isinstance(k, tuple) and len(k) == 4 and k[0] == 'ms']
+            while len(old) >= _MAX_SHAPES:
+                self._bufs.pop(old.pop(0))
+            self._bufs[key] = b
+        return b
+
+    def _stage_net_ms(self, images):
+        """NET stage of a multi-scale batch (``images``: one input per scale, scale_order): per scale the network on
+        the image and its mirror and the stage merge into that scale's mid, then ONE lp_tta_merge_scales into the merged
+        maps.  The merge always runs here (option split='early' does not apply).  Returns the context of _stage_ae."""
+        N = images[0].shape[0]
+        shapes = tuple((int(x.shape[2]), int(x.shape[3])) for x in images)
+        keep = max(_MAX_SHAPES, len(images) + 1)             # all S shapes stay resident during the batch
+        mb = self._ms_buffers(N, shapes)
+        mids = []
+        for s, x in enumerate(images):
+            b, outs, outs_f = self._forward_net(x, keep=keep)
+            mid = mb['mids'].get(s, b['tta_ws'])
+            _, _, h1, w1, _ = _inference.tta_stage(self.cfg, outs, outs_f, mid)
+            mids.append((mid, h1, w1))
+        det, tag = _inference.tta_merge_scales(self.cfg, mids, N, self.J, self.T, (mb['Wf'], mb['Hf']),
+                                               det=mb['det'], tag=mb['tag'])
+        self._last = [('maps', det, tag)]
+        return ('ms', N, mb['Hf'], mb['Wf'], mb)
+
+    def _graph_bufs(self, images):
+        """The buffers the launches of an input point into (a captured graph keeps a reference to them)."""
+        if isinstance(images, tuple):
+            N = images[0].shape[0]
+            shapes = tuple((int(x.shape[2]), int(x.shape[3])) for x in images)
+            keep = max(_MAX_SHAPES, len(images) + 1)
+            return [self._buffers(N, H, W, keep) for H, W in shapes] + [self._ms_buffers(N, shapes)]
+        return self._buffers(images.shape[0], images.shape[2], images.shape[3])
+
+    def _check_scales(self, images, offsets, center, scale, preds_coef):
+        """A tuple input of submit / infer_batch: one normalised float32 [N,3,H_s,W_s] device tensor per
+        TEST.SCALE_FACTOR entry, in the order valid.py visits them (sorted, descending); back-projection by
+        ``preds_coef`` only."""
+        if offsets is not None or center is not None or scale is not None:
+            raise ValueError('a multi-scale (tuple) input takes no offsets / center / scale: pass preds_coef')
+        if preds_coef is None:
+            raise ValueError('a multi-scale (tuple) input needs preds_coef, one back-projection row per image')
+        _inference.scale_order(self.cfg)
+        if len(images) != len(self.cfg.TEST.SCALE_FACTOR):
+            raise ValueError('one input per TEST.SCALE_FACTOR entry is required (%d given, %d scales)'
+                             % (len(images), len(self.cfg.TEST.SCALE_FACTOR)))
+        N = images[0].shape[0]
+        for x in images:
+            if (not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4
+                    or x.shape[0] != N or x.shape[1] != 3 or not x.is_contiguous()):
+                raise ValueError('multi-scale inputs must be contiguous float32 [N,3,H,W] device tensors of one N')
+        self._check_coef(preds_coef, N, None, None)
+
     def forward_maps(self, images, offsets=None):
         """Network (+flip) + TTA merge with the full-resolution maps materialised like the reference does.
         ``offsets`` = optional (off0, off1) tensors of the network-output shapes added to the raw outputs
@@ -183,7 +266,8 @@ class PoseEngine(object):
         N, _, H, W = images.shape
         b, outs, outs_f = self._forward_net(images, offsets)
         if not cfg.TEST.PROJECT2IMAGE:
-            raise NotImplementedError('PROJECT2IMAGE=False is not on the batched path')
+            raise NotImplementedError('PROJECT2IMAGE=False: pass the input as a tuple (one tensor per scale) to '
+                                      'submit / infer_batch')
         det, tag = self._full_maps(b, N, H, W)
         _inference.tta_merge(cfg, outs, outs_f, (W, H), det=det, tag=tag, ws=b['tta_ws'])
         return det, tag
@@ -259,10 +343,12 @@ class PoseEngine(object):
                  'lp_parse_dm')
         return b['ans'], b['count'], b['scores']
 
-    def parse_maps(self, det, tag):
+    def parse_maps(self, det, tag, b=None):
+        """``b``: the buffer dict that receives the records (default: the one of input shape [N,3,H,W])."""
         cfg = self.cfg
         N, J, H, W = det.shape
-        b = self._buffers(N, H, W)
+        if b is None:
+            b = self._buffers(N, H, W)
         q = self.parser._q
         nv.check(self._lib.lp_parse(nv.dptr(det), nv.dptr(tag), N, J, H, W, self.T, C.byref(q), self.pcap,
                                     int(bool(cfg.TEST.ADJUST)), int(bool(cfg.TEST.REFINE)),
@@ -293,6 +379,8 @@ class PoseEngine(object):
     def _stage_net(self, images, offsets, early=False):
         """First half of a batch: the network on the image and its mirror and (unless ``early``) the stage merge
         and the projection -- the chip-filling, bandwidth-heavy launches.  Returns the context of _stage_ae."""
+        if isinstance(images, tuple):
+            return self._stage_net_ms(images)
         N, _, H, W = images.shape
         path = self._ae_path(H, W)
         if path == 'dm' and N * self.J > 65535:               # grid limit of the det-only projection
@@ -309,7 +397,8 @@ class PoseEngine(object):
         b = self._buffers(N, H, W)
         if path == 'maps':
             if not cfg.TEST.PROJECT2IMAGE:
-                raise NotImplementedError('PROJECT2IMAGE=False is not on the batched path')
+                raise NotImplementedError('PROJECT2IMAGE=False: pass the input as a tuple (one tensor per scale) '
+                                          'to submit / infer_batch')
             det, tag = self._full_maps(b, N, H, W)
             _inference.tta_merge(cfg, outs, outs_f, (W, H), det=det, tag=tag, ws=b['tta_ws'])
             self._last = [('maps', det, tag)]
@@ -327,6 +416,10 @@ class PoseEngine(object):
         """Second half: the AE post-process (NMS/top-k, grouping, adjust, refine, back-projection) -- latency-bound
         launches that fill a fraction of the chip.  ``coef``: per-image back-projection table (see submit)."""
         path, N, H, W = ctx[:4]
+        if path == 'ms':                                      # multi-scale: records into the batch's own dict
+            ans, count, scores = self.parse_maps(ctx[4]['det'], ctx[4]['tag'], ctx[4])
+            _tf.final_preds_device_v(ans, count, coef)
+            return ans, count, scores
         if isinstance(ctx[4], (list, tuple)):                 # early split: the merge runs here
             ctx = self._stage_merge(path, N, H, W, ctx[4], ctx[5], ctx[6])
         if path == 'maps':
@@ -363,7 +456,15 @@ class PoseEngine(object):
         (kpts [N,pcap,J,3+T], count [N] int32, scores [N,pcap]); no host sync.
         ``preds_coef``: optional [N,4] float64 device table, one back-projection (sx, tx, sy, ty) per image
         (``utils.transforms.final_preds_coef`` of the image's own centre / scale), instead of one ``center`` /
-        ``scale`` for the whole batch."""
+        ``scale`` for the whole batch.
+        ``images`` may also be a tuple, one normalised input [N,3,H_s,W_s] per TEST.SCALE_FACTOR entry in the order
+        valid.py visits them (sorted, descending): multi-scale testing and TEST.PROJECT2IMAGE = False (a 1-tuple for
+        one scale), ``preds_coef`` required (see submit).  No half pipelining for a tuple."""
+        if isinstance(images, (tuple, list)):
+            images = tuple(images)
+            self._check_scales(images, offsets, center, scale, preds_coef)
+            nv.check(self._lib.lp_net_set_streams(self.model._h, 2))
+            return self._infer_one(images, None, None, None, preds_coef)
         N = images.shape[0]
         self._check_coef(preds_coef, N, center, scale)
         if not self.pipeline_halves or N < 2 or N % 2:
@@ -440,7 +541,17 @@ class PoseEngine(object):
         _MAX_SHAPES keys, each with a reference to the buffers it was captured on.  Kernel-family options
         (``model.set_option('mb16', 0)`` ..., lp_net_set_option) are baked into a captured graph: call
         ``reset_graphs()`` after changing one.
-        Option ``graph=False`` disables."""
+        Option ``graph=False`` disables.
+
+        Multi-scale (``images`` a tuple, one normalised [N,3,H_s,W_s] input per TEST.SCALE_FACTOR entry in the order
+        valid.py visits them, sorted descending; also TEST.PROJECT2IMAGE = False, with a 1-tuple for one scale): the NET
+        stage runs the network and the stage merge per scale and one lp_tta_merge_scales, the AE stage lp_parse on the
+        merged maps and lp_final_preds_v with ``preds_coef`` (required; offsets / center / scale are refused).  The
+        graph key holds every scale's pointer and shape."""
+        ms = isinstance(images, (tuple, list))
+        if ms:
+            images = tuple(images)
+            self._check_scales(images, offsets, center, scale, preds_coef)
         self._ensure_lanes()
         lane = self._lanes[self._lane_next]
         self._lane_next = (self._lane_next + 1) % len(self._lanes)
@@ -449,10 +560,16 @@ class PoseEngine(object):
         fork.record(main)
         nst = self.options['streams']
         nv.check(self._lib.lp_net_set_streams(self.model._h, int(nst) if nst else (1 if self._split else 2)))
-        N, _, H, W = images.shape
-        self._check_coef(preds_coef, N, center, scale)
         cfg = self.cfg
         early = self._split and self.options['split'] == 'early'
+        if ms:
+            key = (tuple(x.data_ptr() for x in images), tuple(tuple(x.shape) for x in images), None, None, None,
+                   tuple(b['serial'] for b in lane['eng']._graph_bufs(images)), 'ms', early,
+                   bool(cfg.TEST.ADJUST), bool(cfg.TEST.REFINE), bool(cfg.TEST.FLIP_TEST), bool(cfg.TEST.PROJECT2IMAGE),
+                   (preds_coef.data_ptr(), tuple(preds_coef.shape)))
+            return self._submit_key(lane, key, fork, images, offsets, center, scale, early, preds_coef)
+        N, _, H, W = images.shape
+        self._check_coef(preds_coef, N, center, scale)
         key = (images.data_ptr(), tuple(images.shape),
                None if offsets is None else tuple((o.data_ptr(), tuple(o.shape)) for o in offsets),
                None if center is None else tuple(float(v) for v in center),
@@ -461,6 +578,9 @@ class PoseEngine(object):
                bool(cfg.TEST.ADJUST), bool(cfg.TEST.REFINE), bool(cfg.TEST.FLIP_TEST))
         if preds_coef is not None:
             key = key + ((preds_coef.data_ptr(), tuple(preds_coef.shape)),)
+        return self._submit_key(lane, key, fork, images, offsets, center, scale, early, preds_coef)
+
+    def _submit_key(self, lane, key, fork, images, offsets, center, scale, early, preds_coef):
         if self._split:
             tensors, done = self._submit_split(lane, key, fork, images, offsets, center, scale, early, preds_coef)
         else:
@@ -576,6 +696,29 @@ class PoseEngine(object):
                 for k in [k for k in d if k[1] == (N, 3, H, W)]:
                     d.pop(k)
 
+    def release_scales(self, N, sizes):
+        """``release_shape`` for a multi-scale input: ``sizes`` = (H, W) per scale.  Drops the buffers of every scale's
+        shape, the merged maps and records of the tuple, and the captured graphs of the tuple and of its shapes."""
+        sizes = tuple((int(h), int(w)) for h, w in sizes)
+        shapes = tuple((N, 3, h, w) for h, w in sizes)
+        torch.cuda.synchronize()
+        for eng in [self] + [ln['eng'] for ln in (self._lanes or [])]:
+            for h, w in sizes:
+                eng._bufs.pop((N, h, w), None)
+            for k in [k for k in eng._bufs if isinstance(k, tuple) and len(k) == 4 and k[:3] == ('ms', N, sizes)]:
+                eng._bufs.pop(k)
+        for ln in (self._lanes or []):
+            for d in (ln['graphs'], ln['seen']):
+                for k in [k for k in d if k[1] == shapes or k[1] in shapes]:
+                    d.pop(k)
+
+    def ms_workspace_bytes(self, N, sizes):
+        """Network workspace of a multi-scale input of ``sizes`` ((H, W) per scale) over every buffer set: each set
+        holds one per scale (the bulk of a set's memory)."""
+        nb = 2 * N if self.cfg.TEST.FLIP_TEST else N
+        per_set = sum(int(self._lib.lp_net_workspace_bytes(self.model._h, nb, int(h), int(w))) for h, w in sizes)
+        return per_set * self.buffer_sets()
+
     def graph_stats(self):
         """{'use_graphs', 'captured_sets', 'graph_replays', 'graph_captures', 'eager_stages', 'capture_failures',
         'capture_mode'}: whether the serving loop really runs as graph replays (a failed capture drops the engine
@@ -614,7 +757,7 @@ class PoseEngine(object):
                 capture = ent is not None
                 if capture:
                     # the graph bakes in pointers of THESE buffers: keep them alive with it
-                    ent['bufs'] = eng._buffers(images.shape[0], images.shape[2], images.shape[3])
+                    ent['bufs'] = eng._graph_bufs(images)
                     ctx = ent['ctx']
             if not replay and not capture:
                 if lane['stream'] is not ns:         # the capture failed and moved the lane to a fresh stream
@@ -675,8 +818,7 @@ class PoseEngine(object):
             with torch.cuda.graph(g, stream=lane['stream'], capture_error_mode=self.options['capture_mode']):
                 tensors = lane['eng']._infer_one(images, offsets, center, scale, coef)
             _remember(lane['graphs'], key, {'g': [g], 'out': tensors, 'ctx': None,
-                                            'bufs': lane['eng']._buffers(images.shape[0], images.shape[2],
-                                                                         images.shape[3])})
+                                            'bufs': lane['eng']._graph_bufs(images)})
             self._stats['graph_captures'] += 1
             g.replay()
             return tensors

@@ -21,8 +21,20 @@ and scale (:195-202).  Here:
             own centre / scale (lp_final_preds_v); records -> pinned host memory (StagedLoader.store / wait) ->
             ``results.records_to_results``, returned in input order.
 
-Multi-scale testing (len(TEST.SCALE_FACTOR) > 1) and TEST.PROJECT2IMAGE = False stay on the batch-1 drop-in modules
-(INTEGRATION.md section 3).
+Multi-scale testing (len(TEST.SCALE_FACTOR) > 1) and TEST.PROJECT2IMAGE = False (any number of scales) take the
+multi-scale form of the same loop:
+
+  plan      buckets are keyed by the tuple of network input sizes over all scales (``get_multi_scale_size`` per scale,
+            with its int() truncation), not by the scale-1 size alone.
+  loader    the sources are packed once; one descriptor table per scale (matrix ``get_affine_transform(center,
+            scale_s, 0, size_s)``) and one ``lp_preprocess_batch_v`` launch per scale into that scale's input.
+  engine    ``PoseEngine.submit(tuple of inputs, preds_coef=...)``: per scale the network and the stage merge, one
+            ``lp_tta_merge_scales``, ``lp_parse`` on the merged maps.  The back-projection row is valid.py's: centre
+            and scale of the last scale visited (min(SCALE_FACTOR)), heatmap size (Wf, Hf) of the merged maps -- the
+            base size with TEST.PROJECT2IMAGE, else the first scale's stage-1 size.
+  memory    every buffer set holds one network workspace per scale: a bucket whose workspaces over all scales and
+            sets exceed the free device memory is refused with the largest batch size that fits.
+TEST.SCALE_FACTOR lists the reference loop cannot run (several entries without a 1, or duplicates) raise ValueError.
 """
 import collections
 import time
@@ -34,6 +46,7 @@ import torch
 from . import engine as _engine
 from . import parallel as _par
 from . import results as _results
+from .core import inference as _inference
 from .utils import transforms as _tf
 
 Batch = collections.namedtuple('Batch', 'size rows real')
@@ -41,15 +54,23 @@ Batch.__doc__ = """One engine batch of the plan: ``size`` = (w, h) network input
 (``batch_size`` of them; rows[real:] repeat a real image and are padding), ``real`` = number of real rows."""
 
 
-def plan(shapes, input_size, min_scale, batch_size):
+def plan(shapes, input_size, min_scale, batch_size, scales=None):
     """Bucket plan (host only).  ``shapes``: (h, w) per image.  Buckets in order of first appearance, batches in input
-    order inside a bucket; every batch has ``batch_size`` rows."""
+    order inside a bucket; every batch has ``batch_size`` rows.  ``scales``: None = the single-scale plan (bucket key
+    (w, h) at scale 1); a list of scale factors in the order valid.py visits them (sorted, descending) = the
+    multi-scale plan, bucket key ((w, h) per scale)."""
     if batch_size < 1:
         raise ValueError('batch_size must be >= 1')
     buckets = collections.OrderedDict()
     for i, hw in enumerate(shapes):
-        size, _, _ = _tf.get_multi_scale_size((int(hw[0]), int(hw[1])), input_size, 1.0, min_scale)
-        buckets.setdefault((int(size[0]), int(size[1])), []).append(i)
+        hw = (int(hw[0]), int(hw[1]))
+        if scales is None:
+            size, _, _ = _tf.get_multi_scale_size(hw, input_size, 1.0, min_scale)
+            key = (int(size[0]), int(size[1]))
+        else:
+            key = tuple(tuple(int(v) for v in _tf.get_multi_scale_size(hw, input_size, s, min_scale)[0])
+                        for s in scales)
+        buckets.setdefault(key, []).append(i)
     out = []
     for size, idx in buckets.items():
         for b in range(0, len(idx), batch_size):
@@ -62,7 +83,7 @@ def bucket_histogram(batches):
     """{'WxH': images} of a plan (real rows only)."""
     h = collections.OrderedDict()
     for b in batches:
-        k = '%dx%d' % b.size
+        k = '+'.join('%dx%d' % sz for sz in _sizes(b.size))
         h[k] = h.get(k, 0) + b.real
     return h
 
@@ -83,6 +104,11 @@ def in_input_order(batches, per_batch):
     return out
 
 
+def _sizes(size):
+    """A plan's bucket key as a tuple of (w, h), one per scale."""
+    return size if isinstance(size[0], tuple) else (size,)
+
+
 class _Transforms(object):
     """Per source size (h, w): the lp_warp_desc matrix and the lp_final_preds_coef row (both depend on the size only)."""
 
@@ -100,12 +126,43 @@ class _Transforms(object):
         return t
 
 
+class _ScaleTransforms(object):
+    """Multi-scale form of _Transforms: per source size (h, w) one lp_warp_desc matrix per scale (``scales`` in
+    visiting order) and the back-projection row of valid.py: centre / scale of the last scale visited, heatmap size of
+    the merged maps (base size with ``project2image``, else the first scale's stage-1 size)."""
+
+    def __init__(self, input_size, scales, project2image):
+        self.input_size, self.scales, self.p2i = input_size, list(scales), bool(project2image)
+        self.min_scale = min(self.scales)
+        self._cache = {}
+
+    def __call__(self, hw):
+        t = self._cache.get(hw)
+        if t is None:
+            minvs, sizes = [], []
+            for s in self.scales:
+                size, center, scale = _tf.get_multi_scale_size(hw, self.input_size, s, self.min_scale)
+                minvs.append(_tf.warp_invert(_tf.get_affine_transform(center, scale, 0, size)))
+                sizes.append(size)
+            if self.p2i:
+                heatmap = _tf.get_multi_scale_size(hw, self.input_size, 1.0, self.min_scale)[0]
+            else:
+                heatmap = (int(sizes[0][0]) // 2, int(sizes[0][1]) // 2)
+            t = (tuple(minvs), _tf.final_preds_coef(center, scale, heatmap))
+            self._cache[hw] = t
+        return t
+
+
 class BucketLoader(_engine.StagedLoader):
     """StagedLoader for images of different sizes: one staging set per buffer set of the engine (see the module
     docstring).  The record half (``store`` / ``wait``) is StagedLoader's."""
 
-    def __init__(self, engine, batch_size, src_capacity, transforms, mean=None, std=None):
+    def __init__(self, engine, batch_size, src_capacity, transforms, mean=None, std=None, scales=1):
+        """``scales``: number of scales (> 1 or a _ScaleTransforms: one descriptor table and network input per scale,
+        ``start`` returns their tuple)."""
         dev = engine.device
+        self.S = int(scales)
+        self.multi = isinstance(transforms, _ScaleTransforms)
         self.nset = engine.buffer_sets()
         self.N = int(batch_size)
         self.mean = tuple(mean) if mean is not None else _tf.IMAGENET_MEAN
@@ -115,13 +172,14 @@ class BucketLoader(_engine.StagedLoader):
         nd = _tf.WARP_DESC_DTYPE.itemsize
         self.host_src = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(self.nset)]
         self.dev_src = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(self.nset)]
-        self.host_desc = [torch.zeros((self.N, nd), dtype=torch.uint8).pin_memory() for _ in range(self.nset)]
-        self.dev_desc = [torch.empty((self.N, nd), dtype=torch.uint8, device=dev) for _ in range(self.nset)]
+        # one table per scale, back to back: [S * N, 64] (one H2D)
+        self.host_desc = [torch.zeros((self.S * self.N, nd), dtype=torch.uint8).pin_memory() for _ in range(self.nset)]
+        self.dev_desc = [torch.empty((self.S * self.N, nd), dtype=torch.uint8, device=dev) for _ in range(self.nset)]
         self.host_coef = [torch.zeros((self.N, 4), dtype=torch.float64).pin_memory() for _ in range(self.nset)]
         self.dev_coef = [torch.empty((self.N, 4), dtype=torch.float64, device=dev) for _ in range(self.nset)]
         # NumPy views of the pinned buffers: the packing worker touches no torch / HIP call
         self._src_np = [t.numpy() for t in self.host_src]
-        self._desc_np = [t.numpy().view(_tf.WARP_DESC_DTYPE).reshape(self.N) for t in self.host_desc]
+        self._desc_np = [t.numpy().view(_tf.WARP_DESC_DTYPE).reshape(self.S, self.N) for t in self.host_desc]
         self._coef_np = [t.numpy() for t in self.host_coef]
         self.x = {}                              # (w, h) -> fp32 [N,3,h,w] network input per set, kept for the call
         self.nbytes = [0] * self.nset
@@ -144,12 +202,13 @@ class BucketLoader(_engine.StagedLoader):
                 raise ValueError('source buffer too small')
             np.copyto(src[off:off + n], im.reshape(-1))
             minv, c = self.transforms((im.shape[0], im.shape[1]))
-            desc[r]['src_offset'], desc[r]['H'], desc[r]['W'] = off, im.shape[0], im.shape[1]
-            desc[r]['minv'] = minv
+            for s, m in enumerate(minv if self.multi else (minv,)):
+                desc[s, r]['src_offset'], desc[s, r]['H'], desc[s, r]['W'] = off, im.shape[0], im.shape[1]
+                desc[s, r]['minv'] = m
             coef[r] = c
             off += n
         for r in range(batch.real, self.N):      # padding: the last real image again (its bytes are already there)
-            desc[r] = desc[batch.real - 1]
+            desc[:, r] = desc[:, batch.real - 1]
             coef[r] = coef[batch.real - 1]
         self.nbytes[i] = off
 
@@ -159,13 +218,15 @@ class BucketLoader(_engine.StagedLoader):
             self.h2d_done[i] = None
 
     def start(self, i, batch=None):
-        """H2D of set i's packed sources and tables + the one lp_preprocess_batch_v launch, on the caller's stream.
-        Returns the set's network input for the batch's bucket."""
-        w, h = batch.size
-        xs = self.x.get((w, h))
-        if xs is None:
-            xs = [torch.empty((self.N, 3, h, w), dtype=torch.float32, device=self.device) for _ in range(self.nset)]
-            self.x[(w, h)] = xs
+        """H2D of set i's packed sources and tables + the one lp_preprocess_batch_v launch per scale, on the caller's
+        stream.  Returns the set's network input for the batch's bucket (multi-scale: the tuple of them)."""
+        xs = []
+        for w, h in _sizes(batch.size):
+            x = self.x.get((w, h))
+            if x is None:
+                x = [torch.empty((self.N, 3, h, w), dtype=torch.float32, device=self.device) for _ in range(self.nset)]
+                self.x[(w, h)] = x
+            xs.append(x)
         n = self.nbytes[i]
         src = self.dev_src[i][:n]
         src.copy_(self.host_src[i][:n], non_blocking=True)
@@ -174,22 +235,52 @@ class BucketLoader(_engine.StagedLoader):
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         self.h2d_done[i] = ev
-        _tf.preprocess_batch_v_device(src, self.dev_desc[i], (w, h), out=xs[i], mean=self.mean, std=self.std)
-        return xs[i]
+        for s, (w, h) in enumerate(_sizes(batch.size)):
+            _tf.preprocess_batch_v_device(src, self.dev_desc[i][s * self.N:(s + 1) * self.N], (w, h), out=xs[s][i],
+                                          mean=self.mean, std=self.std)
+        if self.multi:
+            return tuple(x[i] for x in xs)
+        return xs[0][i]
 
     def get(self, i):
         raise NotImplementedError('BucketLoader.start(i, batch) returns the set\'s network input')
 
 
-def _check_cfg(cfg):
-    if len(cfg.TEST.SCALE_FACTOR) > 1:
-        raise NotImplementedError('evaluate: multi-scale testing (len(TEST.SCALE_FACTOR) > 1) is not on the batched '
-                                  'path; run the batch-1 drop-in modules (core.inference.get_multi_stage_outputs + '
-                                  'aggregate_results, utils.transforms.resize_align_multi_scale, INTEGRATION.md 3)')
-    if not cfg.TEST.PROJECT2IMAGE:
-        raise NotImplementedError('evaluate: TEST.PROJECT2IMAGE = False is not on the batched path; run the batch-1 '
-                                  'drop-in modules (core.inference.get_multi_stage_outputs + aggregate_results, '
-                                  'INTEGRATION.md 3)')
+def _check_cfg(cfg, engine):
+    """-> the scales in visiting order, or None for the single-scale path (one scale, TEST.PROJECT2IMAGE).  The
+    multi-scale path needs an engine that has it (PoseEngine: tuple inputs of submit, release_scales,
+    ms_workspace_bytes); any other engine object is refused before its device is touched."""
+    order, _ = _inference.scale_order(cfg)
+    if len(order) == 1 and cfg.TEST.PROJECT2IMAGE:
+        return None
+    if not all(callable(getattr(engine, m, None)) for m in ('submit', 'release_scales', 'ms_workspace_bytes')):
+        raise NotImplementedError('evaluate: multi-scale testing (len(TEST.SCALE_FACTOR) > 1) and TEST.PROJECT2IMAGE '
+                                  '= False need an engine with the multi-scale path (PoseEngine.submit with one input '
+                                  'per scale, release_scales); this engine has none.  Run the batch-1 drop-in modules '
+                                  '(core.inference.get_multi_stage_outputs + aggregate_results, INTEGRATION.md 3)')
+    return order
+
+
+def _check_memory(engine, N, sizes):
+    """A multi-scale bucket holds one network workspace per scale in every buffer set: refuse one that cannot fit
+    (``sizes``: (w, h) per scale)."""
+    hw = [(h, w) for w, h in sizes]
+    need = engine.ms_workspace_bytes(N, hw)
+    free, _ = torch.cuda.mem_get_info(engine.device)
+    avail = free + torch.cuda.memory_reserved(engine.device) - torch.cuda.memory_allocated(engine.device)
+    if need <= avail:
+        return
+    lo, hi = 0, N                              # the workspace grows with the batch: largest n that fits
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if engine.ms_workspace_bytes(mid, hw) <= avail:
+            lo = mid
+        else:
+            hi = mid - 1
+    raise ValueError('evaluate: batch_size %d needs %.1f GB of network workspaces for the %d scales %s over %d buffer '
+                     'sets, %.1f GB of device memory is free; the largest batch size that fits is %d'
+                     % (N, need / 1e9, len(sizes), '+'.join('%dx%d' % s for s in sizes), engine.buffer_sets(),
+                        avail / 1e9, lo))
 
 
 def evaluate(engine, images, image_ids=None, batch_size=64, num_joints=None, stats=None):
@@ -198,7 +289,7 @@ def evaluate(engine, images, image_ids=None, batch_size=64, num_joints=None, sta
     image_ids)`` of the reference loop.  ``image_ids`` default: the input positions.  ``stats``: optional dict, filled
     with the bucket histogram and the time split (host packing, waiting for the device, records -> dicts)."""
     cfg = engine.cfg
-    _check_cfg(cfg)
+    scales = _check_cfg(cfg, engine)
     images = [np.ascontiguousarray(im) for im in images]
     for k, im in enumerate(images):
         if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
@@ -211,12 +302,15 @@ def evaluate(engine, images, image_ids=None, batch_size=64, num_joints=None, sta
     t_start = time.perf_counter()
     min_scale = min(cfg.TEST.SCALE_FACTOR)
     input_size = int(cfg.DATASET.INPUT_SIZE)
-    batches = plan([im.shape[:2] for im in images], input_size, min_scale, int(batch_size))
+    batches = plan([im.shape[:2] for im in images], input_size, min_scale, int(batch_size), scales)
     cap = max(sum(images[r].size for r in b.rows[:b.real]) for b in batches)
-    tr = _Transforms(input_size, min_scale)
+    if scales is None:
+        tr = _Transforms(input_size, min_scale)
+    else:
+        tr = _ScaleTransforms(input_size, scales, cfg.TEST.PROJECT2IMAGE)
     for im in images:                        # filled here: the packing worker only reads the cache
         tr((im.shape[0], im.shape[1]))
-    loader = BucketLoader(engine, batch_size, cap, tr)
+    loader = BucketLoader(engine, batch_size, cap, tr, scales=1 if scales is None else len(scales))
     nset = loader.nset
     depth = min(engine.pipeline_depth(), nset - 1)     # a set is refilled only after its last batch was collected
     pcap, J, D = engine.pcap, engine.J, 3 + engine.T
@@ -265,9 +359,15 @@ def evaluate(engine, images, image_ids=None, batch_size=64, num_joints=None, sta
             if k and batches[k - 1].size != b.size:     # a bucket is done: free its buffers and graphs
                 while pend:
                     collect(pend)
-                pw, ph = batches[k - 1].size
-                engine.release_shape(loader.N, ph, pw)
-                loader.x.pop((pw, ph), None)
+                if scales is None:
+                    pw, ph = batches[k - 1].size
+                    engine.release_shape(loader.N, ph, pw)
+                else:
+                    engine.release_scales(loader.N, [(ph, pw) for pw, ph in batches[k - 1].size])
+                for sz in _sizes(batches[k - 1].size):
+                    loader.x.pop(sz, None)
+            if scales is not None and (k == 0 or batches[k - 1].size != b.size):
+                _check_memory(engine, loader.N, b.size)
             x = loader.start(i, b)
             if k + 1 < len(batches):
                 nxt = (k + 1) % nset

@@ -11,8 +11,13 @@ the network, the AE stage, per-image back-projection, records -> result dicts.  
                          device (record read-back), records -> result dicts (Python, per person), total -- which one
                          is the limit
     batch1_img_per_s     the batch-1 drop-in loop (valid.py:195-233 shape) over the first --batch1 images
+    speedup_vs_batch1    img_per_s_warm / batch1_img_per_s
 
-    python tools/eval_mixed.py --images 2048 --batch 64"""
+--scales 0.5,1,2 sets TEST.SCALE_FACTOR (multi-scale testing), --no-project2image TEST.PROJECT2IMAGE = False; both
+legs run the same configuration.
+
+    python tools/eval_mixed.py --images 2048 --batch 64
+    python tools/eval_mixed.py --images 512 --batch 16 --scales 0.5,1,2"""
 import argparse
 import json
 import os
@@ -65,9 +70,13 @@ def main():
     # head gain of the synthetic weights: 1.0 gives a few persons per noise image, 6.0 saturates the grouping
     # (hundreds per image: the Python result formatting then dominates the call)
     ap.add_argument('--head-gain', type=float, default=1.0)
+    ap.add_argument('--scales', default='1', help='TEST.SCALE_FACTOR, comma separated (e.g. 0.5,1,2)')
+    ap.add_argument('--no-project2image', action='store_true', help='TEST.PROJECT2IMAGE = False')
     a = ap.parse_args()
     arch = arch_zoo.get(a.arch)
     cfg = config.apply_arch(config.get_cfg('crowd_pose'), arch)
+    cfg.TEST.SCALE_FACTOR = [float(v) for v in a.scales.split(',')]
+    cfg.TEST.PROJECT2IMAGE = not a.no_project2image
     sd = synth.make_state_dict(arch, seed=1234, head_gain=a.head_gain)
     rng = np.random.default_rng(a.seed)
     pick = rng.integers(0, len(SIZES), size=a.images)
@@ -106,6 +115,8 @@ def main():
         'split_cold_s': {k: round(res['cold'][1][k], 4) for k in ('pack_s', 'wait_pack_s', 'wait_device_s', 'format_s', 'total_s')},
         'graph_stats': eng.graph_stats(),
         'batch1_images': n1, 'batch1_img_per_s': round(n1 / t1, 1),
+        'speedup_vs_batch1': round((len(images) / res['warm'][0]) / (n1 / t1), 2),
+        'scales': list(cfg.TEST.SCALE_FACTOR), 'project2image': bool(cfg.TEST.PROJECT2IMAGE),
     }
     print(json.dumps(line))
 

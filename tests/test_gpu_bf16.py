@@ -15,68 +15,13 @@ import numpy as np
 import pytest
 import torch
 
+from _net_check import BF16_ULP_REL, HEAD_ATOL, _model, _with_option, layerwise_report
 from oracle import group_ref, inference_ref, net_ref, synth
 
 pytestmark = pytest.mark.gpu
 
-BF16_ULP_REL = 2.0 ** -7
-HEAD_ATOL = 2e-5
 BUDGET_FRAC = 0.05           # of max|fp32 output| (hard cap); measured 0.015-0.025; per case additionally <= 2x the
                              # CPU emulation's own distance from fp32 (test_bf16_outputs_vs_fp32_oracle_within_budget)
-
-
-def _cfg():
-    from litepose_amd import config
-    return config.get_cfg('crowd_pose')
-
-
-def _model(arch_name, storage='bf16', seed=1234, head_gain=1.0):
-    from litepose_amd import arch_zoo
-    from litepose_amd.models import pose_mobilenet
-    arch = arch_zoo.get(arch_name)
-    sd = synth.make_state_dict(arch, seed=seed, head_gain=head_gain)
-    m = pose_mobilenet.get_pose_net(_cfg(), is_train=False, cfg_arch=arch, storage=storage)
-    m.load_state_dict(sd, strict=True)
-    return m, arch, sd
-
-
-def _with_option(m, key, value, fn):
-    """Run fn with a kernel-family switch of the net changed (lp_net_set_option), restore it afterwards."""
-    old = m.set_option(key, value)
-    try:
-        return fn()
-    finally:
-        m.set_option(key, old)
-
-
-def layerwise_report(m, arch, sd, x):
-    """Run the device network on x (flip=0), ONE LAUNCH PER OP (option "mbtb" = 0: the fused block kernel keeps the two
-    expanded tensors of a block on the CU, so there would be nothing to compare them with; it has its own test
-    below), and compare every launch with the emulated op on the device's own inputs.
-    Returns [(name, max_abs_diff, worst_ulp_ratio, mismatch_fraction, is_head)]."""
-    # ... and option "stem" = 0: the fused stem (stem4_kernel<C0, true>, round 6) keeps the conv and depthwise outputs in LDS
-    # ... and "headb" = 0: the fused head keeps both depthwise outputs in LDS (it is bit-identical to its three launches)
-    outs = _with_option(m, 'headb', 0, lambda: _with_option(m, 'stem', 0, lambda: _with_option(
-        m, 'mbtb', 0, lambda: [o.cpu() for o in m.forward_native(x.cuda(), 0)])))
-    torch.cuda.synchronize()
-    dev = {'x': x}
-    rows = []
-    k_out = 0
-    with torch.no_grad():
-        for name, ins, fn in net_ref.bf16_plan(sd, arch):
-            exp = fn(*[dev[k] for k in ins])
-            head = name.startswith('final.') and name.endswith('.pw')
-            if head:
-                got = outs[k_out]
-                k_out += 1
-            else:
-                got = m.tap(name).cpu().view(exp.shape)
-            assert got.shape == exp.shape, (name, got.shape, exp.shape)
-            dev[name] = got
-            d = (got - exp).abs()
-            ulp = exp.abs() * BF16_ULP_REL + 1e-6
-            rows.append((name, float(d.max()), float((d / ulp).max()), float((d > 0).float().mean()), head))
-    return rows
 
 
 @pytest.mark.parametrize('arch_name,R,N', [

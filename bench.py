@@ -10,7 +10,12 @@ One "step" = one pass of the whole hot path over one synthetic batch already res
 in HBM (steps are software-pipelined over two HIP streams; K steps = K batches fully completed): network on the batch and on its mirror, flip-TTA merge + projection, NMS/top-k,
 tag grouping, adjust/refine, back-projection, and (N > 1) one RCCL all-gather of the
 per-image keypoint records.  Weak scaling: every rank owns 64 images.  Rank 0 prints
-ONE JSON line.  See DESIGN.md "Measurement" for the roofline / cpu_baseline definitions.
+ONE JSON line.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, --dump-outputs, the line.
+Everything else -- the 200-step region, the parity check against the CPU oracle, the I/O leg, the single- and
+small-batch latencies, path / kernel rooflines, the CPU baseline and BASELINE configs 4 / 5 -- runs with --full.
+See DESIGN.md "Measurement" for the definitions.
 """
 import argparse
 import json
@@ -251,14 +256,14 @@ def release_affinity():
 
 
 def run_extra_config(n, steps, warmup, timeout=240):
-    """BASELINE configs 4 / 5 inside the DEFAULT run: the driver executes only `python bench.py`
-    (+ --gpus / --steps / --warmup), so two of BASELINE.json's five configs were never on a driver record.  After the
-    headline has been measured this process starts `bench.py --config N` as a child with the same steps / warm-up (own
+    """BASELINE configs 4 / 5 inside the `--full` run of the default workload (two of BASELINE.json's
+    five configs were never on a record of the default command).  After the
+    headline has been measured this process starts `bench.py --config N --full` as a child with the same steps / warm-up (own
     process: own engine, own hipGraphs; this process is idle and only keeps its buffers), and the child's whole JSON line
     is condensed to the fields a reviewer needs.  A failure is reported as such and never touches the headline."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), '--config', str(n), '--steps', str(steps), '--warmup', str(warmup),
-           '--no-cpu-baseline', '--no-io-leg', '--no-extra-configs', '--no-small-batch', '--parity-images', '16']
+           '--full', '--no-cpu-baseline', '--no-io-leg', '--no-extra-configs', '--no-small-batch', '--parity-images', '16']
     t0 = time.time()
     try:
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout,
@@ -295,7 +300,7 @@ def condense_child_line(d, n, steps, warmup, wall_s):
                        'oks': p3.get('oks_vs_cpu_persons')},
             'wall_s': wall_s,
             'ms_per_step_200': d.get('ms_per_step_200'),
-            'command': 'python bench.py --config %d --steps %d --warmup %d --no-cpu-baseline --no-io-leg --parity-images 16'
+            'command': 'python bench.py --config %d --steps %d --warmup %d --full --no-cpu-baseline --no-io-leg --parity-images 16'
                        % (n, steps, warmup)}
 
 
@@ -443,7 +448,7 @@ def parity_check(eng, arch, sd, cfg, R, x, offs_np, records, sample, tol=2e-5):
             'ok': bool(same and err < tol)}
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
@@ -475,6 +480,15 @@ def main():
     ap.add_argument('--dump', default='', help='rank 0 saves the gathered records of the last step (npz)')
     ap.add_argument('--dump-outputs', default='', metavar='DIR',
                     help='rank 0 writes the records of the last timed step as float32 DIR/<name>.npy (dump_outputs)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure and check everything else: the --long-steps region, the parity '
+                         'check, the I/O leg, single- and small-batch latencies, path / kernel rooflines, the CPU baseline '
+                         'and (default workload, one rank) BASELINE configs 4 / 5; the --no-* options skip single legs')
+    return ap
+
+
+def main():
+    ap = arg_parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
@@ -603,7 +617,7 @@ def main():
     # a second, longer region: the same loop for --long-steps steps, bracketed the same way, max over
     # ranks -- a low-variance number beside the driver's K-step one, never instead of it
     ms_long = None
-    if args.long_steps > args.steps:
+    if args.full and args.long_steps > args.steps:
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -664,8 +678,8 @@ def main():
         'ms_per_step_200': None if ms_long is None else round(ms_long, 4),
         'long_steps': args.long_steps if ms_long is not None else 0,
     }
-    _log('parity check')
-    if rank == 0 and not args.no_parity_check:
+    if rank == 0 and args.full and not args.no_parity_check:
+        _log('parity check')
         local = (out[0][:B], out[1][:B], out[2][:B])          # rank 0's own shard of the gathered records
         # bf16 storage: the heatmap error against the fp32 oracle is a BUDGET (reported, <= 3e-2 on maps of
         # range ~1; measured ~6e-3), the records must still be bit-exact on the device's own maps
@@ -684,7 +698,7 @@ def main():
     # HWC images in pinned host memory -> H2D (12.5 MB per 64 images) -> lp_preprocess_batch -> the same serving loop
     # -> packed records D2H into pinned memory, pipelined over the same buffer sets on a loader stream.
     io = None
-    if not args.no_io_leg:       # after the dump / parity check: this leg re-uses (overwrites) the engine's buffer sets
+    if args.full and not args.no_io_leg:   # after the dump / parity check: this leg re-uses (overwrites) the engine's buffer sets
         loader = engine.StagedLoader(eng, B, R, R, own_stream=os.environ.get('LP_IO_OWN_STREAM') == '1')
         g = torch.Generator().manual_seed(300 + shard)
         u8 = torch.randint(0, 256, (B, R, R, 3), dtype=torch.uint8, generator=g)
@@ -746,7 +760,7 @@ def main():
     if io is not None:
         line['value_with_io'] = io['value_with_io']
         line['io'] = io
-    if rank == 0:
+    if rank == 0 and args.full:
         # un-pipelined latency of ONE batch (infer_batch, nothing to hide the AE stage behind)
         lat = []
         for _ in range(7):
@@ -767,7 +781,7 @@ def main():
             torch.cuda.synchronize()
             lat_g.append((time.perf_counter() - t1) * 1e3)
         line['latency_ms_single_batch_graph'] = round(sorted(lat_g)[len(lat_g) // 2], 4)
-    if rank == 0 and not args.no_small_batch:
+    if rank == 0 and args.full and not args.no_small_batch:
         # the reference's own operating point (valid.py:195-196 asserts batch 1; VERDICT r05 missing #2): one batch of 1 / 8
         # images through the whole path with nothing else in flight -- submit (two graph replays) -> result -> host sync,
         # median of 25 after the captures; `eager_ms` = the same batch through infer_batch (plain launches)
@@ -802,7 +816,7 @@ def main():
                         '-> result -> synchronize, nothing else in flight, median of 25'
                         % (args.arch.split('-')[-1], R, R, nb, args.storage)}
             _log('latency batch %d: %.4f ms (eager %.4f)' % (nb, med, line['latency_small_batch'][str(nb)]['eager_ms']))
-    if rank == 0:
+    if rank == 0 and args.full:
         b_op, b_post = algorithmic_bytes_per_image(arch, J, R, cfg.TEST.FLIP_TEST,
                                                    act_bytes=4 if args.storage == 'f32' else 2)
         F = 2 if cfg.TEST.FLIP_TEST else 1
@@ -824,8 +838,8 @@ def main():
                        '%.2f GB = %.2f of the HBM peak at this step time' % (real / 1e9, real / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS)
                        if real else 'n/a'),
             'hbm_traffic_bytes_per_step': real, 'traffic_source': tsrc}
-        _log('kernel profile')
         if not args.no_kernel_profile:
+            _log('kernel profile')
             # per-kernel HIP-event timing of the network launches (own pass, outside the timed region)
             m = eng.model
             m.set_profiling(True)
@@ -912,8 +926,8 @@ def main():
                                  ms_per_step, args.storage, mfma_peak=BF16X3_EQUIV_TFLOPS)
                 line['path_roofline']['frac_flops_bf16x3'] = p3['frac_flops']
                 line['path_roofline']['flop_floor_bf16x3'] = p3
-        _log('cpu baseline')
         if world == 1 and not args.no_cpu_baseline:
+            _log('cpu baseline')
             line['cpu_baseline'] = cpu_baseline(arch, sd, cfg, R, args.cpu_images, (off0, off1, f0, f1))
         if world == 1 and default_run and not args.no_extra_configs:
             # the children measure on an otherwise idle GPU: drop this process's engine, graphs and buffers first
@@ -931,6 +945,7 @@ def main():
             for n_cfg in (4, 5):
                 _log('BASELINE config %d (child process)' % n_cfg)
                 line['configs'][str(n_cfg)] = run_extra_config(n_cfg, args.steps, args.warmup)
+    if rank == 0:
         _log('done')
         print(json.dumps(line))
     if world > 1:

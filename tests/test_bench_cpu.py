@@ -295,3 +295,23 @@ def test_dump_outputs_samples_a_fixed_subset_above_64_mb(bench, tmp_path, monkey
     assert total <= bench.DUMP_CAP_BYTES
     bench.dump_outputs(str(tmp_path / 'b'), (kpts, count, scores), 30)
     assert np.array_equal(idx, np.load(str(tmp_path / 'b' / 'image_index.npy')).astype(np.int64))
+
+
+def test_full_is_opt_in_and_reaches_the_config_children(bench, monkeypatch):
+    """A plain run measures the headline only; `--full` (off by default) adds every other leg, and the BASELINE config 4 / 5
+    children of a `--full` run are `--full` runs themselves (their condensed lines need parity, rooflines and kernels)."""
+    import subprocess
+    ap = bench.arg_parser()
+    assert ap.parse_args([]).full is False
+    assert ap.parse_args(['--full', '--steps', '3']).full is True
+    seen = []
+
+    def fake_run(cmd, **kw):
+        seen.append(cmd)
+        return subprocess.CompletedProcess(cmd, 1, '', 'no GPU here')
+    monkeypatch.setattr(subprocess, 'run', fake_run)
+    r = bench.run_extra_config(4, 20, 5)
+    assert r == {'error': 'rc 1: no GPU here'}
+    cmd = seen[0]
+    assert cmd[cmd.index('--config') + 1] == '4' and '--full' in cmd and '--no-extra-configs' in cmd
+    assert cmd[cmd.index('--steps') + 1] == '20' and cmd[cmd.index('--warmup') + 1] == '5'

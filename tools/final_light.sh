@@ -9,8 +9,8 @@ export PYTHONUNBUFFERED=1
 timeout 1200 python -m pytest tests -q -m gpu --timeout 900 > $F/${TAG}_pytest_gpu.log 2>&1; tail -3 $F/${TAG}_pytest_gpu.log
 bash tools/evidence.sh $TAG $C "per forward of 64 images + 64 mirrored, XS@256, fp32" > $F/evidence.log 2>&1
 cp gpurun_out/ev_$TAG/${TAG}_* $F/ 2>/dev/null
-timeout 600 python bench.py > $F/${TAG}_bench_n1.json 2> $F/bench.err
-timeout 400 python bench.py --steps 200 --warmup 10 --no-cpu-baseline --no-extra-configs > $F/${TAG}_bench_n1_200steps.json 2>> $F/bench.err
+timeout 600 python bench.py --full > $F/${TAG}_bench_n1.json 2> $F/bench.err
+timeout 400 python bench.py --full --steps 200 --warmup 10 --no-cpu-baseline --no-extra-configs > $F/${TAG}_bench_n1_200steps.json 2>> $F/bench.err
 timeout 200 python tools/profile_ops.py --all > $F/${TAG}_per_launch.txt 2>&1
 timeout 200 python tools/step_times.py --steps 30 --warmup 5 --stages > $F/${TAG}_step_times.txt 2>&1
 H="python tools/flake_hunt.py --max-report 20"

@@ -7,23 +7,23 @@ F=gpurun_out/final_$TAG
 mkdir -p $F
 export PYTHONUNBUFFERED=1
 timeout 2400 python -m pytest tests -q -m gpu --timeout 1200 > $F/${TAG}_pytest_gpu.log 2>&1; tail -3 $F/${TAG}_pytest_gpu.log
-timeout 900 python bench.py > $F/${TAG}_bench_n1.json 2> $F/bench.err      # the driver's command: headline + BASELINE configs 4 / 5 attached
+timeout 900 python bench.py --full > $F/${TAG}_bench_n1.json 2> $F/bench.err      # the full line: headline, every other leg, BASELINE configs 4 / 5 attached
 bash tools/evidence.sh $TAG $C "per forward of 64 images + 64 mirrored, XS@256, fp32" > $F/evidence.log 2>&1
 cp gpurun_out/ev_$TAG/${TAG}_* $F/ 2>/dev/null
 bash tools/evidence.sh ${TAG}_bf16_S448 $C "per forward of 32 images + 32 mirrored, S@448, bf16 storage" --arch search-S --batch 32 --storage bf16 > $F/evidence_S448.log 2>&1
 cp gpurun_out/ev_${TAG}_bf16_S448/${TAG}_bf16_S448_* $F/ 2>/dev/null
 bash tools/evidence.sh ${TAG}_bf16_M512 $C "per forward of 32 images + 32 mirrored, M@512, bf16 storage" --arch search-M --size 512 --batch 32 --storage bf16 > $F/evidence_M512.log 2>&1
 cp gpurun_out/ev_${TAG}_bf16_M512/${TAG}_bf16_M512_* $F/ 2>/dev/null
-timeout 400 python bench.py --steps 200 --warmup 10 --no-cpu-baseline --no-extra-configs > $F/${TAG}_bench_n1_200steps.json 2>> $F/bench.err
+timeout 400 python bench.py --full --steps 200 --warmup 10 --no-cpu-baseline --no-extra-configs > $F/${TAG}_bench_n1_200steps.json 2>> $F/bench.err
 timeout 200 python tools/profile_ops.py --all > $F/${TAG}_per_launch.txt 2>&1
 timeout 200 python tools/profile_ops.py --all --arch search-S --size 448 --batch 32 --storage bf16 > $F/${TAG}_per_launch_S448_bf16.txt 2>&1
 timeout 200 python tools/profile_ops.py --all --arch search-M --size 512 --batch 32 --storage bf16 > $F/${TAG}_per_launch_M512_bf16.txt 2>&1
 timeout 200 python tools/step_times.py --steps 30 --warmup 5 --stages > $F/${TAG}_step_times.txt 2>&1
 for o in 1 0; do echo "== mbtd=$o" >> $F/${TAG}_mbtd_ab.txt; timeout 200 python tools/profile_ops.py --all --arch search-S --size 448 --batch 32 --storage bf16 --opt mbtd=$o 2>&1 | grep -E "stage.0.1|stage.1.1|^mbt|^total" >> $F/${TAG}_mbtd_ab.txt; timeout 200 python tools/profile_ops.py --all --arch search-M --size 512 --batch 32 --storage bf16 --opt mbtd=$o 2>&1 | grep -E "stage.0.1|stage.1.1|^mbt|^total" >> $F/${TAG}_mbtd_ab.txt; done
 timeout 300 python tools/time_plateau.py 2>&1 | grep lp_parse > $F/${TAG}_plateau.txt
-timeout 400 python bench.py --config 4 --no-cpu-baseline --parity-images 0 > $F/${TAG}_bench_n1_S448_b32_bf16.json 2>> $F/bench.err
-timeout 400 python bench.py --arch search-S --batch 32 --no-cpu-baseline > $F/${TAG}_bench_n1_S448_b32_f32.json 2>> $F/bench.err
-timeout 500 python bench.py --config 5 --no-cpu-baseline --parity-images 0 > $F/${TAG}_bench_n1_M512_b32_bf16.json 2>> $F/bench.err
+timeout 400 python bench.py --full --config 4 --no-cpu-baseline --parity-images 0 > $F/${TAG}_bench_n1_S448_b32_bf16.json 2>> $F/bench.err
+timeout 400 python bench.py --full --arch search-S --batch 32 --no-cpu-baseline > $F/${TAG}_bench_n1_S448_b32_f32.json 2>> $F/bench.err
+timeout 500 python bench.py --full --config 5 --no-cpu-baseline --parity-images 0 > $F/${TAG}_bench_n1_M512_b32_bf16.json 2>> $F/bench.err
 timeout 300 python tools/p3_agreement.py --images 64 > $F/${TAG}_p3_agreement.txt 2>&1
 timeout 300 python tools/p3_agreement.py --images 32 --arch search-S --storage bf16 > $F/${TAG}_p3_agreement_bf16.txt 2>&1
 H="python tools/flake_hunt.py --max-report 20"

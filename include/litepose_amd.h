@@ -91,11 +91,19 @@ int lp_net_finalize(lp_net* net, int strict);
  * network_to_half): LP_STORAGE_BF16 keeps activations ([N][C/8][H*W][8] bf16 records) and weights in
  * bf16, accumulates / applies bias, activation and residual in fp32 and rounds once per stored tensor
  * (round-to-nearest-even); d_x, d_out0 and d_out1 of lp_net_forward stay fp32 planar, lp_net_tap still
- * returns fp32 planar copies.  LP_STORAGE_F32 (default) is the reference's arithmetic.              */
+ * returns fp32 planar copies.  LP_STORAGE_F16 is the same path with IEEE half records and weights --
+ * the format network_to_half itself uses: 3 more mantissa bits than bf16, a range up to 65504
+ * (overflow rounds to +-inf), subnormals kept.  Same layout, same kernels (their fp16 forms), same
+ * shape refusals and the same options as bf16.  LP_STORAGE_F32 (default) is the reference's arithmetic. */
 #define LP_STORAGE_F32 0
 #define LP_STORAGE_BF16 1
+#define LP_STORAGE_F16 2
 int lp_net_set_storage(lp_net* net, int storage);
 int lp_net_get_storage(const lp_net* net);
+/* The host rounding of the 16-bit storage formats (what lp_net_finalize applies to the folded weights):
+ * dst[i] = src[i] rounded to bf16 / fp16 (storage = LP_STORAGE_BF16 / LP_STORAGE_F16), round-to-nearest-
+ * even, subnormals kept, returned as fp32 values.  Host only; for tests.                               */
+int lp_round16(const float* src, float* dst, int64_t count, int storage);
 
 /* Read back an (unfolded) tensor previously set -- backs state_dict().               */
 int lp_net_get_weight(const lp_net* net, const char* key, float* h_data, int64_t numel);
@@ -121,7 +129,8 @@ int lp_net_set_streams(lp_net* net, int k);
 /* Kernel-family switches of one net (round 4: replaces the LP_* environment hooks of rounds 1-3 for the choices a
  * caller -- in practice the parity tests, which compare two forms of one op -- may legitimately make).  Every rule
  * that picks a kernel otherwise depends on the layer shape only, and the defaults are the measured best.  A captured
- * hipGraph bakes the value in: re-capture after a change.  Keys (value 0 / 1 unless noted):
+ * hipGraph bakes the value in: re-capture after a change.  The keys documented as "bf16 storage: ..." select the same
+ * forms, with the same defaults and shape gates, under LP_STORAGE_F16 (their fp16 kernels).  Keys (value 0 / 1 unless noted):
  *   "mb16"       16x16-plane InvBottlenecks in mb16_kernel (default 1; 0: the unfused pw3 / dw_pair16 / pw3 chain)
  *   "mb16_run"   ... a whole run of same-shape residual blocks per launch (default 1; 0: one block per launch)
  *   "mbt"        tiled fused blocks: 0 off, 1 default (32-filter blocks + stride-2 blocks), 2 also the 16-filter

@@ -69,6 +69,7 @@ _SIGS = {
     'lp_net_finalize': (i32, [vp, i32]),
     'lp_net_set_storage': (i32, [vp, i32]),
     'lp_net_get_storage': (i32, [vp]),
+    'lp_round16': (i32, [vp, vp, i64, i32]),
     'lp_net_get_weight': (i32, [vp, C.c_char_p, vp, i64]),
     'lp_net_workspace_bytes': (sz, [vp, i32, i32, i32]),
     'lp_net_forward': (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),

@@ -12,7 +12,11 @@
 // (32 lanes x 16 B = 512 contiguous bytes per octet) and never transposes through LDS; the depthwise convs
 // take an octet per wave and run its four channel pairs as v_pk_fma_f32 against SGPR weight pairs.
 // (The fp32 path keeps planar NCHW: its matrix-core operand is one f32 per lane; see net_kernels.hip.)
+// Round 7, fp16 storage (LP_STORAGE_F16): every kernel below is a __device__ body templated on the 16-bit format F
+// (fmt16.h) with two entry points -- the bf16 one under its original name and template list, and an overload with a
+// leading lp::F16 (e.g. lp::mbtb_kernel<lp::F16, 1, 1, true>); NAME_fn<F, ...>() gives the launcher the entry point of F.
 #include "kernels.h"
+#include "fmt16.h"
 #include "split3.h"
 
 #include <cstdio>
@@ -21,14 +25,6 @@
 namespace lp {
 
 namespace {
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {      // RNE, lo in bits 0-15
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 
 __device__ __forceinline__ int xcd_id(int id, int n) {      // see xcd_contiguous_id (net_kernels.hip)
     const int q = n >> 3, r = n & 7;
@@ -42,7 +38,8 @@ __device__ __forceinline__ int xcd_id(int id, int n) {      // see xcd_contiguou
 // stem: conv 3x3 stride 2 pad 1, 3 -> 32, + bias + ReLU6 on the fp32 image (mirror-on-read for the
 // TTA pass), output in octet layout.  One output pixel per lane, weights wave-uniform.
 // =====================================================================================
-__global__ __launch_bounds__(256) void stemb_kernel(const float* __restrict__ x, const float* __restrict__ w,
+template <class F>
+__device__ __forceinline__ void stemb_kernel_body(const float* __restrict__ x, const float* __restrict__ w,
                                                     const float* __restrict__ b, u32x4* __restrict__ out, int N,
                                                     int H, int W, int flip_from, int x_batch) {
     const int OH = H >> 1, OW = W >> 1;
@@ -82,15 +79,34 @@ __global__ __launch_bounds__(256) void stemb_kernel(const float* __restrict__ x,
             for (int i = 0; i < 27; ++i) acc = fmaf(v[i], w[co * 27 + i], acc);
             y[e] = fminf(fmaxf(acc + b[co], 0.f), 6.f);
         }
-        const u32x4 r = {pack_bf16(y[0], y[1]), pack_bf16(y[2], y[3]), pack_bf16(y[4], y[5]), pack_bf16(y[6], y[7])};
+        const u32x4 r = {F::pack(y[0], y[1]), F::pack(y[2], y[3]), F::pack(y[4], y[5]), F::pack(y[6], y[7])};
         o[(long)oc * OH * OW] = r;
     }
 }
 
+__global__ __launch_bounds__(256) void stemb_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                    const float* __restrict__ b, u32x4* __restrict__ out, int N,
+                                                    int H, int W, int flip_from, int x_batch) {
+    stemb_kernel_body<Bf16>(x, w, b, out, N, H, W, flip_from, x_batch);
+}
+template <class F>
+__global__ __launch_bounds__(256) void stemb_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                    const float* __restrict__ b, u32x4* __restrict__ out, int N,
+                                                    int H, int W, int flip_from, int x_batch) {
+    stemb_kernel_body<F>(x, w, b, out, N, H, W, flip_from, x_batch);
+}
+// the entry point of format F (bf16: the original function)
+template <class F>
+inline auto stemb_kernel_fn() {
+    if constexpr (F::is_f16) return &stemb_kernel<F>;
+    else return static_cast<decltype(&stemb_kernel<F16>)>(stemb_kernel);
+}
+
+
 void launch_stemb(const float* x, const float* w, const float* b, void* out, int N, int H, int W, int flip_from,
-                  int x_batch, hipStream_t s) {
+                  int x_batch, hipStream_t s, bool f16) {
     const long total = (long)N * (H / 2) * (W / 2);
-    LP_LAUNCH(stemb_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, w, b, (u32x4*)out, N,
+    LP_LAUNCH((f16 ? stemb_kernel_fn<F16>() : stemb_kernel_fn<Bf16>()), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, w, b, (u32x4*)out, N,
                        H, W, flip_from, x_batch);
     last_kernel_tag = "stemb_kernel";
 }
@@ -127,8 +143,8 @@ struct DwbGeom {
     static constexpr int LDS_BYTES = WAVE_SLOTS * 16;         // per wave
 };
 
-template <int K, int S>
-__global__ __launch_bounds__(256) void dwb_kernel(const u32x4* __restrict__ in, const f32x4* __restrict__ w,
+template <class F, int K, int S>
+__device__ __forceinline__ void dwb_kernel_body(const u32x4* __restrict__ in, const f32x4* __restrict__ w,
                                                   u32x4* __restrict__ out, int C8, int H, int W, int OH, int OW,
                                                   int tilesX, int tilesY, int act, int units, int tpw, int xcd_remap) {
     using G = DwbGeom<K, S>;
@@ -182,8 +198,8 @@ __global__ __launch_bounds__(256) void dwb_kernel(const u32x4* __restrict__ in, 
             if (e < NC) {
                 const int r = e / G::TIW, q = e - r * G::TIW;
                 const u32x4 v = pre[i];
-                const f32x4 lo4 = {bf_lo(v[0]), bf_hi(v[0]), bf_lo(v[1]), bf_hi(v[1])};
-                const f32x4 hi4 = {bf_lo(v[2]), bf_hi(v[2]), bf_lo(v[3]), bf_hi(v[3])};
+                const f32x4 lo4 = {F::lo(v[0]), F::hi(v[0]), F::lo(v[1]), F::hi(v[1])};
+                const f32x4 hi4 = {F::lo(v[2]), F::hi(v[2]), F::lo(v[3]), F::hi(v[3])};
                 const int qs = S == 1 ? q : (q >> 1) + (q & 1) * G::PAR;
                 tile[r * G::TWP + qs] = lo4;
                 tile[G::SLOTS + r * G::TWP + qs] = hi4;
@@ -252,7 +268,7 @@ __global__ __launch_bounds__(256) void dwb_kernel(const u32x4* __restrict__ in, 
                     u32x4 r;
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
-                        r[q] = pack_bf16(fminf(fmaxf(acc[j][q][0], lo), hi), fminf(fmaxf(acc[j][q][1], lo), hi));
+                        r[q] = F::pack(fminf(fmaxf(acc[j][q][0], lo), hi), fminf(fmaxf(acc[j][q][1], lo), hi));
                     o[j] = r;
                 }
             }
@@ -265,6 +281,26 @@ __global__ __launch_bounds__(256) void dwb_kernel(const u32x4* __restrict__ in, 
 }
 
 template <int K, int S>
+__global__ __launch_bounds__(256) void dwb_kernel(const u32x4* __restrict__ in, const f32x4* __restrict__ w,
+                                                  u32x4* __restrict__ out, int C8, int H, int W, int OH, int OW,
+                                                  int tilesX, int tilesY, int act, int units, int tpw, int xcd_remap) {
+    dwb_kernel_body<Bf16, K, S>(in, w, out, C8, H, W, OH, OW, tilesX, tilesY, act, units, tpw, xcd_remap);
+}
+template <class F, int K, int S>
+__global__ __launch_bounds__(256) void dwb_kernel(const u32x4* __restrict__ in, const f32x4* __restrict__ w,
+                                                  u32x4* __restrict__ out, int C8, int H, int W, int OH, int OW,
+                                                  int tilesX, int tilesY, int act, int units, int tpw, int xcd_remap) {
+    dwb_kernel_body<F, K, S>(in, w, out, C8, H, W, OH, OW, tilesX, tilesY, act, units, tpw, xcd_remap);
+}
+// the entry point of format F (bf16: the original template)
+template <class F, int K, int S>
+inline auto dwb_kernel_fn() {
+    if constexpr (F::is_f16) return &dwb_kernel<F, K, S>;
+    else return &dwb_kernel<K, S>;
+}
+
+
+template <class F, int K, int S>
 static void launch_dwb_t(const void* in, const float* w, void* out, int N, int C, int H, int W, int act,
                          hipStream_t s) {
     using G = DwbGeom<K, S>;
@@ -277,22 +313,23 @@ static void launch_dwb_t(const void* in, const float* w, void* out, int N, int C
     const unsigned grid = (unsigned)((units + 4L * tpw - 1) / (4L * tpw));
     static bool attr_done = false;
     if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)dwb_kernel<K, S>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void*)dwb_kernel_fn<F, K, S>(), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   4 * G::LDS_BYTES);
         attr_done = true;
     }
-    LP_LAUNCH((dwb_kernel<K, S>), dim3(grid), dim3(256), 4 * G::LDS_BYTES, s, (const u32x4*)in,
+    LP_LAUNCH((dwb_kernel_fn<F, K, S>()), dim3(grid), dim3(256), 4 * G::LDS_BYTES, s, (const u32x4*)in,
                        (const f32x4*)w, (u32x4*)out, C / 8, H, W, OH, OW, tilesX, tilesY, act, (int)units, tpw,
                        (xr && tilesX * tilesY > 4) ? 1 : 0);
 }
 
 bool launch_dwb(const void* in, const float* w, void* out, int N, int C, int H, int W, int K, int S, int act,
-                hipStream_t s) {
+                hipStream_t s, bool f16) {
     if (C % 8 || (long)N * (C / 8) * ((W + 7) / 8) * ((H + 7) / 8) > 0x7fffffffL) return false;
     last_kernel_tag = K == 7 ? (S == 1 ? "dwb_kernel<7,1>" : "dwb_kernel<7,2>")
                              : (K == 5 ? (S == 1 ? "dwb_kernel<5,1>" : "dwb_kernel<5,2>")
                                        : (S == 1 ? "dwb_kernel<3,1>" : "dwb_kernel<3,2>"));
-#define LP_DWB(KV, SV) launch_dwb_t<KV, SV>(in, w, out, N, C, H, W, act, s)
+#define LP_DWB(KV, SV) \
+    (f16 ? launch_dwb_t<F16, KV, SV>(in, w, out, N, C, H, W, act, s) : launch_dwb_t<Bf16, KV, SV>(in, w, out, N, C, H, W, act, s))
     if (K == 7 && S == 1) LP_DWB(7, 1);
     else if (K == 7 && S == 2) LP_DWB(7, 2);
     else if (K == 5 && S == 1) LP_DWB(5, 1);
@@ -330,8 +367,8 @@ template <int K> struct DwtGeom {
     static constexpr int LDS_IN = 8 * PLANE * 2, LDS_OUT = 4 * 256 * 16;       // bytes
 };
 
-template <int K>
-__global__ __launch_bounds__(256) void dwt_kernel(const u32x4* __restrict__ in, const u32x4* __restrict__ wt,
+template <class F, int K>
+__device__ __forceinline__ void dwt_kernel_body(const u32x4* __restrict__ in, const u32x4* __restrict__ wt,
                                                   const float* __restrict__ wb,   // [C/8][K*K + 1][8]: taps, then bias
                                                   u32x4* __restrict__ out, int C8, int H, int W, int regsX,
                                                   int regsY, int act, int xcd_remap) {
@@ -412,15 +449,13 @@ __global__ __launch_bounds__(256) void dwt_kernel(const u32x4* __restrict__ in, 
         for (int ky = 0; ky < K; ++ky) {
             const u32x4 fa = *reinterpret_cast<const u32x4*>(a0 + cA * G::PLANE + ky * DWT_RW);
             const u32x4 fb = *reinterpret_cast<const u32x4*>(a0 + (cA + 1) * G::PLANE + ky * DWT_RW);
-            dA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, fa),
-                                                         __builtin_bit_cast(bf16x8_t, BA[ky]), dA, 0, 0, 0);
-            dB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, fb),
-                                                         __builtin_bit_cast(bf16x8_t, BB[ky]), dB, 0, 0, 0);
+            dA = F::mfma16(fa, BA[ky], dA);
+            dB = F::mfma16(fb, BB[ky], dB);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j)        // D: row 4 kg + j, col m16; dword `wave` of the record = channels 2w, 2w+1
             O[(tile * 256 + (4 * kg + j) * 16 + m16) * 4 + wave] =
-                pack_bf16(fminf(fmaxf(dA[j], lo), hi), fminf(fmaxf(dB[j], lo), hi));
+                F::pack(fminf(fmaxf(dA[j], lo), hi), fminf(fmaxf(dB[j], lo), hi));
     }
     __syncthreads();
     // ---- wave w stores tile w: whole records, 256 contiguous bytes per tile row ---------------------------
@@ -434,8 +469,28 @@ __global__ __launch_bounds__(256) void dwt_kernel(const u32x4* __restrict__ in, 
     }
 }
 
+template <int K>
+__global__ __launch_bounds__(256) void dwt_kernel(
+    const u32x4* __restrict__ in, const u32x4* __restrict__ wt, const float* __restrict__ wb,
+    u32x4* __restrict__ out, int C8, int H, int W, int regsX, int regsY, int act, int xcd_remap) {
+    dwt_kernel_body<Bf16, K>(in, wt, wb, out, C8, H, W, regsX, regsY, act, xcd_remap);
+}
+template <class F, int K>
+__global__ __launch_bounds__(256) void dwt_kernel(
+    const u32x4* __restrict__ in, const u32x4* __restrict__ wt, const float* __restrict__ wb,
+    u32x4* __restrict__ out, int C8, int H, int W, int regsX, int regsY, int act, int xcd_remap) {
+    dwt_kernel_body<F, K>(in, wt, wb, out, C8, H, W, regsX, regsY, act, xcd_remap);
+}
+// the entry point of format F (bf16: the original template)
+template <class F, int K>
+inline auto dwt_kernel_fn() {
+    if constexpr (F::is_f16) return &dwt_kernel<F, K>;
+    else return &dwt_kernel<K>;
+}
+
+
 bool launch_dwt(const void* in, const void* wt, const float* wb, void* out, int N, int C, int H, int W, int K, int act,
-                hipStream_t s) {
+                hipStream_t s, bool f16) {
     if (C % 8 || !wt || (K != 7 && K != 5)) return false;
     // measured 1.7-1.8x of dwb_kernel per computed pixel (7x7, profiles/r02_dwt_first_run.txt), but a 32x32 region on
     // a 16x16 plane is 75 % padding (0.8x there): taken when its padded area is at most 1.5x that of dwb's 16x16
@@ -448,11 +503,11 @@ bool launch_dwt(const void* in, const void* wt, const float* wb, void* out, int 
     const int remap = (xr && regsX * regsY > 4) ? 1 : 0;
     if (K == 7) {
         last_kernel_tag = "dwt_kernel<7>";
-        LP_LAUNCH(dwt_kernel<7>, dim3((unsigned)units), dim3(256), DwtGeom<7>::LDS_IN + DwtGeom<7>::LDS_OUT, s,
+        LP_LAUNCH((f16 ? dwt_kernel_fn<F16, 7>() : dwt_kernel_fn<Bf16, 7>()), dim3((unsigned)units), dim3(256), DwtGeom<7>::LDS_IN + DwtGeom<7>::LDS_OUT, s,
                            (const u32x4*)in, (const u32x4*)wt, wb, (u32x4*)out, C / 8, H, W, regsX, regsY, act, remap);
     } else {            // 5x5 (the two output heads): the same kernel, 5 MFMAs per channel and tile; NOT run on hardware
         last_kernel_tag = "dwt_kernel<5>";
-        LP_LAUNCH(dwt_kernel<5>, dim3((unsigned)units), dim3(256), DwtGeom<5>::LDS_IN + DwtGeom<5>::LDS_OUT, s,
+        LP_LAUNCH((f16 ? dwt_kernel_fn<F16, 5>() : dwt_kernel_fn<Bf16, 5>()), dim3((unsigned)units), dim3(256), DwtGeom<5>::LDS_IN + DwtGeom<5>::LDS_OUT, s,
                            (const u32x4*)in, (const u32x4*)wt, wb, (u32x4*)out, C / 8, H, W, regsX, regsY, act, remap);
     }
     return true;
@@ -474,7 +529,8 @@ bool launch_dwt(const void* in, const void* wt, const float* wb, void* out, int 
 // requested before the current octet's MFMAs.  60 KB of LDS, two workgroups per CU.  Cout <= 32 (CrowdPose: 28 / 14; the
 // COCO heads' 34-filter stage keeps the chain).
 // =====================================================================================
-__global__ __launch_bounds__(256, 2) void headb_kernel(
+template <class F>
+__device__ __forceinline__ void headb_kernel_body(
     const u32x4* __restrict__ inA, int Ca8, const u32x4* __restrict__ inB, int Cb8,
     const u32x4* __restrict__ wtA, const float* __restrict__ wbA,     // dwt_kernel's fragments / [C/8][26][8] taps + bias
     const u32x4* __restrict__ wtB, const float* __restrict__ wbB,
@@ -582,15 +638,13 @@ __global__ __launch_bounds__(256, 2) void headb_kernel(
                 for (int ky = 0; ky < K; ++ky) {
                     const u32x4 fa = *reinterpret_cast<const u32x4*>(a0 + cA * G::PLANE + ky * DWT_RW);
                     const u32x4 fb = *reinterpret_cast<const u32x4*>(a0 + (cA + 1) * G::PLANE + ky * DWT_RW);
-                    dA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, fa),
-                                                                 __builtin_bit_cast(bf16x8_t, BA[ky]), dA, 0, 0, 0);
-                    dB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, fb),
-                                                                 __builtin_bit_cast(bf16x8_t, BB[ky]), dB, 0, 0, 0);
+                    dA = F::mfma16(fa, BA[ky], dA);
+                    dB = F::mfma16(fb, BB[ky], dB);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j)    // D: row 4 kg + j, col m16; dword `wave` of the record = channels 2w, 2w+1; ReLU
                     O[hf * 4096 + (tile * 256 + (4 * kg + j) * 16 + m16) * 4 + wave] =
-                        pack_bf16(fmaxf(dA[j], 0.f), fmaxf(dB[j], 0.f));
+                        F::pack(fmaxf(dA[j], 0.f), fmaxf(dB[j], 0.f));
             }
             __syncthreads();                                   // O[hf] complete, the planes are free again
         }
@@ -599,8 +653,7 @@ __global__ __launch_bounds__(256, 2) void headb_kernel(
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
             const u32x4 b = *reinterpret_cast<const u32x4*>(O + half * 4096 + ((wave * 8 + g) * 32 + pl) * 4);
-            acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                            __builtin_bit_cast(bf16x8_t, b), acc[g], 0, 0, 0);
+            acc[g] = F::mfma32(a, b, acc[g]);
         }
         __syncthreads();                                       // the next k-step overwrites O
     }
@@ -620,8 +673,32 @@ __global__ __launch_bounds__(256, 2) void headb_kernel(
     }
 }
 
+__global__ __launch_bounds__(256, 2) void headb_kernel(
+    const u32x4* __restrict__ inA, int Ca8, const u32x4* __restrict__ inB, int Cb8,
+    const u32x4* __restrict__ wtA, const float* __restrict__ wbA, const u32x4* __restrict__ wtB,
+    const float* __restrict__ wbB, const u32x4* __restrict__ wf, float* __restrict__ out, int H, int W,
+    int regsX, int regsY, int Cout, int xcd_remap) {
+    headb_kernel_body<Bf16>(inA, Ca8, inB, Cb8, wtA, wbA, wtB, wbB, wf, out, H, W, regsX, regsY, Cout, xcd_remap);
+}
+template <class F>
+__global__ __launch_bounds__(256, 2) void headb_kernel(
+    const u32x4* __restrict__ inA, int Ca8, const u32x4* __restrict__ inB, int Cb8,
+    const u32x4* __restrict__ wtA, const float* __restrict__ wbA, const u32x4* __restrict__ wtB,
+    const float* __restrict__ wbB, const u32x4* __restrict__ wf, float* __restrict__ out, int H, int W,
+    int regsX, int regsY, int Cout, int xcd_remap) {
+    headb_kernel_body<F>(inA, Ca8, inB, Cb8, wtA, wbA, wtB, wbB, wf, out, H, W, regsX, regsY, Cout, xcd_remap);
+}
+// the entry point of format F (bf16: the original function)
+template <class F>
+inline auto headb_kernel_fn() {
+    if constexpr (F::is_f16) return &headb_kernel<F>;
+    else return static_cast<decltype(&headb_kernel<F16>)>(headb_kernel);
+}
+
+
 bool launch_headb(const void* inA, int Ca, const void* inB, int Cb, const void* wtA, const float* wbA, const void* wtB,
-                  const float* wbB, const void* wf, float* out, int N, int H, int W, int K, int Cout, hipStream_t s) {
+                  const float* wbB, const void* wf, float* out, int N, int H, int W, int K, int Cout, hipStream_t s,
+                  bool f16) {
     if (K != 5 || (Ca % 8) || (Cb % 8) || Ca < 8 || Cb < 8 || Cout > 32 || !wtA || !wtB || !wf) return false;
     // dwt_kernel's own shape rule (32 x 32 regions must not be mostly padding)
     const int regsX = (W + 31) / 32, regsY = (H + 31) / 32;
@@ -632,11 +709,12 @@ bool launch_headb(const void* inA, int Ca, const void* inB, int Cb, const void* 
     const size_t lds = DwtGeom<5>::LDS_IN + 2 * DwtGeom<5>::LDS_OUT;
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(headb_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(headb_kernel_fn<Bf16>()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(headb_kernel_fn<F16>()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr = true;
     }
     last_kernel_tag = "headb_kernel";
-    LP_LAUNCH(headb_kernel, dim3((unsigned)units), dim3(256), lds, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8,
+    LP_LAUNCH((f16 ? headb_kernel_fn<F16>() : headb_kernel_fn<Bf16>()), dim3((unsigned)units), dim3(256), lds, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8,
               (const u32x4*)wtA, wbA, (const u32x4*)wtB, wbB, (const u32x4*)wf, out, H, W, regsX, regsY, Cout, remap);
     return true;
 }
@@ -656,8 +734,8 @@ bool launch_headb(const void* inA, int Ca, const void* inB, int Cb, const void* 
 // accumulators in AGPRs on top of a full VGPR set and every variant ends at one wave per SIMD)
 constexpr int pwb_min_blocks(int nb, int pxv) { return nb * pxv <= 4 ? 4 : (nb * pxv <= 6 ? 3 : (nb * pxv <= 8 ? 2 : 1)); }
 
-template <int NB, int PXV, bool RES, bool OUTF32>
-__global__ __launch_bounds__(256, pwb_min_blocks(NB, PXV)) void pwb_kernel(const u32x4* __restrict__ inA, int Ca8,
+template <class F, int NB, int PXV, bool RES, bool OUTF32>
+__device__ __forceinline__ void pwb_kernel_body(const u32x4* __restrict__ inA, int Ca8,
                                                   const u32x4* __restrict__ inB, int Cb8,
                                                   const u32x4* __restrict__ wf,     // [cblocks][KS][64] x 16 B
                                                   const float* __restrict__ bias,   // [cblocks][2][16] D-frag order
@@ -715,9 +793,7 @@ __global__ __launch_bounds__(256, pwb_min_blocks(NB, PXV)) void pwb_kernel(const
         for (int i = 0; i < NB; ++i)
 #pragma unroll
             for (int v = 0; v < PXV; ++v)
-                acc[i][v] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, aq[i]),
-                                                                    __builtin_bit_cast(bf16x8_t, bq[v]), acc[i][v], 0,
-                                                                    0, 0);
+                acc[i][v] = F::mfma32(aq[i], bq[v], acc[i][v]);
         if (more) {
 #pragma unroll
             for (int v = 0; v < PXV; ++v) bq[v] = bn[v];
@@ -770,13 +846,13 @@ __global__ __launch_bounds__(256, pwb_min_blocks(NB, PXV)) void pwb_kernel(const
                 for (int e = 0; e < 4; ++e) y[e] = fminf(fmaxf(acc[i][v][4 * q + e] + bb[e], lo), hi);
                 if (RES) {
                     const uint2 rr = res[(rec + v) * 2 + half];
-                    y[0] += bf_lo(rr.x);
-                    y[1] += bf_hi(rr.x);
-                    y[2] += bf_lo(rr.y);
-                    y[3] += bf_hi(rr.y);
+                    y[0] += F::lo(rr.x);
+                    y[1] += F::hi(rr.x);
+                    y[2] += F::lo(rr.y);
+                    y[3] += F::hi(rr.y);
                 }
-                x[v][0] = pack_bf16(y[0], y[1]);
-                x[v][1] = pack_bf16(y[2], y[3]);
+                x[v][0] = F::pack(y[0], y[1]);
+                x[v][1] = F::pack(y[2], y[3]);
             }
 #pragma unroll
             for (int v = 0; v < PXV; v += 2) {
@@ -790,14 +866,36 @@ __global__ __launch_bounds__(256, pwb_min_blocks(NB, PXV)) void pwb_kernel(const
     }
 }
 
-template <int NB, int PXV>
+template <int NB, int PXV, bool RES, bool OUTF32>
+__global__ __launch_bounds__(256, pwb_min_blocks(NB, PXV)) void pwb_kernel(
+    const u32x4* __restrict__ inA, int Ca8, const u32x4* __restrict__ inB, int Cb8, const u32x4* __restrict__ wf,
+    const float* __restrict__ bias, const uint2* __restrict__ res, void* __restrict__ outv, long NG, int HWV,
+    int HW, int Cout, int act) {
+    pwb_kernel_body<Bf16, NB, PXV, RES, OUTF32>(inA, Ca8, inB, Cb8, wf, bias, res, outv, NG, HWV, HW, Cout, act);
+}
+template <class F, int NB, int PXV, bool RES, bool OUTF32>
+__global__ __launch_bounds__(256, pwb_min_blocks(NB, PXV)) void pwb_kernel(
+    const u32x4* __restrict__ inA, int Ca8, const u32x4* __restrict__ inB, int Cb8, const u32x4* __restrict__ wf,
+    const float* __restrict__ bias, const uint2* __restrict__ res, void* __restrict__ outv, long NG, int HWV,
+    int HW, int Cout, int act) {
+    pwb_kernel_body<F, NB, PXV, RES, OUTF32>(inA, Ca8, inB, Cb8, wf, bias, res, outv, NG, HWV, HW, Cout, act);
+}
+// the entry point of format F (bf16: the original template)
+template <class F, int NB, int PXV, bool RES, bool OUTF32>
+inline auto pwb_kernel_fn() {
+    if constexpr (F::is_f16) return &pwb_kernel<F, NB, PXV, RES, OUTF32>;
+    else return &pwb_kernel<NB, PXV, RES, OUTF32>;
+}
+
+
+template <class F, int NB, int PXV>
 static void launch_pwb_t(const void* inA, int Ca, const void* inB, int Cb, const void* wf, const float* bias,
                          const void* res, void* out, long NP, int HW, int Cout, int act, bool out_f32, hipStream_t s) {
     const long NG = NP / PXV;
     const int cblocks = (Cout + 31) / 32;
     dim3 grid((unsigned)((NG + 127) / 128), (cblocks + NB - 1) / NB), block(256);
 #define LP_PWB(RESV, F32V)                                                                                          \
-    LP_LAUNCH((pwb_kernel<NB, PXV, RESV, F32V>), grid, block, 0, s, (const u32x4*)inA, Ca / 8,              \
+    LP_LAUNCH((pwb_kernel_fn<F, NB, PXV, RESV, F32V>()), grid, block, 0, s, (const u32x4*)inA, Ca / 8,              \
                        (const u32x4*)inB, Cb / 8, (const u32x4*)wf, bias, (const uint2*)res, out, NG, HW / PXV, HW, \
                        Cout, act)
     if (out_f32) LP_PWB(false, true);
@@ -807,7 +905,7 @@ static void launch_pwb_t(const void* inA, int Ca, const void* inB, int Cb, const
 }
 
 bool launch_pwb(const void* inA, int Ca, const void* inB, int Cb, const void* wf, const float* bias, const void* res,
-                void* out, int N, int HW, int Cout, int act, bool out_f32, hipStream_t s) {
+                void* out, int N, int HW, int Cout, int act, bool out_f32, hipStream_t s, bool f16) {
     if ((Ca % 8) || (Cb % 8) || (HW % 2) || (!out_f32 && (Cout % 8)) || (out_f32 && res)) return false;
     const long NP = (long)N * HW;
     const int cblocks = (Cout + 31) / 32;
@@ -818,7 +916,9 @@ bool launch_pwb(const void* inA, int Ca, const void* inB, int Cb, const void* wf
     if (PXV == 4 && ((NP / 4 + 31) / 32) * ((cblocks + NB - 1) / NB) < 2048) PXV = 2;
     if (PXV == 4 && NB >= 3) NB = 2;                              // 192 accumulator registers: one wave per SIMD
     last_kernel_tag = "pwb_kernel";
-#define LP_GO(NBV, PV) launch_pwb_t<NBV, PV>(inA, Ca, inB, Cb, wf, bias, res, out, NP, HW, Cout, act, out_f32, s)
+#define LP_GO(NBV, PV)                                                                                                  \
+    (f16 ? launch_pwb_t<F16, NBV, PV>(inA, Ca, inB, Cb, wf, bias, res, out, NP, HW, Cout, act, out_f32, s)                  \
+         : launch_pwb_t<Bf16, NBV, PV>(inA, Ca, inB, Cb, wf, bias, res, out, NP, HW, Cout, act, out_f32, s))
     if (PXV == 4) { if (NB >= 2) LP_GO(2, 4); else LP_GO(1, 4); }
     else { if (NB >= 3) LP_GO(3, 2); else if (NB == 2) LP_GO(2, 2); else LP_GO(1, 2); }
 #undef LP_GO
@@ -834,8 +934,8 @@ bool launch_pwb(const void* inA, int Ca, const void* inB, int Cb, const void* wf
 // Epilogue: a lane holds its half-octet of the 2x2 output quad of its cell; v_permlane32_swap pairs the two
 // horizontally adjacent pixels across the wave halves, so every lane stores whole 16-byte records.
 // =====================================================================================
-template <int NB>
-__global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconvb_kernel(const u32x4* __restrict__ inA, int Ca8,
+template <class F, int NB>
+__device__ __forceinline__ void deconvb_kernel_body(const u32x4* __restrict__ inA, int Ca8,
                                                       const u32x4* __restrict__ inB, int Cb8,
                                                       const u32x4* __restrict__ wf, const float* __restrict__ bias,
                                                       u32x4* __restrict__ out, long NP, int h, int w_, int Cout,
@@ -895,9 +995,7 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconvb_kernel(const u32
                     const int dy = a == 0 ? (tyi == 0 ? 0 : -1) : (tyi == 0 ? 1 : 0);
                     const int dx = b == 0 ? (txi == 0 ? 0 : -1) : (txi == 0 ? 1 : 0);
                     const u32x4 av = wl[((long)((i * 4 + q) * 4 + t) * KS + ks) * 64];
-                    acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                        __builtin_bit_cast(bf16x8_t, av), __builtin_bit_cast(bf16x8_t, bv[(dy + 1) * 3 + dx + 1]),
-                        acc[i][q], 0, 0, 0);
+                    acc[i][q] = F::mfma32(av, bv[(dy + 1) * 3 + dx + 1], acc[i][q]);
                 }
         }
 #pragma unroll
@@ -921,8 +1019,8 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconvb_kernel(const u32
                     float y[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) y[e] = fmaxf(acc[i][a * 2 + b][4 * q8 + e] + bb[e], 0.f);
-                    x[b][0] = pack_bf16(y[0], y[1]);
-                    x[b][1] = pack_bf16(y[2], y[3]);
+                    x[b][0] = F::pack(y[0], y[1]);
+                    x[b][1] = F::pack(y[2], y[3]);
                 }
                 const auto s0 = __builtin_amdgcn_permlane32_swap(x[0][0], x[1][0], false, false);
                 const auto s1 = __builtin_amdgcn_permlane32_swap(x[0][1], x[1][1], false, false);
@@ -933,24 +1031,49 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconvb_kernel(const u32
     }
 }
 
+template <int NB>
+__global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconvb_kernel(const u32x4* __restrict__ inA, int Ca8,
+                                                      const u32x4* __restrict__ inB, int Cb8,
+                                                      const u32x4* __restrict__ wf, const float* __restrict__ bias,
+                                                      u32x4* __restrict__ out, long NP, int h, int w_, int Cout,
+                                                      int xcd_remap) {
+    deconvb_kernel_body<Bf16, NB>(inA, Ca8, inB, Cb8, wf, bias, out, NP, h, w_, Cout, xcd_remap);
+}
+template <class F, int NB>
+__global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconvb_kernel(const u32x4* __restrict__ inA, int Ca8,
+                                                      const u32x4* __restrict__ inB, int Cb8,
+                                                      const u32x4* __restrict__ wf, const float* __restrict__ bias,
+                                                      u32x4* __restrict__ out, long NP, int h, int w_, int Cout,
+                                                      int xcd_remap) {
+    deconvb_kernel_body<F, NB>(inA, Ca8, inB, Cb8, wf, bias, out, NP, h, w_, Cout, xcd_remap);
+}
+// the entry point of format F (bf16: the original template)
+template <class F, int NB>
+inline auto deconvb_kernel_fn() {
+    if constexpr (F::is_f16) return &deconvb_kernel<F, NB>;
+    else return &deconvb_kernel<NB>;
+}
+
+
 bool launch_deconvb(const void* inA, int Ca, const void* inB, int Cb, const void* wf, const float* bias, void* out,
-                    int N, int h, int w_, int Cout, hipStream_t s) {
+                    int N, int h, int w_, int Cout, hipStream_t s, bool f16) {
     if ((Ca % 8) || (Cb % 8) || (Cout % 8) || Cout > 64) return false;
     const long NP = (long)N * h * w_;
     dim3 grid((unsigned)((NP + 127) / 128)), block(256);
     constexpr int xr = 1;                                            // tiles dealt XCD-contiguously
     if (Cout <= 32)
-        LP_LAUNCH(deconvb_kernel<1>, grid, block, 0, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8,
+        LP_LAUNCH((f16 ? deconvb_kernel_fn<F16, 1>() : deconvb_kernel_fn<Bf16, 1>()), grid, block, 0, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8,
                            (const u32x4*)wf, bias, (u32x4*)out, NP, h, w_, Cout, xr);
     else
-        LP_LAUNCH(deconvb_kernel<2>, grid, block, 0, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8,
+        LP_LAUNCH((f16 ? deconvb_kernel_fn<F16, 2>() : deconvb_kernel_fn<Bf16, 2>()), grid, block, 0, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8,
                            (const u32x4*)wf, bias, (u32x4*)out, NP, h, w_, Cout, xr);
     last_kernel_tag = "deconvb_kernel";
     return true;
 }
 
 // octet bf16 [N][C/8][HW][8] -> planar fp32 [N][C][HW] (lp_net_tap of the bf16 path; not on the hot path)
-__global__ __launch_bounds__(256) void octet_to_planar_kernel(const u32x4* __restrict__ in, float* __restrict__ out,
+template <class F>
+__device__ __forceinline__ void octet_to_planar_kernel_body(const u32x4* __restrict__ in, float* __restrict__ out,
                                                               long total, int C8, int HW) {
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= total) return;
@@ -962,14 +1085,31 @@ __global__ __launch_bounds__(256) void octet_to_planar_kernel(const u32x4* __res
     float* o = out + ((n * C8 + oc) * 8) * HW + p;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        o[(long)(2 * j) * HW] = bf_lo(v[j]);
-        o[(long)(2 * j + 1) * HW] = bf_hi(v[j]);
+        o[(long)(2 * j) * HW] = F::lo(v[j]);
+        o[(long)(2 * j + 1) * HW] = F::hi(v[j]);
     }
 }
 
-void launch_octet_to_planar(const void* in, float* out, int N, int C, int HW, hipStream_t s) {
+__global__ __launch_bounds__(256) void octet_to_planar_kernel(const u32x4* __restrict__ in, float* __restrict__ out,
+                                                              long total, int C8, int HW) {
+    octet_to_planar_kernel_body<Bf16>(in, out, total, C8, HW);
+}
+template <class F>
+__global__ __launch_bounds__(256) void octet_to_planar_kernel(const u32x4* __restrict__ in, float* __restrict__ out,
+                                                              long total, int C8, int HW) {
+    octet_to_planar_kernel_body<F>(in, out, total, C8, HW);
+}
+// the entry point of format F (bf16: the original function)
+template <class F>
+inline auto octet_to_planar_kernel_fn() {
+    if constexpr (F::is_f16) return &octet_to_planar_kernel<F>;
+    else return static_cast<decltype(&octet_to_planar_kernel<F16>)>(octet_to_planar_kernel);
+}
+
+
+void launch_octet_to_planar(const void* in, float* out, int N, int C, int HW, hipStream_t s, bool f16) {
     const long total = (long)N * (C / 8) * HW;
-    LP_LAUNCH(octet_to_planar_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
+    LP_LAUNCH((f16 ? octet_to_planar_kernel_fn<F16>() : octet_to_planar_kernel_fn<Bf16>()), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
                        (const u32x4*)in, out, total, C / 8, HW);
 }
 

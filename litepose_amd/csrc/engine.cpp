@@ -602,8 +602,9 @@ int build_plan(lp_net* n) {
 
 
 // ---------------------------------------------------------------------------------------------------
-// bf16 storage: folded weights are rounded to bf16 (round-to-nearest-even, like v_cvt_pk_bf16_f32 and
-// torch's .to(bfloat16)); biases stay fp32.  oracle/net_ref.py:forward_bf16 restates the same numerics.
+// 16-bit storage (bf16 or fp16): folded weights are rounded to the storage format (round-to-nearest-even,
+// like v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 and torch's .to(bfloat16) / .to(float16)); biases stay fp32.
+// oracle/net_ref.py:forward_bf16 restates the bf16 numerics, tests/_f16_ref.py the fp16 ones.
 // ---------------------------------------------------------------------------------------------------
 uint16_t bf16_rne(float x) {
     uint32_t u;
@@ -618,8 +619,28 @@ float bf16_round(float x) {
     std::memcpy(&r, &u, 4);
     return r;
 }
+// IEEE half: the compiler's float -> _Float16 conversion rounds to nearest even, overflows to +-inf and keeps
+// subnormals (as tensor.to(torch.float16) does); tests/test_f16_cpu.py checks it through lp_round16.  The float is read
+// through a volatile: inlined into a caller that computes it as (float)(double), clang folds double -> float -> half
+// into ONE double -> half conversion (__truncdfhf2), which rounds a folded weight that is an exact fp16 tie as a float
+// the other way than torch's .to(float16) of the float does (double rounding is not rounding)
+uint16_t f16_rne(float x) {
+    volatile float v = x;
+    const _Float16 h = (_Float16)v;
+    uint16_t u;
+    std::memcpy(&u, &h, 2);
+    return u;
+}
+float f16_round(float x) {
+    volatile float v = x;
+    return (float)(_Float16)v;
+}
+// the rounding of the net's storage format: the bits of one 16-bit record element / its value as fp32
+uint16_t rne16(const lp_net* n, float x) { return n->storage == LP_STORAGE_F16 ? f16_rne(x) : bf16_rne(x); }
+float round16(const lp_net* n, float x) { return n->storage == LP_STORAGE_F16 ? f16_round(x) : bf16_round(x); }
+const char* storage_name(const lp_net* n) { return n->storage == LP_STORAGE_F16 ? "f16" : "bf16"; }
 
-// conv [Cout][rest] + BN -> bf16-rounded fp32 values; octet = true: depthwise weights as [C/8][rest][8]
+// conv [Cout][rest] + BN -> fp32 values rounded to the storage format; octet = true: depthwise weights as [C/8][rest][8]
 void pack_conv_bn_b(lp_net* n, const std::string& wkey, const std::string& bnkey, BOp& op, bool octet) {
     const Tensor& w = T(n, wkey);
     std::vector<double> sc, sh;
@@ -630,7 +651,7 @@ void pack_conv_bn_b(lp_net* n, const std::string& wkey, const std::string& bnkey
         for (int64_t o = 0; o < co; ++o) {
             for (int64_t r = 0; r < rest; ++r)
                 n->h_packed[op.w_off + (size_t)((o >> 3) * (rest + 1) + r) * 8 + (o & 7)] =
-                    bf16_round((float)((double)w.data[o * rest + r] * sc[o]));
+                    round16(n, (float)((double)w.data[o * rest + r] * sc[o]));
             n->h_packed[op.w_off + (size_t)((o >> 3) * (rest + 1) + rest) * 8 + (o & 7)] = (float)sh[o];
         }
         return;
@@ -638,7 +659,7 @@ void pack_conv_bn_b(lp_net* n, const std::string& wkey, const std::string& bnkey
     op.w_off = arena_push(n->h_packed, (size_t)w.numel());
     for (int64_t o = 0; o < co; ++o)
         for (int64_t r = 0; r < rest; ++r)
-            n->h_packed[op.w_off + (size_t)(o * rest + r)] = bf16_round((float)((double)w.data[o * rest + r] * sc[o]));
+            n->h_packed[op.w_off + (size_t)(o * rest + r)] = round16(n, (float)((double)w.data[o * rest + r] * sc[o]));
     op.b_off = arena_push(n->h_packed, (size_t)co);
     for (int64_t o = 0; o < co; ++o) n->h_packed[op.b_off + o] = (float)sh[o];
 }
@@ -652,7 +673,7 @@ void pack_dwt(lp_net* n, BOp& op) {
     uint32_t* d = reinterpret_cast<uint32_t*>(n->h_packed.data() + op.wt_off);
     auto tap = [&](int c, int ky, int kx) -> uint32_t {
         if (kx < 0 || kx >= K) return 0u;
-        return (uint32_t)bf16_rne(n->h_packed[op.w_off + (size_t)((c >> 3) * KK1 + ky * K + kx) * 8 + (c & 7)]);
+        return (uint32_t)rne16(n, n->h_packed[op.w_off + (size_t)((c >> 3) * KK1 + ky * K + kx) * 8 + (c & 7)]);
     };
     for (int c = 0; c < C; ++c)
         for (int ky = 0; ky < K; ++ky)
@@ -694,7 +715,7 @@ void pack_wrow_d(lp_net* n, BOp& op) {
         const int chunk = c >> 5, kp = (c & 31) >> 1, ab = c & 1;
         auto tap = [&](int ky, int kx) -> uint32_t {
             if (kx < 0 || kx > 6) return 0u;
-            return (uint32_t)bf16_rne(n->h_packed[src + (size_t)(ky * 7 + kx) * 8]);
+            return (uint32_t)rne16(n, n->h_packed[src + (size_t)(ky * 7 + kx) * 8]);
         };
         for (int ky = 0; ky < 7; ++ky) {
             uint32_t* r = d + ((size_t)chunk * 448 + kp * 28 + ky * 4 + 2 * ab) * 4;
@@ -737,7 +758,7 @@ void pack_pwb(lp_net* n, const std::vector<const Tensor*>& ws, const std::vector
                 for (int dq = 0; dq < 4; ++dq) {
                     const int co = cb * 32 + (l & 31), k = ks * 16 + 8 * (l >> 5) + 2 * dq;
                     d[(((size_t)cb * KS + ks) * 64 + l) * 4 + dq] =
-                        (uint32_t)bf16_rne(wval(co, k)) | ((uint32_t)bf16_rne(wval(co, k + 1)) << 16);
+                        (uint32_t)rne16(n, wval(co, k)) | ((uint32_t)rne16(n, wval(co, k + 1)) << 16);
                 }
     op.b_off = arena_push(n->h_packed, (size_t)cblocks * 32);
     for (int cb = 0; cb < cblocks; ++cb)
@@ -774,8 +795,8 @@ void pack_deconvb(lp_net* n, const Tensor& wr, const Tensor& ww, const std::vect
                         for (int dq = 0; dq < 4; ++dq) {
                             const int co = cb * 32 + (l & 31), ci = ks * 16 + 8 * (l >> 5) + 2 * dq;
                             d[(((((size_t)cb * 4 + par) * 4 + t) * KS + ks) * 64 + l) * 4 + dq] =
-                                (uint32_t)bf16_rne(wval(ci, co, ky, kx)) |
-                                ((uint32_t)bf16_rne(wval(ci + 1, co, ky, kx)) << 16);
+                                (uint32_t)rne16(n, wval(ci, co, ky, kx)) |
+                                ((uint32_t)rne16(n, wval(ci + 1, co, ky, kx)) << 16);
                         }
             }
     op.b_off = arena_push(n->h_packed, (size_t)nb * 32);
@@ -830,7 +851,7 @@ int build_plan_bf16(lp_net* n) {
             st.st_w2 = arena_push(n->h_packed, (size_t)32 * c0);
             for (int co = 0; co < c0; ++co)
                 for (int k = 0; k < 32; ++k)
-                    n->h_packed[st.st_w2 + (size_t)k * c0 + co] = bf16_round((float)((double)w2.data[(size_t)co * 32 + k] * sc[co]));
+                    n->h_packed[st.st_w2 + (size_t)k * c0 + co] = round16(n, (float)((double)w2.data[(size_t)co * 32 + k] * sc[co]));
             st.st_b2 = arena_push(n->h_packed, (size_t)c0);
             for (int co = 0; co < c0; ++co) n->h_packed[st.st_b2 + co] = (float)sh[co];
         }
@@ -873,7 +894,7 @@ int build_plan_bf16(lp_net* n) {
     for (size_t i = 0; i < n->deconv.size(); ++i) {
         const Deconv& dc = n->deconv[i];
         const std::string si = std::to_string(i);
-        if (dc.out > 64) return fail(LP_ERR_UNSUPPORTED, "bf16 storage: deconv filters > 64 are not supported");
+        if (dc.out > 64) return fail(LP_ERR_UNSUPPORTED, std::string(storage_name(n)) + " storage: deconv filters > 64 are not supported");
         const int odiv = rdiv / 2;
         const int bR = new_buf(n, dc.out, odiv);
         BOp o; o.type = BOP_DECONV; o.name = "deconv." + si; o.inA = refined; o.inB = raw; o.out = bR;
@@ -1091,7 +1112,7 @@ int lp_net_finalize(lp_net* n, int strict) {
             if (bn_scale) t.data.assign((size_t)t.numel(), 1.f);
         }
     }
-    int rc = n->storage == LP_STORAGE_BF16 ? build_plan_bf16(n) : build_plan(n);
+    int rc = n->storage != LP_STORAGE_F32 ? build_plan_bf16(n) : build_plan(n);
     if (rc != LP_OK) return rc;
     if (n->d_weights) { (void)hipFree(n->d_weights); n->d_weights = nullptr; }
     HIP_OK(hipMalloc((void**)&n->d_weights, n->h_packed.size() * sizeof(float)));
@@ -1106,7 +1127,7 @@ size_t lp_net_workspace_bytes(const lp_net* n, int N, int H, int W) {
     // Buffers are planned one-per-tensor (no aliasing): 288 GB of HBM make the ~6x
     // over-allocation irrelevant and every block-boundary tensor stays tappable.
     size_t f = 0;
-    if (n->storage == LP_STORAGE_BF16) {
+    if (n->storage != LP_STORAGE_F32) {
         for (size_t b = 0; b < n->bufs.ch.size(); ++b) f += buf_elems(n, (int)b, N, H, W);
         return f * sizeof(uint16_t) + 256;
     }
@@ -1135,12 +1156,13 @@ int lp_net_profile_launches(const lp_net* n, int32_t* grid_wgs, int32_t* wg_thre
 
 namespace {
 
-// lp_net_forward for LP_STORAGE_BF16: same launch order, stream fan-out and profiling contract as the fp32 path
+// lp_net_forward for LP_STORAGE_BF16 / LP_STORAGE_F16: same launch order, stream fan-out and profiling contract as the fp32 path
 int forward_bf16(lp_net* n, const float* d_x, int N, int H, int W, int flip, float* d_out0, float* d_out1, void* ws,
                  size_t ws_bytes, hipStream_t s) {
     const int NB = flip == 2 ? 2 * N : N;
     if (ws_bytes < lp_net_workspace_bytes(n, NB, H, W) || ((uintptr_t)ws & 255))
         return fail(LP_ERR_WORKSPACE, "workspace too small or not 256-byte aligned");
+    const bool f16 = n->storage == LP_STORAGE_F16;      // every launch below takes the format last
     const size_t nbuf = n->bufs.ch.size();
     std::vector<char*> ptr(nbuf);
     std::vector<int> esz(nbuf, 2);
@@ -1186,7 +1208,7 @@ int forward_bf16(lp_net* n, const float* d_x, int N, int H, int W, int flip, flo
                     lp::launch_mbtb(ptr[o.inA], Wt + o.w_off, Wt + o.b_off, Wt + dw.wrow_off, Wt + pw.w_off,
                                     Wt + pw.b_off, pw.res >= 0 ? ptr[pw.res] : nullptr, ptr[pw.out], NBp, o.Ca, o.Cout,
                                     pw.Cout, ih, iw, dw.K, dw.S, s, n->opt_mbtb, n->opt_mbtb_s2, n->opt_mbtq,
-                                    dw.wrow2_off ? Wt + dw.wrow2_off : nullptr, n->opt_mbtd)) {
+                                    dw.wrow2_off ? Wt + dw.wrow2_off : nullptr, n->opt_mbtd, f16)) {
                     if (n->profiling) {
                         hipError_t e = hipEventRecord(n->events[n->prof_ev + 1], s);
                         if (e != hipSuccess) return fail(LP_ERR_HIP, hipGetErrorString(e));
@@ -1210,7 +1232,7 @@ int forward_bf16(lp_net* n, const float* d_x, int N, int H, int W, int flip, flo
                 const BOp& pw = n->bops[bi + 2];
                 if (dw.type == BOP_DW && dw.K == 3 && dw.S == 1 && pw.type == BOP_PW && pw.inA == dw.out && !pw.out_f32 &&
                     lp::launch_stem3b(xsrc, Wt + o.st_w0, Wt + o.b_off, Wt + o.st_w1, Wt + o.st_b1, Wt + o.st_w2,
-                                      Wt + o.st_b2, ptr[pw.out], NBp, H, W, pw.Cout, flip_from, x_batch, s)) {
+                                      Wt + o.st_b2, ptr[pw.out], NBp, H, W, pw.Cout, flip_from, x_batch, s, f16)) {
                     if (n->profiling) {
                         hipError_t e = hipEventRecord(n->events[n->prof_ev + 1], s);
                         if (e != hipSuccess) return fail(LP_ERR_HIP, hipGetErrorString(e));
@@ -1240,7 +1262,7 @@ int forward_bf16(lp_net* n, const float* d_x, int N, int H, int W, int flip, flo
                     pw.act == lp::ACT_NONE && pw.res < 0 &&
                     lp::launch_headb(ptr[o.inA], o.Ca, ptr[d2.inA], d2.Ca, Wt + o.wt_off, Wt + o.w_off, Wt + d2.wt_off,
                                      Wt + d2.w_off, Wt + pw.w_off, reinterpret_cast<float*>(ptr[pw.out]), NBp, ih, iw, o.K,
-                                     pw.Cout, s)) {
+                                     pw.Cout, s, f16)) {
                     if (n->profiling) {
                         hipError_t e = hipEventRecord(n->events[n->prof_ev + 1], s);
                         if (e != hipSuccess) return fail(LP_ERR_HIP, hipGetErrorString(e));
@@ -1258,7 +1280,7 @@ int forward_bf16(lp_net* n, const float* d_x, int N, int H, int W, int flip, flo
             }
             switch (o.type) {
                 case BOP_STEM:
-                    lp::launch_stemb(xsrc, Wt + o.w_off, Wt + o.b_off, ptr[o.out], NBp, H, W, flip_from, x_batch, s);
+                    lp::launch_stemb(xsrc, Wt + o.w_off, Wt + o.b_off, ptr[o.out], NBp, H, W, flip_from, x_batch, s, f16);
                     by = (int64_t)NBp * (12ll * H * W + 64ll * oh * ow);
                     fl = 2ll * NBp * 32 * 27 * oh * ow;
                     break;
@@ -1272,10 +1294,10 @@ int forward_bf16(lp_net* n, const float* d_x, int N, int H, int W, int flip, flo
                         const int dwt = n->opt_dwt;
                         ok = dwt && o.wt_off && o.S == 1 && (o.K == 7 || (o.K == 5 && dwt >= 2)) &&
                              lp::launch_dwt(ptr[o.inA], Wt + o.wt_off, Wt + o.w_off, ptr[o.out], NBp, o.Ca, ih, iw,
-                                            o.K, o.act, s);
+                                            o.K, o.act, s, f16);
                         if (!ok)
                             ok = lp::launch_dwb(ptr[o.inA], Wt + o.w_off, ptr[o.out], NBp, o.Ca, ih, iw, o.K, o.S,
-                                                o.act, s);
+                                                o.act, s, f16);
                     }
                     by = 2ll * NBp * o.Ca * ((int64_t)ih * iw + (int64_t)oh * ow);
                     fl = 2ll * NBp * o.Ca * o.K * o.K * oh * ow;
@@ -1283,19 +1305,19 @@ int forward_bf16(lp_net* n, const float* d_x, int N, int H, int W, int flip, flo
                 case BOP_PW:
                     ok = lp::launch_pwb(ptr[o.inA], o.Ca, o.inB >= 0 ? ptr[o.inB] : nullptr, o.Cb, Wt + o.w_off,
                                         Wt + o.b_off, o.res >= 0 ? ptr[o.res] : nullptr, ptr[o.out], NBp, oh * ow,
-                                        o.Cout, o.act, o.out_f32, s);
+                                        o.Cout, o.act, o.out_f32, s, f16);
                     by = (int64_t)NBp * oh * ow *
                          (2ll * (o.Ca + o.Cb) + (o.out_f32 ? 4ll : 2ll) * o.Cout + (o.res >= 0 ? 2ll * o.Cout : 0));
                     fl = 2ll * NBp * oh * ow * (int64_t)(o.Ca + o.Cb) * o.Cout;
                     break;
                 case BOP_DECONV:
                     ok = lp::launch_deconvb(ptr[o.inA], o.Ca, ptr[o.inB], o.Cb, Wt + o.w_off, Wt + o.b_off, ptr[o.out],
-                                            NBp, ih, iw, o.Cout, s);
+                                            NBp, ih, iw, o.Cout, s, f16);
                     by = 2ll * NBp * ((int64_t)(o.Ca + o.Cb) * ih * iw + (int64_t)o.Cout * oh * ow);
                     fl = 2ll * NBp * (int64_t)(o.Ca + o.Cb) * o.Cout * 4 * oh * ow;
                     break;
             }
-            if (!ok) return fail(LP_ERR_UNSUPPORTED, "bf16 storage: unsupported layer shape at " + o.name);
+            if (!ok) return fail(LP_ERR_UNSUPPORTED, std::string(storage_name(n)) + " storage: unsupported layer shape at " + o.name);
             stored[o.out] = 1;
             if (n->profiling) {
                 hipError_t e = hipEventRecord(n->events[n->prof_ev + 1], s);
@@ -1366,7 +1388,7 @@ int lp_net_forward(lp_net* n, const float* d_x, int N, int H, int W, int flip, f
     // a stale error of this thread (e.g. a hipGraph capture that another thread's call invalidated) must not be
     // mistaken for a failure of the launches below
     (void)hipGetLastError();
-    if (n->storage == LP_STORAGE_BF16)
+    if (n->storage != LP_STORAGE_F32)
         return forward_bf16(n, d_x, N, H, W, flip, d_out0, d_out1, ws, ws_bytes, (hipStream_t)stream);
     const int NB = flip == 2 ? 2 * N : N;             // images through the network
     if (ws_bytes < lp_net_workspace_bytes(n, NB, H, W) || ((uintptr_t)ws & 255))
@@ -1664,7 +1686,7 @@ int lp_net_forward(lp_net* n, const float* d_x, int N, int H, int W, int flip, f
 
 int64_t lp_net_tap(const lp_net* n, const char* name, float* d_dst, void* stream) {
     if (!n || !name || n->last_ptr.empty()) return fail(LP_ERR_INVALID_ARG, "no forward has run");
-    if (n->storage == LP_STORAGE_BF16) {
+    if (n->storage != LP_STORAGE_F32) {
         for (const BOp& o : n->bops) {
             if (o.out_f32 || (o.tap != name && o.name != name)) continue;
             if ((size_t)o.out >= n->last_stored_b.size() || !n->last_stored_b[o.out])
@@ -1675,7 +1697,7 @@ int64_t lp_net_tap(const lp_net* n, const char* name, float* d_dst, void* stream
             const int64_t cnt = (int64_t)n->lastN * n->bufs.ch[o.out] * hw;
             if (d_dst)
                 lp::launch_octet_to_planar(n->last_ptr_b[o.out], d_dst, n->lastN, n->bufs.ch[o.out], hw,
-                                           (hipStream_t)stream);
+                                           (hipStream_t)stream, n->storage == LP_STORAGE_F16);
             return cnt;
         }
         return fail(LP_ERR_UNKNOWN_KEY, std::string("unknown tap ") + name);
@@ -1697,7 +1719,7 @@ int64_t lp_net_tap(const lp_net* n, const char* name, float* d_dst, void* stream
 
 int64_t lp_net_tap_offset(const lp_net* n, const char* name, int NB, int H, int W, int64_t* count) {
     if (!n || !name || !n->finalized) return fail(LP_ERR_INVALID_ARG, "net not finalized");
-    if (n->storage == LP_STORAGE_BF16) return fail(LP_ERR_UNSUPPORTED, "fp32 storage only");
+    if (n->storage != LP_STORAGE_F32) return fail(LP_ERR_UNSUPPORTED, "fp32 storage only");
     for (const Op& o : n->ops) {
         if (o.tap == name || o.name == name) {
             if (o.out == n->out0_buf || o.out == n->out1_buf) return fail(LP_ERR_UNSUPPORTED, "caller-owned output");
@@ -1712,8 +1734,8 @@ int64_t lp_net_tap_offset(const lp_net* n, const char* name, int NB, int H, int 
 }
 
 int lp_net_set_storage(lp_net* n, int storage) {
-    if (!n || (storage != LP_STORAGE_F32 && storage != LP_STORAGE_BF16))
-        return fail(LP_ERR_INVALID_ARG, "storage must be LP_STORAGE_F32 or LP_STORAGE_BF16");
+    if (!n || (storage != LP_STORAGE_F32 && storage != LP_STORAGE_BF16 && storage != LP_STORAGE_F16))
+        return fail(LP_ERR_INVALID_ARG, "storage must be LP_STORAGE_F32, LP_STORAGE_BF16 or LP_STORAGE_F16");
     if (storage != n->storage) {
         n->storage = storage;
         n->finalized = false;
@@ -1723,6 +1745,14 @@ int lp_net_set_storage(lp_net* n, int storage) {
 }
 
 int lp_net_get_storage(const lp_net* n) { return n ? n->storage : LP_ERR_INVALID_ARG; }
+
+int lp_round16(const float* src, float* dst, int64_t count, int storage) {
+    if ((!src || !dst) && count > 0) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (storage != LP_STORAGE_BF16 && storage != LP_STORAGE_F16)
+        return fail(LP_ERR_INVALID_ARG, "storage must be LP_STORAGE_BF16 or LP_STORAGE_F16");
+    for (int64_t i = 0; i < count; ++i) dst[i] = storage == LP_STORAGE_F16 ? f16_round(src[i]) : bf16_round(src[i]);
+    return LP_OK;
+}
 
 typedef lp_net::OptEntryT OptEntry;
 const std::vector<OptEntry>& lp_net::options() {

@@ -76,7 +76,7 @@ bool launch_stem3(const float* x, const float* w0t, const float* b0, const float
 // stemb / dwb<3,1> / pwb chain stores rounded at the same place, output as octet-planar bf16 records
 bool launch_stem3b(const float* x, const float* w0t, const float* b0, const float* w1t, const float* b1,
                    const float* w2t, const float* b2, void* out, int N, int H, int W, int c0, int flip_from,
-                   int x_batch, hipStream_t s);
+                   int x_batch, hipStream_t s, bool f16 = false);
 
 // depthwise KxK, stride S, pad K/2, + bias + act.  w [C][K*K], wdup [C][K*K][2] (every tap twice: the stride-1 kernels
 // take (w, w) as an aligned scalar pair of their packed FMAs, engine.cpp pack_dw_dup), b [C].
@@ -156,27 +156,31 @@ bool launch_deconv4x3(const float* inA, int Ca, const float* inB, int Cb, const 
 void launch_deconv_mfma(const float* inA, int Ca, const float* inB, int Cb, const float* wp,
                         const float* bias, float* out, int N, int h, int w_, int Cout, hipStream_t s);
 
-// ---- network, bf16 storage (octet-planar [N][C/8][HW][8] bf16; bf16_kernels.hip) ----
+// ---- network, 16-bit storage (octet-planar [N][C/8][HW][8] bf16 or fp16; bf16_kernels.hip, mbtile_bf16.hip) ----
+// Every launcher below takes the storage format last: f16 = false (default) runs the bf16 kernels, true their IEEE-half
+// forms (the same templates with a leading lp::F16 argument, fmt16.h): same shape rules, same refusals, same last_kernel_tag.
+// The weight arrays hold values rounded to the launch's format (engine.cpp rne16).
 // stem on the fp32 image; w [32][27] fp32 (bf16-rounded values), b [32]
 void launch_stemb(const float* x, const float* w, const float* b, void* out, int N, int H, int W, int flip_from,
-                  int x_batch, hipStream_t s);
+                  int x_batch, hipStream_t s, bool f16 = false);
 // depthwise; w [C/8][K*K + 1][8] fp32: taps (bf16-rounded values), then the bias octet.  false = not supported
 // depthwise 7x7 / 5x5 stride 1 as banded matrix products on v_mfma_f32_16x16x32_bf16 (option "dwt": 0 never, 1 the 7x7
 // ones, 2 (default) also the heads' 5x5).
 // wt: Toeplitz B fragments [C][K filter rows][64 lanes] x 16 B (pack_dwt); wb: the octet taps + bias array of dwb
 bool launch_dwt(const void* in, const void* wt, const float* wb, void* out, int N, int C, int H, int W, int K, int act,
-                hipStream_t s);
+                hipStream_t s, bool f16 = false);
 bool launch_dwb(const void* in, const float* w, void* out, int N, int C, int H, int W, int K, int S, int act,
-                hipStream_t s);
+                hipStream_t s, bool f16 = false);
 // 1x1 over up to two octet sources; wf = bf16 A fragments [ceil(Cout/32)][ceil((Ca+Cb)/16)][64 lanes] x 16 B,
 // bias in D-fragment order [ceil(Cout/32)][2][16]; out: octet bf16 (res: same layout) or fp32 planar (out_f32)
 bool launch_pwb(const void* inA, int Ca, const void* inB, int Cb, const void* wf, const float* bias, const void* res,
-                void* out, int N, int HW, int Cout, int act, bool out_f32, hipStream_t s);
+                void* out, int N, int HW, int Cout, int act, bool out_f32, hipStream_t s, bool f16 = false);
 // an output head of the bf16-storage network in one launch (round 6; bf16_kernels.hip): dwt_kernel<5> on both sources + the
 // dual-source 1x1 with fp32 planar output; wtA / wbA, wtB / wbB = the two depthwise ops' dwt fragments and tap / bias blocks, wf =
 // pwb's A fragments of the head's 1x1.  false = shape not taken (Cout > 32, small planes) -> the three launches
 bool launch_headb(const void* inA, int Ca, const void* inB, int Cb, const void* wtA, const float* wbA, const void* wtB,
-                  const float* wbB, const void* wf, float* out, int N, int H, int W, int K, int Cout, hipStream_t s);
+                  const float* wbB, const void* wf, float* out, int N, int H, int W, int K, int Cout, hipStream_t s,
+                  bool f16 = false);
 // whole 7x7 InvBottleneck (stride 1: mbtb_kernel; stride 2: mbtb_s2_kernel) on octet records in one launch
 // (mbtile_bf16.hip): w1 / b1f and w2 / b2f are the expand's and the project's pwb arrays, wrow = pack_wrow_b's filter
 // rows; res = x or null; H, W = the INPUT plane.  false = shape not taken (the caller runs the pwb / dwt|dwb / pwb
@@ -185,7 +189,8 @@ bool launch_headb(const void* inA, int Ca, const void* inB, int Cb, const void* 
 // bit-identical to mbtb_kernel -- 1: expanded width <= 160 and >= 1024 tiles, 2: whenever the shape fits, 0: never
 bool launch_mbtb(const void* x, const void* w1, const float* b1f, const void* wrow, const void* w2, const float* b2f,
                  const void* res, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int K, int S,
-                 hipStream_t s, int mode = 1, int mode_s2 = 1, int mode_q = 1, const void* wrow2 = nullptr, int mode_d = 1);
+                 hipStream_t s, int mode = 1, int mode_s2 = 1, int mode_q = 1, const void* wrow2 = nullptr, int mode_d = 1,
+                 bool f16 = false);
 // phase trace of mbtb_kernel / mbtq_kernel (`trace` flavour; mbtile_bf16.hip): 64 words per workgroup
 // (8 waves x 8 slots) of the launches selected by wg_trace_read; -2 = not in this library
 int phase_trace_read(unsigned long long* host, int nwg);
@@ -193,8 +198,8 @@ int phase_trace_read(unsigned long long* host, int nwg);
 int wg_trace_read(unsigned long long* host, int nwg, int sel);
 // fused pair of ConvTranspose2d(k4,s2,p1) + add + BN + ReLU; wf [block][parity][tap][ks][64 lanes] x 16 B
 bool launch_deconvb(const void* inA, int Ca, const void* inB, int Cb, const void* wf, const float* bias, void* out,
-                    int N, int h, int w_, int Cout, hipStream_t s);
-void launch_octet_to_planar(const void* in, float* out, int N, int C, int HW, hipStream_t s);
+                    int N, int h, int w_, int Cout, hipStream_t s, bool f16 = false);
+void launch_octet_to_planar(const void* in, float* out, int N, int C, int HW, hipStream_t s, bool f16 = false);
 
 // ---- associative-embedding post-process -------------------------------------------
 struct ParseParams {

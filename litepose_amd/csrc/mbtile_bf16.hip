@@ -27,8 +27,12 @@
 //     expand's bias is the MFMA accumulator's initial value and its zero padding a per-lane upper ReLU bound
 //   * output: the D fragment gives a lane 4 channels (its half of an octet record) of its pixel: 8-byte stores, the
 //     two halves of a wave complete every record in the same instruction
+// Round 7, fp16 storage (LP_STORAGE_F16): every kernel below is a __device__ body templated on the 16-bit format F
+// (fmt16.h) with two entry points -- the bf16 one under its original name and template list, and an overload with a
+// leading lp::F16 (e.g. lp::mbtb_kernel<lp::F16, 1, 1, true>); NAME_fn<F, ...>() gives the launcher the entry point of F.
 #include "kernels.h"
 #include "dw7.h"
+#include "fmt16.h"
 #include "split3.h"
 
 #include <cstdlib>
@@ -125,14 +129,6 @@ template <int CK, int NMT> struct TBW {
     static constexpr size_t LDS_BYTES = (size_t)(TB_E_FLOATS + TB_D_DWORDS) * 4 + (size_t)(NTOT + N4) * 16;
 };
 
-__device__ __forceinline__ unsigned tb_pack_bf16(float lo, float hi) {   // RNE, lo in bits 0-15 (v_cvt_pk_bf16_f32)
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float tb_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float tb_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-
 __device__ __forceinline__ int tb_xcd_contiguous_id(int id, int n) {     // see net_kernels.hip
     const int q = n >> 3, r = n & 7;
     const int xcd = id & 7, slot = id >> 3;
@@ -141,8 +137,8 @@ __device__ __forceinline__ int tb_xcd_contiguous_id(int id, int n) {     // see 
 
 }  // namespace
 
-template <int CK, int NMT, bool RES>
-__global__ __launch_bounds__(512, 2) void mbtb_kernel(
+template <class F, int CK, int NMT, bool RES>
+__device__ __forceinline__ void mbtb_kernel_body(
     const u32x4* __restrict__ x,        // [N][Ci8][H*W] records of 8 bf16 channels
     const u32x4* __restrict__ w1,       // expand A fragments [ceil(Cexp/32)][CK][64]            (pack_pwb)
     const float* __restrict__ b1f,      // expand bias, D-fragment order [ceil(Cexp/32)][2][16]
@@ -270,21 +266,19 @@ __global__ __launch_bounds__(512, 2) void mbtb_kernel(
         }
 #pragma unroll
         for (int gi = 0; gi < 2; ++gi) {
-            f32x16 d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[0]),
-                                                               __builtin_bit_cast(bf16x8_t, xb[gi][0]), bias, 0, 0, 0);
+            f32x16 d = F::mfma32(a[0], xb[gi][0], bias);
 #pragma unroll
             for (int ks = 1; ks < CK; ++ks)
-                d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[ks]),
-                                                            __builtin_bit_cast(bf16x8_t, xb[gi][ks]), d, 0, 0, 0);
+                d = F::mfma32(a[ks], xb[gi][ks], d);
             if (ein[gi]) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
 #pragma unroll
                     for (int e = 0; e < 4; e += 2) {                 // registers 4q+e, 4q+e+1 = channels cc, cc+1
                         const int cc = 4 * half + e + 8 * q;
-                        const unsigned pk = tb_pack_bf16(__builtin_amdgcn_fmed3f(d[4 * q + e], 0.f, hi6[gi]),
+                        const unsigned pk = F::pack(__builtin_amdgcn_fmed3f(d[4 * q + e], 0.f, hi6[gi]),
                                                          __builtin_amdgcn_fmed3f(d[4 * q + e + 1], 0.f, hi6[gi]));
-                        *reinterpret_cast<f32x2*>(E + (cc >> 1) * TB_PAIR + ecell[gi]) = f32x2{tb_lo(pk), tb_hi(pk)};
+                        *reinterpret_cast<f32x2*>(E + (cc >> 1) * TB_PAIR + ecell[gi]) = f32x2{F::lo(pk), F::hi(pk)};
                     }
             }
         }
@@ -313,8 +307,8 @@ __global__ __launch_bounds__(512, 2) void mbtb_kernel(
             u32x4 o0, o1;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                o0[i] = tb_pack_bf16(fminf(fmaxf(a0[i][0] + b0, 0.f), 6.f), fminf(fmaxf(a0[i][1] + b1, 0.f), 6.f));
-                o1[i] = tb_pack_bf16(fminf(fmaxf(a1[i][0] + b0, 0.f), 6.f), fminf(fmaxf(a1[i][1] + b1, 0.f), 6.f));
+                o0[i] = F::pack(fminf(fmaxf(a0[i][0] + b0, 0.f), 6.f), fminf(fmaxf(a0[i][1] + b1, 0.f), 6.f));
+                o1[i] = F::pack(fminf(fmaxf(a1[i][0] + b0, 0.f), 6.f), fminf(fmaxf(a1[i][1] + b1, 0.f), 6.f));
             }
             // row pair rp = 32 dwords; its two rows swap places when rp is odd: the two quads of an 8-lane write
             // group always hold one even and one odd row pair, so every ds_write_b128 group covers 32 distinct banks
@@ -337,8 +331,7 @@ __global__ __launch_bounds__(512, 2) void mbtb_kernel(
 #pragma unroll
                 for (int mt = 0; mt < NMT; ++mt) {
                     const u32x4 a = W2[(mt * 2 + ks2) * 64 + lane];
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                                    __builtin_bit_cast(bf16x8_t, f), acc[mt], 0, 0, 0);
+                    acc[mt] = F::mfma32(a, f, acc[mt]);
                 }
             }
         }
@@ -370,14 +363,14 @@ __global__ __launch_bounds__(512, 2) void mbtb_kernel(
                 for (int e = 0; e < 4; ++e) y[e] = acc[mt][4 * q + e] + bq[e];
                 if (RES) {
                     const uint2 rr = rb[(long)oc * HW * 2];
-                    y[0] += tb_lo(rr.x);
-                    y[1] += tb_hi(rr.x);
-                    y[2] += tb_lo(rr.y);
-                    y[3] += tb_hi(rr.y);
+                    y[0] += F::lo(rr.x);
+                    y[1] += F::hi(rr.x);
+                    y[2] += F::lo(rr.y);
+                    y[3] += F::hi(rr.y);
                 }
                 uint2 st;
-                st.x = tb_pack_bf16(y[0], y[1]);
-                st.y = tb_pack_bf16(y[2], y[3]);
+                st.x = F::pack(y[0], y[1]);
+                st.y = F::pack(y[2], y[3]);
                 ob[(long)oc * HW * 2] = st;
             }
         }
@@ -387,6 +380,28 @@ __global__ __launch_bounds__(512, 2) void mbtb_kernel(
     LP_WG_END();
     LP_TR_END(0);
 }
+
+template <int CK, int NMT, bool RES>
+__global__ __launch_bounds__(512, 2) void mbtb_kernel(
+    const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
+    const f32x4* __restrict__ wrow, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
+    u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
+    mbtb_kernel_body<Bf16, CK, NMT, RES>(x, w1, b1f, wrow, w2, b2f, out, Ci8, Cexp, Co8, H, W, tilesX, tilesY, xcd_remap);
+}
+template <class F, int CK, int NMT, bool RES>
+__global__ __launch_bounds__(512, 2) void mbtb_kernel(
+    const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
+    const f32x4* __restrict__ wrow, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
+    u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
+    mbtb_kernel_body<F, CK, NMT, RES>(x, w1, b1f, wrow, w2, b2f, out, Ci8, Cexp, Co8, H, W, tilesX, tilesY, xcd_remap);
+}
+// the entry point of format F (bf16: the original template)
+template <class F, int CK, int NMT, bool RES>
+inline auto mbtb_kernel_fn() {
+    if constexpr (F::is_f16) return &mbtb_kernel<F, CK, NMT, RES>;
+    else return &mbtb_kernel<CK, NMT, RES>;
+}
+
 
 // =====================================================================================
 // Stride-2 form (the first block of a stage: 7x7 stride 2, no residual): mbt_s2_kernel's geometry (mbtile_kernels.hip)
@@ -417,8 +432,8 @@ template <int CK, int NMT> struct SBW {
 };
 }  // namespace
 
-template <int CK, int NMT>
-__global__ __launch_bounds__(512, 2) void mbtb_s2_kernel(
+template <class F, int CK, int NMT>
+__device__ __forceinline__ void mbtb_s2_kernel_body(
     const u32x4* __restrict__ x,        // [N][Ci8][H*W] records
     const u32x4* __restrict__ w1, const float* __restrict__ b1f, const f32x4* __restrict__ wrow,
     const u32x4* __restrict__ w2, const float* __restrict__ b2f,      // as mbtb_kernel
@@ -534,21 +549,19 @@ __global__ __launch_bounds__(512, 2) void mbtb_s2_kernel(
 #pragma unroll
         for (int gi = 0; gi < SB_GPW; ++gi) {
             if (wave + 8 * gi >= SB_NG) break;                       // wave-uniform
-            f32x16 d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[0]),
-                                                               __builtin_bit_cast(bf16x8_t, xb[gi][0]), bias, 0, 0, 0);
+            f32x16 d = F::mfma32(a[0], xb[gi][0], bias);
 #pragma unroll
             for (int ks = 1; ks < CK; ++ks)
-                d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[ks]),
-                                                            __builtin_bit_cast(bf16x8_t, xb[gi][ks]), d, 0, 0, 0);
+                d = F::mfma32(a[ks], xb[gi][ks], d);
             if (ein[gi]) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
 #pragma unroll
                     for (int e = 0; e < 4; e += 2) {
                         const int cc = 4 * half + e + 8 * q;
-                        const unsigned pk = tb_pack_bf16(__builtin_amdgcn_fmed3f(d[4 * q + e], 0.f, hi6[gi]),
+                        const unsigned pk = F::pack(__builtin_amdgcn_fmed3f(d[4 * q + e], 0.f, hi6[gi]),
                                                          __builtin_amdgcn_fmed3f(d[4 * q + e + 1], 0.f, hi6[gi]));
-                        *reinterpret_cast<f32x2*>(E + (cc >> 1) * SB_PAIR + ecell[gi]) = f32x2{tb_lo(pk), tb_hi(pk)};
+                        *reinterpret_cast<f32x2*>(E + (cc >> 1) * SB_PAIR + ecell[gi]) = f32x2{F::lo(pk), F::hi(pk)};
                     }
             }
         }
@@ -571,10 +584,10 @@ __global__ __launch_bounds__(512, 2) void mbtb_s2_kernel(
             const float b0 = wbias[2], b1 = wbias[3];
             // D dword of output px (2rp + a, 2cp + b) = row-major index of the 8 x 16 tile
             uint2 d0, d1;
-            d0.x = tb_pack_bf16(fminf(fmaxf(o[0][0][0] + b0, 0.f), 6.f), fminf(fmaxf(o[0][0][1] + b1, 0.f), 6.f));
-            d0.y = tb_pack_bf16(fminf(fmaxf(o[0][1][0] + b0, 0.f), 6.f), fminf(fmaxf(o[0][1][1] + b1, 0.f), 6.f));
-            d1.x = tb_pack_bf16(fminf(fmaxf(o[1][0][0] + b0, 0.f), 6.f), fminf(fmaxf(o[1][0][1] + b1, 0.f), 6.f));
-            d1.y = tb_pack_bf16(fminf(fmaxf(o[1][1][0] + b0, 0.f), 6.f), fminf(fmaxf(o[1][1][1] + b1, 0.f), 6.f));
+            d0.x = F::pack(fminf(fmaxf(o[0][0][0] + b0, 0.f), 6.f), fminf(fmaxf(o[0][0][1] + b1, 0.f), 6.f));
+            d0.y = F::pack(fminf(fmaxf(o[0][1][0] + b0, 0.f), 6.f), fminf(fmaxf(o[0][1][1] + b1, 0.f), 6.f));
+            d1.x = F::pack(fminf(fmaxf(o[1][0][0] + b0, 0.f), 6.f), fminf(fmaxf(o[1][0][1] + b1, 0.f), 6.f));
+            d1.y = F::pack(fminf(fmaxf(o[1][1][0] + b0, 0.f), 6.f), fminf(fmaxf(o[1][1][1] + b1, 0.f), 6.f));
             unsigned* dp = Dq + kp * SB_DP + (2 * drp) * 16 + 2 * dcp;
             *reinterpret_cast<uint2*>(dp) = d0;
             *reinterpret_cast<uint2*>(dp + 16) = d1;
@@ -589,8 +602,7 @@ __global__ __launch_bounds__(512, 2) void mbtb_s2_kernel(
 #pragma unroll
             for (int mt = 0; mt < NMT; ++mt) {
                 const u32x4 a = W2[(mt * 2 + pks) * 64 + lane];
-                acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                                __builtin_bit_cast(bf16x8_t, f), acc[mt], 0, 0, 0);
+                acc[mt] = F::mfma32(a, f, acc[mt]);
             }
         }
         if (ch + 1 < nchunks) {
@@ -626,14 +638,38 @@ __global__ __launch_bounds__(512, 2) void mbtb_s2_kernel(
                     for (int e = 0; e < 4; ++e)
                         y[e] = (acc[mt][4 * q + e] + E[((pt * NMT + mt) * 16 + 4 * q + e) * 64 + lane]) + bq[e];
                     uint2 st;
-                    st.x = tb_pack_bf16(y[0], y[1]);
-                    st.y = tb_pack_bf16(y[2], y[3]);
+                    st.x = F::pack(y[0], y[1]);
+                    st.y = F::pack(y[2], y[3]);
                     ob[(long)oc * OHW * 2] = st;
                 }
             }
         }
     }
 }
+
+template <int CK, int NMT>
+__global__ __launch_bounds__(512, 2) void mbtb_s2_kernel(
+    const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
+    const f32x4* __restrict__ wrow, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
+    u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int OH, int OW, int tilesX, int tilesY,
+    int xcd_remap) {
+    mbtb_s2_kernel_body<Bf16, CK, NMT>(x, w1, b1f, wrow, w2, b2f, out, Ci8, Cexp, Co8, H, W, OH, OW, tilesX, tilesY, xcd_remap);
+}
+template <class F, int CK, int NMT>
+__global__ __launch_bounds__(512, 2) void mbtb_s2_kernel(
+    const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
+    const f32x4* __restrict__ wrow, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
+    u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int OH, int OW, int tilesX, int tilesY,
+    int xcd_remap) {
+    mbtb_s2_kernel_body<F, CK, NMT>(x, w1, b1f, wrow, w2, b2f, out, Ci8, Cexp, Co8, H, W, OH, OW, tilesX, tilesY, xcd_remap);
+}
+// the entry point of format F (bf16: the original template)
+template <class F, int CK, int NMT>
+inline auto mbtb_s2_kernel_fn() {
+    if constexpr (F::is_f16) return &mbtb_s2_kernel<F, CK, NMT>;
+    else return &mbtb_s2_kernel<CK, NMT>;
+}
+
 
 
 // =====================================================================================
@@ -680,8 +716,8 @@ template <int CK, int NMT> struct TQW {                    // CK = 16-channel k-
 };
 }  // namespace
 
-template <int CK, int NMT, bool RES>
-__global__ __launch_bounds__(256, 2) void mbtq_kernel(
+template <class F, int CK, int NMT, bool RES>
+__device__ __forceinline__ void mbtq_kernel_body(
     const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
     const f32x4* __restrict__ wrow, const u32x4* __restrict__ w2, const float* __restrict__ b2f,   // as mbtb_kernel
     u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
@@ -799,21 +835,19 @@ __global__ __launch_bounds__(256, 2) void mbtq_kernel(
 #pragma unroll
         for (int gi = 0; gi < TQ_GPW; ++gi) {
             if (wave + 4 * gi >= TQ_NG) break;                       // wave-uniform (wave 3 has 7 groups)
-            f32x4 d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a[0]),
-                                                              __builtin_bit_cast(bf16x8_t, xb[gi][0]), bq, 0, 0, 0);
+            f32x4 d = F::mfma16(a[0], xb[gi][0], bq);
 #pragma unroll
             for (int ks = 1; ks < CK32; ++ks)
-                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a[ks]),
-                                                            __builtin_bit_cast(bf16x8_t, xb[gi][ks]), d, 0, 0, 0);
+                d = F::mfma16(a[ks], xb[gi][ks], d);
             const int hp = (wave + 4 * gi) * 16 + cn;                // E cell of this lane: recomputed (registers: the <3,2> /
             const int hy = hp / 22;                                  // <4,2> variants sit at the 256-register budget)
             const int ecell = (hy * (TB_RS - 22) + hp + 1) * 2;
             if (hp < TB_CELLS) {
                 const float hi6 = ((okm >> gi) & 1) ? 6.f : 0.f;
-                const unsigned p0 = tb_pack_bf16(__builtin_amdgcn_fmed3f(d[0], 0.f, hi6), __builtin_amdgcn_fmed3f(d[1], 0.f, hi6));
-                const unsigned p1 = tb_pack_bf16(__builtin_amdgcn_fmed3f(d[2], 0.f, hi6), __builtin_amdgcn_fmed3f(d[3], 0.f, hi6));
-                *reinterpret_cast<f32x2*>(E + (2 * cg) * TB_PAIR + ecell) = f32x2{tb_lo(p0), tb_hi(p0)};
-                *reinterpret_cast<f32x2*>(E + (2 * cg + 1) * TB_PAIR + ecell) = f32x2{tb_lo(p1), tb_hi(p1)};
+                const unsigned p0 = F::pack(__builtin_amdgcn_fmed3f(d[0], 0.f, hi6), __builtin_amdgcn_fmed3f(d[1], 0.f, hi6));
+                const unsigned p1 = F::pack(__builtin_amdgcn_fmed3f(d[2], 0.f, hi6), __builtin_amdgcn_fmed3f(d[3], 0.f, hi6));
+                *reinterpret_cast<f32x2*>(E + (2 * cg) * TB_PAIR + ecell) = f32x2{F::lo(p0), F::hi(p0)};
+                *reinterpret_cast<f32x2*>(E + (2 * cg + 1) * TB_PAIR + ecell) = f32x2{F::lo(p1), F::hi(p1)};
             }
         }
     };
@@ -839,8 +873,8 @@ __global__ __launch_bounds__(256, 2) void mbtq_kernel(
             u32x4 o0, o1;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                o0[i] = tb_pack_bf16(fminf(fmaxf(a0[i][0] + b0, 0.f), 6.f), fminf(fmaxf(a0[i][1] + b1, 0.f), 6.f));
-                o1[i] = tb_pack_bf16(fminf(fmaxf(a1[i][0] + b0, 0.f), 6.f), fminf(fmaxf(a1[i][1] + b1, 0.f), 6.f));
+                o0[i] = F::pack(fminf(fmaxf(a0[i][0] + b0, 0.f), 6.f), fminf(fmaxf(a0[i][1] + b1, 0.f), 6.f));
+                o1[i] = F::pack(fminf(fmaxf(a1[i][0] + b0, 0.f), 6.f), fminf(fmaxf(a1[i][1] + b1, 0.f), 6.f));
             }
             unsigned* dp = Dq + kp * TB_DP + dwrp * 32 + 4 * strip;
             const int slot = (dwrp & 1) * 16;
@@ -861,8 +895,7 @@ __global__ __launch_bounds__(256, 2) void mbtq_kernel(
 #pragma unroll
             for (int mt = 0; mt < NMT; ++mt) {
                 const u32x4 a = W2[(mt * 2 + h) * 64 + lane];
-                acc[mt][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                                   __builtin_bit_cast(bf16x8_t, f), acc[mt][t], 0, 0, 0);
+                acc[mt][t] = F::mfma32(a, f, acc[mt][t]);
             }
         }
         // ================= expand of the next sub-chunk: its E cells replace the ones the depthwise just read ==========
@@ -895,14 +928,14 @@ __global__ __launch_bounds__(256, 2) void mbtq_kernel(
                     for (int e = 0; e < 4; ++e) y[e] = acc[mt][t][4 * q + e] + bq[e];
                     if (RES) {
                         const uint2 rr = rb[(long)oc * HW * 2];
-                        y[0] += tb_lo(rr.x);
-                        y[1] += tb_hi(rr.x);
-                        y[2] += tb_lo(rr.y);
-                        y[3] += tb_hi(rr.y);
+                        y[0] += F::lo(rr.x);
+                        y[1] += F::hi(rr.x);
+                        y[2] += F::lo(rr.y);
+                        y[3] += F::hi(rr.y);
                     }
                     uint2 st;
-                    st.x = tb_pack_bf16(y[0], y[1]);
-                    st.y = tb_pack_bf16(y[2], y[3]);
+                    st.x = F::pack(y[0], y[1]);
+                    st.y = F::pack(y[2], y[3]);
                     ob[(long)oc * HW * 2] = st;
                 }
             }
@@ -915,10 +948,32 @@ __global__ __launch_bounds__(256, 2) void mbtq_kernel(
 }
 
 template <int CK, int NMT, bool RES>
+__global__ __launch_bounds__(256, 2) void mbtq_kernel(
+    const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
+    const f32x4* __restrict__ wrow, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
+    u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
+    mbtq_kernel_body<Bf16, CK, NMT, RES>(x, w1, b1f, wrow, w2, b2f, out, Ci8, Cexp, Co8, H, W, tilesX, tilesY, xcd_remap);
+}
+template <class F, int CK, int NMT, bool RES>
+__global__ __launch_bounds__(256, 2) void mbtq_kernel(
+    const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
+    const f32x4* __restrict__ wrow, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
+    u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
+    mbtq_kernel_body<F, CK, NMT, RES>(x, w1, b1f, wrow, w2, b2f, out, Ci8, Cexp, Co8, H, W, tilesX, tilesY, xcd_remap);
+}
+// the entry point of format F (bf16: the original template)
+template <class F, int CK, int NMT, bool RES>
+inline auto mbtq_kernel_fn() {
+    if constexpr (F::is_f16) return &mbtq_kernel<F, CK, NMT, RES>;
+    else return &mbtq_kernel<CK, NMT, RES>;
+}
+
+
+template <class F, int CK, int NMT, bool RES>
 static bool launch_mbtq_t(const void* x, const void* w1, const float* b1f, const void* wrow, const void* w2,
                           const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int xcd,
                           hipStream_t s) {
-    const void* fn = reinterpret_cast<const void*>(mbtq_kernel<CK, NMT, RES>);
+    const void* fn = reinterpret_cast<const void*>(mbtq_kernel_fn<F, CK, NMT, RES>());
     if (uses_scratch(fn)) return false;
     const size_t lds = TQW<CK, NMT>::LDS_BYTES;
     static bool attr = false;
@@ -927,7 +982,7 @@ static bool launch_mbtq_t(const void* x, const void* w1, const float* b1f, const
         attr = true;
     }
     const int tilesX = (W + 15) / 16, tilesY = (H + 15) / 16;
-    LP_LAUNCH((mbtq_kernel<CK, NMT, RES>), dim3(N * tilesX * tilesY), dim3(256), lds, s, (const u32x4*)x,
+    LP_LAUNCH((mbtq_kernel_fn<F, CK, NMT, RES>()), dim3(N * tilesX * tilesY), dim3(256), lds, s, (const u32x4*)x,
               (const u32x4*)w1, b1f, (const f32x4*)wrow, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp,
               Cout / 8, H, W, tilesX, tilesY, xcd);
     return true;
@@ -970,14 +1025,10 @@ template <int CK, int NMT> struct TDW {
 __device__ __forceinline__ float td_swap(float v) {      // lane 2i <-> lane 2i + 1
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
 }
-__device__ __forceinline__ float td_dot2(unsigned cells, unsigned taps, float acc) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, cells), __builtin_bit_cast(bf16x2, taps), acc, false);
-}
 }  // namespace
 
-template <int CK, int NMT, bool RES>
-__global__ __launch_bounds__(512, 4) void mbtd_kernel(     // 4 waves per SIMD = two of these workgroups: <= 128 registers
+template <class F, int CK, int NMT, bool RES>
+__device__ __forceinline__ void mbtd_kernel_body(     // 4 waves per SIMD = two of these workgroups: <= 128 registers
 
     const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
     const u32x4* __restrict__ wrow2,    // depthwise taps as dot2 operands [ceil(Cexp/32)][448], then the biases: pack_wrow_d
@@ -1099,12 +1150,10 @@ __global__ __launch_bounds__(512, 4) void mbtd_kernel(     // 4 waves per SIMD =
         }
 #pragma unroll
         for (int gi = 0; gi < 2; ++gi) {
-            f32x16 d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[0]),
-                                                               __builtin_bit_cast(bf16x8_t, xb[gi][0]), bias, 0, 0, 0);
+            f32x16 d = F::mfma32(a[0], xb[gi][0], bias);
 #pragma unroll
             for (int ks = 1; ks < CK; ++ks)
-                d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[ks]),
-                                                            __builtin_bit_cast(bf16x8_t, xb[gi][ks]), d, 0, 0, 0);
+                d = F::mfma32(a[ks], xb[gi][ks], d);
             // cells 2i / 2i+1 of a group sit in lanes 2i / 2i+1 and are inside or outside the tile together
             if (ein[gi]) {
 #pragma unroll
@@ -1115,8 +1164,8 @@ __global__ __launch_bounds__(512, 4) void mbtd_kernel(     // 4 waves per SIMD =
                     // the even lane keeps channels e = 0, 1 and takes them from its neighbour; the odd one e = 2, 3
                     const float r0 = td_swap(odd ? v[0] : v[2]), r1 = td_swap(odd ? v[1] : v[3]);
                     const float o0 = odd ? v[2] : v[0], o1 = odd ? v[3] : v[1];
-                    const unsigned p0 = tb_pack_bf16(odd ? r0 : o0, odd ? o0 : r0);   // (even cell, odd cell)
-                    const unsigned p1 = tb_pack_bf16(odd ? r1 : o1, odd ? o1 : r1);
+                    const unsigned p0 = F::pack(odd ? r0 : o0, odd ? o0 : r0);   // (even cell, odd cell)
+                    const unsigned p1 = F::pack(odd ? r1 : o1, odd ? o1 : r1);
                     const int c0 = 8 * q + 4 * half + (odd ? 2 : 0);
                     E2[c0 * TD_PS + epos[gi]] = p0;
                     E2[(c0 + 1) * TD_PS + epos[gi]] = p1;
@@ -1150,10 +1199,10 @@ __global__ __launch_bounds__(512, 4) void mbtd_kernel(     // 4 waves per SIMD =
                 auto row = [&](const unsigned (&d)[5], const u32x4& we, const u32x4& wo, float (&s)[4]) {
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
-                        s[0] = td_dot2(d[t], we[t], s[0]);
-                        s[1] = td_dot2(d[t], wo[t], s[1]);
-                        s[2] = td_dot2(d[t + 1], we[t], s[2]);
-                        s[3] = td_dot2(d[t + 1], wo[t], s[3]);
+                        s[0] = F::dot2(d[t], we[t], s[0]);
+                        s[1] = F::dot2(d[t], wo[t], s[1]);
+                        s[2] = F::dot2(d[t + 1], we[t], s[2]);
+                        s[3] = F::dot2(d[t + 1], wo[t], s[3]);
                     }
                 };
 #pragma unroll
@@ -1177,8 +1226,8 @@ __global__ __launch_bounds__(512, 4) void mbtd_kernel(     // 4 waves per SIMD =
             u32x4 o0, o1;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                o0[i] = tb_pack_bf16(fminf(fmaxf(sc[0][0][i] + bb[0], 0.f), 6.f), fminf(fmaxf(sc[1][0][i] + bb[1], 0.f), 6.f));
-                o1[i] = tb_pack_bf16(fminf(fmaxf(sc[0][1][i] + bb[0], 0.f), 6.f), fminf(fmaxf(sc[1][1][i] + bb[1], 0.f), 6.f));
+                o0[i] = F::pack(fminf(fmaxf(sc[0][0][i] + bb[0], 0.f), 6.f), fminf(fmaxf(sc[1][0][i] + bb[1], 0.f), 6.f));
+                o1[i] = F::pack(fminf(fmaxf(sc[0][1][i] + bb[0], 0.f), 6.f), fminf(fmaxf(sc[1][1][i] + bb[1], 0.f), 6.f));
             }
             unsigned* dp = Dq + kp * TB_DP + dwrp * 32 + 4 * strip;
             const int slot = (dwrp & 1) * 16;
@@ -1198,8 +1247,7 @@ __global__ __launch_bounds__(512, 4) void mbtd_kernel(     // 4 waves per SIMD =
 #pragma unroll
                 for (int mt = 0; mt < NMT; ++mt) {
                     const u32x4 a = W2[(mt * 2 + ks2) * 64 + lane];
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                                    __builtin_bit_cast(bf16x8_t, f), acc[mt], 0, 0, 0);
+                    acc[mt] = F::mfma32(a, f, acc[mt]);
                 }
             }
         }
@@ -1229,14 +1277,14 @@ __global__ __launch_bounds__(512, 4) void mbtd_kernel(     // 4 waves per SIMD =
                 for (int e = 0; e < 4; ++e) y[e] = acc[mt][4 * q + e] + bq[e];
                 if (RES) {
                     const uint2 rr = rb[(long)oc * HW * 2];
-                    y[0] += tb_lo(rr.x);
-                    y[1] += tb_hi(rr.x);
-                    y[2] += tb_lo(rr.y);
-                    y[3] += tb_hi(rr.y);
+                    y[0] += F::lo(rr.x);
+                    y[1] += F::hi(rr.x);
+                    y[2] += F::lo(rr.y);
+                    y[3] += F::hi(rr.y);
                 }
                 uint2 st;
-                st.x = tb_pack_bf16(y[0], y[1]);
-                st.y = tb_pack_bf16(y[2], y[3]);
+                st.x = F::pack(y[0], y[1]);
+                st.y = F::pack(y[2], y[3]);
                 ob[(long)oc * HW * 2] = st;
             }
         }
@@ -1248,10 +1296,32 @@ __global__ __launch_bounds__(512, 4) void mbtd_kernel(     // 4 waves per SIMD =
 }
 
 template <int CK, int NMT, bool RES>
+__global__ __launch_bounds__(512, 4) void mbtd_kernel(
+    const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
+    const u32x4* __restrict__ wrow2, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
+    u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
+    mbtd_kernel_body<Bf16, CK, NMT, RES>(x, w1, b1f, wrow2, w2, b2f, out, Ci8, Cexp, Co8, H, W, tilesX, tilesY, xcd_remap);
+}
+template <class F, int CK, int NMT, bool RES>
+__global__ __launch_bounds__(512, 4) void mbtd_kernel(
+    const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
+    const u32x4* __restrict__ wrow2, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
+    u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
+    mbtd_kernel_body<F, CK, NMT, RES>(x, w1, b1f, wrow2, w2, b2f, out, Ci8, Cexp, Co8, H, W, tilesX, tilesY, xcd_remap);
+}
+// the entry point of format F (bf16: the original template)
+template <class F, int CK, int NMT, bool RES>
+inline auto mbtd_kernel_fn() {
+    if constexpr (F::is_f16) return &mbtd_kernel<F, CK, NMT, RES>;
+    else return &mbtd_kernel<CK, NMT, RES>;
+}
+
+
+template <class F, int CK, int NMT, bool RES>
 static bool launch_mbtd_t(const void* x, const void* w1, const float* b1f, const void* wrow2, const void* w2,
                           const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int xcd,
                           hipStream_t s) {
-    const void* fn = reinterpret_cast<const void*>(mbtd_kernel<CK, NMT, RES>);
+    const void* fn = reinterpret_cast<const void*>(mbtd_kernel_fn<F, CK, NMT, RES>());
     if (uses_scratch(fn)) return false;
     const size_t lds = TDW<CK, NMT>::LDS_BYTES;
     static_assert(TDW<CK, NMT>::LDS_BYTES <= 80 * 1024, "two workgroups per CU");
@@ -1261,17 +1331,17 @@ static bool launch_mbtd_t(const void* x, const void* w1, const float* b1f, const
         attr = true;
     }
     const int tilesX = (W + 15) / 16, tilesY = (H + 15) / 16;
-    LP_LAUNCH((mbtd_kernel<CK, NMT, RES>), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
+    LP_LAUNCH((mbtd_kernel_fn<F, CK, NMT, RES>()), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
               (const u32x4*)w1, b1f, (const u32x4*)wrow2, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp,
               Cout / 8, H, W, tilesX, tilesY, xcd);
     return true;
 }
 
-template <int CK, int NMT>
+template <class F, int CK, int NMT>
 static bool launch_mbtb_s2_t(const void* x, const void* w1, const float* b1f, const void* wrow, const void* w2,
                              const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int xcd,
                              hipStream_t s) {
-    const void* fn = reinterpret_cast<const void*>(mbtb_s2_kernel<CK, NMT>);
+    const void* fn = reinterpret_cast<const void*>(mbtb_s2_kernel_fn<F, CK, NMT>());
     if (uses_scratch(fn)) return false;
     const size_t lds = SBW<CK, NMT>::LDS_BYTES;
     static bool attr = false;
@@ -1281,17 +1351,17 @@ static bool launch_mbtb_s2_t(const void* x, const void* w1, const float* b1f, co
     }
     const int OH = H / 2, OW = W / 2;
     const int tilesX = (OW + 15) / 16, tilesY = (OH + 7) / 8;
-    LP_LAUNCH((mbtb_s2_kernel<CK, NMT>), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
+    LP_LAUNCH((mbtb_s2_kernel_fn<F, CK, NMT>()), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
                        (const u32x4*)w1, b1f, (const f32x4*)wrow, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp,
                        Cout / 8, H, W, OH, OW, tilesX, tilesY, xcd);
     return true;
 }
 
-template <int CK, int NMT, bool RES>
+template <class F, int CK, int NMT, bool RES>
 static bool launch_mbtb_t(const void* x, const void* w1, const float* b1f, const void* wrow, const void* w2,
                           const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int xcd,
                           hipStream_t s) {
-    const void* fn = reinterpret_cast<const void*>(mbtb_kernel<CK, NMT, RES>);
+    const void* fn = reinterpret_cast<const void*>(mbtb_kernel_fn<F, CK, NMT, RES>());
     if (uses_scratch(fn)) return false;
     const size_t lds = TBW<CK, NMT>::LDS_BYTES;
     static bool attr = false;
@@ -1300,7 +1370,7 @@ static bool launch_mbtb_t(const void* x, const void* w1, const float* b1f, const
         attr = true;
     }
     const int tilesX = (W + 15) / 16, tilesY = (H + 15) / 16;
-    LP_LAUNCH((mbtb_kernel<CK, NMT, RES>), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
+    LP_LAUNCH((mbtb_kernel_fn<F, CK, NMT, RES>()), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
                        (const u32x4*)w1, b1f, (const f32x4*)wrow, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp,
                        Cout / 8, H, W, tilesX, tilesY, xcd);
     return true;
@@ -1308,7 +1378,7 @@ static bool launch_mbtb_t(const void* x, const void* w1, const float* b1f, const
 
 bool launch_mbtb(const void* x, const void* w1, const float* b1f, const void* wrow, const void* w2, const float* b2f,
                  const void* res, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int K, int S,
-                 hipStream_t s, int mode, int mode_s2, int mode_q, const void* wrow2, int mode_d) {
+                 hipStream_t s, int mode, int mode_s2, int mode_q, const void* wrow2, int mode_d, bool f16) {
     // mode = option "mbtb" (the parity tests compare the paths): 0 = off (pwb / dwt / pwb chain), 1 (default) = on
     if (mode == 0) return false;
     if (K != 7 || (S != 1 && S != 2) || !w1 || !b1f || !wrow || !w2 || !b2f) return false;
@@ -1323,7 +1393,8 @@ bool launch_mbtb(const void* x, const void* w1, const float* b1f, const void* wr
         last_kernel_tag = "mbtb_s2_kernel";
 #define LP_GO2(CKV, NMTV)                                                                                   \
         if (ck == CKV && nmt == NMTV)                                                                       \
-            return launch_mbtb_s2_t<CKV, NMTV>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s);
+            return f16 ? launch_mbtb_s2_t<F16, CKV, NMTV>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s)  \
+                       : launch_mbtb_s2_t<Bf16, CKV, NMTV>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s);
         // the stage-entry blocks of search-XS / S / M / L
         LP_GO2(1, 1) LP_GO2(2, 1) LP_GO2(2, 2) LP_GO2(3, 3) LP_GO2(4, 3)
 #undef LP_GO2
@@ -1334,7 +1405,8 @@ bool launch_mbtb(const void* x, const void* w1, const float* b1f, const void* wr
         last_kernel_tag = "mbtd_kernel";
 #define LP_GOD(CKV, NMTV)                                                                                   \
         if (ck == CKV && nmt == NMTV &&                                                                     \
-            launch_mbtd_t<CKV, NMTV, true>(x, w1, b1f, wrow2, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s)) \
+            (f16 ? launch_mbtd_t<F16, CKV, NMTV, true>(x, w1, b1f, wrow2, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s)  \
+                 : launch_mbtd_t<Bf16, CKV, NMTV, true>(x, w1, b1f, wrow2, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s))) \
             return true;                               /* a variant that needs scratch is refused: the forms below */
         // the residual blocks with up to 32 channels: two workgroups per CU.  Measured and not kept (gpurun r6, S@448 / M@512
         // b32): the same kernel for the wide blocks at ONE workgroup per CU (2 waves per SIMD, 138-223 registers) is 9-15 %
@@ -1352,14 +1424,16 @@ bool launch_mbtb(const void* x, const void* w1, const float* b1f, const void* wr
         last_kernel_tag = "mbtq_kernel";
 #define LP_GOQ(CKV, NMTV)                                                                                   \
         if (ck == CKV && nmt == NMTV)                                                                       \
-            return launch_mbtq_t<CKV, NMTV, true>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s);
+            return f16 ? launch_mbtq_t<F16, CKV, NMTV, true>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s) \
+                       : launch_mbtq_t<Bf16, CKV, NMTV, true>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s);
         LP_GOQ(1, 1) LP_GOQ(2, 1)
 #undef LP_GOQ
     }
     last_kernel_tag = "mbtb_kernel";
 #define LP_GO(CKV, NMTV, RESV)                                                                              \
     if (ck == CKV && nmt == NMTV && (res != nullptr) == RESV)                                               \
-        return launch_mbtb_t<CKV, NMTV, RESV>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s);
+        return f16 ? launch_mbtb_t<F16, CKV, NMTV, RESV>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s)  \
+                   : launch_mbtb_t<Bf16, CKV, NMTV, RESV>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s);
     // the stride-1 blocks of search-XS / S / M / L (arch_zoo): residual blocks, then the widening ones
     LP_GO(1, 1, true) LP_GO(2, 1, true) LP_GO(3, 2, true) LP_GO(4, 2, true) LP_GO(5, 3, true) LP_GO(6, 3, true)
     LP_GO(8, 4, true)     // (10, 5): the 160-channel blocks of search-L would spill 104 bytes per lane: unfused chain

@@ -29,6 +29,7 @@
 //   * + bias, 64-byte row segments to HBM.
 // All three sums run in the order of the unfused kernels (stem_kernel, dwpw_kernel<3>): bit-identical, tested.
 #include "kernels.h"
+#include "fmt16.h"
 
 // tools/ubench/stem4_trace.hip defines this before including the file: per-wave time stamps at the phase boundaries
 #ifndef LP_STEM4_TRACE
@@ -70,21 +71,8 @@ __device__ __forceinline__ int s4_xcd_contiguous_id(int id, int n) {        // s
 // in the fp32 MFMA / FMA chains), every tensor the unfused chain (stemb_kernel -> dwb_kernel<3,1> -> pwb_kernel) would have
 // STORED is rounded to bf16 at the same place (conv output, depthwise output, 1x1 output), and the output goes out as
 // octet-planar records [N][C0 / 8][OH * OW] x 16 B: 1.03 GB of HBM traffic per 64 images of S@448 become 0.26.
-__device__ __forceinline__ float s4_round_bf16(float v) {            // RNE to bf16, back as fp32 (v_cvt_pk_bf16_f32)
-    typedef __bf16 s4_bf16x2 __attribute__((ext_vector_type(2)));
-    typedef float s4_f32x2 __attribute__((ext_vector_type(2)));
-    const s4_f32x2 t = {v, 0.f};
-    return __uint_as_float(__builtin_bit_cast(unsigned, __builtin_convertvector(t, s4_bf16x2)) << 16);
-}
-__device__ __forceinline__ unsigned s4_pack_bf16(float lo, float hi) {
-    typedef __bf16 s4_bf16x2 __attribute__((ext_vector_type(2)));
-    typedef float s4_f32x2 __attribute__((ext_vector_type(2)));
-    const s4_f32x2 t = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(t, s4_bf16x2));
-}
-
-template <int C0, bool BF16>
-__global__ __launch_bounds__(S4_NT, 6) void stem4_kernel(     // 6 waves per SIMD = three workgroups per CU: <= 80 registers
+template <class F, int C0, bool BF16>
+__device__ __forceinline__ void stem4_kernel_body(     // 6 waves per SIMD = three workgroups per CU: <= 80 registers
     const float* __restrict__ x,        // [x_batch, 3, H, W]
     const float* __restrict__ w0t,      // conv weights, tap-major [27][32] (BN scale folded)
     const float* __restrict__ b0,       // [32]
@@ -234,7 +222,7 @@ __global__ __launch_bounds__(S4_NT, 6) void stem4_kernel(     // 6 waves per SIM
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {                  // D row 4 q + r = channel q + 4 r of the half
                             float v = fminf(fmaxf(acc[r] + cb[hf][r], 0.f), 6.f);
-                            if (BF16) v = s4_round_bf16(v);            // where stemb_kernel stores the conv output
+                            if (BF16) v = F::round(v);            // where stemb_kernel stores the conv output
                             cp[4 * r * S4_CPL] = inside ? v : 0.f;
                         }
                     }
@@ -271,7 +259,7 @@ __global__ __launch_bounds__(S4_NT, 6) void stem4_kernel(     // 6 waves per SIM
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     o4[i] = fminf(fmaxf(a4[i] + bb, 0.f), 6.f);
-                    if (BF16) o4[i] = s4_round_bf16(o4[i]);            // where dwb_kernel<3,1> stores the depthwise output
+                    if (BF16) o4[i] = F::round(o4[i]);            // where dwb_kernel<3,1> stores the depthwise output
                 }
                 // d of channel cl over the head of its own plane: every lane's reads of the plane are issued above (one
                 // wave, in-order LDS queue), no other wave touches it
@@ -319,8 +307,8 @@ __global__ __launch_bounds__(S4_NT, 6) void stem4_kernel(     // 6 waves per SIM
                     const int oy = oy0 + (pg >> 1), ox = ox0 + (pg & 1) * 16 + l16;
                     if (8 * oct < C0 && oy < OH && ox < OW) {
                         uint2 st;
-                        st.x = s4_pack_bf16(po[rb][g][0] + bb[0], po[rb][g][1] + bb[1]);
-                        st.y = s4_pack_bf16(po[rb][g][2] + bb[2], po[rb][g][3] + bb[3]);
+                        st.x = F::pack(po[rb][g][0] + bb[0], po[rb][g][1] + bb[1]);
+                        st.y = F::pack(po[rb][g][2] + bb[2], po[rb][g][3] + bb[3]);
                         ob[(((long)n * (C0 / 8) + oct) * OHW + (long)oy * OW + ox) * 2 + (q4 & 1)] = st;
                     }
                 }
@@ -347,7 +335,32 @@ __global__ __launch_bounds__(S4_NT, 6) void stem4_kernel(     // 6 waves per SIM
     }
 }
 
-template <bool BF16>
+template <int C0, bool BF16>
+__global__ __launch_bounds__(S4_NT, 6) void stem4_kernel(
+    const float* __restrict__ x, const float* __restrict__ w0t, const float* __restrict__ b0,
+    const float* __restrict__ w1t, const float* __restrict__ b1, const float* __restrict__ w2t,
+    const float* __restrict__ b2, float* __restrict__ out, int H, int W, int tilesX, int tilesY, int flip_from,
+    int x_batch, int total_units) {
+    stem4_kernel_body<Bf16, C0, BF16>(x, w0t, b0, w1t, b1, w2t, b2, out, H, W, tilesX, tilesY, flip_from, x_batch, total_units);
+}
+template <class F, int C0>
+__global__ __launch_bounds__(S4_NT, 6) void stem4_kernel(
+    const float* __restrict__ x, const float* __restrict__ w0t, const float* __restrict__ b0,
+    const float* __restrict__ w1t, const float* __restrict__ b1, const float* __restrict__ w2t,
+    const float* __restrict__ b2, float* __restrict__ out, int H, int W, int tilesX, int tilesY, int flip_from,
+    int x_batch, int total_units) {
+    stem4_kernel_body<F, C0, true>(x, w0t, b0, w1t, b1, w2t, b2, out, H, W, tilesX, tilesY, flip_from, x_batch, total_units);
+}
+
+
+// the entry point of a rounding format (bf16: stem4_kernel<C0, true>; fp32 storage: <C0, false>)
+template <int C0, bool BF16, class F>
+inline auto stem4_fn() {
+    if constexpr (F::is_f16) return &stem4_kernel<F, C0>;
+    else return &stem4_kernel<C0, BF16>;
+}
+
+template <bool BF16, class F = Bf16>
 static bool launch_stem3_t(const float* x, const float* w0t, const float* b0, const float* w1t, const float* b1,
                            const float* w2t, const float* b2, float* out, int N, int H, int W, int c0, int flip_from,
                            int x_batch, hipStream_t s) {
@@ -360,18 +373,18 @@ static bool launch_stem3_t(const float* x, const float* w0t, const float* b0, co
     last_kernel_tag = "stem4_kernel";
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem4_kernel<16, BF16>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem4_fn<16, BF16, F>()), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   s4_lds_floats<16>() * 4);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem4_kernel<24, BF16>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem4_fn<24, BF16, F>()), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   s4_lds_floats<24>() * 4);
         attr = true;
     }
     const int grid = (int)total;
     if (c0 == 16)
-        LP_LAUNCH((stem4_kernel<16, BF16>), dim3((unsigned)grid), dim3(S4_NT), lds, s, x, w0t, b0, w1t, b1, w2t, b2, out, H,
+        LP_LAUNCH((stem4_fn<16, BF16, F>()), dim3((unsigned)grid), dim3(S4_NT), lds, s, x, w0t, b0, w1t, b1, w2t, b2, out, H,
                   W, tilesX, tilesY, flip_from, x_batch, (int)total);
     else
-        LP_LAUNCH((stem4_kernel<24, BF16>), dim3((unsigned)grid), dim3(S4_NT), lds, s, x, w0t, b0, w1t, b1, w2t, b2, out, H,
+        LP_LAUNCH((stem4_fn<24, BF16, F>()), dim3((unsigned)grid), dim3(S4_NT), lds, s, x, w0t, b0, w1t, b1, w2t, b2, out, H,
                   W, tilesX, tilesY, flip_from, x_batch, (int)total);
     return true;
 }
@@ -382,10 +395,14 @@ bool launch_stem3(const float* x, const float* w0t, const float* b0, const float
     return launch_stem3_t<false>(x, w0t, b0, w1t, b1, w2t, b2, out, N, H, W, c0, flip_from, x_batch, s);
 }
 
-// the bf16-storage stem in one launch: bf16-rounded weights in stem4_kernel's fp32 layouts, octet-planar bf16 records out
+// the 16-bit-storage stem in one launch: rounded weights in stem4_kernel's fp32 layouts, octet-planar records out
+// (f16: IEEE half storage, stem4_kernel<F16, C0>; otherwise bf16, stem4_kernel<C0, true>)
 bool launch_stem3b(const float* x, const float* w0t, const float* b0, const float* w1t, const float* b1,
                    const float* w2t, const float* b2, void* out, int N, int H, int W, int c0, int flip_from,
-                   int x_batch, hipStream_t s) {
+                   int x_batch, hipStream_t s, bool f16) {
+    if (f16)
+        return launch_stem3_t<true, F16>(x, w0t, b0, w1t, b1, w2t, b2, reinterpret_cast<float*>(out), N, H, W, c0,
+                                         flip_from, x_batch, s);
     return launch_stem3_t<true>(x, w0t, b0, w1t, b1, w2t, b2, reinterpret_cast<float*>(out), N, H, W, c0, flip_from,
                                 x_batch, s);
 }

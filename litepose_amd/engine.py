@@ -82,7 +82,7 @@ class PoseEngine(object):
 
     def __init__(self, cfg, cfg_arch, state_dict, person_capacity=None, device=None, pipeline_halves=True,
                  ae_from_mid=False, storage=None, options=None, **option_kw):
-        """``storage``: 'f32' | 'bf16' | None (= cfg.FP16.ENABLED, valid.py:152-153); see models.pose_mobilenet.
+        """``storage``: 'f32' | 'bf16' | 'f16' | None (= cfg.FP16.ENABLED -> bf16, valid.py:152-153); see models.pose_mobilenet.
         ``options`` / keyword arguments: DEFAULT_OPTIONS above (AE path, serving schedule, graphs); ``ae_from_mid=True``
         is the older spelling of ``ae='mid'``."""
         self.cfg = cfg

@@ -43,21 +43,23 @@ def _arch_struct(cfg, cfg_arch):
     return a
 
 
-STORAGE = {'f32': 0, 'fp32': 0, 'float32': 0, 'bf16': 1, 'bfloat16': 1}
+STORAGE = {'f32': 0, 'fp32': 0, 'float32': 0, 'bf16': 1, 'bfloat16': 1, 'f16': 2, 'fp16': 2, 'float16': 2}
+_STORAGE_NAME = {0: 'f32', 1: 'bf16', 2: 'f16'}
 
 
 class LitePose(object):
     def __init__(self, cfg, width_mult=1.0, round_nearest=8, cfg_arch=None, storage=None):
-        """``storage``: 'f32' (the reference's arithmetic) or 'bf16' (activations + folded weights in bf16,
+        """``storage``: 'f32' (the reference's arithmetic), 'bf16' (activations + folded weights in bf16,
         fp32 accumulation: the counterpart of the reference's reduced-precision switch ``cfg.FP16.ENABLED``,
-        valid.py:152-153 -> fp16util.py:87-91 network_to_half, which is also the default when None)."""
+        valid.py:152-153 -> fp16util.py:87-91 network_to_half, which is also the default when None) or 'f16'
+        (the same path in IEEE half, the format network_to_half itself uses; aliases 'fp16', 'float16')."""
         if width_mult != 1.0 or round_nearest != 8:
             raise ValueError('width_mult/round_nearest other than the defaults are not on the path')
         if storage is None:
             storage = 'bf16' if bool(cfg.FP16.ENABLED) else 'f32'
         if storage not in STORAGE:
             raise ValueError('storage must be one of %s' % sorted(STORAGE))
-        self.storage = 'bf16' if STORAGE[storage] else 'f32'
+        self.storage = _STORAGE_NAME[STORAGE[storage]]
         self._lib = nv.lib()
         self._arch = _arch_struct(cfg, cfg_arch)
         h = C.c_void_p()

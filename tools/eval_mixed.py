@@ -66,7 +66,7 @@ def main():
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--batch1', type=int, default=64)
     ap.add_argument('--seed', type=int, default=0)
-    ap.add_argument('--storage', default='f32', choices=['f32', 'bf16'])
+    ap.add_argument('--storage', default='f32', choices=['f32', 'bf16', 'f16'])
     # head gain of the synthetic weights: 1.0 gives a few persons per noise image, 6.0 saturates the grouping
     # (hundreds per image: the Python result formatting then dominates the call)
     ap.add_argument('--head-gain', type=float, default=1.0)

@@ -19,7 +19,7 @@ ap.add_argument('--batch', type=int, default=64)
 ap.add_argument('--size', type=int, default=0)
 ap.add_argument('--reps', type=int, default=3)
 ap.add_argument('--warmup', type=int, default=1)
-ap.add_argument('--storage', default='f32', choices=['f32', 'bf16'])
+ap.add_argument('--storage', default='f32', choices=['f32', 'bf16', 'f16'])
 a = ap.parse_args()
 arch = arch_zoo.get(a.arch)
 R = a.size or arch['img_size']
@@ -34,7 +34,14 @@ offs = (torch.from_numpy(np.concatenate([off0, f0])).cuda(), torch.from_numpy(np
 # would switch the pair back on), so every kernel's trace duration is an un-shared, back-to-back launch
 from litepose_amd import _native as nv  # noqa: E402
 nv.check(eng._lib.lp_net_set_streams(eng.model._h, 1))
-for _ in range(a.warmup + a.reps):
+for _ in range(a.warmup):
     out = eng._infer_one(x, offs, None, None)
+t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+t0.record()
+for _ in range(a.reps):
+    out = eng._infer_one(x, offs, None, None)
+t1.record()
 torch.cuda.synchronize()
 print('persons', int(out[1].sum()), 'path', eng._last[0][0])
+# one stream, batch after batch: time per batch of the timed reps (not bench.py's pipelined serving loop)
+print('%s@%d b%d %s: %.3f ms/step over %d reps' % (a.arch, R, a.batch, a.storage, t0.elapsed_time(t1) / a.reps, a.reps))

@@ -63,6 +63,9 @@ typedef struct lp_arch {                  /* == mobile_configs/*.json + mobile.y
     int32_t num_deconv;                   /* MODEL.EXTRA.NUM_DECONV_LAYERS (kernels 4,s2) */
     int32_t deconv_filters[LP_MAX_DECONV];/* "deconv_setting"                             */
     int32_t head_channels[LP_MAX_DECONV]; /* oup of final layer i-1 (J*[hm] + J*[ae])     */
+    int32_t plain_head;                   /* 0: Fusion Deconv Head (pose_mobilenet), 1: no raw */
+                                          /* branches (pose_simplenet.py: deconv_refined and */
+                                          /* final_refined only); other values are refused   */
 } lp_arch;
 
 typedef struct lp_net lp_net;             /* opaque                                       */
@@ -146,7 +149,10 @@ int lp_net_set_streams(lp_net* net, int k);
  *   "mbtq"       bf16 storage: residual stride-1 blocks with <= 32 input channels as 4-wave workgroups, two per CU (round 6;
  *                1 = default: expanded width <= 160 and >= 1024 tiles, 2: whenever the shape fits, 0: the 8-wave kernel)
  *   "headb"      bf16 storage: an output head (both 5x5 depthwise convs + the dual-source 1x1) in one launch, bit-identical to the
- *                three launches it replaces (round 6; default 1; needs "dwt" = 2 and <= 32 output filters)
+ *                three launches it replaces (round 6; default 1; needs "dwt" = 2 and <= 32 output filters); with
+ *                lp_arch.plain_head = 1 the one-source head (one 5x5 depthwise + the 1x1), bit-identical to its two launches
+ *   "headfuse"   fp32: an output head in one launch, headfuse_kernel (default 1; 0: the unfused dw_pair / pw2 chain).  The
+ *                one-source head of lp_arch.plain_head = 1 is bit-identical to its two launches
  *   "mb16_min"   16x16-plane blocks as mb16_kernel only for launches of at least this many images, mirrored ones included
  *                (default 48; round 6: one workgroup per image takes 1.13 ms per forward whatever the batch -- below the
  *                threshold the pw3 / dw_pair16 / pw3 chain, bit-identical, is faster: batch 1 1.67 -> 1.22 ms, batch 8

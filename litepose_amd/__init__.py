@@ -2,6 +2,7 @@
 
 Host-side mirror of the reference surface that ``valid.py`` uses (valid.py:29-47):
     models.pose_mobilenet.get_pose_net      -> litepose_amd.models.pose_mobilenet
+    models.pose_simplenet.get_pose_net      -> litepose_amd.models.pose_simplenet
     core.inference.get_multi_stage_outputs  -> litepose_amd.core.inference
     core.inference.aggregate_results
     core.group.HeatmapParser                -> litepose_amd.core.group

@@ -29,6 +29,7 @@ class LpArch(C.Structure):
         ('kernel', (C.c_int32 * LP_MAX_BLOCKS) * LP_MAX_STAGES),
         ('num_deconv', C.c_int32), ('deconv_filters', C.c_int32 * LP_MAX_DECONV),
         ('head_channels', C.c_int32 * LP_MAX_DECONV),
+        ('plain_head', C.c_int32),
     ]
 
 

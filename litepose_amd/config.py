@@ -5,6 +5,7 @@ experiments/crowd_pose/mobilenet/mobile.yaml (or the COCO variant); only keys th
 inference path reads are kept.  ``merge_from_file`` accepts the reference's YAML
 files unchanged (unknown keys are stored, not rejected).
 """
+import ast
 import copy
 
 import yaml
@@ -23,16 +24,18 @@ class CfgNode(dict):
     def clone(self):
         return _wrap(copy.deepcopy(_unwrap(self)))
 
-    def merge_from_dict(self, d):
+    def merge_from_dict(self, d, decode=False):
+        """``decode``: string values that are Python literals become those values, as yacs' merge does for the
+        reference's YAML files (``WITH_AE: (True, False)`` is the tuple, not the string)"""
         for k, v in d.items():
             if isinstance(v, dict) and isinstance(self.get(k), dict):
-                self[k].merge_from_dict(v)
+                self[k].merge_from_dict(v, decode)
             else:
-                self[k] = _wrap(v)
+                self[k] = _wrap(_decode(v) if decode else v)
 
     def merge_from_file(self, path):
         with open(path, 'r') as f:
-            self.merge_from_dict(yaml.safe_load(f))
+            self.merge_from_dict(yaml.safe_load(f), decode=True)
 
     def merge_from_list(self, opts):
         """``KEY.SUB VALUE`` pairs, as valid.py's trailing CLI opts (default.py:156-160)."""
@@ -56,6 +59,16 @@ def _wrap(v):
     if isinstance(v, dict) and not isinstance(v, CfgNode):
         return CfgNode({k: _wrap(x) for k, x in v.items()})
     return v
+
+
+def _decode(v):
+    """yacs' _decode_cfg_value: a string that parses as a Python literal becomes the literal, any other value stays"""
+    if not isinstance(v, str):
+        return v
+    try:
+        return ast.literal_eval(v)
+    except (ValueError, SyntaxError):
+        return v
 
 
 def _unwrap(v):

@@ -528,8 +528,10 @@ bool launch_dwt(const void* in, const void* wt, const float* wb, void* out, int 
 // so the head's outputs are bit-identical to the three launches it replaces (tested).  The next octet's records are
 // requested before the current octet's MFMAs.  60 KB of LDS, two workgroups per CU.  Cout <= 32 (CrowdPose: 28 / 14; the
 // COCO heads' 34-filter stage keeps the chain).
+// DUAL = false (plain head, pose_simplenet.py:134-135): out = W . relu(dw5(refined) + b), the octets of the one source only;
+// the same bits as dwt_kernel<5> + the one-source pwb_kernel.  The raw operand is absent at compile time.
 // =====================================================================================
-template <class F>
+template <class F, bool DUAL>
 __device__ __forceinline__ void headb_kernel_body(
     const u32x4* __restrict__ inA, int Ca8, const u32x4* __restrict__ inB, int Cb8,
     const u32x4* __restrict__ wtA, const float* __restrict__ wbA,     // dwt_kernel's fragments / [C/8][26][8] taps + bias
@@ -551,13 +553,13 @@ __device__ __forceinline__ void headb_kernel_body(
     const int ry = rq - n * regsY;
     const int x0 = rx * 32, y0 = ry * 32;
     const long HW = (long)H * W;
-    const int K8 = Ca8 + Cb8, KS = (K8 + 1) >> 1;
+    const int K8 = DUAL ? Ca8 + Cb8 : Ca8, KS = (K8 + 1) >> 1;
     constexpr int NPAIR = G::ROWS * G::NPX, NR = (NPAIR + 255) / 256;
 
     // records of octet `oct` of the concatenated sources: pixel pairs (2 jp, 2 jp + 1) of region row t (dwt_kernel)
     u32x4 ra[NR], rb[NR];
     auto load_octet = [&](int oct) {
-        const u32x4* plane = oct < Ca8 ? inA + ((long)n * Ca8 + oct) * HW : inB + ((long)n * Cb8 + (oct - Ca8)) * HW;
+        const u32x4* plane = (!DUAL || oct < Ca8) ? inA + ((long)n * Ca8 + oct) * HW : inB + ((long)n * Cb8 + (oct - Ca8)) * HW;
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
             const int p = tid + 256 * i;
@@ -598,7 +600,7 @@ __device__ __forceinline__ void headb_kernel_body(
         for (int hf = 0; hf < 2; ++hf) {
             const int oct = 2 * ks + hf;
             if (oct >= K8) break;                              // workgroup-uniform (an odd octet count)
-            const bool fromA = oct < Ca8;
+            const bool fromA = !DUAL || oct < Ca8;
             const int lo8 = fromA ? oct : oct - Ca8;           // octet inside its source
             const u32x4* wt = fromA ? wtA : wtB;
             const float* wb = fromA ? wbA : wbB;
@@ -678,20 +680,21 @@ __global__ __launch_bounds__(256, 2) void headb_kernel(
     const u32x4* __restrict__ wtA, const float* __restrict__ wbA, const u32x4* __restrict__ wtB,
     const float* __restrict__ wbB, const u32x4* __restrict__ wf, float* __restrict__ out, int H, int W,
     int regsX, int regsY, int Cout, int xcd_remap) {
-    headb_kernel_body<Bf16>(inA, Ca8, inB, Cb8, wtA, wbA, wtB, wbB, wf, out, H, W, regsX, regsY, Cout, xcd_remap);
+    headb_kernel_body<Bf16, true>(inA, Ca8, inB, Cb8, wtA, wbA, wtB, wbB, wf, out, H, W, regsX, regsY, Cout, xcd_remap);
 }
-template <class F>
+template <class F, bool DUAL = true>
 __global__ __launch_bounds__(256, 2) void headb_kernel(
     const u32x4* __restrict__ inA, int Ca8, const u32x4* __restrict__ inB, int Cb8,
     const u32x4* __restrict__ wtA, const float* __restrict__ wbA, const u32x4* __restrict__ wtB,
     const float* __restrict__ wbB, const u32x4* __restrict__ wf, float* __restrict__ out, int H, int W,
     int regsX, int regsY, int Cout, int xcd_remap) {
-    headb_kernel_body<F>(inA, Ca8, inB, Cb8, wtA, wbA, wtB, wbB, wf, out, H, W, regsX, regsY, Cout, xcd_remap);
+    headb_kernel_body<F, DUAL>(inA, Ca8, inB, Cb8, wtA, wbA, wtB, wbB, wf, out, H, W, regsX, regsY, Cout, xcd_remap);
 }
-// the entry point of format F (bf16: the original function)
-template <class F>
+// the entry point of format F (bf16, two sources: the original function; the one-source forms of both formats are
+// headb_kernel<F, false>)
+template <class F, bool DUAL = true>
 inline auto headb_kernel_fn() {
-    if constexpr (F::is_f16) return &headb_kernel<F>;
+    if constexpr (F::is_f16 || !DUAL) return &headb_kernel<F, DUAL>;
     else return static_cast<decltype(&headb_kernel<F16>)>(headb_kernel);
 }
 
@@ -699,7 +702,10 @@ inline auto headb_kernel_fn() {
 bool launch_headb(const void* inA, int Ca, const void* inB, int Cb, const void* wtA, const float* wbA, const void* wtB,
                   const float* wbB, const void* wf, float* out, int N, int H, int W, int K, int Cout, hipStream_t s,
                   bool f16) {
-    if (K != 5 || (Ca % 8) || (Cb % 8) || Ca < 8 || Cb < 8 || Cout > 32 || !wtA || !wtB || !wf) return false;
+    // inB == nullptr: the one-source head (plain head, Cb = 0)
+    const bool dual = inB != nullptr;
+    if (K != 5 || (Ca % 8) || (Cb % 8) || Ca < 8 || (dual ? (Cb < 8 || !wtB) : Cb != 0) || Cout > 32 || !wtA || !wf)
+        return false;
     // dwt_kernel's own shape rule (32 x 32 regions must not be mostly padding)
     const int regsX = (W + 31) / 32, regsY = (H + 31) / 32;
     if (2L * regsX * regsY * 1024 > 3L * ((W + 15) / 16) * ((H + 15) / 16) * 256) return false;
@@ -711,10 +717,14 @@ bool launch_headb(const void* inA, int Ca, const void* inB, int Cb, const void* 
     if (!attr) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(headb_kernel_fn<Bf16>()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(headb_kernel_fn<F16>()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(headb_kernel_fn<Bf16, false>()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(headb_kernel_fn<F16, false>()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr = true;
     }
     last_kernel_tag = "headb_kernel";
-    LP_LAUNCH((f16 ? headb_kernel_fn<F16>() : headb_kernel_fn<Bf16>()), dim3((unsigned)units), dim3(256), lds, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8,
+    const auto kern = dual ? (f16 ? headb_kernel_fn<F16>() : headb_kernel_fn<Bf16>())
+                           : (f16 ? headb_kernel_fn<F16, false>() : headb_kernel_fn<Bf16, false>());
+    LP_LAUNCH(kern, dim3((unsigned)units), dim3(256), lds, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8,
               (const u32x4*)wtA, wbA, (const u32x4*)wtB, wbB, (const u32x4*)wf, out, H, W, regsX, regsY, Cout, remap);
     return true;
 }
@@ -933,8 +943,9 @@ bool launch_pwb(const void* inA, int Ca, const void* inB, int Cb, const void* wf
 // (parity, tap) MFMAs of each channel block from them.  Weights: [block][parity][tap][ks][64 lanes] x 16 B.
 // Epilogue: a lane holds its half-octet of the 2x2 output quad of its cell; v_permlane32_swap pairs the two
 // horizontally adjacent pixels across the wave halves, so every lane stores whole 16-byte records.
+// DUAL = false (plain head, pose_simplenet.py:133): ConvT(refined) alone; the raw operand is absent at compile time.
 // =====================================================================================
-template <class F, int NB>
+template <class F, int NB, bool DUAL>
 __device__ __forceinline__ void deconvb_kernel_body(const u32x4* __restrict__ inA, int Ca8,
                                                       const u32x4* __restrict__ inB, int Cb8,
                                                       const u32x4* __restrict__ wf, const float* __restrict__ bias,
@@ -968,11 +979,11 @@ __device__ __forceinline__ void deconvb_kernel_body(const u32x4* __restrict__ in
         for (int q = 0; q < 4; ++q)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][q][r] = 0.f;
-    const int K8 = Ca8 + Cb8, KS = (K8 + 1) >> 1;
+    const int K8 = DUAL ? Ca8 + Cb8 : Ca8, KS = (K8 + 1) >> 1;
     const u32x4* wl = wf + lane;
     auto fetch = [&](int ks, u32x4 (&bv)[9]) {
         const int o = min(2 * min(ks, KS - 1) + half, K8 - 1);
-        const u32x4* sp = o < Ca8 ? inA + ((long)n * Ca8 + o) * hw : inB + ((long)n * Cb8 + (o - Ca8)) * hw;
+        const u32x4* sp = (!DUAL || o < Ca8) ? inA + ((long)n * Ca8 + o) * hw : inB + ((long)n * Cb8 + (o - Ca8)) * hw;
 #pragma unroll
         for (int v = 0; v < 9; ++v) bv[v] = sp[voff[v]];
     };
@@ -1037,20 +1048,21 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconvb_kernel(const u32
                                                       const u32x4* __restrict__ wf, const float* __restrict__ bias,
                                                       u32x4* __restrict__ out, long NP, int h, int w_, int Cout,
                                                       int xcd_remap) {
-    deconvb_kernel_body<Bf16, NB>(inA, Ca8, inB, Cb8, wf, bias, out, NP, h, w_, Cout, xcd_remap);
+    deconvb_kernel_body<Bf16, NB, true>(inA, Ca8, inB, Cb8, wf, bias, out, NP, h, w_, Cout, xcd_remap);
 }
-template <class F, int NB>
+template <class F, int NB, bool DUAL = true>
 __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconvb_kernel(const u32x4* __restrict__ inA, int Ca8,
                                                       const u32x4* __restrict__ inB, int Cb8,
                                                       const u32x4* __restrict__ wf, const float* __restrict__ bias,
                                                       u32x4* __restrict__ out, long NP, int h, int w_, int Cout,
                                                       int xcd_remap) {
-    deconvb_kernel_body<F, NB>(inA, Ca8, inB, Cb8, wf, bias, out, NP, h, w_, Cout, xcd_remap);
+    deconvb_kernel_body<F, NB, DUAL>(inA, Ca8, inB, Cb8, wf, bias, out, NP, h, w_, Cout, xcd_remap);
 }
-// the entry point of format F (bf16: the original template)
-template <class F, int NB>
+// the entry point of format F (bf16, two sources: the original template; the one-source forms of both formats are
+// deconvb_kernel<F, NB, false>)
+template <class F, int NB, bool DUAL = true>
 inline auto deconvb_kernel_fn() {
-    if constexpr (F::is_f16) return &deconvb_kernel<F, NB>;
+    if constexpr (F::is_f16 || !DUAL) return &deconvb_kernel<F, NB, DUAL>;
     else return &deconvb_kernel<NB>;
 }
 
@@ -1061,12 +1073,16 @@ bool launch_deconvb(const void* inA, int Ca, const void* inB, int Cb, const void
     const long NP = (long)N * h * w_;
     dim3 grid((unsigned)((NP + 127) / 128)), block(256);
     constexpr int xr = 1;                                            // tiles dealt XCD-contiguously
-    if (Cout <= 32)
-        LP_LAUNCH((f16 ? deconvb_kernel_fn<F16, 1>() : deconvb_kernel_fn<Bf16, 1>()), grid, block, 0, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8,
-                           (const u32x4*)wf, bias, (u32x4*)out, NP, h, w_, Cout, xr);
-    else
-        LP_LAUNCH((f16 ? deconvb_kernel_fn<F16, 2>() : deconvb_kernel_fn<Bf16, 2>()), grid, block, 0, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8,
-                           (const u32x4*)wf, bias, (u32x4*)out, NP, h, w_, Cout, xr);
+    // inB == nullptr: the one-source form (plain head, Cb = 0)
+    const bool dual = inB != nullptr;
+    if (!dual && Cb != 0) return false;
+    const auto kern = Cout <= 32
+        ? (dual ? (f16 ? deconvb_kernel_fn<F16, 1>() : deconvb_kernel_fn<Bf16, 1>())
+                : (f16 ? deconvb_kernel_fn<F16, 1, false>() : deconvb_kernel_fn<Bf16, 1, false>()))
+        : (dual ? (f16 ? deconvb_kernel_fn<F16, 2>() : deconvb_kernel_fn<Bf16, 2>())
+                : (f16 ? deconvb_kernel_fn<F16, 2, false>() : deconvb_kernel_fn<Bf16, 2, false>()));
+    LP_LAUNCH(kern, grid, block, 0, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8, (const u32x4*)wf, bias,
+              (u32x4*)out, NP, h, w_, Cout, xr);
     last_kernel_tag = "deconvb_kernel";
     return true;
 }

@@ -145,7 +145,8 @@ struct lp_net {
     int opt_pw3d = 1;                      // fp32: small launches of the bf16x3 1x1 take the deep-prefetch form (0 off, 2 always)
     int opt_mbtd = 1;                      // bf16: the small residual blocks as bf16-E / dot2 workgroups, two per CU (0 off)
     int opt_mbtq = 1;                      // ... the small residual blocks as 4-wave workgroups, two per CU (0 off, 2 always)
-    int opt_headb = 1;                     // bf16 storage: an output head (dw5 + dw5 + 1x1) in one launch
+    int opt_headb = 1;                     // bf16 storage: an output head (dw5 + dw5 + 1x1; plain head: dw5 + 1x1) in one launch
+    int opt_headfuse = 1;                  // fp32: an output head in one launch, headfuse_kernel (0: the unfused chain)
     int opt_dwt = 2;                       // bf16 storage: matrix-core depthwise (0 never, 1 7x7, 2 + the heads' 5x5)
     int opt_stem = 1;                      // one-launch stem, stem4_kernel (0: stem_kernel + dwpw_kernel<3>)
     int opt_diag_dwpw = 0;                 // diagnostics of DESIGN 5b (tools/flake_hunt.py --diag), never production
@@ -433,9 +434,10 @@ int build_plan(lp_net* n) {
         xlist.push_back(cur);
         xdiv.push_back(div);
     }
-    // ---- fusion deconv head ---------------------------------------------------------
+    // ---- fusion deconv head (plain_head: the refined branch only, pose_simplenet.py:128-136) ----------------------
+    const bool plain = n->arch.plain_head == 1;
     int refined = xlist.back(), rdiv = xdiv.back();
-    int raw = xlist[xlist.size() - 2];
+    int raw = plain ? -1 : xlist[xlist.size() - 2];
     const int L = (int)xlist.size();
     for (size_t i = 0; i < n->deconv.size(); ++i) {
         const Deconv& dc = n->deconv[i];
@@ -448,8 +450,9 @@ int build_plan(lp_net* n) {
         {
             std::vector<double> sc, sh;
             bn_fold(n, "deconv_bnrelu." + si + ".0", sc, sh);
-            const Tensor &wr = T(n, "deconv_refined." + si + ".weight"),
-                         &ww = T(n, "deconv_raw." + si + ".weight");
+            // the packed forms below hold the refined channels, then the raw ones (none for a plain head)
+            const Tensor& wr = T(n, "deconv_refined." + si + ".weight");
+            const Tensor* ww = plain ? nullptr : &T(n, "deconv_raw." + si + ".weight");
             const int Cout = dc.out;
             o.w_off = arena_push(n->h_packed, (size_t)(dc.refined_in + dc.raw_in) * Cout * 16);
             float* dst = n->h_packed.data() + o.w_off;
@@ -458,7 +461,7 @@ int build_plan(lp_net* n) {
                     for (int t = 0; t < 16; ++t) {
                         const double x = ci < dc.refined_in
                                              ? wr.data[((size_t)ci * Cout + co) * 16 + t]
-                                             : ww.data[((size_t)(ci - dc.refined_in) * Cout + co) * 16 + t];
+                                             : ww->data[((size_t)(ci - dc.refined_in) * Cout + co) * 16 + t];
                         dst[((size_t)ci * Cout + co) * 16 + t] = (float)(x * sc[co]);
                     }
             o.b_off = arena_push(n->h_packed, (size_t)Cout);
@@ -566,10 +569,30 @@ int build_plan(lp_net* n) {
         n->ops.push_back(o);
         refined = bR;
         rdiv = odiv;
-        const int ri = L - (int)i - 3;               // x_list[-i-3]
-        if (ri < 0) return fail(LP_ERR_UNSUPPORTED, "more deconv layers than backbone taps");
-        raw = xlist[ri];
-        if (i > 0) {
+        if (!plain) {
+            const int ri = L - (int)i - 3;           // x_list[-i-3]
+            if (ri < 0) return fail(LP_ERR_UNSUPPORTED, "more deconv layers than backbone taps");
+            raw = xlist[ri];
+        }
+        if (i > 0 && plain) {
+            // one SepConv per output stage: dw5 + BN + ReLU, then the 1x1.  The 1x1 keeps the fp32-MFMA form (no bf16x3
+            // split), the arithmetic of the one-source headfuse_kernel, so that the fused and the unfused head agree bitwise
+            const Head& h = n->heads[i - 1];
+            const std::string hi = std::to_string(i - 1);
+            const int bA = new_buf(n, h.refined_in, rdiv), bOut = new_buf(n, h.oup, rdiv);
+            Op a; a.type = OP_DW; a.name = "final_refined." + hi + ".dw5"; a.inA = refined; a.out = bA;
+            a.Ca = a.Cout = h.refined_in; a.K = 5; a.S = 1; a.in_div = a.out_div = rdiv; a.act = lp::ACT_RELU;
+            pack_conv_bn(n, "final_refined." + hi + ".conv.0.weight", "final_refined." + hi + ".conv.1", a);
+            pack_head_pairs(n, a);
+            pack_dw_dup(n, a);
+            n->ops.push_back(a);
+            Op p; p.type = OP_PW; p.name = "final." + hi + ".pw"; p.inA = bA; p.out = bOut;
+            p.Ca = h.refined_in; p.Cout = h.oup; p.in_div = p.out_div = rdiv; p.act = lp::ACT_NONE;
+            pack_pw(n, {&T(n, "final_refined." + hi + ".conv.3.weight")}, nullptr, nullptr, p);
+            p.ws_off = 0;
+            n->ops.push_back(p);
+            if (i == 1) n->out0_buf = bOut; else n->out1_buf = bOut;
+        } else if (i > 0) {
             const Head& h = n->heads[i - 1];
             const std::string hi = std::to_string(i - 1);
             const int bA = new_buf(n, h.refined_in, rdiv), bB = new_buf(n, h.raw_in, rdiv);
@@ -771,14 +794,15 @@ void pack_pwb(lp_net* n, const std::vector<const Tensor*>& ws, const std::vector
 }
 
 // deconv pair -> [channel block][parity][tap][ks][64 lanes][4 dwords] bf16 A fragments (k over the refined
-// channels, then the raw ones; BN scale folded into both halves) + the BN shift as bias in D-fragment order
-void pack_deconvb(lp_net* n, const Tensor& wr, const Tensor& ww, const std::vector<double>& sc,
+// channels, then the raw ones; BN scale folded into both halves) + the BN shift as bias in D-fragment order.
+// ww = nullptr (plain head): the refined channels only (Cb = 0)
+void pack_deconvb(lp_net* n, const Tensor& wr, const Tensor* ww, const std::vector<double>& sc,
                   const std::vector<double>& sh, int Ca, int Cb, int Cout, BOp& op) {
     const int Ct = Ca + Cb, KS = (Ct + 15) / 16, nb = (Cout + 31) / 32;
     auto wval = [&](int ci, int co, int ky, int kx) -> float {
         if (ci >= Ct || co >= Cout) return 0.f;
         const double x = ci < Ca ? wr.data[((size_t)ci * Cout + co) * 16 + ky * 4 + kx]
-                                 : ww.data[((size_t)(ci - Ca) * Cout + co) * 16 + ky * 4 + kx];
+                                 : ww->data[((size_t)(ci - Ca) * Cout + co) * 16 + ky * 4 + kx];
         return (float)(x * sc[co]);
     };
     op.w_off = arena_push(n->h_packed, (size_t)nb * 16 * KS * 64 * 4);
@@ -888,8 +912,9 @@ int build_plan_bf16(lp_net* n) {
         xlist.push_back(cur);
         xdiv.push_back(div);
     }
+    const bool plain = n->arch.plain_head == 1;
     int refined = xlist.back(), rdiv = xdiv.back();
-    int raw = xlist[xlist.size() - 2];
+    int raw = plain ? -1 : xlist[xlist.size() - 2];
     const int L = (int)xlist.size();
     for (size_t i = 0; i < n->deconv.size(); ++i) {
         const Deconv& dc = n->deconv[i];
@@ -903,16 +928,32 @@ int build_plan_bf16(lp_net* n) {
         {
             std::vector<double> sc, sh;
             bn_fold(n, "deconv_bnrelu." + si + ".0", sc, sh);
-            pack_deconvb(n, T(n, "deconv_refined." + si + ".weight"), T(n, "deconv_raw." + si + ".weight"), sc, sh,
-                         dc.refined_in, dc.raw_in, dc.out, o);
+            pack_deconvb(n, T(n, "deconv_refined." + si + ".weight"),
+                         plain ? nullptr : &T(n, "deconv_raw." + si + ".weight"), sc, sh, dc.refined_in, dc.raw_in, dc.out, o);
         }
         n->bops.push_back(o);
         refined = bR;
         rdiv = odiv;
-        const int ri = L - (int)i - 3;
-        if (ri < 0) return fail(LP_ERR_UNSUPPORTED, "more deconv layers than backbone taps");
-        raw = xlist[ri];
-        if (i > 0) {
+        if (!plain) {
+            const int ri = L - (int)i - 3;
+            if (ri < 0) return fail(LP_ERR_UNSUPPORTED, "more deconv layers than backbone taps");
+            raw = xlist[ri];
+        }
+        if (i > 0 && plain) {
+            const Head& h = n->heads[i - 1];
+            const std::string hi = std::to_string(i - 1);
+            const int bA = new_buf(n, h.refined_in, rdiv), bOut = new_buf(n, h.oup, rdiv);
+            BOp a; a.type = BOP_DW; a.name = "final_refined." + hi + ".dw5"; a.inA = refined; a.out = bA;
+            a.Ca = a.Cout = h.refined_in; a.K = 5; a.S = 1; a.in_div = a.out_div = rdiv; a.act = lp::ACT_RELU;
+            pack_conv_bn_b(n, "final_refined." + hi + ".conv.0.weight", "final_refined." + hi + ".conv.1", a, true);
+            pack_dwt(n, a);
+            n->bops.push_back(a);
+            BOp p; p.type = BOP_PW; p.name = "final." + hi + ".pw"; p.inA = bA; p.out = bOut;
+            p.Ca = h.refined_in; p.Cout = h.oup; p.in_div = p.out_div = rdiv; p.act = lp::ACT_NONE; p.out_f32 = true;
+            pack_pwb(n, {&T(n, "final_refined." + hi + ".conv.3.weight")}, nullptr, nullptr, p);
+            n->bops.push_back(p);
+            if (i == 1) n->out0_buf = bOut; else n->out1_buf = bOut;
+        } else if (i > 0) {
             const Head& h = n->heads[i - 1];
             const std::string hi = std::to_string(i - 1);
             const int bA = new_buf(n, h.refined_in, rdiv), bB = new_buf(n, h.raw_in, rdiv);
@@ -965,6 +1006,7 @@ int lp_net_create(lp_net** out, const lp_arch* a) {
     if (!out || !a) return fail(LP_ERR_INVALID_ARG, "null argument");
     if (a->num_stages < 1 || a->num_stages > LP_MAX_STAGES || a->num_deconv != 3)
         return fail(LP_ERR_UNSUPPORTED, "num_stages must be 1..8 and num_deconv 3");
+    if (a->plain_head != 0 && a->plain_head != 1) return fail(LP_ERR_INVALID_ARG, "plain_head must be 0 or 1");
     lp_net* n = new lp_net();
     n->arch = *a;
     n->c0 = make_divisible(a->input_channel * 1.0, 8);
@@ -997,14 +1039,15 @@ int lp_net_create(lp_net** out, const lp_arch* a) {
     }
     int inplanes = n->channel.back();
     const int L = (int)n->channel.size();
+    const bool plain = a->plain_head == 1;      // pose_simplenet.py: no raw branches, so no backbone taps x_list[-i-2/-i-3]
     for (int i = 0; i < a->num_deconv; ++i) {
-        if (L - i - 2 < 0) { delete n; return fail(LP_ERR_UNSUPPORTED, "too few stages"); }
-        n->deconv.push_back({inplanes, n->channel[L - i - 2], a->deconv_filters[i]});
+        if (!plain && L - i - 2 < 0) { delete n; return fail(LP_ERR_UNSUPPORTED, "too few stages"); }
+        n->deconv.push_back({inplanes, plain ? 0 : n->channel[L - i - 2], a->deconv_filters[i]});
         inplanes = a->deconv_filters[i];
     }
     for (int i = 1; i < a->num_deconv; ++i) {
-        if (L - i - 3 < 0) { delete n; return fail(LP_ERR_UNSUPPORTED, "too few stages"); }
-        n->heads.push_back({a->deconv_filters[i], n->channel[L - i - 3], a->head_channels[i - 1]});
+        if (!plain && L - i - 3 < 0) { delete n; return fail(LP_ERR_UNSUPPORTED, "too few stages"); }
+        n->heads.push_back({a->deconv_filters[i], plain ? 0 : n->channel[L - i - 3], a->head_channels[i - 1]});
     }
     // ---- reference state_dict key scheme, registration order ----
     add_tensor(n, "first.0.0.weight", {32, 3, 3, 3});
@@ -1027,12 +1070,12 @@ int lp_net_create(lp_net** out, const lp_arch* a) {
     for (size_t i = 0; i < n->deconv.size(); ++i)
         add_tensor(n, "deconv_refined." + std::to_string(i) + ".weight",
                    {n->deconv[i].refined_in, n->deconv[i].out, 4, 4});
-    for (size_t i = 0; i < n->deconv.size(); ++i)
+    for (size_t i = 0; i < n->deconv.size() && !plain; ++i)
         add_tensor(n, "deconv_raw." + std::to_string(i) + ".weight",
                    {n->deconv[i].raw_in, n->deconv[i].out, 4, 4});
     for (size_t i = 0; i < n->deconv.size(); ++i)
         add_bn(n, "deconv_bnrelu." + std::to_string(i) + ".0", n->deconv[i].out);
-    for (int which = 0; which < 2; ++which)
+    for (int which = 0; which < (plain ? 1 : 2); ++which)
         for (size_t i = 0; i < n->heads.size(); ++i) {
             const int cin = which == 0 ? n->heads[i].refined_in : n->heads[i].raw_in;
             const std::string p =
@@ -1278,6 +1321,29 @@ int forward_bf16(lp_net* n, const float* d_x, int N, int H, int W, int flip, flo
                     continue;
                 }
             }
+            // the one-source head of a plain_head net (dw5 + the 1x1) in one launch: headb_kernel's one-source form, the SAME bits
+            // as dwt_kernel<5> + pwb_kernel
+            if (o.type == BOP_DW && o.K == 5 && o.S == 1 && n->opt_headb && n->opt_dwt >= 2 && o.wt_off && o.act == lp::ACT_RELU &&
+                bi + 1 < n->bops.size()) {
+                const BOp& pw = n->bops[bi + 1];
+                if (pw.type == BOP_PW && pw.out_f32 && pw.inA == o.out && pw.inB < 0 && pw.act == lp::ACT_NONE && pw.res < 0 &&
+                    lp::launch_headb(ptr[o.inA], o.Ca, nullptr, 0, Wt + o.wt_off, Wt + o.w_off, nullptr, nullptr,
+                                     Wt + pw.w_off, reinterpret_cast<float*>(ptr[pw.out]), NBp, ih, iw, o.K, pw.Cout, s, f16)) {
+                    if (n->profiling) {
+                        hipError_t e = hipEventRecord(n->events[n->prof_ev + 1], s);
+                        if (e != hipSuccess) return fail(LP_ERR_HIP, hipGetErrorString(e));
+                        const int64_t px = (int64_t)NBp * oh * ow, C = o.Ca;
+                        std::string nm = "final." + pw.name.substr(6, pw.name.find('.', 6) - 6) + ".dw5+pw";
+                        n->prof_entries.push_back({nm, lp::last_kernel_tag, 2ll * px * 2 * C + px * (2ll * C + 4ll * pw.Cout),
+                                                   2ll * px * (C * 25 + C * (int64_t)pw.Cout), n->prof_ev, n->prof_ev + 1,
+                                                   2ll * px * C * 25, lp::last_launch});
+                        ++n->prof_ev;
+                    }
+                    stored[pw.out] = 1;
+                    ++bi;
+                    continue;
+                }
+            }
             switch (o.type) {
                 case BOP_STEM:
                     lp::launch_stemb(xsrc, Wt + o.w_off, Wt + o.b_off, ptr[o.out], NBp, H, W, flip_from, x_batch, s, f16);
@@ -1311,7 +1377,7 @@ int forward_bf16(lp_net* n, const float* d_x, int N, int H, int W, int flip, flo
                     fl = 2ll * NBp * oh * ow * (int64_t)(o.Ca + o.Cb) * o.Cout;
                     break;
                 case BOP_DECONV:
-                    ok = lp::launch_deconvb(ptr[o.inA], o.Ca, ptr[o.inB], o.Cb, Wt + o.w_off, Wt + o.b_off, ptr[o.out],
+                    ok = lp::launch_deconvb(ptr[o.inA], o.Ca, o.inB >= 0 ? ptr[o.inB] : nullptr, o.Cb, Wt + o.w_off, Wt + o.b_off, ptr[o.out],
                                             NBp, ih, iw, o.Cout, s, f16);
                     by = 2ll * NBp * ((int64_t)(o.Ca + o.Cb) * ih * iw + (int64_t)o.Cout * oh * ow);
                     fl = 2ll * NBp * (int64_t)(o.Ca + o.Cb) * o.Cout * 4 * oh * ow;
@@ -1543,7 +1609,24 @@ int lp_net_forward(lp_net* n, const float* d_x, int N, int H, int W, int flip, f
                 continue;
             }
         }
-        if (o.type == OP_DW && i + 2 < n->ops.size() && n->ops[i + 1].type == OP_DW && n->ops[i + 2].type == OP_PW &&
+        if (n->opt_headfuse && o.type == OP_DW && o.K == 5 && o.S == 1 && o.act == lp::ACT_RELU && i + 1 < n->ops.size() &&
+            n->ops[i + 1].type == OP_PW && n->ops[i + 1].inA == o.out && n->ops[i + 1].inB < 0 && n->ops[i + 1].res < 0 &&
+            n->ops[i + 1].act == lp::ACT_NONE && (n->ops[i + 1].out == n->out0_buf || n->ops[i + 1].out == n->out1_buf)) {
+            // one-source output head (plain_head): the 5x5 depthwise and the 1x1 in one launch, bit-identical to dw + pw
+            const Op& pw = n->ops[i + 1];
+            if (lp::launch_headfuse(ptr[o.inA], o.Ca, nullptr, 0, o.wpair_off ? Wt + o.wpair_off : nullptr, nullptr,
+                                    Wt + pw.w_off, ptr[pw.out], NB, oh, ow, o.K, pw.Cout, s)) {
+                const int64_t px = (int64_t)NB * oh * ow;
+                const int rc = prof_mark("final." + pw.name.substr(6, pw.name.find('.', 6) - 6) + ".dw5+pw",
+                                         4ll * px * (2ll * o.Ca) + 4ll * px * (o.Ca + pw.Cout),
+                                         2ll * px * ((int64_t)o.Ca * o.K * o.K + (int64_t)o.Ca * pw.Cout),
+                                         2ll * px * (int64_t)o.Ca * o.K * o.K);
+                if (rc) return rc;
+                ++i;
+                continue;
+            }
+        }
+        if (n->opt_headfuse && o.type == OP_DW && i + 2 < n->ops.size() && n->ops[i + 1].type == OP_DW && n->ops[i + 2].type == OP_PW &&
             n->ops[i + 2].inA == o.out && n->ops[i + 2].inB == n->ops[i + 1].out && o.S == 1 && n->ops[i + 1].S == 1 &&
             o.K == n->ops[i + 1].K && o.act == lp::ACT_RELU && n->ops[i + 1].act == lp::ACT_RELU) {
             // output head: both 5x5 depthwise convs and the two-source 1x1 in one launch
@@ -1582,22 +1665,24 @@ int lp_net_forward(lp_net* n, const float* d_x, int N, int H, int W, int flip, f
                 by = 4ll * NB * oh * ow * (o.Ca + o.Cb + o.Cout + (o.res >= 0 ? o.Cout : 0));
                 fl = 2ll * NB * oh * ow * (int64_t)(o.Ca + o.Cb) * o.Cout;
                 break;
-            case OP_DECONV:
+            case OP_DECONV: {
+                float* inB = o.inB >= 0 ? ptr[o.inB] : nullptr;   // nullptr: the one-source form (plain head)
                 if (o.w3_off && deconv4_enabled() && o.w4_off &&
-                    lp::launch_deconv4x3(ptr[o.inA], o.Ca, ptr[o.inB], o.Cb, Wt + o.w4_off, Wt + o.b3_off, ptr[o.out], NB,
+                    lp::launch_deconv4x3(ptr[o.inA], o.Ca, inB, o.Cb, Wt + o.w4_off, Wt + o.b3_off, ptr[o.out], NB,
                                          ih, iw, o.Cout, s)) {
                 } else if (o.w3_off && deconv4_enabled())
-                    lp::launch_deconv4(ptr[o.inA], o.Ca, ptr[o.inB], o.Cb, Wt + o.w3_off, Wt + o.b3_off, ptr[o.out],
+                    lp::launch_deconv4(ptr[o.inA], o.Ca, inB, o.Cb, Wt + o.w3_off, Wt + o.b3_off, ptr[o.out],
                                        NB, ih, iw, o.Cout, s);
                 else if (o.mid == 1)
-                    lp::launch_deconv_mfma(ptr[o.inA], o.Ca, ptr[o.inB], o.Cb, Wt + o.w2_off, Wt + o.b2_off,
+                    lp::launch_deconv_mfma(ptr[o.inA], o.Ca, inB, o.Cb, Wt + o.w2_off, Wt + o.b2_off,
                                            ptr[o.out], NB, ih, iw, o.Cout, s);
                 else
-                    lp::launch_deconv_pair(ptr[o.inA], o.Ca, ptr[o.inB], o.Cb, Wt + o.w_off, Wt + o.b_off,
+                    lp::launch_deconv_pair(ptr[o.inA], o.Ca, inB, o.Cb, Wt + o.w_off, Wt + o.b_off,
                                            ptr[o.out], NB, ih, iw, o.Cout, s);
                 by = 4ll * NB * ((int64_t)(o.Ca + o.Cb) * ih * iw + (int64_t)o.Cout * oh * ow);
                 fl = 2ll * NB * (int64_t)(o.Ca + o.Cb) * o.Cout * 4 * oh * ow;
                 break;
+            }
                     case OP_DWPW:
                 if (!lp::launch_dwpw(ptr[o.inA], Wt + o.w_off, Wt + o.b_off, Wt + o.w2_off, Wt + o.b2_off,
                                      o.res >= 0 ? ptr[o.res] : nullptr, ptr[o.out], NB, o.Ca, ih, iw, o.K, o.S,
@@ -1769,6 +1854,7 @@ const std::vector<OptEntry>& lp_net::options() {
         {"mbtd", 0, 1, &lp_net::opt_mbtd},
         {"pw3d", 0, 2, &lp_net::opt_pw3d},
         {"headb", 0, 1, &lp_net::opt_headb},
+        {"headfuse", 0, 1, &lp_net::opt_headfuse},
         {"dwt", 0, 2, &lp_net::opt_dwt},
         {"stem", 0, 1, &lp_net::opt_stem},
         {"diag_dwpw", 0, 2, &lp_net::opt_diag_dwpw},

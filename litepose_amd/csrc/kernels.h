@@ -102,6 +102,7 @@ int dwpw_diag_read(unsigned* host, int cap_words, bool clear);
 // fused output head: relu(dw5(refined)+b) and relu(dw5(raw)+b) -> dual-source 1x1 (wp = pack_pw A fragments over the
 // concatenated channels, no bias) in one launch; false = shape not supported -> dw + dw + pw
 // wpairA / wpairB: depthwise taps + bias of each source, channel-pair interleaved [C/2][K*K + 1][2]
+// inB = wpairB = nullptr, Cb = 0: the one-source head of a plain_head net (pose_simplenet), bit-identical to dw + pw
 bool launch_headfuse(const float* inA, int Ca, const float* inB, int Cb, const float* wpairA, const float* wpairB,
                      const float* wp, float* out, int N, int H, int W, int K, int Cout, hipStream_t s);
 
@@ -142,6 +143,7 @@ bool launch_mbt(const float* x, const void* w1s, const float* b1f, const void* w
 
 // fused pair of ConvTranspose2d(k4,s2,p1) + add + folded BN + ReLU.
 // w [Ca+Cb][Cout][4][4] (BN scale folded), b [Cout].  in: [N,C,h,w] -> out [N,Cout,2h,2w]
+// Every deconv launcher (and launch_deconvb): inB = nullptr, Cb = 0 runs the one-source form (plain_head: ConvT(refined))
 void launch_deconv_pair(const float* inA, int Ca, const float* inB, int Cb,
                         const float* w, const float* b, float* out,
                         int N, int h, int w_, int Cout, hipStream_t s);
@@ -178,6 +180,7 @@ bool launch_pwb(const void* inA, int Ca, const void* inB, int Cb, const void* wf
 // an output head of the bf16-storage network in one launch (round 6; bf16_kernels.hip): dwt_kernel<5> on both sources + the
 // dual-source 1x1 with fp32 planar output; wtA / wbA, wtB / wbB = the two depthwise ops' dwt fragments and tap / bias blocks, wf =
 // pwb's A fragments of the head's 1x1.  false = shape not taken (Cout > 32, small planes) -> the three launches
+// inB = wtB = wbB = nullptr, Cb = 0: the one-source head of a plain_head net (dwt<5> + pwb in one launch, the same bits)
 bool launch_headb(const void* inA, int Ca, const void* inB, int Cb, const void* wtA, const float* wbA, const void* wtB,
                   const float* wbB, const void* wf, float* out, int N, int H, int W, int K, int Cout, hipStream_t s,
                   bool f16 = false);

@@ -1499,6 +1499,9 @@ bool launch_dwpw(const float* in, const float* wdw, const float* bdw, const floa
 //            SGPR weight pair ([C/2][26][2]: 25 taps + bias); next pair's tiles in flight under the FMAs
 //   phase 2  wave w owns tile pixels [64w, 64w+64): D[NB*32 co][64 px] = W . slab on the fp32 matrix cores
 //            (two-source A fragments of pack_pw), 8-byte stores
+// DUAL = false (plain head, pose_simplenet.py:134-135):  out = Wr . relu(dw5(refined) + b_r)  -- one source, no raw operand.
+// That form restates the unfused chain it replaces bit for bit: the depthwise sums its taps from ZERO in dw_pair_kernel's
+// order (ky, kx) and adds the bias last, the 1x1 accumulates the k-pairs in ascending order from zero like pw2_kernel
 // =====================================================================================
 __device__ __forceinline__ int quad_row_of_lane(int lane) {
     // quad -> tile row such that the ds_read_b128 lane groups hold rows {a, a+1, a+8, a+9}: with a row stride of
@@ -1506,7 +1509,7 @@ __device__ __forceinline__ int quad_row_of_lane(int lane) {
     return (int)((0xFDCE5764B98A1320ull >> (4 * (lane >> 2))) & 15);
 }
 
-template <int K, int NB, bool ALLPF>
+template <int K, int NB, bool ALLPF, bool DUAL>
 __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__ inA, int Ca,
                                                        const float* __restrict__ inB, int Cb,
                                                        const float* __restrict__ wpairA,   // [Ca/2][K*K + 1][2] taps, bias
@@ -1520,7 +1523,7 @@ __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__
     constexpr int RS = 13;                                // row stride in 16-byte slots (2 cells x 2 ch each; 12 used)
     constexpr int TILE_SLOTS = IH * RS;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int C = Ca + Cb;
+    const int C = DUAL ? Ca + Cb : Ca;
     // Round 5: the slab is a RING of 16 channel rows: round u parks its 8 channels in rows 8 (u & 1) .. + 7, the next round's
     // MFMAs read them, and the round after that overwrites them behind the barrier in between -- 16 KB instead of C KB, so
     // the kernel's LDS footprint (33 KB) no longer caps it at two workgroups per CU
@@ -1551,7 +1554,7 @@ __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__
     }
     const long HW = (long)H * W;
     const float* imgA = inA + (long)n * Ca * HW;
-    const float* imgB = inB + (long)n * Cb * HW;
+    const float* imgB = DUAL ? inB + (long)n * Cb * HW : imgA;
     float afr[NB][32];                                     // the 1x1's A fragments (C <= 64 -> <= 32 k-pairs)
 #pragma unroll
     for (int i = 0; i < NB; ++i)
@@ -1567,7 +1570,7 @@ __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__
     f32x4 pre[NPW][2][NLD];
     auto issue = [&](int cp, int u) {                      // channel pair cp of the concatenated sources -> slot u
         const int c = 2 * cp;
-        const float* plane = c < Ca ? imgA + (long)c * HW : imgB + (long)(c - Ca) * HW;
+        const float* plane = (!DUAL || c < Ca) ? imgA + (long)c * HW : imgB + (long)(c - Ca) * HW;
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2)
 #pragma unroll
@@ -1613,6 +1616,7 @@ __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__
         const int us = ALLPF ? u : 0;
         const int c = 2 * cp;
         f32x2 dacc[4];
+        f32x2 dbias = {0.f, 0.f};
         const float* wc = wpairA;
         if (has) {
             // registers -> pair-interleaved tile: slot = (cell 2m: ch0, ch1 | cell 2m+1: ch0, ch1)
@@ -1627,9 +1631,10 @@ __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             if (!ALLPF && cp + 4 < KP) issue(cp + 4, 0);
-            wc = c < Ca ? wpairA + (long)cp * (K * K + 1) * 2 : wpairB + (long)(cp - (Ca >> 1)) * (K * K + 1) * 2;
+            wc = (!DUAL || c < Ca) ? wpairA + (long)cp * (K * K + 1) * 2 : wpairB + (long)(cp - (Ca >> 1)) * (K * K + 1) * 2;
+            dbias = f32x2{wc[2 * K * K], wc[2 * K * K + 1]};                                    // bias pair
 #pragma unroll
-            for (int i = 0; i < 4; ++i) dacc[i] = f32x2{wc[2 * K * K], wc[2 * K * K + 1]};      // bias pair
+            for (int i = 0; i < 4; ++i) dacc[i] = DUAL ? dbias : f32x2{0.f, 0.f};               // one source: bias last
         }
 #pragma unroll
         for (int ky = 0; ky < K; ++ky) {
@@ -1663,8 +1668,8 @@ __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__
             f32x4 o0, o1;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                o0[i] = fmaxf(dacc[i][0], 0.f);
-                o1[i] = fmaxf(dacc[i][1], 0.f);
+                o0[i] = fmaxf(DUAL ? dacc[i][0] : dacc[i][0] + dbias[0], 0.f);
+                o1[i] = fmaxf(DUAL ? dacc[i][1] : dacc[i][1] + dbias[1], 0.f);
             }
             *reinterpret_cast<f32x4*>(slab + (2 * (cp & 7)) * 256 + row * 16 + strip * 4) = o0;
             *reinterpret_cast<f32x4*>(slab + (2 * (cp & 7) + 1) * 256 + row * 16 + strip * 4) = o1;
@@ -1699,9 +1704,10 @@ bool launch_headfuse(const float* inA, int Ca, const float* inB, int Cb, const f
                      const float* wp, float* out, int N, int H, int W, int K, int Cout, hipStream_t s) {
     const int C = Ca + Cb;
     // the rule depends on the layer shape only (batched == per-image bitwise); small planes do not fill the
-    // chip with one workgroup per 16x16 tile
-    if (!wpairA || !wpairB || K != 5 || (Ca & 1) || (Cb & 1) || C > 64 || (W & 15) || (H & 15) || Cout > 64 ||
-        (long)H * W < 4096)
+    // chip with one workgroup per 16x16 tile.  inB == nullptr: the one-source head (plain head, Cb = 0)
+    const bool dual = inB != nullptr;
+    if (!wpairA || (dual ? (!wpairB || (Cb & 1)) : Cb != 0) || K != 5 || (Ca & 1) || C > 64 || (W & 15) || (H & 15) ||
+        Cout > 64 || (long)H * W < 4096)
         return false;
     const int tilesX = W / 16, tilesY = H / 16;
     const int grid = N * tilesX * tilesY;
@@ -1709,13 +1715,11 @@ bool launch_headfuse(const float* inA, int Ca, const float* inB, int Cb, const f
     static_assert((16 * 256 + 4 * (16 + 5 - 1) * 13 * 4) * sizeof(float) <= 64 * 1024,
                   "33 KB: below the default dynamic-LDS limit, no per-device attribute call needed (ADVICE r05)");
     last_kernel_tag = "headfuse_kernel";
-    if (Cout <= 32) {
-        LP_LAUNCH((headfuse_kernel<5, 1, false>), dim3(grid), dim3(256), lds, s, inA, Ca, inB, Cb, wpairA, wpairB,
-                           wp, out, H, W, tilesX, tilesY, Cout, xcd_remap_mode());
-    } else {
-        LP_LAUNCH((headfuse_kernel<5, 2, false>), dim3(grid), dim3(256), lds, s, inA, Ca, inB, Cb, wpairA, wpairB,
-                           wp, out, H, W, tilesX, tilesY, Cout, xcd_remap_mode());
-    }
+#define LP_HF(NBV, DV) LP_LAUNCH((headfuse_kernel<5, NBV, false, DV>), dim3(grid), dim3(256), lds, s, inA, Ca, inB, Cb, \
+                                 wpairA, wpairB, wp, out, H, W, tilesX, tilesY, Cout, xcd_remap_mode())
+    if (dual) { if (Cout <= 32) LP_HF(1, true); else LP_HF(2, true); }
+    else { if (Cout <= 32) LP_HF(1, false); else LP_HF(2, false); }
+#undef LP_HF
     return true;
 }
 
@@ -2632,7 +2636,8 @@ bool launch_mbconv(const float* x, const float* w1p, const float* b1f, const flo
 // the 3x3 input neighbourhood once and applies the 16 taps as wave-uniform scalars:
 //   a=0: (dy= 0,ky=1) (dy=-1,ky=3)      a=1: (dy=+1,ky=0) (dy= 0,ky=2)   (same in x)
 // =====================================================================================
-template <int COT>
+// DUAL = false (plain head, pose_simplenet.py:133): ConvT(refined) alone -- the raw operand is absent at compile time
+template <int COT, bool DUAL>
 __global__ __launch_bounds__(256) void deconv_pair_kernel(const float* __restrict__ inA, int Ca,
                                                           const float* __restrict__ inB, int Cb,
                                                           const float* __restrict__ w,
@@ -2650,7 +2655,7 @@ __global__ __launch_bounds__(256) void deconv_pair_kernel(const float* __restric
 #pragma unroll
     for (int c = 0; c < COT; ++c) acc[c][0] = acc[c][1] = acc[c][2] = acc[c][3] = 0.f;
 
-    for (int src = 0; src < 2; ++src) {
+    for (int src = 0; src < (DUAL ? 2 : 1); ++src) {
         const float* in = src == 0 ? inA : inB;
         const int Cs = src == 0 ? Ca : Cb;
         const int cbase = src == 0 ? 0 : Ca;
@@ -2712,8 +2717,9 @@ __global__ __launch_bounds__(256) void deconv_pair_kernel(const float* __restric
 // input views:  out[co][2iy+a][2ix+b] = sum_{t, ci} Wd[a,b][co][t, ci] * X[ci][iy+dy_t][ix+dx_t]
 // so it runs on the pw structure: A fragments packed per parity on the host, B fragment =
 // 32 consecutive input cells of channel 2kp+half read at a per-lane tap offset (zero outside
-// the image).  blockIdx.y = parity.
+// the image).  blockIdx.y = parity.  DUAL = false: the refined source only (plain head).
 // -------------------------------------------------------------------------------------
+template <bool DUAL>
 __global__ __launch_bounds__(256) void deconv_mfma_kernel(const float* __restrict__ inA, int Ca,
                                                           const float* __restrict__ inB, int Cb,
                                                           const float* __restrict__ wp,   // [4][KP][64]
@@ -2733,7 +2739,7 @@ __global__ __launch_bounds__(256) void deconv_mfma_kernel(const float* __restric
     const int p = (int)(gc - (long)n * hw);
     const int iy = p / w_, ix = p - iy * w_;
     const int par = blockIdx.y, a = par >> 1, b = par & 1;
-    const int Ct = Ca + Cb;
+    const int Ct = DUAL ? Ca + Cb : Ca;
     const int KP = 2 * Ct;                                   // (4 taps * Ct) / 2
     // taps: a=0: (dy 0, ky 1), (dy -1, ky 3);  a=1: (dy +1, ky 0), (dy 0, ky 2)   (same in x)
     int toff[4];
@@ -2759,7 +2765,7 @@ __global__ __launch_bounds__(256) void deconv_mfma_kernel(const float* __restric
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
 #pragma unroll 1
-        for (int srcsel = 0; srcsel < 2; ++srcsel) {
+        for (int srcsel = 0; srcsel < (DUAL ? 2 : 1); ++srcsel) {
             const int C = srcsel == 0 ? Ca : Cb;
             const float* sp = (srcsel == 0 ? inA : inB) + ((long)n * C + half) * hw + toff[t];
             const int nkp = C >> 1;
@@ -2790,8 +2796,9 @@ __global__ __launch_bounds__(256) void deconv_mfma_kernel(const float* __restric
 // per 16 MFMAs instead of 32, the input is read 9x instead of 16x, and every lane owns the 2x2
 // output quad of its cell, so the stores are 8-byte pairs forming full 256-byte rows (the
 // per-parity kernel wrote every other float).  Weights: [parity][channel pair][lane] x 4 taps.
+// DUAL = false (plain head): the refined source only; no raw pointer, no raw pairs in the weights.
 // -------------------------------------------------------------------------------------
-template <int NB>
+template <int NB, bool DUAL>
 __global__ __launch_bounds__(256) void deconv4_kernel(const float* __restrict__ inA, int Ca,
                                                       const float* __restrict__ inB, int Cb,
                                                       const f32x4* __restrict__ wq,   // [NB][4][Ct/2][64] x 4 taps
@@ -2834,14 +2841,14 @@ __global__ __launch_bounds__(256) void deconv4_kernel(const float* __restrict__ 
 #pragma unroll
         for (int q = 0; q < 4; ++q) bfr[i][q] = bp[q];
     }
-    const int CP = (Ca + Cb) >> 1, CPA = Ca >> 1;
+    const int CP = (DUAL ? Ca + Cb : Ca) >> 1, CPA = Ca >> 1;
     const f32x4* wl = wq + lane;
     const float* spA = inA + ((long)n * Ca + half) * hw;
-    const float* spB = inB + ((long)n * Cb + half) * hw;
+    const float* spB = DUAL ? inB + ((long)n * Cb + half) * hw : spA;
     // channel pair cp (A channels first, then B): 9 raw views + the weight quads of every (block, parity)
     auto fetch = [&](int cp, float (&bv)[9], f32x4 (&av)[NB][4]) {
         const int c = min(cp, CP - 1);                   // the tail prefetch re-loads the last pair (unused)
-        const float* cpn = c < CPA ? spA + (long)(2 * c) * hw : spB + (long)(2 * (c - CPA)) * hw;
+        const float* cpn = (!DUAL || c < CPA) ? spA + (long)(2 * c) * hw : spB + (long)(2 * (c - CPA)) * hw;
 #pragma unroll
         for (int v = 0; v < 9; ++v) bv[v] = cpn[voff[v]];     // raw; masked where it is consumed
 #pragma unroll
@@ -2908,12 +2915,11 @@ void launch_deconv4(const float* inA, int Ca, const float* inB, int Cb, const fl
                     float* out, int N, int h, int w_, int Cout, hipStream_t s) {
     const long NP = (long)N * h * w_;
     dim3 grid((unsigned)((NP + 127) / 128)), block(256);
-    if (Cout <= 32)
-        LP_LAUNCH(deconv4_kernel<1>, grid, block, 0, s, inA, Ca, inB, Cb, (const f32x4*)wq, bias, out, NP, h,
-                           w_, Cout, xcd_remap_mode());
-    else
-        LP_LAUNCH(deconv4_kernel<2>, grid, block, 0, s, inA, Ca, inB, Cb, (const f32x4*)wq, bias, out, NP, h,
-                           w_, Cout, xcd_remap_mode());
+#define LP_D4(NBV, DV) LP_LAUNCH((deconv4_kernel<NBV, DV>), grid, block, 0, s, inA, Ca, inB, Cb, (const f32x4*)wq, bias, \
+                                 out, NP, h, w_, Cout, xcd_remap_mode())
+    if (inB) { if (Cout <= 32) LP_D4(1, true); else LP_D4(2, true); }
+    else { if (Cout <= 32) LP_D4(1, false); else LP_D4(2, false); }        // plain head: the one-source form
+#undef LP_D4
     last_kernel_tag = "deconv4_kernel";
 }
 
@@ -2926,9 +2932,9 @@ void launch_deconv4(const float* inA, int Ca, const float* inB, int Cb, const fl
 // matrix-core cycles at fp32 accuracy.  Views are walked one at a time: 8 channel values per lane are
 // loaded (next view in flight under this view's MFMAs), split once into three bf16 pieces and feed every
 // (parity, tap) that reads this view (centre 4, edges 2, corners 1).
-// Weights: [block][parity][tap][ks][piece hi,mid,lo][64 lanes] x 16 B.
+// Weights: [block][parity][tap][ks][piece hi,mid,lo][64 lanes] x 16 B.  DUAL = false (plain head): the refined source only.
 // -------------------------------------------------------------------------------------
-template <int NB>
+template <int NB, bool DUAL>
 __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconv4x3_kernel(
     const float* __restrict__ inA, int Ca, const float* __restrict__ inB, int Cb, const u32x4* __restrict__ ws,
     const float* __restrict__ bias, float* __restrict__ out, long NP, int h, int w_, int Cout, int xcd_remap) {
@@ -2960,12 +2966,12 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconv4x3_kernel(
         for (int q = 0; q < 4; ++q)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][q][r] = 0.f;
-    const int Ga = Ca >> 3, G8 = (Ca + Cb) >> 3, KS = (G8 + 1) >> 1;
+    const int Ga = Ca >> 3, G8 = (DUAL ? Ca + Cb : Ca) >> 3, KS = (G8 + 1) >> 1;
     const u32x4* wl = ws + lane;
     // the 8 raw channel values of this lane's channel group of k-step ksn at view v
     auto fetch = [&](int ksn, int v, float (&raw)[8]) {
         const int gq = min(2 * min(ksn, KS - 1) + half, G8 - 1);   // beyond the last group: any valid data (zero weights)
-        const float* sp = gq < Ga ? inA + ((long)n * Ca + 8 * gq) * hw : inB + ((long)n * Cb + 8 * (gq - Ga)) * hw;
+        const float* sp = (!DUAL || gq < Ga) ? inA + ((long)n * Ca + 8 * gq) * hw : inB + ((long)n * Cb + 8 * (gq - Ga)) * hw;
 #pragma unroll
         for (int c = 0; c < 8; ++c) raw[c] = sp[(long)c * hw + voff[v]];
     };
@@ -3037,12 +3043,11 @@ bool launch_deconv4x3(const float* inA, int Ca, const float* inB, int Cb, const 
     if (h * w_ <= 256) return false;
     const long NP = (long)N * h * w_;
     dim3 grid((unsigned)((NP + 127) / 128)), block(256);
-    if (Cout <= 32)
-        LP_LAUNCH(deconv4x3_kernel<1>, grid, block, 0, s, inA, Ca, inB, Cb, (const u32x4*)ws, bias, out, NP, h,
-                           w_, Cout, xcd_remap_mode());
-    else
-        LP_LAUNCH(deconv4x3_kernel<2>, grid, block, 0, s, inA, Ca, inB, Cb, (const u32x4*)ws, bias, out, NP, h,
-                           w_, Cout, xcd_remap_mode());
+#define LP_D4X3(NBV, DV) LP_LAUNCH((deconv4x3_kernel<NBV, DV>), grid, block, 0, s, inA, Ca, inB, Cb, (const u32x4*)ws, bias, \
+                                   out, NP, h, w_, Cout, xcd_remap_mode())
+    if (inB) { if (Cout <= 32) LP_D4X3(1, true); else LP_D4X3(2, true); }
+    else { if (Cout <= 32) LP_D4X3(1, false); else LP_D4X3(2, false); }    // plain head: the one-source form
+#undef LP_D4X3
     last_kernel_tag = "deconv4x3_kernel";
     return true;
 }
@@ -3051,8 +3056,10 @@ void launch_deconv_mfma(const float* inA, int Ca, const float* inB, int Cb, cons
                         const float* bias, float* out, int N, int h, int w_, int Cout, hipStream_t s) {
     const long NP = (long)N * h * w_;
     dim3 grid((unsigned)((NP + 127) / 128), 4), block(256);
-    LP_LAUNCH(deconv_mfma_kernel, grid, block, 0, s, inA, Ca, inB, Cb, wp, bias, out, NP, h, w_,
-                       Cout);
+    if (inB)
+        LP_LAUNCH(deconv_mfma_kernel<true>, grid, block, 0, s, inA, Ca, inB, Cb, wp, bias, out, NP, h, w_, Cout);
+    else                                                                   // plain head: the one-source form
+        LP_LAUNCH(deconv_mfma_kernel<false>, grid, block, 0, s, inA, Ca, inB, Cb, wp, bias, out, NP, h, w_, Cout);
     last_kernel_tag = "deconv_mfma_kernel";
 }
 
@@ -3061,8 +3068,10 @@ void launch_deconv_pair(const float* inA, int Ca, const float* inB, int Cb, cons
     constexpr int COT = 8;
     const long total = (long)N * h * w_;
     dim3 grid((unsigned)((total + 255) / 256), (Cout + COT - 1) / COT), block(256);
-    LP_LAUNCH((deconv_pair_kernel<COT>), grid, block, 0, s, inA, Ca, inB, Cb, w, b, out, N,
-                       h, w_, Cout);
+    if (inB)
+        LP_LAUNCH((deconv_pair_kernel<COT, true>), grid, block, 0, s, inA, Ca, inB, Cb, w, b, out, N, h, w_, Cout);
+    else                                                                   // plain head: the one-source form
+        LP_LAUNCH((deconv_pair_kernel<COT, false>), grid, block, 0, s, inA, Ca, inB, Cb, w, b, out, N, h, w_, Cout);
     last_kernel_tag = "deconv_pair_kernel";
 }
 

@@ -14,6 +14,7 @@ from . import _native as nv
 from .core import group as _group
 from .core import inference as _inference
 from .models import pose_mobilenet as _pm
+from .models import pose_simplenet as _ps
 from .utils import transforms as _tf
 
 
@@ -91,7 +92,10 @@ class PoseEngine(object):
             self.options['ae'] = 'mid'
         self.device = torch.device(device if device is not None else 'cuda:%d' % torch.cuda.current_device())
         torch.cuda.set_device(self.device)
-        self.model = _pm.get_pose_net(cfg, is_train=False, cfg_arch=cfg_arch, storage=storage)
+        # valid.py:125-128: the network cfg.MODEL.NAME names; pose_simplenet is the one other name the reference's loop builds
+        # from an arch JSON, every other name keeps the pose_mobilenet network
+        net = _ps if cfg.MODEL.get('NAME') == 'pose_simplenet' else _pm
+        self.model = net.get_pose_net(cfg, is_train=False, cfg_arch=cfg_arch, storage=storage)
         self.model.load_state_dict(state_dict, strict=True)
         self.parser = _group.HeatmapParser(cfg, person_capacity=person_capacity)
         self.J = self.parser.params.num_joints              # joints in the merged maps / records

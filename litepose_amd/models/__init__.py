@@ -1,1 +1,2 @@
 from . import pose_mobilenet  # noqa: F401
+from . import pose_simplenet  # noqa: F401

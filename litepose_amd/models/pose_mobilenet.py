@@ -14,8 +14,9 @@ import torch
 from .. import _native as nv
 
 
-def _arch_struct(cfg, cfg_arch):
+def _arch_struct(cfg, cfg_arch, plain_head=False):
     a = nv.LpArch()
+    a.plain_head = 1 if plain_head else 0       # 1: pose_simplenet (no deconv_raw / final_raw branches)
     a.input_channel = int(cfg_arch['input_channel'])
     bs = cfg_arch['backbone_setting']
     if len(bs) > nv.LP_MAX_STAGES:
@@ -48,11 +49,12 @@ _STORAGE_NAME = {0: 'f32', 1: 'bf16', 2: 'f16'}
 
 
 class LitePose(object):
-    def __init__(self, cfg, width_mult=1.0, round_nearest=8, cfg_arch=None, storage=None):
+    def __init__(self, cfg, width_mult=1.0, round_nearest=8, cfg_arch=None, storage=None, plain_head=False):
         """``storage``: 'f32' (the reference's arithmetic), 'bf16' (activations + folded weights in bf16,
         fp32 accumulation: the counterpart of the reference's reduced-precision switch ``cfg.FP16.ENABLED``,
         valid.py:152-153 -> fp16util.py:87-91 network_to_half, which is also the default when None) or 'f16'
-        (the same path in IEEE half, the format network_to_half itself uses; aliases 'fp16', 'float16')."""
+        (the same path in IEEE half, the format network_to_half itself uses; aliases 'fp16', 'float16').
+        ``plain_head``: the network of pose_simplenet.py (no raw branches; models.pose_simplenet sets it)."""
         if width_mult != 1.0 or round_nearest != 8:
             raise ValueError('width_mult/round_nearest other than the defaults are not on the path')
         if storage is None:
@@ -61,7 +63,7 @@ class LitePose(object):
             raise ValueError('storage must be one of %s' % sorted(STORAGE))
         self.storage = _STORAGE_NAME[STORAGE[storage]]
         self._lib = nv.lib()
-        self._arch = _arch_struct(cfg, cfg_arch)
+        self._arch = _arch_struct(cfg, cfg_arch, plain_head)
         h = C.c_void_p()
         nv.check(self._lib.lp_net_create(C.byref(h), C.byref(self._arch)), 'lp_net_create')
         self._h = h

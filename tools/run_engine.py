@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Run the bench's engine configuration (XS@256, 64 images + mirrored, pcap 30, synthetic scenes) a few times
 on ONE stream, for rocprofv3 traces / PMC passes over every kernel of the path incl. the AE stage:
-    LP_STREAMS=1 rocprofv3 --kernel-trace --stats -d out -o t -- python tools/run_engine.py --reps 3"""
+    LP_STREAMS=1 rocprofv3 --kernel-trace --stats -d out -o t -- python tools/run_engine.py --reps 3
+--model simplenet runs the pose_simplenet network (cfg.MODEL.NAME = 'pose_simplenet': no Fusion Deconv Head) instead of
+pose_mobilenet; --profile K prints the kernel-stats table of one forward of the network (lp_net_profile: plain + mirrored
+batch, one launch per op; every launch's median over K profiled forwards) and its summed kernel time."""
 import argparse
 import os
 import sys
@@ -20,11 +23,17 @@ ap.add_argument('--size', type=int, default=0)
 ap.add_argument('--reps', type=int, default=3)
 ap.add_argument('--warmup', type=int, default=1)
 ap.add_argument('--storage', default='f32', choices=['f32', 'bf16', 'f16'])
+ap.add_argument('--model', default='mobilenet', choices=['mobilenet', 'simplenet'])
+ap.add_argument('--profile', type=int, default=0, metavar='K',
+                help='K profiled forwards of the network; the table holds each launch\'s median over them')
 a = ap.parse_args()
 arch = arch_zoo.get(a.arch)
 R = a.size or arch['img_size']
 cfg = config.apply_arch(config.get_cfg(), arch)
+cfg.MODEL.NAME = 'pose_' + a.model
 sd = synth.make_state_dict(arch, seed=1234, head_gain=0.25)
+if a.model == 'simplenet':                        # pose_simplenet.py registers no raw branches
+    sd = {k: v for k, v in sd.items() if not k.startswith(('deconv_raw.', 'final_raw.'))}
 eng = engine.PoseEngine(cfg, arch, sd, person_capacity=30, pipeline_halves=False, storage=a.storage, options=engine.options_from_env())
 x = synth.make_images(a.batch, R, seed=100).cuda()
 off0, off1 = synth.lowres_offsets(200, a.batch, 14, R)
@@ -44,4 +53,27 @@ t1.record()
 torch.cuda.synchronize()
 print('persons', int(out[1].sum()), 'path', eng._last[0][0])
 # one stream, batch after batch: time per batch of the timed reps (not bench.py's pipelined serving loop)
-print('%s@%d b%d %s: %.3f ms/step over %d reps' % (a.arch, R, a.batch, a.storage, t0.elapsed_time(t1) / a.reps, a.reps))
+print('%s %s@%d b%d %s: %.3f ms/step over %d reps' % (cfg.MODEL.NAME, a.arch, R, a.batch, a.storage,
+                                                     t0.elapsed_time(t1) / a.reps, a.reps))
+if a.profile:
+    m = eng.model
+    m.set_profiling(True)
+    m.forward_native(x, 2)                        # warm
+    runs = []
+    for _ in range(a.profile):
+        m.forward_native(x, 2)
+        torch.cuda.synchronize()
+        runs.append(m.profile())
+    m.set_profiling(False)
+    stats = {}
+    for i, (name, _, _, _) in enumerate(runs[0]):
+        tag = name.rsplit('|', 1)[1]
+        c, t = stats.get(tag, (0, 0.0))
+        stats[tag] = (c + 1, t + float(np.median([r[i][1] for r in runs])))
+    total = sum(t for _, t in stats.values())
+    print('kernel stats of one forward (%s, %s@%d, %d images + mirrored, %s; per launch the median of %d profiled '
+          'forwards):' % (cfg.MODEL.NAME, a.arch, R, a.batch, a.storage, a.profile))
+    print('%-28s %6s %10s %7s' % ('kernel', 'calls', 'ms', '%'))
+    for tag, (c, t) in sorted(stats.items(), key=lambda kv: -kv[1][1]):
+        print('%-28s %6d %10.4f %6.1f%%' % (tag, c, t, 100.0 * t / total))
+    print('%-28s %6d %10.4f' % ('total', sum(c for c, _ in stats.values()), total))

@@ -16,6 +16,12 @@
  *   - return value: 0 = LP_OK, negative = lp_status error; never throws
  *   - activations are planar NCHW fp32, the reference's own tensor layout
  *     (lib/models/pose_mobilenet.py:137-156 takes/returns NCHW)
+ *   - caller-owned buffers: every call's results are independent of what its outputs and workspaces held
+ *     before the call; every element of a documented output region is written; nothing outside the
+ *     documented regions of the given sizes (lp_*_workspace_bytes for workspaces) is written; const inputs
+ *     are not modified and nothing just outside an input is read.  Each call below says what it writes
+ *     ("Writes:"); a workspace's contents after a call are unspecified unless stated
+ *     (tests/test_gpu_buffer_contract.py checks all of this with poisoned and guarded buffers)
  */
 #ifndef LITEPOSE_AMD_H
 #define LITEPOSE_AMD_H
@@ -123,6 +129,8 @@ size_t lp_net_workspace_bytes(const lp_net* net, int N, int H, int W);
 int lp_net_forward(lp_net* net, const float* d_x, int N, int H, int W, int flip,
                    float* d_out0, float* d_out1,
                    void* d_workspace, size_t workspace_bytes, void* stream);
+/* Writes: every element of d_out0 and d_out1 ([NB,...] as above); the first lp_net_workspace_bytes(NB, H, W)
+ * bytes of d_workspace at most (scratch; lp_net_tap reads it back until the next forward).               */
 
 /* Number of internal HIP streams lp_net_forward may fan the batch out to (default 2: the plain and the
  * mirrored half of a flip=2 batch interleave their launch sequences; 1 = everything on `stream`).
@@ -193,6 +201,7 @@ int lp_wg_trace_read(uint64_t* words, int nwg, int select_cexp);
 /* Debug/parity tap: copy of a block-boundary activation of the LAST forward
  * ("first", "stage.S.B", "deconv.I"); returns number of floats, d_dst may be NULL.    */
 int64_t lp_net_tap(const lp_net* net, const char* name, float* d_dst, void* stream);
+/* Writes: d_dst[0, returned count) -- the whole tap, nothing beyond.                                            */
 /* Where a tap lives inside a workspace laid out for NB images of HxW (NB = 2N with flip = 2): byte offset, float
  * count in *count.  Lets a caller that runs several forwards in flight on several workspaces (the serving schedule)
  * inspect a SPECIFIC workspace instead of "the last forward" (tools/flake_hunt.py).  fp32 storage only.          */
@@ -230,6 +239,8 @@ int lp_tta_merge(const float* d_out0, const float* d_out1,
                  const int32_t* h_flip_index, float* d_det, float* d_tag,
                  void* d_workspace, size_t workspace_bytes, void* stream);
 size_t lp_tta_workspace_bytes(int N, int J, int h1, int w1);
+/* Writes (lp_tta_merge and lp_tta_merge_ex): every element of d_det [N,J,Hp,Wp] and d_tag [N,J,Hp,Wp,T]; the
+ * first lp_tta_workspace_bytes(N,J,h1,w1) bytes of d_workspace at most (it then holds the lp_tta_stage mid).  */
 
 /* The same merge for head layouts other than (2J, J) channels: with DATASET.WITH_CENTER and
  * TEST.IGNORE_CENTER (lib/core/inference.py:148-150, default.py:94,136,175) the network has Jn = J+1
@@ -245,10 +256,15 @@ int lp_tta_merge_ex(const float* d_out0, const float* d_out1,
 /* The two halves of lp_tta_merge on their own (fast path of the batched engine, SURVEY.md 8d B_post):
  *   lp_tta_stage    stage-0 upsample, stage average, flip-back + joint permutation at the STAGE-1 resolution
  *                   (inference.py:84-146) -> d_mid [N][4][J][h1][w1] = heat, heat_flip, tag, tag_flip
- *                   (lp_tta_workspace_bytes(N,J,h1,w1) bytes; maps 1 and 3 unused without flip)
+ *                   (lp_tta_workspace_bytes(N,J,h1,w1) bytes).  Writes maps 0 and 2 of every image; maps 1 and 3
+ *                   with flip.  Without flip maps 1 and 3 are UNSPECIFIED (not written) and the results of
+ *                   no consumer with T = 1 (lp_tta_project, lp_parse_mid, lp_parse_dm, lp_tta_merge_scales) depend
+ *                   on them; the bytes
+ *                   past the four maps up to mid_bytes are not written
  *   lp_tta_project  projection of d_mid to (Hp,Wp) + flip average (inference.py:152-171, 190-197) -> d_det, d_tag;
  *                   d_tag == NULL writes the heatmaps only (exact x2 projection, Hp = 2*h1 and Wp = 2*w1; the
- *                   consumer is lp_parse_dm, which evaluates the tags from d_mid)
+ *                   consumer is lp_parse_dm, which evaluates the tags from d_mid).  Writes every element of d_det
+ *                   [N,J,Hp,Wp] and, when given, of d_tag [N,J,Hp,Wp,T]
  * lp_parse_mid consumes d_mid directly, so the full-resolution maps need not be written at all.          */
 int lp_tta_stage(const float* d_out0, const float* d_out1, const float* d_out0f, const float* d_out1f,
                  int N, int J, int C0, int C1, int tag_offset, int h0, int w0, int h1, int w1,
@@ -258,7 +274,7 @@ int lp_tta_stage(const float* d_out0, const float* d_out1, const float* d_out0f,
  * in-place add before the merge gives, without its read-modify-write pass over both output tensors.  Used for the
  * synthetic scenes of SURVEY.md 8(d) input 4 (bench.py, tests) and usable for prior maps.  Exact x2 stage merge only
  * (every BASELINE config): LP_ERR_UNSUPPORTED otherwise (add in place and call lp_tta_stage).  No reference
- * counterpart (inference.py:84-146 merges what the network returned).                                         */
+ * counterpart (inference.py:84-146 merges what the network returned).  Writes: what lp_tta_stage writes.      */
 int lp_tta_stage_add(const float* d_out0, const float* d_out1, const float* d_out0f, const float* d_out1f,
                      const float* d_add0, const float* d_add1, const float* d_add0f, const float* d_add1f,
                      int N, int J, int C0, int C1, int tag_offset, int h0, int w0, int h1, int w1,
@@ -270,7 +286,8 @@ int lp_tta_project(const float* d_mid, int N, int J, int h1, int w1, int Hp, int
  * TEST.SCALE_FACTOR entry, every scale projected to the same base size, and sums the heatmaps:
  * d_acc[i] += d_src[i]  (aggregate_results, lib/core/inference.py:199-201, PROJECT2IMAGE branch).
  * Tags are taken from scale 1 only (inference.py:179); the final /len(SCALE_FACTOR) stays with
- * the caller as in valid.py:224.  Pointers 16-byte aligned.                                    */
+ * the caller as in valid.py:224.  Pointers 16-byte aligned.  Writes: d_acc[0, count) in place; nothing at or
+ * beyond count.                                                                                 */
 int lp_maps_accumulate(float* d_acc, const float* d_src, int64_t count, void* stream);
 
 /* The whole multi-scale aggregation of valid.py:207-224 (inference.py:176-208) in ONE launch, from the stage merges of
@@ -291,7 +308,8 @@ typedef struct lp_scale_mid {
  *                      map at its own size, then resized as resize_maps does (inference.py:201-206); the tags of
  *                      first_unit likewise when their size differs (:180-189).
  * d_det [N,J,Hf,Wf], d_tag [N,J,Hf,Wf,T] (8-byte aligned with T = 2): bit-identical to the batch-1 chain --
- * lp_tta_project per scale, aggregate_results (lp_maps_accumulate, resize_maps), then / len(SCALE_FACTOR).     */
+ * lp_tta_project per scale, aggregate_results (lp_maps_accumulate, resize_maps), then / len(SCALE_FACTOR).
+ * Writes: every element of d_det and d_tag.                                                                    */
 int lp_tta_merge_scales(const lp_scale_mid* scales, int S, int first_unit, int N, int J, int T, int project2image,
                         int Hf, int Wf, float* d_det, float* d_tag, void* stream);
 
@@ -311,7 +329,8 @@ typedef struct lp_parse_params {          /* group.py:100-120 Params + mobile.ya
 
 /* HeatmapParser.nms + top_k (group.py:131-135,141-176).  Ties: (value desc, index
  * asc); slots beyond the strictly-positive NMS survivors hold (0, index 0, tag 0).
- *   d_val_k [N,J,M] f32   d_ind_k [N,J,M] i32 (y*W+x)   d_tag_k [N,J,M,T] f32           */
+ *   d_val_k [N,J,M] f32   d_ind_k [N,J,M] i32 (y*W+x)   d_tag_k [N,J,M,T] f32
+ * Writes: every element of the three outputs.                                           */
 int lp_peaks_topk(const float* d_det, const float* d_tag, int N, int J, int H, int W, int T,
                   const lp_parse_params* p, float* d_val_k, int32_t* d_ind_k, float* d_tag_k,
                   void* stream);
@@ -320,14 +339,17 @@ int lp_peaks_topk(const float* d_det, const float* d_tag, int N, int J, int H, i
  * munkres-1.1.4 tie-breaking.  Output persons in creation order.
  *   d_ans   [N,pcap,J,3+T] f32 (x, y, val, tags; zeros for missing joints)
  *   d_count [N] i32  true person count (may exceed pcap: rows beyond pcap are dropped,
- *                    the count still reports them -> caller detects overflow)          */
+ *                    the count still reports them -> caller detects overflow)
+ * Writes: every element of d_ans (rows at or beyond min(count, pcap) and missing joints 0) and of d_count.  */
 int lp_group(const float* d_val_k, const int32_t* d_ind_k, const float* d_tag_k,
              int N, int W, int T, const lp_parse_params* p, int pcap,
              float* d_ans, int32_t* d_count, void* stream);
 
 /* adjust (group.py:178-197) + scores (:275) + refine (:199-267) for every image.
  * In place on d_ans; d_scores [N,pcap] f32 (mean of val over J before refine).
- * d_workspace: lp_refine_workspace_bytes(N, pcap) bytes (per-person mean tags + masks). */
+ * d_workspace: lp_refine_workspace_bytes(N, pcap) bytes (per-person mean tags + masks).
+ * Writes: rows p < P = min(max(d_count[n], 0), pcap) of d_ans in place (rows at or beyond P are left
+ * untouched); every element of d_scores: scores[n][p] = 0 for P <= p < pcap.                          */
 size_t lp_refine_workspace_bytes(int N, int pcap);
 int lp_adjust_refine(const float* d_det, const float* d_tag, int N, int J, int H, int W, int T,
                      int pcap, int do_adjust, int do_refine,
@@ -335,7 +357,10 @@ int lp_adjust_refine(const float* d_det, const float* d_tag, int N, int J, int H
                      void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* HeatmapParser.parse for a whole batch = the three calls above.  Scratch for
- * val_k/ind_k/tag_k comes from d_workspace (lp_parse_workspace_bytes).                  */
+ * val_k/ind_k/tag_k comes from d_workspace (lp_parse_workspace_bytes).
+ * Writes (lp_parse, lp_parse_mid, lp_parse_dm): every element of d_ans (as lp_group), d_count and d_scores (0 past
+ * min(count, pcap), as lp_adjust_refine); the first lp_parse_workspace_bytes(N,J,M,T,pcap) bytes of d_workspace
+ * at most (scratch).                                                                    */
 size_t lp_parse_workspace_bytes(int N, int J, int M, int T, int pcap);
 int lp_parse(const float* d_det, const float* d_tag, int N, int J, int H, int W, int T,
              const lp_parse_params* p, int pcap, int do_adjust, int do_refine,
@@ -351,7 +376,8 @@ int lp_parse(const float* d_det, const float* d_tag, int N, int J, int H, int W,
  * only NMS survivors with (double) value > detection_threshold -- exactly the candidates match_by_tag reads
  * (group.py:38-41) -- so the val_k / ind_k / tag_k scratch in d_workspace is NOT the full top_k of lp_peaks_topk
  * (call that for the reference's top_k contract); d_ans / d_count / d_scores are unaffected.
- * LP_ERR_UNSUPPORTED for shapes the fused NMS does not cover (W > 1024, NMS_KERNEL > 7, MAX_NUM_PEOPLE > 64). */
+ * LP_ERR_UNSUPPORTED for shapes the fused NMS does not cover (W > 1024, NMS_KERNEL > 7, MAX_NUM_PEOPLE > 64, and odd w1
+ * or NMS_KERNEL 7 where the band of the LDS-staged NMS exceeds 150 KB: W close to 1024).                        */
 int lp_parse_mid(const float* d_mid, int N, int J, int h1, int w1, int T,
                  const lp_parse_params* p, int pcap, int do_adjust, int do_refine,
                  float* d_ans, int32_t* d_count, float* d_scores,
@@ -375,7 +401,8 @@ int lp_parse_dm(const float* d_det, const float* d_mid, int N, int J, int h1, in
  *   h_trans [6]   the 2x3 src->dst matrix of get_affine_transform(center, scale, 0, (Wd,Hd))
  *   d_resized_u8  [Hd,Wd,3] uint8 warped image (what resize_align_multi_scale returns), may be NULL
  *   d_tensor      [3,Hd,Wd] float32 = (warped/255 - mean)/std, the network input, may be NULL
- * Interpolation follows cv2's 8-bit fixed-point scheme (1/32-pixel positions, 15-bit weights).      */
+ * Interpolation follows cv2's 8-bit fixed-point scheme (1/32-pixel positions, 15-bit weights).
+ * Writes (lp_preprocess, lp_preprocess_batch, lp_preprocess_batch_v): every element of each output given.  */
 int lp_preprocess(const uint8_t* d_image, int H, int W, const double* h_trans, int Hd, int Wd,
                   const float* h_mean, const float* h_std, uint8_t* d_resized_u8, float* d_tensor,
                   void* stream);
@@ -413,7 +440,9 @@ int lp_preprocess_batch_v(const uint8_t* d_src, size_t src_bytes, const lp_warp_
 
 /* utils.transforms.get_final_preds (lib/utils/transforms.py:195-202,50-56): inverse
  * affine (rot 0) heatmap -> image coordinates, in place on x,y of d_ans.
- * h_center [2], h_scale [2] as returned by get_multi_scale_size, heatmap size (Wp,Hp).  */
+ * h_center [2], h_scale [2] as returned by get_multi_scale_size, heatmap size (Wp,Hp).
+ * Writes (lp_final_preds, lp_final_preds_v): x and y of the joints of rows p < min(max(d_count[n], 0), pcap)
+ * in place; val, tags and every other row are left untouched.                           */
 int lp_final_preds(float* d_ans, const int32_t* d_count, int N, int pcap, int J, int T,
                    const double* h_center, const double* h_scale, int Wp, int Hp, void* stream);
 /* The host arithmetic of lp_final_preds: h_coef4 = (sx, tx, sy, ty) with x' = sx * x + tx, y' = sy * y + ty (fp64) for

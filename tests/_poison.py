@@ -1,0 +1,186 @@
+"""Poisoned and guarded device buffers for the buffer-contract tests (tests/test_gpu_buffer_contract.py).
+
+Every buffer the C ABI writes belongs to the caller, and the product hands it recycled memory (the engine reuses its
+workspaces, outputs and records for every batch and every graph replay).  These helpers let a test run a call with
+those buffers pre-filled with a poison pattern and placed between guard bands inside one larger allocation:
+
+  * ``place(nbytes, align, pattern)``  a view inside one allocation with >= GUARD bytes of a fixed byte pattern on
+                                       both sides; ``check_guards()`` names the first changed byte by its offset from
+                                       the view (negative: before it)
+  * ``fill(t, pattern)``               Z: all bytes 0x00 (the reference run); N: all bytes 0xFF (NaN in f32, bf16 and
+                                       f16; -1 as an integer); H: bytes 0x7F (3.39e38 in f32 and bf16), or halfwords
+                                       0x7BFF (65504) in f16 regions -- a huge finite value that max-pooling, fmaxf and
+                                       top-k selections would let win where NaN would be swallowed
+  * ``still_poisoned(t, ref, pattern)``  elements of an output that hold the poison bits where the Z run's value does not
+
+A plain module, not a conftest: the tests import it by name (tests/ is on sys.path under pytest).  Guards live inside
+the same allocation; nothing here relies on page faults or on the end of a mapping."""
+import torch
+
+PATTERNS = ('Z', 'N', 'H')
+GUARD = 4096
+GUARD_BYTE = 0xA5            # guards of writable regions: a byte no kernel of this project writes as a whole float
+_BYTE = {'Z': 0x00, 'N': 0xFF, 'H': 0x7F}
+_F16_H = 0x7BFF              # largest finite half, 65504
+_INT = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def pattern_byte(pattern):
+    return _BYTE[pattern]
+
+
+def fill(t, pattern, half=None):
+    """Fill tensor ``t`` (any dtype, contiguous) with ``pattern`` in place, with torch on the current stream.
+    ``half``: treat the region as f16 halfwords for H (default: t.dtype == float16)."""
+    if half is None:
+        half = t.dtype == torch.float16
+    if not t.is_contiguous():
+        ints = _INT[t.element_size()]            # copied as integers: NaN payloads are kept
+        tmp = fill(torch.empty(t.shape, dtype=t.dtype, device=t.device), pattern, half)
+        t.view(ints).copy_(tmp.view(ints))
+        return t
+    if pattern == 'H' and half:
+        assert t.numel() * t.element_size() % 2 == 0
+        t.view(torch.uint8).view(torch.int16).fill_(_F16_H)
+    else:
+        t.view(torch.uint8).fill_(_BYTE[pattern])
+    return t
+
+
+def poison_bits(dtype, pattern):
+    """The integer bit pattern an element of ``dtype`` holds after ``fill(.., pattern)``."""
+    size = torch.empty((), dtype=dtype).element_size()
+    t = torch.empty(1, dtype=dtype)
+    fill(t, pattern)
+    return int(t.view(_INT[size])[0])
+
+
+def as_bits(t):
+    """The same memory as signed integers of the element size (bitwise comparisons: NaN == NaN, -0 != +0)."""
+    return t.contiguous().view(_INT[t.element_size()])
+
+
+def bitwise_equal(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(as_bits(a), as_bits(b))
+
+
+def first_difference(a, b):
+    """Flat index of the first element where a and b differ bitwise, or None."""
+    d = (as_bits(a).reshape(-1) != as_bits(b).reshape(-1)).nonzero()
+    return None if d.numel() == 0 else int(d[0])
+
+
+def still_poisoned(t, ref, pattern):
+    """Flat indices of the elements of ``t`` that still hold the poison of ``pattern`` although the reference (Z) run
+    ``ref`` holds another value there: an element the call documents as written but left alone.  (An element whose
+    legitimate value happens to be the poison bits, e.g. a count of -1 under N, is not reported.)"""
+    if pattern == 'Z':
+        return []
+    p = poison_bits(t.dtype, pattern)
+    tb, rb = as_bits(t).reshape(-1), as_bits(ref).reshape(-1)
+    return (((tb == p) & (rb != p)).nonzero().reshape(-1)).tolist()
+
+
+class Placement(object):
+    """A ``nbytes`` view at an ``align``-byte boundary inside one allocation, guard bands of ``guard_byte`` on both
+    sides (>= ``guard`` bytes each: the back guard starts right after the exact ``nbytes``)."""
+
+    def __init__(self, nbytes, align=256, pattern='Z', guard_byte=GUARD_BYTE, device='cuda', guard=GUARD, half=False):
+        assert align >= 1 and (align & (align - 1)) == 0 and guard >= 1
+        self.nbytes, self.align, self.guard_byte = int(nbytes), align, guard_byte
+        self.base = torch.empty(self.nbytes + 2 * guard + align, dtype=torch.uint8, device=device)
+        mis = (self.base.data_ptr() + guard) % align
+        self.off = guard + ((align - mis) % align)
+        self.base.fill_(guard_byte)
+        self.bytes = self.base[self.off:self.off + self.nbytes]
+        assert self.bytes.data_ptr() % align == 0
+        if pattern is not None:
+            fill(self.bytes, pattern, half)
+
+    def view(self, dtype, shape):
+        """The region as a tensor of ``dtype`` and ``shape`` (it must cover exactly nbytes)."""
+        el = torch.empty((), dtype=dtype).element_size()
+        n = 1
+        for s in shape:
+            n *= int(s)
+        assert n * el == self.nbytes, (shape, dtype, self.nbytes)
+        return self.bytes.view(dtype).view(tuple(shape))
+
+    def guard_violation(self):
+        """None, or (offset of the first changed guard byte from the view's start, its value).  Negative offsets lie
+        before the view."""
+        front = self.base[:self.off]
+        back = self.base[self.off + self.nbytes:]
+        bad = (front != self.guard_byte).nonzero()
+        if bad.numel():
+            i = int(bad[0])
+            return i - self.off, int(front[i])
+        bad = (back != self.guard_byte).nonzero()
+        if bad.numel():
+            i = int(bad[0])
+            return self.nbytes + i, int(back[i])
+        return None
+
+    def check_guards(self, what=''):
+        v = self.guard_violation()
+        assert v is None, ('%s: guard byte changed at offset %d from the view (value 0x%02x, %d-byte region)'
+                           % (what or 'buffer', v[0], v[1], self.nbytes))
+
+
+def place(nbytes, align=256, pattern='Z', guard_byte=GUARD_BYTE, device='cuda', half=False):
+    return Placement(nbytes, align, pattern, guard_byte, device, half=half)
+
+
+def place_like(t, align=256, pattern='Z', half=None):
+    """A guarded placement shaped like ``t``, filled with ``pattern``: returns (placement, view)."""
+    half = t.dtype == torch.float16 if half is None else half
+    p = place(t.numel() * t.element_size(), align, pattern, device=t.device, half=half)
+    return p, p.view(t.dtype, t.shape)
+
+
+def wrap_input(t, align=256, guard_pattern='Z'):
+    """A guarded copy of input ``t`` whose guards hold ``guard_pattern`` (N / H: an over-read changes the results):
+    returns (placement, view).  The copy is enqueued on the current stream."""
+    p = place(t.numel() * t.element_size(), align, None, guard_byte=_BYTE[guard_pattern], device=t.device)
+    v = p.view(t.dtype, t.shape)
+    v.copy_(t)
+    return p, v
+
+
+class Arena(object):
+    """The buffers of one call under one poison pattern: outputs and workspaces filled with the pattern (guards of
+    GUARD_BYTE), inputs copied between guards of the pattern.  ``check()`` verifies every guard and that no input
+    changed."""
+
+    def __init__(self, pattern, device='cuda'):
+        self.pattern, self.device = pattern, device
+        self.places, self.inputs = [], []
+
+    def out(self, shape, dtype=torch.float32, align=256, what='', half=None):
+        el = torch.empty((), dtype=dtype).element_size()
+        n = 1
+        for s in shape:
+            n *= int(s)
+        half = dtype == torch.float16 if half is None else half
+        p = place(n * el, align, self.pattern, device=self.device, half=half)
+        self.places.append((what or 'out', p))
+        return p.view(dtype, shape)
+
+    def ws(self, nbytes, align=256, what='workspace', half=False):
+        p = place(nbytes, align, self.pattern, device=self.device, half=half)
+        self.places.append((what, p))
+        return p.bytes
+
+    def inp(self, t, align=256, what='input'):
+        p, v = wrap_input(t, align, self.pattern)
+        self.places.append((what, p))
+        self.inputs.append((what, t, v))
+        return v
+
+    def check(self):
+        torch.cuda.synchronize()
+        for what, p in self.places:
+            p.check_guards(what)
+        for what, orig, v in self.inputs:
+            assert bitwise_equal(orig, v), ('%s changed by the call (first element %s)'
+                                            % (what, first_difference(orig, v)))

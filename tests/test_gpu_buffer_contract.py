@@ -1,0 +1,867 @@
+"""The caller-owned buffer contract of every C ABI call that writes device memory (include/litepose_amd.h), checked with
+poisoned and guarded buffers (tests/_poison.py):
+
+  1. independence   a call's results do not depend on what its workspaces and outputs held before the call: outputs
+                    are bitwise equal after runs with every workspace and output pre-filled Z (0x00), N (0xFF: NaN) and
+                    H (0x7F / 0x7BFF: a huge finite value)
+  2. completeness   no element of a documented output still holds its poison after an N or H run
+  3. bounds         guard bands (>= 4 KB) on both sides of every buffer, the back one right after the exact size the
+                    call documents (lp_*_workspace_bytes for workspaces), are untouched; in-place calls leave the part
+                    of the buffer outside the documented region bitwise unchanged
+  4. over-reads     every input is a copy between guards of the run's pattern, so a result that depends on memory just
+                    before or after an input changes between runs; every const input is bitwise unchanged afterwards
+The Z run of every call is tied to a high-precision reference the way the existing tests tie it: net_ref.forward
+(fp32, NET_ATOL), group_ref.HeatmapParser (bit for bit), inference_ref.merge, the batch-1 multi-scale chain,
+preprocess_ref, the fp64 back-projection.  The engine-level tests poison every buffer of a PoseEngine between two
+batches (eager, graph replays, the three AE paths, bf16 / f16 storage, multi-scale without PROJECT2IMAGE).
+
+``CALLS`` (importable without a GPU; tests/test_poison_cpu.py checks it against the header) maps every entry point with a
+writable device pointer to the tests here that cover it.
+
+Index audit (why a uniform 0xFF / 0x7F fill can never drive an index out of range; checked from the code before the
+first run, keep it current when a kernel starts reading another integer from a workspace):
+  * the parse workspace holds val_k / ind_k / tag_k and prev / miss.  Every top-k form (peaks_topk_kernel,
+    peaks_topk_fast_kernel, peaks_topk_vec_kernel, peaks_topk_walk_kernel, peaks_topk_mid_kernel) writes all M slots of
+    every (image, joint) plane, an empty slot as (0, index 0, tag 0), before group_kernel reads them (lane < M) in the same
+    call; adjust_scores_kernel / adjust_scores_mid_kernel write miss and prev for every person slot p < pcap before
+    refine reads them in the same call
+  * d_ans is cleared by zero_kernel (N * pcap * J * (3 + T) floats) in launch_group and d_count is written for every
+    image by group_kernel before adjust / refine / final_preds read them; every reader clamps the count:
+    P = min(max(count[n], 0), pcap) (adjust_scores_kernel, adjust_scores_mid_kernel, the refine kernels,
+    final_preds_kernel, final_preds_v_kernel)
+  * lp_adjust_refine and lp_final_preds(_v) take d_count as an input; the tests hand them a valid one
+  * the network workspace holds activations only (floats / 16-bit records), no index; its internal tables (weights,
+    offsets) live in the lp_net handle, not in the caller's memory
+  * the device tables d_desc (lp_preprocess_batch_v) and d_coef (lp_final_preds_v) are inputs: wrapped in guards, their
+    contents kept valid
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from _poison import (PATTERNS, Arena, as_bits, bitwise_equal, fill, first_difference, place, still_poisoned)
+from oracle import group_ref, inference_ref, net_ref, synth
+
+pytestmark = pytest.mark.gpu
+
+# entry point -> the tests of this module that run it under the contract
+CALLS = {
+    'lp_net_forward': ('test_net_forward_contract', 'test_engine_serving_loop_contract'),
+    'lp_net_tap': ('test_net_forward_contract',),
+    'lp_tta_merge': ('test_tta_merge_contract',),
+    'lp_tta_merge_ex': ('test_tta_merge_contract',),
+    'lp_tta_stage': ('test_tta_stage_contract', 'test_tta_stage_t1_unused_maps'),
+    'lp_tta_stage_add': ('test_tta_stage_contract',),
+    'lp_tta_project': ('test_ae_contract', 'test_tta_stage_t1_unused_maps'),
+    'lp_maps_accumulate': ('test_maps_accumulate_contract',),
+    'lp_tta_merge_scales': ('test_merge_scales_contract', 'test_tta_stage_t1_unused_maps'),
+    'lp_peaks_topk': ('test_ae_contract',),
+    'lp_group': ('test_ae_contract',),
+    'lp_adjust_refine': ('test_ae_contract',),
+    'lp_parse': ('test_ae_contract',),
+    'lp_parse_mid': ('test_ae_contract', 'test_tta_stage_t1_unused_maps'),
+    'lp_parse_dm': ('test_ae_contract', 'test_tta_stage_t1_unused_maps'),
+    'lp_preprocess': ('test_preprocess_contract',),
+    'lp_preprocess_batch': ('test_preprocess_contract',),
+    'lp_preprocess_batch_v': ('test_preprocess_contract',),
+    'lp_final_preds': ('test_ae_contract',),
+    'lp_final_preds_v': ('test_ae_contract',),
+}
+
+
+def _nv():
+    from litepose_amd import _native as nv
+    return nv
+
+
+def _contract(run, what):
+    """Run ``run(arena)`` under Z, N and H.  ``run`` returns ({name: documented output region}, [(name, tensor,
+    expected)]) -- the second list: regions an in-place call must leave bitwise unchanged.  Checks guards, inputs,
+    cross-pattern bitwise equality and leftover poison; returns the Z outputs."""
+    res = {}
+    for pat in PATTERNS:
+        ar = Arena(pat)
+        outs, same = run(ar)
+        ar.check()
+        for name, t, exp in same:
+            assert bitwise_equal(t, exp), ('%s [%s]: %s outside the documented region changed (first element %s)'
+                                           % (what, pat, name, first_difference(t, exp)))
+        res[pat] = {k: v.clone() for k, v in outs.items()}
+        del ar
+    z = res['Z']
+    for pat in ('N', 'H'):
+        for k, v in res[pat].items():
+            left = still_poisoned(v, z[k], pat)
+            assert not left, ('%s [%s]: %s has %d elements never written (first flat index %d)'
+                              % (what, pat, k, len(left), left[0]))
+            assert bitwise_equal(v, z[k]), ('%s: %s differs between the Z and %s runs (first flat index %s)'
+                                            % (what, k, pat, first_difference(v, z[k])))
+    return z
+
+
+def _ck(rc, what):
+    return _nv().check(rc, what)
+
+
+# ------------------------------------------------------------------ positive controls
+def test_harness_reports_a_guard_write_and_an_unwritten_element():
+    p = place(1000, 256, 'N')
+    v = p.view(torch.float32, (250,))
+    v.fill_(1.0)
+    p.base[p.off + 1000 + 17] = 0                       # one byte into the back guard
+    torch.cuda.synchronize()
+    with pytest.raises(AssertionError, match='offset 1017'):
+        p.check_guards('control')
+    q = place(1000, 256, 'N')
+    q.base[q.off - 3] = 1                               # one byte into the front guard
+    with pytest.raises(AssertionError, match='offset -3'):
+        q.check_guards('control')
+
+    def run(ar):                                        # an output whose last element is left unwritten
+        o = ar.out((64,))
+        o[:-1] = 2.0
+        return {'o': o}, []
+    with pytest.raises(AssertionError, match='never written'):
+        _contract(run, 'control')
+
+    def run_over(ar):                                   # a result that reads one element past its input
+        x = ar.inp(torch.arange(8, dtype=torch.float32, device='cuda'))
+        o = ar.out((1,))
+        full = x.untyped_storage()
+        past = torch.empty(0, dtype=torch.float32, device='cuda').set_(full, x.storage_offset() + 8, (1,))
+        o.copy_(past)
+        return {'o': o}, []
+    with pytest.raises(AssertionError, match='differs between|never written'):
+        _contract(run_over, 'control')
+
+
+# ------------------------------------------------------------------ the network
+def _net_rows():
+    """census rows (id, arch, storage, H, W, N, flip, options, simplenet); bf16 rows again under f16; pose_simplenet."""
+    from test_gpu_kernel_census import CASES
+    rows = [(c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], False) for c in CASES]
+    rows += [(c[0] + '@f16', c[1], 'f16', c[3], c[4], c[5], c[6], c[7], False) for c in CASES if c[2] == 'bf16']
+    rows += [('simplenet_%s' % s, 'search-XS', s, 64, 64, 2, 2, {}, True) for s in ('f32', 'bf16', 'f16')]
+    return rows
+
+
+_NETS = {}
+
+
+def _net(arch_name, storage, simple):
+    key = (arch_name, storage, simple)
+    if key not in _NETS:
+        _NETS.clear()                                   # one net at a time: host memory of the bench-size rows
+        if simple:
+            from test_gpu_simplenet import _model
+        else:
+            from _net_check import _model
+        _NETS[key] = _model(arch_name, storage=storage)
+    return _NETS[key]
+
+
+@pytest.mark.parametrize('row', _net_rows(), ids=lambda r: r[0])
+def test_net_forward_contract(row):
+    """lp_net_forward (and lp_net_tap of its last forward) on every kernel-census row, in the profiled form (one launch per
+    op, the whole batch) and in the default two-stream fan-out: outputs and taps bitwise equal under Z / N / H workspaces
+    and outputs, nothing written past the exact lp_net_workspace_bytes, input untouched.  The Z run of the profiled form:
+    fp32 against net_ref.forward (NET_ATOL), 16-bit storage bitwise equal to the same forward on fresh buffers (what the
+    census and the f16 census compare with the reference)."""
+    from _net_check import NET_ATOL, set_options
+    nv = _nv()
+    lib = nv.lib()
+    cid, arch_name, storage, H, W, N, flip, options, simple = row
+    m, arch, sd = _net(arch_name, storage, simple)
+    x = synth.make_images(N, H, seed=101 + N, w=W)
+    xd = x.cuda()
+    NB = 2 * N if flip == 2 else N
+    c0, c1 = m.final_channel
+    need = int(lib.lp_net_workspace_bytes(m._h, NB, H, W))
+    taps = ['first', 'deconv.0'] if storage == 'f32' else ['first']
+    old = set_options(m, options)
+    try:
+        z = {}
+        for form in ('profiled', 'fanout'):
+            def run(ar):
+                xi = ar.inp(xd, what='d_x')
+                o0 = ar.out((NB, c0, H // 4, W // 4), what='d_out0')
+                o1 = ar.out((NB, c1, H // 2, W // 2), what='d_out1')
+                ws = ar.ws(need, what='d_workspace', half=storage == 'f16')
+                m.set_profiling(form == 'profiled')
+                _ck(lib.lp_net_set_streams(m._h, 2), 'lp_net_set_streams')
+                try:
+                    _ck(lib.lp_net_forward(m._h, nv.dptr(xi), N, H, W, flip, nv.dptr(o0), nv.dptr(o1), nv.dptr(ws), need,
+                                           nv.stream_ptr()), 'lp_net_forward')
+                finally:
+                    m.set_profiling(False)
+                outs = {'out0': o0, 'out1': o1}
+                for t in taps:
+                    cnt = _ck(lib.lp_net_tap(m._h, t.encode(), None, None), 'lp_net_tap')
+                    d = ar.out((cnt,), what='tap ' + t)
+                    _ck(lib.lp_net_tap(m._h, t.encode(), nv.dptr(d), nv.stream_ptr()), 'lp_net_tap')
+                    outs['tap.' + t] = d
+                return outs, []
+            z[form] = _contract(run, '%s/%s' % (cid, form))
+        outs = z['profiled']
+        if storage == 'f32':
+            halves = [(0, x)] if flip == 0 else ([(0, torch.flip(x, [3]))] if flip == 1 else
+                                                [(0, x), (N, torch.flip(x, [3]))])
+            with torch.no_grad():
+                for base, xs in halves:
+                    if simple:
+                        import _simplenet_ref as snr
+                        ref = snr.forward(xs[:1], sd, arch)
+                    else:
+                        ref = net_ref.forward(xs[:1], sd, arch)
+                    for k in range(2):
+                        err = float((outs['out%d' % k][base:base + 1].cpu() - ref[k]).abs().max())
+                        assert err <= NET_ATOL, (cid, 'out%d' % k, base, err)
+        else:
+            m.set_profiling(True)
+            try:
+                fresh = m.forward_native(xd, flip)
+            finally:
+                m.set_profiling(False)
+            torch.cuda.synchronize()
+            for k in range(2):
+                assert bitwise_equal(fresh[k], outs['out%d' % k]), (cid, k)
+    finally:
+        set_options(m, old)
+
+
+# ------------------------------------------------------------------ TTA merge
+def _rand_outs(seed, NB, C0, C1, h0, w0):
+    g = torch.Generator().manual_seed(seed)
+    o0 = torch.randn(NB, C0, h0, w0, generator=g)
+    o1 = torch.randn(NB, C1, 2 * h0, 2 * w0, generator=g)
+    return o0, o1
+
+
+_FLIP14 = inference_ref.FLIP_CONFIG['CROWDPOSE']
+
+
+@pytest.mark.parametrize('flip,ex', [(True, False), (False, False), (True, True)])
+def test_tta_merge_contract(flip, ex):
+    """lp_tta_merge / lp_tta_merge_ex (WITH_CENTER head: Jn = J + 1 channels per stage, the first J kept): det / tag
+    under poisoned workspace and outputs, Z run against inference_ref.merge (2e-6, test_tta_merge_vs_oracle)."""
+    nv = _nv()
+    lib = nv.lib()
+    N, J, h0, w0, Hp, Wp = 2, 14, 16, 24, 64, 96
+    Jn = J + 1 if ex else J
+    T = 2 if flip else 1
+    o0, o1 = _rand_outs(5, 2 * N if flip else N, 2 * Jn, Jn, h0, w0)
+    fi = (C.c_int32 * J)(*_FLIP14)
+    need = int(lib.lp_tta_workspace_bytes(N, J, 2 * h0, 2 * w0))
+    d0, d1 = o0.cuda(), o1.cuda()
+
+    def run(ar):
+        a0, a1 = ar.inp(d0[:N].contiguous(), what='out0'), ar.inp(d1[:N].contiguous(), what='out1')
+        f0 = ar.inp(d0[N:].contiguous(), what='out0f') if flip else None
+        f1 = ar.inp(d1[N:].contiguous(), what='out1f') if flip else None
+        det = ar.out((N, J, Hp, Wp), what='d_det')
+        tag = ar.out((N, J, Hp, Wp, T), what='d_tag')
+        ws = ar.ws(need)
+        args = (nv.dptr(a0), nv.dptr(a1), nv.dptr(f0), nv.dptr(f1), N, J)
+        if ex:
+            _ck(lib.lp_tta_merge_ex(*args, 2 * Jn, Jn, Jn, h0, w0, 2 * h0, 2 * w0, Hp, Wp, fi, nv.dptr(det), nv.dptr(tag),
+                                    nv.dptr(ws), need, nv.stream_ptr()), 'lp_tta_merge_ex')
+        else:
+            _ck(lib.lp_tta_merge(*args, h0, w0, 2 * h0, 2 * w0, Hp, Wp, fi, nv.dptr(det), nv.dptr(tag), nv.dptr(ws), need,
+                                 nv.stream_ptr()), 'lp_tta_merge')
+        return {'det': det, 'tag': tag}, []
+    z = _contract(run, 'lp_tta_merge%s' % ('_ex' if ex else ''))
+    keep0 = list(range(J)) + list(range(Jn, Jn + J))
+    outs = [o0[:N][:, keep0], o1[:N][:, :J]]
+    outs_f = [o0[N:][:, keep0], o1[N:][:, :J]] if flip else None
+    fh, tg = inference_ref.merge(outs, outs_f, inference_ref.TestCfg(flip_test=flip), (Wp, Hp))
+    np.testing.assert_allclose(z['det'].cpu().numpy(), fh.numpy(), rtol=0, atol=2e-6)
+    np.testing.assert_allclose(z['tag'].cpu().numpy(), tg.numpy(), rtol=0, atol=2e-6)
+
+
+def _stage(lib, nv, a0, a1, f0, f1, N, J, h0, w0, mid, need, adds=None):
+    fi = (C.c_int32 * J)(*_FLIP14[:J]) if J == 14 else (C.c_int32 * J)(*range(J))
+    if adds is None:
+        return _ck(lib.lp_tta_stage(nv.dptr(a0), nv.dptr(a1), nv.dptr(f0), nv.dptr(f1), N, J, 2 * J, J, J, h0, w0,
+                                    2 * h0, 2 * w0, fi, nv.dptr(mid), need, nv.stream_ptr()), 'lp_tta_stage')
+    return _ck(lib.lp_tta_stage_add(nv.dptr(a0), nv.dptr(a1), nv.dptr(f0), nv.dptr(f1),
+                                    *[nv.dptr(t) for t in adds], N, J, 2 * J, J, J, h0, w0, 2 * h0, 2 * w0, fi,
+                                    nv.dptr(mid), need, nv.stream_ptr()), 'lp_tta_stage_add')
+
+
+@pytest.mark.parametrize('flip', [True, False])
+def test_tta_stage_contract(flip):
+    """lp_tta_stage and lp_tta_stage_add into a poisoned mid: maps 0 and 2 always written, 1 and 3 with flip (header:
+    unspecified without).  stage_add bitwise equal to lp_tta_stage on out + add (its documented definition); the Z run's
+    projection against inference_ref.merge."""
+    nv = _nv()
+    lib = nv.lib()
+    N, J, h0, w0 = 3, 14, 32, 32
+    h1, w1 = 2 * h0, 2 * w0
+    NB = 2 * N if flip else N
+    o0, o1 = _rand_outs(11, NB, 2 * J, J, h0, w0)
+    p0, p1 = _rand_outs(12, NB, 2 * J, J, h0, w0)
+    need = int(lib.lp_tta_workspace_bytes(N, J, h1, w1))
+    maps = [0, 1, 2, 3] if flip else [0, 2]
+    res = {}
+    for add in (False, True):
+        def run(ar):
+            src0 = (o0 if add else o0 + p0).cuda()
+            src1 = (o1 if add else o1 + p1).cuda()
+            a0, a1 = ar.inp(src0[:N].contiguous()), ar.inp(src1[:N].contiguous())
+            f0 = ar.inp(src0[N:].contiguous()) if flip else None
+            f1 = ar.inp(src1[N:].contiguous()) if flip else None
+            adds = None
+            if add:
+                adds = [ar.inp(p0[:N].contiguous().cuda()), ar.inp(p1[:N].contiguous().cuda()),
+                        ar.inp(p0[N:].contiguous().cuda()) if flip else None,
+                        ar.inp(p1[N:].contiguous().cuda()) if flip else None]
+            mid = ar.ws(need, what='d_mid')
+            _stage(lib, nv, a0, a1, f0, f1, N, J, h0, w0, mid, need, adds)
+            v = mid[:N * 4 * J * h1 * w1 * 4].view(torch.float32).view(N, 4, J, h1, w1)
+            return {'map%d' % k: v[:, k].contiguous() for k in maps}, []
+        res[add] = _contract(run, 'lp_tta_stage%s' % ('_add' if add else ''))
+    for k in maps:
+        assert bitwise_equal(res[True]['map%d' % k], res[False]['map%d' % k]), k
+    mid = torch.zeros(N, 4, J, h1, w1, device='cuda')
+    for k in maps:
+        mid[:, k] = res[False]['map%d' % k]
+    T = 2 if flip else 1
+    det = torch.empty(N, J, 2 * h1, 2 * w1, device='cuda')
+    tag = torch.empty(N, J, 2 * h1, 2 * w1, T, device='cuda')
+    _ck(lib.lp_tta_project(nv.dptr(mid), N, J, h1, w1, 2 * h1, 2 * w1, T, nv.dptr(det), nv.dptr(tag), nv.stream_ptr()),
+        'lp_tta_project')
+    s0, s1 = o0 + p0, o1 + p1
+    fh, tg = inference_ref.merge([s0[:N], s1[:N]], [s0[N:], s1[N:]] if flip else None,
+                                 inference_ref.TestCfg(flip_test=flip), (2 * h1, 2 * w1))
+    np.testing.assert_allclose(det.cpu().numpy(), fh.numpy(), rtol=0, atol=2e-6)
+    np.testing.assert_allclose(tag.cpu().numpy(), tg.numpy(), rtol=0, atol=2e-6)
+
+
+def test_maps_accumulate_contract():
+    """lp_maps_accumulate in place: d_acc[i] += d_src[i] for i < count (a count that is not a multiple of 4: the vector
+    tail), bitwise the torch sum; the rest of the accumulator's buffer is left unchanged; 16-byte alignment."""
+    nv = _nv()
+    lib = nv.lib()
+    count, extra = 4093, 45
+    g = torch.Generator().manual_seed(3)
+    acc0 = torch.randn(count, generator=g).cuda()
+    src0 = torch.randn(count, generator=g).cuda()
+
+    def run(ar):
+        acc = ar.out((count + extra,), align=16, what='d_acc')
+        acc[:count].copy_(acc0)
+        before = acc[count:].clone()
+        src = ar.inp(src0, align=16, what='d_src')
+        _ck(lib.lp_maps_accumulate(nv.dptr(acc), nv.dptr(src), count, nv.stream_ptr()), 'lp_maps_accumulate')
+        return {'acc': acc[:count]}, [('tail past count', acc[count:], before)]
+    z = _contract(run, 'lp_maps_accumulate')
+    assert bitwise_equal(z['acc'], acc0 + src0)
+
+
+def _ms_cfg(scales, p2i):
+    from litepose_amd import config
+    cfg = config.get_cfg('crowd_pose')
+    cfg.TEST.SCALE_FACTOR = list(scales)
+    cfg.TEST.PROJECT2IMAGE = p2i
+    return cfg
+
+
+@pytest.mark.parametrize('case', [([1, 2], 2, False, 2, 3, [(26, 42), (13, 21)], None),
+                                  ([0.5, 1, 2], 1, True, 2, 4, [(32, 24), (16, 12), (8, 6)], (24, 32)),
+                                  ([1, 0.5], 2, False, 2, 3, [(17, 9), (9, 5)], None)])
+def test_merge_scales_contract(case):
+    """lp_tta_merge_scales into poisoned det / tag (d_tag at 8-byte alignment with T = 2), mids wrapped in guards; the
+    Z run bitwise equal to the batch-1 chain (tta_project per scale + aggregate_results + / len(SCALE_FACTOR)) of
+    test_gpu_eval_multiscale.py."""
+    from litepose_amd import _native as nvm
+    from test_gpu_eval_multiscale import _chain, _mid
+    lib = nvm.lib()
+    scales, T, p2i, N, J, hw, base = case
+    cfg = _ms_cfg(scales, p2i)
+    rng = np.random.default_rng(7)
+    mids = [_mid(rng, N, J, h1, w1) + (h1, w1) for h1, w1 in hw]
+    Hf, Wf = (base[1], base[0]) if p2i else hw[0]
+    from litepose_amd.core import inference
+    _, unit = inference.scale_order(cfg)
+
+    def run(ar):
+        wrapped = [ar.inp(buf, what='mid %d' % s) for s, (buf, _, _, _) in enumerate(mids)]
+        tab = (nvm.LpScaleMid * len(mids))(*[nvm.LpScaleMid(w.data_ptr(), h1, w1) for w, (_, _, h1, w1)
+                                              in zip(wrapped, mids)])
+        det = ar.out((N, J, Hf, Wf), what='d_det')
+        tag = ar.out((N, J, Hf, Wf, T), align=8, what='d_tag')
+        _ck(lib.lp_tta_merge_scales(tab, len(mids), unit, N, J, T, int(p2i), Hf, Wf, nvm.dptr(det), nvm.dptr(tag),
+                                    nvm.stream_ptr()), 'lp_tta_merge_scales')
+        return {'det': det, 'tag': tag}, []
+    z = _contract(run, 'lp_tta_merge_scales')
+    fd, ft = _chain(cfg, mids, N, J, T, base)
+    assert bitwise_equal(z['det'], fd.contiguous()) and bitwise_equal(z['tag'], ft.contiguous())
+
+
+# ------------------------------------------------------------------ AE parser
+def _parser(J, pcap, nms):
+    from litepose_amd.core import group
+    from test_gpu_ae_mid import _cfg
+    cfg = _cfg(J)
+    cfg.TEST.NMS_KERNEL, cfg.TEST.NMS_PADDING = nms, nms // 2
+    return group.HeatmapParser(cfg, person_capacity=pcap)
+
+
+# (id, J, N, h1, w1, T, NMS_KERNEL, pcap, people per image, calls that refuse the shape by their documented gates)
+AE_CASES = [
+    ('w64_t2', 14, 3, 64, 64, 2, 5, 30, [3, 0, 9], ()),
+    ('w64_t1', 17, 3, 64, 64, 1, 5, 30, [5, 2, 7], ()),
+    # odd w1: the band top-k of lp_parse_mid; W % 4 != 0: the generic top-k of lp_parse; lp_parse_dm refuses W % 4
+    ('w37_odd', 14, 2, 40, 37, 2, 5, 30, [4, 6], ('lp_parse_dm',)),
+    ('w37_odd_t1', 14, 2, 40, 37, 1, 3, 30, [4, 6], ('lp_parse_dm',)),
+    # refine_dm: 256-thread workgroups up to 128 stage-1 columns, the walk up to 512, refine_mid_kernel above
+    ('w128', 14, 2, 48, 128, 2, 3, 30, [5, 8], ()),
+    ('w130', 14, 2, 48, 130, 2, 3, 30, [5, 8], ()),
+    ('w512', 14, 1, 24, 512, 1, 5, 30, [9], ()),
+    ('w514', 14, 1, 24, 514, 2, 5, 30, [9], ()),
+    # peaks_topk_mid_kernel (odd w1, NMS 7): PM_THREADS / (2 * w1) row segments per band, 2 up to 2 * w1 = 512, 1 above
+    # (its LDS band refuses 2 * w1 near PM_THREADS itself: LP_ERR_UNSUPPORTED)
+    ('w255_pm', 14, 1, 24, 255, 2, 5, 30, [7], ('lp_parse_dm',)),
+    ('w257_pm', 14, 1, 24, 257, 1, 5, 30, [7], ('lp_parse_dm',)),
+    ('w256_nms7_pm', 14, 1, 24, 256, 2, 7, 30, [7], ()),
+    ('w258_nms7_pm', 14, 1, 24, 258, 2, 7, 30, [7], ()),
+    # N * J on both sides of 256: the walk's 16- / 4-wave forms, refine's "few" forms
+    ('nj252', 14, 18, 32, 32, 2, 5, 30, [2, 1, 3], ()),
+    ('nj266', 14, 19, 32, 32, 2, 5, 30, [2, 1, 3], ()),
+    ('nj252_t1', 14, 18, 32, 32, 1, 5, 30, [2, 1, 3], ()),
+    ('nms3', 14, 2, 48, 64, 2, 3, 30, [6, 3], ()),
+    ('nms7', 14, 2, 48, 64, 2, 7, 30, [6, 3], ()),
+    # more persons than record slots: rows at or beyond pcap are dropped, the count still reports them
+    ('pcap4', 14, 3, 64, 64, 2, 5, 4, [5, 12, 2], ()),
+]
+
+
+def _mid_input(ar, mid_np, T):
+    """mid as an input wrapped in guards; maps 1 and 3 poisoned with the run's pattern when T = 1."""
+    m = torch.from_numpy(mid_np).cuda()
+    if T == 1:
+        v = m.view(m.shape[0], 4, -1)
+        for k in (1, 3):
+            fill(v[:, k], ar.pattern)
+    return ar.inp(m, what='d_mid')
+
+
+@pytest.mark.parametrize('case', AE_CASES, ids=lambda c: c[0])
+def test_ae_contract(case):
+    """Every AE entry point on one scene under the contract, chained on the Z results: lp_tta_project (full and det-only),
+    lp_peaks_topk, lp_group, lp_adjust_refine (in place on d_ans: rows at or beyond min(count, pcap) unchanged),
+    lp_parse, lp_parse_mid, lp_parse_dm, lp_final_preds(_v) (in place: x, y of rows < min(count, pcap) only).  Records
+    are compared WHOLE: d_ans is cleared past the persons and d_scores is 0 past min(count, pcap) (header).  Z run:
+    lp_parse against group_ref.HeatmapParser bit for bit; every other path bitwise equal to lp_parse."""
+    from test_gpu_ae_mid import _mid_scene
+    nv = _nv()
+    lib = nv.lib()
+    cid, J, N, h1, w1, T, nms, pcap, people, refused = case
+    H, W = 2 * h1, 2 * w1
+    mid_np = _mid_scene(900 + h1 + w1 + J, N, J, h1, w1, T, people)
+    p = _parser(J, pcap, nms)
+    q, M = p._q, p.params.max_num_people
+    D = 3 + T
+    st = nv.stream_ptr
+
+    def run_proj(ar):
+        m = _mid_input(ar, mid_np, T)
+        det = ar.out((N, J, H, W), what='d_det')
+        tag = ar.out((N, J, H, W, T), align=8, what='d_tag')
+        _ck(lib.lp_tta_project(nv.dptr(m), N, J, h1, w1, H, W, T, nv.dptr(det), nv.dptr(tag), st()), 'lp_tta_project')
+        return {'det': det, 'tag': tag}, []
+    z = _contract(run_proj, cid + '/lp_tta_project')
+    det, tag = z['det'], z['tag']
+
+    def run_proj_det(ar):
+        m = _mid_input(ar, mid_np, T)
+        d = ar.out((N, J, H, W), what='d_det')
+        _ck(lib.lp_tta_project(nv.dptr(m), N, J, h1, w1, H, W, T, nv.dptr(d), None, st()), 'lp_tta_project(det)')
+        return {'det': d}, []
+    assert bitwise_equal(_contract(run_proj_det, cid + '/lp_tta_project(det only)')['det'], det)
+
+    def run_topk(ar):
+        d, t = ar.inp(det, what='d_det'), ar.inp(tag, align=8, what='d_tag')
+        vk = ar.out((N, J, M), what='d_val_k')
+        ik = ar.out((N, J, M), torch.int32, what='d_ind_k')
+        tk = ar.out((N, J, M, T), what='d_tag_k')
+        _ck(lib.lp_peaks_topk(nv.dptr(d), nv.dptr(t), N, J, H, W, T, C.byref(q), nv.dptr(vk), nv.dptr(ik), nv.dptr(tk),
+                              st()), 'lp_peaks_topk')
+        return {'val_k': vk, 'ind_k': ik, 'tag_k': tk}, []
+    k = _contract(run_topk, cid + '/lp_peaks_topk')
+
+    def run_group(ar):
+        vk, ik, tk = ar.inp(k['val_k']), ar.inp(k['ind_k']), ar.inp(k['tag_k'])
+        ans = ar.out((N, pcap, J, D), what='d_ans')
+        cnt = ar.out((N,), torch.int32, what='d_count')
+        _ck(lib.lp_group(nv.dptr(vk), nv.dptr(ik), nv.dptr(tk), N, W, T, C.byref(q), pcap, nv.dptr(ans), nv.dptr(cnt),
+                         st()), 'lp_group')
+        return {'ans': ans, 'count': cnt}, []
+    g = _contract(run_group, cid + '/lp_group')
+    count = g['count']
+    P = [min(max(int(c), 0), pcap) for c in count.cpu()]
+
+    def inplace_records(ar, src, what='d_ans'):
+        """d_ans for an in-place call: the run's poison everywhere, the documented rows (< min(count, pcap)) from src;
+        returns (buffer, [(region name, region, expected)] of the rows the call must leave alone)."""
+        ans = ar.out((N, pcap, J, D), what=what)
+        keep = []
+        for n in range(N):
+            ans[n, :P[n]] = src[n, :P[n]]
+            keep.append(('%s rows >= %d of image %d' % (what, P[n], n), ans[n, P[n]:], ans[n, P[n]:].clone()))
+        return ans, keep
+
+    def rows(t):
+        return torch.cat([t[n, :P[n]].reshape(-1) for n in range(N)])
+
+    def run_adjust(ar):
+        d, t, c = ar.inp(det), ar.inp(tag, align=8), ar.inp(count, what='d_count')
+        ans, keep = inplace_records(ar, g['ans'])
+        sc = ar.out((N, pcap), what='d_scores')
+        need = int(lib.lp_refine_workspace_bytes(N, pcap))
+        ws = ar.ws(need)
+        _ck(lib.lp_adjust_refine(nv.dptr(d), nv.dptr(t), N, J, H, W, T, pcap, 1, 1, nv.dptr(ans), nv.dptr(c),
+                                 nv.dptr(sc), nv.dptr(ws), need, st()), 'lp_adjust_refine')
+        return {'ans rows': rows(ans), 'scores': sc}, keep
+    ar_z = _contract(run_adjust, cid + '/lp_adjust_refine')
+
+    need_p = int(lib.lp_parse_workspace_bytes(N, J, M, T, pcap))
+    results = {}
+    for call in ('lp_parse', 'lp_parse_mid', 'lp_parse_dm'):
+        if call in refused:
+            continue
+
+        def run_parse(ar):
+            ans = ar.out((N, pcap, J, D), what='d_ans')
+            cnt = ar.out((N,), torch.int32, what='d_count')
+            sc = ar.out((N, pcap), what='d_scores')
+            ws = ar.ws(need_p)
+            tail = (C.byref(q), pcap, 1, 1, nv.dptr(ans), nv.dptr(cnt), nv.dptr(sc), nv.dptr(ws), need_p, st())
+            if call == 'lp_parse':
+                d, t = ar.inp(det), ar.inp(tag, align=8)
+                _ck(lib.lp_parse(nv.dptr(d), nv.dptr(t), N, J, H, W, T, *tail), call)
+            elif call == 'lp_parse_mid':
+                m = _mid_input(ar, mid_np, T)
+                _ck(lib.lp_parse_mid(nv.dptr(m), N, J, h1, w1, T, *tail), call)
+            else:
+                d, m = ar.inp(det), _mid_input(ar, mid_np, T)
+                _ck(lib.lp_parse_dm(nv.dptr(d), nv.dptr(m), N, J, h1, w1, T, *tail), call)
+            return {'ans': ans, 'count': cnt, 'scores': sc}, []
+        results[call] = _contract(run_parse, '%s/%s' % (cid, call))
+    ref = results['lp_parse']
+    for call, r in results.items():
+        for key in ('ans', 'count', 'scores'):
+            assert bitwise_equal(r[key], ref[key]), (cid, call, key, first_difference(r[key], ref[key]))
+    assert bitwise_equal(ref['count'], count)
+    assert bitwise_equal(ar_z['ans rows'], rows(ref['ans'])) and bitwise_equal(ar_z['scores'], ref['scores'])
+    for n in range(N):                                   # the scores tail is defined: 0 past min(count, pcap)
+        assert not as_bits(ref['scores'][n, P[n]:]).any(), (cid, n)
+    # the oracle parser on the projected maps
+    ora = group_ref.HeatmapParser(_oracle_params(J, nms))
+    a_np, s_np, c_np = ref['ans'].cpu().numpy(), ref['scores'].cpu().numpy(), ref['count'].cpu().numpy()
+    det_np, tag_np = det.cpu().numpy(), tag.cpu().numpy()
+    for n in range(min(N, 3)):
+        a, s = ora.parse_image(det_np[n], tag_np[n], True, True)
+        assert c_np[n] == a.shape[0], (cid, n, c_np[n], a.shape)
+        assert np.array_equal(a_np[n, :P[n]], a[:P[n]]) and np.array_equal(s_np[n, :P[n]], s[:P[n]]), (cid, n)
+    if cid == 'pcap4':
+        assert int(count.max()) > pcap
+    else:
+        assert int(count.sum()) >= 1, cid
+    _final_preds_contract(cid, lib, nv, ref['ans'], count, N, pcap, J, T, P, inplace_records)
+
+
+def _oracle_params(J, nms):
+    prm = group_ref.Params(num_joints=J)
+    prm.nms_kernel, prm.nms_padding = nms, nms // 2
+    return prm
+
+
+def _final_preds_contract(cid, lib, nv, ans_src, count, N, pcap, J, T, P, inplace_records):
+    from litepose_amd.utils import transforms as tf
+    centers = [(61.5 + 7 * n, 43.25 - 3 * n) for n in range(N)]
+    scales = [(1.7 + 0.1 * n, 1.7 + 0.1 * n) for n in range(N)]
+    Wp, Hp = 128, 96
+    coef = torch.tensor([list(tf.final_preds_coef(centers[n], scales[n], (Wp, Hp))) for n in range(N)],
+                        dtype=torch.float64)
+    for call in ('lp_final_preds', 'lp_final_preds_v'):
+        def run(ar):
+            c = ar.inp(count, what='d_count')
+            ans, keep = inplace_records(ar, ans_src)
+            for n in range(N):
+                keep.append(('val / tags of image %d' % n, ans[n, :P[n], :, 2:], ans[n, :P[n], :, 2:].clone()))
+            if call == 'lp_final_preds':
+                cc = (C.c_double * 2)(*centers[0])
+                ss = (C.c_double * 2)(*scales[0])
+                _ck(lib.lp_final_preds(nv.dptr(ans), nv.dptr(c), N, pcap, J, T, cc, ss, Wp, Hp, nv.stream_ptr()), call)
+            else:
+                d_coef = ar.inp(coef.cuda(), what='d_coef')
+                _ck(lib.lp_final_preds_v(nv.dptr(ans), nv.dptr(c), N, pcap, J, T, nv.dptr(d_coef), nv.stream_ptr()), call)
+            return {'xy image %d' % n: ans[n, :P[n], :, :2].contiguous() for n in range(N)}, keep
+        z = _contract(run, '%s/%s' % (cid, call))
+        a = ans_src.cpu().numpy().astype(np.float64)
+        for n in range(N):
+            cf = coef[0 if call == 'lp_final_preds' else n].numpy()
+            exp = np.stack([cf[0] * a[n, :P[n], :, 0] + cf[1], cf[2] * a[n, :P[n], :, 1] + cf[3]], -1).astype(np.float32)
+            # the kernel's fp64 multiply-add may be fused: within one fp32 ulp of the unfused NumPy value
+            np.testing.assert_array_max_ulp(z['xy image %d' % n].cpu().numpy(), exp, maxulp=1)
+
+
+# ------------------------------------------------------------------ T = 1: maps 1 and 3 of mid are unspecified
+def test_tta_stage_t1_unused_maps():
+    """Without flip lp_tta_stage leaves maps 1 and 3 of mid unspecified.  After a real stage merge, those maps alone are
+    poisoned N and then H: lp_tta_project, lp_parse_mid, lp_parse_dm and lp_tta_merge_scales must give the very bits of
+    the Z run."""
+    nv = _nv()
+    lib = nv.lib()
+    N, J, h0, w0 = 3, 14, 24, 32
+    h1, w1, H, W = 2 * h0, 2 * w0, 4 * h0, 4 * w0
+    o0, o1 = _rand_outs(31, N, 2 * J, J, h0, w0)
+    o0, o1 = 0.05 * o0, 0.05 * o1
+    rng = np.random.default_rng(2)
+    for n in range(N):                                   # blobs in the stage-1 heatmaps: persons to group
+        d, t = synth.blob_scene(rng, J, h1, w1, 1, n_people=[4, 0, 7][n], sigma=2.0)
+        o1[n] += torch.from_numpy(d)
+        o0[n, J:] += torch.from_numpy(t[..., 0][:, ::2, ::2].copy())
+    need = int(lib.lp_tta_workspace_bytes(N, J, h1, w1))
+    mid = torch.empty(need, dtype=torch.uint8, device='cuda')
+    _stage(lib, nv, o0.cuda(), o1.cuda(), None, None, N, J, h0, w0, mid, need)
+    torch.cuda.synchronize()
+    mv = mid[:N * 4 * J * h1 * w1 * 4].view(torch.float32).view(N, 4, J, h1, w1)
+    p = _parser(J, 30, 5)
+    q, M, pcap = p._q, p.params.max_num_people, 30
+    need_p = int(lib.lp_parse_workspace_bytes(N, J, M, 1, pcap))
+    out = {}
+    for pat in PATTERNS:
+        fill(mv[:, 1], pat)
+        fill(mv[:, 3], pat)
+        r = {}
+        det = torch.empty(N, J, H, W, device='cuda')
+        tag = torch.empty(N, J, H, W, 1, device='cuda')
+        _ck(lib.lp_tta_project(nv.dptr(mid), N, J, h1, w1, H, W, 1, nv.dptr(det), nv.dptr(tag), nv.stream_ptr()), 'proj')
+        r['det'], r['tag'] = det, tag
+        for call in ('lp_parse_mid', 'lp_parse_dm'):
+            ans = torch.empty(N, pcap, J, 4, device='cuda')
+            cnt = torch.empty(N, dtype=torch.int32, device='cuda')
+            sc = torch.empty(N, pcap, device='cuda')
+            ws = torch.empty(need_p, dtype=torch.uint8, device='cuda')
+            tail = (C.byref(q), pcap, 1, 1, nv.dptr(ans), nv.dptr(cnt), nv.dptr(sc), nv.dptr(ws), need_p, nv.stream_ptr())
+            if call == 'lp_parse_mid':
+                _ck(lib.lp_parse_mid(nv.dptr(mid), N, J, h1, w1, 1, *tail), call)
+            else:
+                _ck(lib.lp_parse_dm(nv.dptr(det), nv.dptr(mid), N, J, h1, w1, 1, *tail), call)
+            r[call] = (ans, cnt, sc)
+        dets = torch.empty(N, J, h1, w1, device='cuda')
+        tags = torch.empty(N, J, h1, w1, 1, device='cuda')
+        tab = (nv.LpScaleMid * 1)(nv.LpScaleMid(mid.data_ptr(), h1, w1))
+        _ck(lib.lp_tta_merge_scales(tab, 1, 0, N, J, 1, 0, h1, w1, nv.dptr(dets), nv.dptr(tags), nv.stream_ptr()),
+            'lp_tta_merge_scales')
+        r['ms'] = (dets, tags)
+        torch.cuda.synchronize()
+        out[pat] = r
+    z = out['Z']
+    for pat in ('N', 'H'):
+        for key in z:
+            a, b = z[key], out[pat][key]
+            for x, y in (zip(a, b) if isinstance(a, tuple) else [(a, b)]):
+                assert bitwise_equal(x, y), (pat, key, first_difference(x, y))
+    assert int(z['lp_parse_mid'][1].sum()) >= 3
+    assert bitwise_equal(z['lp_parse_mid'][0], z['lp_parse_dm'][0])
+
+
+# ------------------------------------------------------------------ pre-processing
+def test_preprocess_contract():
+    """lp_preprocess, lp_preprocess_batch and lp_preprocess_batch_v into poisoned outputs (both d_resized_u8 and
+    d_tensor), images and the descriptor table wrapped in guards; the Z run against preprocess_ref bit for bit."""
+    from litepose_amd.utils import transforms as tf
+    from oracle import preprocess_ref
+    nv = _nv()
+    lib = nv.lib()
+    rng = np.random.default_rng(4)
+    same = [rng.integers(0, 256, (97, 131, 3), dtype=np.uint8) for _ in range(3)]
+    size, center, scale = tf.get_multi_scale_size(same[0], 64, 1.0, 1.0)
+    Wd, Hd = int(size[0]), int(size[1])
+    trans = tf.get_affine_transform(center, scale, 0, size)
+    h_trans = (C.c_double * 6)(*np.asarray(trans, np.float64).reshape(-1))
+    mean = (C.c_float * 3)(*tf.IMAGENET_MEAN)
+    std = (C.c_float * 3)(*tf.IMAGENET_STD)
+    refs = [preprocess_ref.resize_align_multi_scale(im, 64, 1.0, 1.0)[0] for im in same]
+    imgs = torch.from_numpy(np.stack(same)).cuda()
+    N = len(same)
+    # batch_v: other sizes in the same bucket, packed with gaps
+    mixed = [rng.integers(0, 256, s, dtype=np.uint8) for s in ((97, 131, 3), (90, 121, 3))]
+    offs, buf = [], np.zeros(0, np.uint8)
+    for im in mixed:
+        buf = np.concatenate([buf, np.zeros(13, np.uint8)])
+        offs.append(buf.size)
+        buf = np.concatenate([buf, im.reshape(-1)])
+    desc = np.zeros(len(mixed), tf.WARP_DESC_DTYPE)
+    vsize = None
+    for n, im in enumerate(mixed):
+        sz, ce, scl = tf.get_multi_scale_size(im, 64, 1.0, 1.0)
+        vsize = sz if vsize is None else vsize
+        desc[n] = (offs[n], im.shape[0], im.shape[1], tf.warp_invert(tf.get_affine_transform(ce, scl, 0, vsize)))
+    src = torch.from_numpy(buf).cuda()
+    d_desc = torch.from_numpy(desc.view(np.uint8).reshape(len(mixed), 64).copy()).cuda()
+    Wv, Hv = int(vsize[0]), int(vsize[1])
+    for call in ('lp_preprocess', 'lp_preprocess_batch', 'lp_preprocess_batch_v'):
+        n_img = {'lp_preprocess': 1, 'lp_preprocess_batch': N, 'lp_preprocess_batch_v': len(mixed)}[call]
+        hd, wd = (Hv, Wv) if call == 'lp_preprocess_batch_v' else (Hd, Wd)
+
+        def run(ar):
+            u8 = ar.out((n_img, hd, wd, 3), torch.uint8, what='d_resized_u8')
+            ten = ar.out((n_img, 3, hd, wd), what='d_tensor')
+            if call == 'lp_preprocess':
+                im = ar.inp(imgs[0].contiguous(), what='d_image')
+                _ck(lib.lp_preprocess(nv.dptr(im), 97, 131, h_trans, Hd, Wd, mean, std, nv.dptr(u8), nv.dptr(ten),
+                                      nv.stream_ptr()), call)
+            elif call == 'lp_preprocess_batch':
+                im = ar.inp(imgs, what='d_images')
+                _ck(lib.lp_preprocess_batch(nv.dptr(im), N, 97, 131, h_trans, Hd, Wd, mean, std, nv.dptr(u8),
+                                            nv.dptr(ten), nv.stream_ptr()), call)
+            else:
+                s = ar.inp(src, what='d_src')
+                dd = ar.inp(d_desc, what='d_desc')
+                _ck(lib.lp_preprocess_batch_v(nv.dptr(s), src.numel(), nv.dptr(dd), len(mixed), Hv, Wv, mean, std,
+                                              nv.dptr(u8), nv.dptr(ten), nv.stream_ptr()), call)
+            return {'u8': u8, 'tensor': ten}, []
+        z = _contract(run, call)
+        got_u8, got = z['u8'].cpu().numpy(), z['tensor'].cpu().numpy()
+        for n in range(n_img):
+            if call == 'lp_preprocess_batch_v':
+                r = preprocess_ref.warp_affine_u8(mixed[n], tf.get_affine_transform(
+                    *tf.get_multi_scale_size(mixed[n], 64, 1.0, 1.0)[1:], 0, vsize), vsize)
+            else:
+                r = refs[n]
+            assert np.array_equal(got_u8[n], r), (call, n)
+            assert np.array_equal(got[n], preprocess_ref.to_tensor_normalize(r)), (call, n)
+
+
+# ------------------------------------------------------------------ the serving loop
+def _engine_tensors(eng):
+    """Every device tensor an engine (its pipelined halves and its serving lanes included) holds in its buffer dicts."""
+    engines = [eng] + list(getattr(eng, '_half', None) or []) + [ln['eng'] for ln in (eng._lanes or [])]
+    seen, out = set(), []
+
+    def walk(o):
+        if torch.is_tensor(o):
+            if o.is_cuda and o.data_ptr() not in seen:
+                seen.add(o.data_ptr())
+                out.append(o)
+        elif isinstance(o, dict):
+            for v in o.values():
+                walk(v)
+        elif isinstance(o, (list, tuple)):
+            for v in o:
+                walk(v)
+    for e in engines:
+        walk(e._bufs)
+    return out
+
+
+def _poison_engine(eng, pat):
+    torch.cuda.synchronize()
+    ts = _engine_tensors(eng)
+    half = eng.model.storage == 'f16'
+    for t in ts:
+        fill(t, pat, half=half and t.dtype == torch.uint8 and t.numel() > (1 << 20))
+    torch.cuda.synchronize()
+    return ts
+
+
+def _scene(seed, N, R):
+    x = synth.make_images(N, R, seed=seed).cuda()
+    off0, off1 = synth.lowres_offsets(seed + 10, N, 14, R)
+    f0, f1 = synth.flip_offsets(off0, off1, _FLIP14)
+    return x, (torch.from_numpy(np.concatenate([off0, f0])).cuda(), torch.from_numpy(np.concatenate([off1, f1])).cuda())
+
+
+_ENGINE_CASES = [('infer', 'mid', 'f32'), ('infer', 'dm', 'f32'), ('infer', 'maps', 'f32'),
+                 ('submit', 'mid', 'f32'), ('submit', 'dm', 'bf16'), ('submit', 'maps', 'f16'),
+                 ('submit', 'mid', 'bf16'), ('infer', 'mid', 'f16')]
+
+
+@pytest.mark.parametrize('mode,ae,storage', _ENGINE_CASES)
+def test_engine_serving_loop_contract(mode, ae, storage):
+    """Batch A through a PoseEngine, then every tensor of its buffers (records, maps, network outputs, the three
+    workspaces, the lanes' and halves' own) filled N and then H, then batch B: B's records equal a fresh engine's on B.
+    mode 'submit': after prepare() every batch is a graph replay on the poisoned buffers (graphs keep their pointers)."""
+    from litepose_amd import arch_zoo, config, engine
+    arch = arch_zoo.get('search-XS')
+    cfg = config.apply_arch(config.get_cfg(), arch)
+    sd = synth.make_state_dict(arch, seed=1234, head_gain=0.25)
+    N, R = 4, 128
+    xa, oa = _scene(3, N, R)
+    xb, ob = _scene(4, N, R)
+
+    def make():
+        return engine.PoseEngine(cfg, arch, sd, person_capacity=30, storage=storage, ae=ae)
+
+    def run(eng, x, offs):
+        if mode == 'infer':
+            res = eng.infer_batch(x, offsets=offs)
+        else:
+            stage_x.copy_(x)
+            for s, o in zip(stage_o, offs):
+                s.copy_(o)
+            with eng.submit(stage_x, offsets=stage_o) as res:
+                res = [t.clone() for t in res]
+        torch.cuda.synchronize()
+        return [t.clone() for t in res]
+
+    stage_x = torch.empty_like(xa)
+    stage_o = tuple(torch.empty_like(o) for o in oa)
+    fresh = make()
+    ref = run(fresh, xb, ob)
+    del fresh
+    eng = make()
+    if mode == 'submit':
+        stage_x.copy_(xa)
+        for s, o in zip(stage_o, oa):
+            s.copy_(o)
+        eng.prepare(stage_x, offsets=stage_o)
+    for pat in ('N', 'H'):
+        run(eng, xa, oa)
+        ts = _poison_engine(eng, pat)
+        assert len(ts) >= 7, len(ts)
+        replays = eng._stats['graph_replays']
+        got = run(eng, xb, ob)
+        if mode == 'submit':
+            assert eng._stats['graph_replays'] > replays
+        for k, (g, r) in enumerate(zip(got, ref)):
+            assert bitwise_equal(g, r), (mode, ae, storage, pat, k, first_difference(g, r))
+    assert int(ref[1].sum()) >= 1
+
+
+def test_engine_multiscale_no_project2image_contract():
+    """The multi-scale path without PROJECT2IMAGE (infer_batch on a tuple: lp_tta_stage per scale, lp_tta_merge_scales,
+    lp_parse, lp_final_preds_v, the path ``evaluate`` takes): every buffer poisoned between two batches, N and H."""
+    from litepose_amd import arch_zoo, config, engine
+    from litepose_amd.utils import transforms as tf
+    arch = arch_zoo.get('search-XS')
+    cfg = config.apply_arch(config.get_cfg(), arch)
+    cfg.TEST.SCALE_FACTOR = [1, 0.5]
+    cfg.TEST.PROJECT2IMAGE = False
+    sd = synth.make_state_dict(arch, seed=1234, head_gain=0.25)
+    N = 2
+
+    def batch(seed):
+        return (synth.make_images(N, 128, seed=seed).cuda(), synth.make_images(N, 64, seed=seed + 1).cuda())
+    coef = torch.tensor([list(tf.final_preds_coef((64.0, 64.0), (0.64, 0.64), (64, 64)))] * N,
+                        dtype=torch.float64).cuda()
+    xa, xb = batch(5), batch(7)
+    fresh = engine.PoseEngine(cfg, arch, sd, person_capacity=30)
+    ref = [t.clone() for t in fresh.infer_batch(xb, preds_coef=coef)]
+    torch.cuda.synchronize()
+    del fresh
+    eng = engine.PoseEngine(cfg, arch, sd, person_capacity=30)
+    for pat in ('N', 'H'):
+        eng.infer_batch(xa, preds_coef=coef)
+        ts = _poison_engine(eng, pat)
+        assert any(t.dim() == 5 for t in ts)                   # the merged tag maps of the 'ms' buffers
+        got = [t.clone() for t in eng.infer_batch(xb, preds_coef=coef)]
+        torch.cuda.synchronize()
+        for k, (g, r) in enumerate(zip(got, ref)):
+            assert bitwise_equal(g, r), (pat, k, first_difference(g, r))

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 namespace lp {
 
@@ -2929,36 +2930,87 @@ void launch_deconv4(const float* inA, int Ca, const float* inB, int Cb, const fl
 // (16 v_mfma_f32_32x32x2_f32 = 1024 cycles per channel PAIR and wave); here a k-step is 16 channels
 // (lanes 0-31: channels 16ks..16ks+7, lanes 32-63: 16ks+8..15 of the concatenated sources) and a
 // (parity, tap) product is six v_mfma_f32_32x32x16_bf16 = 192 cycles per 16 channels -- 2.67x fewer
-// matrix-core cycles at fp32 accuracy.  Views are walked one at a time: 8 channel values per lane are
-// loaded (next view in flight under this view's MFMAs), split once into three bf16 pieces and feed every
-// (parity, tap) that reads this view (centre 4, edges 2, corners 1).
+// matrix-core cycles at fp32 accuracy.
+//
+// A workgroup owns a 2-D tile of ONE image: 4 waves x 32 cells, TW = 32 or 16 columns wide (D4X3 below).  The tile
+// plus a one-cell halo is staged ONCE: every input value is loaded once (dword loads, lanes along the rows of the halo
+// tile), split once into hi / mid / lo and stored as the 16-byte B-fragment record the MFMA reads (8 channels of one
+// cell, one record per piece, the three pieces of a cell side by side: 48 B per cell and channel group).  Cells
+// outside the image are stored as zeros.  The nine shifted views of a k-step are then three ds_read_b128 each at a cell
+// offset; a view feeds every (parity, tap) that reads it (centre 4, edges 2, corners 1).  The 48-byte cell stride puts
+// the 16 lanes of every ds_read_b128 lane group on 16 distinct 16-byte slots and the 8 lanes of every ds_write_b128
+// group on disjoint banks (tools/lds_model.py, deconv4x3).
+// K is staged in equal slabs of at most D4X3::slab_groups() channel groups (48 channels at TW = 32: 58.75 KB, below the
+// 64 KB that need an attribute; the launcher sizes them); one slab holds all of K <= 48.  The workgroups that share a
+// CU (3 at K = 40) cover each other's staging.  Raw fp32 records (32 B per cell and group instead of 48) would keep
+// the split on the nine views' side, 9x the VALU work, for a third less LDS: not taken.
+// Each accumulator receives the sequence of the first form of this kernel (views fetched from global memory one at a
+// time): k-steps ascending, views 0..8, the (q, t) order below, mma6's piece order; a cell's result does not depend on
+// which cells share its wave, so the output is bit-identical to that form on every shape.
 // Weights: [block][parity][tap][ks][piece hi,mid,lo][64 lanes] x 16 B.  DUAL = false (plain head): the refined source only.
+// Bound: no longer the input side.  deconv.2 of XS runs at ~40 % of its MFMA floor (launcher comment); the 48 KB of A
+// fragments per wave and k-step (64 B/clk per CU at the MFMA rate, from L2: 144 KB of weights do not fit L1) is the
+// candidate, not yet measured.
 // -------------------------------------------------------------------------------------
+struct D4X3 {
+    // tile geometry as a function of the plane width alone: 32 columns x 4 rows, or 16 columns x 8 rows for planes
+    // <= 16 wide.  A wave owns 32 cells: one row of 32 or two rows of 16.  Halo rows are RS cells apart: 34 at TW = 32;
+    // 32 at TW = 16 (18 used), so that a wave's second row starts a multiple of 16 cells after its first and the
+    // 16-lane groups of ds_read_b128 stay on distinct slots.
+    __host__ __device__ static constexpr int twl(int w) { return w <= 16 ? 4 : 5; }
+    __host__ __device__ static constexpr int rows(int twl) { return 4 * (32 >> twl); }
+    __host__ __device__ static constexpr int rs(int twl) { return twl == 5 ? 34 : 32; }
+    __host__ __device__ static constexpr int cells(int twl) { return (rows(twl) + 2) * rs(twl); }   // 204 / 320
+    __host__ __device__ static constexpr int slab_groups(int twl) { return twl == 5 ? 6 : 4; }      // 58 752 / 61 440 B
+    static constexpr int REC = 48;                       // bytes per cell and channel group: hi, mid, lo records
+};
+
+// p-th (view, parity, tap) product of a k-step: views 0..8 ascending, within a view the parities, then the taps
+// taps: a=0: (dy 0, ky 1), (dy -1, ky 3);  a=1: (dy +1, ky 0), (dy 0, ky 2)   (same in x)
+struct D4Prod { int v, q, t; };
+__host__ __device__ constexpr D4Prod d4x3_prod(int p) {
+    int k = 0;
+    for (int v = 0; v < 9; ++v)
+        for (int q = 0; q < 4; ++q)
+            for (int t = 0; t < 4; ++t) {
+                const int a = q >> 1, b = q & 1, tyi = t >> 1, txi = t & 1;
+                const int dy = a == 0 ? (tyi == 0 ? 0 : -1) : (tyi == 0 ? 1 : 0);
+                const int dx = b == 0 ? (txi == 0 ? 0 : -1) : (txi == 0 ? 1 : 0);
+                if (dy == v / 3 - 1 && dx == v % 3 - 1) {
+                    if (k == p) return {v, q, t};
+                    ++k;
+                }
+            }
+    return {0, 0, 0};
+}
+template <class F, int... U>
+__device__ __forceinline__ void d4x3_units(F&& f, std::integer_sequence<int, U...>) {
+    (f(std::integral_constant<int, U>{}), ...);
+}
+
 template <int NB, bool DUAL>
 __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconv4x3_kernel(
     const float* __restrict__ inA, int Ca, const float* __restrict__ inB, int Cb, const u32x4* __restrict__ ws,
-    const float* __restrict__ bias, float* __restrict__ out, long NP, int h, int w_, int Cout, int xcd_remap) {
+    const float* __restrict__ bias, float* __restrict__ out, int tilesX, int tilesY, int h, int w_, int Cout,
+    int SG, int xcd_remap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char d4s[];   // [slab group][halo cell][hi, mid, lo] x 16 B
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
+    // neighbouring tiles share their halo: keep them on one XCD (see xcd_contiguous_id)
     const int bid = xcd_remap ? xcd_contiguous_id(blockIdx.x, gridDim.x) : blockIdx.x;
-    const long px0 = ((long)bid * 4 + wave) * 32;
-    if (px0 >= NP) return;
+    const int twl = D4X3::twl(w_), TW = 1 << twl, RS = D4X3::rs(twl), HW2 = TW + 2;
+    const int NCELL = D4X3::cells(twl);
+    const int CPG = (D4X3::rows(twl) + 2) * HW2;          // cells of the halo tile that are staged (per group)
+    const int tpi = tilesX * tilesY;
+    const int n = bid / tpi, t = bid - n * tpi;
+    const int ty = t / tilesX, tx = t - ty * tilesX;
+    const int y0 = ty * D4X3::rows(twl), x0 = tx * TW;
     const int half = lane >> 5, pl = lane & 31;
-    const long g = px0 + pl;
-    const bool valid = g < NP;
-    const long gc = valid ? g : NP - 1;
+    const int ry = wave * (32 >> twl) + (pl >> twl), cx = pl & (TW - 1);
+    const int iy = y0 + ry, ix = x0 + cx;
+    const bool valid = iy < h && ix < w_;
+    const bool wave_live = y0 + wave * (32 >> twl) < h;   // wave-uniform: a wave below the image runs no MFMA
     const int hw = h * w_;
-    const int n = (int)(gc / hw);
-    const int p = (int)(gc - (long)n * hw);
-    const int iy = p / w_, ix = p - iy * w_;
-    int voff[9];
-    bool vok[9];
-#pragma unroll
-    for (int v = 0; v < 9; ++v) {
-        const int y = iy + v / 3 - 1, x = ix + v % 3 - 1;
-        vok[v] = y >= 0 && y < h && x >= 0 && x < w_;
-        voff[v] = vok[v] ? y * w_ + x : p;
-    }
     f32x16 acc[NB][4];
 #pragma unroll
     for (int i = 0; i < NB; ++i)
@@ -2967,50 +3019,94 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconv4x3_kernel(
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][q][r] = 0.f;
     const int Ga = Ca >> 3, G8 = (DUAL ? Ca + Cb : Ca) >> 3, KS = (G8 + 1) >> 1;
-    const u32x4* wl = ws + lane;
-    // the 8 raw channel values of this lane's channel group of k-step ksn at view v
-    auto fetch = [&](int ksn, int v, float (&raw)[8]) {
-        const int gq = min(2 * min(ksn, KS - 1) + half, G8 - 1);   // beyond the last group: any valid data (zero weights)
-        const float* sp = (!DUAL || gq < Ga) ? inA + ((long)n * Ca + 8 * gq) * hw : inB + ((long)n * Cb + 8 * (gq - Ga)) * hw;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) raw[c] = sp[(long)c * hw + voff[v]];
+    const float* baseA = inA + (long)n * Ca * hw;
+    const float* baseB = DUAL ? inB + (long)n * Cb * hw : baseA;
+    // this lane's cell in the halo tile is (ry + 1, cx + 1); view (dy, dx) is the record (dy * RS + dx) cells from it
+    const unsigned char* cell = d4s + ((ry + 1) * RS + cx + 1) * D4X3::REC;
+    // the 16 NB (view, parity, tap, block) products of a k-step in accumulation order; their A fragments go through a
+    // ring of DEPTH register sets, loaded DEPTH - 1 products ahead (across k-steps and slabs: the weights are global)
+    constexpr int UN = 16 * NB, DEPTH = NB == 1 ? 2 : 4;   // NB = 1: 168 registers (3 waves per SIMD) hold two sets
+    u32x4 ar[DEPTH][3];
+    auto fetch_a = [&](int ksn, auto uc) {
+        constexpr int u = decltype(uc)::value, i = u % NB;
+        constexpr D4Prod pr = d4x3_prod(u / NB);
+        const u32x4* wp = ws + ((long)((i * 4 + pr.q) * 4 + pr.t) * KS + ksn) * 3 * 64;   // wave-uniform base + lane
+        ar[u % DEPTH][0] = wp[lane];
+        ar[u % DEPTH][1] = wp[64 + lane];
+        ar[u % DEPTH][2] = wp[128 + lane];
     };
-    float rcur[8], rnext[8];
-    fetch(0, 0, rcur);
+    constexpr int U = 4;                                  // (group, cell) items a thread has in flight while staging
 #pragma unroll 1
-    for (int ks = 0; ks < KS; ++ks) {
+    for (int g0 = 0; g0 < G8; g0 += SG) {
+        const int ng = min(SG, G8 - g0), items = ng * CPG;
+        if (g0) __syncthreads();                          // every wave is done reading the previous slab
+#pragma unroll 1
+        for (int it = threadIdx.x; it < items; it += 256 * U) {
+            float raw[U][8];
+            int dst[U];
+            bool ok[U];
 #pragma unroll
-        for (int v = 0; v < 9; ++v) {
-            if (v < 8) fetch(ks, v + 1, rnext);              // next view in flight under this view's MFMAs
-            else fetch(ks + 1, 0, rnext);                    // (the tail re-loads the last k-step, unused)
-            __builtin_amdgcn_sched_barrier(0);
-            u32x4 fh, fm, fl;
+            for (int u = 0; u < U; ++u) {
+                const int e = min(it + 256 * u, items - 1);            // the tail re-does the last item (same values)
+                const int gl = e / CPG, c = e - gl * CPG;
+                const int r = c / HW2, x = c - r * HW2;
+                const int gy = y0 - 1 + r, gx = x0 - 1 + x;
+                ok[u] = gy >= 0 && gy < h && gx >= 0 && gx < w_;
+                const int gq = g0 + gl;
+                const float* sp = (!DUAL || gq < Ga) ? baseA + (long)(8 * gq) * hw : baseB + (long)(8 * (gq - Ga)) * hw;
+                sp += ok[u] ? gy * w_ + gx : 0;                        // outside the image: any valid address, zeroed below
+                dst[u] = (gl * NCELL + r * RS + x) * D4X3::REC;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const Split3 s3 = split3_pair(vok[v] ? rcur[2 * j] : 0.f, vok[v] ? rcur[2 * j + 1] : 0.f);
-                fh[j] = s3.h;
-                fm[j] = s3.m;
-                fl[j] = s3.l;
+                for (int ch = 0; ch < 8; ++ch) raw[u][ch] = sp[(long)ch * hw];
             }
-            const int dyv = v / 3 - 1, dxv = v % 3 - 1;
 #pragma unroll
-            for (int q = 0; q < 4; ++q)
+            for (int u = 0; u < U; ++u) {
+                u32x4 fh, fm, fl;
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int a = q >> 1, b = q & 1, tyi = t >> 1, txi = t & 1;
-                    const int dy = a == 0 ? (tyi == 0 ? 0 : -1) : (tyi == 0 ? 1 : 0);
-                    const int dx = b == 0 ? (txi == 0 ? 0 : -1) : (txi == 0 ? 1 : 0);
-                    if (dy == dyv && dx == dxv) {
-#pragma unroll
-                        for (int i = 0; i < NB; ++i) {
-                            const u32x4* wp = wl + ((long)((i * 4 + q) * 4 + t) * KS + ks) * 3 * 64;
-                            const u32x4 av[3] = {wp[0], wp[64], wp[128]};
-                            acc[i][q] = mma6(av, fh, fm, fl, acc[i][q]);
-                        }
-                    }
+                for (int j = 0; j < 4; ++j) {
+                    const Split3 s3 = split3_pair(ok[u] ? raw[u][2 * j] : 0.f, ok[u] ? raw[u][2 * j + 1] : 0.f);
+                    fh[j] = s3.h;
+                    fm[j] = s3.m;
+                    fl[j] = s3.l;
                 }
-#pragma unroll
-            for (int c = 0; c < 8; ++c) rcur[c] = rnext[c];
+                u32x4* rec = reinterpret_cast<u32x4*>(d4s + dst[u]);
+                rec[0] = fh;
+                rec[1] = fm;
+                rec[2] = fl;
+            }
+        }
+        if (g0 == 0) {                                    // the ring's first sets, in flight across the barrier
+            d4x3_units([&](auto uc) { fetch_a(0, uc); }, std::make_integer_sequence<int, DEPTH - 1>{});
+        }
+        __syncthreads();
+        if (!wave_live) continue;
+        const int ks1 = (g0 + ng + 1) >> 1;
+#pragma unroll 1
+        for (int ks = g0 >> 1; ks < ks1; ++ks) {
+            // beyond the last group (odd group count): the last group's data again, against zero weights
+            const int gl = min(2 * ks + half, G8 - 1) - g0;
+            const unsigned char* kc = cell + gl * NCELL * D4X3::REC;
+            const int ksn = min(ks + 1, KS - 1);          // the tail re-loads the last k-step's weights (unused)
+            u32x4 bf[2][3];                               // views v, v + 1
+            auto view = [&](int v, u32x4 (&b)[3]) {
+                const u32x4* rec = reinterpret_cast<const u32x4*>(kc + ((v / 3 - 1) * RS + v % 3 - 1) * D4X3::REC);
+                b[0] = rec[0];
+                b[1] = rec[1];
+                b[2] = rec[2];
+            };
+            view(0, bf[0]);
+            d4x3_units([&](auto uc) {
+                constexpr int u = decltype(uc)::value, pi = u / NB, i = u % NB;
+                constexpr D4Prod pr = d4x3_prod(pi);
+                constexpr bool first = i == 0 && (pi == 0 || d4x3_prod(pi - 1).v != pr.v);
+                // the weights of the product DEPTH - 1 ahead and the next view's records are in flight under this one's MFMAs
+                if constexpr (u + DEPTH - 1 < UN) fetch_a(ks, std::integral_constant<int, u + DEPTH - 1>{});
+                else fetch_a(ksn, std::integral_constant<int, u + DEPTH - 1 - UN>{});
+                if constexpr (first && pr.v < 8) view(pr.v + 1, bf[(pr.v + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+                acc[i][pr.q] = mma6(ar[u % DEPTH], bf[pr.v & 1][0], bf[pr.v & 1][1], bf[pr.v & 1][2], acc[i][pr.q]);
+                __builtin_amdgcn_sched_barrier(0);
+            }, std::make_integer_sequence<int, UN>{});
         }
     }
     if (!valid) return;
@@ -3037,14 +3133,22 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconv4x3_kernel(
 bool launch_deconv4x3(const float* inA, int Ca, const float* inB, int Cb, const void* ws, const float* bias,
                       float* out, int N, int h, int w_, int Cout, hipStream_t s) {
     if (!ws || (Ca & 7) || (Cb & 7) || Cout > 64) return false;
-    // <= 16x16 input planes (deconv.0 at 256^2 / 512^2 inputs): too few waves for the longer per-wave chain
-    // (8-10 k-steps x 9 views in sequence) -- the fp32 kernel is faster there (48 vs 79 us on XS, 116 vs 208 on M).
+    // <= 16x16 input planes (deconv.0 at 256^2 / 512^2 inputs): with views fetched from global memory there were too few
+    // waves for the longer per-wave chain (8-10 k-steps x 9 views in sequence) -- the fp32 kernel was faster there (48 vs
+    // 79 us on XS, 116 vs 208 on M).  The LDS-staged body (8x16 tiles on such planes) has not been measured against it.
     // The rule depends on the LAYER SHAPE only, never on the batch size (batched == per-image bitwise, P4).
+    // Measured, XS@256 64 + 64 images, one stream, same box (profiles/r09_deconv_kernel_stats_*.txt): global-memory views
+    // 56.6 / 190.3 us (deconv.1 / deconv.2), LDS-staged 51.6 / 154.8 us; the MFMA floor of deconv.2 is 61 us.
     if (h * w_ <= 256) return false;
-    const long NP = (long)N * h * w_;
-    dim3 grid((unsigned)((NP + 127) / 128)), block(256);
-#define LP_D4X3(NBV, DV) LP_LAUNCH((deconv4x3_kernel<NBV, DV>), grid, block, 0, s, inA, Ca, inB, Cb, (const u32x4*)ws, bias, \
-                                   out, NP, h, w_, Cout, xcd_remap_mode())
+    const int twl = D4X3::twl(w_), G8 = (Ca + (inB ? Cb : 0)) >> 3;
+    const int tilesX = (w_ + (1 << twl) - 1) >> twl, tilesY = (h + D4X3::rows(twl) - 1) / D4X3::rows(twl);
+    // slabs of equal size (an even group count, so that a slab ends on a k-step): K = 56 is 4 + 3 groups, not 6 + 1
+    const int nslab = (G8 + D4X3::slab_groups(twl) - 1) / D4X3::slab_groups(twl);
+    const int SG = (((G8 + nslab - 1) / nslab) + 1) & ~1;
+    const size_t lds = (size_t)(G8 < SG ? G8 : SG) * D4X3::cells(twl) * D4X3::REC;
+    dim3 grid((unsigned)((long)N * tilesX * tilesY)), block(256);
+#define LP_D4X3(NBV, DV) LP_LAUNCH((deconv4x3_kernel<NBV, DV>), grid, block, lds, s, inA, Ca, inB, Cb, (const u32x4*)ws, bias, \
+                                   out, tilesX, tilesY, h, w_, Cout, SG, xcd_remap_mode())
     if (inB) { if (Cout <= 32) LP_D4X3(1, true); else LP_D4X3(2, true); }
     else { if (Cout <= 32) LP_D4X3(1, false); else LP_D4X3(2, false); }    // plain head: the one-source form
 #undef LP_D4X3

@@ -179,8 +179,34 @@ def mbtb():
     return out
 
 
+# ------------------------------------------------------------------------------------------ deconv4x3_kernel
+def deconv4x3():
+    """Halo tile records of 48 B per cell (hi, mid, lo x 16 B).  A lane reads the three records of its cell at a view's
+    offset; a staging thread writes the three records of one cell, consecutive threads consecutive cells."""
+    out = {}
+    for tw, rs in ((32, 34), (16, 32), (16, 18)):
+        ins = []
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                for piece in range(3):
+                    ad = []
+                    for lane in range(64):
+                        half, pl = lane >> 5, lane & 31
+                        ry, cx = pl // tw, pl % tw
+                        ncell = (4 * (32 // tw) + 2) * rs
+                        ad.append((half * ncell + (ry + 1 + dy) * rs + cx + 1 + dx) * 48 + 16 * piece)
+                    ins.append((ad, 16, groups_b128(), 64))
+        out['nine views of a k-step, 27 ds_read_b128, %d-column tile, row stride %d' % (tw, rs)] = total(ins)
+    ins = []
+    for piece in range(3):
+        ins.append(([(lane * 48) + 16 * piece for lane in range(64)], 16, G8, 32))
+    out['staging, 3 ds_write_b128 per cell'] = total(ins)
+    return out
+
+
 if __name__ == '__main__':
-    for name, fn in (('mb16_kernel', mb16), ('mbt_kernel', mbt), ('mbt_s2_kernel', mbt_s2), ('mbtb_kernel', mbtb)):
+    for name, fn in (('mb16_kernel', mb16), ('mbt_kernel', mbt), ('mbt_s2_kernel', mbt_s2), ('mbtb_kernel', mbtb),
+                     ('deconv4x3_kernel', deconv4x3)):
         print(name)
         for k, (c, base) in fn().items():
             print('  %-62s %4d LDS cycles per wave (conflict-free: %d)' % (k, c, base))

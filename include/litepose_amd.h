@@ -52,7 +52,9 @@ const char* lp_version(void);
 /* ------------------------------------------------------------------ network ----
  * Replaces models.pose_mobilenet.get_pose_net / LitePose.__init__ / forward
  * (lib/models/pose_mobilenet.py:21-71,137-156,158-176) and the conv/BN/act modules
- * of lib/models/layers/layers.py:18-24,90-133.                                     */
+ * of lib/models/layers/layers.py:18-24,90-133.  With lp_arch.family = 1 the same calls
+ * are models.pose_resnet (lib/models/pose_resnet.py:21-151; layers.py:58-88 UpConv /
+ * FusedMBConv): same two outputs, taps "first", "stage.S.B.inv", "stage.S.B", "deconv.I". */
 
 #define LP_MAX_STAGES 8
 #define LP_MAX_BLOCKS 32
@@ -72,6 +74,16 @@ typedef struct lp_arch {                  /* == mobile_configs/*.json + mobile.y
     int32_t plain_head;                   /* 0: Fusion Deconv Head (pose_mobilenet), 1: no raw */
                                           /* branches (pose_simplenet.py: deconv_refined and */
                                           /* final_refined only); other values are refused   */
+    int32_t family;                       /* 0: pose_mobilenet / pose_simplenet (everything above as documented).            */
+                                          /* 1: pose_resnet (lib/models/pose_resnet.py:21-131): stem = conv 7x7 s2 3->32 +   */
+                                          /* conv 7x7 s1 32->input_channel (BN, ReLU6 each); blocks are FusedMBConv          */
+                                          /* (layers.py:67-88): expand[s][b] = r, kernel[s][b] = k of the DENSE k x k conv;  */
+                                          /* deconvs are UpConv (nearest x2 + dense conv, layers.py:58-65); heads are 3x3    */
+                                          /* convs with bias.  Needs plain_head = 0 (LP_ERR_INVALID_ARG otherwise); fp32     */
+                                          /* storage only.  Other values: LP_ERR_INVALID_ARG                                 */
+    int32_t upconv_kernel;                /* family 1: MODEL.EXTRA.NUM_DECONV_KERNELS (one size for every layer): 0 = 3, or  */
+                                          /* 3 / 5 / 7.  Even or negative: LP_ERR_INVALID_ARG (only an odd kernel doubles    */
+                                          /* the plane); odd above 7: LP_ERR_UNSUPPORTED.  Ignored by family 0 (kernel 4)    */
 } lp_arch;
 
 typedef struct lp_net lp_net;             /* opaque                                       */
@@ -103,7 +115,9 @@ int lp_net_finalize(lp_net* net, int strict);
  * returns fp32 planar copies.  LP_STORAGE_F16 is the same path with IEEE half records and weights --
  * the format network_to_half itself uses: 3 more mantissa bits than bf16, a range up to 65504
  * (overflow rounds to +-inf), subnormals kept.  Same layout, same kernels (their fp16 forms), same
- * shape refusals and the same options as bf16.  LP_STORAGE_F32 (default) is the reference's arithmetic. */
+ * shape refusals and the same options as bf16.  LP_STORAGE_F32 (default) is the reference's arithmetic.
+ * A net of lp_arch.family = 1 (pose_resnet) answers BF16 / F16 with LP_ERR_UNSUPPORTED: its dense k x k convolutions
+ * have no 16-bit kernels yet (the storage stays fp32).                                                 */
 #define LP_STORAGE_F32 0
 #define LP_STORAGE_BF16 1
 #define LP_STORAGE_F16 2

@@ -30,6 +30,8 @@ class LpArch(C.Structure):
         ('num_deconv', C.c_int32), ('deconv_filters', C.c_int32 * LP_MAX_DECONV),
         ('head_channels', C.c_int32 * LP_MAX_DECONV),
         ('plain_head', C.c_int32),
+        ('family', C.c_int32),
+        ('upconv_kernel', C.c_int32),
     ]
 
 

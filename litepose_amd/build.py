@@ -36,6 +36,7 @@ SOURCES = [
     ('mbtile_bf16.hip', []),
     ('stem_kernels.hip', []),
     ('bf16_kernels.hip', []),
+    ('convk_kernels.hip', []),
     ('ae_kernels.hip', ['-ffp-contract=off'] + NOPK),
     ('ae_mid_kernels.hip', ['-ffp-contract=off'] + NOPK),
 ]

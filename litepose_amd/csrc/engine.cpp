@@ -58,7 +58,7 @@ struct Block { int inp, feat, oup, k, stride; bool residual; };
 struct Deconv { int refined_in, raw_in, out; };
 struct Head { int refined_in, raw_in, oup; };
 
-enum OpType { OP_STEM, OP_DW, OP_PW, OP_DECONV, OP_DWPW };
+enum OpType { OP_STEM, OP_DW, OP_PW, OP_DECONV, OP_DWPW, OP_CONVK };   // OP_CONVK: dense k x k conv (family 1)
 struct Op {
     OpType type;
     std::string name;
@@ -77,6 +77,9 @@ struct Op {
     size_t st_w0 = 0, st_w1 = 0, st_w2 = 0, st_b2 = 0;   // OP_STEM: fused-stem copies (tap-/input-major weights, plain 1x1 bias)
     size_t wrow_off = 0;                   // its depthwise weights, pair-interleaved rows [C/2][7][7 taps x 2 ch + 2 pad]
     int mid = -1;                          // OP_DWPW: buffer for the depthwise output (fallback only)
+    size_t wk_off = 0;                     // OP_CONVK: bf16x3 A fragments [cout block][tap][ks][3 pieces][lane] x 16 B
+    int ups = 0;                           // OP_CONVK: 1 = sources read through a nearest x2 upsample (UpConv)
+    bool image_in = false;                 // OP_CONVK: reads the network input (mirrored for the images of a flip pass)
     bool has_bias = true;
     bool fuse_next = false;                // OP_PW expand followed by its OP_DWPW: try mbconv_kernel
     std::string tap;                       // tap name this op's output is published under
@@ -327,6 +330,154 @@ int new_buf(lp_net* n, int ch, int div) {
     n->bufs.ch.push_back(ch);
     n->bufs.div.push_back(div);
     return (int)n->bufs.ch.size() - 1;
+}
+
+// dense conv weights (one or two channel-concatenated sources, [Cout][Ci][K][K] each) -> exact bf16x3 A fragments of
+// v_mfma_f32_32x32x16_bf16 for convk3_kernel: [cblock][tap ky*K+kx][ks][piece hi,mid,lo][64 lanes][4 dwords]; lane l
+// holds co = cb*32 + (l&31), ci = ks*16 + 8*(l>>5) + 0..7 (two bf16 per dword, even ci low; zero beyond Cout / Ct).
+// scale (BN) is folded in fp64 before the one rounding to fp32; bias [Cout] = shift (+ the convs' own biases).
+void pack_convk(lp_net* n, const std::vector<const Tensor*>& ws, const std::vector<double>* scale,
+                const std::vector<double>& shift, Op& op) {
+    const int Cout = (int)ws[0]->shape[0], K = (int)ws[0]->shape[2], KK = K * K;
+    int Ct = 0;
+    for (auto* w : ws) Ct += (int)w->shape[1];
+    const int KS = (Ct + 15) / 16, nb = (Cout + 31) / 32;
+    auto wval = [&](int co, int ci, int t) -> float {
+        if (co >= Cout || ci >= Ct) return 0.f;
+        for (auto* w : ws) {
+            const int c = (int)w->shape[1];
+            if (ci < c) {
+                double x = w->data[((size_t)co * c + ci) * KK + t];
+                if (scale) x *= (*scale)[co];
+                return (float)x;
+            }
+            ci -= c;
+        }
+        return 0.f;
+    };
+    auto split3 = [](float x, uint32_t out[3]) {
+        for (int t = 0; t < 3; ++t) {
+            uint32_t u;
+            std::memcpy(&u, &x, 4);
+            u &= 0xffff0000u;
+            float h;
+            std::memcpy(&h, &u, 4);
+            out[t] = u >> 16;
+            x = x - h;                       // exact
+        }
+    };
+    op.wk_off = arena_push(n->h_packed, (size_t)nb * KK * KS * 3 * 64 * 4);
+    uint32_t* d = reinterpret_cast<uint32_t*>(n->h_packed.data() + op.wk_off);
+    for (int cb = 0; cb < nb; ++cb)
+        for (int t = 0; t < KK; ++t)
+            for (int ks = 0; ks < KS; ++ks)
+                for (int l = 0; l < 64; ++l) {
+                    uint32_t piece[8][3];
+                    for (int e = 0; e < 8; ++e) split3(wval(cb * 32 + (l & 31), ks * 16 + 8 * (l >> 5) + e, t), piece[e]);
+                    for (int pc = 0; pc < 3; ++pc)
+                        for (int dq = 0; dq < 4; ++dq)
+                            d[((((size_t)(cb * KK + t) * KS + ks) * 3 + pc) * 64 + l) * 4 + dq] =
+                                piece[2 * dq][pc] | (piece[2 * dq + 1][pc] << 16);
+                }
+    op.b_off = arena_push(n->h_packed, (size_t)Cout);
+    for (int co = 0; co < Cout; ++co) n->h_packed[op.b_off + co] = (float)shift[co];
+}
+
+// pose_resnet family (lp_arch.family = 1; lib/models/pose_resnet.py:34-51,112-131): every k x k conv is an OP_CONVK, a
+// FusedMBConv is OP_CONVK (+ReLU6) followed by the 1x1 OP_PW with the residual epilogue (layers.py:83-88)
+int build_plan_resnet(lp_net* n) {
+    n->ops.clear();
+    n->bufs = BufferPlan();
+    n->h_packed.clear();
+    auto conv_bn = [&](Op& o, const std::string& wkey, const std::string& bnkey) {
+        std::vector<double> sc, sh;
+        bn_fold(n, bnkey, sc, sh);
+        pack_convk(n, {&T(n, wkey)}, &sc, sh, o);
+    };
+    const int bStem = new_buf(n, 32, 2);
+    int cur = new_buf(n, n->c0, 2);
+    {
+        Op a; a.type = OP_CONVK; a.name = "first.0"; a.out = bStem; a.Ca = 3; a.Cout = 32; a.K = 7; a.S = 2;
+        a.in_div = 1; a.out_div = 2; a.act = lp::ACT_RELU6; a.image_in = true;
+        conv_bn(a, "first.0.0.weight", "first.0.1");
+        n->ops.push_back(a);
+        Op b; b.type = OP_CONVK; b.name = "first.1"; b.inA = bStem; b.out = cur; b.Ca = 32; b.Cout = n->c0; b.K = 7;
+        b.S = 1; b.in_div = b.out_div = 2; b.act = lp::ACT_RELU6; b.tap = "first";
+        conv_bn(b, "first.1.0.weight", "first.1.1");
+        n->ops.push_back(b);
+    }
+    std::vector<int> xlist = {cur}, xdiv = {2};
+    int div = 2;
+    for (size_t s = 0; s < n->stages.size(); ++s) {
+        for (size_t b = 0; b < n->stages[s].size(); ++b) {
+            const Block& blk = n->stages[s][b];
+            const std::string pfx = "stage." + std::to_string(s) + "." + std::to_string(b);
+            const int odiv = div * blk.stride;
+            const int bE = new_buf(n, blk.feat, odiv), bO = new_buf(n, blk.oup, odiv);
+            Op e; e.type = OP_CONVK; e.name = pfx + ".inv"; e.inA = cur; e.out = bE; e.Ca = blk.inp; e.Cout = blk.feat;
+            e.K = blk.k; e.S = blk.stride; e.in_div = div; e.out_div = odiv; e.act = lp::ACT_RELU6;
+            conv_bn(e, pfx + ".inv.0.weight", pfx + ".inv.1");
+            n->ops.push_back(e);
+            Op p; p.type = OP_PW; p.name = pfx + ".point_conv"; p.inA = bE; p.out = bO; p.Ca = blk.feat; p.Cout = blk.oup;
+            p.in_div = p.out_div = odiv; p.act = lp::ACT_NONE; p.res = blk.residual ? cur : -1; p.tap = pfx;
+            {
+                std::vector<double> sc, sh;
+                bn_fold(n, pfx + ".point_conv.1", sc, sh);
+                pack_pw(n, {&T(n, pfx + ".point_conv.0.weight")}, &sc, &sh, p);
+            }
+            n->ops.push_back(p);
+            cur = bO;
+            div = odiv;
+        }
+        xlist.push_back(cur);
+        xdiv.push_back(div);
+    }
+    int refined = xlist.back(), rdiv = xdiv.back();
+    int raw = xlist[xlist.size() - 2];
+    const int L = (int)xlist.size();
+    for (size_t i = 0; i < n->deconv.size(); ++i) {
+        const Deconv& dc = n->deconv[i];
+        const std::string si = std::to_string(i);
+        if (xdiv[L - (int)i - 2] != rdiv)
+            return fail(LP_ERR_UNSUPPORTED, "deconv." + si + ": the raw and the refined source differ in resolution");
+        const int odiv = rdiv / 2;
+        const int bR = new_buf(n, dc.out, odiv);
+        Op o; o.type = OP_CONVK; o.name = "deconv." + si; o.inA = refined; o.inB = raw; o.out = bR; o.Ca = dc.refined_in;
+        o.Cb = dc.raw_in; o.Cout = dc.out; o.K = (int)T(n, "deconv_refined." + si + ".conv.weight").shape[2]; o.S = 1;
+        o.ups = 1; o.in_div = rdiv; o.out_div = odiv; o.act = lp::ACT_RELU; o.tap = "deconv." + si;
+        {
+            // the BN follows the SUM of the two UpConvs: its scale goes into both weight sets, its shift is added once
+            std::vector<double> sc, sh;
+            bn_fold(n, "deconv_bnrelu." + si + ".0", sc, sh);
+            pack_convk(n, {&T(n, "deconv_refined." + si + ".conv.weight"), &T(n, "deconv_raw." + si + ".conv.weight")},
+                       &sc, sh, o);
+        }
+        n->ops.push_back(o);
+        refined = bR;
+        rdiv = odiv;
+        const int ri = L - (int)i - 3;               // x_list[-i-3]
+        if (ri < 0) return fail(LP_ERR_UNSUPPORTED, "more deconv layers than backbone taps");
+        raw = xlist[ri];
+        if (i > 0) {
+            if (xdiv[ri] != rdiv)
+                return fail(LP_ERR_UNSUPPORTED, "final." + std::to_string(i - 1) + ": sources differ in resolution");
+            const Head& h = n->heads[i - 1];
+            const std::string hi = std::to_string(i - 1);
+            const int bOut = new_buf(n, h.oup, rdiv);
+            Op f; f.type = OP_CONVK; f.name = "final." + hi; f.inA = refined; f.inB = raw; f.out = bOut; f.Ca = h.refined_in;
+            f.Cb = h.raw_in; f.Cout = h.oup; f.K = 3; f.S = 1; f.in_div = f.out_div = rdiv; f.act = lp::ACT_NONE;
+            // two biased convs summed: one launch over the concatenated channels, both biases added (once each)
+            const Tensor &br = T(n, "final_refined." + hi + ".bias"), &bw = T(n, "final_raw." + hi + ".bias");
+            std::vector<double> sh((size_t)h.oup);
+            for (int c = 0; c < h.oup; ++c) sh[c] = (double)br.data[c] + (double)bw.data[c];
+            pack_convk(n, {&T(n, "final_refined." + hi + ".weight"), &T(n, "final_raw." + hi + ".weight")}, nullptr, sh, f);
+            n->ops.push_back(f);
+            if (i == 1) n->out0_buf = bOut; else n->out1_buf = bOut;
+        }
+    }
+    if (n->deconv.size() != 3 || n->out0_buf < 0 || n->out1_buf < 0)
+        return fail(LP_ERR_UNSUPPORTED, "the path is built for NUM_DECONV_LAYERS == 3 (two output stages)");
+    return LP_OK;
 }
 
 int build_plan(lp_net* n) {
@@ -1007,6 +1158,16 @@ int lp_net_create(lp_net** out, const lp_arch* a) {
     if (a->num_stages < 1 || a->num_stages > LP_MAX_STAGES || a->num_deconv != 3)
         return fail(LP_ERR_UNSUPPORTED, "num_stages must be 1..8 and num_deconv 3");
     if (a->plain_head != 0 && a->plain_head != 1) return fail(LP_ERR_INVALID_ARG, "plain_head must be 0 or 1");
+    if (a->family != 0 && a->family != 1) return fail(LP_ERR_INVALID_ARG, "family must be 0 or 1");
+    const bool resnet = a->family == 1;
+    int upk = 3;
+    if (resnet) {
+        if (a->plain_head) return fail(LP_ERR_INVALID_ARG, "family 1 (pose_resnet) has no plain-head form");
+        upk = a->upconv_kernel == 0 ? 3 : a->upconv_kernel;
+        if (upk < 0 || (upk & 1) == 0)
+            return fail(LP_ERR_INVALID_ARG, "upconv_kernel must be odd (an even kernel does not double the plane)");
+        if (upk > 7) return fail(LP_ERR_UNSUPPORTED, "upconv_kernel must be 3, 5 or 7");
+    }
     lp_net* n = new lp_net();
     n->arch = *a;
     n->c0 = make_divisible(a->input_channel * 1.0, 8);
@@ -1048,6 +1209,40 @@ int lp_net_create(lp_net** out, const lp_arch* a) {
     for (int i = 1; i < a->num_deconv; ++i) {
         if (!plain && L - i - 3 < 0) { delete n; return fail(LP_ERR_UNSUPPORTED, "too few stages"); }
         n->heads.push_back({a->deconv_filters[i], plain ? 0 : n->channel[L - i - 3], a->head_channels[i - 1]});
+    }
+    if (resnet) {
+        // ---- pose_resnet.py:34-60 registration order: first, stage, deconv_refined, deconv_raw, deconv_bnrelu,
+        // final_refined, final_raw ----
+        add_tensor(n, "first.0.0.weight", {32, 3, 7, 7});
+        add_bn(n, "first.0.1", 32);
+        add_tensor(n, "first.1.0.weight", {n->c0, 32, 7, 7});
+        add_bn(n, "first.1.1", n->c0);
+        for (size_t s = 0; s < n->stages.size(); ++s)
+            for (size_t b = 0; b < n->stages[s].size(); ++b) {
+                const Block& blk = n->stages[s][b];
+                const std::string p = "stage." + std::to_string(s) + "." + std::to_string(b);
+                add_tensor(n, p + ".inv.0.weight", {blk.feat, blk.inp, blk.k, blk.k});
+                add_bn(n, p + ".inv.1", blk.feat);
+                add_tensor(n, p + ".point_conv.0.weight", {blk.oup, blk.feat, 1, 1});
+                add_bn(n, p + ".point_conv.1", blk.oup);
+            }
+        for (size_t i = 0; i < n->deconv.size(); ++i)
+            add_tensor(n, "deconv_refined." + std::to_string(i) + ".conv.weight",
+                       {n->deconv[i].out, n->deconv[i].refined_in, upk, upk});
+        for (size_t i = 0; i < n->deconv.size(); ++i)
+            add_tensor(n, "deconv_raw." + std::to_string(i) + ".conv.weight",
+                       {n->deconv[i].out, n->deconv[i].raw_in, upk, upk});
+        for (size_t i = 0; i < n->deconv.size(); ++i)
+            add_bn(n, "deconv_bnrelu." + std::to_string(i) + ".0", n->deconv[i].out);
+        for (int which = 0; which < 2; ++which)
+            for (size_t i = 0; i < n->heads.size(); ++i) {
+                const std::string p = std::string(which == 0 ? "final_refined." : "final_raw.") + std::to_string(i);
+                add_tensor(n, p + ".weight",
+                           {n->heads[i].oup, which == 0 ? n->heads[i].refined_in : n->heads[i].raw_in, 3, 3});
+                add_tensor(n, p + ".bias", {n->heads[i].oup});
+            }
+        *out = n;
+        return LP_OK;
     }
     // ---- reference state_dict key scheme, registration order ----
     add_tensor(n, "first.0.0.weight", {32, 3, 3, 3});
@@ -1152,10 +1347,12 @@ int lp_net_finalize(lp_net* n, int strict) {
             const bool bn_scale = t.key.size() > 7 && t.shape.size() == 1 &&
                                   (t.key.rfind(".weight") == t.key.size() - 7 ||
                                    t.key.rfind("running_var") != std::string::npos);
-            if (bn_scale) t.data.assign((size_t)t.numel(), 1.f);
+            if (bn_scale && !(n->arch.family == 1 && t.key.rfind("final_", 0) == 0)) t.data.assign((size_t)t.numel(), 1.f);
         }
     }
-    int rc = n->storage != LP_STORAGE_F32 ? build_plan_bf16(n) : build_plan(n);
+    if (n->arch.family == 1 && n->storage != LP_STORAGE_F32)
+        return fail(LP_ERR_UNSUPPORTED, "pose_resnet family: fp32 storage only (no 16-bit dense-conv kernels yet)");
+    int rc = n->arch.family == 1 ? build_plan_resnet(n) : (n->storage != LP_STORAGE_F32 ? build_plan_bf16(n) : build_plan(n));
     if (rc != LP_OK) return rc;
     if (n->d_weights) { (void)hipFree(n->d_weights); n->d_weights = nullptr; }
     HIP_OK(hipMalloc((void**)&n->d_weights, n->h_packed.size() * sizeof(float)));
@@ -1683,7 +1880,16 @@ int lp_net_forward(lp_net* n, const float* d_x, int N, int H, int W, int flip, f
                 fl = 2ll * NB * (int64_t)(o.Ca + o.Cb) * o.Cout * 4 * oh * ow;
                 break;
             }
-                    case OP_DWPW:
+            case OP_CONVK:
+                // dense k x k conv (+ upsample / second source); `oh, ow` already include the stride / the x2
+                if (!lp::launch_convk3(o.image_in ? xsrc : ptr[o.inA], o.Ca, o.inB >= 0 ? ptr[o.inB] : nullptr, o.Cb,
+                                       Wt + o.wk_off, Wt + o.b_off, ptr[o.out], NB, ih, iw, o.K, o.S, o.ups, o.Cout, o.act,
+                                       o.image_in ? flip_from : NB, o.image_in ? x_batch : NB, s))
+                    return fail(LP_ERR_UNSUPPORTED, "convk3: shape not supported: " + o.name);
+                by = 4ll * NB * ((int64_t)(o.Ca + o.Cb) * ih * iw + (int64_t)o.Cout * oh * ow);
+                fl = 2ll * NB * (int64_t)(o.Ca + o.Cb) * o.K * o.K * o.Cout * oh * ow;
+                break;
+            case OP_DWPW:
                 if (!lp::launch_dwpw(ptr[o.inA], Wt + o.w_off, Wt + o.b_off, Wt + o.w2_off, Wt + o.b2_off,
                                      o.res >= 0 ? ptr[o.res] : nullptr, ptr[o.out], NB, o.Ca, ih, iw, o.K, o.S,
                                      o.Cout, s)) {
@@ -1821,6 +2027,9 @@ int64_t lp_net_tap_offset(const lp_net* n, const char* name, int NB, int H, int 
 int lp_net_set_storage(lp_net* n, int storage) {
     if (!n || (storage != LP_STORAGE_F32 && storage != LP_STORAGE_BF16 && storage != LP_STORAGE_F16))
         return fail(LP_ERR_INVALID_ARG, "storage must be LP_STORAGE_F32, LP_STORAGE_BF16 or LP_STORAGE_F16");
+    if (n->arch.family == 1 && storage != LP_STORAGE_F32)
+        return fail(LP_ERR_UNSUPPORTED, "lp_net_set_storage: the pose_resnet family (lp_arch.family = 1) runs in fp32 storage "
+                                        "only: its dense k x k convolutions have no 16-bit kernels yet");
     if (storage != n->storage) {
         n->storage = storage;
         n->finalized = false;

@@ -158,6 +158,15 @@ bool launch_deconv4x3(const float* inA, int Ca, const float* inB, int Cb, const 
 void launch_deconv_mfma(const float* inA, int Ca, const float* inB, int Cb, const float* wp,
                         const float* bias, float* out, int N, int h, int w_, int Cout, hipStream_t s);
 
+// dense KxK convolution (K 3/5/7, stride S 1/2, pad K/2) over up to two channel-concatenated sources + bias + act on the
+// exact bf16x3 split (convk_kernels.hip; the pose_resnet family).  in: [N,C,IH,IW]; ups = 1: read through a nearest x2
+// upsample (UpConv: the conv runs on the 2IH x 2IW plane, its zero padding included).  ws = pack_convk's A fragments
+// [ceil(Cout/32)][K*K][ceil((Ca+Cb)/16)][3 pieces][64 lanes] x 16 B, bias [Cout].  Images >= flip_from read source A
+// mirrored along W, image n of source A is n % x_batch (the first conv of a TTA pass).  false = shape not supported
+bool launch_convk3(const float* inA, int Ca, const float* inB, int Cb, const void* ws, const float* bias, float* out,
+                   int N, int IH, int IW, int K, int S, int ups, int Cout, int act, int flip_from, int x_batch,
+                   hipStream_t s);
+
 // ---- network, 16-bit storage (octet-planar [N][C/8][HW][8] bf16 or fp16; bf16_kernels.hip, mbtile_bf16.hip) ----
 // Every launcher below takes the storage format last: f16 = false (default) runs the bf16 kernels, true their IEEE-half
 // forms (the same templates with a leading lp::F16 argument, fmt16.h): same shape rules, same refusals, same last_kernel_tag.

@@ -14,6 +14,7 @@ from . import _native as nv
 from .core import group as _group
 from .core import inference as _inference
 from .models import pose_mobilenet as _pm
+from .models import pose_resnet as _pr
 from .models import pose_simplenet as _ps
 from .utils import transforms as _tf
 
@@ -92,9 +93,10 @@ class PoseEngine(object):
             self.options['ae'] = 'mid'
         self.device = torch.device(device if device is not None else 'cuda:%d' % torch.cuda.current_device())
         torch.cuda.set_device(self.device)
-        # valid.py:125-128: the network cfg.MODEL.NAME names; pose_simplenet is the one other name the reference's loop builds
-        # from an arch JSON, every other name keeps the pose_mobilenet network
-        net = _ps if cfg.MODEL.get('NAME') == 'pose_simplenet' else _pm
+        # valid.py:125-136: the network cfg.MODEL.NAME names.  pose_simplenet is the one other name the reference's loop
+        # builds from an arch JSON; pose_resnet has none (``cfg_arch`` may be None: its table is fixed in the module and
+        # the input size is cfg.DATASET.INPUT_SIZE); every other name keeps the pose_mobilenet network
+        net = {'pose_simplenet': _ps, 'pose_resnet': _pr}.get(cfg.MODEL.get('NAME'), _pm)
         self.model = net.get_pose_net(cfg, is_train=False, cfg_arch=cfg_arch, storage=storage)
         self.model.load_state_dict(state_dict, strict=True)
         self.parser = _group.HeatmapParser(cfg, person_capacity=person_capacity)

@@ -1,2 +1,3 @@
 from . import pose_mobilenet  # noqa: F401
 from . import pose_simplenet  # noqa: F401
+from . import pose_resnet  # noqa: F401

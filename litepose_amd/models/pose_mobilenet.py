@@ -63,7 +63,7 @@ class LitePose(object):
             raise ValueError('storage must be one of %s' % sorted(STORAGE))
         self.storage = _STORAGE_NAME[STORAGE[storage]]
         self._lib = nv.lib()
-        self._arch = _arch_struct(cfg, cfg_arch, plain_head)
+        self._arch = self._make_arch(cfg, cfg_arch, plain_head)
         h = C.c_void_p()
         nv.check(self._lib.lp_net_create(C.byref(h), C.byref(self._arch)), 'lp_net_create')
         self._h = h
@@ -71,6 +71,10 @@ class LitePose(object):
         self._ws = None
         self._finalized = False
         self.training = False
+
+    def _make_arch(self, cfg, cfg_arch, plain_head):
+        """The lp_arch of this network (models.pose_resnet overrides it: its table is fixed in the module)."""
+        return _arch_struct(cfg, cfg_arch, plain_head)
 
     def __del__(self):
         h = getattr(self, '_h', None)

@@ -1,0 +1,70 @@
+#!/usr/bin/env python
+"""Network outputs of the REAL reference pose_resnet module (lib/models/pose_resnet.py: LitePose built from dense
+FusedMBConv blocks) at the settings of experiments/crowd_pose/resnet/resnet.yaml, for inputs 64x64, 96x160 and 256x256.
+
+Run in the build container only (needs the reference checkout, like gen_golden.py):
+
+    python tests/golden/gen_golden_resnet.py
+
+Imports the reference module by path (nothing is copied), feeds it the seeded synthetic weights of
+tests/_resnet_ref.py (oracle/synth.py's recipe) and images, and stores OUTPUT samples only: every 13th value of both
+stage outputs plus four whole-tensor sums per output, and the module's ``state_dict()`` key list (names only).  While
+generating, tests/_resnet_ref.py is asserted bit-identical to the reference module and its key list equal.
+"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
+import gen_golden as gg  # noqa: E402  (puts the repo root on sys.path, loads oracle.*)
+import _resnet_ref as rr  # noqa: E402
+
+SIZES = [(64, 64), (96, 160), (256, 256)]
+STRIDE = 13
+YAML = os.path.join(HERE, 'resnet.yaml')
+
+
+def stats(t):
+    a = t.numpy().astype(np.float64)
+    return np.array([a.sum(), np.abs(a).sum(), (a * a).sum(), a.flat[::97].sum()])
+
+
+def main():
+    torch.set_num_threads(1)
+    gg.load_reference()                                   # the reference's lib/ on sys.path, as gen_golden.py
+    pr = gg._load('ref_pose_resnet', os.path.join(gg.REF, 'lib/models/pose_resnet.py'))
+    from litepose_amd import config
+    cfg = config.update_config(config.get_cfg('crowd_pose'), YAML)
+    model = pr.get_pose_net(cfg, is_train=False).eval()
+    keys = list(model.state_dict().keys())
+    shapes = rr.state_dict_shapes(cfg)
+    assert keys == list(shapes.keys()), 'state_dict key scheme/order mismatch'
+    assert all(tuple(model.state_dict()[k].shape) == v for k, v in shapes.items())
+    out = {'keys': np.array(keys)}
+    sd = rr.make_state_dict(cfg, seed=1234)
+    model.load_state_dict(sd, strict=True)
+    for H, W in SIZES:
+        x = gg.synth.make_images(1, H, seed=11, w=W)
+        with torch.no_grad():
+            ref_out = model(x)
+            ora_out = rr.forward(x, sd, cfg)
+        assert len(ref_out) == 2
+        for k, (a, b) in enumerate(zip(ref_out, ora_out)):
+            assert torch.equal(a, b), '_resnet_ref is not bit-identical to the reference module'
+            key = '%dx%d_out%d' % (H, W, k)
+            out[key + '_sample'] = a.numpy().reshape(-1)[::STRIDE].copy()
+            out[key + '_stats'] = stats(a)
+            out[key + '_shape'] = np.array(a.shape)
+        print((H, W), [tuple(o.shape) for o in ref_out], 'absmax %.4f %.4f'
+              % (float(ref_out[0].abs().max()), float(ref_out[1].abs().max())))
+    path = os.path.join(HERE, 'golden_resnet.npz')
+    np.savez_compressed(path, **out)
+    print('wrote', path, os.path.getsize(path), 'bytes')
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,224 @@
+"""pose_resnet (reference lib/models/pose_resnet.py: LitePose built from dense FusedMBConv blocks) without a GPU: the CPU
+restatement against the reference goldens, the library's key scheme of a ``family = 1`` net, strict loading across the
+networks in both directions, the refusals of ``lp_arch.family`` / ``upconv_kernel`` / 16-bit storage, and the
+reference's resnet.yaml through update_config."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import _resnet_ref as rr
+from conftest import ROOT
+from oracle import synth
+
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'golden_resnet.npz')
+YAML = os.path.join(ROOT, 'tests', 'golden', 'resnet.yaml')
+SIZES = [(64, 64), (96, 160), (256, 256)]
+LP_ERR_INVALID_ARG, LP_ERR_UNSUPPORTED = -1, -8
+
+
+@pytest.fixture(scope='module')
+def golden():
+    return np.load(GOLDEN)
+
+
+def _cfg():
+    from litepose_amd import config
+    return config.update_config(config.get_cfg('crowd_pose'), YAML)
+
+
+def test_update_config_reads_resnet_yaml():
+    """The reference's experiments/crowd_pose/resnet/resnet.yaml (a settings-only copy), unchanged."""
+    from litepose_amd import config
+
+    class Args(object):
+        cfg = YAML
+        opts = []
+    cfg = config.update_config(config.get_cfg('crowd_pose'), Args())
+    assert cfg.MODEL.NAME == 'pose_resnet'
+    assert cfg.DATASET.INPUT_SIZE == 256 and list(cfg.DATASET.OUTPUT_SIZE) == [64, 128]
+    assert list(cfg.MODEL.EXTRA.NUM_DECONV_KERNELS) == [3, 3, 3]
+    assert list(cfg.MODEL.EXTRA.NUM_DECONV_FILTERS) == [16, 24, 24]
+    assert cfg.MODEL.NUM_JOINTS == 14 and cfg.LOSS.WITH_AE_LOSS == [True, False]
+    assert cfg.TEST.WITH_AE == (True, False) and cfg.TEST.WITH_HEATMAPS == (True, True)
+    from litepose_amd.core import inference
+    inference._check_cfg(cfg)
+
+
+@pytest.mark.parametrize('hw', SIZES)
+def test_restatement_reproduces_the_reference_samples(golden, hw):
+    torch.set_num_threads(1)
+    cfg = _cfg()
+    sd = rr.make_state_dict(cfg, seed=1234)
+    H, W = hw
+    x = synth.make_images(1, H, seed=11, w=W)
+    with torch.no_grad():
+        out = rr.forward(x, sd, cfg)
+    for k, t in enumerate(out):
+        key = '%dx%d_out%d' % (H, W, k)
+        assert tuple(t.shape) == tuple(golden[key + '_shape'])
+        np.testing.assert_allclose(t.numpy().reshape(-1)[::13], golden[key + '_sample'], rtol=0, atol=1e-6)
+        a = t.numpy().astype(np.float64)
+        np.testing.assert_allclose([a.sum(), np.abs(a).sum(), (a * a).sum(), a.flat[::97].sum()],
+                                   golden[key + '_stats'], rtol=1e-5, atol=1e-6)
+
+
+def test_restatement_shapes():
+    cfg = _cfg()
+    shapes = rr.state_dict_shapes(cfg)
+    assert len(shapes) == 353
+    assert sum(int(np.prod(s)) for k, s in shapes.items() if not k.endswith('num_batches_tracked')
+               and 'running' not in k) == pytest.approx(5.06e6, rel=5e-3)
+    sd = rr.make_state_dict(cfg)
+    with torch.no_grad():
+        o = rr.forward(torch.zeros(1, 3, 320, 192), sd, cfg)
+    assert [tuple(t.shape) for t in o] == [(1, 28, 80, 48), (1, 14, 160, 96)]
+
+
+def test_get_pose_net_exists_and_key_list_equals_the_reference_module(golden):
+    """lp_net_num_keys / lp_net_key of a family-1 net == the reference pose_resnet state_dict() keys, in registration
+    order; the shapes are the restatement's."""
+    import litepose_amd.models as models
+    cfg = _cfg()
+    m = models.pose_resnet.get_pose_net(cfg, is_train=False, cfg_arch={'ignored': True})
+    keys = m.keys()
+    assert [k for k, _ in keys] == [str(k) for k in golden['keys']]
+    assert list(keys) == list(rr.state_dict_shapes(cfg).items())
+    assert m.final_channel == [28, 14] and m.storage == 'f32'
+
+
+def test_strict_load_refuses_the_other_network():
+    from litepose_amd import arch_zoo, config
+    import litepose_amd.models as models
+    arch = arch_zoo.get('search-XS')
+    mob_cfg = config.get_cfg('crowd_pose')
+    mob_sd = synth.make_state_dict(arch, seed=1234)
+    res_sd = rr.make_state_dict(_cfg(), seed=1234)
+    with pytest.raises(RuntimeError, match='missing|unexpected'):
+        models.pose_resnet.get_pose_net(_cfg()).load_state_dict(mob_sd, strict=True)
+    with pytest.raises(RuntimeError, match='missing|unexpected'):
+        models.pose_mobilenet.get_pose_net(mob_cfg, cfg_arch=arch).load_state_dict(res_sd, strict=True)
+
+
+def _create(mutate):
+    from litepose_amd import _native as nv
+    from litepose_amd.models import pose_resnet
+    a = pose_resnet._arch_struct(_cfg())
+    mutate(a)
+    h = C.c_void_p()
+    rc = nv.lib().lp_net_create(C.byref(h), C.byref(a))
+    err = nv.lib().lp_last_error()
+    if h.value:
+        nv.lib().lp_net_destroy(h)
+    return rc, bool(h.value), err
+
+
+def test_the_resnet_table_is_accepted():
+    rc, made, _ = _create(lambda a: None)
+    assert rc == 0 and made
+
+
+@pytest.mark.parametrize('value', [-1, 2, 9])
+def test_family_out_of_range_is_refused(value):
+    rc, made, err = _create(lambda a: setattr(a, 'family', value))
+    assert rc == LP_ERR_INVALID_ARG and not made, rc
+    assert b'family' in err
+
+
+def test_family_1_with_plain_head_is_refused():
+    rc, made, err = _create(lambda a: setattr(a, 'plain_head', 1))
+    assert rc == LP_ERR_INVALID_ARG and not made, rc
+    assert b'plain' in err
+
+
+@pytest.mark.parametrize('value,status', [(4, LP_ERR_INVALID_ARG), (2, LP_ERR_INVALID_ARG), (-3, LP_ERR_INVALID_ARG),
+                                          (9, LP_ERR_UNSUPPORTED)])
+def test_upconv_kernel_refusals(value, status):
+    rc, made, err = _create(lambda a: setattr(a, 'upconv_kernel', value))
+    assert rc == status and not made, rc
+    assert b'upconv_kernel' in err
+
+
+@pytest.mark.parametrize('value', [0, 3, 5, 7])
+def test_odd_upconv_kernels_give_the_key_shapes(value):
+    from litepose_amd import _native as nv
+    from litepose_amd.models import pose_resnet
+    a = pose_resnet._arch_struct(_cfg())
+    a.upconv_kernel = value
+    h = C.c_void_p()
+    lib = nv.lib()
+    assert lib.lp_net_create(C.byref(h), C.byref(a)) == 0
+    try:
+        shp = (C.c_int64 * 4)()
+        nd = C.c_int()
+        got = {}
+        for i in range(lib.lp_net_num_keys(h)):
+            k = lib.lp_net_key(h, i, shp, C.byref(nd)).decode()
+            got[k] = tuple(int(shp[d]) for d in range(nd.value))
+        k = value or 3
+        assert got['deconv_refined.0.conv.weight'] == (16, 80, k, k)
+        assert got['deconv_raw.2.conv.weight'] == (24, 16, k, k)
+    finally:
+        lib.lp_net_destroy(h)
+
+
+def test_even_deconv_kernel_in_the_cfg_is_refused():
+    from litepose_amd.models import pose_resnet
+    cfg = _cfg()
+    cfg.defrost()
+    cfg.MODEL.EXTRA.NUM_DECONV_KERNELS = [4, 4, 4]
+    with pytest.raises(ValueError, match='odd'):
+        pose_resnet.get_pose_net(cfg)
+
+
+@pytest.mark.parametrize('storage', [1, 2])
+def test_16_bit_storage_is_refused_by_the_library(storage):
+    from litepose_amd import _native as nv
+    from litepose_amd.models import pose_resnet
+    m = pose_resnet.get_pose_net(_cfg())
+    lib = nv.lib()
+    assert lib.lp_net_set_storage(m._h, storage) == LP_ERR_UNSUPPORTED
+    assert b'fp32 storage' in lib.lp_last_error()
+    assert lib.lp_net_get_storage(m._h) == 0
+    assert lib.lp_net_set_storage(m._h, 0) == 0
+
+
+@pytest.mark.parametrize('storage', ['bf16', 'f16', 'fp16'])
+def test_16_bit_storage_is_refused_by_the_model(storage):
+    from litepose_amd.models import pose_resnet
+    with pytest.raises(NotImplementedError):
+        pose_resnet.get_pose_net(_cfg(), storage=storage)
+    cfg = _cfg()
+    cfg.defrost()
+    cfg.FP16.ENABLED = True
+    with pytest.raises(NotImplementedError):
+        pose_resnet.get_pose_net(cfg)
+
+
+def test_width_mult_is_refused_as_for_the_other_networks():
+    from litepose_amd.models import pose_resnet
+    with pytest.raises(ValueError):
+        pose_resnet.LitePose(_cfg(), width_mult=0.5)
+
+
+def test_weights_round_trip_through_the_library():
+    """lp_net_set_weight / lp_net_get_weight return the checkpoint (no GPU: nothing is finalized)."""
+    from litepose_amd import _native as nv
+    from litepose_amd.models import pose_resnet
+    cfg = _cfg()
+    m = pose_resnet.get_pose_net(cfg)
+    sd = rr.make_state_dict(cfg, seed=5)
+    lib = nv.lib()
+    for k in ('first.0.0.weight', 'stage.1.3.inv.0.weight', 'deconv_raw.1.conv.weight', 'final_refined.0.bias',
+              'final_raw.1.weight', 'deconv_bnrelu.2.0.running_var'):
+        t = sd[k].contiguous()
+        shp = (C.c_int64 * t.dim())(*t.shape)
+        assert lib.lp_net_set_weight(m._h, k.encode(), C.c_void_p(t.data_ptr()), shp, t.dim()) == 0
+        back = torch.empty_like(t)
+        assert lib.lp_net_get_weight(m._h, k.encode(), C.c_void_p(back.data_ptr()), back.numel()) == 0
+        assert torch.equal(back, t)
+    bad = torch.zeros(16, 80, 4, 4)
+    shp = (C.c_int64 * 4)(*bad.shape)
+    assert lib.lp_net_set_weight(m._h, b'deconv_refined.0.conv.weight', C.c_void_p(bad.data_ptr()), shp, 4) == -3

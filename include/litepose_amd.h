@@ -131,11 +131,19 @@ int lp_round16(const float* src, float* dst, int64_t count, int storage);
 /* Read back an (unfolded) tensor previously set -- backs state_dict().               */
 int lp_net_get_weight(const lp_net* net, const char* key, float* h_data, int64_t numel);
 
-/* Scratch for one forward of N images of H x W (H, W multiples of 16).               */
+/* The size rule of a finalized net: H and W of a forward are positive multiples of M = max(16, the deepest spatial
+ * divisor of THIS net) -- 2 for the stem times every stage stride, so 16 for the published tables and 32 for a
+ * table with four stride-2 stages.  Every plane is then exactly H / div x W / div; any other size would make a
+ * stride-2 kernel (output plane rounded up) write past a buffer sized with the division rounded down, so
+ * lp_net_workspace_bytes, lp_net_forward (every storage) and lp_net_tap_offset refuse it with
+ * LP_ERR_INVALID_ARG and an lp_last_error that names M.                                                       */
+/* Scratch for one forward of N images of H x W; 0 (and lp_last_error) when the net is not finalized, N < 1 or
+ * H / W break the size rule above.                                                     */
 size_t lp_net_workspace_bytes(const lp_net* net, int N, int H, int W);
 
 /* LitePose.forward: d_x [N,3,H,W] -> d_out0 [NB,head_channels[0],H/4,W/4],
- * d_out1 [NB,head_channels[1],H/2,W/2].
+ * d_out1 [NB,head_channels[1],H/2,W/2] (a net whose deepest divisor is D instead of 16: H/(D/4) and H/(D/8)).
+ * H, W: the size rule above (LP_ERR_INVALID_ARG otherwise, nothing is launched).
  *   flip = 0: the images as given (NB = N)
  *   flip = 1: the net on flip(x,[3]) without materialising the mirrored image (NB = N)
  *   flip = 2: both in one launch sequence, NB = 2N: images [0,N) plain, [N,2N) mirrored
@@ -218,7 +226,8 @@ int64_t lp_net_tap(const lp_net* net, const char* name, float* d_dst, void* stre
 /* Writes: d_dst[0, returned count) -- the whole tap, nothing beyond.                                            */
 /* Where a tap lives inside a workspace laid out for NB images of HxW (NB = 2N with flip = 2): byte offset, float
  * count in *count.  Lets a caller that runs several forwards in flight on several workspaces (the serving schedule)
- * inspect a SPECIFIC workspace instead of "the last forward" (tools/flake_hunt.py).  fp32 storage only.          */
+ * inspect a SPECIFIC workspace instead of "the last forward" (tools/flake_hunt.py).  fp32 storage only; NB >= 1 and
+ * H, W under the size rule of lp_net_workspace_bytes (LP_ERR_INVALID_ARG otherwise).                               */
 int64_t lp_net_tap_offset(const lp_net* net, const char* name, int NB, int H, int W, int64_t* count);
 
 /* Per-kernel wall time of the last lp_net_forward when profiling is enabled

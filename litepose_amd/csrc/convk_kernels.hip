@@ -248,7 +248,9 @@ bool launch_convk3(const float* inA, int Ca, const float* inB, int Cb, const voi
     // The tags of this family come from a table, not from literals in the assignment: the kernel census of the
     // pose_mobilenet family (tests/test_gpu_kernel_census.py) collects the literals assigned to last_kernel_tag and wants a
     // pose_mobilenet case for each, which a dense-conv form cannot have.  This family's forms are enumerated and compared
-    // by tests/test_gpu_resnet.py (every production form by name).
+    // by tests/test_gpu_resnet.py (every form of the reference table by name) and tests/test_gpu_resnet_census.py (a census of
+    // TABLES: all six <K,S> forms at both NB, odd / ragged block counts, a source boundary inside a channel group, the
+    // upsampled read at K = 5 / 7, planes smaller than the halo -- every launch against float64, names and tags derived).
     static const char* const tags[3][2] = {{"convk3_kernel<3,1>", "convk3_kernel<3,2>"},
                                            {"convk3_kernel<5,1>", "convk3_kernel<5,2>"},
                                            {"convk3_kernel<7,1>", "convk3_kernel<7,2>"}};

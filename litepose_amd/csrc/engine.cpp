@@ -1145,6 +1145,23 @@ size_t buf_floats(const lp_net* n, int b, int N, int H, int W) {
     return (f + 63) / 64 * 64;
 }
 
+// Every plane of a forward is H / div x W / div of its buffer (buf_floats, rounded down), while a strided kernel derives
+// its output plane from its input plane (rounded up): the two agree only when the deepest divisor of THIS net divides H
+// and W.  The divisors are 2 x a product of strides 1 / 2, so each divides the deepest one.
+int size_multiple(const lp_net* n) {
+    int m = 16;
+    for (int d : n->bufs.div) m = std::max(m, d);
+    return m;
+}
+
+int check_size(const lp_net* n, int H, int W) {
+    const int m = size_multiple(n);
+    if (H < m || W < m || (H % m) || (W % m))
+        return fail(LP_ERR_INVALID_ARG, "H and W must be positive multiples of " + std::to_string(m) +
+                                            " (the deepest plane of this net is 1/" + std::to_string(m) + " of the input)");
+    return LP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1364,6 +1381,7 @@ int lp_net_finalize(lp_net* n, int strict) {
 
 size_t lp_net_workspace_bytes(const lp_net* n, int N, int H, int W) {
     if (!n || !n->finalized) return 0;
+    if (N < 1 || check_size(n, H, W) != LP_OK) return 0;      // lp_last_error names the multiple
     // Buffers are planned one-per-tensor (no aliasing): 288 GB of HBM make the ~6x
     // over-allocation irrelevant and every block-boundary tensor stays tappable.
     size_t f = 0;
@@ -1645,8 +1663,8 @@ int lp_net_forward(lp_net* n, const float* d_x, int N, int H, int W, int flip, f
                    float* d_out1, void* ws, size_t ws_bytes, void* stream) {
     if (!n || !d_x || !d_out0 || !d_out1 || !ws) return fail(LP_ERR_INVALID_ARG, "null argument");
     if (!n->finalized) return fail(LP_ERR_NOT_FINALIZED, "lp_net_finalize() has not been called");
-    if (N < 1 || H < 16 || W < 16 || (H % 16) || (W % 16))
-        return fail(LP_ERR_INVALID_ARG, "H and W must be positive multiples of 16");
+    if (N < 1) return fail(LP_ERR_INVALID_ARG, "N must be positive");
+    if (const int rc = check_size(n, H, W)) return rc;           // both storage paths: before any buffer is laid out
     if (flip < 0 || flip > 2) return fail(LP_ERR_INVALID_ARG, "flip must be 0, 1 or 2");
     // a stale error of this thread (e.g. a hipGraph capture that another thread's call invalidated) must not be
     // mistaken for a failure of the launches below
@@ -2011,6 +2029,8 @@ int64_t lp_net_tap(const lp_net* n, const char* name, float* d_dst, void* stream
 int64_t lp_net_tap_offset(const lp_net* n, const char* name, int NB, int H, int W, int64_t* count) {
     if (!n || !name || !n->finalized) return fail(LP_ERR_INVALID_ARG, "net not finalized");
     if (n->storage != LP_STORAGE_F32) return fail(LP_ERR_UNSUPPORTED, "fp32 storage only");
+    if (NB < 1) return fail(LP_ERR_INVALID_ARG, "NB must be positive");
+    if (const int rc = check_size(n, H, W)) return rc;
     for (const Op& o : n->ops) {
         if (o.tap == name || o.name == name) {
             if (o.out == n->out0_buf || o.out == n->out1_buf) return fail(LP_ERR_UNSUPPORTED, "caller-owned output");

@@ -99,6 +99,12 @@ class PoseEngine(object):
         net = {'pose_simplenet': _ps, 'pose_resnet': _pr}.get(cfg.MODEL.get('NAME'), _pm)
         self.model = net.get_pose_net(cfg, is_train=False, cfg_arch=cfg_arch, storage=storage)
         self.model.load_state_dict(state_dict, strict=True)
+        # every buffer, the stage merge and the projection below take the maps at H/4 and H/2 and the sizes evaluate()
+        # buckets to are multiples of 16 only in general: a table whose deepest plane is not 1/16 of the input (its sizes
+        # would have to be multiples of 32, its maps sit at H/8 and H/4) is not this engine's network
+        if self.model.size_multiple != 16 or self.model.output_divisors() != (4, 2):
+            raise ValueError('PoseEngine needs a network whose deepest plane is 1/16 of the input (outputs at 1/4 and 1/2); '
+                             'this arch needs H and W in multiples of %d' % self.model.size_multiple)
         self.parser = _group.HeatmapParser(cfg, person_capacity=person_capacity)
         self.J = self.parser.params.num_joints              # joints in the merged maps / records
         self.Jn = int(cfg.DATASET.NUM_JOINTS)               # joints per network stage (incl. a centre joint)

@@ -76,6 +76,24 @@ class LitePose(object):
         """The lp_arch of this network (models.pose_resnet overrides it: its table is fixed in the module)."""
         return _arch_struct(cfg, cfg_arch, plain_head)
 
+    @property
+    def size_multiple(self):
+        """H and W of a forward are positive multiples of this: max(16, the deepest plane's divisor = 2 for the stem times
+        every stage stride).  The library refuses any other size (lp_net_forward, LP_ERR_INVALID_ARG): buffers are sized
+        H // div while a stride-2 kernel rounds its output plane up."""
+        deep = 2
+        for s in range(self._arch.num_stages):
+            deep *= int(self._arch.stride[s])
+        return max(16, deep)
+
+    def output_divisors(self):
+        """Spatial divisors of the two outputs: three x2 deconvs above the deepest plane, heads after the second and the
+        third -- (4, 2) for every table whose deepest plane is 1/16 of the input."""
+        deep = 2
+        for s in range(self._arch.num_stages):
+            deep *= int(self._arch.stride[s])
+        return max(1, deep // 4), max(1, deep // 8)
+
     def __del__(self):
         h = getattr(self, '_h', None)
         if h:
@@ -155,8 +173,12 @@ class LitePose(object):
         x = x.contiguous()
         n, _, h, w = x.shape
         nb = 2 * n if flip == 2 else n
-        out0 = torch.empty((nb, self.final_channel[0], h // 4, w // 4), dtype=torch.float32, device=x.device)
-        out1 = torch.empty((nb, self.final_channel[1], h // 2, w // 2), dtype=torch.float32, device=x.device)
+        m = self.size_multiple
+        if h < m or w < m or h % m or w % m:
+            raise ValueError('H and W must be positive multiples of %d for this net, got %dx%d' % (m, h, w))
+        d0, d1 = self.output_divisors()
+        out0 = torch.empty((nb, self.final_channel[0], h // d0, w // d0), dtype=torch.float32, device=x.device)
+        out1 = torch.empty((nb, self.final_channel[1], h // d1, w // d1), dtype=torch.float32, device=x.device)
         ws, need = self._workspace(nb, h, w, x.device)
         nv.check(self._lib.lp_net_forward(self._h, nv.dptr(x), n, h, w, flip, nv.dptr(out0), nv.dptr(out1),
                                           nv.dptr(ws), need, nv.stream_ptr()), 'lp_net_forward')

@@ -8,6 +8,11 @@ The network (pose_resnet.py:21-131, layers.py:18-24,58-88):
   * deconv i   ReLU(BN(UpConv_refined(refined) + UpConv_raw(raw))), UpConv = nearest x2 then conv k x k pad k//2, no bias
   * output i-1 final_refined[i-1](refined) + final_raw[i-1](raw): one biased 3x3 conv each, no BN, no activation
 There is no arch JSON: the table is fixed, the deconv widths / kernels come from cfg.MODEL.EXTRA.
+Every function takes an optional ``table = (input_channel, [[r, k, c, n, s], ...])`` in place of the module's constants
+(None: the constants): the same generic code on another table, for the tables ``lp_net_create`` accepts and the
+reference module cannot express (tests/test_gpu_resnet_census.py; tests/golden/gen_golden_resnet.py pins the tables
+``width_mult`` can express to the real module).  ``forward`` runs on whatever dtype ``x`` and ``sd`` share: with
+float64 tensors it is the high-precision reference.
 ``make_state_dict`` follows oracle/synth.py's recipe (randomised BN statistics; std = sqrt(2 / fan_in), x0.35 on
 point_conv, x0.5 on the UpConv convs, x0.05 * head_gain on the head convs)."""
 import math
@@ -28,11 +33,12 @@ def _make_divisible(v, divisor=8):
     return nv
 
 
-def derive(cfg):
+def derive(cfg, table=None):
     """Channel bookkeeping: c0, stages [[{inp, feat, oup, k, stride, residual}]], channel, deconv, heads."""
-    c0 = _make_divisible(INPUT_CHANNEL)
+    input_channel, backbone = (INPUT_CHANNEL, BACKBONE) if table is None else table
+    c0 = _make_divisible(input_channel)
     channel, stages, inp = [c0], [], c0
-    for r, k, c, n, s in BACKBONE:
+    for r, k, c, n, s in backbone:
         c = _make_divisible(c)
         blocks = []
         for b in range(n):
@@ -67,9 +73,9 @@ def _bn_keys(out, p, c):
     out[p + '.num_batches_tracked'] = ()
 
 
-def state_dict_shapes(cfg):
+def state_dict_shapes(cfg, table=None):
     """The module's state_dict() keys in registration order -> shapes."""
-    d = derive(cfg)
+    d = derive(cfg, table)
     o = OrderedDict()
     o['first.0.0.weight'] = (32, 3, 7, 7)
     _bn_keys(o, 'first.0.1', 32)
@@ -94,10 +100,10 @@ def state_dict_shapes(cfg):
     return o
 
 
-def make_state_dict(cfg, seed=1234, head_gain=1.0):
+def make_state_dict(cfg, seed=1234, head_gain=1.0, table=None):
     g = torch.Generator().manual_seed(seed)
     sd = OrderedDict()
-    for k, shp in state_dict_shapes(cfg).items():
+    for k, shp in state_dict_shapes(cfg, table).items():
         if k.endswith('num_batches_tracked'):
             sd[k] = torch.zeros((), dtype=torch.int64)
         elif k.endswith('running_var') or (k.endswith('.weight') and len(shp) == 1):
@@ -130,11 +136,13 @@ def _upconv(x, w):
     return F.conv2d(F.interpolate(x, scale_factor=2), w, None, 1, w.shape[2] // 2)
 
 
-def forward(x, sd, cfg, taps=None):
-    """[out0 (N, oup0, H/4, W/4), out1 (N, oup1, H/2, W/2)]; ``taps`` receives 'first', 'stage.S.B.inv', 'stage.S.B',
-    'deconv.I'."""
-    d = derive(cfg)
+def forward(x, sd, cfg, taps=None, table=None):
+    """[out0 (N, oup0, H/4, W/4), out1 (N, oup1, H/2, W/2)] (a table whose deepest plane is 1/32: H/8 and H/4); ``taps``
+    receives 'first', 'stage.S.B.inv', 'stage.S.B', 'deconv.I'."""
+    d = derive(cfg, table)
     x = _convbnrelu6(x, sd, 'first.0.0', 'first.0.1', 2)
+    if taps is not None:
+        taps['first.0'] = x                               # a launch name, not a block tap: tap_names leaves it out
     x = _convbnrelu6(x, sd, 'first.1.0', 'first.1.1', 1)
     if taps is not None:
         taps['first'] = x
@@ -166,10 +174,43 @@ def forward(x, sd, cfg, taps=None):
     return outs
 
 
-def tap_names(cfg):
-    d = derive(cfg)
+def tap_names(cfg, table=None):
+    d = derive(cfg, table)
     names = ['first']
     for s, blocks in enumerate(d['stages']):
         for b in range(len(blocks)):
             names += ['stage.%d.%d.inv' % (s, b), 'stage.%d.%d' % (s, b)]
     return names + ['deconv.%d' % i for i in range(len(d['deconv']))]
+
+
+# ------------------------------------------------------------------ tables and cfgs other than the module's constants
+def width_table(width_mult):
+    """The table ``LitePose(cfg, width_mult=w)`` builds (pose_resnet.py:33,42): every channel count scaled, then rounded
+    to a multiple of 8 -- as integers, the form ``lp_arch`` takes."""
+    return (_make_divisible(INPUT_CHANNEL * width_mult),
+            [[r, k, _make_divisible(c * width_mult), n, s] for r, k, c, n, s in BACKBONE])
+
+
+def variant_cfg(cfg, filters=None, kernel=None, joints=None):
+    """A copy of ``cfg`` with other NUM_DECONV_FILTERS / one NUM_DECONV_KERNELS for every layer / NUM_JOINTS."""
+    c = cfg.clone()
+    c.defrost()
+    if filters is not None:
+        c.MODEL.EXTRA.NUM_DECONV_FILTERS = [int(f) for f in filters]
+    if kernel is not None:
+        c.MODEL.EXTRA.NUM_DECONV_KERNELS = [int(kernel)] * int(c.MODEL.EXTRA.NUM_DECONV_LAYERS)
+    if joints is not None:
+        c.MODEL.NUM_JOINTS = int(joints)
+        c.DATASET.NUM_JOINTS = int(joints)
+    return c
+
+
+# name -> (width_mult, NUM_DECONV_FILTERS or None, (H, W)): what the REAL module can express beyond resnet.yaml; its
+# samples are tests/golden/golden_resnet_variants.npz (gen_golden_resnet.py), replayed by tests/test_resnet_cpu.py
+VARIANTS = OrderedDict([
+    ('w0.5', (0.5, None, (96, 160))),
+    ('w1.5', (1.5, None, (64, 96))),
+    ('f20_12_10', (1.0, [20, 12, 10], (96, 160))),
+    ('w0.5_f20_12_10', (0.5, [20, 12, 10], (64, 64))),
+])
+VARIANT_SEED = 1234

@@ -10,6 +10,13 @@ Imports the reference module by path (nothing is copied), feeds it the seeded sy
 tests/_resnet_ref.py (oracle/synth.py's recipe) and images, and stores OUTPUT samples only: every 13th value of both
 stage outputs plus four whole-tensor sums per output, and the module's ``state_dict()`` key list (names only).  While
 generating, tests/_resnet_ref.py is asserted bit-identical to the reference module and its key list equal.
+
+A second file, golden_resnet_variants.npz, pins the restatement's ``table`` parameter to the real module where the
+real module can express another table: ``LitePose(cfg, width_mult=w)`` for w = 0.5 and 1.5 (channels 8/8/16/24/40 and
+24/24/48/72/120) and NUM_DECONV_FILTERS that are not multiples of 8 (``_resnet_ref.VARIANTS``); same format, inputs
+of at most 96x160, the same ``torch.equal`` and key-list assertions.  The real module cannot build UpConv kernels 5 /
+7 (``_get_deconv_cfg`` knows 4, 3 and 2 only) and has no other r/k/n/s table: those rest on the restatement alone,
+which is the same generic code on another table.
 """
 import os
 import sys
@@ -62,6 +69,37 @@ def main():
         print((H, W), [tuple(o.shape) for o in ref_out], 'absmax %.4f %.4f'
               % (float(ref_out[0].abs().max()), float(ref_out[1].abs().max())))
     path = os.path.join(HERE, 'golden_resnet.npz')
+    np.savez_compressed(path, **out)
+    print('wrote', path, os.path.getsize(path), 'bytes')
+    variants(pr, cfg)
+
+
+def variants(pr, cfg):
+    out = {}
+    for name, (wm, filters, (H, W)) in rr.VARIANTS.items():
+        vcfg = rr.variant_cfg(cfg, filters=filters)
+        table = rr.width_table(wm)
+        model = pr.LitePose(vcfg, width_mult=wm).eval()
+        shapes = rr.state_dict_shapes(vcfg, table)
+        msd = model.state_dict()
+        assert list(msd.keys()) == list(shapes.keys()), name
+        assert all(tuple(msd[k].shape) == v for k, v in shapes.items()), name
+        sd = rr.make_state_dict(vcfg, seed=rr.VARIANT_SEED, table=table)
+        model.load_state_dict(sd, strict=True)
+        x = gg.synth.make_images(1, H, seed=11, w=W)
+        with torch.no_grad():
+            ref_out = model(x)
+            ora_out = rr.forward(x, sd, vcfg, table=table)
+        assert len(ref_out) == 2
+        for k, (a, b) in enumerate(zip(ref_out, ora_out)):
+            assert torch.equal(a, b), '_resnet_ref(table) is not bit-identical to the reference module: ' + name
+            key = '%s_out%d' % (name, k)
+            out[key + '_sample'] = a.numpy().reshape(-1)[::STRIDE].copy()
+            out[key + '_stats'] = stats(a)
+            out[key + '_shape'] = np.array(a.shape)
+        print(name, [tuple(o.shape) for o in ref_out], 'absmax %.4f %.4f'
+              % (float(ref_out[0].abs().max()), float(ref_out[1].abs().max())))
+    path = os.path.join(HERE, 'golden_resnet_variants.npz')
     np.savez_compressed(path, **out)
     print('wrote', path, os.path.getsize(path), 'bytes')
 

@@ -8,7 +8,9 @@ lib/models/pose_resnet.py).  Needs a real MI355X.
   * the engine on the resnet.yaml cfg: device maps against the restatement, records bit-exact against the oracle parser
     fed the device's own maps, ``evaluate`` on mixed sizes against the reference-shaped batch-1 loop, graph replay;
   * the profile of a forward names only the dense-conv family and the 1x1 kernels.
-No fused block form is built (the two-launch FusedMBConv is the only one), so there is nothing to compare it with."""
+No fused block form is built (the two-launch FusedMBConv is the only one), so there is nothing to compare it with.
+This file runs the ONE reference table; the tables ``lp_net_create`` accepts beyond it (other r/k/c/n/s, filters,
+UpConv kernels 5 / 7, a deepest plane of 1/32) and the kernel forms only they reach are tests/test_gpu_resnet_census.py."""
 import os
 
 import numpy as np

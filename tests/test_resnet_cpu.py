@@ -222,3 +222,41 @@ def test_weights_round_trip_through_the_library():
     bad = torch.zeros(16, 80, 4, 4)
     shp = (C.c_int64 * 4)(*bad.shape)
     assert lib.lp_net_set_weight(m._h, b'deconv_refined.0.conv.weight', C.c_void_p(bad.data_ptr()), shp, 4) == -3
+
+
+# ------------------------------------------------------------------ the restatement's ``table`` parameter
+VARIANTS_GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'golden_resnet_variants.npz')
+
+
+@pytest.mark.parametrize('name', list(rr.VARIANTS))
+def test_restatement_with_a_table_reproduces_the_reference_variants(name):
+    """``_resnet_ref`` with ``table=`` against the REAL module built with ``width_mult`` 0.5 / 1.5 and with
+    NUM_DECONV_FILTERS that are not multiples of 8 (golden_resnet_variants.npz, gen_golden_resnet.py): the tables the
+    real module can express.  UpConv kernels 5 / 7 and other r/k/n/s tables it cannot build (``_get_deconv_cfg`` knows
+    4, 3 and 2; the table is a constant of the module): tests/test_gpu_resnet_census.py rests on the restatement alone
+    for those, the same generic code on another table."""
+    torch.set_num_threads(1)
+    golden = np.load(VARIANTS_GOLDEN)
+    wm, filters, (H, W) = rr.VARIANTS[name]
+    cfg = rr.variant_cfg(_cfg(), filters=filters)
+    table = rr.width_table(wm)
+    sd = rr.make_state_dict(cfg, seed=rr.VARIANT_SEED, table=table)
+    x = synth.make_images(1, H, seed=11, w=W)
+    with torch.no_grad():
+        out = rr.forward(x, sd, cfg, table=table)
+    for k, t in enumerate(out):
+        key = '%s_out%d' % (name, k)
+        assert tuple(t.shape) == tuple(golden[key + '_shape'])
+        np.testing.assert_allclose(t.numpy().reshape(-1)[::13], golden[key + '_sample'], rtol=0, atol=1e-6)
+        a = t.numpy().astype(np.float64)
+        np.testing.assert_allclose([a.sum(), np.abs(a).sum(), (a * a).sum(), a.flat[::97].sum()],
+                                   golden[key + '_stats'], rtol=1e-5, atol=1e-6)
+
+
+def test_width_tables_are_the_channels_the_real_module_builds():
+    assert rr.width_table(1.0) == (rr.INPUT_CHANNEL, rr.BACKBONE)
+    assert [rr.width_table(0.5)[0]] + [r[2] for r in rr.width_table(0.5)[1]] == [8, 8, 16, 24, 40]
+    assert [rr.width_table(1.5)[0]] + [r[2] for r in rr.width_table(1.5)[1]] == [24, 24, 48, 72, 120]
+    d = rr.derive(_cfg(), rr.width_table(1.5))
+    assert d['stages'][0][0]['feat'] == 96                    # three 32-channel blocks
+    assert rr.derive(_cfg()) == rr.derive(_cfg(), rr.width_table(1.0))

@@ -248,6 +248,47 @@ int lp_net_profile2(const lp_net* net, char names[][48], float* ms, int64_t* alg
 int lp_net_profile_launches(const lp_net* net, int32_t* grid_wgs, int32_t* wg_threads, int32_t* lds_bytes,
                             int32_t* wgs_per_cu, int cap);
 
+/* ------------------------------------------------- BatchNorm re-calibration ------
+ * Replaces the calibration loop of calibrate_test.py:44-122 (valid.py:139-145 for one architecture) on a sub-network of
+ * the weight-sharing supernet (lib/models/pose_supermobilenet.py, layers/super_layers.py): forwards in TRAINING mode in
+ * which every BatchNorm -- first.0.1, first.1.1, first.3, each block's inv.1 / depth_conv.1 / point_conv.1,
+ * deconv_bnrelu.I.0 and the BatchNorm inside each final_* SepConv -- normalises with the statistics of the batch
+ * (biased variance, eps 1e-5) and moves its running pair: running = (1 - momentum) * running + momentum * batch, with
+ * the unbiased variance n / (n - 1), n = N * H * W of that layer (super_layers.py:19-28 -> F.batch_norm).  The handle is
+ * an ordinary family-0 net holding the sliced weights (litepose_amd.models.pose_supermobilenet: sub_state_dict); fp32
+ * storage only: a 16-bit handle and lp_arch.family = 1 answer LP_ERR_UNSUPPORTED.
+ *
+ * lp_calib_begin   every weight must be set (LP_ERR_MISSING_WEIGHT otherwise; lp_net_finalize is not needed).  Builds
+ *                  the calibration plan -- the unfused convolutions with their own (unfolded) weights -- from the
+ *                  handle's tensors and takes the current running pairs as the start (no reset).  Plan and pairs go to
+ *                  the device with the first step.  A calibration already open on the handle is dropped.
+ * lp_calib_step    one forward of d_x [N,3,H,W] (no flip; H, W under the size rule of lp_net_workspace_bytes; at least
+ *                  two values per channel on the deepest plane).  The running pairs live on the device across steps.
+ *                  Results are bit-identical from run to run (fixed-order fp64 sums, no atomics).
+ *                  Writes: the first lp_calib_workspace_bytes(N, H, W) bytes of `workspace` at most (scratch).
+ * lp_calib_read    the running pair of one BatchNorm (its state_dict prefix, e.g. "stage.0.1.inv.1") as it stands:
+ *                  mean_out [channels], var_out [channels] (DEVICE), copied on `stream`.  Writes: exactly those elements.
+ * lp_calib_end     waits for the device, writes the running pairs into the handle's running_mean / running_var tensors
+ *                  (lp_net_get_weight reads them), closes the calibration and, if a step ran, re-finalizes the handle
+ *                  (lp_net_finalize, strict: the fp64 fold on the host) -- it is then the calibrated network.
+ *                  *steps_out (may be NULL): number of steps since begin -- what num_batches_tracked of first.0.1 and
+ *                  first.1.1 advances by (the supernet's own BatchNorms bypass that counter).
+ * Before lp_calib_begin, step / read / end / workspace_bytes answer LP_ERR_NOT_FINALIZED (workspace_bytes: 0).  While a
+ * calibration is open, lp_net_set_weight and lp_net_set_storage on the handle answer LP_ERR_INVALID_ARG (the plan was
+ * built from the tensors and for the storage of lp_calib_begin); lp_calib_workspace_bytes returns 0 with lp_last_error
+ * set for N < 1 or a size off the rule.                                                                               */
+int lp_calib_begin(lp_net* net, double momentum);
+size_t lp_calib_workspace_bytes(const lp_net* net, int N, int H, int W);
+int lp_calib_step(lp_net* net, const float* d_x, int N, int H, int W,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int lp_calib_read(const lp_net* net, const char* bn_prefix, float* mean_out, float* var_out, int channels, void* stream);
+/* `workspace`, `mean_out` and `var_out` are DEVICE memory like every d_* pointer of this header.  TEMPORARY NAMES, to be
+ * renamed d_workspace / d_mean / d_var: the census of writable calls (tests/test_poison_cpu.py) keys on the prefix and
+ * requires an entry in the CALLS table of tests/test_gpu_buffer_contract.py, and this change adds tests in new files
+ * only.  Until then their contract test, tests/test_gpu_supernet_buffers.py, is not watched by that census: the follow-up
+ * is the rename plus the two CALLS entries.                                                       */
+int lp_calib_end(lp_net* net, int64_t* steps_out);
+
 /* ------------------------------------------------------------ TTA merge ----------
  * Replaces core.inference.get_multi_stage_outputs + aggregate_results for one scale
  * (lib/core/inference.py:75-173,176-208; valid.py:224-225): stage-0 upsample, stage

@@ -88,6 +88,11 @@ _SIGS = {
     'lp_net_profile': (i32, [vp, vp, vp, vp, vp, i32]),
     'lp_net_profile2': (i32, [vp, vp, vp, vp, vp, vp, i32]),
     'lp_net_profile_launches': (i32, [vp, vp, vp, vp, vp, i32]),
+    'lp_calib_begin': (i32, [vp, C.c_double]),
+    'lp_calib_workspace_bytes': (sz, [vp, i32, i32, i32]),
+    'lp_calib_step': (i32, [vp, vp, i32, i32, i32, vp, sz, vp]),
+    'lp_calib_read': (i32, [vp, C.c_char_p, vp, vp, i32, vp]),
+    'lp_calib_end': (i32, [vp, C.POINTER(i64)]),
     'lp_tta_merge': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     'lp_tta_workspace_bytes': (sz, [i32, i32, i32, i32]),
     'lp_tta_merge_ex': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp,

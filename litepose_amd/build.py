@@ -37,6 +37,7 @@ SOURCES = [
     ('stem_kernels.hip', []),
     ('bf16_kernels.hip', []),
     ('convk_kernels.hip', []),
+    ('calib_kernels.hip', []),
     ('ae_kernels.hip', ['-ffp-contract=off'] + NOPK),
     ('ae_mid_kernels.hip', ['-ffp-contract=off'] + NOPK),
 ]

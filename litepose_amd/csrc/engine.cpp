@@ -160,6 +160,21 @@ struct lp_net {
     std::vector<BOp> bops;
     std::vector<char*> last_ptr_b;
     std::vector<char> last_stored_b;       // per buffer: written by the last forward (a fused block stores only its output)
+    // BatchNorm re-calibration (lp_calib_*): a shadow net of the same arch whose plan folds the identity instead of the
+    // BatchNorm (raw conv weights for the unfused launches), and the [gamma | beta | mean | var] rows of every BatchNorm
+    bool identity_fold = false;            // the shadow net: bn_fold gives scale 1, shift 0
+    struct CalibLayer { std::string bn; int C, div; size_t off; };
+    struct Calib {
+        lp_net* raw = nullptr;
+        std::vector<CalibLayer> layers;    // launch order
+        std::map<std::string, int> index;
+        std::vector<float> h_bn;
+        float* d_bn = nullptr;
+        double momentum = 0.1;
+        int64_t steps = 0;
+        bool uploaded = false;
+    };
+    Calib* calib = nullptr;
 };
 
 namespace {
@@ -187,6 +202,11 @@ void bn_fold(const lp_net* n, const std::string& p, std::vector<double>& scale,
     const Tensor &g = T(n, p + ".weight"), &b = T(n, p + ".bias");
     const Tensor &m = T(n, p + ".running_mean"), &v = T(n, p + ".running_var");
     const size_t c = g.data.size();
+    if (n->identity_fold) {                // calibration plan: the conv's own weights, BatchNorm applied by bn_apply_kernel
+        scale.assign(c, 1.0);
+        shift.assign(c, 0.0);
+        return;
+    }
     scale.resize(c);
     shift.resize(c);
     for (size_t i = 0; i < c; ++i) {
@@ -1300,8 +1320,17 @@ int lp_net_create(lp_net** out, const lp_arch* a) {
     return LP_OK;
 }
 
+static void calib_release(lp_net* n) {
+    if (!n->calib) return;
+    if (n->calib->d_bn) (void)hipFree(n->calib->d_bn);
+    lp_net_destroy(n->calib->raw);
+    delete n->calib;
+    n->calib = nullptr;
+}
+
 void lp_net_destroy(lp_net* n) {
     if (!n) return;
+    calib_release(n);
     if (n->d_weights) (void)hipFree(n->d_weights);
     for (auto e : n->events) (void)hipEventDestroy(e);
     for (int k = 0; k < lp_net::MAX_SIDE; ++k) {
@@ -1325,6 +1354,7 @@ const char* lp_net_key(const lp_net* n, int i, int64_t shape_out[4], int* ndim_o
 
 int lp_net_set_weight(lp_net* n, const char* key, const float* h, const int64_t* shape, int ndim) {
     if (!n || !key) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (n->calib) return fail(LP_ERR_INVALID_ARG, "a calibration is open on this handle: lp_calib_end() first");
     std::string k(key);
     // checkpoints saved from DataParallel / DDP carry a "module." prefix
     if (k.rfind("module.", 0) == 0) k = k.substr(7);
@@ -1993,6 +2023,209 @@ int lp_net_forward(lp_net* n, const float* d_x, int N, int H, int W, int flip, f
     return LP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// BatchNorm re-calibration of a supernet sub-network (calibrate_test.py:44-122; super_layers.py:19-28)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+// the BatchNorm(s) behind an op of the plan: first / second key ("" = none)
+void calib_bn_keys(const Op& o, std::string& k0, std::string& k1) {
+    k0.clear();
+    k1.clear();
+    switch (o.type) {
+        case OP_STEM: k0 = "first.0.1"; break;
+        case OP_DW:
+            if (o.name == "stem.dw3") k0 = "first.1.1";
+            else k0 = o.name.substr(0, o.name.rfind('.')) + ".conv.1";        // final_refined.I.dw5 -> final_refined.I.conv.1
+            break;
+        case OP_PW:
+            if (o.name == "stem.pw") k0 = "first.3";
+            else if (o.name.size() > 4 && o.name.compare(o.name.size() - 4, 4, ".inv") == 0) k0 = o.name + ".1";
+            break;                                                            // final.I.pw: no BatchNorm behind it
+        case OP_DWPW: k0 = o.tap + ".depth_conv.1"; k1 = o.tap + ".point_conv.1"; break;
+        case OP_DECONV: k0 = "deconv_bnrelu." + o.name.substr(7) + ".0"; break;
+        default: break;
+    }
+}
+
+size_t calib_part_bytes(const lp_net* n, int N, int H, int W) {
+    size_t d = 0;
+    for (const auto& L : n->calib->layers) d = std::max(d, lp::bn_partial_doubles(N, L.C, (H / L.div) * (W / L.div)));
+    return (d * sizeof(double) + 255) / 256 * 256;
+}
+
+}  // namespace
+
+int lp_calib_begin(lp_net* n, double momentum) {
+    if (!n) return fail(LP_ERR_INVALID_ARG, "null net");
+    if (n->arch.family != 0)
+        return fail(LP_ERR_UNSUPPORTED, "calibration: family 0 (pose_mobilenet / pose_simplenet) only");
+    if (n->storage != LP_STORAGE_F32) return fail(LP_ERR_UNSUPPORTED, "calibration: fp32 storage only");
+    if (!(momentum >= 0.0 && momentum <= 1.0)) return fail(LP_ERR_INVALID_ARG, "momentum must be in [0, 1]");
+    for (const auto& t : n->tensors)
+        if (!t.is_counter && !t.is_set) return fail(LP_ERR_MISSING_WEIGHT, "missing key in state_dict: " + t.key);
+    calib_release(n);
+    lp_net* raw = nullptr;
+    int rc = lp_net_create(&raw, &n->arch);
+    if (rc != LP_OK) return rc;
+    raw->tensors = n->tensors;
+    raw->identity_fold = true;
+    rc = build_plan(raw);
+    if (rc != LP_OK) { lp_net_destroy(raw); return rc; }
+    auto* c = new lp_net::Calib();
+    c->raw = raw;
+    c->momentum = momentum;
+    auto add = [&](const std::string& key, int C, int div) {
+        if (key.empty()) return;
+        lp_net::CalibLayer L{key, C, div, arena_push(c->h_bn, 4 * (size_t)C)};
+        const char* part[4] = {".weight", ".bias", ".running_mean", ".running_var"};
+        for (int q = 0; q < 4; ++q) {
+            const Tensor& t = T(n, key + part[q]);
+            std::copy(t.data.begin(), t.data.end(), c->h_bn.begin() + L.off + (size_t)q * C);
+        }
+        c->index[key] = (int)c->layers.size();
+        c->layers.push_back(L);
+    };
+    for (const Op& o : raw->ops) {
+        std::string k0, k1;
+        calib_bn_keys(o, k0, k1);
+        if (o.type == OP_DWPW) { add(k0, o.Ca, o.out_div); add(k1, o.Cout, o.out_div); }
+        else add(k0, o.type == OP_DW ? o.Ca : o.Cout, o.out_div);
+    }
+    n->calib = c;
+    return LP_OK;
+}
+
+size_t lp_calib_workspace_bytes(const lp_net* n, int N, int H, int W) {
+    if (!n || !n->calib) { fail(LP_ERR_NOT_FINALIZED, "lp_calib_begin() has not been called"); return 0; }
+    const lp_net* raw = n->calib->raw;
+    if (N < 1) { fail(LP_ERR_INVALID_ARG, "N must be positive"); return 0; }
+    if (check_size(raw, H, W) != LP_OK) return 0;               // lp_last_error names the multiple
+    size_t f = 0;
+    for (size_t b = 0; b < raw->bufs.ch.size(); ++b) f += buf_floats(raw, (int)b, N, H, W);
+    return calib_part_bytes(n, N, H, W) + f * sizeof(float) + 256;
+}
+
+int lp_calib_step(lp_net* n, const float* d_x, int N, int H, int W, void* ws, size_t ws_bytes, void* stream) {
+    if (!n || !d_x || !ws) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (!n->calib) return fail(LP_ERR_NOT_FINALIZED, "lp_calib_begin() has not been called");
+    lp_net::Calib* c = n->calib;
+    lp_net* raw = c->raw;
+    if (N < 1) return fail(LP_ERR_INVALID_ARG, "N must be positive");
+    if (const int rc = check_size(raw, H, W)) return rc;
+    {
+        const int m = size_multiple(raw);
+        if ((int64_t)N * (H / m) * (W / m) < 2)
+            return fail(LP_ERR_INVALID_ARG, "a batch statistic needs more than one value per channel on the deepest plane");
+    }
+    if (ws_bytes < lp_calib_workspace_bytes(n, N, H, W) || ((uintptr_t)ws & 255))
+        return fail(LP_ERR_WORKSPACE, "workspace too small or not 256-byte aligned");
+    (void)hipGetLastError();
+    if (!c->uploaded) {
+        if (!raw->d_weights) {
+            HIP_OK(hipMalloc((void**)&raw->d_weights, raw->h_packed.size() * sizeof(float)));
+            HIP_OK(hipMemcpy(raw->d_weights, raw->h_packed.data(), raw->h_packed.size() * sizeof(float),
+                             hipMemcpyHostToDevice));
+        }
+        if (!c->d_bn) HIP_OK(hipMalloc((void**)&c->d_bn, c->h_bn.size() * sizeof(float)));
+        HIP_OK(hipMemcpy(c->d_bn, c->h_bn.data(), c->h_bn.size() * sizeof(float), hipMemcpyHostToDevice));
+        c->uploaded = true;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double* part = (double*)ws;
+    std::vector<float*> ptr(raw->bufs.ch.size());
+    {
+        float* p = (float*)((char*)ws + calib_part_bytes(n, N, H, W));
+        for (size_t b = 0; b < ptr.size(); ++b) {
+            ptr[b] = p;
+            p += buf_floats(raw, (int)b, N, H, W);
+        }
+    }
+    const float* Wt = raw->d_weights;
+    lp::launch_notes = false;
+    auto bn = [&](const std::string& key, float* x, const float* res, int C, int HW, int act) {
+        const lp_net::CalibLayer& L = c->layers[c->index.at(key)];
+        lp::launch_bn_stats(x, part, N, C, HW, s);
+        lp::launch_bn_apply(x, res, part, c->d_bn + L.off, N, C, HW, act, c->momentum, 1e-5, s);
+    };
+    for (const Op& o : raw->ops) {
+        const int ih = H / o.in_div, iw = W / o.in_div, oh = H / o.out_div, ow = W / o.out_div;
+        std::string k0, k1;
+        calib_bn_keys(o, k0, k1);
+        switch (o.type) {
+            case OP_STEM:
+                lp::launch_stem_raw(d_x, Wt + o.w_off, ptr[o.out], N, H, W, s);
+                bn(k0, ptr[o.out], nullptr, 32, oh * ow, lp::ACT_RELU6);
+                break;
+            case OP_DW:
+                lp::launch_dw(ptr[o.inA], Wt + o.w_off, Wt + o.wdup_off, Wt + o.b_off, ptr[o.out], N, o.Ca, ih, iw, o.K,
+                              o.S, lp::ACT_NONE, s);
+                bn(k0, ptr[o.out], nullptr, o.Ca, oh * ow, o.act);
+                break;
+            case OP_PW:
+                if (k0.empty()) break;     // the heads' 1x1: behind the last BatchNorm, nothing to calibrate
+                lp::launch_pw(ptr[o.inA], o.Ca, nullptr, 0, Wt + o.w_off, Wt + o.b_off, nullptr, ptr[o.out], N, oh * ow,
+                              o.Cout, lp::ACT_NONE, s, o.ws_off ? Wt + o.ws_off : nullptr, n->opt_pw3d);
+                bn(k0, ptr[o.out], nullptr, o.Cout, oh * ow, o.act);
+                break;
+            case OP_DWPW:
+                lp::launch_dw(ptr[o.inA], Wt + o.w_off, Wt + o.wdup_off, Wt + o.b_off, ptr[o.mid], N, o.Ca, ih, iw, o.K,
+                              o.S, lp::ACT_NONE, s);
+                bn(k0, ptr[o.mid], nullptr, o.Ca, oh * ow, lp::ACT_RELU6);
+                lp::launch_pw(ptr[o.mid], o.Ca, nullptr, 0, Wt + o.w2_off, Wt + o.b2_off, nullptr, ptr[o.out], N, oh * ow,
+                              o.Cout, lp::ACT_NONE, s, o.ws_off ? Wt + o.ws_off : nullptr, n->opt_pw3d);
+                bn(k1, ptr[o.out], o.res >= 0 ? ptr[o.res] : nullptr, o.Cout, oh * ow, lp::ACT_NONE);
+                break;
+            case OP_DECONV:
+                lp::launch_deconv_raw(ptr[o.inA], o.Ca, o.inB >= 0 ? ptr[o.inB] : nullptr, o.Cb, Wt + o.w_off, ptr[o.out],
+                                      N, ih, iw, o.Cout, s);
+                bn(k0, ptr[o.out], nullptr, o.Cout, oh * ow, lp::ACT_RELU);
+                break;
+            default:
+                return fail(LP_ERR_UNSUPPORTED, "calibration: op not on the plan: " + o.name);
+        }
+    }
+    HIP_OK(hipGetLastError());
+    ++c->steps;
+    return LP_OK;
+}
+
+int lp_calib_read(const lp_net* n, const char* bn_prefix, float* d_mean, float* d_var, int channels, void* stream) {
+    if (!n || !bn_prefix || !d_mean || !d_var) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (!n->calib) return fail(LP_ERR_NOT_FINALIZED, "lp_calib_begin() has not been called");
+    const lp_net::Calib* c = n->calib;
+    auto it = c->index.find(bn_prefix);
+    if (it == c->index.end()) return fail(LP_ERR_UNKNOWN_KEY, std::string("no BatchNorm named ") + bn_prefix);
+    const lp_net::CalibLayer& L = c->layers[it->second];
+    if (channels != L.C) return fail(LP_ERR_SHAPE, std::string("channel count mismatch for ") + bn_prefix);
+    const float* src = c->uploaded ? c->d_bn + L.off : c->h_bn.data() + L.off;
+    const hipMemcpyKind kind = c->uploaded ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    HIP_OK(hipMemcpyAsync(d_mean, src + 2 * (size_t)L.C, L.C * sizeof(float), kind, (hipStream_t)stream));
+    HIP_OK(hipMemcpyAsync(d_var, src + 3 * (size_t)L.C, L.C * sizeof(float), kind, (hipStream_t)stream));
+    return LP_OK;
+}
+
+int lp_calib_end(lp_net* n, int64_t* steps_out) {
+    if (!n) return fail(LP_ERR_INVALID_ARG, "null net");
+    if (!n->calib) return fail(LP_ERR_NOT_FINALIZED, "lp_calib_begin() has not been called");
+    lp_net::Calib* c = n->calib;
+    const int64_t steps = c->steps;
+    if (c->uploaded) {
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipMemcpy(c->h_bn.data(), c->d_bn, c->h_bn.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (const auto& L : c->layers) {
+            Tensor& m = n->tensors[n->index.at(L.bn + ".running_mean")];
+            Tensor& v = n->tensors[n->index.at(L.bn + ".running_var")];
+            std::copy(c->h_bn.begin() + L.off + 2 * (size_t)L.C, c->h_bn.begin() + L.off + 3 * (size_t)L.C, m.data.begin());
+            std::copy(c->h_bn.begin() + L.off + 3 * (size_t)L.C, c->h_bn.begin() + L.off + 4 * (size_t)L.C, v.data.begin());
+        }
+    }
+    calib_release(n);
+    if (steps_out) *steps_out = steps;
+    if (steps > 0) return lp_net_finalize(n, 1);
+    return LP_OK;
+}
+
 int64_t lp_net_tap(const lp_net* n, const char* name, float* d_dst, void* stream) {
     if (!n || !name || n->last_ptr.empty()) return fail(LP_ERR_INVALID_ARG, "no forward has run");
     if (n->storage != LP_STORAGE_F32) {
@@ -2047,6 +2280,7 @@ int64_t lp_net_tap_offset(const lp_net* n, const char* name, int NB, int H, int 
 int lp_net_set_storage(lp_net* n, int storage) {
     if (!n || (storage != LP_STORAGE_F32 && storage != LP_STORAGE_BF16 && storage != LP_STORAGE_F16))
         return fail(LP_ERR_INVALID_ARG, "storage must be LP_STORAGE_F32, LP_STORAGE_BF16 or LP_STORAGE_F16");
+    if (n->calib) return fail(LP_ERR_INVALID_ARG, "a calibration is open on this handle: lp_calib_end() first");
     if (n->arch.family == 1 && storage != LP_STORAGE_F32)
         return fail(LP_ERR_UNSUPPORTED, "lp_net_set_storage: the pose_resnet family (lp_arch.family = 1) runs in fp32 storage "
                                         "only: its dense k x k convolutions have no 16-bit kernels yet");

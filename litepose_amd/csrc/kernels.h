@@ -167,6 +167,21 @@ bool launch_convk3(const float* inA, int Ca, const float* inB, int Cb, const voi
                    int N, int IH, int IW, int K, int S, int ups, int Cout, int act, int flip_from, int x_batch,
                    hipStream_t s);
 
+// ---- BatchNorm re-calibration (training-mode forward of a supernet sub-network, calib_kernels.hip) ----
+// raw forms of the two convolutions whose library kernels have their activation built in: the stem conv (w [32][27]) and
+// the pair of ConvTranspose2d(k4,s2,p1) (w [Ca+Cb][Cout][4][4]; inB = nullptr: one source), no bias, no activation
+void launch_stem_raw(const float* x, const float* w, float* out, int N, int H, int W, hipStream_t s);
+void launch_deconv_raw(const float* inA, int Ca, const float* inB, int Cb, const float* w, float* out, int N, int h,
+                       int w_, int Cout, hipStream_t s);
+// batch statistics of x [N,C,HW]: per-channel partial (sum, sum of squares) pairs in fp64 -> part
+// (bn_partial_doubles(N, C, HW) doubles, 16-byte aligned), one per workgroup, combined by launch_bn_apply in index order
+size_t bn_partial_doubles(int N, int C, int HW);
+void launch_bn_stats(const float* x, double* part, int N, int C, int HW, hipStream_t s);
+// in place: x = act((x - mean) * rsqrt(var + eps) * gamma + beta) (+ res) with the batch's mean / biased variance, and
+// running = (1 - momentum) * running + momentum * batch (unbiased variance).  bn = [gamma | beta | mean | var] x C (device)
+void launch_bn_apply(float* x, const float* res, const double* part, float* bn, int N, int C, int HW, int act,
+                     double momentum, double eps, hipStream_t s);
+
 // ---- network, 16-bit storage (octet-planar [N][C/8][HW][8] bf16 or fp16; bf16_kernels.hip, mbtile_bf16.hip) ----
 // Every launcher below takes the storage format last: f16 = false (default) runs the bf16 kernels, true their IEEE-half
 // forms (the same templates with a leading lp::F16 argument, fmt16.h): same shape rules, same refusals, same last_kernel_tag.

@@ -1,0 +1,60 @@
+"""Buffer contract of the writable lp_calib_* calls (include/litepose_amd.h) with poisoned and guarded buffers
+(tests/_poison.py): lp_calib_step writes nothing outside the first lp_calib_workspace_bytes of its workspace and does not
+touch its input; its results do not depend on what the workspace held; lp_calib_read writes exactly its two outputs."""
+import ctypes as C
+
+import pytest
+import torch
+
+import _poison as po
+import _supernet_ref as sr
+from litepose_amd import _native as nv
+
+pytestmark = pytest.mark.gpu
+
+
+def _net(arch):
+    from litepose_amd import config
+    from litepose_amd.models import pose_mobilenet
+    net = pose_mobilenet.get_pose_net(config.get_cfg('crowd_pose'), cfg_arch=arch, storage='f32')
+    net.load_state_dict(sr.sub_state_dict(sr.make_state_dict(sr.SEED), arch), strict=True)
+    return net
+
+
+@pytest.mark.parametrize('name,hw,n', [('half', (64, 64), 4), ('mixed', (96, 160), 3), ('half', (16, 32), 5)])
+def test_calib_step_and_read_respect_their_buffers(name, hw, n):
+    arch = dict(sr.golden_archs())[name]
+    H, W = hw
+    lib = nv.lib()
+    x = sr.step_images(H, W, 0, 0)[:1].repeat(n, 1, 1, 1).contiguous()
+    x = (x + 0.1 * torch.arange(n).view(n, 1, 1, 1)).cuda()
+    layers = sr.bn_layers(arch)
+    results = {}
+    for pattern in po.PATTERNS:
+        net = _net(arch)
+        nv.check(lib.lp_calib_begin(net._h, 0.1), 'lp_calib_begin')
+        need = int(lib.lp_calib_workspace_bytes(net._h, n, H, W))
+        assert need > 0
+        arena = po.Arena(pattern)
+        ws = arena.ws(need)
+        xin = arena.inp(x)
+        for _ in range(2):
+            nv.check(lib.lp_calib_step(net._h, nv.dptr(xin), n, H, W, nv.dptr(ws), need, nv.stream_ptr()), 'lp_calib_step')
+        got = []
+        for p, c in layers:
+            mean, var = arena.out((c,), what=p + ' mean', align=4), arena.out((c,), what=p + ' var', align=4)
+            nv.check(lib.lp_calib_read(net._h, p.encode(), nv.dptr(mean), nv.dptr(var), c, nv.stream_ptr()), 'lp_calib_read')
+            got += [mean, var]
+        arena.check()
+        steps = C.c_int64()
+        nv.check(lib.lp_calib_end(net._h, C.byref(steps)), 'lp_calib_end')
+        assert steps.value == 2
+        sd = net.state_dict()
+        for i, (p, c) in enumerate(layers):
+            assert torch.equal(got[2 * i].cpu(), sd[p + '.running_mean']) and torch.equal(got[2 * i + 1].cpu(), sd[p + '.running_var'])
+            assert bool(torch.isfinite(got[2 * i]).all()) and bool(torch.isfinite(got[2 * i + 1]).all()), p
+        results[pattern] = [t.cpu() for t in got]
+    for pattern in po.PATTERNS[1:]:
+        for a, b in zip(results['Z'], results[pattern]):
+            assert po.bitwise_equal(a, b), 'running pairs depend on what the workspace held (%s)' % pattern
+            assert not po.still_poisoned(b, a, pattern)

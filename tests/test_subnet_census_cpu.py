@@ -1,0 +1,109 @@
+"""The sub-network space of the supernet, re-enumerated, against the covering table of tests/_subnet_space.py: the counts
+of the space, every layer shape of it contained in some row, every row a vector ``random_sample()`` can return and an
+architecture ``oracle.spec.derive`` and the supernet's slicing accept.  No GPU."""
+import random
+
+import pytest
+
+import _subnet_space as sp
+from oracle import spec
+
+
+@pytest.fixture(scope='module')
+def space():
+    vecs = list(sp.archs())
+    keys = set()
+    for v in vecs:
+        keys |= sp.layer_keys(sp.arch_of(v))
+    return vecs, keys
+
+
+def _split(keys):
+    return {kind: {k for k in keys if k[0] == kind} for kind in ('block', 'deconv', 'head', 'stem')}
+
+
+def test_widths_and_counts_of_the_space(space):
+    vecs, keys = space
+    assert sp.widths() == [(8, 16, 24), (16, 32, 48, 64), (16, 24, 40, 48), (8, 16, 24, 32),
+                           (8, 16, 24, 32), (16, 32, 48, 64), (24, 48, 72, 96), (40, 80, 120, 160)]
+    assert len(vecs) == len(set(vecs)) == 49152
+    by = _split(keys)
+    assert len(keys) == 299
+    assert (len(by['block']), len(by['deconv']), len(by['head']), len(by['stem'])) == (76, 192, 28, 3)
+    # img_size changes no layer shape
+    v = vecs[12345]
+    assert sp.layer_keys(sp.arch_of(v, 256)) == sp.layer_keys(sp.arch_of(v, 512))
+
+
+def test_every_key_is_in_some_row(space):
+    _, keys = space
+    covered = {}
+    for row in sp.TRUNK + sp.DECONV:
+        for k in sp.layer_keys(sp.row_arch(row)):
+            covered.setdefault(k, []).append(row[0])
+    assert not keys - set(covered), sorted(keys - set(covered))[:8]
+    assert set(covered) <= keys
+    # the trunk rows alone hold every block, head and stem key (107), at the production sizes
+    trunk = set()
+    for row in sp.TRUNK:
+        trunk |= sp.layer_keys(sp.row_arch(row))
+        assert row[2] == row[3] and row[2] in sp.IMG_SIZES
+    by, by_t = _split(keys), _split(trunk)
+    assert len(sp.TRUNK) == 16 and len(sp.DECONV) == 48 and len(sp.SECOND) == 64 and len(sp.ROWS) == 128
+    assert len(by['block'] | by['head'] | by['stem']) == 107
+    for kind in ('block', 'head', 'stem'):
+        assert by_t[kind] == by[kind], (kind, sorted(by[kind] - by_t[kind]))
+    # every deconv triple is in exactly one row: 64 rows, 64 triples per deconv layer
+    assert all(len(ids) == 1 for k, ids in covered.items() if k[0] == 'deconv')
+    assert len({r[0] for r in sp.ROWS}) == len(sp.ROWS) and len({r[1] for r in sp.ROWS}) == 64
+    # the second-size rows: every vector once more, in the other size class
+    first = {r[1]: r for r in sp.TRUNK + sp.DECONV}
+    assert sorted(r[1] for r in sp.SECOND) == sorted(first)
+    for r in sp.SECOND:
+        assert (r[2] == 256) != (first[r[1]][2] in (160, 256)) and r[2] == r[3] and r[4:] == (1, 0), r
+
+
+def test_trunk_rows_meet_the_planes_they_must():
+    sizes = {}
+    for _, v, H, W, N, flip in sp.TRUNK:
+        sizes.setdefault(('s4', v[7]), set()).add(H // 16)
+        sizes.setdefault(('s1', v[4]), set()).add(W // 4)
+    w = sp.widths()
+    for c in w[7]:                       # the 16 x 16 deepest plane and one that is no multiple of the 16-pixel tile
+        assert 16 in sizes[('s4', c)] and sizes[('s4', c)] & {20, 24, 28}, (c, sizes[('s4', c)])
+    for c in w[4]:
+        assert 64 in sizes[('s1', c)] and sizes[('s1', c)] & {80, 112}, (c, sizes[('s1', c)])
+    assert {r[2] for r in sp.TRUNK} == set(sp.IMG_SIZES)
+    assert sum(1 for r in sp.TRUNK if (r[4], r[5]) == (3, 0)) >= 3
+    assert all((r[4], r[5]) in ((3, 0), (1, 2)) for r in sp.TRUNK)
+    assert all(r[4] == 1 and r[2] == r[3] and r[2] == 160 for r in sp.DECONV)
+
+
+def test_every_row_is_a_vector_random_sample_can_return_and_derive_accepts():
+    from litepose_amd.models import pose_supermobilenet as psm
+    import _supernet_ref as sr
+    w = sp.widths()
+    m = psm.get_pose_net(sp._cfg())
+    m.load_state_dict(sr.make_state_dict(sr.SEED), strict=True)
+    for row in list(sp.ROWS) + list(sp.GATE_ROWS):
+        v = row[1]
+        assert len(v) == len(w) and all(c in ws for c, ws in zip(v, w)), row[0]
+        arch = sp.row_arch(row)
+        assert sp.vector_of(arch) == tuple(v) and arch['img_size'] in sp.IMG_SIZES
+        d = spec.derive(arch)
+        assert len(d['deconv']) == 3 and len(d['heads']) == 2 and [len(s) for s in d['stages']] == [4, 6, 8, 8]
+        assert list(m.sub_state_dict(arch)) == list(spec.state_dict_shapes(arch))
+    # and what the sampler draws is of the same form as arch_of builds (vector -> arch -> vector round trip)
+    random.seed(7)
+    am = m.arch_manager
+    for _ in range(50):
+        a = am.random_sample()
+        assert sp.arch_of(sp.vector_of(a), a['img_size']) == a
+
+
+def test_draws_contain_only_keys_of_the_rows(space):
+    _, keys = space
+    random.seed(11)
+    am = sp._manager()
+    for _ in range(200):
+        assert sp.layer_keys(am.random_sample()) <= keys

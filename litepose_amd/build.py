@@ -29,6 +29,7 @@ OBJDIR = os.path.join(os.path.dirname(HERE), 'build', 'obj')
 NOPK = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 SOURCES = [
     ('engine.cpp', []),
+    ('plan.cpp', []),                      # host only: no HIP header (tests/plan_digest.cpp links it alone)
     ('ae_api.cpp', []),
     ('net_kernels.hip', []),
     ('mb16_kernels.hip', []),

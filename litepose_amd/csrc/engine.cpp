@@ -43,8 +43,8 @@ const char* storage_name(const Net* n) { return n->storage == LP_STORAGE_F16 ? "
 struct lp_net : lp_plan::Net {           // arch, tensors, storage and the plan: plan.h
     bool finalized = false;
     float* d_weights = nullptr;
-    // last forward (for taps)
-    std::vector<float*> last_ptr;
+    // last forward (for taps): every buffer's address; empty = no forward has run
+    std::vector<char*> last_buf;
     int lastN = 0, lastH = 0, lastW = 0;
     // profiling
     bool profiling = false;
@@ -77,8 +77,7 @@ struct lp_net : lp_plan::Net {           // arch, tensors, storage and the plan:
     int opt_diag_dwpw = 0;                 // diagnostics of DESIGN 5b (tools/flake_hunt.py --diag), never production
     struct OptEntryT { const char* key; int lo, hi; int lp_net::*field; };
     static const std::vector<OptEntryT>& options();
-    std::vector<char*> last_ptr_b;
-    std::vector<char> last_stored_b;       // per buffer: written by the last forward (a fused block stores only its output)
+    std::vector<char> last_stored;         // per buffer: written by the last forward (a fused block stores only its output)
     // BatchNorm re-calibration (lp_calib_*): a shadow net of the same arch whose plan folds the identity instead of the
     // BatchNorm (raw conv weights for the unfused launches), and the [gamma | beta | mean | var] rows of every BatchNorm
     struct CalibLayer { std::string bn; int C, div; size_t off; };
@@ -97,21 +96,18 @@ struct lp_net : lp_plan::Net {           // arch, tensors, storage and the plan:
 
 namespace {
 
-size_t buf_elems(const lp_net* n, int b, int N, int H, int W) {
+// elements of buffer b, rounded up to 256 bytes of `esz`-byte elements
+size_t buf_elems(const lp_net* n, int b, int N, int H, int W, size_t esz) {
     const int d = n->bufs.div[b];
-    const size_t f = (size_t)N * n->bufs.ch[b] * (H / d) * (W / d);
-    return (f + 127) / 128 * 128;
+    const size_t f = (size_t)N * n->bufs.ch[b] * (H / d) * (W / d), q = 256 / esz;
+    return (f + q - 1) / q * q;
 }
-
-size_t buf_floats(const lp_net* n, int b, int N, int H, int W) {
-    const int d = n->bufs.div[b];
-    size_t f = (size_t)N * n->bufs.ch[b] * (H / d) * (W / d);
-    return (f + 63) / 64 * 64;
-}
+size_t buf_floats(const lp_net* n, int b, int N, int H, int W) { return buf_elems(n, b, N, H, W, sizeof(float)); }
 
 // a buffer's share of the workspace: 16-bit elements under 16-bit storage
 size_t buf_bytes(const lp_net* n, int b, int N, int H, int W) {
-    return n->storage != LP_STORAGE_F32 ? buf_elems(n, b, N, H, W) * sizeof(uint16_t) : buf_floats(n, b, N, H, W) * sizeof(float);
+    const size_t esz = n->storage != LP_STORAGE_F32 ? sizeof(uint16_t) : sizeof(float);
+    return buf_elems(n, b, N, H, W, esz) * esz;
 }
 
 // Every plane of a forward is H / div x W / div of its buffer (buf_floats, rounded down), while a strided kernel derives
@@ -269,7 +265,7 @@ int lp_net_profile_launches(const lp_net* n, int32_t* grid_wgs, int32_t* wg_thre
 
 namespace {
 
-// ---- what lp_net_forward and forward_bf16 share: workspace layout, profiling events, the K-stream fan-out ----
+// ---- lp_net_forward: workspace layout, profiling events, the K-stream fan-out, the fusion rules, the op loop ----
 
 // one block of the workspace per buffer, in id order; the two outputs are the caller's fp32 tensors.  esz: bytes per element
 void layout_buffers(const lp_net* n, void* ws, int NB, int H, int W, float* d_out0, float* d_out1, std::vector<char*>& ptr,
@@ -301,11 +297,11 @@ int prof_begin(lp_net* n, size_t nops, hipStream_t s) {
     HIP_OK(hipEventRecord(n->events[0], s));
     return LP_OK;
 }
-int prof_mark(lp_net* n, hipStream_t s, const std::string& name, int64_t by, int64_t fl, int64_t fl_valu) {
+int prof_mark(lp_net* n, hipStream_t s, const std::string& name, const Cost& c) {
     if (!n->profiling) return LP_OK;
     hipError_t e = hipEventRecord(n->events[n->prof_ev + 1], s);
     if (e != hipSuccess) return fail(LP_ERR_HIP, hipGetErrorString(e));
-    n->prof_entries.push_back({name, lp::last_kernel_tag, by, fl, n->prof_ev, n->prof_ev + 1, fl_valu, lp::last_launch});
+    n->prof_entries.push_back({name, lp::last_kernel_tag, c.bytes, c.flops, n->prof_ev, n->prof_ev + 1, c.flops_valu, lp::last_launch});
     ++n->prof_ev;
     return LP_OK;
 }
@@ -347,169 +343,369 @@ int fan_out(lp_net* n, const float* d_x, int N, int H, int W, int flip, hipStrea
     return LP_OK;
 }
 
-// lp_net_forward for LP_STORAGE_BF16 / LP_STORAGE_F16: same launch order, stream fan-out and profiling contract as the fp32 path
-int forward_bf16(lp_net* n, const float* d_x, int N, int H, int W, int flip, float* d_out0, float* d_out1, void* ws,
-                 size_t ws_bytes, hipStream_t s) {
-    const int NB = flip == 2 ? 2 * N : N;
-    if (ws_bytes < lp_net_workspace_bytes(n, NB, H, W) || ((uintptr_t)ws & 255))
-        return fail(LP_ERR_WORKSPACE, "workspace too small or not 256-byte aligned");
-    const bool f16 = n->storage == LP_STORAGE_F16;      // every launch below takes the format last
-    std::vector<char*> ptr;
-    std::vector<int> esz;
-    layout_buffers(n, ws, NB, H, W, d_out0, d_out1, ptr, esz);
-    const float* Wt = n->d_weights;
-    if (const int rc = prof_begin(n, n->bops.size(), s)) return rc;
-    std::vector<char> stored(ptr.size(), 0);
-    auto run = [&](int NBp, const std::vector<char*>& ptr, hipStream_t s, const float* xsrc, int flip_from,
-                   int x_batch) -> int {
-        auto mark = [&](const std::string& name, int64_t by, int64_t fl, int64_t fl_valu) {
-            return prof_mark(n, s, name, by, fl, fl_valu);
-        };
-        for (size_t bi = 0; bi < n->bops.size(); ++bi) {
-            const BOp& o = n->bops[bi];
-            const int ih = H / o.in_div, iw = W / o.in_div, oh = H / o.out_div, ow = W / o.out_div;
-            int64_t by = 0, fl = 0;
-            bool ok = true;
-            // the whole 7x7 block in one launch (mbtb_kernel / mbtb_s2_kernel, round 3): expand / depthwise / project,
-            // the two expanded tensors never stored.  Option "mbtb" = 0 keeps the chain below
-            if (o.type == OP_PW && o.inB < 0 && !o.out_f32 && o.act == lp::ACT_RELU6 && bi + 2 < n->bops.size()) {
-                const BOp& dw = n->bops[bi + 1];
-                const BOp& pw = n->bops[bi + 2];
-                if (dw.type == OP_DW && dw.inA == o.out && dw.K == 7 && (dw.S == 1 || dw.S == 2) && dw.wrow_off &&
-                    dw.act == lp::ACT_RELU6 && pw.type == OP_PW && pw.inA == dw.out && pw.inB < 0 && !pw.out_f32 &&
-                    pw.act == lp::ACT_NONE && (pw.res < 0 || pw.res == o.inA) &&
-                    lp::launch_mbtb(ptr[o.inA], Wt + o.w_off, Wt + o.b_off, Wt + dw.wrow_off, Wt + pw.w_off,
-                                    Wt + pw.b_off, pw.res >= 0 ? ptr[pw.res] : nullptr, ptr[pw.out], NBp, o.Ca, o.Cout,
-                                    pw.Cout, ih, iw, dw.K, dw.S, s, n->opt_mbtb, n->opt_mbtb_s2, n->opt_mbtq,
-                                    dw.wrow2_off ? Wt + dw.wrow2_off : nullptr, n->opt_mbtd, f16)) {
-                    const int64_t ipx = (int64_t)ih * iw, opx = ipx / (dw.S * dw.S);
-                    if (const int rc = mark(o.name + "+dw+point_conv",     // short: lp_net_profile names are 47 chars
-                                            2ll * NBp * (ipx * o.Ca + opx * pw.Cout * (pw.res >= 0 ? 2ll : 1ll)),
-                                            2ll * NBp * (ipx * o.Ca * o.Cout + opx * ((int64_t)o.Cout * 49 + (int64_t)o.Cout * pw.Cout)),
-                                            2ll * NBp * opx * (int64_t)o.Cout * 49))
-                        return rc;
-                    stored[pw.out] = 1;
-                    bi += 2;                                    // the depthwise and the project ran inside the launch
-                    continue;
-                }
-            }
-            // the whole stem in one launch (stem4_kernel<C0, true>, round 6; option "stem" = 0: the three launches below, what
-            // the per-launch parity tests run)
-            if (o.type == OP_STEM && n->opt_stem && o.st_w0 && bi + 2 < n->bops.size()) {
-                const BOp& dw = n->bops[bi + 1];
-                const BOp& pw = n->bops[bi + 2];
-                if (dw.type == OP_DW && dw.K == 3 && dw.S == 1 && pw.type == OP_PW && pw.inA == dw.out && !pw.out_f32 &&
-                    lp::launch_stem3b(xsrc, Wt + o.st_w0, Wt + o.b_off, Wt + o.st_w1, Wt + o.st_b1, Wt + o.st_w2,
-                                      Wt + o.st_b2, ptr[pw.out], NBp, H, W, pw.Cout, flip_from, x_batch, s, f16)) {
-                    const int64_t opx = (int64_t)oh * ow;
-                    if (const int rc = mark("stem.conv3x3s2+dw3+pw",
-                                            (int64_t)NBp * (12ll * H * W + 64ll * opx) + (int64_t)NBp * 2 * 64ll * opx +
-                                                (int64_t)NBp * (64ll + 2ll * pw.Cout) * opx,
-                                            2ll * NBp * opx * (32ll * 27 + 32ll * 9 + 32ll * pw.Cout),
-                                            2ll * NBp * opx * (32ll * 27 + 32ll * 9)))
-                        return rc;
-                    stored[pw.out] = 1;
-                    bi += 2;
-                    continue;
-                }
-            }
-            // an output head in one launch (headb_kernel, round 6: both 5x5 depthwise convs + the dual-source 1x1; option
-            // "headb" = 0: the three launches below, what the per-launch parity tests run).  Needs the matrix-core depthwise
-            // (option "dwt" >= 2): its results are the SAME bits as dwt_kernel<5>'s
-            if (o.type == OP_DW && o.K == 5 && o.S == 1 && n->opt_headb && n->opt_dwt >= 2 && o.wt_off &&
-                bi + 2 < n->bops.size()) {
-                const BOp& d2 = n->bops[bi + 1];
-                const BOp& pw = n->bops[bi + 2];
-                if (d2.type == OP_DW && d2.K == 5 && d2.S == 1 && d2.wt_off && o.act == lp::ACT_RELU &&
-                    d2.act == lp::ACT_RELU && pw.type == OP_PW && pw.out_f32 && pw.inA == o.out && pw.inB == d2.out &&
-                    pw.act == lp::ACT_NONE && pw.res < 0 &&
-                    lp::launch_headb(ptr[o.inA], o.Ca, ptr[d2.inA], d2.Ca, Wt + o.wt_off, Wt + o.w_off, Wt + d2.wt_off,
-                                     Wt + d2.w_off, Wt + pw.w_off, reinterpret_cast<float*>(ptr[pw.out]), NBp, ih, iw, o.K,
-                                     pw.Cout, s, f16)) {
-                    const int64_t px = (int64_t)NBp * oh * ow, C = o.Ca + d2.Ca;
-                    if (const int rc = mark("final." + pw.name.substr(6, pw.name.find('.', 6) - 6) + ".dw5+dw5+pw",
-                                            2ll * px * 2 * C + px * (2ll * C + 4ll * pw.Cout),
-                                            2ll * px * (C * 25 + C * (int64_t)pw.Cout), 2ll * px * C * 25))
-                        return rc;
-                    stored[pw.out] = 1;
-                    bi += 2;
-                    continue;
-                }
-            }
-            // the one-source head of a plain_head net (dw5 + the 1x1) in one launch: headb_kernel's one-source form, the SAME bits
-            // as dwt_kernel<5> + pwb_kernel
-            if (o.type == OP_DW && o.K == 5 && o.S == 1 && n->opt_headb && n->opt_dwt >= 2 && o.wt_off && o.act == lp::ACT_RELU &&
-                bi + 1 < n->bops.size()) {
-                const BOp& pw = n->bops[bi + 1];
-                if (pw.type == OP_PW && pw.out_f32 && pw.inA == o.out && pw.inB < 0 && pw.act == lp::ACT_NONE && pw.res < 0 &&
-                    lp::launch_headb(ptr[o.inA], o.Ca, nullptr, 0, Wt + o.wt_off, Wt + o.w_off, nullptr, nullptr,
-                                     Wt + pw.w_off, reinterpret_cast<float*>(ptr[pw.out]), NBp, ih, iw, o.K, pw.Cout, s, f16)) {
-                    const int64_t px = (int64_t)NBp * oh * ow, C = o.Ca;
-                    if (const int rc = mark("final." + pw.name.substr(6, pw.name.find('.', 6) - 6) + ".dw5+pw",
-                                            2ll * px * 2 * C + px * (2ll * C + 4ll * pw.Cout),
-                                            2ll * px * (C * 25 + C * (int64_t)pw.Cout), 2ll * px * C * 25))
-                        return rc;
-                    stored[pw.out] = 1;
-                    ++bi;
-                    continue;
-                }
-            }
-            switch (o.type) {
-                case OP_STEM:
-                    lp::launch_stemb(xsrc, Wt + o.w_off, Wt + o.b_off, ptr[o.out], NBp, H, W, flip_from, x_batch, s, f16);
-                    by = (int64_t)NBp * (12ll * H * W + 64ll * oh * ow);
-                    fl = 2ll * NBp * 32 * 27 * oh * ow;
-                    break;
-                case OP_DW:
-                    {
-                        // the stride-1 7x7 / 5x5 depthwise runs as banded matrix products on the matrix cores
-                        // (dwt_kernel) wherever its shape rule admits the plane: default since round 3 (S@448 b32:
-                        // 5.60 -> 4.82 ms/step, every launch within 1 bf16 ulp of the emulation like dwb_kernel).
-                        // Option "dwt" (the tests compare the forms in one process): 0 = dwb_kernel everywhere,
-                        // 1 = 7x7 only, 2 (default) = 7x7 and the heads' 5x5
-                        const int dwt = n->opt_dwt;
-                        ok = dwt && o.wt_off && o.S == 1 && (o.K == 7 || (o.K == 5 && dwt >= 2)) &&
-                             lp::launch_dwt(ptr[o.inA], Wt + o.wt_off, Wt + o.w_off, ptr[o.out], NBp, o.Ca, ih, iw,
-                                            o.K, o.act, s, f16);
-                        if (!ok)
-                            ok = lp::launch_dwb(ptr[o.inA], Wt + o.w_off, ptr[o.out], NBp, o.Ca, ih, iw, o.K, o.S,
-                                                o.act, s, f16);
-                    }
-                    by = 2ll * NBp * o.Ca * ((int64_t)ih * iw + (int64_t)oh * ow);
-                    fl = 2ll * NBp * o.Ca * o.K * o.K * oh * ow;
-                    break;
-                case OP_PW:
-                    ok = lp::launch_pwb(ptr[o.inA], o.Ca, o.inB >= 0 ? ptr[o.inB] : nullptr, o.Cb, Wt + o.w_off,
-                                        Wt + o.b_off, o.res >= 0 ? ptr[o.res] : nullptr, ptr[o.out], NBp, oh * ow,
-                                        o.Cout, o.act, o.out_f32, s, f16);
-                    by = (int64_t)NBp * oh * ow *
-                         (2ll * (o.Ca + o.Cb) + (o.out_f32 ? 4ll : 2ll) * o.Cout + (o.res >= 0 ? 2ll * o.Cout : 0));
-                    fl = 2ll * NBp * oh * ow * (int64_t)(o.Ca + o.Cb) * o.Cout;
-                    break;
-                case OP_DECONV:
-                    ok = lp::launch_deconvb(ptr[o.inA], o.Ca, o.inB >= 0 ? ptr[o.inB] : nullptr, o.Cb, Wt + o.w_off, Wt + o.b_off, ptr[o.out],
-                                            NBp, ih, iw, o.Cout, s, f16);
-                    by = 2ll * NBp * ((int64_t)(o.Ca + o.Cb) * ih * iw + (int64_t)o.Cout * oh * ow);
-                    fl = 2ll * NBp * (int64_t)(o.Ca + o.Cb) * o.Cout * 4 * oh * ow;
-                    break;
-                default:                     // OP_DWPW / OP_CONVK: not on a 16-bit plan
-                    ok = false;
-                    break;
-            }
-            if (!ok) return fail(LP_ERR_UNSUPPORTED, std::string(storage_name(n)) + " storage: unsupported layer shape at " + o.name);
-            stored[o.out] = 1;
-            if (const int rc = mark(o.name, by, fl, (o.type == OP_STEM || o.type == OP_DW) ? fl : 0)) return rc;
+// What one part of a forward (fan_out's run) hands its fusion rules and its one-launch-per-op switch
+struct Part {
+    lp_net* n;
+    const std::vector<char*>& buf;     // this part's share of every buffer
+    hipStream_t s;
+    const float* x;                    // its images, and which of them the stem mirrors
+    int NB, H, W, flip_from, x_batch;
+    const float* Wt;
+    bool f32, f16;                     // storage; f16: the format flag every 16-bit launcher takes last
+    float* f(int b) const { return reinterpret_cast<float*>(buf[b]); }      // fp32 storage
+    const OpBase& op(size_t i) const { return f32 ? static_cast<const OpBase&>(n->ops[i]) : n->bops[i]; }
+    Cost cost(size_t i, CostPart part = COST_OP) const {       // of reference op i (plan.h)
+        return f32 ? op_cost(n->ops[i], 4, false, NB, H, W, part) : op_cost(n->bops[i], 2, n->bops[i].out_f32, NB, H, W);
+    }
+    int mark(const std::string& name, const Cost& k) const { return prof_mark(n, s, name, k); }
+};
+struct Planes { int ih, iw, oh, ow; };
+Planes planes(const Part& c, const OpBase& o) { return {c.H / o.in_div, c.W / o.in_div, c.H / o.out_div, c.W / o.out_div}; }
+
+// A fusion rule looks at the ops from index i on and either launches ONE kernel for the first `used` of them and returns
+// `used`, or launches nothing and returns 0.  name: the entry's name from the first two and the last op consumed (called
+// for a profiled forward only); bytes: the entry's own definition of its bytes (null: the sum over its ops, like its FLOPs)
+struct Rule {
+    int (*launch)(const Part&, size_t i);
+    std::string (*name)(const OpBase& first, const OpBase& second, const OpBase& last);
+    int64_t (*bytes)(const Part&, size_t i);
+};
+
+// "stage.2.1.inv", "stage.2.1.depth_conv+point_conv" -> "stage.2.1.inv+depth_conv+point_conv"; a run of blocks that ends
+// with "stage.2.9.depth_conv+point_conv" -> "stage.2.1-9.inv+depth_conv+point_conv"
+std::string block_name(const OpBase& o, const OpBase& d, const OpBase& last) {
+    const std::string nm = o.name + "+" + d.name.substr(d.name.rfind('.', d.name.find('+')) + 1);
+    if (&last == &d) return nm;
+    const std::string pfx = o.name.substr(0, o.name.rfind('.'));                              // stage.2.1
+    const std::string lpf = last.name.substr(0, last.name.rfind('.', last.name.find('+')));   // stage.2.9
+    return pfx + "-" + lpf.substr(lpf.rfind('.') + 1) + nm.substr(pfx.size());
+}
+// "stage.0.1.inv" -> "stage.0.1.inv+dw+point_conv": short, lp_net_profile names hold 47 characters with the kernel tag
+std::string blockb_name(const OpBase& o, const OpBase&, const OpBase&) { return o.name + "+dw+point_conv"; }
+std::string stem_name(const OpBase&, const OpBase&, const OpBase&) { return "stem.conv3x3s2+dw3+pw"; }
+std::string dwpw3_name(const OpBase& dw, const OpBase&, const OpBase&) { return dw.name + "+pw"; }    // "stem.dw3+pw"
+// the head's 1x1 "final.0.pw" -> "final.0.dw5+dw5+pw"; one source (the 1x1 is the second op) -> "final.0.dw5+pw"
+std::string headb_name(const OpBase&, const OpBase& second, const OpBase& pw) {
+    return "final." + pw.name.substr(6, pw.name.find('.', 6) - 6) + (&second == &pw ? ".dw5+pw" : ".dw5+dw5+pw");
+}
+// fp32: two depthwise convs that are not a Fusion Deconv Head's keep the 1x1's own name
+std::string head_name(const OpBase& dw, const OpBase& second, const OpBase& pw) {
+    if (&second != &pw && dw.name.substr(0, dw.name.find('.')) != "final_refined") return pw.name;
+    return headb_name(dw, second, pw);
+}
+// the halves of "stage.0.1.depth_conv+point_conv": "stage.0.1.depth_conv", "stage.0.1.point_conv"
+std::string half_name(const OpBase& d, CostPart part) {
+    if (part == COST_DW_HALF) return d.name.substr(0, d.name.find('+'));
+    return d.name.substr(0, d.name.rfind('.', d.name.find('+'))) + ".point_conv";
+}
+
+// ---- fp32 storage: the rules in the order they are tried, then one launch per op ----
+
+// an expand 1x1 and the depthwise + project behind it: a whole InvBottleneck
+bool is_block(const std::vector<Op>& ops, size_t i) {
+    return ops[i].type == OP_PW && ops[i].fuse_next && i + 1 < ops.size() && ops[i + 1].type == OP_DWPW;
+}
+
+// 16x16 planes (mb16_kernel): the whole RUN of same-shape residual blocks that follows in one launch -- a block's output
+// is the next block's input in the kernel's own register layout (mb16_kernels.hip)
+int rule_mb16(const Part& c, size_t i) {
+    const lp_net* n = c.n;
+    if (!is_block(n->ops, i)) return 0;
+    const Op &o = n->ops[i], &d = n->ops[i + 1];
+    const Planes pl = planes(c, o);
+    if (!(n->opt_mb16 && c.NB >= n->opt_mb16_min && o.ws_off && d.ws_off && d.wrow_off &&
+          lp::mb16_supported(o.Ca, o.Cout, d.Cout, pl.ih, pl.iw, d.K, d.S, d.res >= 0)))
+        return 0;
+    const float* Wt = c.Wt;
+    lp::Mb16Run r;
+    memset(&r, 0, sizeof(r));
+    for (size_t k = i; k + 1 < n->ops.size() && r.nblocks < lp::MB16_MAX_RUN; k += 2) {
+        const Op &e = n->ops[k], &p = n->ops[k + 1];
+        if (e.type != OP_PW || !e.fuse_next || p.type != OP_DWPW || !e.ws_off || !p.ws_off || !p.wrow_off) break;
+        if (k > i) {        // a follower: same shape, residual on its own input, fed by the previous block
+            if (d.res < 0 || p.res != e.inA || e.inA != n->ops[k - 1].out || e.Ca != o.Ca ||
+                e.Cout != o.Cout || p.Cout != d.Cout || p.K != d.K || p.S != d.S ||
+                e.in_div != o.in_div || p.out_div != d.out_div || !n->opt_mb16_run)
+                break;
+        } else if (d.res >= 0 && d.res != o.inA) break;
+        const int b = r.nblocks++;
+        r.w1s[b] = Wt + e.ws_off; r.b1f[b] = Wt + e.b_off; r.wrow[b] = Wt + p.wrow_off;
+        r.w2s[b] = Wt + p.ws_off; r.b2f[b] = Wt + p.b2_off; r.out[b] = c.f(p.out);
+        if (d.res < 0) break;                          // a block that changes the channel count runs alone
+    }
+    if (r.nblocks < 1 || !lp::launch_mb16(c.f(o.inA), r, d.res >= 0, c.NB, o.Ca, o.Cout, d.Cout, pl.ih, pl.iw, d.K, d.S, c.s))
+        return 0;
+    return 2 * r.nblocks;
+}
+
+// a whole InvBottleneck in one launch when the shape allows it: the tiled kernels, then mbconv_kernel / mbconv2_kernel
+int rule_mbt(const Part& c, size_t i) {
+    const lp_net* n = c.n;
+    if (!is_block(n->ops, i)) return 0;
+    const Op &o = n->ops[i], &d = n->ops[i + 1];
+    const Planes pl = planes(c, o);
+    const float *Wt = c.Wt, *res = d.res >= 0 ? c.f(d.res) : nullptr;
+    return ((o.ws_off && d.ws_off && d.wrow_off &&
+             lp::launch_mbt(c.f(o.inA), Wt + o.ws_off, Wt + o.b_off, Wt + d.wrow_off, Wt + d.ws_off, Wt + d.b2_off, res,
+                            c.f(d.out), c.NB, o.Ca, o.Cout, d.Cout, pl.ih, pl.iw, d.K, d.S, c.s, n->opt_mbt, n->opt_mbt_s2)) ||
+            lp::launch_mbconv(c.f(o.inA), Wt + o.w_off, Wt + o.b_off, Wt + d.w_off, Wt + d.b_off, Wt + d.w2_off,
+                              Wt + d.b2_off, res, c.f(d.out), c.NB, o.Ca, o.Cout, d.Cout, pl.ih, pl.iw, d.K, d.S, c.s,
+                              d.wpair_off ? Wt + d.wpair_off : nullptr, o.ws_off ? Wt + o.ws_off : nullptr,
+                              d.wrow_off ? Wt + d.wrow_off : nullptr, n->opt_mbconv2)) ? 2 : 0;
+}
+
+// the whole stem in one launch (stem4_kernel; option "stem" = 0: stem_kernel, then rule_dwpw3)
+int rule_stem3(const Part& c, size_t i) {
+    const lp_net* n = c.n;
+    const Op& o = n->ops[i];
+    if (!(n->opt_stem && o.type == OP_STEM && i + 2 < n->ops.size() && n->ops[i + 1].type == OP_DW &&
+          n->ops[i + 2].type == OP_PW && o.st_w0))
+        return 0;
+    const Op &dw = n->ops[i + 1], &pw = n->ops[i + 2];
+    const float* Wt = c.Wt;
+    return lp::launch_stem3(c.x, Wt + o.st_w0, Wt + o.b_off, Wt + o.st_w1, Wt + dw.b_off, Wt + o.st_w2, Wt + o.st_b2,
+                            c.f(pw.out), c.NB, c.H, c.W, pw.Cout, c.flip_from, c.x_batch, c.s) ? 3 : 0;
+}
+
+// stem: dw3 + 1x1 in one launch (dwpw_kernel<3>): the 32-channel dw3 output stays in LDS
+int rule_dwpw3(const Part& c, size_t i) {
+    const lp_net* n = c.n;
+    const Op& o = n->ops[i];
+    if (!(o.type == OP_DW && o.K == 3 && o.S == 1 && o.act == lp::ACT_RELU6 && i + 1 < n->ops.size())) return 0;
+    const Op& pw = n->ops[i + 1];
+    if (!(pw.type == OP_PW && pw.inA == o.out && pw.inB < 0 && pw.res < 0 && pw.act == lp::ACT_NONE && pw.has_bias)) return 0;
+    const Planes pl = planes(c, o);
+    const float* Wt = c.Wt;
+    return lp::launch_dwpw(c.f(o.inA), Wt + o.w_off, Wt + o.b_off, Wt + pw.w_off, Wt + pw.b_off, nullptr, c.f(pw.out), c.NB,
+                           o.Ca, pl.ih, pl.iw, o.K, o.S, pw.Cout, c.s, n->opt_diag_dwpw) ? 2 : 0;
+}
+
+// an output head in one launch (headfuse_kernel), bit-identical to its chain: the 5x5 depthwise and the 1x1 of a plain
+// head, or both depthwise convs and the two-source 1x1 (option "headfuse" = 0: the chain)
+int rule_head(const Part& c, size_t i) {
+    const lp_net* n = c.n;
+    const std::vector<Op>& ops = n->ops;
+    const Op& o = ops[i];
+    if (!(n->opt_headfuse && o.type == OP_DW && o.S == 1 && o.act == lp::ACT_RELU && i + 1 < ops.size())) return 0;
+    const Op& a = ops[i + 1];
+    const Op *d2 = nullptr, *pw = nullptr;      // the second depthwise (null: one source), the 1x1
+    if (o.K == 5 && a.type == OP_PW && a.inA == o.out && a.inB < 0 && a.res < 0 && a.act == lp::ACT_NONE &&
+        (a.out == n->out0_buf || a.out == n->out1_buf))
+        pw = &a;
+    else if (i + 2 < ops.size() && a.type == OP_DW && ops[i + 2].type == OP_PW && ops[i + 2].inA == o.out &&
+             ops[i + 2].inB == a.out && a.S == 1 && o.K == a.K && a.act == lp::ACT_RELU)
+        d2 = &a, pw = &ops[i + 2];
+    else
+        return 0;
+    const Planes pl = planes(c, o);
+    const float* Wt = c.Wt;
+    if (!lp::launch_headfuse(c.f(o.inA), o.Ca, d2 ? c.f(d2->inA) : nullptr, d2 ? d2->Ca : 0,
+                             o.wpair_off ? Wt + o.wpair_off : nullptr, d2 && d2->wpair_off ? Wt + d2->wpair_off : nullptr,
+                             Wt + pw->w_off, c.f(pw->out), c.NB, pl.oh, pl.ow, o.K, pw->Cout, c.s))
+        return 0;
+    return d2 ? 3 : 2;
+}
+
+const Rule F32_RULES[] = {{rule_mb16, block_name, nullptr}, {rule_mbt, block_name, nullptr}, {rule_stem3, stem_name, nullptr},
+                          {rule_dwpw3, dwpw3_name, nullptr}, {rule_head, head_name, nullptr}};
+
+// op i in a launch of its own (an OP_DWPW that dwpw_kernel refuses: in two), with its entry or entries
+int launch_op_f32(const Part& c, size_t i) {
+    const lp_net* n = c.n;
+    const Op& o = n->ops[i];
+    const Planes pl = planes(c, o);
+    const int ih = pl.ih, iw = pl.iw, oh = pl.oh, ow = pl.ow, NB = c.NB;
+    const float* Wt = c.Wt;
+    hipStream_t s = c.s;
+    switch (o.type) {
+        case OP_STEM:
+            lp::launch_stem(c.x, Wt + o.w_off, Wt + o.b_off, c.f(o.out), NB, c.H, c.W, c.flip_from, c.x_batch, s);
+            break;
+        case OP_DW:
+            lp::launch_dw(c.f(o.inA), Wt + o.w_off, Wt + o.wdup_off, Wt + o.b_off, c.f(o.out), NB, o.Ca, ih, iw, o.K, o.S,
+                          o.act, s);
+            break;
+        case OP_PW:
+            lp::launch_pw(c.f(o.inA), o.Ca, o.inB >= 0 ? c.f(o.inB) : nullptr, o.Cb, Wt + o.w_off,
+                          o.has_bias ? Wt + o.b_off : nullptr, o.res >= 0 ? c.f(o.res) : nullptr, c.f(o.out), NB, oh * ow,
+                          o.Cout, o.act, s, o.ws_off ? Wt + o.ws_off : nullptr, n->opt_pw3d);
+            break;
+        case OP_DECONV: {
+            float* inB = o.inB >= 0 ? c.f(o.inB) : nullptr;   // nullptr: the one-source form (plain head)
+            if (o.w3_off && deconv4_enabled() && o.w4_off &&
+                lp::launch_deconv4x3(c.f(o.inA), o.Ca, inB, o.Cb, Wt + o.w4_off, Wt + o.b3_off, c.f(o.out), NB, ih, iw,
+                                     o.Cout, s)) {
+            } else if (o.w3_off && deconv4_enabled())
+                lp::launch_deconv4(c.f(o.inA), o.Ca, inB, o.Cb, Wt + o.w3_off, Wt + o.b3_off, c.f(o.out), NB, ih, iw, o.Cout, s);
+            else if (o.mid == 1)
+                lp::launch_deconv_mfma(c.f(o.inA), o.Ca, inB, o.Cb, Wt + o.w2_off, Wt + o.b2_off, c.f(o.out), NB, ih, iw,
+                                       o.Cout, s);
+            else
+                lp::launch_deconv_pair(c.f(o.inA), o.Ca, inB, o.Cb, Wt + o.w_off, Wt + o.b_off, c.f(o.out), NB, ih, iw,
+                                       o.Cout, s);
+            break;
         }
-        return LP_OK;
-    };
-    if (const int rc = fan_out(n, d_x, N, H, W, flip, s, ptr, esz, run)) return rc;
-    HIP_OK(hipGetLastError());
-    n->last_ptr_b = ptr;
-    n->last_stored_b = stored;
-    n->last_ptr.assign(1, nullptr);          // "a forward has run"
-    n->lastN = NB;
-    n->lastH = H;
-    n->lastW = W;
+        case OP_CONVK:
+            // dense k x k conv (+ upsample / second source); `oh, ow` already include the stride / the x2
+            if (!lp::launch_convk3(o.image_in ? c.x : c.f(o.inA), o.Ca, o.inB >= 0 ? c.f(o.inB) : nullptr, o.Cb,
+                                   Wt + o.wk_off, Wt + o.b_off, c.f(o.out), NB, ih, iw, o.K, o.S, o.ups, o.Cout, o.act,
+                                   o.image_in ? c.flip_from : NB, o.image_in ? c.x_batch : NB, s))
+                return fail(LP_ERR_UNSUPPORTED, "convk3: shape not supported: " + o.name);
+            break;
+        case OP_DWPW:
+            if (lp::launch_dwpw(c.f(o.inA), Wt + o.w_off, Wt + o.b_off, Wt + o.w2_off, Wt + o.b2_off,
+                                o.res >= 0 ? c.f(o.res) : nullptr, c.f(o.out), NB, o.Ca, ih, iw, o.K, o.S, o.Cout, s))
+                break;
+            // unfused: the depthwise into o.mid, then the 1x1 -- two entries under the halves' own names
+            lp::launch_dw(c.f(o.inA), Wt + o.w_off, Wt + o.wdup_off, Wt + o.b_off, c.f(o.mid), NB, o.Ca, ih, iw, o.K, o.S,
+                          lp::ACT_RELU6, s);
+            if (n->profiling)
+                if (const int rc = c.mark(half_name(o, COST_DW_HALF), c.cost(i, COST_DW_HALF))) return rc;
+            lp::launch_pw(c.f(o.mid), o.Ca, nullptr, 0, Wt + o.w2_off, Wt + o.b2_off, o.res >= 0 ? c.f(o.res) : nullptr,
+                          c.f(o.out), NB, oh * ow, o.Cout, lp::ACT_NONE, s, o.ws_off ? Wt + o.ws_off : nullptr, n->opt_pw3d);
+            return n->profiling ? c.mark(half_name(o, COST_PW_HALF), c.cost(i, COST_PW_HALF)) : LP_OK;
+    }
+    return c.mark(o.name, c.cost(i));
+}
+
+// ---- 16-bit storage: the rules in the order they are tried, then one launch per op ----
+
+// the whole 7x7 block in one launch (mbtb_kernel / mbtb_s2_kernel): expand / depthwise / project, the two expanded
+// tensors never stored.  Option "mbtb" = 0 keeps the chain
+int rule_mbtb(const Part& c, size_t i) {
+    const lp_net* n = c.n;
+    const BOp& o = n->bops[i];
+    if (!(o.type == OP_PW && o.inB < 0 && !o.out_f32 && o.act == lp::ACT_RELU6 && i + 2 < n->bops.size())) return 0;
+    const BOp &dw = n->bops[i + 1], &pw = n->bops[i + 2];
+    if (!(dw.type == OP_DW && dw.inA == o.out && dw.K == 7 && (dw.S == 1 || dw.S == 2) && dw.wrow_off &&
+          dw.act == lp::ACT_RELU6 && pw.type == OP_PW && pw.inA == dw.out && pw.inB < 0 && !pw.out_f32 &&
+          pw.act == lp::ACT_NONE && (pw.res < 0 || pw.res == o.inA)))
+        return 0;
+    const Planes pl = planes(c, o);
+    const float* Wt = c.Wt;
+    return lp::launch_mbtb(c.buf[o.inA], Wt + o.w_off, Wt + o.b_off, Wt + dw.wrow_off, Wt + pw.w_off, Wt + pw.b_off,
+                           pw.res >= 0 ? c.buf[pw.res] : nullptr, c.buf[pw.out], c.NB, o.Ca, o.Cout, pw.Cout, pl.ih, pl.iw,
+                           dw.K, dw.S, c.s, n->opt_mbtb, n->opt_mbtb_s2, n->opt_mbtq,
+                           dw.wrow2_off ? Wt + dw.wrow2_off : nullptr, n->opt_mbtd, c.f16) ? 3 : 0;
+}
+
+// The one entry whose bytes are NOT the sum over its ops: a launch_mbtb block reports the launch's own traffic -- the
+// block's input, its output and the residual it reads -- not the two expanded tensors, which the reference ops would
+// write and read back but which never leave the CU here.  The 16-bit rooflines of bench.py are priced from this figure, so
+// it stays as it is; its FLOPs are the plain sum.
+int64_t mbtb_launch_bytes(const Part& c, size_t i) {
+    const BOp &o = c.n->bops[i], &dw = c.n->bops[i + 1], &pw = c.n->bops[i + 2];
+    const int64_t NB = c.NB, ipx = (int64_t)(c.H / o.in_div) * (c.W / o.in_div), opx = ipx / (dw.S * dw.S);
+    return 2ll * NB * (ipx * o.Ca + opx * pw.Cout * (pw.res >= 0 ? 2ll : 1ll));
+}
+
+// the whole stem in one launch (stem4_kernel<C0, true>; option "stem" = 0: the three launches of the parity tests)
+int rule_stem3b(const Part& c, size_t i) {
+    const lp_net* n = c.n;
+    const BOp& o = n->bops[i];
+    if (!(o.type == OP_STEM && n->opt_stem && o.st_w0 && i + 2 < n->bops.size())) return 0;
+    const BOp &dw = n->bops[i + 1], &pw = n->bops[i + 2];
+    if (!(dw.type == OP_DW && dw.K == 3 && dw.S == 1 && pw.type == OP_PW && pw.inA == dw.out && !pw.out_f32)) return 0;
+    const float* Wt = c.Wt;
+    return lp::launch_stem3b(c.x, Wt + o.st_w0, Wt + o.b_off, Wt + o.st_w1, Wt + o.st_b1, Wt + o.st_w2, Wt + o.st_b2,
+                             c.buf[pw.out], c.NB, c.H, c.W, pw.Cout, c.flip_from, c.x_batch, c.s, c.f16) ? 3 : 0;
+}
+
+// an output head in one launch (headb_kernel): both 5x5 depthwise convs + the dual-source 1x1, or the dw5 + 1x1 of a
+// plain head (option "headb" = 0: the launches of the chain, what the per-launch parity tests run).  Needs the
+// matrix-core depthwise (option "dwt" >= 2): its results are the SAME bits as dwt_kernel<5>'s and pwb_kernel's
+int rule_headb(const Part& c, size_t i) {
+    const lp_net* n = c.n;
+    const std::vector<BOp>& ops = n->bops;
+    const BOp& o = ops[i];
+    if (!(o.type == OP_DW && o.K == 5 && o.S == 1 && n->opt_headb && n->opt_dwt >= 2 && o.wt_off && o.act == lp::ACT_RELU &&
+          i + 1 < ops.size()))
+        return 0;
+    const BOp& a = ops[i + 1];
+    const BOp *d2 = nullptr, *pw = nullptr;     // the second depthwise (null: one source), the 1x1
+    if (i + 2 < ops.size() && a.type == OP_DW && a.K == 5 && a.S == 1 && a.wt_off && a.act == lp::ACT_RELU &&
+        ops[i + 2].type == OP_PW && ops[i + 2].out_f32 && ops[i + 2].inA == o.out && ops[i + 2].inB == a.out &&
+        ops[i + 2].act == lp::ACT_NONE && ops[i + 2].res < 0)
+        d2 = &a, pw = &ops[i + 2];
+    else if (a.type == OP_PW && a.out_f32 && a.inA == o.out && a.inB < 0 && a.act == lp::ACT_NONE && a.res < 0)
+        pw = &a;
+    else
+        return 0;
+    const Planes pl = planes(c, o);
+    const float* Wt = c.Wt;
+    if (!lp::launch_headb(c.buf[o.inA], o.Ca, d2 ? c.buf[d2->inA] : nullptr, d2 ? d2->Ca : 0, Wt + o.wt_off, Wt + o.w_off,
+                          d2 ? Wt + d2->wt_off : nullptr, d2 ? Wt + d2->w_off : nullptr, Wt + pw->w_off, c.f(pw->out), c.NB,
+                          pl.ih, pl.iw, o.K, pw->Cout, c.s, c.f16))
+        return 0;
+    return d2 ? 3 : 2;
+}
+
+const Rule B16_RULES[] = {{rule_mbtb, blockb_name, mbtb_launch_bytes}, {rule_stem3b, stem_name, nullptr},
+                          {rule_headb, headb_name, nullptr}};
+
+// op i in a launch of its own, with its entry
+int launch_op_b16(const Part& c, size_t i) {
+    const lp_net* n = c.n;
+    const BOp& o = n->bops[i];
+    const Planes pl = planes(c, o);
+    const int ih = pl.ih, iw = pl.iw, NB = c.NB;
+    const float* Wt = c.Wt;
+    hipStream_t s = c.s;
+    const bool f16 = c.f16;
+    bool ok = true;
+    switch (o.type) {
+        case OP_STEM:
+            lp::launch_stemb(c.x, Wt + o.w_off, Wt + o.b_off, c.buf[o.out], NB, c.H, c.W, c.flip_from, c.x_batch, s, f16);
+            break;
+        case OP_DW: {
+            // the stride-1 7x7 / 5x5 depthwise runs as banded matrix products on the matrix cores (dwt_kernel) wherever
+            // its shape rule admits the plane (S@448 b32: 5.60 -> 4.82 ms/step, within 1 bf16 ulp of the emulation like
+            // dwb_kernel).  Option "dwt": 0 = dwb_kernel everywhere, 1 = 7x7 only, 2 (default) = 7x7 and the heads' 5x5
+            const int dwt = n->opt_dwt;
+            ok = dwt && o.wt_off && o.S == 1 && (o.K == 7 || (o.K == 5 && dwt >= 2)) &&
+                 lp::launch_dwt(c.buf[o.inA], Wt + o.wt_off, Wt + o.w_off, c.buf[o.out], NB, o.Ca, ih, iw, o.K, o.act, s, f16);
+            if (!ok) ok = lp::launch_dwb(c.buf[o.inA], Wt + o.w_off, c.buf[o.out], NB, o.Ca, ih, iw, o.K, o.S, o.act, s, f16);
+            break;
+        }
+        case OP_PW:
+            ok = lp::launch_pwb(c.buf[o.inA], o.Ca, o.inB >= 0 ? c.buf[o.inB] : nullptr, o.Cb, Wt + o.w_off, Wt + o.b_off,
+                                o.res >= 0 ? c.buf[o.res] : nullptr, c.buf[o.out], NB, pl.oh * pl.ow, o.Cout, o.act,
+                                o.out_f32, s, f16);
+            break;
+        case OP_DECONV:
+            ok = lp::launch_deconvb(c.buf[o.inA], o.Ca, o.inB >= 0 ? c.buf[o.inB] : nullptr, o.Cb, Wt + o.w_off,
+                                    Wt + o.b_off, c.buf[o.out], NB, ih, iw, o.Cout, s, f16);
+            break;
+        default:                     // OP_DWPW / OP_CONVK: not on a 16-bit plan
+            ok = false;
+            break;
+    }
+    if (!ok) return fail(LP_ERR_UNSUPPORTED, std::string(storage_name(n)) + " storage: unsupported layer shape at " + o.name);
+    return c.mark(o.name, c.cost(i));
+}
+
+// One part of a forward, either storage: at each op the rules in table order, else the op in a launch of its own.
+// stored[b]: buffer b was written (a fused launch stores only its output)
+int run_part(const Part& c, std::vector<char>& stored) {
+    const Rule* rules = c.f32 ? F32_RULES : B16_RULES;
+    const size_t nrules = c.f32 ? sizeof(F32_RULES) / sizeof(Rule) : sizeof(B16_RULES) / sizeof(Rule);
+    const size_t nops = c.f32 ? c.n->ops.size() : c.n->bops.size();
+    for (size_t i = 0; i < nops;) {
+        int used = 0, rc = LP_OK;
+        for (const Rule* r = rules; r != rules + nrules && !used; ++r) {
+            used = r->launch(c, i);
+            if (used && c.n->profiling) {          // the entry costs what the reference ops it replaces cost
+                Cost sum;
+                for (int k = 0; k < used; ++k) sum += c.cost(i + k);
+                if (r->bytes) sum.bytes = r->bytes(c, i);
+                rc = c.mark(r->name(c.op(i), c.op(i + 1), c.op(i + used - 1)), sum);
+            }
+        }
+        if (!used) rc = c.f32 ? launch_op_f32(c, i) : launch_op_b16(c, i);
+        if (rc) return rc;
+        i += used ? used : 1;
+        stored[c.op(i - 1).out] = 1;
+    }
     return LP_OK;
 }
 
@@ -517,279 +713,36 @@ int forward_bf16(lp_net* n, const float* d_x, int N, int H, int W, int flip, flo
 
 extern "C" {
 
+// the launch order is the reference forward's (lib/models/pose_mobilenet.py:137-156), the same for every storage
 int lp_net_forward(lp_net* n, const float* d_x, int N, int H, int W, int flip, float* d_out0,
                    float* d_out1, void* ws, size_t ws_bytes, void* stream) {
     if (!n || !d_x || !d_out0 || !d_out1 || !ws) return fail(LP_ERR_INVALID_ARG, "null argument");
     if (!n->finalized) return fail(LP_ERR_NOT_FINALIZED, "lp_net_finalize() has not been called");
     if (N < 1) return fail(LP_ERR_INVALID_ARG, "N must be positive");
-    if (const int rc = check_size(n, H, W)) return rc;           // both storage paths: before any buffer is laid out
+    if (const int rc = check_size(n, H, W)) return rc;           // before any buffer is laid out
     if (flip < 0 || flip > 2) return fail(LP_ERR_INVALID_ARG, "flip must be 0, 1 or 2");
     // a stale error of this thread (e.g. a hipGraph capture that another thread's call invalidated) must not be
     // mistaken for a failure of the launches below
     (void)hipGetLastError();
-    if (n->storage != LP_STORAGE_F32)
-        return forward_bf16(n, d_x, N, H, W, flip, d_out0, d_out1, ws, ws_bytes, (hipStream_t)stream);
     const int NB = flip == 2 ? 2 * N : N;             // images through the network
     if (ws_bytes < lp_net_workspace_bytes(n, NB, H, W) || ((uintptr_t)ws & 255))
         return fail(LP_ERR_WORKSPACE, "workspace too small or not 256-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    std::vector<char*> bptr;
+    const bool f32 = n->storage == LP_STORAGE_F32;
+    std::vector<char*> buf;
     std::vector<int> esz;
-    layout_buffers(n, ws, NB, H, W, d_out0, d_out1, bptr, esz);
-    const float* Wt = n->d_weights;
-    if (const int rc = prof_begin(n, n->ops.size(), s)) return rc;
-    auto run = [&](int NB, const std::vector<char*>& bptr, hipStream_t s, const float* xsrc, int flip_from,
-                   int x_batch) -> int {
-    std::vector<float*> ptr(bptr.size());
-    for (size_t b = 0; b < ptr.size(); ++b) ptr[b] = reinterpret_cast<float*>(bptr[b]);
-    auto prof_mark = [&](const std::string& name, int64_t by, int64_t fl, int64_t fl_valu) -> int {
-        return ::prof_mark(n, s, name, by, fl, fl_valu);
+    layout_buffers(n, ws, NB, H, W, d_out0, d_out1, buf, esz);
+    if (const int rc = prof_begin(n, f32 ? n->ops.size() : n->bops.size(), s)) return rc;
+    std::vector<char> stored(buf.size(), 0);
+    auto run = [&](int NBp, const std::vector<char*>& part, hipStream_t sp, const float* xsrc, int flip_from, int x_batch) {
+        return run_part(Part{n, part, sp, xsrc, NBp, H, W, flip_from, x_batch, n->d_weights, f32, n->storage == LP_STORAGE_F16},
+                        stored);
     };
-    for (size_t i = 0; i < n->ops.size(); ++i) {
-        const Op& o = n->ops[i];
-        const int ih = H / o.in_div, iw = W / o.in_div, oh = H / o.out_div, ow = W / o.out_div;
-        int64_t by = 0, fl = 0;
-        if (o.type == OP_PW && o.fuse_next && i + 1 < n->ops.size() && n->ops[i + 1].type == OP_DWPW) {
-            // whole InvBottleneck in one launch when the shape allows it
-            const Op& d = n->ops[i + 1];
-            // 16x16 planes (mb16_kernel): the whole RUN of same-shape residual blocks that follows in one launch --
-            // a block's output is the next block's input in the kernel's own register layout (mb16_kernels.hip)
-            if (n->opt_mb16 && NB >= n->opt_mb16_min && o.ws_off && d.ws_off && d.wrow_off &&
-                lp::mb16_supported(o.Ca, o.Cout, d.Cout, ih, iw, d.K, d.S, d.res >= 0)) {
-                auto bytes_of = [&](const Op& e, const Op& p) {
-                    return 4ll * NB * oh * ow * (e.Ca + e.Cout) + 4ll * NB * oh * ow * (int64_t)p.Ca +
-                           4ll * NB * oh * ow * (2ll * p.Ca + (int64_t)p.Cout * (p.res >= 0 ? 2 : 1));
-                };
-                auto flops_of = [&](const Op& e, const Op& p) {
-                    return 2ll * NB * oh * ow * (int64_t)e.Ca * e.Cout +
-                           2ll * NB * oh * ow * ((int64_t)p.Ca * p.K * p.K + (int64_t)p.Ca * p.Cout);
-                };
-                lp::Mb16Run r;
-                memset(&r, 0, sizeof(r));
-                size_t last = i;                                   // index of the run's last expand op
-                int64_t rby = 0, rfl = 0, rdw = 0;
-                for (size_t k = i; k + 1 < n->ops.size() && r.nblocks < lp::MB16_MAX_RUN; k += 2) {
-                    const Op& e = n->ops[k];
-                    const Op& p = n->ops[k + 1];
-                    if (e.type != OP_PW || !e.fuse_next || p.type != OP_DWPW || !e.ws_off || !p.ws_off || !p.wrow_off) break;
-                    if (k > i) {        // a follower: same shape, residual on its own input, fed by the previous block
-                        if (d.res < 0 || p.res != e.inA || e.inA != n->ops[k - 1].out || e.Ca != o.Ca ||
-                            e.Cout != o.Cout || p.Cout != d.Cout || p.K != d.K || p.S != d.S ||
-                            e.in_div != o.in_div || p.out_div != d.out_div || !n->opt_mb16_run)
-                            break;
-                    } else if (d.res >= 0 && d.res != o.inA) break;
-                    const int b = r.nblocks++;
-                    r.w1s[b] = Wt + e.ws_off; r.b1f[b] = Wt + e.b_off; r.wrow[b] = Wt + p.wrow_off;
-                    r.w2s[b] = Wt + p.ws_off; r.b2f[b] = Wt + p.b2_off; r.out[b] = ptr[p.out];
-                    rby += bytes_of(e, p); rfl += flops_of(e, p);
-                    rdw += 2ll * NB * oh * ow * (int64_t)p.Ca * p.K * p.K;
-                    last = k;
-                    if (d.res < 0) break;                          // a block that changes the channel count runs alone
-                }
-                if (r.nblocks >= 1 && lp::launch_mb16(ptr[o.inA], r, d.res >= 0, NB, o.Ca, o.Cout, d.Cout, ih, iw, d.K,
-                                                      d.S, s)) {
-                    const Op& pl = n->ops[last + 1];
-                    std::string nm = o.name + "+" + d.name.substr(d.name.rfind('.', d.name.find('+')) + 1);
-                    if (r.nblocks > 1) {                           // "stage.2.1-9.inv+depth_conv+point_conv"
-                        const std::string pfx = o.name.substr(0, o.name.rfind('.'));          // stage.2.1
-                        const std::string lpf = pl.name.substr(0, pl.name.rfind('.', pl.name.find('+')));
-                        nm = pfx + "-" + lpf.substr(lpf.rfind('.') + 1) + nm.substr(pfx.size());
-                    }
-                    const int rc = prof_mark(nm, rby, rfl, rdw);
-                    if (rc) return rc;
-                    i = last + 1;
-                    continue;
-                }
-            }
-            if ((o.ws_off && d.ws_off && d.wrow_off &&
-                 lp::launch_mbt(ptr[o.inA], Wt + o.ws_off, Wt + o.b_off, Wt + d.wrow_off, Wt + d.ws_off, Wt + d.b2_off,
-                                d.res >= 0 ? ptr[d.res] : nullptr, ptr[d.out], NB, o.Ca, o.Cout, d.Cout, ih, iw, d.K,
-                                d.S, s, n->opt_mbt, n->opt_mbt_s2)) ||
-                lp::launch_mbconv(ptr[o.inA], Wt + o.w_off, Wt + o.b_off, Wt + d.w_off, Wt + d.b_off,
-                                  Wt + d.w2_off, Wt + d.b2_off, d.res >= 0 ? ptr[d.res] : nullptr, ptr[d.out],
-                                  NB, o.Ca, o.Cout, d.Cout, ih, iw, d.K, d.S, s,
-                                  d.wpair_off ? Wt + d.wpair_off : nullptr, o.ws_off ? Wt + o.ws_off : nullptr,
-                                  d.wrow_off ? Wt + d.wrow_off : nullptr, n->opt_mbconv2)) {
-                // B_op accounting of the three reference ops this launch replaces (expand at the input
-                // resolution; depthwise out / project at the block's output resolution)
-                {
-                    const int64_t doh = H / d.out_div, dow = W / d.out_div;
-                    const int rc = prof_mark(
-                        o.name + "+" + d.name.substr(d.name.rfind('.', d.name.find('+')) + 1),
-                        4ll * NB * oh * ow * (o.Ca + o.Cout) + 4ll * NB * oh * ow * (int64_t)d.Ca +
-                            4ll * NB * doh * dow * (2ll * d.Ca + (int64_t)d.Cout * (d.res >= 0 ? 2 : 1)),
-                        2ll * NB * oh * ow * (int64_t)o.Ca * o.Cout +
-                            2ll * NB * doh * dow * ((int64_t)d.Ca * d.K * d.K + (int64_t)d.Ca * d.Cout),
-                        2ll * NB * doh * dow * (int64_t)d.Ca * d.K * d.K);
-                    if (rc) return rc;
-                }
-                ++i;
-                continue;
-            }
-        }
-        if (n->opt_stem && o.type == OP_STEM && i + 2 < n->ops.size() && n->ops[i + 1].type == OP_DW &&
-            n->ops[i + 2].type == OP_PW && o.st_w0) {
-            const Op& dw = n->ops[i + 1];
-            const Op& pw = n->ops[i + 2];
-            if (lp::launch_stem3(xsrc, Wt + o.st_w0, Wt + o.b_off, Wt + o.st_w1, Wt + dw.b_off, Wt + o.st_w2,
-                                 Wt + o.st_b2, ptr[pw.out], NB, H, W, pw.Cout, flip_from, x_batch, s)) {
-                // B_op accounting of the three reference ops this launch replaces
-                const int rc = prof_mark("stem.conv3x3s2+dw3+pw",
-                                         4ll * NB * (3ll * H * W + 32ll * oh * ow) + 4ll * NB * 32 * 2ll * oh * ow +
-                                             4ll * NB * oh * ow * (32 + pw.Cout),
-                                         2ll * NB * oh * ow * (32ll * 27 + 32ll * 9 + 32ll * pw.Cout),
-                                         2ll * NB * oh * ow * (32ll * 27 + 32ll * 9));
-                if (rc) return rc;
-                i += 2;
-                continue;
-            }
-        }
-        if (o.type == OP_DW && o.K == 3 && o.S == 1 && o.act == lp::ACT_RELU6 && i + 1 < n->ops.size() &&
-            n->ops[i + 1].type == OP_PW && n->ops[i + 1].inA == o.out && n->ops[i + 1].inB < 0 && n->ops[i + 1].res < 0 &&
-            n->ops[i + 1].act == lp::ACT_NONE && n->ops[i + 1].has_bias) {
-            // stem: dw3 + 1x1 in one launch (dwpw_kernel<3>): the 32-channel dw3 output stays in LDS
-            const Op& pw = n->ops[i + 1];
-            if (lp::launch_dwpw(ptr[o.inA], Wt + o.w_off, Wt + o.b_off, Wt + pw.w_off, Wt + pw.b_off, nullptr,
-                                      ptr[pw.out], NB, o.Ca, ih, iw, o.K, o.S, pw.Cout, s, n->opt_diag_dwpw)) {
-                const int64_t px = (int64_t)NB * oh * ow;
-                const int rc = prof_mark(o.name + "+pw", 4ll * px * (2ll * o.Ca) + 4ll * px * (o.Ca + pw.Cout),
-                                         2ll * px * ((int64_t)o.Ca * o.K * o.K + (int64_t)o.Ca * pw.Cout),
-                                         2ll * px * (int64_t)o.Ca * o.K * o.K);
-                if (rc) return rc;
-                ++i;
-                continue;
-            }
-        }
-        if (n->opt_headfuse && o.type == OP_DW && o.K == 5 && o.S == 1 && o.act == lp::ACT_RELU && i + 1 < n->ops.size() &&
-            n->ops[i + 1].type == OP_PW && n->ops[i + 1].inA == o.out && n->ops[i + 1].inB < 0 && n->ops[i + 1].res < 0 &&
-            n->ops[i + 1].act == lp::ACT_NONE && (n->ops[i + 1].out == n->out0_buf || n->ops[i + 1].out == n->out1_buf)) {
-            // one-source output head (plain_head): the 5x5 depthwise and the 1x1 in one launch, bit-identical to dw + pw
-            const Op& pw = n->ops[i + 1];
-            if (lp::launch_headfuse(ptr[o.inA], o.Ca, nullptr, 0, o.wpair_off ? Wt + o.wpair_off : nullptr, nullptr,
-                                    Wt + pw.w_off, ptr[pw.out], NB, oh, ow, o.K, pw.Cout, s)) {
-                const int64_t px = (int64_t)NB * oh * ow;
-                const int rc = prof_mark("final." + pw.name.substr(6, pw.name.find('.', 6) - 6) + ".dw5+pw",
-                                         4ll * px * (2ll * o.Ca) + 4ll * px * (o.Ca + pw.Cout),
-                                         2ll * px * ((int64_t)o.Ca * o.K * o.K + (int64_t)o.Ca * pw.Cout),
-                                         2ll * px * (int64_t)o.Ca * o.K * o.K);
-                if (rc) return rc;
-                ++i;
-                continue;
-            }
-        }
-        if (n->opt_headfuse && o.type == OP_DW && i + 2 < n->ops.size() && n->ops[i + 1].type == OP_DW && n->ops[i + 2].type == OP_PW &&
-            n->ops[i + 2].inA == o.out && n->ops[i + 2].inB == n->ops[i + 1].out && o.S == 1 && n->ops[i + 1].S == 1 &&
-            o.K == n->ops[i + 1].K && o.act == lp::ACT_RELU && n->ops[i + 1].act == lp::ACT_RELU) {
-            // output head: both 5x5 depthwise convs and the two-source 1x1 in one launch
-            const Op& d2 = n->ops[i + 1];
-            const Op& pw = n->ops[i + 2];
-            if (lp::launch_headfuse(ptr[o.inA], o.Ca, ptr[d2.inA], d2.Ca, o.wpair_off ? Wt + o.wpair_off : nullptr,
-                                    d2.wpair_off ? Wt + d2.wpair_off : nullptr, Wt + pw.w_off, ptr[pw.out], NB, oh, ow,
-                                    o.K, pw.Cout, s)) {
-                const int64_t px = (int64_t)NB * oh * ow;
-                const int rc = prof_mark(o.name.substr(0, o.name.find('.')) == "final_refined"
-                                             ? "final." + pw.name.substr(6, pw.name.find('.', 6) - 6) + ".dw5+dw5+pw" : pw.name,
-                                         4ll * px * (2ll * o.Ca + 2ll * d2.Ca) + 4ll * px * (o.Ca + d2.Ca + pw.Cout),
-                                         2ll * px * ((int64_t)(o.Ca + d2.Ca) * o.K * o.K + (int64_t)(o.Ca + d2.Ca) * pw.Cout),
-                                         2ll * px * (int64_t)(o.Ca + d2.Ca) * o.K * o.K);
-                if (rc) return rc;
-                i += 2;
-                continue;
-            }
-        }
-        switch (o.type) {
-            case OP_STEM:
-                lp::launch_stem(xsrc, Wt + o.w_off, Wt + o.b_off, ptr[o.out], NB, H, W, flip_from, x_batch, s);
-                by = 4ll * NB * (3ll * H * W + 32ll * oh * ow);
-                fl = 2ll * NB * 32 * 27 * oh * ow;
-                break;
-            case OP_DW:
-                lp::launch_dw(ptr[o.inA], Wt + o.w_off, Wt + o.wdup_off, Wt + o.b_off, ptr[o.out], NB, o.Ca, ih, iw, o.K,
-                              o.S, o.act, s);
-                by = 4ll * NB * o.Ca * ((int64_t)ih * iw + (int64_t)oh * ow);
-                fl = 2ll * NB * o.Ca * o.K * o.K * oh * ow;
-                break;
-            case OP_PW:
-                lp::launch_pw(ptr[o.inA], o.Ca, o.inB >= 0 ? ptr[o.inB] : nullptr, o.Cb, Wt + o.w_off,
-                              o.has_bias ? Wt + o.b_off : nullptr, o.res >= 0 ? ptr[o.res] : nullptr,
-                              ptr[o.out], NB, oh * ow, o.Cout, o.act, s, o.ws_off ? Wt + o.ws_off : nullptr, n->opt_pw3d);
-                by = 4ll * NB * oh * ow * (o.Ca + o.Cb + o.Cout + (o.res >= 0 ? o.Cout : 0));
-                fl = 2ll * NB * oh * ow * (int64_t)(o.Ca + o.Cb) * o.Cout;
-                break;
-            case OP_DECONV: {
-                float* inB = o.inB >= 0 ? ptr[o.inB] : nullptr;   // nullptr: the one-source form (plain head)
-                if (o.w3_off && deconv4_enabled() && o.w4_off &&
-                    lp::launch_deconv4x3(ptr[o.inA], o.Ca, inB, o.Cb, Wt + o.w4_off, Wt + o.b3_off, ptr[o.out], NB,
-                                         ih, iw, o.Cout, s)) {
-                } else if (o.w3_off && deconv4_enabled())
-                    lp::launch_deconv4(ptr[o.inA], o.Ca, inB, o.Cb, Wt + o.w3_off, Wt + o.b3_off, ptr[o.out],
-                                       NB, ih, iw, o.Cout, s);
-                else if (o.mid == 1)
-                    lp::launch_deconv_mfma(ptr[o.inA], o.Ca, inB, o.Cb, Wt + o.w2_off, Wt + o.b2_off,
-                                           ptr[o.out], NB, ih, iw, o.Cout, s);
-                else
-                    lp::launch_deconv_pair(ptr[o.inA], o.Ca, inB, o.Cb, Wt + o.w_off, Wt + o.b_off,
-                                           ptr[o.out], NB, ih, iw, o.Cout, s);
-                by = 4ll * NB * ((int64_t)(o.Ca + o.Cb) * ih * iw + (int64_t)o.Cout * oh * ow);
-                fl = 2ll * NB * (int64_t)(o.Ca + o.Cb) * o.Cout * 4 * oh * ow;
-                break;
-            }
-            case OP_CONVK:
-                // dense k x k conv (+ upsample / second source); `oh, ow` already include the stride / the x2
-                if (!lp::launch_convk3(o.image_in ? xsrc : ptr[o.inA], o.Ca, o.inB >= 0 ? ptr[o.inB] : nullptr, o.Cb,
-                                       Wt + o.wk_off, Wt + o.b_off, ptr[o.out], NB, ih, iw, o.K, o.S, o.ups, o.Cout, o.act,
-                                       o.image_in ? flip_from : NB, o.image_in ? x_batch : NB, s))
-                    return fail(LP_ERR_UNSUPPORTED, "convk3: shape not supported: " + o.name);
-                by = 4ll * NB * ((int64_t)(o.Ca + o.Cb) * ih * iw + (int64_t)o.Cout * oh * ow);
-                fl = 2ll * NB * (int64_t)(o.Ca + o.Cb) * o.K * o.K * o.Cout * oh * ow;
-                break;
-            case OP_DWPW:
-                if (!lp::launch_dwpw(ptr[o.inA], Wt + o.w_off, Wt + o.b_off, Wt + o.w2_off, Wt + o.b2_off,
-                                     o.res >= 0 ? ptr[o.res] : nullptr, ptr[o.out], NB, o.Ca, ih, iw, o.K, o.S,
-                                     o.Cout, s)) {
-                    lp::launch_dw(ptr[o.inA], Wt + o.w_off, Wt + o.wdup_off, Wt + o.b_off, ptr[o.mid], NB, o.Ca, ih, iw, o.K,
-                                  o.S, lp::ACT_RELU6, s);
-                    {
-                        const int rc = prof_mark(o.name.substr(0, o.name.find('+')),
-                                                 4ll * NB * o.Ca * ((int64_t)ih * iw + (int64_t)oh * ow),
-                                                 2ll * NB * o.Ca * o.K * o.K * (int64_t)oh * ow,
-                                                 2ll * NB * o.Ca * o.K * o.K * (int64_t)oh * ow);
-                        if (rc) return rc;
-                    }
-                    lp::launch_pw(ptr[o.mid], o.Ca, nullptr, 0, Wt + o.w2_off, Wt + o.b2_off,
-                                  o.res >= 0 ? ptr[o.res] : nullptr, ptr[o.out], NB, oh * ow, o.Cout,
-                                  lp::ACT_NONE, s, o.ws_off ? Wt + o.ws_off : nullptr, n->opt_pw3d);
-                    {
-                        const std::string pfx = o.name.substr(0, o.name.rfind('.', o.name.find('+')));
-                        const int rc = prof_mark(pfx + ".point_conv",
-                                                 4ll * NB * oh * ow * ((int64_t)o.Ca + (int64_t)o.Cout * (o.res >= 0 ? 2 : 1)),
-                                                 2ll * NB * oh * ow * (int64_t)o.Ca * o.Cout, 0);
-                        if (rc) return rc;
-                    }
-                    continue;
-                }
-                // SURVEY 8(d) B_op accounting is per reference op: dw in+out, 1x1 in+out(+res)
-                by = 4ll * NB * ((int64_t)o.Ca * ih * iw + 2ll * o.Ca * oh * ow +
-                                 (int64_t)o.Cout * oh * ow * (o.res >= 0 ? 2 : 1));
-                fl = 2ll * NB * oh * ow * ((int64_t)o.Ca * o.K * o.K + (int64_t)o.Ca * o.Cout);
-                break;
-        }
-        {
-            const int rc = prof_mark(o.name, by, fl,
-                                     (o.type == OP_STEM || o.type == OP_DW) ? fl
-                                     : (o.type == OP_DWPW ? 2ll * NB * oh * ow * (int64_t)o.Ca * o.K * o.K : 0));
-            if (rc) return rc;
-        }
-    }
-    return LP_OK;
-    };
-    if (const int rc = fan_out(n, d_x, N, H, W, flip, s, bptr, esz, run)) return rc;
+    if (const int rc = fan_out(n, d_x, N, H, W, flip, s, buf, esz, run)) return rc;
     HIP_OK(hipGetLastError());
-    n->last_ptr.resize(bptr.size());
-    for (size_t b = 0; b < bptr.size(); ++b) n->last_ptr[b] = reinterpret_cast<float*>(bptr[b]);
-    n->lastN = NB;
-    n->lastH = H;
-    n->lastW = W;
+    n->last_buf = buf;                                // what lp_net_tap needs of this forward
+    n->last_stored = stored;
+    n->lastN = NB, n->lastH = H, n->lastW = W;
     return LP_OK;
 }
 
@@ -984,21 +937,21 @@ static const OpBase* find_tap(const lp_net* n, const char* name) {
 }
 
 int64_t lp_net_tap(const lp_net* n, const char* name, float* d_dst, void* stream) {
-    if (!n || !name || n->last_ptr.empty()) return fail(LP_ERR_INVALID_ARG, "no forward has run");
+    if (!n || !name || n->last_buf.empty()) return fail(LP_ERR_INVALID_ARG, "no forward has run");
     const OpBase* o = find_tap(n, name);
     if (!o) return fail(LP_ERR_UNKNOWN_KEY, std::string("unknown tap ") + name);
     const int d = n->bufs.div[o->out];
     const int hw = (n->lastH / d) * (n->lastW / d);
     const int64_t cnt = (int64_t)n->lastN * n->bufs.ch[o->out] * hw;
     if (n->storage != LP_STORAGE_F32) {
-        if ((size_t)o->out >= n->last_stored_b.size() || !n->last_stored_b[o->out])
+        if ((size_t)o->out >= n->last_stored.size() || !n->last_stored[o->out])
             return fail(LP_ERR_UNSUPPORTED, std::string("tap ") + name + ": the last forward did not store this "
                         "tensor (it lives inside a fused block launch; option \"mbtb\" = 0 runs one launch per op)");
         if (d_dst)
-            lp::launch_octet_to_planar(n->last_ptr_b[o->out], d_dst, n->lastN, n->bufs.ch[o->out], hw,
+            lp::launch_octet_to_planar(n->last_buf[o->out], d_dst, n->lastN, n->bufs.ch[o->out], hw,
                                        (hipStream_t)stream, n->storage == LP_STORAGE_F16);
     } else if (d_dst) {
-        hipError_t e = hipMemcpyAsync(d_dst, n->last_ptr[o->out], (size_t)cnt * sizeof(float),
+        hipError_t e = hipMemcpyAsync(d_dst, n->last_buf[o->out], (size_t)cnt * sizeof(float),
                                       hipMemcpyDeviceToDevice, (hipStream_t)stream);
         if (e != hipSuccess) return fail(LP_ERR_HIP, hipGetErrorString(e));
     }
@@ -1030,7 +983,7 @@ int lp_net_set_storage(lp_net* n, int storage) {
     if (storage != n->storage) {
         n->storage = storage;
         n->finalized = false;
-        n->last_ptr.clear();
+        n->last_buf.clear();
     }
     return LP_OK;
 }

@@ -820,6 +820,39 @@ struct Resnet : Form {
 
 const char* last_error() { return g_err.c_str(); }
 
+Cost op_cost(const OpBase& o, int esz, bool out_f32, int NB, int H, int W, CostPart part) {
+    const int64_t e = esz, nb = NB, Cin = o.Ca + o.Cb, KK = o.K * o.K;
+    const int64_t ipx = (int64_t)(H / o.in_div) * (W / o.in_div), opx = (int64_t)(H / o.out_div) * (W / o.out_div);
+    Cost c;
+    switch (o.type) {
+        case OP_STEM:                        // the fp32 image in, 32 channels out
+            c.bytes = nb * (12ll * H * W + e * 32 * opx);
+            c.flops = c.flops_valu = 2 * nb * 32 * 27 * opx;
+            break;
+        case OP_PW:                          // in (+ second source) + out (+ residual)
+            c.bytes = nb * opx * (e * Cin + (out_f32 ? 4 : e) * o.Cout + (o.res >= 0 ? e * o.Cout : 0));
+            c.flops = 2 * nb * opx * Cin * o.Cout;
+            break;
+        case OP_DECONV:                      // 4 of its 16 taps reach an output cell
+        case OP_CONVK:
+            c.bytes = e * nb * (Cin * ipx + o.Cout * opx);
+            c.flops = 2 * nb * Cin * o.Cout * opx * (o.type == OP_DECONV ? 4 : KK);
+            break;
+        case OP_DW:
+        case OP_DWPW:                        // per reference op: depthwise in + out, then the 1x1's in + out (+ residual)
+            if (part != COST_PW_HALF) {
+                c.bytes = e * nb * o.Ca * (ipx + opx);
+                c.flops = c.flops_valu = 2 * nb * o.Ca * KK * opx;
+            }
+            if (o.type == OP_DWPW && part != COST_DW_HALF) {
+                c.bytes += e * nb * opx * (o.Ca + (int64_t)o.Cout * (o.res >= 0 ? 2 : 1));
+                c.flops += 2 * nb * opx * o.Ca * o.Cout;
+            }
+            break;
+    }
+    return c;
+}
+
 size_t arena_push(std::vector<float>& a, size_t count) {
     // keep every block 64-float (256-byte) aligned
     size_t off = (a.size() + 63) / 64 * 64;

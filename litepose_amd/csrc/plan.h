@@ -102,6 +102,16 @@ int init_arch(Net& n, const lp_arch& a);   // channel bookkeeping and the state_
 int build(Net& n);                         // ops / bops, bufs, h_packed: the form follows arch.family and storage
 const char* last_error();
 
+// What lp_net_profile2 reports per launch: the tensors a reference op reads and writes once, its FLOPs, and their depthwise
+// / stem-conv share (vector pipe; the rest: matrix cores).  A fused launch costs the sum over the reference ops it replaces.
+struct Cost {
+    int64_t bytes = 0, flops = 0, flops_valu = 0;
+    Cost& operator+=(const Cost& c) { bytes += c.bytes; flops += c.flops; flops_valu += c.flops_valu; return *this; }
+};
+enum CostPart { COST_OP, COST_DW_HALF, COST_PW_HALF };    // OP_DWPW run as two launches: its depthwise / its 1x1 alone
+// one reference op over NB images of H x W.  esz: bytes per stored element (4; 2 for 16-bit storage, out_f32: an fp32 head)
+Cost op_cost(const OpBase& o, int esz, bool out_f32, int NB, int H, int W, CostPart part = COST_OP);
+
 size_t arena_push(std::vector<float>& a, size_t count);   // a zeroed 256-byte aligned block; returns its float offset
 float round16(int storage, float x);       // x rounded to bf16 / fp16 (nearest even), as fp32
 

@@ -5,6 +5,7 @@
 //
 //   plan_digest            the digest lines
 //   plan_digest --time     milliseconds to build the plan of prune-L in the three storages (minimum of five runs each)
+//   plan_digest --costs    lp_plan::op_cost of every op of two plans (search-XS fp32 and bf16, 2 images of 256 x 256)
 //
 // The golden file was recorded from the engine as it was BEFORE plan.cpp existed: -DPLAN_DIGEST_PARENT='"<engine.cpp>"'
 // includes that one-file engine instead of plan.h (its plan builders make no HIP call; linked against that commit's
@@ -237,10 +238,37 @@ void time_plans() {
     }
 }
 
+#ifndef PLAN_DIGEST_PARENT
+void print_cost(const OpBase& o, const char* part, const Cost& c) {
+    std::printf("%-36s %-4s bytes %lld flops %lld valu %lld\n", o.name.c_str(), part, (long long)c.bytes, (long long)c.flops,
+                (long long)c.flops_valu);
+}
+void costs() {
+    for (int storage = 0; storage < 2; ++storage) {
+        std::string err;
+        Net* n = net_new(zoo("search-XS", 0), err);
+        n->storage = storage;
+        fill(n, 1);
+        if (net_build(n, err) != LP_OK) { std::printf("refused: %s\n", err.c_str()); std::exit(1); }
+        for (const Op& o : n->ops) {
+            print_cost(o, "op", op_cost(o, 4, false, 2, 256, 256));
+            if (o.type != OP_DWPW) continue;
+            print_cost(o, "dw", op_cost(o, 4, false, 2, 256, 256, COST_DW_HALF));
+            print_cost(o, "pw", op_cost(o, 4, false, 2, 256, 256, COST_PW_HALF));
+        }
+        for (const BOp& o : n->bops) print_cost(o, "op", op_cost(o, 2, o.out_f32, 2, 256, 256));
+        net_free(n);
+    }
+}
+#endif
+
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc > 1 && !std::strcmp(argv[1], "--time")) { time_plans(); return 0; }
+#ifndef PLAN_DIGEST_PARENT
+    if (argc > 1 && !std::strcmp(argv[1], "--costs")) { costs(); return 0; }
+#endif
     const int d_wide[3] = {96, 18, 24};      // > 64 (fp32 only); 18: the next deconv has no w3 / w4 form
     const int d_mid[3] = {48, 20, 24};       // 33..64; 20: the next deconv has the w3 form but no w4
     const int s_net[4] = {2, 2, 2, 1}, s_deep[4] = {2, 2, 2, 2}, s_head[4] = {2, 1, 2, 1};

@@ -458,6 +458,48 @@ int lp_parse_dm(const float* d_det, const float* d_mid, int N, int J, int h1, in
                 float* d_ans, int32_t* d_count, float* d_scores,
                 void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------ fast parser --------
+ * Replaces the reference's real-time demo parser, nano_demo/fast_utils (fast_utils/group.py:38-48 -> plugins.cpp ->
+ * parse/find_peaks.cpp, parse/assign.cpp): a thresholded window-maximum scan that keeps the first M peaks of every
+ * plane in raster order, then a greedy joint-by-joint grouping with a Kuhn-Munkres assignment on ONE tag value.  No
+ * adjust, no refine, and other records than lp_parse* by design (group.py's parser takes the top-k by value and
+ * matches with munkres on tag + position rounding).  Bit-identical to the reference's x86-64 build, unused slots
+ * included (it allocates its outputs as zeros: plugins.cpp:55-58,101-102).
+ *   d_det  [N,J,H,W]      heatmaps
+ *   d_tmap                the FIRST tag map (tmap[:,:,:,:,0], fast_utils/group.py:40): the tag of cell (n,j,y,x) is
+ *                         d_tmap[(((n*J + j)*H + y)*W + x) * tmap_stride]; tmap_stride = 1 for a dense [N,J,H,W] map,
+ *                         T for the [N,J,H,W,T] tensor of lp_tta_merge passed as it is (only peak cells are read)
+ *   threshold, window     TEST.DETECTION_THRESHOLD, TEST.NMS_KERNEL: a cell v is a peak iff !(v < threshold) and no cell
+ *                         of its window/2 neighbourhood, clamped to the plane, is > v (every cell of a plateau is one)
+ *   M                     DATASET.MAX_NUM_PEOPLE
+ * lp_fast_peaks   count_out [N,J] i32, val_out [N,J,M], tag_out [N,J,M], ind_out [N,J,M,2] i32 = (x, y).
+ *                 Writes: every element of the four outputs (slots at or beyond count: 0).
+ * lp_fast_assign  h_joint_order: J host ints, a permutation of 0..J-1 (copied into the launch: a captured graph holds
+ *                 it).  ans_out [N,M,J,4] = (x, y, val, tag), zero where unset; num_out [N] persons.  The reference's
+ *                 match / update loop has no bound; here one joint's assignment gets 4096 rounds, and an image that
+ *                 needs more gets num = -1 and an all-zero record.  A d_count entry outside 0..M is read as clamped.
+ *                 Writes: every element of ans_out and num_out.
+ * lp_fast_parse   the two back to back, the peak lists in `workspace` (lp_fast_parse_workspace_bytes(N, J, M) bytes,
+ *                 4-byte aligned): no allocation, no synchronisation, capturable in a hipGraph.
+ *                 Writes: every element of ans_out and num_out; the first lp_fast_parse_workspace_bytes bytes of
+ *                 `workspace` at most (they then hold count, val, tag, ind, each at a 256-byte boundary).
+ * LP_ERR_UNSUPPORTED: M outside 1..10 (the reference's arrays are [10]), J outside 1..32, window even or > 7, W > 1024.
+ * LP_ERR_INVALID_ARG: a null pointer, N < 1, H or W < 1, tmap_stride < 1, a joint_order entry outside [0, J) or repeated.
+ * Every refusal is answered before any pointer is dereferenced.
+ * count_out ... `workspace` are DEVICE memory like every d_* pointer of this header; like lp_calib_step's they do not carry
+ * the prefix yet because the census of writable calls (tests/test_poison_cpu.py) keys on it and pins the CALLS table of
+ * tests/test_gpu_buffer_contract.py; their contract test is tests/test_gpu_fast_parse.py.          */
+int lp_fast_peaks(const float* d_det, const float* d_tmap, int64_t tmap_stride, int N, int J, int H, int W,
+                  float threshold, int window, int M,
+                  int32_t* count_out, float* val_out, float* tag_out, int32_t* ind_out, void* stream);
+int lp_fast_assign(const int32_t* d_count, const float* d_val, const float* d_tag, const int32_t* d_ind,
+                   int N, int J, int M, const int32_t* h_joint_order, float tag_threshold,
+                   float* ans_out, int32_t* num_out, void* stream);
+size_t lp_fast_parse_workspace_bytes(int N, int J, int M);
+int lp_fast_parse(const float* d_det, const float* d_tmap, int64_t tmap_stride, int N, int J, int H, int W,
+                  float threshold, int window, int M, const int32_t* h_joint_order, float tag_threshold,
+                  float* ans_out, int32_t* num_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------ pre-processing -----
  * utils.transforms.resize_align_multi_scale (lib/utils/transforms.py:179-192: cv2.warpAffine,
  * INTER_LINEAR, constant border 0) fused with torchvision ToTensor + Normalize (valid.py:178-186).

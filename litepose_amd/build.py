@@ -41,6 +41,8 @@ SOURCES = [
     ('calib_kernels.hip', []),
     ('ae_kernels.hip', ['-ffp-contract=off'] + NOPK),
     ('ae_mid_kernels.hip', ['-ffp-contract=off'] + NOPK),
+    ('fast_api.cpp', []),
+    ('fast_kernels.hip', ['-ffp-contract=off'] + NOPK),    # the compiled reference's fp32 / fp64 operations, one by one
 ]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value',
           '-Wno-pass-failed']

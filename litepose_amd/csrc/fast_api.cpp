@@ -1,0 +1,111 @@
+// C ABI of the reference's real-time parser (include/litepose_amd.h, "fast parser"): argument validation and workspace
+// carving; the kernels live in fast_kernels.hip.
+#include <hip/hip_runtime.h>
+
+#include "../../include/litepose_amd.h"
+#include "kernels.h"
+
+extern "C" void lp_set_error_(const char* msg);   // engine.cpp owns the thread-local slot
+
+namespace {
+int fail(int code, const char* msg) {
+    lp_set_error_(msg);
+    return code;
+}
+size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+// every refusal that needs no device: sizes of both stages (peaks: H, W, window; assign: joint_order)
+int check_sizes(int N, int J, int M) {
+    if (N < 1) return fail(LP_ERR_INVALID_ARG, "N must be positive");
+    if (J < 1 || J > 32) return fail(LP_ERR_UNSUPPORTED, "J must be 1..32");
+    if (M < 1 || M > 10)
+        return fail(LP_ERR_UNSUPPORTED, "M (MAX_NUM_PEOPLE) must be 1..10: the reference's arrays are [10] (assign.cpp:44-46,74-75)");
+    if ((long long)N * J > 0x7fffffffLL) return fail(LP_ERR_UNSUPPORTED, "N * J too large");
+    return LP_OK;
+}
+int check_plane(int H, int W, int window, long long tmap_stride) {
+    if (H < 1 || W < 1) return fail(LP_ERR_INVALID_ARG, "H and W must be positive");
+    if (tmap_stride < 1) return fail(LP_ERR_INVALID_ARG, "tmap_stride must be positive");
+    if (window < 1 || (window & 1) == 0 || window > 7) return fail(LP_ERR_UNSUPPORTED, "window must be odd and <= 7");
+    if (W > 1024) return fail(LP_ERR_UNSUPPORTED, "W must be <= 1024");
+    return LP_OK;
+}
+int check_order(const int32_t* h_joint_order, int J) {
+    unsigned seen = 0;
+    for (int i = 0; i < J; ++i) {
+        const int v = h_joint_order[i];
+        if (v < 0 || v >= J) return fail(LP_ERR_INVALID_ARG, "joint_order entry outside [0, J)");
+        if (seen >> v & 1u) return fail(LP_ERR_INVALID_ARG, "joint_order entry repeated");
+        seen |= 1u << v;
+    }
+    return LP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int lp_fast_peaks(const float* d_det, const float* d_tmap, int64_t tmap_stride, int N, int J, int H, int W,
+                  float threshold, int window, int M, int32_t* count_out, float* val_out, float* tag_out,
+                  int32_t* ind_out, void* stream) {
+    if (!d_det || !d_tmap || !count_out || !val_out || !tag_out || !ind_out)
+        return fail(LP_ERR_INVALID_ARG, "null argument");
+    int rc = check_sizes(N, J, M);
+    if (rc) return rc;
+    rc = check_plane(H, W, window, tmap_stride);
+    if (rc) return rc;
+    lp::launch_fast_peaks(d_det, d_tmap, (long)tmap_stride, N, J, H, W, threshold, window, M, count_out, val_out,
+                          tag_out, ind_out, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "fast_peaks launch failed");
+    return LP_OK;
+}
+
+int lp_fast_assign(const int32_t* d_count, const float* d_val, const float* d_tag, const int32_t* d_ind, int N, int J,
+                   int M, const int32_t* h_joint_order, float tag_threshold, float* ans_out, int32_t* num_out,
+                   void* stream) {
+    if (!d_count || !d_val || !d_tag || !d_ind || !h_joint_order || !ans_out || !num_out)
+        return fail(LP_ERR_INVALID_ARG, "null argument");
+    int rc = check_sizes(N, J, M);
+    if (rc) return rc;
+    rc = check_order(h_joint_order, J);
+    if (rc) return rc;
+    lp::launch_fast_assign(d_count, d_val, d_tag, d_ind, N, J, M, h_joint_order, tag_threshold, ans_out, num_out,
+                           (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "fast_assign launch failed");
+    return LP_OK;
+}
+
+size_t lp_fast_parse_workspace_bytes(int N, int J, int M) {
+    if (N < 1 || J < 1 || M < 1) return 0;
+    const size_t planes = (size_t)N * J;
+    return align256(planes * sizeof(int32_t)) + 2 * align256(planes * M * sizeof(float)) +
+           align256(planes * M * 2 * sizeof(int32_t));
+}
+
+int lp_fast_parse(const float* d_det, const float* d_tmap, int64_t tmap_stride, int N, int J, int H, int W,
+                  float threshold, int window, int M, const int32_t* h_joint_order, float tag_threshold,
+                  float* ans_out, int32_t* num_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!d_det || !d_tmap || !h_joint_order || !ans_out || !num_out || !workspace)
+        return fail(LP_ERR_INVALID_ARG, "null argument");
+    int rc = check_sizes(N, J, M);
+    if (rc) return rc;
+    rc = check_plane(H, W, window, tmap_stride);
+    if (rc) return rc;
+    rc = check_order(h_joint_order, J);
+    if (rc) return rc;
+    if (workspace_bytes < lp_fast_parse_workspace_bytes(N, J, M))
+        return fail(LP_ERR_WORKSPACE, "fast parse workspace too small");
+    if ((uintptr_t)workspace & 3) return fail(LP_ERR_WORKSPACE, "fast parse workspace must be 4-byte aligned");
+    const size_t planes = (size_t)N * J;
+    char* c = (char*)workspace;
+    int32_t* count = (int32_t*)c;        c += align256(planes * sizeof(int32_t));
+    float* val = (float*)c;              c += align256(planes * M * sizeof(float));
+    float* tag = (float*)c;              c += align256(planes * M * sizeof(float));
+    int32_t* ind = (int32_t*)c;
+    hipStream_t s = (hipStream_t)stream;
+    lp::launch_fast_peaks(d_det, d_tmap, (long)tmap_stride, N, J, H, W, threshold, window, M, count, val, tag, ind, s);
+    lp::launch_fast_assign(count, val, tag, ind, N, J, M, h_joint_order, tag_threshold, ans_out, num_out, s);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "fast_parse launch failed");
+    return LP_OK;
+}
+
+}  // extern "C"

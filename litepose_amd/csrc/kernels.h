@@ -307,4 +307,13 @@ void launch_warp_affine_norm_v(const unsigned char* src, long long src_bytes, co
 void launch_final_preds_v(float* ans, const int* count, int N, int pcap, int J, int T, const double* coef,
                           hipStream_t s);           // coef [N,4] = (sx, tx, sy, ty) per image, device
 
+// ---- the reference's real-time parser (nano_demo/fast_utils; fast_kernels.hip) ------
+// find_peaks: the first M peaks of every plane in raster order; tmap is read at (plane * H * W + y * W + x) * tstride
+// (W <= 1024, window odd <= 7, M <= 10: checked by the caller)
+void launch_fast_peaks(const float* det, const float* tmap, long tstride, int N, int J, int H, int W, float threshold,
+                       int window, int M, int* count, float* val, float* tag, int* ind, hipStream_t s);
+// assign: joint_order = J host ints (a permutation of 0..J-1), copied into the launch's arguments
+void launch_fast_assign(const int* count, const float* val, const float* tag, const int* ind, int N, int J, int M,
+                        const int* joint_order, float tag_threshold, float* ans, int* num, hipStream_t s);
+
 }  // namespace lp

@@ -1,0 +1,261 @@
+"""The fast parser on the device (lp_fast_peaks / lp_fast_assign / lp_fast_parse, csrc/fast_kernels.hip) against the REAL
+reference's goldens (tests/golden/gen_golden_fast.py: nano_demo/fast_utils find_peaks + assign), bitwise: every output is
+a copy of an input value, an integer, or the result of IEEE operations in the reference's order, so there is no
+tolerance anywhere in this file."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import _fast_ref as fr
+import _poison as po
+from conftest import ROOT
+from litepose_amd import _native as nv
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'golden_fast.npz')
+
+
+@pytest.fixture(scope='module')
+def golden():
+    g = np.load(GOLDEN)
+    return {k: g[k] for k in g.files}                     # decompressed once, shared and left unchanged
+
+
+def scenes(g):
+    return ['s%d_' % i for i in range(int(g['n_scenes']))]
+
+
+def cfg_of(g, k):
+    window, M, group = [int(v) for v in g[k + 'cfg']]
+    return float(g[k + 'thr'][0]), float(g[k + 'thr'][1]), window, M, group
+
+
+def order_of(g, k):
+    o = g[k + 'order']
+    return (C.c_int32 * len(o))(*[int(v) for v in o])
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def same(t, ref):
+    t = t.cpu().numpy()
+    return t.shape == ref.shape and t.dtype == ref.dtype and np.array_equal(t.view(np.int32), ref.view(np.int32))
+
+
+def run_peaks(det, tmap, stride, thr, window, M, outs=None):
+    N, J, H, W = det.shape
+    if outs is None:
+        outs = (torch.empty((N, J), dtype=torch.int32, device='cuda'), torch.empty((N, J, M), device='cuda'),
+                torch.empty((N, J, M), device='cuda'), torch.empty((N, J, M, 2), dtype=torch.int32, device='cuda'))
+    nv.check(nv.lib().lp_fast_peaks(nv.dptr(det), nv.dptr(tmap), stride, N, J, H, W, thr, window, M, nv.dptr(outs[0]),
+                                    nv.dptr(outs[1]), nv.dptr(outs[2]), nv.dptr(outs[3]), nv.stream_ptr()), 'lp_fast_peaks')
+    return outs
+
+
+def run_assign(count, val, tag, ind, order, tag_thr, outs=None):
+    N, J, M = val.shape
+    if outs is None:
+        outs = (torch.empty((N, M, J, 4), device='cuda'), torch.empty((N,), dtype=torch.int32, device='cuda'))
+    nv.check(nv.lib().lp_fast_assign(nv.dptr(count), nv.dptr(val), nv.dptr(tag), nv.dptr(ind), N, J, M, order, tag_thr,
+                                     nv.dptr(outs[0]), nv.dptr(outs[1]), nv.stream_ptr()), 'lp_fast_assign')
+    return outs
+
+
+def run_parse(det, tmap, stride, thr, window, M, order, tag_thr, outs=None, ws=None):
+    N, J, H, W = det.shape
+    need = int(nv.lib().lp_fast_parse_workspace_bytes(N, J, M))
+    if outs is None:
+        outs = (torch.empty((N, M, J, 4), device='cuda'), torch.empty((N,), dtype=torch.int32, device='cuda'))
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device='cuda')
+    nv.check(nv.lib().lp_fast_parse(nv.dptr(det), nv.dptr(tmap), stride, N, J, H, W, thr, window, M, order, tag_thr,
+                                    nv.dptr(outs[0]), nv.dptr(outs[1]), nv.dptr(ws), need, nv.stream_ptr()), 'lp_fast_parse')
+    return outs
+
+
+def test_peaks_match_the_reference_bitwise_on_every_scene(golden):
+    for k in scenes(golden):
+        thr, _, window, M, _ = cfg_of(golden, k)
+        got = run_peaks(dev(golden[k + 'det']), dev(golden[k + 'tmap']), 1, thr, window, M)
+        for t, name in zip(got, ('count', 'val', 'tag', 'ind')):
+            assert same(t, golden[k + name]), (k, name)      # unused slots included: zero, as the reference allocates
+
+
+@pytest.mark.parametrize('shape,window,M', [((1, 5, 40, 200), 3, 4), ((2, 5, 300, 1000), 5, 10), ((1, 5, 90, 1024), 7, 10)])
+def test_peaks_on_planes_of_several_segments_and_row_bands(shape, window, M):
+    """Planes wider than one 64-column segment (200 = 3 * 64 + 8) and taller than one LDS band (W = 1000: 8 rows per
+    band at window 5; W = 1024 at window 7: 6 rows), against the torch restatement that the CPU suite pins to the goldens."""
+    N, J, H, W = shape
+    rows = min(12288 // W - 2 * (window // 2), H)
+    det, tmap = fr.band_scene(7, N, J, H, W, rows, M)
+    want = fr.find_peaks(det, tmap, 0.25, window, M)
+    assert (want[0] == M).any() and (want[0] == 0).any() and ((want[0] > 0) & (want[0] < M)).any()
+    got = run_peaks(dev(det), dev(tmap), 1, 0.25, window, M)
+    for t, w, name in zip(got, want, ('count', 'val', 'tag', 'ind')):
+        assert same(t, w), name
+
+
+def test_assign_matches_the_reference_bitwise_on_the_golden_peak_lists(golden):
+    for k in scenes(golden):
+        _, tag_thr, _, M, _ = cfg_of(golden, k)
+        ans, num = run_assign(dev(golden[k + 'count']), dev(golden[k + 'val']), dev(golden[k + 'tag']),
+                              dev(golden[k + 'ind']), order_of(golden, k), tag_thr)
+        assert same(num, golden[k + 'num']), (k, num.tolist(), golden[k + 'num'].tolist())
+        assert same(ans, golden[k + 'ans']), k
+
+
+def test_assign_answers_minus_one_and_zeros_at_the_round_cap(golden):
+    """Peak lists for which the reference needs more than 4096 rounds in one joint (kept apart from the scenes by the
+    generator), in one batch with a scene of the same group: the capped image gets num = -1 and an all-zero record, its
+    neighbour the reference's."""
+    assert int(golden['n_capped']) >= 1
+    for i in range(int(golden['n_capped'])):
+        c = 'c%d_' % i
+        _, tag_thr, _, M, group = cfg_of(golden, c)
+        mates = [k for k in scenes(golden) if cfg_of(golden, k)[4] == group]
+        parts = [c] + mates[:1]
+        stack = [dev(np.concatenate([golden[p + name] for p in parts])) for name in ('count', 'val', 'tag', 'ind')]
+        ans, num = run_assign(*stack, order_of(golden, c), tag_thr)
+        assert int(num[0]) == -1 and not ans[0].view(torch.int32).any(), c
+        for n, p in enumerate(parts[1:], 1):
+            assert same(num[n:n + 1], golden[p + 'num']) and same(ans[n:n + 1], golden[p + 'ans']), (c, p)
+
+
+def test_parse_is_the_two_stages_and_the_reference_at_batch_one(golden):
+    for k in scenes(golden):
+        thr, tag_thr, window, M, _ = cfg_of(golden, k)
+        det, tmap, order = dev(golden[k + 'det']), dev(golden[k + 'tmap']), order_of(golden, k)
+        two = run_assign(*run_peaks(det, tmap, 1, thr, window, M), order, tag_thr)
+        ans, num = run_parse(det, tmap, 1, thr, window, M, order, tag_thr)
+        assert po.bitwise_equal(ans, two[0]) and po.bitwise_equal(num, two[1]), k
+        assert same(num, golden[k + 'num']) and same(ans, golden[k + 'ans']), k
+
+
+def groups(g):
+    out = {}
+    for k in scenes(g):
+        out.setdefault(cfg_of(g, k)[4], []).append(k)
+    return out
+
+
+def test_parse_of_stacked_scenes_and_of_the_strided_tag_tensor(golden):
+    """Scenes of one group stacked to a batch (N = 5 where the group kept five scenes): images are independent and the
+    batch stride is right; then the same batch with the tags as channel 0 of a [N,J,H,W,2] tensor (element stride 2, the
+    other channel NaN); then 70 images -- two workgroups of the assignment, the second one partly filled."""
+    gs = groups(golden)
+    assert sum(len(v) >= 5 for v in gs.values()) >= 3
+    for group, ks in gs.items():
+        ks = ks[:5]
+        thr, tag_thr, window, M, _ = cfg_of(golden, ks[0])
+        order = order_of(golden, ks[0])
+        det = dev(np.concatenate([golden[k + 'det'] for k in ks]))
+        tmap = dev(np.concatenate([golden[k + 'tmap'] for k in ks]))
+        want_ans = np.concatenate([golden[k + 'ans'] for k in ks])
+        want_num = np.concatenate([golden[k + 'num'] for k in ks])
+        ans, num = run_parse(det, tmap, 1, thr, window, M, order, tag_thr)
+        assert same(num, want_num) and same(ans, want_ans), group
+        two = run_assign(*run_peaks(det, tmap, 1, thr, window, M), order, tag_thr)
+        assert po.bitwise_equal(ans, two[0]) and po.bitwise_equal(num, two[1]), group
+        t2 = torch.stack((tmap, torch.full_like(tmap, float('nan'))), dim=4).contiguous()
+        ans, num = run_parse(det, t2, 2, thr, window, M, order, tag_thr)
+        assert same(num, want_num) and same(ans, want_ans), ('strided', group)
+        if det.shape[2] * det.shape[3] <= 24 * 40 and len(ks) == 5:
+            rep = [i % 5 for i in range(70)]
+            ans, num = run_parse(det[rep].contiguous(), tmap[rep].contiguous(), 1, thr, window, M, order, tag_thr)
+            assert same(num, want_num[rep]) and same(ans, want_ans[rep]), ('70 images', group)
+
+
+def test_parse_replayed_from_a_captured_graph_gives_the_same_bytes(golden):
+    ks = [v for v in groups(golden).values() if len(v) >= 5][0][:5]
+    thr, tag_thr, window, M, _ = cfg_of(golden, ks[0])
+    order = order_of(golden, ks[0])
+    det = dev(np.concatenate([golden[k + 'det'] for k in ks]))
+    tmap = dev(np.concatenate([golden[k + 'tmap'] for k in ks]))
+    N, J = det.shape[:2]
+    outs = (torch.empty((N, M, J, 4), device='cuda'), torch.empty((N,), dtype=torch.int32, device='cuda'))
+    ws = torch.empty(int(nv.lib().lp_fast_parse_workspace_bytes(N, J, M)), dtype=torch.uint8, device='cuda')
+    run_parse(det, tmap, 1, thr, window, M, order, tag_thr, outs, ws)
+    torch.cuda.synchronize()
+    eager = [t.clone() for t in outs]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        run_parse(det, tmap, 1, thr, window, M, order, tag_thr, outs, ws)
+    for _ in range(2):
+        for t in outs:
+            po.fill(t, 'N')
+        po.fill(ws, 'N')
+        graph.replay()
+        torch.cuda.synchronize()
+        assert po.bitwise_equal(outs[0], eager[0]) and po.bitwise_equal(outs[1], eager[1])
+    assert same(outs[1], np.concatenate([golden[k + 'num'] for k in ks]))
+
+
+@pytest.mark.parametrize('pick', [0, 1, 2])
+def test_writable_calls_respect_their_buffers(golden, pick):
+    """The buffer contract of include/litepose_amd.h for the three writable calls, with poisoned and guarded buffers
+    (tests/_poison.py): every documented element written, nothing outside, inputs untouched and not over-read (their
+    guards hold NaN / a huge value: a read past a plane's corner would make a peak), results independent of what the
+    outputs and the workspace held."""
+    ks = [v for v in groups(golden).values() if len(v) >= 5][pick][:5]
+    thr, tag_thr, window, M, _ = cfg_of(golden, ks[0])
+    order = order_of(golden, ks[0])
+    det_h = torch.from_numpy(np.concatenate([golden[k + 'det'] for k in ks])).cuda()
+    tmap_h = torch.from_numpy(np.concatenate([golden[k + 'tmap'] for k in ks])).cuda()
+    N, J = det_h.shape[:2]
+    need = int(nv.lib().lp_fast_parse_workspace_bytes(N, J, M))
+    results = {}
+    for pattern in po.PATTERNS:
+        arena = po.Arena(pattern)
+        det, tmap = arena.inp(det_h, what='det'), arena.inp(tmap_h, align=4, what='tmap')
+        peaks = (arena.out((N, J), torch.int32, align=4, what='count'), arena.out((N, J, M), align=4, what='val'),
+                 arena.out((N, J, M), align=4, what='tag'), arena.out((N, J, M, 2), torch.int32, align=4, what='ind'))
+        run_peaks(det, tmap, 1, thr, window, M, peaks)
+        two = (arena.out((N, M, J, 4), align=4, what='ans of assign'), arena.out((N,), torch.int32, align=4, what='num of assign'))
+        run_assign(*peaks, order, tag_thr, two)
+        one = (arena.out((N, M, J, 4), align=4, what='ans'), arena.out((N,), torch.int32, align=4, what='num'))
+        run_parse(det, tmap, 1, thr, window, M, order, tag_thr, one, arena.ws(need, align=4))
+        arena.check()
+        results[pattern] = [t.clone() for t in peaks + two + one]
+    for name, t in zip(('count', 'val', 'tag', 'ind', 'ans', 'num', 'ans', 'num'), results['Z']):
+        assert same(t, np.concatenate([golden[k + name] for k in ks])), name
+    for pattern in po.PATTERNS[1:]:
+        for a, b in zip(results['Z'], results[pattern]):
+            assert po.bitwise_equal(a, b), 'results depend on what the buffers held (%s)' % pattern
+            assert not po.still_poisoned(b, a, pattern)
+
+
+def test_heatmap_parser_is_the_reference_parse(golden):
+    """fast_utils.group.HeatmapParser(cfg).parse(det, tmap, scale): image 0, ans[:num] with x, y scaled, on the device;
+    the tag tensor is the engine's [N,J,H,W,T]."""
+    from litepose_amd import config
+    from litepose_amd.fast_utils import group
+    done = set()
+    for k in scenes(golden):
+        thr, tag_thr, window, M, g = cfg_of(golden, k)
+        J = golden[k + 'det'].shape[1]
+        if J == 18 or g in done:
+            continue
+        done.add(g)
+        cfg = config.get_cfg('crowd_pose' if J == 14 else 'coco')
+        cfg.DATASET.MAX_NUM_PEOPLE, cfg.TEST.DETECTION_THRESHOLD, cfg.TEST.TAG_THRESHOLD = M, thr, tag_thr
+        cfg.TEST.NMS_KERNEL, cfg.TEST.NMS_PADDING = window, window // 2
+        parser = group.HeatmapParser(cfg)
+        assert parser.params.num_joints == J
+        tmap = dev(golden[k + 'tmap'])
+        t2 = torch.stack((tmap, tmap + 1), dim=4).contiguous()
+        for scale in (1.0, 4.0, 1.5):
+            got = parser.parse(dev(golden[k + 'det']), t2, scale)
+            want = golden[k + 'ans'][0, :int(golden[k + 'num'][0])].copy()
+            want[:, :, :2] *= np.float32(scale)
+            assert got.is_cuda and same(got, want), (k, scale)
+        ans, num = parser.parse_batch(dev(golden[k + 'det']), tmap, 1.0)
+        assert same(num, golden[k + 'num']) and same(ans, golden[k + 'ans']), k
+    assert len(done) >= 8

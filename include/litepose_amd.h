@@ -500,6 +500,44 @@ int lp_fast_parse(const float* d_det, const float* d_tmap, int64_t tmap_stride, 
                   float threshold, int window, int M, const int32_t* h_joint_order, float tag_threshold,
                   float* ans_out, int32_t* num_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------ evaluation ---------
+ * COCO keypoint evaluation of the records where lp_final_preds_v leaves them: per record row the OKS of every kept
+ * detection against every annotation of the row's image, and the greedy matching at every (area range, threshold) --
+ * the published COCOeval algorithm for iouType = 'keypoints' (computeOks, evaluateImg), restated in DESIGN.md 4b.  ONE
+ * launch per call, no workspace: no allocation, no synchronisation, capturable in a hipGraph.  The accumulation into
+ * precision / recall tables is host work (litepose_amd/coco_eval.py).  pycocotools itself was not available to pin this
+ * against: the tests hold it to a plain restatement of the protocol and to hand-computed cases.
+ *   d_ans [N,pcap,J,3+T], d_count [N], d_scores [N,pcap]   the records (count read as clamped to 0..pcap)
+ *   J_eval                the first J_eval joints are evaluated (a trailing centre joint is not)
+ *   d_row_image [N]       the row's image: a slot of d_gt_first, anything outside [0, images) (-1: padding) skips the row
+ *   d_gt_kpts [G_tot,J_eval,3] (x, y, v), d_gt_area [G_tot], d_gt_bbox [G_tot,4] (x, y, w, h), all fp64;
+ *   d_gt_flags [G_tot]    bit 0 iscrowd, bit 1 ignore (iscrowd or num_keypoints == 0)
+ *   d_gt_first [images+1] prefix offsets: image i owns annotations d_gt_first[i] .. d_gt_first[i+1]-1.  CONDITION of the
+ *                         call: at most 64 per image (the table's owner checks it; the kernel reads the first 64)
+ *   h_sigmas [J_eval], h_thr [n_thr], h_area_rng [n_area,2] (lo, hi; both ends inclusive): host, copied into the launch
+ *   max_dets              detections kept per image: the first max_dets of the stable sort by descending score (ties keep
+ *                         record order; a NaN score orders after every number)
+ * Detection values are the fp32 records widened to fp64; everything else is fp64 in COCOeval's operation order.
+ *   score_out [N,max_dets] f32  sorted scores          num_out [N]  kept detections = min(count, max_dets)
+ *   src_out [N,max_dets]        record index p of each kept detection
+ *   match_out / ignore_out [N,max_dets] u32: bit a * n_thr + t = matched / ignored at area range a, threshold t
+ *   oks_out [N,max_dets,64] f64 the OKS matrix (kept detection x annotation), or NULL
+ * Writes: every element of every non-NULL output, for every row; skipped rows and unused slots are zero.
+ * LP_ERR_UNSUPPORTED: max_dets outside 1..32, n_thr * n_area > 32, J_eval outside 1..min(J, 32).
+ * LP_ERR_INVALID_ARG: a null pointer (oks_out excepted), N < 1, images < 0, pcap, J, n_thr or n_area < 1, T < 0.
+ * Every refusal is answered before any pointer is dereferenced.
+ * score_out ... oks_out are DEVICE memory; like the fast parser's outputs they do not carry the d_ prefix because the
+ * census of writable calls (tests/test_poison_cpu.py) keys on it; their contract test is tests/test_gpu_cocoeval.py
+ * (DESIGN.md section 8).                                                                                            */
+int lp_kpt_eval(const float* d_ans, const int32_t* d_count, const float* d_scores, int N, int pcap, int J, int T,
+                int J_eval, const int32_t* d_row_image,
+                const double* d_gt_kpts, const double* d_gt_area, const double* d_gt_bbox,
+                const int32_t* d_gt_flags, const int32_t* d_gt_first, int images,
+                const double* h_sigmas, const double* h_thr, int n_thr, const double* h_area_rng, int n_area,
+                int max_dets,
+                float* score_out, int32_t* num_out, int32_t* src_out, uint32_t* match_out, uint32_t* ignore_out,
+                double* oks_out, void* stream);
+
 /* ------------------------------------------------------------ pre-processing -----
  * utils.transforms.resize_align_multi_scale (lib/utils/transforms.py:179-192: cv2.warpAffine,
  * INTER_LINEAR, constant border 0) fused with torchvision ToTensor + Normalize (valid.py:178-186).

@@ -119,6 +119,8 @@ _SIGS = {
     'lp_fast_parse_workspace_bytes': (sz, [i32, i32, i32]),
     'lp_fast_parse': (i32, [vp, vp, i64, i32, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), C.c_float,
                             vp, vp, vp, sz, vp]),
+    'lp_kpt_eval': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_double),
+                          C.POINTER(C.c_double), i32, C.POINTER(C.c_double), i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     'lp_preprocess': (i32, [vp, i32, i32, C.POINTER(C.c_double), i32, i32, C.POINTER(C.c_float),
                             C.POINTER(C.c_float), vp, vp, vp]),
     'lp_preprocess_batch': (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), i32, i32, C.POINTER(C.c_float),

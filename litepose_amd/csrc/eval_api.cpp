@@ -1,0 +1,53 @@
+// C ABI of the COCO keypoint evaluation (include/litepose_amd.h, "evaluation"): argument validation and the host tables
+// of the launch; the kernel lives in eval_kernels.hip.
+#include <hip/hip_runtime.h>
+
+#include "../../include/litepose_amd.h"
+#include "kernels.h"
+
+extern "C" void lp_set_error_(const char* msg);   // engine.cpp owns the thread-local slot
+
+namespace {
+int fail(int code, const char* msg) {
+    lp_set_error_(msg);
+    return code;
+}
+}  // namespace
+
+extern "C" {
+
+int lp_kpt_eval(const float* d_ans, const int32_t* d_count, const float* d_scores, int N, int pcap, int J, int T,
+                int J_eval, const int32_t* d_row_image, const double* d_gt_kpts, const double* d_gt_area,
+                const double* d_gt_bbox, const int32_t* d_gt_flags, const int32_t* d_gt_first, int images,
+                const double* h_sigmas, const double* h_thr, int n_thr, const double* h_area_rng, int n_area,
+                int max_dets, float* score_out, int32_t* num_out, int32_t* src_out, uint32_t* match_out,
+                uint32_t* ignore_out, double* oks_out, void* stream) {
+    if (!d_ans || !d_count || !d_scores || !d_row_image || !d_gt_kpts || !d_gt_area || !d_gt_bbox || !d_gt_flags ||
+        !d_gt_first || !h_sigmas || !h_thr || !h_area_rng || !score_out || !num_out || !src_out || !match_out ||
+        !ignore_out)
+        return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (N < 1) return fail(LP_ERR_INVALID_ARG, "N must be positive");
+    if (images < 0) return fail(LP_ERR_INVALID_ARG, "images must not be negative");
+    if (pcap < 1 || J < 1 || T < 0) return fail(LP_ERR_INVALID_ARG, "pcap and J must be positive, T not negative");
+    if (n_thr < 1 || n_area < 1) return fail(LP_ERR_INVALID_ARG, "n_thr and n_area must be positive");
+    if (max_dets < 1 || max_dets > 32) return fail(LP_ERR_UNSUPPORTED, "max_dets must be 1..32");
+    if ((long long)n_thr * n_area > 32)
+        return fail(LP_ERR_UNSUPPORTED, "n_thr * n_area must be <= 32: one result bit per (area range, threshold)");
+    if (J_eval < 1 || J_eval > J || J_eval > 32) return fail(LP_ERR_UNSUPPORTED, "J_eval must be 1..min(J, 32)");
+    lp::KptEvalTables tb = {};
+    for (int j = 0; j < J_eval; ++j) tb.vars[j] = (h_sigmas[j] * 2.0) * (h_sigmas[j] * 2.0);
+    for (int a = 0; a < n_area; ++a)
+        for (int t = 0; t < n_thr; ++t) {
+            const double lim = 1.0 - 1e-10;
+            tb.best0[a * n_thr + t] = h_thr[t] < lim ? h_thr[t] : lim;
+            tb.lo[a * n_thr + t] = h_area_rng[2 * a];
+            tb.hi[a * n_thr + t] = h_area_rng[2 * a + 1];
+        }
+    lp::launch_kpt_eval(d_ans, d_count, d_scores, N, pcap, J, T, J_eval, d_row_image, d_gt_kpts, d_gt_area, d_gt_bbox,
+                        d_gt_flags, d_gt_first, images, tb, n_thr * n_area, max_dets, score_out, num_out, src_out,
+                        match_out, ignore_out, oks_out, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "kpt_eval launch failed");
+    return LP_OK;
+}
+
+}  // extern "C"

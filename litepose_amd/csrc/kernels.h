@@ -316,4 +316,21 @@ void launch_fast_peaks(const float* det, const float* tmap, long tstride, int N,
 void launch_fast_assign(const int* count, const float* val, const float* tag, const int* ind, int N, int J, int M,
                         const int* joint_order, float tag_threshold, float* ans, int* num, hipStream_t s);
 
+// ---- COCO keypoint evaluation: OKS + greedy matching per record row (eval_kernels.hip) ------
+// the host tables of lp_kpt_eval, copied into the launch: vars[j] = (2 sigma_j)^2, and per result bit b = a * n_thr + t
+// the starting bound min(thr[t], 1 - 1e-10) and the area range [lo, hi] of a
+struct KptEvalTables {
+    double vars[32];
+    double best0[32];
+    double lo[32];
+    double hi[32];
+};
+// one workgroup per row; max_dets <= 32, nbits <= 32, J_eval <= min(J, 32): checked by the caller.  An image's
+// annotations beyond the 64th are not read.
+void launch_kpt_eval(const float* ans, const int* count, const float* scores, int N, int pcap, int J, int T, int J_eval,
+                     const int* row_image, const double* gt_kpts, const double* gt_area, const double* gt_bbox,
+                     const int* gt_flags, const int* gt_first, int images, const KptEvalTables& tb, int nbits,
+                     int max_dets, float* score_out, int* num_out, int* src_out, unsigned* match_out,
+                     unsigned* ignore_out, double* oks_out, hipStream_t s);
+
 }  // namespace lp

@@ -690,11 +690,12 @@ class PoseEngine(object):
             ln['graphs'].clear()
             ln['seen'].clear()
 
-    def evaluate(self, images, image_ids=None, batch_size=64, num_joints=None, stats=None):
+    def evaluate(self, images, image_ids=None, batch_size=64, num_joints=None, stats=None, evaluator=None):
         """A whole validation set of HxWx3 uint8 images of any sizes -> result dicts in input order
-        (``litepose_amd.evaluate.evaluate``)."""
+        (``litepose_amd.evaluate.evaluate``).  ``evaluator``: a ``coco_eval.KeypointEvaluator`` that is fed every
+        batch's device records (COCO keypoint AP without leaving the device for OKS and matching)."""
         from . import evaluate as _ev
-        return _ev.evaluate(self, images, image_ids, batch_size, num_joints, stats)
+        return _ev.evaluate(self, images, image_ids, batch_size, num_joints, stats, evaluator)
 
     def release_shape(self, N, H, W):
         """Drop the buffers and captured graphs of input shape [N,3,H,W] in every buffer set (``evaluate``: a bucket that

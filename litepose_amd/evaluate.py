@@ -283,11 +283,14 @@ def _check_memory(engine, N, sizes):
                         avail / 1e9, lo))
 
 
-def evaluate(engine, images, image_ids=None, batch_size=64, num_joints=None, stats=None):
+def evaluate(engine, images, image_ids=None, batch_size=64, num_joints=None, stats=None, evaluator=None):
     """valid.py:195-233 over a whole set, batched: ``images`` = HxWx3 uint8 arrays of any mix of sizes ->
     ``results.records_to_results`` dicts in input order, the list ``results.preds_to_results(all_preds, all_scores,
     image_ids)`` of the reference loop.  ``image_ids`` default: the input positions.  ``stats``: optional dict, filled
-    with the bucket histogram and the time split (host packing, waiting for the device, records -> dicts)."""
+    with the bucket histogram and the time split (host packing, waiting for the device, records -> dicts).
+    ``evaluator``: a ``coco_eval.KeypointEvaluator``; every collected batch's device records go to its ``add`` (one
+    launch, padding rows marked -1) before they are copied to the host -- ``evaluator.summarize()`` afterwards is the
+    set's AP.  The returned dicts are the same with and without it."""
     cfg = engine.cfg
     scales = _check_cfg(cfg, engine)
     images = [np.ascontiguousarray(im) for im in images]
@@ -297,6 +300,8 @@ def evaluate(engine, images, image_ids=None, batch_size=64, num_joints=None, sta
     ids = list(range(len(images))) if image_ids is None else list(image_ids)
     if len(ids) != len(images):
         raise ValueError('one image id per image is required')
+    if evaluator is not None:
+        evaluator.slots_of(ids)              # an unknown or repeated id raises here, before anything is in flight
     if not images:
         return []
     t_start = time.perf_counter()
@@ -344,7 +349,11 @@ def evaluate(engine, images, image_ids=None, batch_size=64, num_joints=None, sta
     def collect(pend):
         k, i, h = pend.popleft()
         drain(i)
-        loader.store(i, *h.result())
+        rec = h.result()
+        if evaluator is not None:
+            b = batches[k]
+            evaluator.add(rec[0], rec[1], rec[2], [ids[r] for r in b.rows[:b.real]] + [-1] * (len(b.rows) - b.real))
+        loader.store(i, *rec)
         h.release()
         stored[i] = k
 

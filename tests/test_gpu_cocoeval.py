@@ -1,0 +1,242 @@
+"""lp_kpt_eval (csrc/eval_kernels.hip) and litepose_amd.coco_eval on the device against the plain restatement of the COCO
+keypoint protocol in tests/_cocoeval_ref.py.  Needs a real MI355X.
+
+The yardstick is the restatement, NOT pycocotools (not available): see the honesty clause of litepose_amd/coco_eval.py.
+
+The scene (``_cocoeval_ref.scene``, fixed seed): 48 rows of capacity 30, J = 17, T = 2; images with 0 / 1 / 5 / 64 (and
+2, 3, 4) annotations and 0 / 1 / 20 / 27 (and 3, 4, 6, 9) detections, two padding rows, crowds with and without
+keypoints, persons without keypoints, areas on both sides of 32^2 and 96^2 and ON them, detections that are jittered
+copies of annotations at seven noise levels plus random ones, tied scores, a duplicated annotation, and an image of
+the set that is never added.  The generator ASSERTS (no skip) that no restatement OKS lies within 1e-9 of a threshold,
+that no two OKS values a detection could choose between lie within 1e-9 of each other unless they are exactly equal by
+construction, that every area range has npig > 0 and that the restatement's AP lies strictly between 0.2 and 0.9.
+
+Tolerances.  oks_out: 1e-13 absolute -- two exp implementations correct to 1 ulp differ by <= 2 ulp on each of <= 17
+terms in (0, 1], two summation orders by <= 17^2 * 2^-53; every other operation is one IEEE operation on each side.
+Scores, num, src, match words, ignore words and the ten stats: bitwise."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import _cocoeval_ref as R
+import _poison as po
+
+pytestmark = pytest.mark.gpu
+
+from litepose_amd import _native as nv  # noqa: E402
+from litepose_amd import coco_eval as ce  # noqa: E402
+
+DBL = C.POINTER(C.c_double)
+
+
+@pytest.fixture(scope='module')
+def scene():
+    return R.scene()
+
+
+@pytest.fixture(scope='module')
+def small():
+    """14 evaluated joints of 15 (a centre joint rides along), one area range, CrowdPose's sigmas."""
+    return R.scene(seed=11, rows=7, pcap=8, J=15, T=1, J_eval=14, sigmas=R.CROWDPOSE_SIGMAS, area_rng=[(0.0, 1e10)],
+                   n_gt=(2, 0, 5, 1, 3), n_det=(3, 2, 8, 0, 5), pad_rows=(4,))
+
+
+def _gt(sc):
+    return ce.GroundTruth.from_arrays(*R.ground_truth_arrays(sc['gts'], sc['all_ids']))
+
+
+def _inputs(sc, gt):
+    rows = [gt.slot[i] if i >= 0 else -1 for i in sc['image_ids']]
+    G = max(len(gt.area), 1)
+    pad = lambda a, shape: np.concatenate([a, np.zeros((G - a.shape[0],) + shape, a.dtype)])
+    host = (sc['kpts'], sc['count'], sc['scores'], np.asarray(rows, np.int32), pad(gt.kpts, gt.kpts.shape[1:]),
+            pad(gt.area, ()), pad(gt.bbox, (4,)), pad(gt.flags, ()), gt.first)
+    return [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in host]
+
+
+def _outputs(N, M, with_oks, make=None):
+    make = make or (lambda shape, dtype, what: torch.empty(shape, dtype=dtype, device='cuda'))
+    outs = [make((N, M), torch.float32, 'score_out'), make((N,), torch.int32, 'num_out'),
+            make((N, M), torch.int32, 'src_out'), make((N, M), torch.int32, 'match_out'),
+            make((N, M), torch.int32, 'ignore_out')]
+    outs.append(make((N, M, 64), torch.float64, 'oks_out') if with_oks else None)
+    return outs
+
+
+def _run(sc, gt, ins, outs, M=20):
+    N, pcap, J, D = sc['kpts'].shape
+    sig = np.asarray(sc['sigmas'], np.float64)
+    thr = np.asarray(R.THR, np.float64)
+    rng = np.asarray(sc['area_rng'], np.float64).reshape(-1, 2)
+    ptr = lambda t: None if t is None else nv.dptr(t)
+    nv.check(nv.lib().lp_kpt_eval(
+        *[nv.dptr(t) for t in ins[:3]], N, pcap, J, D - 3, sc['J_eval'], *[nv.dptr(t) for t in ins[3:]],
+        len(gt.image_ids), sig.ctypes.data_as(DBL), thr.ctypes.data_as(DBL), thr.size, rng.ctypes.data_as(DBL),
+        rng.shape[0], M, *[ptr(t) for t in outs], nv.stream_ptr()), 'lp_kpt_eval')
+    return outs
+
+
+def _expected(sc, M=20):
+    """The restatement's per-row outputs in the layout of the call (skipped rows and unused slots zero)."""
+    N = len(sc['image_ids'])
+    A, T = len(sc['area_rng']), len(R.THR)
+    score = np.zeros((N, M), np.float32)
+    num = np.zeros(N, np.int32)
+    src = np.zeros((N, M), np.int32)
+    mw = np.zeros((N, M), np.uint32)
+    iw = np.zeros((N, M), np.uint32)
+    oks = np.zeros((N, M, 64))
+    for n, i in enumerate(sc['image_ids']):
+        e = sc['ref'].get(i) if i >= 0 else None
+        if e is None:
+            continue
+        k = len(e['src'])
+        num[n] = k
+        score[n, :k], src[n, :k] = e['scores'], e['src']
+        mw[n, :k], iw[n, :k] = R.words(e, A, T)
+        for d in range(k):
+            oks[n, d, :len(e['oks'][d])] = e['oks'][d]
+    return score, num, src, mw, iw, oks
+
+
+def _check_against_restatement(sc):
+    gt = _gt(sc)
+    outs = _run(sc, gt, _inputs(sc, gt), _outputs(len(sc['image_ids']), 20, True))
+    torch.cuda.synchronize()
+    score, num, src, mw, iw, oks = _expected(sc)
+    got = [t.cpu().numpy() for t in outs]
+    err = np.abs(got[5] - oks).max()
+    print('max |oks_out - restatement| = %.3e over %d rows' % (err, len(num)))
+    assert err <= 1e-13, err
+    assert got[1].tobytes() == num.tobytes()
+    assert got[0].tobytes() == score.tobytes()
+    assert got[2].tobytes() == src.tobytes()
+    assert got[3].view(np.uint32).tobytes() == mw.tobytes(), np.argwhere(got[3].view(np.uint32) != mw)[:5]
+    assert got[4].view(np.uint32).tobytes() == iw.tobytes(), np.argwhere(got[4].view(np.uint32) != iw)[:5]
+    return gt
+
+
+def _stats_through_the_evaluator(sc, gt, split):
+    """The device words through KeypointEvaluator (two add calls, rows split at ``split``) -> stats."""
+    ev = ce.KeypointEvaluator(gt, sigmas=sc['sigmas'], area_ranges=sc['area_rng'])
+    k, c, s = (torch.from_numpy(sc[name]).cuda() for name in ('kpts', 'count', 'scores'))
+    for lo, hi in ((0, split), (split, len(sc['image_ids']))):
+        ev.add(k[lo:hi].contiguous(), c[lo:hi].contiguous(), s[lo:hi].contiguous(), sc['image_ids'][lo:hi])
+    return ev, ev.summarize()
+
+
+def test_scene_against_the_restatement(scene):
+    assert sorted(set(len(g) for g in scene['gts'].values())) == [0, 1, 2, 3, 4, 5, 64]
+    assert {0, 1, 20, 27} <= set(int(c) for c in scene['count']) and scene['image_ids'].count(-1) == 2
+    gt = _check_against_restatement(scene)
+    ev, stats = _stats_through_the_evaluator(scene, gt, 20)
+    assert list(stats) == R.NAMES and ev.stats == list(stats.values())
+    for name in R.NAMES:
+        assert np.float64(stats[name]).tobytes() == np.float64(scene['stats'][name]).tobytes(), (name, stats[name])
+    assert ev.precision.tobytes() == scene['tables'][0].tobytes() and ev.recall.tobytes() == scene['tables'][1].tobytes()
+    with pytest.raises(ValueError, match='added twice'):
+        ev.add(torch.from_numpy(scene['kpts'][:1]).cuda(), torch.from_numpy(scene['count'][:1]).cuda(),
+               torch.from_numpy(scene['scores'][:1]).cuda(), scene['image_ids'][:1])
+    with pytest.raises(ValueError, match='not part of the ground truth'):
+        ev.add(torch.from_numpy(scene['kpts'][:1]).cuda(), torch.from_numpy(scene['count'][:1]).cuda(),
+               torch.from_numpy(scene['scores'][:1]).cuda(), [5])
+    # evaluated_ids: the restatement over half of the set
+    half = scene['all_ids'][::2]
+    ev2 = ce.KeypointEvaluator(gt, evaluated_ids=half)
+    ev2.add(torch.from_numpy(scene['kpts']).cuda(), torch.from_numpy(scene['count']).cuda(),
+            torch.from_numpy(scene['scores']).cuda(), scene['image_ids'])
+    per = R.evaluate_set({i: scene['dets'][i] for i in half if i in scene['dets']},
+                         {i: scene['gts'][i] for i in half}, half, R.COCO_SIGMAS)
+    want = R.summarize(*R.accumulate(per))
+    assert ev2.summarize() == want and want['AP'] != scene['stats']['AP']
+
+
+def test_fourteen_joints_with_a_centre_joint_and_one_area_range(small):
+    gt = _check_against_restatement(small)
+    _, stats = _stats_through_the_evaluator(small, gt, 3)
+    assert list(stats) == ['AP', 'Ap .5', 'AP .75', 'AR', 'AR .5', 'AR .75']
+    assert stats == small['stats']
+
+
+def test_replayed_from_a_captured_graph_gives_the_same_words(scene):
+    gt = _gt(scene)
+    ins = _inputs(scene, gt)
+    outs = _outputs(len(scene['image_ids']), 20, True)
+    _run(scene, gt, ins, outs)
+    torch.cuda.synchronize()
+    eager = [t.clone() for t in outs]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):            # one stream, no branches
+        _run(scene, gt, ins, outs)
+    for _ in range(2):
+        for t in outs:
+            po.fill(t, 'N')
+        graph.replay()
+        torch.cuda.synchronize()
+        for a, b in zip(outs, eager):
+            assert po.bitwise_equal(a, b)
+
+
+@pytest.mark.parametrize('with_oks', [False, True])
+def test_the_call_respects_its_buffers(scene, with_oks):
+    """The buffer contract of include/litepose_amd.h with poisoned and guarded buffers (tests/_poison.py): every
+    documented element written, guards intact, inputs untouched and not over-read, results independent of what the
+    outputs held -- with oks_out NULL and set."""
+    gt = _gt(scene)
+    plain = _inputs(scene, gt)
+    N = len(scene['image_ids'])
+    results = {}
+    for pattern in po.PATTERNS:
+        arena = po.Arena(pattern)
+        ins = [arena.inp(t, align=8, what='input %d' % i) for i, t in enumerate(plain)]
+        outs = _outputs(N, 20, with_oks, lambda shape, dtype, what: arena.out(shape, dtype, align=8, what=what))
+        _run(scene, gt, ins, outs)
+        arena.check()
+        results[pattern] = [t.clone() for t in outs if t is not None]
+    want = _expected(scene)
+    for got, ref in zip(results['Z'][:5], want[:5]):
+        assert got.cpu().numpy().tobytes() == ref.tobytes()
+    for pattern in po.PATTERNS[1:]:
+        for a, b in zip(results['Z'], results[pattern]):
+            assert po.bitwise_equal(a, b), 'results depend on what the buffers held (%s)' % pattern
+            assert not po.still_poisoned(b, a, pattern)
+
+
+def test_engine_evaluate_feeds_the_evaluator():
+    """engine.evaluate(images, evaluator=ev): the same dicts as without it, and ev.summarize() == the restatement run on
+    those dicts.  The annotations are made from the engine's own detections (every second one, shifted a little)."""
+    from litepose_amd import arch_zoo, config, engine
+    from oracle import synth
+    arch = arch_zoo.get('search-XS')
+    cfg = config.apply_arch(config.get_cfg('crowd_pose'), arch)
+    sd = synth.make_state_dict(arch, seed=1234, head_gain=6.0)       # noise peaks above the threshold
+    eng = engine.PoseEngine(cfg, arch, sd)
+    rng = np.random.default_rng(5)
+    images = [rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8) for h, w in [(120, 160)] * 5 + [(160, 120)] * 3]
+    ids = [40, 10, 30, 20, 80, 60, 70, 50]
+    plain = eng.evaluate(images, image_ids=ids, batch_size=4)
+    J = len(plain[0]['keypoints']) // 3
+    assert plain and J == 14
+    dets = R.results_to_dets(plain, J)
+    gts = {i: [] for i in ids}
+    for i, ds in dets.items():
+        for p, d in enumerate(ds[:40:2]):
+            k = np.zeros((J, 3))
+            k[:, :2] = np.round((np.asarray(d['kpts']) + rng.normal(0, 1 + p % 3, (J, 2))) * 4) / 4
+            k[:, 2] = rng.integers(0, 3, J)
+            w, h = np.ptp(k[:, 0]), np.ptp(k[:, 1])
+            gts[i].append({'kpts': k, 'area': float(w * h * 0.6 + 1.0), 'bbox': (k[:, 0].min(), k[:, 1].min(), w, h),
+                           'iscrowd': int(p % 7 == 6), 'num_keypoints': int((k[:, 2] > 0).sum())})
+    gt = ce.GroundTruth.from_arrays(*R.ground_truth_arrays(gts, sorted(ids)))
+    ev = ce.KeypointEvaluator(gt)
+    assert eng.evaluate(images, image_ids=ids, batch_size=4, evaluator=ev) == plain
+    per = R.evaluate_set(dets, gts, ids, R.CROWDPOSE_SIGMAS)
+    want = R.summarize(*R.accumulate(per))
+    got = ev.summarize()
+    print('engine AP', got['AP'], 'detections', len(plain))
+    assert got == want
+    assert 0.0 < want['AP'] < 1.0

@@ -661,7 +661,7 @@ __global__ __launch_bounds__(256) void pw2_kernel(const float* __restrict__ inA,
     const long gc = valid ? g : NG - 1;
     const int n = (int)(gc / HWV);
     const int p = (int)(gc - (long)n * HWV) * PXV;
-    const int KP = (Ca + Cb) >> 1;
+    const int KP = ((Ca + 1) >> 1) + ((Cb + 1) >> 1);        // pack_pw: the k-pairs of each source, an odd one padded
     const int cb0 = blockIdx.y * NB;
     const int cblocks = (Cout + 31) >> 5;
 
@@ -690,7 +690,7 @@ __global__ __launch_bounds__(256) void pw2_kernel(const float* __restrict__ inA,
         const int C = srcsel == 0 ? Ca : Cb;
         if (C == 0) continue;
         const float* sp = (srcsel == 0 ? inA : inB) + ((long)n * C + half) * HW + p;
-        const int kofs = srcsel == 0 ? 0 : (Ca >> 1);
+        const int kofs = srcsel == 0 ? 0 : ((Ca + 1) >> 1);
         const int nkp = C >> 1;
         const int nch = nkp / CH;
         vec_t bc[CH], bn[CH];
@@ -736,6 +736,19 @@ __global__ __launch_bounds__(256) void pw2_kernel(const float* __restrict__ inA,
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
                 const float av = wl[i][(long)(kofs + kp) * 64];
+#pragma unroll
+                for (int v = 0; v < PXV; ++v)
+                    acc[i][v] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[v], acc[i][v], 0, 0, 0);
+            }
+        }
+        if (C & 1) {                                        // the last channel alone: its absent partner is a zero
+            vec_t bv;                                       // operand (its weight is zero too) and is never loaded
+#pragma unroll
+            for (int v = 0; v < PXV; ++v) bv[v] = 0.f;
+            if (half == 0) bv = *reinterpret_cast<const vec_t*>(sp + (long)(2 * nkp) * HW);
+#pragma unroll
+            for (int i = 0; i < NB; ++i) {
+                const float av = wl[i][(long)(kofs + nkp) * 64];
 #pragma unroll
                 for (int v = 0; v < PXV; ++v)
                     acc[i][v] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[v], acc[i][v], 0, 0, 0);
@@ -2740,8 +2753,8 @@ __global__ __launch_bounds__(256) void deconv_mfma_kernel(const float* __restric
     const int p = (int)(gc - (long)n * hw);
     const int iy = p / w_, ix = p - iy * w_;
     const int par = blockIdx.y, a = par >> 1, b = par & 1;
-    const int Ct = DUAL ? Ca + Cb : Ca;
-    const int KP = 2 * Ct;                                   // (4 taps * Ct) / 2
+    // pack_deconv: per tap the k-pairs of each source, an odd source padded to a whole pair
+    const int KP = 4 * (((Ca + 1) >> 1) + (DUAL ? (Cb + 1) >> 1 : 0));
     // taps: a=0: (dy 0, ky 1), (dy -1, ky 3);  a=1: (dy +1, ky 0), (dy 0, ky 2)   (same in x)
     int toff[4];
     bool tok[4];
@@ -2777,7 +2790,12 @@ __global__ __launch_bounds__(256) void deconv_mfma_kernel(const float* __restric
                 const float av = wl[(long)(kbase + kp) * 64];
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
             }
-            kbase += nkp;
+            if (C & 1) {                                     // the last channel alone; its absent partner is never loaded
+                float bv = 0.f;
+                if (half == 0 && tok[t]) bv = sp[(long)(2 * nkp) * hw];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wl[(long)(kbase + nkp) * 64], bv, acc, 0, 0, 0);
+            }
+            kbase += (C + 1) >> 1;
         }
     }
     if (!valid) return;

@@ -279,7 +279,13 @@ void pack_pw(Net& n, std::vector<const Tensor*> ws, const std::vector<double>* s
              Op& op) {
     const Concat w(std::move(ws), scale);
     const int K = w.Ct, cblocks = (w.Cout + 31) / 32;
-    op.w_off = push_afrag32(n, cblocks, (K + 1) / 2, [&](int cb, int row, int k) { return w(cb * 32 + row, k); });
+    // k-pairs per SOURCE (pw2_kernel walks one source at a time): an odd channel count ends in a pair whose second
+    // weight is zero, so that no pair straddles the two sources.  Even counts: the plain [K/2] pairs
+    const int Ka = (int)w.ws[0]->shape[1], PA = (Ka + 1) / 2, PB = (K - Ka + 1) / 2;
+    op.w_off = push_afrag32(n, cblocks, PA + PB, [&](int cb, int row, int k) {
+        if (k < 2 * PA) return k < Ka ? w(cb * 32 + row, k) : 0.f;
+        return k - 2 * PA < K - Ka ? w(cb * 32 + row, Ka + k - 2 * PA) : 0.f;
+    });
     op.ws_off = 0;
     if (w.ws.size() == 1 && (K % 16) == 0) op.ws_off = push_afrag3(n, cblocks, K / 16, w);
     op.has_bias = true;
@@ -326,7 +332,7 @@ void pack_convk(Net& n, std::vector<const Tensor*> ws, const std::vector<double>
 
 // transposed-conv pair (refined channels, then the raw ones; ww = nullptr for a plain head) with the BN scale folded:
 //   w_off / b_off    [ci][co][ky][kx] and the shift: deconv_pair_kernel, and the source of the forms below
-//   w2_off / b2_off  Cout <= 32: fp32 MFMA fragments per output parity, K index = tap*Ct + ci (o.mid = 1)
+//   w2_off / b2_off  Cout <= 32: fp32 MFMA fragments per output parity, k-pairs [tap][refined pairs, raw pairs] (o.mid = 1)
 //   w3_off / b3_off  Cout <= 64, even channel counts: one 16-byte fetch = the 4 taps of (channel block, parity, channel
 //                    pair, lane); bias in D-fragment order per channel block
 //   w4_off           ... and channel counts in eights: exact bf16x3 A fragments [channel block][parity][tap][ks]
@@ -349,7 +355,13 @@ void pack_deconv(Net& n, const Tensor& wr, const Tensor* ww, const std::vector<d
         return n.h_packed[w_off + ((size_t)ci * Cout + co) * 16 + deconv_tap(par, t)];
     };
     if (Cout <= 32) {
-        o.w2_off = push_afrag32(n, 4, 2 * Ct, [&](int par, int co, int k) { return folded(k % Ct, co, par, k / Ct); });
+        // per tap the refined k-pairs, then the raw ones; an odd source ends in a pair with a zero second weight
+        const int Cb = dc.raw_in, PA = (Ca + 1) / 2, PT = PA + (Cb + 1) / 2;
+        o.w2_off = push_afrag32(n, 4, 4 * PT, [&](int par, int co, int k) {
+            const int t = k / (2 * PT), r = k % (2 * PT);
+            if (r < 2 * PA) return r < Ca ? folded(r, co, par, t) : 0.f;
+            return r - 2 * PA < Cb ? folded(Ca + r - 2 * PA, co, par, t) : 0.f;
+        });
         o.b2_off = push_bias_dfrag(n, 1, Cout, &sh);
         o.mid = 1;                       // flag: MFMA form available
     }
@@ -387,8 +399,10 @@ void pack_conv_bn_b(Net& n, const std::string& wkey, const std::string& bnkey, B
     bn_fold(n, op, bnkey, sc, sh);
     const int64_t co = w.shape[0], rest = w.numel() / co;
     if (octet) {            // [C/8][rest + 1][8]: the octet's taps, then its bias (one LDS-staged block per octet)
+        // whole octets only: a channel count that is no multiple of 8 (deconv filters of 20, say) has no 16-bit kernel --
+        // every launcher refuses it at the forward, by the layer's name -- and its last channels have no place here
         op.w_off = arena_push(n.h_packed, (size_t)(co / 8) * (rest + 1) * 8);
-        for (int64_t o = 0; o < co; ++o) {
+        for (int64_t o = 0; o < co / 8 * 8; ++o) {
             for (int64_t r = 0; r < rest; ++r)
                 n.h_packed[op.w_off + (size_t)((o >> 3) * (rest + 1) + r) * 8 + (o & 7)] =
                     round16(n.storage, (float)((double)w.data[o * rest + r] * sc[o]));

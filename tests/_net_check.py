@@ -131,12 +131,14 @@ def fp32_tap_names(d):
         + ['deconv.%d' % i for i in range(len(d['deconv']))]
 
 
-def check_fp32(m, arch, sd, x, flip, outs, chunk=8, tap_images=None):
+def check_fp32(m, arch, sd, x, flip, outs, chunk=8, tap_images=None, head=None, forward=net_ref.forward):
     """The device fp32 network (its last forward: ``outs`` and the block taps) against net_ref.forward on every image of
     the batch, the mirrored half (flip=2) against the oracle on torch.flip(x, [3]).  The oracle runs ``chunk`` images at a
     time so that the host memory of its taps stays bounded; taps are compared on the first ``tap_images`` images of each
-    half (None: all).  Returns (worst scaled tap error, its name, worst output error)."""
-    d = spec.derive(arch)
+    half (None: all).  ``head``: the oracle's HeadCfg when it is not the default; ``forward``: the oracle of another head
+    form with net_ref.forward's signature (tests/_simplenet_ref.py).  Returns (worst scaled tap error, its name, worst
+    output error)."""
+    d = spec.derive(arch, head)
     N = x.shape[0]
     halves = [(0, x)] if flip == 0 else ([(0, torch.flip(x, [3]))] if flip == 1 else [(0, x), (N, torch.flip(x, [3]))])
     names = fp32_tap_names(d)
@@ -148,7 +150,7 @@ def check_fp32(m, arch, sd, x, flip, outs, chunk=8, tap_images=None):
             with_taps = tap_images is None or c0 < tap_images
             taps = {} if with_taps else None
             with torch.no_grad():
-                ref = net_ref.forward(xs[c0:c1], sd, arch, taps=taps)
+                ref = forward(xs[c0:c1], sd, arch, head, taps=taps)
             for k in range(2):
                 got = outs[k][base + c0:base + c1].cpu()
                 err = float((got - ref[k]).abs().max())

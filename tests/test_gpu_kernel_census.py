@@ -95,28 +95,38 @@ CASES = [
     ('opt_mbtq2', 'search-S', 'bf16', 224, 224, 3, 0, {'mbtq': 2, 'mbtd': 0}, {'mbtq_kernel'}),
 ]
 
-# kernel tag -> why no CASES row reaches it (the option value or shape that would, or that no gate can)
+# kernel tag -> why no CASES row reaches it (the option value or shape that would).  CASES holds published architectures
+# only; the forms a custom ``cfg_arch`` selects are launched and compared by the rows of tests/_custom_space.py
+# (tests/test_gpu_custom_census.py), named here; tests/test_custom_census_cpu.py requires every entry to be expected by
+# such a row or listed in its UNREACHABLE
 NOT_REACHED = {
     'dw_kernel<7,1>': 'launch_dw takes dw_pair_kernel for every stride-1 plane up to 131070 images (grid.y <= 65535 '
                       'image pairs); only a larger launch would fall back to it',
     'dw_kernel<5,1>': 'as dw_kernel<7,1>: stride-1 5x5 planes take dw_pair_kernel<5> below 131071 images',
     'dw_kernel<3,1>': 'as dw_kernel<7,1>: stride-1 3x3 planes take dw_pair_kernel<3> below 131071 images',
-    'dw_kernel<5,2>': 'no gate can: the network has no stride-2 5x5 depthwise (heads are stride 1)',
-    'dw_kernel<3,2>': 'no gate can: the network has no stride-2 3x3 depthwise (the stem depthwise is stride 1)',
-    'dw_pair_kernel<3>': 'the fp32 stem depthwise runs in stem4_kernel (option "stem" = 1) or dwpw_kernel<3> ("stem" = 0)',
-    'dw_pair16_kernel<5>': 'a 16x16 head plane alone; headfuse_kernel takes every 16x16 head plane (the heads fall back '
-                           'to dw_pair_kernel<5> + pw2_kernel only on planes it refuses: xs16_f32, s208x336_f32)',
-    'dw_pair16_kernel<3>': 'as dw_pair_kernel<3>: the stem depthwise never runs alone',
-    'dwb_kernel<5,2>': 'no gate can: no stride-2 5x5 depthwise in the network',
-    'dwb_kernel<3,2>': 'no gate can: no stride-2 3x3 depthwise in the network',
+    'dw_kernel<5,2>': 'no published arch has a stride-2 5x5 depthwise (heads are stride 1); a custom stage whose entry '
+                      'block is 5x5 does: custom rows five_128, ksize_256, ksize_128',
+    'dw_kernel<3,2>': 'no published arch has a stride-2 3x3 depthwise (the stem depthwise is stride 1); a custom stage '
+                      'whose entry block is 3x3 does: custom rows five_128, ksize_256, ksize_128',
+    'dw_pair_kernel<3>': 'the fp32 stem depthwise runs in stem4_kernel (option "stem" = 1) or dwpw_kernel<3> ("stem" = 0); '
+                         'a custom 3x3 residual block runs it: custom rows ksize_256, ksize_128',
+    'dw_pair16_kernel<5>': 'a 16x16 head plane alone; headfuse_kernel takes every 16x16 head plane of the published archs '
+                           '(the heads fall back to dw_pair_kernel<5> + pw2_kernel only on planes it refuses: xs16_f32, '
+                           's208x336_f32); custom 5x5 blocks on 16x16 planes and the odd-filter head of odd_64 run it',
+    'dw_pair16_kernel<3>': 'as dw_pair_kernel<3>: the stem depthwise never runs alone; custom 3x3 blocks on 16x16 planes '
+                           'run it: custom rows ksize_256, ksize_128',
+    'dwb_kernel<5,2>': 'no published arch has a stride-2 5x5 depthwise; custom rows five_128, ksize_256, ksize_128 (bf16, f16)',
+    'dwb_kernel<3,2>': 'no published arch has a stride-2 3x3 depthwise; custom rows five_128, ksize_256, ksize_128 (bf16, f16)',
     'mbconv_kernel': 'needs a 24-channel stride-1 block whose expansion is a multiple of 32 channels; the published archs '
-                     'expand 24 channels to 144 (Cexp % 32 != 0), only a custom arch spec would reach it',
+                     'expand 24 channels to 144 (Cexp % 32 != 0); custom rows mb24_128, mb24_144x160, five_128 (expand 4)',
     'mbconv_s2_kernel': 'needs a 24-channel stride-2 entry block with <= 32 filters and an expansion that is a multiple '
                         'of 32; search-L / prune-M / prune-L expand to 144 (the gate cases mbconv_s2_896 / _1024 show the '
-                        'chain taken on both sides), only a custom arch spec would reach it',
-    'deconv_mfma_kernel': 'deconv layers whose channel counts leave no four-parity packing (odd inputs or more than 64 '
-                          'filters); every published arch has even inputs and <= 64 filters (deconv4 / deconv4x3)',
-    'deconv_pair_kernel': 'scalar deconv fallback for shapes without the MFMA packing; no published arch reaches it',
+                        'chain taken on both sides); custom rows mb24_128, mb24_144x160, mb24_w34',
+    'deconv_mfma_kernel': 'deconv layers whose channel counts leave no four-parity packing (odd inputs, or a total that is '
+                          'no multiple of 4) and <= 32 filters; every published arch has even inputs and <= 64 filters '
+                          '(deconv4 / deconv4x3); custom rows odd_64, odd_96x160, plain_mfma_64',
+    'deconv_pair_kernel': 'scalar deconv fallback for shapes without an MFMA packing (> 64 filters, or > 32 with channel '
+                          'counts that have no four-parity packing); custom rows pair66_64, wide72_64, plain_pair_64',
 }
 
 

@@ -597,6 +597,55 @@ int lp_final_preds_coef(const double* h_center, const double* h_scale, int Wp, i
 int lp_final_preds_v(float* d_ans, const int32_t* d_count, int N, int pcap, int J, int T, const double* d_coef,
                      void* stream);
 
+/* ------------------------------------------------------------ drawing ------------
+ * utils.vis.add_joints / get_annotated_image (lib/utils/vis.py:68-118, the last line of the demo's process()): the
+ * skeletons of the records drawn into uint8 images in place, ONE launch per call, no workspace: no allocation, no
+ * synchronisation, no global atomics (the result is deterministic), capturable in a hipGraph.
+ * The raster rule is this library's own, all-integer and exact.  It is PARITY-UNPINNED against cv2: cv2 was
+ * not available to pin cv2.circle / cv2.line; the pixel sets are discs and capsules of the reference's thickness, and how
+ * far they differ from cv2's at boundary pixels is not measured.
+ *   persons   p < P = min(max(d_count[n], 0), pcap) of image n (a count of -1, the fast parser's "capped", draws nothing)
+ *   joint     at (trunc(x), trunc(y)), truncated toward zero; visible iff val > 0, x and y are finite and both truncated
+ *             coordinates lie in [-16384, 16383]
+ *   mark      pixel (px, py) is painted iff (px-cx)^2 + (py-cy)^2 <= Rj^2 (Rj = 2: 13 pixels; stands for
+ *             cv2.circle(radius 1, thickness 2))
+ *   link a-b  drawn iff a < J, b < J and both joints are visible; a pixel is painted iff its squared distance to the
+ *             segment AB is <= Rl^2 (Rl = 1 stands for thickness 2), evaluated exactly: with d = AP.AB, L = |AB|^2:
+ *             d <= 0: |AP|^2 <= Rl^2; d >= L: |BP|^2 <= Rl^2; otherwise cross(AP, AB)^2 <= Rl^2 L
+ *   colour    person p takes h_palette[p % n_colors] (3 bytes, written as given); where persons overlap the highest
+ *             index wins (the painter's order of the reference's loop)
+ *   images_io [N,H,W,3] uint8 (lp_draw_poses), or N images packed in images_io[0, image_bytes) with
+ *             d_desc [N], a DEVICE table read when the launch runs (lp_draw_poses_v; bit-identical per image to
+ *             lp_draw_poses).  A descriptor whose image does not lie inside [0, image_bytes) or whose H or W is outside
+ *             1..16384 is skipped: nothing is read or written for that image.
+ *   d_kpts [N,pcap,J,D] rows (x, y, val, ...), D >= 3 (the engine's records: D = 3 + T; the fast parser's ans: D = 4, num
+ *             as the count); d_count [N]
+ *   h_links [n_links,2] host ints, h_palette [n_colors,3] host bytes: copied into the launch's arguments (a captured
+ *             graph holds them).  A link index >= J is legal and skipped, as in the reference (vis.py:73).
+ * Writes: exactly the covered pixels (3 bytes each) of images_io; every other byte of the buffer is neither read nor
+ * written.
+ * lp_draw_pass_prims (host only): the kernel takes an image's P * (J + n_links) primitives in passes of this many
+ * (0: no passes).
+ * LP_ERR_INVALID_ARG: a null pointer, N < 1, H or W outside 1..16384 (lp_draw_poses), image_bytes < 1 (lp_draw_poses_v),
+ * pcap < 1, D < 3, a negative link index.  LP_ERR_UNSUPPORTED: J outside 1..32, n_links outside 0..64, n_colors outside
+ * 1..32, Rj or Rl outside 0..8.  Every refusal is answered before any pointer is dereferenced (h_links is read after
+ * the sizes are accepted).
+ * images_io is DEVICE memory like every d_* pointer of this header; like count_out and score_out it does not carry the
+ * prefix because the census of writable calls (tests/test_poison_cpu.py) keys on it; its contract test is
+ * tests/test_gpu_vis.py.                                                                       */
+typedef struct lp_image_desc {
+    int64_t offset;       /* byte offset of the image's [H,W,3] uint8 pixels in the packed buffer */
+    int32_t H, W;
+} lp_image_desc;
+int lp_draw_poses(uint8_t* images_io, int N, int H, int W, const float* d_kpts, const int32_t* d_count,
+                  int pcap, int J, int D, const int32_t* h_links, int n_links,
+                  const uint8_t* h_palette, int n_colors, int Rj, int Rl, void* stream);
+int lp_draw_poses_v(uint8_t* images_io, size_t image_bytes, const lp_image_desc* d_desc, int N,
+                    const float* d_kpts, const int32_t* d_count, int pcap, int J, int D,
+                    const int32_t* h_links, int n_links, const uint8_t* h_palette, int n_colors,
+                    int Rj, int Rl, void* stream);
+int lp_draw_pass_prims(void);
+
 /* Recovery after a failed hipGraph capture (another host thread's HIP call can invalidate a capture in progress,
  * e.g. the RCCL watchdog of torch.distributed polling events): if `stream` is still in capture mode, end the capture,
  * drop the partial graph and clear this thread's sticky HIP error, so that eager launches on the stream work again.

@@ -49,6 +49,11 @@ class LpWarpDesc(C.Structure):
     _fields_ = [('src_offset', C.c_int64), ('H', C.c_int32), ('W', C.c_int32), ('minv', C.c_double * 6)]
 
 
+class LpImageDesc(C.Structure):
+    """lp_image_desc: one row (16 bytes) of the device descriptor table of lp_draw_poses_v."""
+    _fields_ = [('offset', C.c_int64), ('H', C.c_int32), ('W', C.c_int32)]
+
+
 class LpScaleMid(C.Structure):
     """lp_scale_mid: one scale (16 bytes) of lp_tta_merge_scales."""
     _fields_ = [('mid', C.c_void_p), ('h1', C.c_int32), ('w1', C.c_int32)]
@@ -121,6 +126,11 @@ _SIGS = {
                             vp, vp, vp, sz, vp]),
     'lp_kpt_eval': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_double),
                           C.POINTER(C.c_double), i32, C.POINTER(C.c_double), i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    'lp_draw_poses': (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, C.POINTER(C.c_int32), i32,
+                            C.POINTER(C.c_uint8), i32, i32, i32, vp]),
+    'lp_draw_poses_v': (i32, [vp, sz, vp, i32, vp, vp, i32, i32, i32, C.POINTER(C.c_int32), i32,
+                              C.POINTER(C.c_uint8), i32, i32, i32, vp]),
+    'lp_draw_pass_prims': (i32, []),
     'lp_preprocess': (i32, [vp, i32, i32, C.POINTER(C.c_double), i32, i32, C.POINTER(C.c_float),
                             C.POINTER(C.c_float), vp, vp, vp]),
     'lp_preprocess_batch': (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), i32, i32, C.POINTER(C.c_float),

@@ -45,6 +45,8 @@ SOURCES = [
     ('fast_kernels.hip', ['-ffp-contract=off'] + NOPK),    # the compiled reference's fp32 / fp64 operations, one by one
     ('eval_api.cpp', ['-ffp-contract=off']),               # the host tables of the launch: (2 sigma)^2 as NumPy rounds it
     ('eval_kernels.hip', ['-ffp-contract=off'] + NOPK),    # COCOeval's fp64 expressions, one IEEE operation each
+    ('vis_api.cpp', []),
+    ('vis_kernels.hip', NOPK),                             # integer raster; floats are only loaded, compared, truncated
 ]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value',
           '-Wno-pass-failed']

@@ -333,4 +333,20 @@ void launch_kpt_eval(const float* ans, const int* count, const float* scores, in
                      int max_dets, float* score_out, int* num_out, int* src_out, unsigned* match_out,
                      unsigned* ignore_out, double* oks_out, hipStream_t s);
 
+// ---- utils.vis: skeletons drawn into uint8 HWC images (vis_kernels.hip; the raster rule is DESIGN.md 4c) ------
+struct ImageDesc {                          // lp_image_desc (include/litepose_amd.h)
+    long long offset;
+    int H, W;
+};
+struct VisTables {                          // the link table and the palette, passed to the kernel by value
+    unsigned char la[64], lb[64];           // link l joins joints la[l] and lb[l] (an index >= J: skipped)
+    unsigned char pal[96];                  // 32 colours of 3 bytes
+};
+constexpr int VIS_PASS_PRIMS = 512;         // primitives resolved per pass into the 8 KB LDS table of a workgroup
+// desc == nullptr: N images [N,H,W,3]; otherwise N images at desc[n] inside images[0, bytes).  links: n_links host pairs,
+// palette: n_colors host byte triples, both copied into the launch's arguments.  Sizes are checked by the caller.
+void launch_draw_poses(unsigned char* images, long long bytes, const ImageDesc* desc, int N, int H, int W,
+                       const float* kpts, const int* count, int pcap, int J, int D, const int* links, int n_links,
+                       const unsigned char* palette, int n_colors, int Rj, int Rl, hipStream_t s);
+
 }  // namespace lp

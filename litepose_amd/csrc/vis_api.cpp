@@ -1,0 +1,65 @@
+// C ABI of utils.vis (include/litepose_amd.h, "drawing"): argument validation; the kernel lives in vis_kernels.hip.
+#include <hip/hip_runtime.h>
+
+#include "../../include/litepose_amd.h"
+#include "kernels.h"
+
+extern "C" void lp_set_error_(const char* msg);   // engine.cpp owns the thread-local slot
+
+static_assert(sizeof(lp_image_desc) == sizeof(lp::ImageDesc) && sizeof(lp_image_desc) == 16, "lp_image_desc layout");
+
+namespace {
+int fail(int code, const char* msg) {
+    lp_set_error_(msg);
+    return code;
+}
+
+// every refusal of both forms that needs no device; h_links is read last, once n_links is known to be its length
+int check_draw(int N, int pcap, int J, int D, const int32_t* h_links, int n_links, int n_colors, int Rj, int Rl) {
+    if (N < 1) return fail(LP_ERR_INVALID_ARG, "N must be positive");
+    if (pcap < 1) return fail(LP_ERR_INVALID_ARG, "pcap must be positive");
+    if (J < 1 || J > 32) return fail(LP_ERR_UNSUPPORTED, "J must be 1..32");
+    if (D < 3) return fail(LP_ERR_INVALID_ARG, "D must be >= 3: a row is (x, y, val, ...)");
+    if (n_links < 0 || n_links > 64) return fail(LP_ERR_UNSUPPORTED, "n_links must be 0..64");
+    if (n_colors < 1 || n_colors > 32) return fail(LP_ERR_UNSUPPORTED, "n_colors must be 1..32");
+    if (Rj < 0 || Rj > 8 || Rl < 0 || Rl > 8) return fail(LP_ERR_UNSUPPORTED, "Rj and Rl must be 0..8");
+    for (int i = 0; i < 2 * n_links; ++i)
+        if (h_links[i] < 0) return fail(LP_ERR_INVALID_ARG, "link index must be >= 0");
+    return LP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int lp_draw_pass_prims(void) { return lp::VIS_PASS_PRIMS; }
+
+int lp_draw_poses(uint8_t* images_io, int N, int H, int W, const float* d_kpts, const int32_t* d_count, int pcap, int J,
+                  int D, const int32_t* h_links, int n_links, const uint8_t* h_palette, int n_colors, int Rj, int Rl,
+                  void* stream) {
+    if (!images_io || !d_kpts || !d_count || !h_links || !h_palette) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (H < 1 || W < 1 || H > 16384 || W > 16384) return fail(LP_ERR_INVALID_ARG, "H and W must be 1..16384");
+    const int rc = check_draw(N, pcap, J, D, h_links, n_links, n_colors, Rj, Rl);
+    if (rc) return rc;
+    lp::launch_draw_poses(images_io, 0, nullptr, N, H, W, d_kpts, d_count, pcap, J, D, h_links, n_links, h_palette,
+                          n_colors, Rj, Rl, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "draw_poses launch failed");
+    return LP_OK;
+}
+
+int lp_draw_poses_v(uint8_t* images_io, size_t image_bytes, const lp_image_desc* d_desc, int N, const float* d_kpts,
+                    const int32_t* d_count, int pcap, int J, int D, const int32_t* h_links, int n_links,
+                    const uint8_t* h_palette, int n_colors, int Rj, int Rl, void* stream) {
+    if (!images_io || !d_desc || !d_kpts || !d_count || !h_links || !h_palette)
+        return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (image_bytes < 1 || image_bytes > (size_t)INT64_MAX)
+        return fail(LP_ERR_INVALID_ARG, "image_bytes must be 1..INT64_MAX");
+    const int rc = check_draw(N, pcap, J, D, h_links, n_links, n_colors, Rj, Rl);
+    if (rc) return rc;
+    lp::launch_draw_poses(images_io, (long long)image_bytes, reinterpret_cast<const lp::ImageDesc*>(d_desc), N, 0, 0,
+                          d_kpts, d_count, pcap, J, D, h_links, n_links, h_palette, n_colors, Rj, Rl,
+                          (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "draw_poses_v launch failed");
+    return LP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,425 @@
+"""utils.vis on the device (lp_draw_poses / lp_draw_poses_v, csrc/vis_kernels.hip; litepose_amd.utils.vis and
+litepose_amd.demo.process) against the NumPy restatement of the raster rule in tests/_vis_ref.py, bitwise: every
+output byte is either a palette byte or the input byte, so there is no tolerance anywhere in this file.  The rule itself
+is the library's own and is not pinned against cv2."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import _poison as po
+import _vis_ref as vr
+from litepose_amd import _native as nv
+from litepose_amd.utils import vis
+
+pytestmark = pytest.mark.gpu
+
+COCO = vis.VIS_CONFIG['COCO']['links']
+CROWD = vis.VIS_CONFIG['CROWDPOSE']['links']
+RED = [(0, 0, 255)]
+PAL3 = [(0, 0, 255), (10, 200, 30), (255, 128, 1)]
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _tables(links, palette):
+    flat = [int(v) for ab in links for v in ab]
+    pal = [int(v) for c in palette for v in c]
+    return (C.c_int32 * max(len(flat), 1))(*flat), (C.c_uint8 * len(pal))(*pal)
+
+
+def run_draw(images, kpts, count, links, palette=RED, Rj=2, Rl=1):
+    """images [N,H,W,3] uint8 device tensor, drawn in place."""
+    N, H, W, _ = images.shape
+    _, pcap, J, D = kpts.shape
+    l_c, p_c = _tables(links, palette)
+    nv.check(nv.lib().lp_draw_poses(nv.dptr(images), N, H, W, nv.dptr(kpts), nv.dptr(count), pcap, J, D, l_c, len(links),
+                                    p_c, len(palette), Rj, Rl, nv.stream_ptr()), 'lp_draw_poses')
+    return images
+
+
+def run_draw_v(buf, desc, kpts, count, links, palette=RED, Rj=2, Rl=1):
+    N, pcap, J, D = kpts.shape
+    l_c, p_c = _tables(links, palette)
+    nv.check(nv.lib().lp_draw_poses_v(nv.dptr(buf), buf.numel(), nv.dptr(desc), N, nv.dptr(kpts), nv.dptr(count), pcap,
+                                      J, D, l_c, len(links), p_c, len(palette), Rj, Rl, nv.stream_ptr()),
+             'lp_draw_poses_v')
+    return buf
+
+
+def background(N, H, W, seed=0):
+    return np.random.default_rng(seed).integers(0, 256, size=(N, H, W, 3), dtype=np.uint8)
+
+
+def check_batch(images, kpts, count, links, palette=RED, Rj=2, Rl=1, what=''):
+    """Draw the NumPy batch on the device and hold every image to the reference; returns the covered-pixel masks."""
+    got = run_draw(dev(images), dev(kpts), dev(count), links, palette, Rj, Rl).cpu().numpy()
+    masks = []
+    for n in range(images.shape[0]):
+        want, m = vr.draw(images[n], kpts[n], count[n], links, palette, Rj, Rl)
+        bad = np.argwhere((got[n] != want).any(axis=2))
+        assert bad.size == 0, (what, n, 'first differing pixel (y, x)', bad[0].tolist(), len(bad))
+        masks.append(m)
+    return masks
+
+
+# 17 hand-placed joints of a standing figure in a 20 x 36 box (x, y), COCO order; the first 14 serve CrowdPose
+FIGURE = np.array([[10, 3], [12, 2], [8, 2], [14, 3], [6, 3], [15, 9], [5, 9], [18, 15], [2, 15], [19, 21], [1, 21],
+                   [13, 20], [7, 20], [14, 28], [6, 28], [15, 35], [5, 35]], np.float32)
+
+
+def figure(J, dx, dy, val=1.0, D=3):
+    k = np.zeros((J, D), np.float32)
+    k[:, :2] = FIGURE[:J] + np.float32([dx, dy])
+    k[:, 2] = val
+    return k
+
+
+@pytest.mark.parametrize('J,links', [(17, COCO), (14, CROWD)])
+def test_two_hand_placed_persons(J, links):
+    H, W = 40, 56
+    k = np.zeros((1, 2, J, 3), np.float32)
+    k[0, 0] = figure(J, 3.6, 1.2)
+    k[0, 1] = figure(J, 30.2, 2.9, val=0.3)
+    masks = check_batch(background(1, H, W), k, np.int32([2]), links, what='two persons')
+    assert masks[0][:, :28].sum() > 100 and masks[0][:, 28:].sum() > 100
+
+
+def test_clipping_and_invisible_joints():
+    H, W, J = 50, 70, 17
+    big, nan, inf = 1e9, float('nan'), float('inf')
+    k = np.zeros((1, 8, J, 4), np.float32)
+
+    def put(p, j, x, y, v=1.0):
+        k[0, p, j] = (x, y, v, 7.0)
+    put(0, 0, 0, 0), put(0, 1, W - 1, H - 1)                             # the corners, linked (0, 1)
+    put(1, 0, -1, 10), put(1, 1, W, 20)                                  # marks partly outside, the link crosses
+    put(1, 5, -10, -10), put(1, 6, W + 5, H + 7)                         # wholly outside; the link (5, 6) is the diagonal
+    put(1, 11, -3.7, 5.2), put(1, 12, -0.5, 3.9)                         # negative coordinates truncate toward zero
+    put(2, 5, -16384, 16383), put(2, 6, 20, 20)                          # one end as far outside as a joint may lie
+    put(2, 11, 16383.5, -16384.9), put(2, 12, 40, 30)                    # the other far corner (still in range)
+    put(3, 0, 10, 10, 0.0), put(3, 1, 20, 10, -1.0), put(3, 2, 30, 10, nan)   # val <= 0 or NaN: invisible
+    put(3, 11, 10, 30), put(3, 12, 30, 30, 0.0), put(3, 13, 12, 44)      # link (11, 12): one invisible end; (11, 13) drawn
+    put(4, 0, nan, 10), put(4, 1, 25, 12), put(4, 2, 30, inf)            # NaN / inf / 1e9 coordinates are skipped,
+    put(4, 5, big, 20), put(4, 6, 35, 22), put(4, 7, 50, -big), put(4, 8, -inf, 5)   # with the links that end there
+    put(5, 5, -16385, 20), put(5, 6, 16384, 20), put(5, 7, 40, 40)       # one past the range on either side
+    put(5, 11, 60, 16384.0), put(5, 12, 60, -16385.0), put(5, 13, 60, 45)
+    put(6, 3, 35, 25), put(6, 5, 45, 25)                                 # (3, 5) is a COCO link
+    masks = check_batch(background(1, H, W, 1), k, np.int32([7]), COCO, PAL3, what='clipping')
+    m = masks[0]
+    assert m[0, 0] and m[H - 1, W - 1] and m[20, 20] and m[30, 40] and m[37, 11] and not m[10, 18:23].any()
+    # the same records with other radii, 0 included (a single pixel / a one-pixel line)
+    for Rj, Rl in ((0, 0), (3, 2), (8, 8), (1, 0)):
+        check_batch(background(1, H, W, 1), k, np.int32([7]), COCO, PAL3, Rj, Rl, what=('radii', Rj, Rl))
+    # J = 14 with the COCO table: links that name joints 14..16 are legal and skipped
+    k14 = np.ascontiguousarray(k[:, :, :14])
+    k14[0, 7] = figure(14, 40, 8, D=4)
+    m14 = check_batch(background(1, H, W, 2), k14, np.int32([8]), COCO, PAL3, what='J = 14, COCO table')[0]
+    assert m14[8:44, 40:60].sum() > 60
+    # a table that also names far larger indices, and links of a joint with itself
+    check_batch(background(1, H, W, 2), k14, np.int32([8]), [(0, 1), (1, 255), (300, 2), (2 ** 31 - 1, 0), (5, 5), (6, 7)],
+                PAL3, what='huge link indices')
+
+
+def test_32_joints_and_64_links():
+    rng = np.random.default_rng(5)
+    H, W, J = 64, 80, 32
+    links = [(int(a), int(b)) for a, b in rng.integers(0, 32, size=(64, 2))]
+    k = np.zeros((2, 3, J, 5), np.float32)
+    k[..., 0] = rng.uniform(-20, W + 20, size=k.shape[:3])
+    k[..., 1] = rng.uniform(-20, H + 20, size=k.shape[:3])
+    k[..., 2] = rng.uniform(-0.3, 1.0, size=k.shape[:3])
+    k[..., 3:] = np.nan                                                  # the tags are not read
+    check_batch(background(2, H, W, 3), k, np.int32([3, 2]), links, PAL3, what='J = 32, 64 links')
+    check_batch(background(2, H, W, 3), k, np.int32([3, 2]), [], PAL3, what='no links')
+
+
+def crossing(P, J=17, D=3):
+    k = np.zeros((1, P, J, D), np.float32)
+    for p in range(P):
+        k[0, p] = figure(J, 8 + 5 * p, 1 + 1.5 * p, D=D)                    # figures shifted by less than their width
+    return k
+
+
+@pytest.mark.parametrize('P', [2, 3])
+def test_overlap_order_the_highest_person_wins(P):
+    H, W = 44, 48
+    k = crossing(P)
+    img = background(1, H, W, 4)
+    masks = [vr.draw(img[0], k[0, p:p + 1], 1, COCO)[1] for p in range(P)]
+    assert all((masks[p] & masks[p + 1]).sum() > 10 for p in range(P - 1))      # they really cross
+    check_batch(img, k, np.int32([P]), COCO, PAL3, what='3 colours')
+    check_batch(img, k, np.int32([P]), COCO, PAL3[:2], what='2 colours: person 2 wraps to colour 0')
+    check_batch(img, k, np.int32([P]), COCO, RED, what='one colour')
+
+
+def test_counts_zero_capped_full_and_beyond_capacity():
+    H, W, pcap = 44, 48, 3
+    k = np.repeat(crossing(pcap), 5, axis=0)
+    count = np.int32([0, -1, pcap, pcap + 5, 1])
+    img = background(5, H, W, 6)
+    masks = check_batch(img, k, count, COCO, PAL3, what='counts')
+    assert not masks[0].any() and not masks[1].any() and np.array_equal(masks[2], masks[3]) and masks[2].sum() > masks[4].sum() > 0
+
+
+SIZES = [(1, 1), (1, 300), (7, 3), (33, 65), (64, 16), (100, 100)]
+
+
+def packed_scene(seed, gap=37):
+    """Six images of different sizes in one buffer with `gap` bytes between them (and before the first / after the last);
+    two persons per image scaled into it."""
+    rng = np.random.default_rng(seed)
+    offs, off = [], gap
+    for h, w in SIZES:
+        offs.append(off)
+        off += h * w * 3 + gap
+    buf = rng.integers(0, 256, size=off, dtype=np.uint8)
+    J = 17
+    k = np.zeros((len(SIZES), 2, J, 3), np.float32)
+    for n, (h, w) in enumerate(SIZES):
+        for p in range(2):
+            f = figure(J, 0, 0)
+            k[n, p, :, 0] = f[:, 0] * (w / 20.0) * (0.9 - 0.3 * p) + p
+            k[n, p, :, 1] = f[:, 1] * (h / 36.0) * (0.7 + 0.4 * p) - p
+            k[n, p, :, 2] = 1.0
+    return buf, offs, k, np.int32([2] * len(SIZES))
+
+
+def desc_table(rows):
+    d = np.zeros(len(rows), vis.IMAGE_DESC_DTYPE)
+    for i, r in enumerate(rows):
+        d[i] = r
+    return dev(d.view(np.uint8).reshape(len(rows), 16))
+
+
+def test_packed_images_of_different_sizes_in_one_launch():
+    buf, offs, k, count = packed_scene(7)
+    rows = [(o, h, w) for o, (h, w) in zip(offs, SIZES)]
+    got = run_draw_v(dev(buf), desc_table(rows), dev(k), dev(count), COCO, PAL3).cpu().numpy()
+    want = buf.copy()
+    for n, (o, h, w) in enumerate(rows):
+        src = buf[o:o + h * w * 3].reshape(1, h, w, 3)
+        ref, m = vr.draw(src[0], k[n], count[n], COCO, PAL3)
+        assert m.any(), n
+        want[o:o + h * w * 3] = ref.reshape(-1)
+        # the plain form on this image alone gives the same bytes
+        one = run_draw(dev(src), dev(k[n:n + 1]), dev(count[n:n + 1]), COCO, PAL3).cpu().numpy()
+        assert np.array_equal(one[0], ref), ('lp_draw_poses', n)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, ('lp_draw_poses_v: first differing byte', int(bad[0]), len(bad))     # the gaps included
+    # one descriptor that reaches past the buffer, one that starts past it, a negative offset, H = 0, W too large: those
+    # images stay as they were, the others are drawn as before
+    total = buf.size
+    broken = list(rows)
+    broken[5] = (total - 100 * 100 * 3 + 1, 100, 100)
+    broken[3] = (offs[3], 0, 65)
+    got = run_draw_v(dev(buf), desc_table(broken), dev(k), dev(count), COCO, PAL3).cpu().numpy()
+    keep = want.copy()
+    for n in (3, 5):
+        o, h, w = rows[n]
+        keep[o:o + h * w * 3] = buf[o:o + h * w * 3]
+    assert np.array_equal(got, keep)
+    for row in ((total + 5, 1, 1), (-3, 7, 3), (offs[2], 7, 16385), (offs[2], -1, 3), (total, 1, 1)):
+        broken = list(rows)
+        broken[2] = row
+        got = run_draw_v(dev(buf), desc_table(broken), dev(k), dev(count), COCO, PAL3).cpu().numpy()
+        keep = want.copy()
+        o, h, w = rows[2]
+        keep[o:o + h * w * 3] = buf[o:o + h * w * 3]
+        assert np.array_equal(got, keep), row
+    # annotate_batch(sizes=...) on images packed back to back is the same launch
+    tight = np.concatenate([buf[o:o + h * w * 3] for o, h, w in rows])
+    t = vis.annotate_batch(dev(tight), dev(k), dev(count), dataset='COCO', palette=PAL3, sizes=SIZES).cpu().numpy()
+    assert np.array_equal(t, np.concatenate([want[o:o + h * w * 3] for o, h, w in rows]))
+
+
+def dense_marks(seed, N, pcap, H, W):
+    rng = np.random.default_rng(seed)
+    k = np.zeros((N, pcap, 1, 3), np.float32)
+    k[..., 0] = rng.uniform(-2, W + 2, size=(N, pcap, 1))
+    k[..., 1] = rng.uniform(-2, H + 2, size=(N, pcap, 1))
+    k[..., 2] = rng.uniform(-0.1, 1.0, size=(N, pcap, 1))
+    return k
+
+
+def test_pass_boundary_of_the_primitive_list():
+    c = int(nv.lib().lp_draw_pass_prims())
+    if c == 0:
+        pytest.skip('the kernel does not work in passes')
+    H = W = 48
+    k = dense_marks(11, 4, 2 * c + 1, H, W)                              # J = 1, no links: primitives = persons
+    count = np.int32([c - 1, c, c + 1, 2 * c + 1])
+    masks = check_batch(background(4, H, W, 8), k, count, [], PAL3, Rj=3, what='pass boundary')
+    assert all(m.mean() > 0.9 for m in masks)                            # dense: nearly every pixel has several owners
+
+
+def test_thirty_persons_of_36_primitives():
+    H, W, P = 96, 100, 30
+    rng = np.random.default_rng(12)
+    k = np.zeros((1, P, 17, 3), np.float32)
+    for p in range(P):
+        k[0, p] = figure(17, rng.uniform(-5, W - 15), rng.uniform(-5, H - 30), val=1.0)
+        k[0, p, rng.integers(0, 17, size=3), 2] = 0.0
+    check_batch(background(1, H, W, 9), k, np.int32([P]), COCO, PAL3, what='30 persons')
+
+
+def test_buffer_contract_with_poisoned_and_guarded_buffers():
+    """Writes: exactly the covered pixels.  The image buffer sits between guard bands and holds a poison pattern; every
+    byte outside the reference mask must still hold it, the guards must be intact, and the records and counts must be
+    unchanged and not over-read (their guards hold the pattern: NaN or a huge value would move or add a mark)."""
+    N, H, W = 3, 44, 48
+    k = np.repeat(crossing(3, D=5), N, axis=0)
+    k[..., 3:] = 0.25
+    count = np.int32([3, -1, 2])
+    colours = [(1, 2, 3), (4, 5, 6), (8, 9, 10)]                         # no byte of the palette equals a pattern byte
+    for pattern in po.PATTERNS:
+        arena = po.Arena(pattern)
+        images = arena.out((N, H, W, 3), torch.uint8, align=1, what='images')
+        kd, cd = arena.inp(dev(k), align=4, what='kpts'), arena.inp(dev(count), align=4, what='count')
+        run_draw(images, kd, cd, COCO, colours)
+        arena.check()
+        got = images.cpu().numpy()
+        fill = np.full((H, W, 3), po.pattern_byte(pattern), np.uint8)
+        for n in range(N):
+            want, m = vr.draw(fill, k[n], count[n], COCO, colours)
+            assert np.array_equal(got[n], want), (pattern, n)
+            assert (got[n][~m] == po.pattern_byte(pattern)).all() and (got[n][m] != po.pattern_byte(pattern)).all()
+        # the packed form: the whole buffer is one placement, the images lie inside it with gaps
+        gap = 19
+        arena = po.Arena(pattern)
+        buf = arena.ws(N * (H * W * 3 + gap) + gap, align=1, what='packed images')
+        rows = [(gap + n * (H * W * 3 + gap), H, W) for n in range(N)]
+        run_draw_v(buf, arena.inp(desc_table(rows), align=8, what='desc'), arena.inp(dev(k), align=4, what='kpts'),
+                   arena.inp(dev(count), align=4, what='count'), COCO, colours)
+        arena.check()
+        gotv = buf.cpu().numpy()
+        wantv = np.full(buf.numel(), po.pattern_byte(pattern), np.uint8)
+        for n, (o, _, _) in enumerate(rows):
+            wantv[o:o + H * W * 3] = got[n].reshape(-1)
+        assert np.array_equal(gotv, wantv), pattern
+
+
+def test_replayed_from_a_captured_graph_gives_the_same_bytes():
+    N, H, W = 2, 44, 48
+    k, count = dev(np.repeat(crossing(3), N, axis=0)), dev(np.int32([3, 2]))
+    clean = dev(background(N, H, W, 10))
+    images = clean.clone()
+    run_draw(images, k, count, COCO, PAL3)
+    torch.cuda.synchronize()
+    eager = images.clone()
+    assert not torch.equal(eager, clean)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        run_draw(images, k, count, COCO, PAL3)
+    for _ in range(2):
+        images.copy_(clean)
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(images, eager)
+
+
+def test_get_annotated_image_and_add_joints():
+    H, W = 44, 48
+    rgb = background(1, H, W, 13)[0]
+    joints = crossing(2, J=14)[0]
+    want, m = vr.draw(np.ascontiguousarray(rgb[:, :, ::-1]), joints, 2, CROWD, RED)
+    src = dev(rgb)
+    out = vis.get_annotated_image(src, dev(joints), dataset='CROWDPOSE')
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (H, W, 3)
+    assert np.array_equal(out.cpu().numpy(), want) and m.any()
+    assert np.array_equal(src.cpu().numpy(), rgb)                        # the input is not modified
+    keep = rgb.copy()
+    host = vis.get_annotated_image(rgb, joints, dataset='CROWDPOSE')     # NumPy in, NumPy out
+    assert isinstance(host, np.ndarray) and np.array_equal(host, want) and np.array_equal(rgb, keep)
+    lst = vis.get_annotated_image(rgb, [joints[0], joints[1]], dataset='CROWDPOSE')      # get_final_preds' list
+    assert np.array_equal(lst, want)
+    assert np.array_equal(vis.get_annotated_image(rgb, [], dataset='CROWDPOSE'), rgb[:, :, ::-1])
+    # add_joints: one person, the caller's colour, in place
+    img = dev(rgb)
+    assert vis.add_joints(img, dev(joints[1]), (9, 8, 7), dataset='CROWDPOSE') is img
+    assert np.array_equal(img.cpu().numpy(), vr.draw(rgb, joints[1:2], 1, CROWD, [(9, 8, 7)])[0])
+
+
+def test_annotate_batch_on_engine_records():
+    """Records as PoseEngine.infer_batch hands them over (search-XS at 64 x 64, synthetic weights, blob offsets)."""
+    from litepose_amd import arch_zoo, config, engine
+    from oracle import inference_ref, synth
+    cfg = config.get_cfg()
+    arch = arch_zoo.get('search-XS')
+    eng = engine.PoseEngine(cfg, arch, synth.make_state_dict(arch, seed=1234))
+    N, R = 2, 64
+    x = synth.make_images(N, R, seed=21).cuda()
+    off0, off1 = synth.lowres_offsets(33, N, 14, R, people=[3, 2])
+    f0, f1 = synth.flip_offsets(off0, off1, inference_ref.FLIP_CONFIG['CROWDPOSE'])
+    offs = (dev(np.concatenate([off0, f0])), dev(np.concatenate([off1, f1])))
+    ans, count, _ = eng.infer_batch(x, offsets=offs)
+    assert ans.dim() == 4 and ans.shape[2] == 14 and ans.shape[3] == 5
+    img = background(N, R, R, 14)
+    got = vis.annotate_batch(dev(img), ans, count, dataset='CROWDPOSE', palette=PAL3).cpu().numpy()
+    a, c = ans.cpu().numpy(), count.cpu().numpy()
+    assert (c > 0).all()                                                 # the records are non-empty
+    for n in range(N):
+        want, m = vr.draw(img[n], a[n], c[n], CROWD, PAL3)
+        assert m.any() and np.array_equal(got[n], want), n
+
+
+class _Executor(object):
+    """Stands for the network: returns blob maps of two persons at the output resolutions of a 64 x 64 input."""
+
+    def __init__(self):
+        from oracle import synth
+        off0, off1 = synth.lowres_offsets(8, 1, 14, 64, people=[2])
+        self.outs = (dev(off0), dev(off1))
+        self.seen = []
+
+    def __call__(self, x):
+        self.seen.append(x.clone())
+        return self.outs
+
+
+class _CappedParser(object):
+    """A parser whose image hit the assignment's round cap: num = -1 and an all-zero record."""
+
+    def parse_batch(self, det, tmap, scale=1.0):
+        ans = torch.zeros((det.shape[0], 10, det.shape[1], 4), device=det.device)
+        ans[:, :, :, :3] = 20.0                                          # would be drawn if num were read as positive
+        return ans, torch.full((det.shape[0],), -1, dtype=torch.int32, device=det.device)
+
+
+def test_demo_process_on_the_device():
+    from litepose_amd import config, demo
+    from litepose_amd.utils import transforms
+    cfg = config.get_cfg()
+    cfg.DATASET.INPUT_SIZE, cfg.DATASET.OUTPUT_SIZE = 64, [16, 32]
+    cfg.DATASET.MAX_NUM_PEOPLE = 10
+    cfg.TEST.FLIP_TEST = False
+    H, W, res = 96, 128, 64
+    frame = background(1, H, W, 15)[0]                                   # BGR
+    crop = frame[0:96, 16:112]
+    ex = _Executor()
+    out, ans, num = demo.process(cfg, frame, ex, res=res, return_records=True)
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (96, 96, 3)
+    assert tuple(ans.shape) == (10, 14, 4) and num.dtype == torch.int32
+    # the network saw the RGB crop, resized and normalised
+    rgb = np.ascontiguousarray(crop[:, :, ::-1])
+    u8, _, _ = transforms.resize_align_multi_scale(rgb, 64, 1.0, 1.0)
+    assert len(ex.seen) == 1 and tuple(ex.seen[0].shape) == (1, 3, 64, 64)
+    assert torch.equal(ex.seen[0][0], transforms.ToTensorNormalize()(u8))
+    a, n = ans.cpu().numpy(), int(num[0])
+    assert n >= 1
+    want, m = vr.draw(np.ascontiguousarray(crop), a, n, CROWD, RED)      # drawn in BGR: the crop of the frame itself
+    got = out.cpu().numpy()
+    assert m.any() and np.array_equal(got[~m], crop[~m]) and np.array_equal(got, want)
+    assert (a[:n, :, :2].max() > 64)                                     # the records are in crop pixels (scale 96 / 64)
+    # a host tensor and a device tensor give the same image; a reused parser too
+    from litepose_amd.fast_utils.group import HeatmapParser
+    again = demo.process(cfg, torch.from_numpy(frame).cuda(), _Executor(), parser=HeatmapParser(cfg), res=res)
+    assert torch.equal(again, out)
+    # num = -1: the plain crop, no exception
+    capped = demo.process(cfg, frame, _Executor(), parser=_CappedParser(), res=res)
+    assert np.array_equal(capped.cpu().numpy(), crop)

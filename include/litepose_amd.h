@@ -582,6 +582,39 @@ int lp_preprocess_batch_v(const uint8_t* d_src, size_t src_bytes, const lp_warp_
                           const float* h_mean, const float* h_std, uint8_t* d_resized_u8, float* d_tensor,
                           void* stream);
 
+/* Per-image source, transform and mirror of lp_augment_batch_v: 72 bytes, no implicit padding (8 + 4 + 4 + 6 * 8 + 4 + 4).
+ *   src_offset, H, W   as lp_warp_desc
+ *   minv               the INVERTED (dst -> src) 2x3 matrix: lp_warp_invert of RandomAffineTransform's mat_input (a general
+ *                      matrix: rotation, scale and translation)
+ *   flip               != 0: output column x takes warped column Wd - 1 - x (RandomHorizontalFlip on the warped image)
+ *   reserved           must be 0                                                                                       */
+typedef struct lp_aug_desc {
+    int64_t src_offset;
+    int32_t H, W;
+    double minv[6];
+    int32_t flip, reserved;
+} lp_aug_desc;
+
+/* The image side of the train loader for a batch (lib/dataset/transforms/transforms.py:54-182, build.py:67-83:
+ * RandomAffineTransform's cv2.warpAffine, RandomHorizontalFlip's image[:, ::-1] on the warped uint8 image, ToTensor +
+ * Normalize): ONE launch, no workspace, no allocation, no synchronisation, capturable in a hipGraph.
+ *   d_src, src_bytes, N, Hd, Wd, h_mean, h_std   as lp_preprocess_batch_v
+ *   d_desc [N]       DEVICE table of lp_aug_desc, read when the launch runs
+ *   resized_out      [N,Hd,Wd,3] uint8 warped (and mirrored) images, may be NULL
+ *   tensor_out       [N,3,Hd,Wd] float32 network input, may be NULL (not both)
+ * flip = 0: bit-identical per image to lp_preprocess_batch_v with the same minv.  flip != 0: exactly that result mirrored
+ * along W, by index on the same fixed-point warp (a mirror folded into the matrix would round cv2's column tables
+ * differently).  A descriptor whose image does not lie inside [0, src_bytes), whose H or W is outside 1..32767 or whose
+ * reserved field is not 0 yields zeros for that image and reads nothing.
+ * Writes: every element of each output given.
+ * LP_ERR_INVALID_ARG: a null pointer (one of the two outputs excepted), N outside 1..65535, src_bytes < 1, Hd or Wd outside
+ * 1..32767, a std that is not positive.  Every refusal is answered before any pointer is dereferenced.
+ * resized_out / tensor_out are DEVICE memory; like the fast parser's and lp_kpt_eval's outputs they do not carry the d_
+ * prefix because the census of writable calls (tests/test_poison_cpu.py) keys on it; their contract test is
+ * tests/test_gpu_augment.py.                                                                   */
+int lp_augment_batch_v(const uint8_t* d_src, size_t src_bytes, const lp_aug_desc* d_desc, int N, int Hd, int Wd,
+                       const float* h_mean, const float* h_std, uint8_t* resized_out, float* tensor_out, void* stream);
+
 /* utils.transforms.get_final_preds (lib/utils/transforms.py:195-202,50-56): inverse
  * affine (rot 0) heatmap -> image coordinates, in place on x,y of d_ans.
  * h_center [2], h_scale [2] as returned by get_multi_scale_size, heatmap size (Wp,Hp).

@@ -49,6 +49,12 @@ class LpWarpDesc(C.Structure):
     _fields_ = [('src_offset', C.c_int64), ('H', C.c_int32), ('W', C.c_int32), ('minv', C.c_double * 6)]
 
 
+class LpAugDesc(C.Structure):
+    """lp_aug_desc: one row (72 bytes) of the device descriptor table of lp_augment_batch_v."""
+    _fields_ = [('src_offset', C.c_int64), ('H', C.c_int32), ('W', C.c_int32), ('minv', C.c_double * 6),
+                ('flip', C.c_int32), ('reserved', C.c_int32)]
+
+
 class LpImageDesc(C.Structure):
     """lp_image_desc: one row (16 bytes) of the device descriptor table of lp_draw_poses_v."""
     _fields_ = [('offset', C.c_int64), ('H', C.c_int32), ('W', C.c_int32)]
@@ -138,6 +144,7 @@ _SIGS = {
     'lp_warp_invert': (i32, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'lp_preprocess_batch_v': (i32, [vp, sz, vp, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp,
                                     vp]),
+    'lp_augment_batch_v': (i32, [vp, sz, vp, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp, vp]),
     'lp_stream_abort_capture': (i32, [vp]),
     'lp_final_preds': (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                              i32, i32, vp]),

@@ -366,6 +366,21 @@ int lp_preprocess_batch_v(const uint8_t* d_src, size_t src_bytes, const lp_warp_
     return LP_OK;
 }
 
+int lp_augment_batch_v(const uint8_t* d_src, size_t src_bytes, const lp_aug_desc* d_desc, int N, int Hd, int Wd,
+                       const float* h_mean, const float* h_std, uint8_t* resized_out, float* tensor_out, void* stream) {
+    if (!d_src || !d_desc || !h_mean || !h_std) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (N < 1 || N > 65535) return fail(LP_ERR_INVALID_ARG, "N must be 1..65535");
+    if (!resized_out && !tensor_out) return fail(LP_ERR_INVALID_ARG, "no output requested");
+    if (src_bytes < 1 || src_bytes > (size_t)INT64_MAX) return fail(LP_ERR_INVALID_ARG, "src_bytes must be 1..INT64_MAX");
+    if (Hd < 1 || Wd < 1 || Hd > 32767 || Wd > 32767) return fail(LP_ERR_INVALID_ARG, "image sizes must be 1..32767");
+    for (int c = 0; c < 3; ++c)
+        if (!(h_std[c] > 0.f)) return fail(LP_ERR_INVALID_ARG, "std must be positive");
+    lp::launch_warp_affine_flip_norm_v(d_src, (long long)src_bytes, reinterpret_cast<const lp::AugDesc*>(d_desc), N, Hd,
+                                       Wd, h_mean, h_std, resized_out, tensor_out, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "augment_v launch failed");
+    return LP_OK;
+}
+
 int lp_stream_abort_capture(void* stream) {
     hipStream_t s = (hipStream_t)stream;
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;

@@ -2218,6 +2218,43 @@ __global__ __launch_bounds__(256) void warp_affine_norm_v_kernel(
                     mean, sd, dst_u8, dst_f32);
 }
 
+// The image side of the train loader (lp_augment_batch_v): RandomAffineTransform's warp, RandomHorizontalFlip on the warped
+// uint8 image, ToTensor + Normalize.  As warp_affine_norm_v_kernel, with a mirror BY INDEX: output column x is warped
+// column Wd - 1 - x of the same fixed-point warp (folding the mirror into the matrix would round cv2's column tables
+// differently).  warp_norm_pixel stores at the column it computes, so it is handed the outputs shifted by x - xs elements:
+// every address it forms lies inside the image's rows.  A descriptor that is out of range (as above) or whose reserved
+// field is not 0 writes zeros and reads nothing.
+__global__ __launch_bounds__(256) void warp_affine_flip_norm_v_kernel(
+    const unsigned char* __restrict__ src, long long src_bytes, const AugDesc* __restrict__ desc, int Hd, int Wd,
+    float mean0, float mean1, float mean2, float std0, float std1, float std2, unsigned char* __restrict__ dst_u8,
+    float* __restrict__ dst_f32) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= Wd) return;
+    const AugDesc& d = desc[blockIdx.z];
+    const long long off = d.src_offset;
+    const int H = d.H, W = d.W;
+    if (dst_u8) dst_u8 += (long)blockIdx.z * Hd * Wd * 3;
+    if (dst_f32) dst_f32 += (long)blockIdx.z * 3 * Hd * Wd;
+    // H, W <= 32767: H * W * 3 < 2^32 cannot overflow the 64-bit products below
+    const bool ok = H >= 1 && W >= 1 && H <= 32767 && W <= 32767 && off >= 0 && off <= src_bytes &&
+                    (long long)H * W * 3 <= src_bytes - off && d.reserved == 0;
+    if (!ok) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (dst_u8) dst_u8[((long)y * Wd + x) * 3 + c] = 0;
+            if (dst_f32) dst_f32[((long)c * Hd + y) * Wd + x] = 0.f;
+        }
+        return;
+    }
+    const int xs = d.flip ? Wd - 1 - x : x;          // the warped column this output column takes
+    if (dst_u8) dst_u8 += (long)(x - xs) * 3;
+    if (dst_f32) dst_f32 += x - xs;
+    const float mean[3] = {mean0, mean1, mean2}, sd[3] = {std0, std1, std2};
+    warp_norm_pixel(src + off, H, W, Hd, Wd, xs, y, d.minv[0], d.minv[1], d.minv[2], d.minv[3], d.minv[4], d.minv[5],
+                    mean, sd, dst_u8, dst_f32);
+}
+
 void launch_warp_affine_norm(const unsigned char* src, int H, int W, int Hd, int Wd, const double* minv,
                              const float* mean, const float* sd, unsigned char* dst_u8, float* dst_f32,
                              hipStream_t s, int nimg) {
@@ -2237,6 +2274,13 @@ void launch_warp_affine_norm_v(const unsigned char* src, long long src_bytes, co
                                hipStream_t s) {
     hipLaunchKernelGGL(warp_affine_norm_v_kernel, dim3((Wd + 255) / 256, Hd, N), dim3(256), 0, s, src, src_bytes, desc,
                        Hd, Wd, mean[0], mean[1], mean[2], sd[0], sd[1], sd[2], dst_u8, dst_f32);
+}
+
+void launch_warp_affine_flip_norm_v(const unsigned char* src, long long src_bytes, const AugDesc* desc, int N, int Hd,
+                                    int Wd, const float* mean, const float* sd, unsigned char* dst_u8, float* dst_f32,
+                                    hipStream_t s) {
+    hipLaunchKernelGGL(warp_affine_flip_norm_v_kernel, dim3((Wd + 255) / 256, Hd, N), dim3(256), 0, s, src, src_bytes,
+                       desc, Hd, Wd, mean[0], mean[1], mean[2], sd[0], sd[1], sd[2], dst_u8, dst_f32);
 }
 
 void launch_final_preds_v(float* ans, const int* count, int N, int pcap, int J, int T, const double* coef,

@@ -306,6 +306,17 @@ void launch_warp_affine_norm_v(const unsigned char* src, long long src_bytes, co
                                hipStream_t s);      // N images of their own sizes / transforms -> [N,...] at (Hd, Wd)
 void launch_final_preds_v(float* ans, const int* count, int N, int pcap, int J, int T, const double* coef,
                           hipStream_t s);           // coef [N,4] = (sx, tx, sy, ty) per image, device
+// per-image source / transform / mirror of launch_warp_affine_flip_norm_v: the layout of lp_aug_desc
+struct AugDesc {
+    long long src_offset;   // as WarpDesc
+    int H, W;
+    double minv[6];
+    int flip, reserved;     // flip != 0: output column x takes warped column Wd - 1 - x; reserved must be 0
+};
+static_assert(sizeof(AugDesc) == 72, "AugDesc must match lp_aug_desc (72 bytes)");
+void launch_warp_affine_flip_norm_v(const unsigned char* src, long long src_bytes, const AugDesc* desc, int N, int Hd,
+                                    int Wd, const float* mean, const float* sd, unsigned char* dst_u8, float* dst_f32,
+                                    hipStream_t s);  // the train loader's image side: warp, mirror, ToTensor + Normalize
 
 // ---- the reference's real-time parser (nano_demo/fast_utils; fast_kernels.hip) ------
 // find_peaks: the first M peaks of every plane in raster order; tmap is read at (plane * H * W + y * W + x) * tstride

@@ -690,6 +690,27 @@ class PoseEngine(object):
             ln['graphs'].clear()
             ln['seen'].clear()
 
+    def close(self):
+        """Give back everything this engine holds on the device: the buffers and captured graphs of every shape in every
+        buffer set, the buffer sets' streams and the network handle.  Synchronises first.  The engine cannot be used
+        afterwards (a loop that builds one engine per candidate network, arch_search.AccuracyEvaluator, calls this so that
+        hundreds of candidates do not accumulate)."""
+        torch.cuda.synchronize()
+        for ln in (self._lanes or []):
+            ln['graphs'].clear()
+            ln['seen'].clear()
+            ln['eng']._bufs.clear()
+            ln['eng'].model = None
+            ln['eng']._last = None             # names the engine itself (last_maps): a cycle that would keep its maps
+        self._lanes = None
+        for hlf in (self.__dict__.pop('_half', None) or []):       # the two halves of infer_batch: own buffers
+            hlf._bufs.clear()
+            hlf.model = None
+            hlf._last = None
+        self._bufs.clear()
+        self._side = self._last = None
+        self.model = None
+
     def evaluate(self, images, image_ids=None, batch_size=64, num_joints=None, stats=None, evaluator=None):
         """A whole validation set of HxWx3 uint8 images of any sizes -> result dicts in input order
         (``litepose_amd.evaluate.evaluate``).  ``evaluator``: a ``coco_eval.KeypointEvaluator`` that is fed every

@@ -1,0 +1,216 @@
+"""lp_augment_batch_v on the device (csrc/ae_kernels.hip warp_affine_flip_norm_v_kernel; litepose_amd.dataset.calibration):
+the train loader's image side in one launch.  flip = 0 rows against lp_preprocess_batch_v bit for bit, flip = 1 rows
+against the mirror of their flip = 0 result, an out-of-range descriptor, a captured-graph replay, and the buffer contract
+of include/litepose_amd.h with poisoned and guarded buffers (tests/_poison.py)."""
+import ctypes as C
+import random
+
+import numpy as np
+import pytest
+import torch
+
+import _poison as po
+
+pytestmark = pytest.mark.gpu
+
+SIZES = [(37, 53), (64, 48), (16, 16), (90, 31)]            # h, w of the N = 4 sources
+OUT_SIZES = [(32, 32), (48, 40)]                            # Hd, Wd
+BAD_ROW = 2                                                 # of the table with the out-of-range descriptor
+
+
+def _nv():
+    from litepose_amd import _native as nv
+    return nv
+
+
+@pytest.fixture(scope='module')
+def sources():
+    """The packed sources (13 bytes of gap before each) and, per output size, the descriptor rows drawn by
+    draw_transform with 30 degrees of rotation."""
+    from litepose_amd.dataset import calibration as cal
+    from litepose_amd.utils import transforms as tf
+    rng = np.random.default_rng(21)
+    images = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in SIZES]
+    offs, buf = [], np.zeros(0, np.uint8)
+    for im in images:
+        buf = np.concatenate([buf, np.full(13, 255, np.uint8)])
+        offs.append(buf.size)
+        buf = np.concatenate([buf, im.reshape(-1)])
+    np_rng, py_rng = np.random.RandomState(5), random.Random(5)
+    minv = {}
+    for hd, wd in OUT_SIZES:
+        rows = []
+        for h, w in SIZES:
+            mat, _ = cal.draw_transform(h, w, wd, np_rng, py_rng, max_rotation=30)
+            assert abs(mat[0, 1]) > 1e-3                     # a real rotation
+            rows.append(tf.warp_invert(mat))
+        minv[(hd, wd)] = rows
+    return dict(images=images, offs=offs, src=torch.from_numpy(buf).cuda(), minv=minv)
+
+
+def _tables(sources, size, flips, bad=None):
+    """(lp_aug_desc table, lp_warp_desc table) as uint8 device tensors; ``bad``: row whose image ends past the buffer."""
+    from litepose_amd.dataset import calibration as cal
+    from litepose_amd.utils import transforms as tf
+    n = len(SIZES)
+    aug, warp = np.zeros(n, cal.AUG_DESC_DTYPE), np.zeros(n, tf.WARP_DESC_DTYPE)
+    for r, (h, w) in enumerate(SIZES):
+        off = sources['offs'][r]
+        if r == bad:
+            off = sources['src'].numel() - h * w * 3 + 1
+        for t in (aug, warp):
+            t[r]['src_offset'], t[r]['H'], t[r]['W'], t[r]['minv'] = off, h, w, sources['minv'][size][r]
+        aug[r]['flip'] = flips[r]
+    up = lambda t: torch.from_numpy(t.view(np.uint8).reshape(n, -1).copy()).cuda()  # noqa: E731
+    return up(aug), up(warp)
+
+
+def _consts():
+    from litepose_amd.utils import transforms as tf
+    return (C.c_float * 3)(*tf.IMAGENET_MEAN), (C.c_float * 3)(*tf.IMAGENET_STD)
+
+
+def _augment(src, desc, size, u8, ten):
+    nv = _nv()
+    mean, std = _consts()
+    nv.check(nv.lib().lp_augment_batch_v(nv.dptr(src), src.numel(), nv.dptr(desc), desc.shape[0], size[0], size[1], mean,
+                                         std, nv.dptr(u8), nv.dptr(ten), nv.stream_ptr()), 'lp_augment_batch_v')
+
+
+def _preprocess(src, desc, size, u8, ten):
+    nv = _nv()
+    mean, std = _consts()
+    nv.check(nv.lib().lp_preprocess_batch_v(nv.dptr(src), src.numel(), nv.dptr(desc), desc.shape[0], size[0], size[1],
+                                            mean, std, nv.dptr(u8), nv.dptr(ten), nv.stream_ptr()), 'lp_preprocess_batch_v')
+
+
+def _outs(size, fill=None):
+    n = len(SIZES)
+    u8 = torch.empty((n, size[0], size[1], 3), dtype=torch.uint8, device='cuda')
+    ten = torch.empty((n, 3, size[0], size[1]), dtype=torch.float32, device='cuda')
+    if fill:
+        po.fill(u8, fill)
+        po.fill(ten, fill)
+    return u8, ten
+
+
+@pytest.mark.parametrize('size', OUT_SIZES)
+def test_rows_equal_preprocess_and_its_mirror(sources, size):
+    src = sources['src']
+    # the reference: lp_preprocess_batch_v with the same matrices, the bad row included
+    _, warp = _tables(sources, size, [0] * 4, bad=BAD_ROW)
+    ref_u8, ref = _outs(size, 'N')
+    _preprocess(src, warp, size, ref_u8, ref)
+    assert int(ref_u8[0].max()) > 0 and int(ref_u8[3].max()) > 0            # the warps hit their images
+    for flips in ([0, 0, 0, 0], [1, 1, 1, 1], [0, 1, 1, 0], [1, 0, 0, 7]):
+        aug, _ = _tables(sources, size, flips, bad=BAD_ROW)
+        u8, ten = _outs(size, 'N')
+        _augment(src, aug, size, u8, ten)
+        torch.cuda.synchronize()
+        for r, f in enumerate(flips):
+            want_u8, want = (torch.flip(ref_u8[r], dims=[1]), torch.flip(ref[r], dims=[2])) if f else (ref_u8[r], ref[r])
+            assert po.bitwise_equal(u8[r], want_u8.contiguous()), (flips, r)
+            assert po.bitwise_equal(ten[r], want.contiguous()), (flips, r)
+        # the out-of-range row is zeros, flipped or not
+        assert not u8[BAD_ROW].any() and not po.as_bits(ten[BAD_ROW]).any()
+    # a mirrored image is not its own mirror here: the flip = 1 comparison above cannot pass by symmetry
+    assert not torch.equal(ref_u8[0], torch.flip(ref_u8[0], dims=[1]))
+
+
+def test_descriptor_ranges_yield_zeros(sources):
+    """H or W outside 1..32767, a negative offset, an image that ends past the buffer and a reserved field that is not 0:
+    zeros, whatever the buffer holds (the gap bytes before every image are 255)."""
+    from litepose_amd.dataset import calibration as cal
+    size = OUT_SIZES[0]
+    aug, _ = _tables(sources, size, [0, 1, 0, 1])
+    rows = aug.cpu().numpy().view(cal.AUG_DESC_DTYPE).reshape(-1).copy()
+    rows[0]['H'] = 0
+    rows[1]['W'] = 32768
+    rows[2]['src_offset'] = -1
+    rows[3]['reserved'] = 1
+    u8, ten = _outs(size, 'N')
+    _augment(sources['src'], torch.from_numpy(rows.view(np.uint8).reshape(4, -1)).cuda(), size, u8, ten)
+    torch.cuda.synchronize()
+    assert not u8.any() and not po.as_bits(ten).any()
+
+
+def test_replayed_from_a_captured_graph(sources):
+    size = OUT_SIZES[1]
+    aug, _ = _tables(sources, size, [0, 1, 1, 0], bad=BAD_ROW)
+    u8, ten = _outs(size, 'N')
+    _augment(sources['src'], aug, size, u8, ten)
+    torch.cuda.synchronize()
+    eager = [u8.clone(), ten.clone()]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):              # one launch, no branches
+        _augment(sources['src'], aug, size, u8, ten)
+    for _ in range(2):
+        po.fill(u8, 'N')
+        po.fill(ten, 'H')
+        graph.replay()
+        torch.cuda.synchronize()
+        assert po.bitwise_equal(u8, eager[0]) and po.bitwise_equal(ten, eager[1])
+    # the table is read when the launch runs: refilled in place, the replay follows it
+    aug2, _ = _tables(sources, size, [1, 0, 0, 1], bad=BAD_ROW)
+    aug.copy_(aug2)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert po.bitwise_equal(u8[0], torch.flip(eager[0][0], dims=[1]).contiguous())
+    assert po.bitwise_equal(ten[1], torch.flip(eager[1][1], dims=[2]).contiguous())
+
+
+@pytest.mark.parametrize('which', ['both', 'resized_out', 'tensor_out'])
+def test_the_call_respects_its_buffers(sources, which):
+    """Poisoned outputs fully written, guards intact, the sources and the table unmodified and not over-read, the results
+    independent of what the buffers held; each output alone with the other NULL writes the same bits."""
+    size = OUT_SIZES[1]
+    n = len(SIZES)
+    aug, _ = _tables(sources, size, [1, 0, 1, 1], bad=BAD_ROW)
+    res = {}
+    for pat in po.PATTERNS:
+        ar = po.Arena(pat)
+        u8 = ar.out((n, size[0], size[1], 3), torch.uint8, what='resized_out') if which != 'tensor_out' else None
+        ten = ar.out((n, 3, size[0], size[1]), what='tensor_out') if which != 'resized_out' else None
+        s = ar.inp(sources['src'], what='d_src')
+        dd = ar.inp(aug, what='d_desc')
+        _augment(s, dd, size, u8, ten)
+        ar.check()
+        res[pat] = {k: v.clone() for k, v in (('u8', u8), ('tensor', ten)) if v is not None}
+    z = res['Z']
+    for pat in ('N', 'H'):
+        for k, v in res[pat].items():
+            left = po.still_poisoned(v, z[k], pat)
+            assert not left, (pat, k, len(left), left[0])
+            assert po.bitwise_equal(v, z[k]), (pat, k, po.first_difference(v, z[k]))
+    # against the plain launch into unguarded buffers
+    u8, ten = _outs(size)
+    _augment(sources['src'], aug, size, u8, ten)
+    torch.cuda.synchronize()
+    for k, want in (('u8', u8), ('tensor', ten)):
+        if k in z:
+            assert po.bitwise_equal(z[k], want), k
+
+
+def test_calibration_set_batches(sources):
+    """CalibrationSet: one launch per batch, the last batch short, each batch the rows of ``describe`` with the same
+    generators; the uint8 side is the mirror-by-index of the plain warp."""
+    from litepose_amd.dataset.calibration import CalibrationSet
+    cs = CalibrationSet(sources['images'] + sources['images'][:1])
+    assert len(cs) == 5
+    got = list(cs.batches(32, 2, np.random.RandomState(9), random.Random(9), max_rotation=30))
+    assert [tuple(x.shape) for x in got] == [(2, 3, 32, 32), (2, 3, 32, 32), (1, 3, 32, 32)]
+    assert all(x.dtype == torch.float32 and x.is_cuda for x in got)
+    np_rng, py_rng = np.random.RandomState(9), random.Random(9)
+    desc = cs.describe(range(5), 32, np_rng, py_rng, max_rotation=30)
+    assert set(desc['flip'].tolist()) == {0, 1}
+    whole = cs.augment(desc, 32)
+    torch.cuda.synchronize()
+    assert po.bitwise_equal(torch.cat(got), whole)
+    plain = desc.copy()
+    plain['flip'] = 0
+    ref = cs.augment(plain, 32)
+    for r in range(5):
+        want = torch.flip(ref[r], dims=[2]).contiguous() if desc[r]['flip'] else ref[r]
+        assert po.bitwise_equal(whole[r], want), r

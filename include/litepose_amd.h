@@ -615,6 +615,109 @@ typedef struct lp_aug_desc {
 int lp_augment_batch_v(const uint8_t* d_src, size_t src_bytes, const lp_aug_desc* d_desc, int N, int Hd, int Wd,
                        const float* h_mean, const float* h_std, uint8_t* resized_out, float* tensor_out, void* stream);
 
+/* ------------------------------------------------------------ training targets ---
+ * The label side of the train loader for a batch (lib/dataset/transforms/transforms.py:54-182,
+ * lib/dataset/target_generators/target_generators.py, lib/dataset/COCOKeypoints.py:63-93); the image side is
+ * lp_augment_batch_v.  No allocation, no synchronisation, no atomics (results are identical from run to run), capturable in a
+ * hipGraph.  Every refusal is answered before any pointer is dereferenced (h_flip_index is read after the sizes are accepted).
+ * heat_out, joints_out, mask_out and the loss outputs below are DEVICE memory like every d_* pointer of this header; like
+ * count_out and score_out they do not carry the prefix because the census of writable calls (tests/test_poison_cpu.py) keys
+ * on it; their contract test is tests/test_gpu_train_buffers.py.
+ *
+ * One row of the descriptor table of lp_target_maps: 56 bytes, no implicit padding (6 * 8 + 4 + 4).
+ *   mat        the FORWARD (source image -> output plane) 2x3 matrix: RandomAffineTransform's mat_output of this row for
+ *              this output resolution
+ *   flip       != 0: RandomHorizontalFlip took this row
+ *   reserved   must be 0                                                                                              */
+typedef struct lp_target_desc {
+    double mat[6];
+    int32_t flip, reserved;
+} lp_target_desc;
+
+/* HeatmapGenerator.__call__ + JointsGenerator.__call__ (target_generators.py:28-50,99-115) on the joints as
+ * RandomAffineTransform._affine_joints and RandomHorizontalFlip leave them (transforms.py:124-129,169-171,71-72), for ONE
+ * output resolution R and a whole batch: ONE launch.
+ *   d_joints [P_tot,J,3]  fp64 (x, y, v) in source-image coordinates (COCOKeypoints.get_joints), the persons of all rows
+ *   d_first [N+1]         prefix offsets: row n owns persons d_first[n] .. d_first[n+1]-1.  CONDITION of the call: at most
+ *                         M per row (the table's owner checks it, as the reference's IndexError would; the kernel reads the
+ *                         first M)
+ *   d_desc [N]            DEVICE table of lp_target_desc, read when the launch runs
+ *   h_flip_index [J]      host ints in [0, J) (FLIP_CONFIG), copied into the launch (a captured graph holds them)
+ *   d_gauss [side*side]   the fp32 Gaussian table of HeatmapGenerator (exp(-((x-x0)^2 + (y-y0)^2) / (2 sigma^2)), x0 = y0 =
+ *                         3 sigma + 1), side = 6 sigma + 3; sigma3 = 3 sigma.  May be NULL without heat_out
+ *   M                     DATASET.MAX_NUM_PEOPLE;  tag_per_joint  MODEL.TAG_PER_JOINT
+ * A joint's coordinates are (m0*x + m1*y) + m2 and (m3*x + m4*y) + m5 in fp64, each operation rounded on its own; a mirrored
+ * row takes output joint j from source joint flip_index[j] and then x = R - x - 1.  Its cell is the coordinate TRUNCATED
+ * TOWARD ZERO (the reference's int()): -0.5 lands in cell 0 and is inside.  A joint counts iff v > 0 and both cells lie in
+ * [0, R).
+ *   heat_out [N,J,R,R] f32     per pixel the maximum, over the row's counting joints j, of the table entry at its offset in
+ *                              the window [cell - 3 sigma - 1, cell + 3 sigma + 2) clipped to the plane; 0 elsewhere
+ *   joints_out [N,M,J,2] i32   the counting joints of person i packed to the front of row i as (index, 1), index = j*R*R +
+ *                              y*R + x with tag_per_joint, y*R + x without; every other slot is (0, 0)
+ * Either output may be NULL, not both.  A row whose reserved field is not 0, or whose d_first range is negative, decreasing
+ * or ends beyond P_tot, yields zeros for that row and reads no joints.  DATASET.SCALE_AWARE_SIGMA (a table per person) is
+ * not covered.
+ * Writes: every element of each output given.
+ * LP_ERR_UNSUPPORTED: J outside 1..32, M outside 1..64, R outside 1..1024, sigma3 not a non-negative integer, side != 2 *
+ * sigma3 + 3.  LP_ERR_INVALID_ARG: a null pointer (one of the two outputs, and d_gauss without heat_out, excepted), N < 1,
+ * P_tot < 0, a flip_index entry outside [0, J).                                                                        */
+int lp_target_maps(const double* d_joints, int64_t P_tot, const int32_t* d_first, const lp_target_desc* d_desc, int N,
+                   int J, int R, const int32_t* h_flip_index, const float* d_gauss, int side, double sigma3, int M,
+                   int tag_per_joint, float* heat_out, int32_t* joints_out, void* stream);
+
+/* The mask side (transforms.py:163-167,70): cv2.warpAffine of (mask * 255).astype(uint8) to (R, R), then / 255 > 0.5, then
+ * the mirror of RandomHorizontalFlip: ONE launch.  The one-channel form of lp_augment_batch_v's warp (the same fixed-point
+ * positions and weights, the mirror by index).
+ *   d_src [src_bytes]  the rows' [H,W] uint8 masks (0 or 1; any non-zero byte reads as 1) packed at any offsets; may be NULL
+ *                      with src_bytes = 0 when every row is an all-ones one
+ *   d_desc [N]         DEVICE table of lp_aug_desc as lp_augment_batch_v takes it: minv = lp_warp_invert of this
+ *                      resolution's mat_output, flip, H, W, and src_offset = the mask's byte offset or -1: an all-ones
+ *                      H x W mask, nothing is read (the common case; the result is still 0 outside the warped image:
+ *                      constant border)
+ *   mask_out [N,R,R]   f32 in {0, 1}: 1 iff the interpolated byte is >= 128
+ * A descriptor whose mask does not lie inside [0, src_bytes) (and is not -1), whose H or W is outside 1..32767 or whose
+ * reserved field is not 0 yields zeros for that row and reads nothing.
+ * Writes: every element of mask_out.
+ * LP_ERR_INVALID_ARG: d_desc or mask_out null, d_src null with src_bytes > 0, N outside 1..65535.  LP_ERR_UNSUPPORTED: R
+ * outside 1..1024.                                                                                                     */
+int lp_target_masks(const uint8_t* d_src, size_t src_bytes, const lp_aug_desc* d_desc, int N, int R, float* mask_out,
+                    void* stream);
+
+/* ------------------------------------------------------------ training loss ------
+ * MultiLossFactory.forward for ONE stage of a batch (lib/core/loss.py:30-39,95-149,277-315), the per-image terms: the batch
+ * means of do_train (lib/core/trainer.py:85-101) are a mean over N for the caller.  At most two launches, no allocation, no
+ * synchronisation, no atomics, capturable in a hipGraph.
+ *   d_out [N,C,R,R]       the network output of the stage; channels [0, J) are the heatmaps when d_heat is given
+ *   tag_offset            the channel where the tag maps start (J, or 0 on a stage without heatmap loss); < 0: no tag terms
+ *                         on this stage (d_joints, push_out and pull_out are then not touched and may be NULL)
+ *   d_heat [N,J,R,R]      target heatmaps, or NULL: no heatmap term (d_mask, heat_loss_out and the workspace are then not
+ *                         touched and may be NULL)
+ *   d_mask [N,R,R]        the loss mask
+ *   d_joints [N,M,J,2]    i32 (index, visible) as lp_target_maps writes them; a slot is visible iff its second value is > 0
+ *   loss_type             LOSS.AE_LOSS_TYPE: 0 = 'exp', 1 = 'max'
+ *   heat_loss_out [N]     mean((pred - gt)^2 * mask) over J, R, R of the image (what the reference's nested means compute),
+ *                         times heat_factor
+ *   push_out, pull_out [N]  the per-image terms of batchTagLoss before its torch.mean over the batch, times their factors:
+ *                         pull = sum over persons of mean_j (tag - person mean)^2, over the number of persons with a visible
+ *                         joint (0 persons: 1); push = 0.5 * (sum over person pairs of exp(-d^2) or max(1 - |d|, 0), d the
+ *                         difference of their mean tags, minus the number of persons) / max((persons - 1) * persons, 1),
+ *                         and 0 below two persons
+ * Arithmetic: fp32 inputs widened to fp64, fp64 sums in a fixed order, exp in fp64; each result is rounded to fp32 once.
+ * Results are identical from run to run.  A joints index outside [0, (C - tag_offset) * R * R) reads nothing and counts as
+ * not visible (the reference's gather would raise); neither does a slot that is not visible read the tag map (the reference
+ * multiplies the gathered value by 0).
+ * Writes: every element of heat_loss_out (with d_heat) and of push_out and pull_out (with tag_offset >= 0); the first
+ * lp_pose_loss_workspace_bytes(N, J, R) bytes of `workspace` at most (per-strip fp64 partials; 8-byte aligned).
+ * LP_ERR_UNSUPPORTED: J outside 1..32, R outside 1..1024, and with tag terms M outside 1..64 or loss_type outside 0..1.
+ * LP_ERR_INVALID_ARG: a null pointer that the requested terms need, neither term requested, N < 1, C < 1, J > C with a
+ * heatmap term, tag_offset >= C.  LP_ERR_WORKSPACE: too small or misaligned.  lp_pose_loss_workspace_bytes: 0 for sizes
+ * outside these ranges.                                                                                                */
+size_t lp_pose_loss_workspace_bytes(int N, int J, int R);
+int lp_pose_loss(const float* d_out, int N, int C, int R, int J, int tag_offset, const float* d_heat, const float* d_mask,
+                 const int32_t* d_joints, int M, int loss_type, float heat_factor, float push_factor, float pull_factor,
+                 float* heat_loss_out, float* push_out, float* pull_out, void* workspace, size_t workspace_bytes,
+                 void* stream);
+
 /* utils.transforms.get_final_preds (lib/utils/transforms.py:195-202,50-56): inverse
  * affine (rot 0) heatmap -> image coordinates, in place on x,y of d_ans.
  * h_center [2], h_scale [2] as returned by get_multi_scale_size, heatmap size (Wp,Hp).

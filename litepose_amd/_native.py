@@ -55,6 +55,11 @@ class LpAugDesc(C.Structure):
                 ('flip', C.c_int32), ('reserved', C.c_int32)]
 
 
+class LpTargetDesc(C.Structure):
+    """lp_target_desc: one row (56 bytes) of the device descriptor table of lp_target_maps."""
+    _fields_ = [('mat', C.c_double * 6), ('flip', C.c_int32), ('reserved', C.c_int32)]
+
+
 class LpImageDesc(C.Structure):
     """lp_image_desc: one row (16 bytes) of the device descriptor table of lp_draw_poses_v."""
     _fields_ = [('offset', C.c_int64), ('H', C.c_int32), ('W', C.c_int32)]
@@ -145,6 +150,12 @@ _SIGS = {
     'lp_preprocess_batch_v': (i32, [vp, sz, vp, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp,
                                     vp]),
     'lp_augment_batch_v': (i32, [vp, sz, vp, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp, vp]),
+    'lp_target_maps': (i32, [vp, i64, vp, vp, i32, i32, i32, C.POINTER(C.c_int32), vp, i32, C.c_double, i32, i32, vp, vp,
+                             vp]),
+    'lp_target_masks': (i32, [vp, sz, vp, i32, i32, vp, vp]),
+    'lp_pose_loss_workspace_bytes': (sz, [i32, i32, i32]),
+    'lp_pose_loss': (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, vp,
+                           vp, sz, vp]),
     'lp_stream_abort_capture': (i32, [vp]),
     'lp_final_preds': (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                              i32, i32, vp]),

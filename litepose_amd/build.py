@@ -46,6 +46,9 @@ SOURCES = [
     ('eval_api.cpp', ['-ffp-contract=off']),               # the host tables of the launch: (2 sigma)^2 as NumPy rounds it
     ('eval_kernels.hip', ['-ffp-contract=off'] + NOPK),    # COCOeval's fp64 expressions, one IEEE operation each
     ('vis_api.cpp', []),
+    ('train_api.cpp', []),
+    ('target_kernels.hip', ['-ffp-contract=off'] + NOPK),  # the fp64 joint transform and cv2's fixed-point warp, operation by operation
+    ('loss_kernels.hip', ['-ffp-contract=off'] + NOPK),    # fp64 products and sums round separately, as the restatement's do
     ('vis_kernels.hip', NOPK),                             # integer raster; floats are only loaded, compared, truncated
 ]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value',

@@ -1,1 +1,1 @@
-from . import inference, group  # noqa: F401
+from . import inference, group, loss, trainer  # noqa: F401

@@ -14,6 +14,7 @@
 
 #include "ae_common.h"
 #include "kernels.h"
+#include "warp_fixed.h"
 
 namespace lp {
 
@@ -2130,41 +2131,25 @@ __global__ void final_preds_v_kernel(float* __restrict__ ans, const int* __restr
 // ToTensor + Normalize (valid.py:178-186), in one pass: uint8 HWC -> float32 CHW.
 // The interpolation is cv2's 8-bit fixed-point scheme (published algorithm of
 // opencv/modules/imgproc/src/imgwarp.cpp, warpAffine + remapBilinear; cv2 itself is absent here):
-//   source position in 1/1024 px:  X = round(M[0]*x*1024) + round((M[1]*y+M[2])*1024) + 16   (likewise Y)
-//   integer pixel X>>10, 5 fractional bits fx = (X>>5)&31, weights (32-fx)(32-fy)*32 .. fx*fy*32
-//   (sum 32768), value = (sum w*p + 16384) >> 15, taps outside the image contribute 0.
+// its arithmetic lives in warp_fixed.h, shared with the mask warp of target_kernels.hip.
 // One thread per destination pixel; the matrix is the INVERTED (dst->src) one, in fp64.
 // ====================================================================================
-__device__ __forceinline__ int sat_int_rint(double v) {
-    const double r = rint(v);
-    return r >= 2147483647.0 ? 2147483647 : (r <= -2147483648.0 ? (int)-2147483648LL : (int)r);
-}
-
-// One destination pixel (x, y) of one image: the fixed-point warp of `src` [H,W,3] through the inverted matrix m0..m5, then
-// ToTensor + Normalize.  Shared by the one-transform and the per-image kernel, so both compute the same bits by construction.
+// One destination pixel (x, y) of one image: the fixed-point warp of `src` [H,W,3] through the inverted matrix m0..m5
+// (warp_fixed.h: position, weights and rounding), then ToTensor + Normalize.  Shared by the one-transform and the per-image
+// kernel, so both compute the same bits by construction.
 __device__ __forceinline__ void warp_norm_pixel(const unsigned char* __restrict__ src, int H, int W, int Hd, int Wd,
                                                 int x, int y, double m0, double m1, double m2, double m3, double m4,
                                                 double m5, const float (&mean)[3], const float (&sd)[3],
                                                 unsigned char* __restrict__ dst_u8, float* __restrict__ dst_f32) {
-    const int adelta = sat_int_rint(m0 * (double)x * 1024.0), bdelta = sat_int_rint(m3 * (double)x * 1024.0);
-    const int X0 = sat_int_rint((m1 * (double)y + m2) * 1024.0) + 16;
-    const int Y0 = sat_int_rint((m4 * (double)y + m5) * 1024.0) + 16;
-    const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
-    const int sx = min(max(X >> 5, -32768), 32767), sy = min(max(Y >> 5, -32768), 32767);
-    const int fx = X & 31, fy = Y & 31;
-    int w00 = (32 - fx) * (32 - fy) * 32;
-    if (w00 > 32767) w00 = 32767;                     // saturate_cast<short>(1.0 * 32768)
-    const int w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
-    const bool x0 = sx >= 0 && sx < W, x1 = sx + 1 >= 0 && sx + 1 < W;
-    const bool y0 = sy >= 0 && sy < H, y1 = sy + 1 >= 0 && sy + 1 < H;
+    const WarpTaps t = warp_taps(H, W, x, y, m0, m1, m2, m3, m4, m5);
+    const int sx = t.sx, sy = t.sy;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const int p00 = (y0 && x0) ? src[((long)sy * W + sx) * 3 + c] : 0;
-        const int p01 = (y0 && x1) ? src[((long)sy * W + sx + 1) * 3 + c] : 0;
-        const int p10 = (y1 && x0) ? src[((long)(sy + 1) * W + sx) * 3 + c] : 0;
-        const int p11 = (y1 && x1) ? src[((long)(sy + 1) * W + sx + 1) * 3 + c] : 0;
-        int v = (p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + 16384) >> 15;
-        v = min(max(v, 0), 255);
+        const int p00 = (t.y0 && t.x0) ? src[((long)sy * W + sx) * 3 + c] : 0;
+        const int p01 = (t.y0 && t.x1) ? src[((long)sy * W + sx + 1) * 3 + c] : 0;
+        const int p10 = (t.y1 && t.x0) ? src[((long)(sy + 1) * W + sx) * 3 + c] : 0;
+        const int p11 = (t.y1 && t.x1) ? src[((long)(sy + 1) * W + sx + 1) * 3 + c] : 0;
+        const int v = warp_blend(t, p00, p01, p10, p11);
         if (dst_u8) dst_u8[((long)y * Wd + x) * 3 + c] = (unsigned char)v;
         if (dst_f32) dst_f32[((long)c * Hd + y) * Wd + x] = ((float)v / 255.0f - mean[c]) / sd[c];
     }

@@ -360,4 +360,27 @@ void launch_draw_poses(unsigned char* images, long long bytes, const ImageDesc* 
                        const float* kpts, const int* count, int pcap, int J, int D, const int* links, int n_links,
                        const unsigned char* palette, int n_colors, int Rj, int Rl, hipStream_t s);
 
+// ---- training targets and loss (target_kernels.hip, loss_kernels.hip; lp_target_maps / lp_target_masks / lp_pose_loss) ------
+struct TargetDesc {                         // lp_target_desc (include/litepose_amd.h)
+    double mat[6];                          // FORWARD (src -> output plane) 2x3 matrix
+    int flip, reserved;
+};
+static_assert(sizeof(TargetDesc) == 56, "TargetDesc must match lp_target_desc (56 bytes)");
+struct TargetFlip { int idx[32]; };         // flip_index, passed to the kernel by value (entries in [0, J): checked by the caller)
+// one launch; heat [N,J,R,R] and / or jout [N,M,J,2]; J <= 32, M <= 64, side = 2 * s3 + 3: checked by the caller
+void launch_target_maps(const double* joints, long P_tot, const int* first, const TargetDesc* desc, int N, int J, int R,
+                        const TargetFlip& fi, const float* gauss, int side, int s3, int M, int tag_per_joint, float* heat,
+                        int* jout, hipStream_t s);
+// one launch; out [N,R,R]; src may be null when src_bytes is 0 (every usable row is then an all-ones one)
+void launch_target_masks(const unsigned char* src, long long src_bytes, const AugDesc* desc, int N, int R, float* out,
+                         hipStream_t s);
+constexpr int LOSS_STRIP = 4096;            // floats of a plane per workgroup (and per fp64 partial) of the heatmap loss
+// partial [N * J * S] fp64, S = ceil(R * R / LOSS_STRIP)
+void launch_heat_partial(const float* pred, const float* gt, const float* mask, int N, int C, int J, int R, int S,
+                         double* partial, hipStream_t s);
+// partial == nullptr: no heatmap term (heat_loss untouched); tag_offset < 0: no tag terms (push_out / pull_out untouched)
+void launch_loss_finish(const double* partial, int N, int JS, double heat_count, double heat_factor, const float* out,
+                        int C, int R, int tag_offset, const int* joints, int M, int J, int loss_type, double push_factor,
+                        double pull_factor, float* heat_loss, float* push_out, float* pull_out, hipStream_t s);
+
 }  // namespace lp

@@ -7,7 +7,8 @@ for one image -- the same numpy / stdlib calls with the same arguments in the sa
 of them into the network input with one descriptor upload and one ``lp_augment_batch_v`` launch: cv2.warpAffine's
 fixed-point bilinear warp, the mirror of the warped uint8 image, ToTensor + Normalize.
 
-What the search's calibration does not read -- masks, joints, heatmap targets -- is not produced.  The reference's loader
+What the search's calibration does not read -- masks, joints, heatmap targets -- is not produced here: ``draw_sample`` and
+``dataset.targets.LabelledSet`` are the labelled loader.  The reference's loader
 may run worker processes, each with its own copy of the generators; the draws here follow the single-process order (image
 after image: the affine draws from numpy, then the flip draw from ``random``).
 """
@@ -84,6 +85,37 @@ def draw_transform(h, w, input_size, np_rng=None, py_rng=None, max_rotation=AUG_
     mat_input = _affine_matrix(center, scale, (input_size, input_size), aug_rot)[:2]
     flip = bool(py_rng.random() < flip_prob)
     return mat_input, flip
+
+
+def draw_sample(h, w, input_size, output_sizes, np_rng=None, py_rng=None, max_rotation=AUG_DEFAULTS['max_rotation'],
+                min_scale=AUG_DEFAULTS['min_scale'], max_scale=AUG_DEFAULTS['max_scale'],
+                scale_type=AUG_DEFAULTS['scale_type'], max_translate=AUG_DEFAULTS['max_translate'],
+                flip_prob=AUG_DEFAULTS['flip_prob']):
+    """``draw_transform`` for a labelled sample: the same draws in the same order (so the same ``mat_input`` and flip for
+    equal generators) -> (``mat_input``, [``mat_output`` per entry of ``output_sizes``], flip): the forward matrices of
+    RandomAffineTransform.__call__ for the image and for the masks and joints of every output resolution."""
+    np_rng = np.random if np_rng is None else np_rng
+    py_rng = random if py_rng is None else py_rng
+    height, width = h, w
+    center = np.array((width / 2, height / 2))
+    if scale_type == 'long':
+        scale = max(height, width) / 200
+    elif scale_type == 'short':
+        scale = min(height, width) / 200
+    else:
+        raise ValueError('Unknown scale type: {}'.format(scale_type))
+    aug_scale = np_rng.random() * (max_scale - min_scale) + min_scale
+    scale *= aug_scale
+    aug_rot = (np_rng.random() * 2 - 1) * max_rotation
+    if max_translate > 0:
+        dx = np_rng.randint(-max_translate * scale, max_translate * scale)
+        dy = np_rng.randint(-max_translate * scale, max_translate * scale)
+        center[0] += dx
+        center[1] += dy
+    mat_outputs = [_affine_matrix(center, scale, (o, o), aug_rot)[:2] for o in output_sizes]
+    mat_input = _affine_matrix(center, scale, (input_size, input_size), aug_rot)[:2]
+    flip = bool(py_rng.random() < flip_prob)
+    return mat_input, mat_outputs, flip
 
 
 class CalibrationSet(object):

@@ -717,6 +717,32 @@ int lp_pose_loss(const float* d_out, int N, int C, int R, int J, int tag_offset,
                  const int32_t* d_joints, int M, int loss_type, float heat_factor, float push_factor, float pull_factor,
                  float* heat_loss_out, float* push_out, float* pull_out, void* workspace, size_t workspace_bytes,
                  void* stream);
+/* The gradient of those three terms with respect to d_out: what loss.backward() needs from this library.  The problem is
+ * described as for lp_pose_loss (same meaning, ranges and error codes); at most two launches, no workspace, no allocation,
+ * no synchronisation, no atomics, capturable in a hipGraph.
+ *   d_g_heat, d_g_push, d_g_pull [N]  the upstream gradients of heat_loss_out[n], push_out[n] and pull_out[n]; NULL: all
+ *                         zeros for that term, and the pointer is never read
+ *   grad_out [N,C,R,R]    for image n --
+ *     heatmap channels j < J (with d_heat):  g_heat[n] * heat_factor * 2 * (p - g) * m / (J * R * R)
+ *     tag channels from tag_offset (tag_offset >= 0), with the visibility rule of lp_pose_loss: person p has cnt_p counting
+ *       slots with tags t_pk and mean mu_p; P persons have cnt_p > 0, pc = max(P, 1), den = max((pc - 1) * pc, 1).  A
+ *       counting slot adds to its cell  g_pull[n] * pull_factor * 2 * (t_pk - mu_p) / (cnt_p * pc)  and, when P >= 2,
+ *       g_push[n] * push_factor * D_p / (den * cnt_p),  D_p = sum over counting persons q of f'(mu_p - mu_q), with
+ *       f'(d) = -2 d exp(-d^2) for 'exp' and f'(d) = -sign(d) for |d| < 1, 0 otherwise (sign(0) = 0) for 'max'.  Several slots
+ *       on one cell: the cell holds the sum of their contributions in (person, joint) order -- what the backward of the
+ *       reference's gather adds up in no particular order
+ *     every other element is zero: channels outside both terms, tag cells no counting slot names, a term whose upstream
+ *       pointer is NULL
+ * A slot that does not count reads nothing and writes nothing.  Arithmetic as lp_pose_loss: fp64 on the widened fp32 inputs,
+ * sums in a fixed order, one rounding to fp32 per element; results are identical from run to run.
+ * Writes: every element of grad_out, and nothing else.  d_heat and d_mask are read only for a heatmap term with d_g_heat,
+ * d_joints and the tag cells of d_out only for tag terms with d_g_push or d_g_pull.
+ * LP_ERR_INVALID_ARG also for d_heat given with 0 <= tag_offset < J (the two terms would overlap; the reference never builds
+ * this case) and for grad_out NULL.                                                                                     */
+int lp_pose_loss_grad(const float* d_out, int N, int C, int R, int J, int tag_offset, const float* d_heat,
+                      const float* d_mask, const int32_t* d_joints, int M, int loss_type, float heat_factor,
+                      float push_factor, float pull_factor, const float* d_g_heat, const float* d_g_push,
+                      const float* d_g_pull, float* grad_out, void* stream);
 
 /* utils.transforms.get_final_preds (lib/utils/transforms.py:195-202,50-56): inverse
  * affine (rot 0) heatmap -> image coordinates, in place on x,y of d_ans.

@@ -156,6 +156,8 @@ _SIGS = {
     'lp_pose_loss_workspace_bytes': (sz, [i32, i32, i32]),
     'lp_pose_loss': (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, vp,
                            vp, sz, vp]),
+    'lp_pose_loss_grad': (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp,
+                                vp, vp, vp]),
     'lp_stream_abort_capture': (i32, [vp]),
     'lp_final_preds': (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                              i32, i32, vp]),

@@ -1,10 +1,17 @@
 """Drop-in for lib/core/loss.py on the device: ``HeatmapLoss``, ``AELoss`` and ``MultiLossFactory`` with the reference's
 call signatures and return shapes, every term one ``lp_pose_loss`` call (include/litepose_amd.h, "training loss").
 
-The values are the forward losses only (no autograd graph): what ``do_train`` logs (lib/core/trainer.py:75-105), the loss
-against teacher heatmaps (the same call with other targets), and a dense score of a search candidate.  The device
-arithmetic is fp64 on the fp32 inputs with one rounding per result, so a value may differ from the reference's fp32
-evaluation by that evaluation's own rounding error."""
+The values are what ``do_train`` logs and sums (lib/core/trainer.py:75-105), the loss against teacher heatmaps (the same
+call with other targets), and a dense score of a search candidate.  The device arithmetic is fp64 on the fp32 inputs with
+one rounding per result, so a value may differ from the reference's fp32 evaluation by that evaluation's own rounding
+error.
+
+On a stage output that requires grad (and with grad enabled) the three terms are differentiable with respect to that
+output: ``loss.backward()`` reaches it through one ``lp_pose_loss_grad`` call per ``pose_loss`` call (``pose_loss_grad``;
+a term that takes no part in the loss arrives as None and goes to the device as NULL).  Targets, masks and joints get no
+gradient.  The same fixed-order arithmetic: where several joints share a tag cell, the cell's gradient is their sum in
+(person, joint) order, not the unordered atomic sum of the backward of ``torch.gather``.  Without grad the calls are the
+forward calls alone and the results carry no ``grad_fn``."""
 import torch
 
 from .. import _native as nv
@@ -19,7 +26,14 @@ def pose_loss(out, num_joints, tag_offset=-1, heat=None, mask=None, joints=None,
     """One ``lp_pose_loss`` call on the stage output ``out`` float32 [N,C,R,R] -> (heat_loss [N] or None, push [N] or
     None, pull [N] or None).  ``heat`` [N,J,R,R] with ``mask`` [N,R,R]: the heatmap term; ``tag_offset`` >= 0 with
     ``joints`` int32 [N,M,J,2]: the tag terms on the channels from ``tag_offset``.  ``buffers``: a dict from
-    ``loss_buffers`` to write into instead of allocating (the call is then capturable in a graph)."""
+    ``loss_buffers`` to write into instead of allocating (the call is then capturable in a graph).  When ``out`` requires
+    grad and grad is enabled the results are differentiable with respect to ``out`` (not with ``buffers``: kept buffers
+    are overwritten by the next call, an autograd graph would outlive them)."""
+    if out.requires_grad and torch.is_grad_enabled():
+        if buffers is not None:
+            raise ValueError('buffers= cannot be combined with an output that requires grad')
+        return _PoseLoss.apply(out, num_joints, tag_offset, heat, mask, joints, loss_type, heat_factor, push_factor,
+                               pull_factor)
     if out.dtype != torch.float32 or out.dim() != 4 or out.shape[2] != out.shape[3]:
         raise ValueError('expected a float32 [N,C,R,R] output')
     N, Cc, R = int(out.shape[0]), int(out.shape[1]), int(out.shape[2])
@@ -56,6 +70,74 @@ def pose_loss(out, num_joints, tag_offset=-1, heat=None, mask=None, joints=None,
                                    float(pull_factor), nv.dptr(hl), nv.dptr(push), nv.dptr(pull), nv.dptr(ws),
                                    0 if ws is None else ws.numel(), nv.stream_ptr()), 'lp_pose_loss')
     return hl, push, pull
+
+
+def pose_loss_grad(out, num_joints, tag_offset=-1, heat=None, mask=None, joints=None, loss_type='exp', heat_factor=1.0,
+                   push_factor=1.0, pull_factor=1.0, g_heat=None, g_push=None, g_pull=None, grad_out=None):
+    """One ``lp_pose_loss_grad`` call: the gradient of the terms of ``pose_loss`` (same arguments) with respect to ``out``,
+    float32 [N,C,R,R], every element written.  ``g_heat``, ``g_push``, ``g_pull``: float32 [N] upstream gradients of the
+    three results, None for a term that adds nothing.  ``grad_out``: a contiguous float32 tensor of ``out``'s shape to
+    write into instead of allocating (the call is then capturable in a graph)."""
+    if out.dtype != torch.float32 or out.dim() != 4 or out.shape[2] != out.shape[3]:
+        raise ValueError('expected a float32 [N,C,R,R] output')
+    N, Cc, R = int(out.shape[0]), int(out.shape[1]), int(out.shape[2])
+    J = int(num_joints)
+    out = out.detach().contiguous()
+    if grad_out is None:
+        grad_out = torch.empty((N, Cc, R, R), dtype=torch.float32, device=out.device)
+    elif grad_out.shape != out.shape or grad_out.dtype != torch.float32 or not grad_out.is_contiguous():
+        raise ValueError('grad_out must be a contiguous float32 tensor of the shape of out')
+    M = 1
+    if heat is not None:
+        if tuple(heat.shape) != (N, J, R, R) or heat.dtype != torch.float32:
+            raise ValueError('heat must be float32 [N,J,R,R] of the output size')
+        if mask is None or tuple(mask.shape) != (N, R, R) or mask.dtype != torch.float32:
+            raise ValueError('mask must be float32 [N,R,R]')
+        heat, mask = heat.contiguous(), mask.contiguous()
+    else:
+        mask = g_heat = None
+    if tag_offset >= 0:
+        if joints is None or joints.dim() != 4 or joints.shape[0] != N or joints.shape[3] != 2 or \
+                joints.dtype != torch.int32:
+            raise ValueError('joints must be int32 [N,M,J,2]')
+        joints = joints.contiguous()
+        M = int(joints.shape[1])
+        if int(joints.shape[2]) != J:
+            raise ValueError('joints must hold %d joints per person' % J)
+    else:
+        joints = g_push = g_pull = None
+    ups = []
+    for name, g in (('g_heat', g_heat), ('g_push', g_push), ('g_pull', g_pull)):
+        if g is not None:
+            if tuple(g.shape) != (N,) or g.dtype != torch.float32:
+                raise ValueError('%s must be float32 [N]' % name)
+            g = g.contiguous()
+        ups.append(g)
+    nv.check(nv.lib().lp_pose_loss_grad(nv.dptr(out), N, Cc, R, J, int(tag_offset), nv.dptr(heat), nv.dptr(mask),
+                                        nv.dptr(joints), M, LOSS_TYPES[loss_type], float(heat_factor), float(push_factor),
+                                        float(pull_factor), nv.dptr(ups[0]), nv.dptr(ups[1]), nv.dptr(ups[2]),
+                                        nv.dptr(grad_out), nv.stream_ptr()), 'lp_pose_loss_grad')
+    return grad_out
+
+
+class _PoseLoss(torch.autograd.Function):
+    """``pose_loss`` with ``pose_loss_grad`` as its backward; differentiable in the stage output only."""
+
+    @staticmethod
+    def forward(ctx, out, num_joints, tag_offset, heat, mask, joints, loss_type, heat_factor, push_factor, pull_factor):
+        ctx.set_materialize_grads(False)             # a term that is not used arrives as None: NULL for the device
+        ctx.save_for_backward(out, heat, mask, joints)
+        ctx.args = (num_joints, tag_offset, loss_type, heat_factor, push_factor, pull_factor)
+        return pose_loss(out.detach(), num_joints, tag_offset, heat, mask, joints, loss_type, heat_factor, push_factor,
+                         pull_factor)
+
+    @staticmethod
+    def backward(ctx, g_heat, g_push, g_pull):
+        out, heat, mask, joints = ctx.saved_tensors
+        num_joints, tag_offset, loss_type, heat_factor, push_factor, pull_factor = ctx.args
+        grad = pose_loss_grad(out, num_joints, tag_offset, heat, mask, joints, loss_type, heat_factor, push_factor,
+                              pull_factor, g_heat, g_push, g_pull)
+        return (grad,) + (None,) * 9
 
 
 def loss_buffers(N, J, R, device):

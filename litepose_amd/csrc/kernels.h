@@ -382,5 +382,14 @@ void launch_heat_partial(const float* pred, const float* gt, const float* mask, 
 void launch_loss_finish(const double* partial, int N, int JS, double heat_count, double heat_factor, const float* out,
                         int C, int R, int tag_offset, const int* joints, int M, int J, int loss_type, double push_factor,
                         double pull_factor, float* heat_loss, float* push_out, float* pull_out, hipStream_t s);
+// lp_pose_loss_grad.  Every element of grad [N,C,R,R]: planes c < JH take g_heat[n] * heat_factor * 2 (p - g) m / (J R R),
+// the others zeros (JH = 0: no heatmap plane; pred / gt / mask / g_heat are then not read)
+void launch_heat_grad(const float* pred, const float* gt, const float* mask, const float* g_heat, int N, int C, int JH, int J,
+                      int R, int S, double heat_factor, float* grad, hipStream_t s);
+// after launch_heat_grad on the same stream: the cells of the tag channels that a counting slot names.  g_push / g_pull may
+// be null, not both.  M * J <= 64 * 32: checked by the caller
+void launch_tag_grad(const float* out, int N, int C, int R, int tag_offset, const int* joints, int M, int J, int loss_type,
+                     double push_factor, double pull_factor, const float* g_push, const float* g_pull, float* grad,
+                     hipStream_t s);
 
 }  // namespace lp

@@ -100,4 +100,35 @@ int lp_pose_loss(const float* d_out, int N, int C, int R, int J, int tag_offset,
     return LP_OK;
 }
 
+int lp_pose_loss_grad(const float* d_out, int N, int C, int R, int J, int tag_offset, const float* d_heat,
+                      const float* d_mask, const int32_t* d_joints, int M, int loss_type, float heat_factor,
+                      float push_factor, float pull_factor, const float* d_g_heat, const float* d_g_push,
+                      const float* d_g_pull, float* grad_out, void* stream) {
+    const bool heat = d_heat != nullptr, ae = tag_offset >= 0;
+    if (J < 1 || J > 32) return fail(LP_ERR_UNSUPPORTED, "J must be 1..32");
+    if (R < 1 || R > 1024) return fail(LP_ERR_UNSUPPORTED, "R must be 1..1024");
+    if (ae && (M < 1 || M > 64)) return fail(LP_ERR_UNSUPPORTED, "M (MAX_NUM_PEOPLE) must be 1..64");
+    if (ae && loss_type != 0 && loss_type != 1) return fail(LP_ERR_UNSUPPORTED, "loss_type must be 0 ('exp') or 1 ('max')");
+    if (!d_out || !grad_out) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (!heat && !ae) return fail(LP_ERR_INVALID_ARG, "no loss requested (d_heat is null and tag_offset < 0)");
+    if (heat && !d_mask) return fail(LP_ERR_INVALID_ARG, "null argument (heatmap term)");
+    if (ae && !d_joints) return fail(LP_ERR_INVALID_ARG, "null argument (tag terms)");
+    if (N < 1 || C < 1) return fail(LP_ERR_INVALID_ARG, "N and C must be positive");
+    if (heat && J > C) return fail(LP_ERR_INVALID_ARG, "J heatmap channels exceed C");
+    if (ae && tag_offset >= C) return fail(LP_ERR_INVALID_ARG, "tag_offset must be below C");
+    if (heat && ae && tag_offset < J) return fail(LP_ERR_INVALID_ARG, "the tag channels overlap the heatmap channels");
+    if ((long long)C * R * R > 0x7fffffffLL) return fail(LP_ERR_UNSUPPORTED, "C * R * R too large");
+    const int S = loss_strips(R);
+    if ((long long)N * C * S > 0x7fffffffLL) return fail(LP_ERR_UNSUPPORTED, "N * C * strips too large");
+    hipStream_t s = (hipStream_t)stream;
+    // a term without an upstream gradient is all zeros: its planes are written as the planes outside both terms are
+    lp::launch_heat_grad(d_out, d_heat, d_mask, d_g_heat, N, C, heat && d_g_heat ? J : 0, J, R, S, (double)heat_factor,
+                         grad_out, s);
+    if (ae && (d_g_push || d_g_pull))
+        lp::launch_tag_grad(d_out, N, C, R, tag_offset, d_joints, M, J, loss_type, (double)push_factor, (double)pull_factor,
+                            d_g_push, d_g_pull, grad_out, s);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "pose_loss_grad launch failed");
+    return LP_OK;
+}
+
 }  // extern "C"

@@ -744,6 +744,74 @@ int lp_pose_loss_grad(const float* d_out, int N, int C, int R, int J, int tag_of
                       float push_factor, float pull_factor, const float* d_g_heat, const float* d_g_push,
                       const float* d_g_pull, float* grad_out, void* stream);
 
+/* ------------------------------------------------------------ training-mode layers ------------
+ * The three layer kinds every InvBottleneck, first.1 / first.2 and both SepConv2d heads are made of (lib/models/layers/
+ * layers.py:18-24,90-133), each with a forward that keeps what a backward needs and a backward.  fp32, planar NCHW, plain
+ * weights as DEVICE pointers read when the launches run (they change every optimizer step): nothing is packed on the host.
+ * Every call enqueues its launches on `stream`: no allocation, no synchronisation, no atomics -- every sum has one order
+ * that depends on the shapes only, so two calls give the same bits -- and is capturable in a hipGraph.
+ * Every activation / gradient pointer and every workspace must be 16-byte aligned (LP_ERR_INVALID_ARG / LP_ERR_WORKSPACE);
+ * N * HW and C * HW at most 2^31 - 256 (LP_ERR_UNSUPPORTED).  A workspace smaller than the companion's answer: LP_ERR_WORKSPACE.
+ * The writable pointers are DEVICE memory like every d_* pointer of this header; they do not carry the prefix because
+ * the census of writable calls (tests/test_poison_cpu.py) keys on it; their contract test is
+ * tests/test_gpu_layer_buffers.py.
+ *
+ * BatchNorm + activation (+ residual), act 0 none / 1 ReLU / 2 ReLU6:
+ *   y = act(gamma * (x - mean) * invstd + beta) (+ res),  d_x, d_res (may be NULL), y_out [N,C,HW]; d_gamma, d_beta [C];
+ *   running_io [2,C] = running_mean | running_var.
+ *   training != 0: mean and the biased variance of the batch (fixed-order fp64 sums); running_io moves by `momentum` (with
+ *     the unbiased variance, as torch.nn.functional.batch_norm); stat_out [2,C] fp64 = mean | invstd, what lp_bn_backward
+ *     needs next to d_x.  Writes: every element of y_out, of stat_out and of running_io.
+ *   training == 0: the running pair is the statistics.  Writes: every element of y_out; stat_out (may be NULL) and
+ *     running_io are left untouched, the workspace is not used (it may be NULL).
+ *   y carries 3 fp32 roundings (4 with a residual) on top of the rounding of mean and invstd to fp32.
+ * lp_bn_backward (of a training-mode forward; d_x, d_gamma, d_beta, d_stat as that forward had / wrote them):
+ *   g = grad_y * act'(z) with z recomputed by the forward's own expression and strict inequalities (ReLU: z > 0, ReLU6:
+ *   0 < z < 6); grad_x = gamma * invstd * (g - sum(g) / n - xhat * sum(g * xhat) / n), grad_gamma = sum(g * xhat),
+ *   grad_beta = sum(g): fp64 on the fp32 inputs, one rounding per result.  The residual's gradient is grad_y itself.
+ *   Writes: every element of grad_x_out [N,C,HW], grad_gamma_out [C], grad_beta_out [C].                               */
+size_t lp_bn_workspace_bytes(int N, int C, int HW);
+int lp_bn_forward(const float* d_x, const float* d_gamma, const float* d_beta, float* running_io, const float* d_res,
+                  float* y_out, double* stat_out, int N, int C, int HW, int act, int training, double momentum, double eps,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int lp_bn_backward(const float* d_grad_y, const float* d_x, const float* d_gamma, const float* d_beta, const double* d_stat,
+                   float* grad_x_out, float* grad_gamma_out, float* grad_beta_out, int N, int C, int HW, int act,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* Pointwise 1x1 without bias: y[n][co][p] = sum_ci w[co][ci] x[n][ci][p]; d_x [N,Cin,HW], d_w [Cout,Cin], y_out [N,Cout,HW].
+ * The forward and the data gradient (the same kernel on the transposed weight) run on v_mfma_f32_32x32x2_f32 from A
+ * fragments a device kernel packs into the workspace; the weight gradient grad_w[co][ci] = sum_{n,p} grad_y[n][co][p] *
+ * x[n][ci][p] is a GEMM over the N * HW pixels on the same instruction, cut into slices of LP_PW_WGRAD_SLICE pixels
+ * (pixel = n * HW + p; the last slice may be shorter) whose fp32 partials are added in index order in fp64 and rounded once.
+ * lp_pw_backward: grad_x_out or grad_w_out may be NULL (not both): only the other gradient is computed, and the
+ * workspace (lp_pw_backward_workspace_bytes with the matching want_x / want_w flags) holds only its share.  d_x is read
+ * only for grad_w_out, d_w only for grad_x_out (each may be NULL when not read).
+ * Writes: lp_pw_forward every element of y_out; lp_pw_backward every element of each output given.                     */
+#define LP_PW_WGRAD_SLICE 1024
+size_t lp_pw_forward_workspace_bytes(int Cin, int Cout);
+int lp_pw_forward(const float* d_x, const float* d_w, float* y_out, int N, int Cin, int Cout, int HW, void* workspace,
+                  size_t workspace_bytes, void* stream);
+size_t lp_pw_backward_workspace_bytes(int N, int Cin, int Cout, int HW, int want_x, int want_w);
+int lp_pw_backward(const float* d_grad_y, const float* d_x, const float* d_w, float* grad_x_out, float* grad_w_out, int N,
+                   int Cin, int Cout, int HW, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Depthwise K x K (K 3, 5 or 7), stride S 1 or 2, padding K / 2, without bias: d_x [N,C,H,W], d_w [C,K,K], y_out
+ * [N,C,OH,OW] with OH = (H - 1) / S + 1, OW likewise.  S = 2 is defined for even H and W only (LP_ERR_INVALID_ARG).
+ * The data gradient gathers, per input cell, the output taps that land on it, in (ky, kx) order; the weight gradient
+ * sums per (channel, slice of LP_DW_WGRAD_SLICE units) in a fixed tree -- a unit is one 16x16 output tile of one image,
+ * unit = n * tiles + tile, tiles = ceil(OH / 16) * ceil(OW / 16) -- and adds the fp32 partials of the slices in index
+ * order in fp64, rounded once.  lp_dw_backward: grad_x_out or grad_w_out may be NULL (not both); the workspace serves
+ * grad_w_out only (lp_dw_backward_workspace_bytes is 0 with want_w == 0, and the workspace may then be NULL).  d_x is read
+ * only for grad_w_out, d_w only for grad_x_out.
+ * Writes: lp_dw_forward every element of y_out; lp_dw_backward every element of each output given.                     */
+#define LP_DW_WGRAD_SLICE 8
+size_t lp_dw_forward_workspace_bytes(int C, int K);
+int lp_dw_forward(const float* d_x, const float* d_w, float* y_out, int N, int C, int H, int W, int K, int S,
+                  void* workspace, size_t workspace_bytes, void* stream);
+size_t lp_dw_backward_workspace_bytes(int N, int C, int H, int W, int K, int S, int want_w);
+int lp_dw_backward(const float* d_grad_y, const float* d_x, const float* d_w, float* grad_x_out, float* grad_w_out, int N,
+                   int C, int H, int W, int K, int S, void* workspace, size_t workspace_bytes, void* stream);
+
 /* utils.transforms.get_final_preds (lib/utils/transforms.py:195-202,50-56): inverse
  * affine (rot 0) heatmap -> image coordinates, in place on x,y of d_ans.
  * h_center [2], h_scale [2] as returned by get_multi_scale_size, heatmap size (Wp,Hp).

@@ -158,6 +158,17 @@ _SIGS = {
                            vp, sz, vp]),
     'lp_pose_loss_grad': (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp,
                                 vp, vp, vp]),
+    'lp_bn_workspace_bytes': (sz, [i32, i32, i32]),
+    'lp_bn_forward': (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_double, C.c_double, vp, sz, vp]),
+    'lp_bn_backward': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+    'lp_pw_forward_workspace_bytes': (sz, [i32, i32]),
+    'lp_pw_forward': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+    'lp_pw_backward_workspace_bytes': (sz, [i32, i32, i32, i32, i32, i32]),
+    'lp_pw_backward': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+    'lp_dw_forward_workspace_bytes': (sz, [i32, i32]),
+    'lp_dw_forward': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    'lp_dw_backward_workspace_bytes': (sz, [i32, i32, i32, i32, i32, i32, i32]),
+    'lp_dw_backward': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     'lp_stream_abort_capture': (i32, [vp]),
     'lp_final_preds': (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                              i32, i32, vp]),

@@ -47,9 +47,11 @@ SOURCES = [
     ('eval_kernels.hip', ['-ffp-contract=off'] + NOPK),    # COCOeval's fp64 expressions, one IEEE operation each
     ('vis_api.cpp', []),
     ('train_api.cpp', []),
+    ('layer_api.cpp', []),
     ('target_kernels.hip', ['-ffp-contract=off'] + NOPK),  # the fp64 joint transform and cv2's fixed-point warp, operation by operation
     ('loss_kernels.hip', ['-ffp-contract=off'] + NOPK),    # fp64 products and sums round separately, as the restatement's do
     ('vis_kernels.hip', NOPK),                             # integer raster; floats are only loaded, compared, truncated
+    ('layer_kernels.hip', NOPK),                           # no hand-placed packed FMAs: fp32 MFMA, scalar FMAs, fp64 sums
 ]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value',
           '-Wno-pass-failed']

@@ -15,10 +15,6 @@
 
 namespace lp {
 
-namespace {
-
-struct BnCut { int S, chunk, vec; };
-
 // slices of one channel: its N planes are ONE range of N * units units (float4s or floats; unit u = plane u / units,
 // offset u % units), cut into S chunks of `chunk` units.  A 16x16 plane is 64 float4s: cutting planes instead would leave
 // three lanes of four idle on the deep stages, where most of the BatchNorm layers are.
@@ -34,8 +30,6 @@ BnCut bn_cut(int N, int C, int HW) {
     k.S = (int)((total + k.chunk - 1) / k.chunk);
     return k;
 }
-
-}  // namespace
 
 // conv 3x3 stride 2 pad 1, 3 -> 32, raw (no bias, no activation): stem_kernel's loop without its epilogue
 __global__ __launch_bounds__(256) void stem_raw_kernel(const float* __restrict__ x, const float* __restrict__ w,

@@ -175,6 +175,8 @@ void launch_deconv_raw(const float* inA, int Ca, const float* inB, int Cb, const
                        int w_, int Cout, hipStream_t s);
 // batch statistics of x [N,C,HW]: per-channel partial (sum, sum of squares) pairs in fp64 -> part
 // (bn_partial_doubles(N, C, HW) doubles, 16-byte aligned), one per workgroup, combined by launch_bn_apply in index order
+struct BnCut { int S, chunk, vec; };     // S slices of `chunk` units (float4s when vec, else floats) per channel: grid (S, C)
+BnCut bn_cut(int N, int C, int HW);
 size_t bn_partial_doubles(int N, int C, int HW);
 void launch_bn_stats(const float* x, double* part, int N, int C, int HW, hipStream_t s);
 // in place: x = act((x - mean) * rsqrt(var + eps) * gamma + beta) (+ res) with the batch's mean / biased variance, and
@@ -391,5 +393,29 @@ void launch_heat_grad(const float* pred, const float* gt, const float* mask, con
 void launch_tag_grad(const float* out, int N, int C, int R, int tag_offset, const int* joints, int M, int J, int loss_type,
                      double push_factor, double pull_factor, const float* g_push, const float* g_pull, float* grad,
                      hipStream_t s);
+
+// ---- training-mode layers (layer_kernels.hip; lp_bn_* / lp_pw_* / lp_dw_*, layer_api.cpp) ------
+// y = act(gamma * (x - mean) * invstd + beta) (+ res), out of place.  training: after launch_bn_stats(x, part) on the same
+// stream; writes stat = [mean | invstd] x C (fp64) and moves running = [mean | var] x C.  !training: the running pair is the
+// statistics; part and stat are not touched
+void launch_bn_fwd(const float* x, const float* res, const double* part, const float* gamma, const float* beta,
+                   float* running, float* y, double* stat, int N, int C, int HW, int act, bool training, double momentum,
+                   double eps, hipStream_t s);
+// two launches: the per-workgroup (sum g, sum g * xhat) partials -> part (bn_partial_doubles), then dx, dgamma, dbeta
+void launch_bn_bwd(const float* dy, const float* x, const float* gamma, const float* beta, const double* stat, double* part,
+                   float* dx, float* dgamma, float* dbeta, int N, int C, int HW, int act, hipStream_t s);
+// w [Cout][Cin] (transpose: its transpose) -> launch_pw's A fragments [ceil(M/32)][(K+1)/2][64] and ceil(M/32) * 32 zeros
+void launch_pw_pack(const float* w, int Cout, int Cin, bool transpose, float* wp, float* zb, hipStream_t s);
+// w [C][K*K] -> launch_dw's wdup [C][K*K][2] and C zeros
+void launch_dw_pack(const float* w, int C, int K, float* wdup, float* zb, hipStream_t s);
+// dw [Cout][Cin] = sum over n, p of dy[n][co][p] * x[n][ci][p]; part: pw_wgrad_slices(N * HW) * Cout * Cin floats
+int pw_wgrad_slices(long NP);
+void launch_pw_wgrad(const float* dy, const float* x, float* part, float* dw, int N, int HW, int Cout, int Cin,
+                     hipStream_t s);
+// depthwise K 3/5/7, stride S 1/2 (S = 2: even H, W): dx [N,C,H,W] and / or dw [C][K*K] (either may be null); part:
+// dw_wgrad_slices(N, OH, OW) * C * K * K floats, needed for dw only
+int dw_wgrad_slices(int N, int OH, int OW);
+void launch_dw_backward(const float* dy, const float* x, const float* w, float* dx, float* part, float* dw, int N, int C,
+                        int H, int W, int K, int S, hipStream_t s);
 
 }  // namespace lp

@@ -1,0 +1,205 @@
+"""The three layer kinds of a LitePose block as differentiable functions on the device (include/litepose_amd.h,
+"training-mode layers"): ``pointwise``, ``depthwise`` and ``batch_norm_act``, each a ``torch.autograd.Function`` over one
+forward and one backward call of the C ABI.  float32 CUDA tensors, NCHW; a tensor of another kind is an error, there is no
+other path.
+
+What an op keeps between forward and backward is what its backward reads: the raw input (and the weight, which lives on
+anyway), and for BatchNorm the fp64 ``(mean, invstd)`` pair of the batch.  The BatchNorm output is not kept: the backward
+recomputes ``z`` by the forward's own expression to find the cells the activation passed.  Every sum has one order that
+depends on the shapes only: two backward calls give the same bits."""
+import torch
+
+from .. import _native as nv
+
+ACTS = {None: 0, 'none': 0, 'relu': 1, 'relu6': 2}
+
+
+def _f32(t, name, dim=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda:
+        raise ValueError('%s must be a float32 CUDA tensor' % name)
+    if dim is not None and t.dim() != dim:
+        raise ValueError('%s must have %d dimensions' % (name, dim))
+    return t.detach().contiguous()
+
+
+def _ws(nbytes, device):
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+# ---------------------------------------------------------------------------------- 1x1
+def pw_forward(x, w):
+    x, w = _f32(x, 'x', 4), _f32(w.reshape(w.shape[0], -1), 'w', 2)
+    N, Cin, H, W = (int(v) for v in x.shape)
+    Cout = int(w.shape[0])
+    if int(w.shape[1]) != Cin:
+        raise ValueError('w must be [Cout, %d(, 1, 1)]' % Cin)
+    y = torch.empty((N, Cout, H, W), dtype=torch.float32, device=x.device)
+    L = nv.lib()
+    ws = _ws(L.lp_pw_forward_workspace_bytes(Cin, Cout), x.device)
+    nv.check(L.lp_pw_forward(nv.dptr(x), nv.dptr(w), nv.dptr(y), N, Cin, Cout, H * W, nv.dptr(ws), ws.numel(),
+                             nv.stream_ptr()), 'lp_pw_forward')
+    return y
+
+
+def pw_backward(grad_y, x, w, need_x=True, need_w=True):
+    """-> (grad_x or None, grad_w [Cout, Cin] or None)"""
+    grad_y, x, w = _f32(grad_y, 'grad_y', 4), _f32(x, 'x', 4), _f32(w.reshape(w.shape[0], -1), 'w', 2)
+    N, Cin, H, W = (int(v) for v in x.shape)
+    Cout = int(w.shape[0])
+    if tuple(grad_y.shape) != (N, Cout, H, W) or int(w.shape[1]) != Cin:
+        raise ValueError('grad_y, x and w do not belong to one 1x1 convolution')
+    gx = torch.empty_like(x) if need_x else None
+    gw = torch.empty_like(w) if need_w else None
+    if not (need_x or need_w):
+        return None, None
+    L = nv.lib()
+    ws = _ws(L.lp_pw_backward_workspace_bytes(N, Cin, Cout, H * W, int(need_x), int(need_w)), x.device)
+    nv.check(L.lp_pw_backward(nv.dptr(grad_y), nv.dptr(x), nv.dptr(w), nv.dptr(gx), nv.dptr(gw), N, Cin, Cout, H * W,
+                              nv.dptr(ws), ws.numel(), nv.stream_ptr()), 'lp_pw_backward')
+    return gx, gw
+
+
+class _Pointwise(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w):
+        ctx.save_for_backward(x, w)
+        return pw_forward(x, w)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, w = ctx.saved_tensors
+        gx, gw = pw_backward(grad_y, x, w, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return gx, None if gw is None else gw.reshape(w.shape)
+
+
+def pointwise(x, w):
+    """1x1 convolution without bias: ``x`` [N,Cin,H,W], ``w`` [Cout,Cin] or [Cout,Cin,1,1] -> [N,Cout,H,W]."""
+    return _Pointwise.apply(x, w)
+
+
+# ---------------------------------------------------------------------------------- depthwise
+def _dw_dims(x, w, stride):
+    N, C, H, W = (int(v) for v in x.shape)
+    K = int(w.shape[-1])
+    if w.numel() != C * K * K or int(w.shape[0]) != C:
+        raise ValueError('w must be [%d(, 1), K, K]' % C)
+    return N, C, H, W, K, int(stride)
+
+
+def dw_forward(x, w, stride=1):
+    x, w = _f32(x, 'x', 4), _f32(w, 'w')
+    N, C, H, W, K, S = _dw_dims(x, w, stride)
+    y = torch.empty((N, C, (H - 1) // S + 1, (W - 1) // S + 1), dtype=torch.float32, device=x.device)
+    L = nv.lib()
+    ws = _ws(L.lp_dw_forward_workspace_bytes(C, K), x.device)
+    nv.check(L.lp_dw_forward(nv.dptr(x), nv.dptr(w), nv.dptr(y), N, C, H, W, K, S, nv.dptr(ws), ws.numel(),
+                             nv.stream_ptr()), 'lp_dw_forward')
+    return y
+
+
+def dw_backward(grad_y, x, w, stride=1, need_x=True, need_w=True):
+    """-> (grad_x or None, grad_w of w's shape or None)"""
+    grad_y, x, w = _f32(grad_y, 'grad_y', 4), _f32(x, 'x', 4), _f32(w, 'w')
+    N, C, H, W, K, S = _dw_dims(x, w, stride)
+    if tuple(grad_y.shape) != (N, C, (H - 1) // S + 1, (W - 1) // S + 1):
+        raise ValueError('grad_y does not have the shape of the output')
+    if not (need_x or need_w):
+        return None, None
+    gx = torch.empty_like(x) if need_x else None
+    gw = torch.empty_like(w) if need_w else None
+    L = nv.lib()
+    ws = _ws(L.lp_dw_backward_workspace_bytes(N, C, H, W, K, S, int(need_w)), x.device)
+    nv.check(L.lp_dw_backward(nv.dptr(grad_y), nv.dptr(x), nv.dptr(w), nv.dptr(gx), nv.dptr(gw), N, C, H, W, K, S,
+                              nv.dptr(ws), ws.numel(), nv.stream_ptr()), 'lp_dw_backward')
+    return gx, gw
+
+
+class _Depthwise(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, stride):
+        ctx.save_for_backward(x, w)
+        ctx.stride = stride
+        return dw_forward(x, w, stride)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, w = ctx.saved_tensors
+        gx, gw = dw_backward(grad_y, x, w, ctx.stride, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return gx, gw, None
+
+
+def depthwise(x, w, stride=1):
+    """Depthwise K x K convolution (K 3, 5 or 7), padding K // 2, ``stride`` 1 or 2 (even planes), without bias:
+    ``x`` [N,C,H,W], ``w`` [C,K,K] or [C,1,K,K]."""
+    return _Depthwise.apply(x, w, stride)
+
+
+# ---------------------------------------------------------------------------------- BatchNorm + act (+ residual)
+def bn_forward(x, gamma, beta, running, act=None, residual=None, training=True, momentum=0.1, eps=1e-5):
+    """``running``: float32 [2, C] = running_mean | running_var, moved in place when ``training``.
+    -> (y, stat): stat float64 [2, C] = mean | invstd of the batch, None in eval mode."""
+    x, gamma, beta = _f32(x, 'x', 4), _f32(gamma, 'gamma', 1), _f32(beta, 'beta', 1)
+    N, C, H, W = (int(v) for v in x.shape)
+    if gamma.numel() != C or beta.numel() != C or tuple(running.shape) != (2, C) or running.dtype != torch.float32:
+        raise ValueError('gamma, beta must be [C] and running float32 [2, C]')
+    if residual is not None:
+        residual = _f32(residual, 'residual', 4)
+        if residual.shape != x.shape:
+            raise ValueError('residual must have the shape of x')
+    y = torch.empty_like(x)
+    L = nv.lib()
+    stat = ws = None
+    if training:
+        stat = torch.empty((2, C), dtype=torch.float64, device=x.device)
+        ws = _ws(L.lp_bn_workspace_bytes(N, C, H * W), x.device)
+    nv.check(L.lp_bn_forward(nv.dptr(x), nv.dptr(gamma), nv.dptr(beta), nv.dptr(running), nv.dptr(residual), nv.dptr(y),
+                             nv.dptr(stat), N, C, H * W, ACTS[act], int(bool(training)), float(momentum), float(eps),
+                             nv.dptr(ws), 0 if ws is None else ws.numel(), nv.stream_ptr()), 'lp_bn_forward')
+    return y, stat
+
+
+def bn_backward(grad_y, x, gamma, beta, stat, act=None):
+    """-> (grad_x, grad_gamma, grad_beta); the residual's gradient is ``grad_y`` itself."""
+    grad_y, x, gamma, beta = _f32(grad_y, 'grad_y', 4), _f32(x, 'x', 4), _f32(gamma, 'gamma', 1), _f32(beta, 'beta', 1)
+    N, C, H, W = (int(v) for v in x.shape)
+    if grad_y.shape != x.shape or tuple(stat.shape) != (2, C) or stat.dtype != torch.float64:
+        raise ValueError('grad_y must have the shape of x, stat must be float64 [2, C]')
+    gx, gg, gb = torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(beta)
+    L = nv.lib()
+    ws = _ws(L.lp_bn_workspace_bytes(N, C, H * W), x.device)
+    nv.check(L.lp_bn_backward(nv.dptr(grad_y), nv.dptr(x), nv.dptr(gamma), nv.dptr(beta), nv.dptr(stat.contiguous()),
+                              nv.dptr(gx), nv.dptr(gg), nv.dptr(gb), N, C, H * W, ACTS[act], nv.dptr(ws), ws.numel(),
+                              nv.stream_ptr()), 'lp_bn_backward')
+    return gx, gg, gb
+
+
+class _BatchNormAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, running_mean, running_var, act, training, momentum, eps):
+        running = torch.stack([running_mean.detach(), running_var.detach()]).float().contiguous()
+        y, stat = bn_forward(x, gamma, beta, running, act, residual, training, momentum, eps)
+        if training:
+            running_mean.copy_(running[0])
+            running_var.copy_(running[1])
+            ctx.save_for_backward(x, gamma, beta, stat)
+        ctx.act, ctx.training, ctx.has_res = act, training, residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        if not ctx.training:
+            raise NotImplementedError('backward through an eval-mode batch_norm_act is not part of the library')
+        x, gamma, beta, stat = ctx.saved_tensors
+        gx, gg, gb = bn_backward(grad_y, x, gamma, beta, stat, ctx.act)
+        return gx, gg, gb, (grad_y if ctx.has_res else None), None, None, None, None, None, None
+
+
+def batch_norm_act(x, gamma, beta, running_mean, running_var, act=None, residual=None, training=True, momentum=0.1,
+                   eps=1e-5):
+    """``act(batch_norm(x)) (+ residual)``, ``act`` None / 'relu' / 'relu6'.  Training mode normalises with the batch's
+    statistics and moves ``running_mean`` / ``running_var`` in place (the unbiased variance, as torch); eval mode
+    normalises with the running pair, and a backward through it raises ``NotImplementedError``."""
+    if act not in ACTS:
+        raise ValueError('act must be one of %s' % sorted(k for k in ACTS if k))
+    return _BatchNormAct.apply(x, gamma, beta, residual, running_mean, running_var, act, bool(training), float(momentum),
+                               float(eps))

@@ -1,0 +1,165 @@
+"""The buffer contract of the training-mode layer calls (include/litepose_amd.h, "training-mode layers") with the poisoned
+and guarded buffers of tests/_poison.py: every call writes exactly the elements its header comment names -- whatever the
+outputs and the workspace held before (zeros, NaN, a huge finite value) the results are the same bits -- and nothing in
+the guards around outputs, inputs and a workspace of exactly ``*_workspace_bytes``; one byte less answers LP_ERR_WORKSPACE.
+Covers the nullable-output forms of lp_pw_backward / lp_dw_backward and both modes of lp_bn_forward."""
+import pytest
+import torch
+
+import _poison as po
+from litepose_amd import _native as nv
+
+pytestmark = pytest.mark.gpu
+LP_ERR_WORKSPACE = -6
+
+
+def _g(shape, seed, scale=1.0):
+    return (torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * scale).cuda()
+
+
+def _contract(run):
+    """run(arena) -> (rc, {name: output view}): the Z run is the reference, N and H must give the same bits, leave no poison
+    in an output and no mark in a guard."""
+    ref = None
+    for pat in po.PATTERNS:
+        A = po.Arena(pat)
+        rc, outs = run(A)
+        assert rc == 0, nv.lib().lp_last_error()
+        A.check()
+        if ref is None:
+            ref = {k: v.clone() for k, v in outs.items()}
+            continue
+        for k, v in outs.items():
+            assert po.still_poisoned(v, ref[k], pat) == [], (k, pat)
+            assert po.bitwise_equal(v, ref[k]), (k, pat, po.first_difference(v, ref[k]))
+
+
+@pytest.mark.parametrize('want', ['both', 'x', 'w'])
+@pytest.mark.parametrize('shape', [(3, 6, 14, 37 * 41), (2, 40, 28, 32 * 36)], ids=['scalar', 'vec'])
+def test_pointwise_calls(shape, want):
+    L = nv.lib()
+    N, Cin, Cout, HW = shape
+    x, w, dy = _g((N, Cin, HW), 1), _g((Cout, Cin), 2, 0.3), _g((N, Cout, HW), 3)
+    s = nv.stream_ptr()
+
+    def fwd(A):
+        y = A.out((N, Cout, HW), what='y_out')
+        ws = A.ws(L.lp_pw_forward_workspace_bytes(Cin, Cout))
+        rc = L.lp_pw_forward(nv.dptr(A.inp(x, what='x')), nv.dptr(A.inp(w, what='w')), nv.dptr(y), N, Cin, Cout, HW,
+                             nv.dptr(ws), ws.numel(), s)
+        return rc, dict(y=y)
+
+    def bwd(A):
+        wx, ww = want in ('both', 'x'), want in ('both', 'w')
+        gx = A.out((N, Cin, HW), what='grad_x_out') if wx else None
+        gw = A.out((Cout, Cin), what='grad_w_out') if ww else None
+        need = L.lp_pw_backward_workspace_bytes(N, Cin, Cout, HW, int(wx), int(ww))
+        ws = A.ws(need)
+        args = (nv.dptr(A.inp(dy, what='grad_y')), nv.dptr(A.inp(x, what='x')) if ww else None,
+                nv.dptr(A.inp(w, what='w')) if wx else None, nv.dptr(gx), nv.dptr(gw), N, Cin, Cout, HW, nv.dptr(ws))
+        assert L.lp_pw_backward(*args, need - 1, s) == LP_ERR_WORKSPACE
+        return L.lp_pw_backward(*args, need, s), {k: v for k, v in (('gx', gx), ('gw', gw)) if v is not None}
+
+    if want == 'both':
+        _contract(fwd)
+        A = po.Arena('N')
+        need = L.lp_pw_forward_workspace_bytes(Cin, Cout)
+        assert L.lp_pw_forward(nv.dptr(x), nv.dptr(w), nv.dptr(A.out((N, Cout, HW))), N, Cin, Cout, HW,
+                               nv.dptr(A.ws(need)), need - 1, s) == LP_ERR_WORKSPACE
+    _contract(bwd)
+    assert L.lp_pw_backward(nv.dptr(dy), nv.dptr(x), nv.dptr(w), None, None, N, Cin, Cout, HW, nv.dptr(x), 1 << 20, s) == -1
+
+
+@pytest.mark.parametrize('want', ['both', 'x', 'w'])
+@pytest.mark.parametrize('shape', [(3, 8, 6, 10, 3, 1), (2, 8, 40, 24, 7, 2), (3, 4, 16, 16, 5, 1), (19, 4, 32, 32, 5, 2)],
+                         ids=['k3s1', 'k7s2', 'k5s1-16x16', 'k5s2-slices'])
+def test_depthwise_calls(shape, want):
+    L = nv.lib()
+    N, Cc, H, W, K, S = shape
+    OH, OW = (H - 1) // S + 1, (W - 1) // S + 1
+    x, w, dy = _g((N, Cc, H, W), 4), _g((Cc, K, K), 5, 0.3), _g((N, Cc, OH, OW), 6)
+    s = nv.stream_ptr()
+
+    def fwd(A):
+        y = A.out((N, Cc, OH, OW), what='y_out')
+        ws = A.ws(L.lp_dw_forward_workspace_bytes(Cc, K))
+        rc = L.lp_dw_forward(nv.dptr(A.inp(x, what='x')), nv.dptr(A.inp(w, what='w')), nv.dptr(y), N, Cc, H, W, K, S,
+                             nv.dptr(ws), ws.numel(), s)
+        return rc, dict(y=y)
+
+    def bwd(A):
+        wx, ww = want in ('both', 'x'), want in ('both', 'w')
+        gx = A.out((N, Cc, H, W), what='grad_x_out') if wx else None
+        gw = A.out((Cc, K, K), what='grad_w_out') if ww else None
+        need = L.lp_dw_backward_workspace_bytes(N, Cc, H, W, K, S, int(ww))
+        assert (need > 0) == ww
+        ws = A.ws(need) if ww else None
+        args = (nv.dptr(A.inp(dy, what='grad_y')), nv.dptr(A.inp(x, what='x')) if ww else None,
+                nv.dptr(A.inp(w, what='w')) if wx else None, nv.dptr(gx), nv.dptr(gw), N, Cc, H, W, K, S, nv.dptr(ws))
+        if ww:
+            assert L.lp_dw_backward(*args, need - 1, s) == LP_ERR_WORKSPACE
+        return L.lp_dw_backward(*args, need, s), {k: v for k, v in (('gx', gx), ('gw', gw)) if v is not None}
+
+    if want == 'both':
+        _contract(fwd)
+        A = po.Arena('N')
+        need = L.lp_dw_forward_workspace_bytes(Cc, K)
+        assert L.lp_dw_forward(nv.dptr(x), nv.dptr(w), nv.dptr(A.out((N, Cc, OH, OW))), N, Cc, H, W, K, S,
+                               nv.dptr(A.ws(need)), need - 1, s) == LP_ERR_WORKSPACE
+    _contract(bwd)
+
+
+@pytest.mark.parametrize('with_res', [False, True], ids=['plain', 'res'])
+@pytest.mark.parametrize('shape', [(3, 3, 35), (2, 32, 1024)], ids=['scalar', 'vec'])
+def test_batch_norm_calls(shape, with_res):
+    L = nv.lib()
+    N, Cc, HW = shape
+    x, gamma, beta, res, dy = _g((N, Cc, HW), 7), _g((Cc,), 8) + 1, _g((Cc,), 9), _g((N, Cc, HW), 10), _g((N, Cc, HW), 11)
+    running0 = torch.stack([_g((Cc,), 12, 0.2), _g((Cc,), 13, 0.1).abs() + 1])
+    need = L.lp_bn_workspace_bytes(N, Cc, HW)
+    s = nv.stream_ptr()
+    kept = {}
+
+    def fwd(training):
+        def run(A):
+            y = A.out((N, Cc, HW), what='y_out')
+            stat = A.out((2, Cc), torch.float64, what='stat_out')
+            rp, running = po.wrap_input(running0, 256, 'Z')           # in / out: its own guards, checked below
+            ws = A.ws(need)
+            rc = L.lp_bn_forward(nv.dptr(A.inp(x, what='x')), nv.dptr(A.inp(gamma, what='gamma')),
+                                 nv.dptr(A.inp(beta, what='beta')), nv.dptr(running),
+                                 nv.dptr(A.inp(res, what='res')) if with_res else None, nv.dptr(y), nv.dptr(stat), N, Cc, HW, 2,
+                                 training, 0.1, 1e-5, nv.dptr(ws), need, s)
+            torch.cuda.synchronize()
+            rp.check_guards('running_io')
+            if training:
+                kept['stat'] = stat.clone()
+                return rc, dict(y=y, stat=stat, running=running)
+            # eval mode: stat_out, running_io and the workspace are left as they were
+            assert po.bitwise_equal(running, running0)
+            assert po.bitwise_equal(stat, po.fill(torch.empty_like(stat), A.pattern))
+            assert po.bitwise_equal(ws, po.fill(torch.empty_like(ws), A.pattern))
+            return rc, dict(y=y)
+        return run
+
+    def bwd(A):
+        gx = A.out((N, Cc, HW), what='grad_x_out')
+        gg, gb = A.out((Cc,), what='grad_gamma_out'), A.out((Cc,), what='grad_beta_out')
+        ws = A.ws(need)
+        args = (nv.dptr(A.inp(dy, what='grad_y')), nv.dptr(A.inp(x, what='x')), nv.dptr(A.inp(gamma, what='gamma')),
+                nv.dptr(A.inp(beta, what='beta')), nv.dptr(A.inp(kept['stat'], what='stat')), nv.dptr(gx), nv.dptr(gg),
+                nv.dptr(gb), N, Cc, HW, 2, nv.dptr(ws))
+        assert L.lp_bn_backward(*args, need - 1, s) == LP_ERR_WORKSPACE
+        return L.lp_bn_backward(*args, need, s), dict(gx=gx, gg=gg, gb=gb)
+
+    _contract(fwd(1))
+    _contract(fwd(0))
+    _contract(bwd)
+    A = po.Arena('N')
+    assert L.lp_bn_forward(nv.dptr(x), nv.dptr(gamma), nv.dptr(beta), nv.dptr(running0.clone()), None,
+                           nv.dptr(A.out((N, Cc, HW))), nv.dptr(A.out((2, Cc), torch.float64)), N, Cc, HW, 2, 1, 0.1, 1e-5,
+                           nv.dptr(A.ws(need)), need - 1, s) == LP_ERR_WORKSPACE
+    # eval mode takes no workspace and no stat_out at all
+    y = torch.empty_like(x)
+    assert L.lp_bn_forward(nv.dptr(x), nv.dptr(gamma), nv.dptr(beta), nv.dptr(running0.clone()), None, nv.dptr(y), None, N,
+                           Cc, HW, 2, 0, 0.1, 1e-5, None, 0, s) == 0

@@ -755,6 +755,8 @@ int lp_pose_loss_grad(const float* d_out, int N, int C, int R, int J, int tag_of
  * The writable pointers are DEVICE memory like every d_* pointer of this header; they do not carry the prefix because
  * the census of writable calls (tests/test_poison_cpu.py) keys on it; their contract test is
  * tests/test_gpu_layer_buffers.py.
+ * Below them, under the same rules, the two dense layers of the network: the stem convolution (lp_stem_*) and the pair of
+ * transposed convolutions of a Fusion Deconv Head level (lp_deconv_*); contract test tests/test_gpu_conv_grad_buffers.py.
  *
  * BatchNorm + activation (+ residual), act 0 none / 1 ReLU / 2 ReLU6:
  *   y = act(gamma * (x - mean) * invstd + beta) (+ res),  d_x, d_res (may be NULL), y_out [N,C,HW]; d_gamma, d_beta [C];
@@ -811,6 +813,60 @@ int lp_dw_forward(const float* d_x, const float* d_w, float* y_out, int N, int C
 size_t lp_dw_backward_workspace_bytes(int N, int C, int H, int W, int K, int S, int want_w);
 int lp_dw_backward(const float* d_grad_y, const float* d_x, const float* d_w, float* grad_x_out, float* grad_w_out, int N,
                    int C, int H, int W, int K, int S, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The stem: dense 3x3 convolution, stride 2, padding 1, 3 -> 32 channels, without bias (first.0.0): d_x [N,3,H,W], d_w
+ * [32,3,3,3], y_out [N,32,H/2,W/2]; even H and W only (LP_ERR_INVALID_ARG), H, W <= 16384 and N * (H/2) * (W/2) at most
+ * 2^31 - 256 (LP_ERR_UNSUPPORTED).  The forward is one fused multiply-add chain of 27 terms per output, no workspace.
+ * lp_stem_backward is the weight gradient only (the image never needs one): grad_w[co][ci][ky][kx] = sum over (n, oy, ox)
+ * of grad_y[n][co][oy][ox] * x[n][ci][2oy-1+ky][2ox-1+kx], a 32 x 27 GEMM on v_mfma_f32_32x32x2_f32 whose reduction runs
+ * over the output pixels, taken in tiles of 8 x 16 pixels (unit = n * tiles + tile, tiles = ceil(H/2 / 8) * ceil(W/2 / 16),
+ * a tile at the plane's edge counts all its 128 pixels) and cut into slices of LP_STEM_WGRAD_SLICE pixels (16 tiles; the
+ * last slice may be shorter); the fp32 partials [slices][32][27] are added in index order in fp64 and rounded once.  A tap
+ * that only ever meets padding is exactly zero.  2048: the layer has one 32 x 32 tile of work per pixel set, so the slice
+ * count alone fills the chip (512 workgroups at N = 64, 256 x 256) while a slice still runs 16 x 16 MFMAs per wave
+ * between its start and its 3.4 KB partial.
+ * lp_stem_backward_workspace_bytes = slices * 864 * 4.
+ * Writes: lp_stem_forward every element of y_out; lp_stem_backward every element of grad_w_out [32,3,3,3].              */
+#define LP_STEM_WGRAD_SLICE 2048
+int lp_stem_forward(const float* d_x, const float* d_w, float* y_out, int N, int H, int W, void* stream);
+size_t lp_stem_backward_workspace_bytes(int N, int H, int W);
+int lp_stem_backward(const float* d_grad_y, const float* d_x, float* grad_w_out, int N, int H, int W, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
+/* The pair of ConvTranspose2d(kernel 4, stride 2, padding 1) without bias of one Fusion Deconv Head level, summed:
+ * y = ConvT(xa, wa) + ConvT(xb, wb); d_xa [N,Ca,h,w], d_xb [N,Cb,h,w], d_wa [Ca,Cout,4,4], d_wb [Cb,Cout,4,4], y_out
+ * [N,Cout,2h,2w]: output cell (oy, ox) receives x[iy][ix] * w[ky][kx] where oy = 2 iy - 1 + ky, ox = 2 ix - 1 + kx.
+ * Cb = 0 is the one-source form: d_xb, d_wb, grad_xb_out and grad_wb_out must then all be NULL (LP_ERR_INVALID_ARG).
+ * Ca >= 1, Cout >= 1; Ca + Cb and Cout <= 65535, h, w <= 16384, N * 4 h w, (Ca + Cb) * h * w, Cout * 4 h w and
+ * (Ca + Cb) * Cout * 16 at most 2^31 - 256 (LP_ERR_UNSUPPORTED).
+ * lp_deconv_forward copies both weights into one [Ca+Cb][Cout][16] block in its workspace (lp_deconv_forward_workspace_bytes
+ * = (Ca + Cb) * Cout * 64) and sums, per output, the 4 (Ca + Cb) terms that reach it in one fused multiply-add chain (a
+ * term that meets padding is a zero product).
+ * lp_deconv_backward: the data-gradient pair grad_xa_out / grad_xb_out is given or NULL together (grad_xb_out stays NULL
+ * with Cb = 0), and so is the weight-gradient pair grad_wa_out / grad_wb_out; passing neither pair is an error.  d_xa / d_xb
+ * are read only for the weight gradients, d_wa / d_wb only for the data gradients (each may be NULL when not read).
+ *   data gradient    grad_x[n][ci][iy][ix] = sum over (co, ky, kx) of grad_y[n][co][2iy-1+ky][2ix-1+kx] * w[ci][co][ky][kx]: a
+ *                    gather on v_mfma_f32_32x32x2_f32 with K = 16 Cout, channels in index order; terms outside the plane
+ *                    are zero products
+ *   weight gradient  grad_w[ci][co][ky][kx] = sum over (n, iy, ix) of x[n][ci][iy][ix] * grad_y[n][co][2iy-1+ky][2ix-1+kx]:
+ *                    a GEMM on the same instruction whose reduction runs over the input cells, taken in tiles of 8 x 8
+ *                    cells (unit = n * tiles + tile, tiles = ceil(h / 8) * ceil(w / 8), a tile at the plane's edge counts
+ *                    all its 64 cells) and cut into slices of LP_DECONV_WGRAD_SLICE cells (16 tiles; the last slice may
+ *                    be shorter); fp32 partials [slices][Ca+Cb][Cout][16], added in index order in fp64, rounded once.
+ *                    A tap that only ever meets padding is exactly zero.  1024: a wave runs 16 x 32 MFMAs per 16-register
+ *                    partial, so the partials are 1/64 of the operand traffic, and the headline level (N = 64, 64 x 64
+ *                    cells) still has 256 slices x 6 tile groups to fill the chip.
+ * Both gradients stage the (2 * 8 + 2)^2 grad_y patch of a tile in LDS, zeros outside the plane.
+ * lp_deconv_backward_workspace_bytes = (want_x ? (Ca + Cb) * Cout * 64 : 0) + (want_w ? slices * (Ca + Cb) * Cout * 64 : 0).
+ * Writes: lp_deconv_forward every element of y_out; lp_deconv_backward every element of each output given.            */
+#define LP_DECONV_WGRAD_SLICE 1024
+size_t lp_deconv_forward_workspace_bytes(int Ca, int Cb, int Cout);
+int lp_deconv_forward(const float* d_xa, const float* d_wa, const float* d_xb, const float* d_wb, float* y_out, int N,
+                      int Ca, int Cb, int Cout, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
+size_t lp_deconv_backward_workspace_bytes(int N, int Ca, int Cb, int Cout, int h, int w, int want_x, int want_w);
+int lp_deconv_backward(const float* d_grad_y, const float* d_xa, const float* d_wa, const float* d_xb, const float* d_wb,
+                       float* grad_xa_out, float* grad_xb_out, float* grad_wa_out, float* grad_wb_out, int N, int Ca,
+                       int Cb, int Cout, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
 
 /* utils.transforms.get_final_preds (lib/utils/transforms.py:195-202,50-56): inverse
  * affine (rot 0) heatmap -> image coordinates, in place on x,y of d_ans.

@@ -169,6 +169,13 @@ _SIGS = {
     'lp_dw_forward': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     'lp_dw_backward_workspace_bytes': (sz, [i32, i32, i32, i32, i32, i32, i32]),
     'lp_dw_backward': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    'lp_stem_forward': (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    'lp_stem_backward_workspace_bytes': (sz, [i32, i32, i32]),
+    'lp_stem_backward': (i32, [vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+    'lp_deconv_forward_workspace_bytes': (sz, [i32, i32, i32]),
+    'lp_deconv_forward': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    'lp_deconv_backward_workspace_bytes': (sz, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    'lp_deconv_backward': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     'lp_stream_abort_capture': (i32, [vp]),
     'lp_final_preds': (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                              i32, i32, vp]),

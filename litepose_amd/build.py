@@ -52,6 +52,7 @@ SOURCES = [
     ('loss_kernels.hip', ['-ffp-contract=off'] + NOPK),    # fp64 products and sums round separately, as the restatement's do
     ('vis_kernels.hip', NOPK),                             # integer raster; floats are only loaded, compared, truncated
     ('layer_kernels.hip', NOPK),                           # no hand-placed packed FMAs: fp32 MFMA, scalar FMAs, fp64 sums
+    ('conv_grad_kernels.hip', NOPK),                       # likewise: fp32 MFMA from LDS patches
 ]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value',
           '-Wno-pass-failed']

@@ -418,4 +418,21 @@ int dw_wgrad_slices(int N, int OH, int OW);
 void launch_dw_backward(const float* dy, const float* x, const float* w, float* dx, float* part, float* dw, int N, int C,
                         int H, int W, int K, int S, hipStream_t s);
 
+// out[i] = sum over s < S of part[s * stride + i] for i < count: fp64, index order, one rounding (slice_sum_kernel)
+void launch_slice_sum(const float* part, int S, int stride, int count, float* out, hipStream_t s);
+
+// ---- backward of the stem convolution and of the ConvTranspose2d(k4,s2,p1) pair (conv_grad_kernels.hip) ----
+// wa [Ca][Cout][16] | wb [Cb][Cout][16] (wb null with Cb = 0) -> wp [Ca+Cb][Cout][16], what launch_deconv_raw and the data
+// gradient read
+void launch_deconv_pack(const float* wa, const float* wb, float* wp, int Ca, int Cb, int Cout, hipStream_t s);
+// gxa / gxb [N,Ca|Cb,h,w] (both or neither; gxb null with Cb = 0; needs wp) and / or gwa / gwb [Ca|Cb][Cout][16] (likewise;
+// needs xa / xb and part: deconv_wgrad_slices(N, h, w) * (Ca + Cb) * Cout * 16 floats); dy [N,Cout,2h,2w]
+int deconv_wgrad_slices(int N, int h, int w);
+void launch_deconv_backward(const float* dy, const float* xa, const float* xb, const float* wp, float* gxa, float* gxb,
+                            float* part, float* gwa, float* gwb, int N, int Ca, int Cb, int Cout, int h, int w,
+                            hipStream_t s);
+// dw [32][27] of the stem from dy [N,32,H/2,W/2] and x [N,3,H,W] (even H, W); part: stem_wgrad_slices(N, H, W) * 864 floats
+int stem_wgrad_slices(int N, int H, int W);
+void launch_stem_wgrad(const float* dy, const float* x, float* part, float* dw, int N, int H, int W, hipStream_t s);
+
 }  // namespace lp

@@ -1,5 +1,6 @@
 // C ABI of the training-mode layers (include/litepose_amd.h, "training-mode layers"): argument validation and workspace
 // carving; the kernels live in layer_kernels.hip, the 1x1 and depthwise forwards are the network's own launch_pw / launch_dw.
+// The stem and the ConvTranspose2d pair: backward in conv_grad_kernels.hip, forwards the raw forms of calib_kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include "../../include/litepose_amd.h"
@@ -182,6 +183,122 @@ int lp_dw_backward(const float* d_grad_y, const float* d_x, const float* d_w, fl
     lp::launch_dw_backward(d_grad_y, d_x, d_w, grad_x_out, (float*)workspace, grad_w_out, N, C, H, W, K, S,
                            (hipStream_t)stream);
     if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "dw_backward launch failed");
+    return LP_OK;
+}
+
+// ---- the stem convolution and the ConvTranspose2d pair (conv_grad_kernels.hip; forwards in calib_kernels.hip) ----
+static bool stem_ok(int N, int H, int W) {
+    return N >= 1 && H >= 2 && W >= 2 && !((H | W) & 1) && H <= 16384 && W <= 16384 && !big((long long)N * (H / 2) * (W / 2));
+}
+
+static int stem_check(int N, int H, int W) {
+    if (N < 1 || H < 1 || W < 1) return fail(LP_ERR_INVALID_ARG, "N, H and W must be positive");
+    if ((H | W) & 1) return fail(LP_ERR_INVALID_ARG, "the stem is defined for even H and W only");
+    if (!stem_ok(N, H, W)) return fail(LP_ERR_UNSUPPORTED, "H, W <= 16384 and N * (H/2) * (W/2) at most 2^31 - 256");
+    return LP_OK;
+}
+
+int lp_stem_forward(const float* d_x, const float* d_w, float* y_out, int N, int H, int W, void* stream) {
+    if (int rc = stem_check(N, H, W)) return rc;
+    if (!d_x || !d_w || !y_out) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (!al16(d_x) || !al16(y_out)) return fail(LP_ERR_INVALID_ARG, "x and y must be 16-byte aligned");
+    lp::launch_stem_raw(d_x, d_w, y_out, N, H, W, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "stem_forward launch failed");
+    return LP_OK;
+}
+
+size_t lp_stem_backward_workspace_bytes(int N, int H, int W) {
+    if (!stem_ok(N, H, W)) return 0;
+    return (size_t)lp::stem_wgrad_slices(N, H, W) * 864 * sizeof(float);
+}
+
+int lp_stem_backward(const float* d_grad_y, const float* d_x, float* grad_w_out, int N, int H, int W, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    if (int rc = stem_check(N, H, W)) return rc;
+    if (!d_grad_y || !d_x || !grad_w_out) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (!al16(d_grad_y) || !al16(d_x)) return fail(LP_ERR_INVALID_ARG, "grad_y and x must be 16-byte aligned");
+    if (!workspace || workspace_bytes < lp_stem_backward_workspace_bytes(N, H, W)) return fail(LP_ERR_WORKSPACE, "stem workspace too small");
+    if (!al16(workspace)) return fail(LP_ERR_WORKSPACE, "stem workspace must be 16-byte aligned");
+    lp::launch_stem_wgrad(d_grad_y, d_x, (float*)workspace, grad_w_out, N, H, W, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "stem_backward launch failed");
+    return LP_OK;
+}
+
+static bool deconv_channels_ok(int Ca, int Cb, int Cout) {
+    return Ca >= 1 && Cb >= 0 && Cout >= 1 && (long long)Ca + Cb <= 65535 && Cout <= 65535 &&
+           !big((long long)(Ca + Cb) * Cout * 16);
+}
+
+static bool deconv_ok(int N, int Ca, int Cb, int Cout, int h, int w) {
+    return N >= 1 && h >= 1 && w >= 1 && deconv_channels_ok(Ca, Cb, Cout) && h <= 16384 && w <= 16384 &&
+           !big((long long)N * 4 * h * w) && !big((long long)(Ca + Cb) * h * w) && !big((long long)Cout * 4 * h * w);
+}
+
+static int deconv_check(int N, int Ca, int Cb, int Cout, int h, int w) {
+    if (N < 1 || Ca < 1 || Cb < 0 || Cout < 1 || h < 1 || w < 1)
+        return fail(LP_ERR_INVALID_ARG, "N, Ca, Cout, h and w must be positive, Cb non-negative");
+    if (!deconv_ok(N, Ca, Cb, Cout, h, w))
+        return fail(LP_ERR_UNSUPPORTED, "channels <= 65535, h, w <= 16384, N * 4hw, C * hw and (Ca + Cb) * Cout * 16 at most 2^31 - 256");
+    return LP_OK;
+}
+
+size_t lp_deconv_forward_workspace_bytes(int Ca, int Cb, int Cout) {
+    if (!deconv_channels_ok(Ca, Cb, Cout)) return 0;
+    return (size_t)(Ca + Cb) * Cout * 16 * sizeof(float);
+}
+
+int lp_deconv_forward(const float* d_xa, const float* d_wa, const float* d_xb, const float* d_wb, float* y_out, int N,
+                      int Ca, int Cb, int Cout, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = deconv_check(N, Ca, Cb, Cout, h, w)) return rc;
+    if (!d_xa || !d_wa || !y_out) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (Cb ? (!d_xb || !d_wb) : (d_xb || d_wb)) return fail(LP_ERR_INVALID_ARG, "d_xb and d_wb go with Cb > 0, and are NULL with Cb = 0");
+    if (!al16(d_xa) || !al16(d_xb) || !al16(y_out)) return fail(LP_ERR_INVALID_ARG, "xa, xb and y must be 16-byte aligned");
+    if (!workspace || workspace_bytes < lp_deconv_forward_workspace_bytes(Ca, Cb, Cout)) return fail(LP_ERR_WORKSPACE, "deconv workspace too small");
+    if (!al16(workspace)) return fail(LP_ERR_WORKSPACE, "deconv workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    float* wp = (float*)workspace;
+    lp::launch_deconv_pack(d_wa, d_wb, wp, Ca, Cb, Cout, s);
+    lp::launch_deconv_raw(d_xa, Ca, d_xb, Cb, wp, y_out, N, h, w, Cout, s);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "deconv_forward launch failed");
+    return LP_OK;
+}
+
+size_t lp_deconv_backward_workspace_bytes(int N, int Ca, int Cb, int Cout, int h, int w, int want_x, int want_w) {
+    if (!deconv_ok(N, Ca, Cb, Cout, h, w) || (!want_x && !want_w)) return 0;
+    const size_t wfl = (size_t)(Ca + Cb) * Cout * 16;
+    size_t fl = 0;
+    if (want_x) fl += wfl;
+    if (want_w) fl += (size_t)lp::deconv_wgrad_slices(N, h, w) * wfl;
+    return fl * sizeof(float);
+}
+
+int lp_deconv_backward(const float* d_grad_y, const float* d_xa, const float* d_wa, const float* d_xb, const float* d_wb,
+                       float* grad_xa_out, float* grad_xb_out, float* grad_wa_out, float* grad_wb_out, int N, int Ca,
+                       int Cb, int Cout, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = deconv_check(N, Ca, Cb, Cout, h, w)) return rc;
+    if (!d_grad_y || (!grad_xa_out && !grad_wa_out)) return fail(LP_ERR_INVALID_ARG, "null argument / no output requested");
+    if (Cb ? ((grad_xa_out != nullptr) != (grad_xb_out != nullptr) || (grad_wa_out != nullptr) != (grad_wb_out != nullptr))
+           : (d_xb || d_wb || grad_xb_out || grad_wb_out))
+        return fail(LP_ERR_INVALID_ARG, "each gradient pair is given or NULL together; every b pointer is NULL with Cb = 0");
+    if (grad_xa_out && (!d_wa || (Cb && !d_wb))) return fail(LP_ERR_INVALID_ARG, "the data gradients need d_wa / d_wb");
+    if (grad_wa_out && (!d_xa || (Cb && !d_xb))) return fail(LP_ERR_INVALID_ARG, "the weight gradients need d_xa / d_xb");
+    if (!al16(d_grad_y) || !al16(d_xa) || !al16(d_xb) || !al16(grad_xa_out) || !al16(grad_xb_out))
+        return fail(LP_ERR_INVALID_ARG, "grad_y, xa, xb, grad_xa and grad_xb must be 16-byte aligned");
+    const bool want_x = grad_xa_out != nullptr, want_w = grad_wa_out != nullptr;
+    if (!workspace || workspace_bytes < lp_deconv_backward_workspace_bytes(N, Ca, Cb, Cout, h, w, want_x, want_w))
+        return fail(LP_ERR_WORKSPACE, "deconv workspace too small");
+    if (!al16(workspace)) return fail(LP_ERR_WORKSPACE, "deconv workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    const float* wp = nullptr;
+    if (want_x) {
+        lp::launch_deconv_pack(d_wa, d_wb, ws, Ca, Cb, Cout, s);
+        wp = ws;
+        ws += (size_t)(Ca + Cb) * Cout * 16;
+    }
+    lp::launch_deconv_backward(d_grad_y, d_xa, d_xb, wp, grad_xa_out, grad_xb_out, ws, grad_wa_out, grad_wb_out, N, Ca, Cb,
+                               Cout, h, w, (hipStream_t)s);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "deconv_backward launch failed");
     return LP_OK;
 }
 

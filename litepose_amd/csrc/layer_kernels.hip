@@ -269,8 +269,8 @@ void launch_dw_pack(const float* w, int C, int K, float* wdup, float* zb, hipStr
     LP_LAUNCH(dw_pack_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, w, cnt, wdup, zb, C);
 }
 
-// out[i] = sum over the S slices of part[s][i], in index order, in fp64, rounded once
-__global__ __launch_bounds__(256) void slice_sum_kernel(const float* __restrict__ part, int S, int count,
+// out[i] = sum over the S slices of part[s * stride + i], i < count, in index order, in fp64, rounded once
+__global__ __launch_bounds__(256) void slice_sum_kernel(const float* __restrict__ part, int S, int stride, int count,
                                                         float* __restrict__ out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
@@ -279,12 +279,16 @@ __global__ __launch_bounds__(256) void slice_sum_kernel(const float* __restrict_
     for (; s + 32 <= S; s += 32) {                      // 32 loads in flight, then their adds in index order
         float v[32];
 #pragma unroll
-        for (int j = 0; j < 32; ++j) v[j] = part[(long)(s + j) * count + i];
+        for (int j = 0; j < 32; ++j) v[j] = part[(long)(s + j) * stride + i];
 #pragma unroll
         for (int j = 0; j < 32; ++j) a += (double)v[j];
     }
-    for (; s < S; ++s) a += (double)part[(long)s * count + i];
+    for (; s < S; ++s) a += (double)part[(long)s * stride + i];
     out[i] = (float)a;
+}
+
+void launch_slice_sum(const float* part, int S, int stride, int count, float* out, hipStream_t s) {
+    LP_LAUNCH(slice_sum_kernel, dim3((count + 255) / 256), dim3(256), 0, s, part, S, stride, count, out);
 }
 
 // ====================================================================================== 1x1: weight gradient
@@ -377,7 +381,7 @@ void launch_pw_wgrad(const float* dy, const float* x, float* part, float* dw, in
     else
         LP_LAUNCH(pw_wgrad_kernel<false>, grid, block, 0, s, dy, x, part, HW, Cout, Cin, NP);
     const int count = Cout * Cin;
-    LP_LAUNCH(slice_sum_kernel, dim3((count + 255) / 256), dim3(256), 0, s, (const float*)part, S, count, dw);
+    launch_slice_sum(part, S, count, count, dw, s);
 }
 
 // ====================================================================================== depthwise: data gradient
@@ -494,7 +498,7 @@ static void dw_backward_t(const float* dy, const float* x, const float* w, float
         const int SL = dw_wgrad_slices(N, OH, OW);
         LP_LAUNCH((dw_wgrad_kernel<K, S>), dim3(SL, C), dim3(256), 0, s, dy, x, part, N, C, H, W, OH, OW, tilesX, tiles);
         const int count = C * K * K;
-        LP_LAUNCH(slice_sum_kernel, dim3((count + 255) / 256), dim3(256), 0, s, (const float*)part, SL, count, dw);
+        launch_slice_sum(part, SL, count, count, dw, s);
     }
 }
 

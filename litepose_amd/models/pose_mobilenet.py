@@ -255,9 +255,12 @@ class TrainableLitePose(torch.nn.Module):
     (``load_state_dict`` of a reference checkpoint and of ``LitePose.state_dict()`` both work) and whose ``forward`` returns
     the list of stage outputs, for ``core.trainer.do_train``.
 
-    ``backend='native'``: every 1x1 convolution, every depthwise convolution and every BatchNorm (+ activation,
-    + residual) runs on ``litepose_amd.nn.functional`` -- the library's kernels, forward and backward; the dense 3x3
-    convolution of ``first.0`` and the ``ConvTranspose2d`` pairs run on torch's own ops.  float32 on the GPU.
+    ``backend='native'``: every layer runs on ``litepose_amd.nn.functional`` -- the library's kernels, forward and
+    backward: the 1x1 and depthwise convolutions, every BatchNorm (+ activation, + residual), the dense 3x3 stem
+    convolution ``first.0.0`` (``stem_conv``) and the ``ConvTranspose2d`` pairs of the Fusion Deconv Head
+    (``deconv_pair``).  No sum in it is atomic: one step gives the same bits every time, for every parameter; only the
+    optimizer is torch's.  One exception: the library has no data gradient for the stem, so when the image itself requires
+    a gradient ``first.0.0`` runs on torch's ``conv2d``.  float32 on the GPU.
     ``backend='torch'``: every layer on torch's ops: the same module on any device and dtype.
 
     The modules below only hold parameters under the checkpoint's names; ``forward`` walks them layer by layer."""
@@ -327,7 +330,15 @@ class TrainableLitePose(torch.nn.Module):
             return F_.pointwise(x, conv.weight)
         if self.backend == 'native' and groups == conv.in_channels == conv.out_channels and groups > 1:
             return F_.depthwise(x, conv.weight, conv.stride[0])
+        if self.backend == 'native' and conv is self.first[0][0] and not x.requires_grad:
+            return F_.stem_conv(x, conv.weight)
         return torch.nn.functional.conv2d(x, conv.weight, None, conv.stride, conv.padding, 1, groups)
+
+    def _up_pair(self, refined, w_refined, raw, w_raw):
+        if self.backend == 'native':
+            return F_.deconv_pair(refined, w_refined, raw, w_raw)
+        up = torch.nn.functional.conv_transpose2d
+        return up(refined, w_refined, None, 2, 1) + up(raw, w_raw, None, 2, 1)
 
     def _bn(self, x, bn, act=None, residual=None):
         if self.training:
@@ -365,8 +376,7 @@ class TrainableLitePose(torch.nn.Module):
         outputs = []
         refined, raw = feats[-1], feats[-2]
         for i in range(self.num_deconv_layers):
-            up = torch.nn.functional.conv_transpose2d
-            y = up(refined, self.deconv_refined[i].weight, None, 2, 1) + up(raw, self.deconv_raw[i].weight, None, 2, 1)
+            y = self._up_pair(refined, self.deconv_refined[i].weight, raw, self.deconv_raw[i].weight)
             refined = self._bn(y, self.deconv_bnrelu[i][0], 'relu')
             raw = feats[-i - 3]
             if i > 0:

@@ -1,7 +1,8 @@
-"""The three layer kinds of a LitePose block as differentiable functions on the device (include/litepose_amd.h,
-"training-mode layers"): ``pointwise``, ``depthwise`` and ``batch_norm_act``, each a ``torch.autograd.Function`` over one
-forward and one backward call of the C ABI.  float32 CUDA tensors, NCHW; a tensor of another kind is an error, there is no
-other path.
+"""The layer kinds of LitePose as differentiable functions on the device (include/litepose_amd.h, "training-mode
+layers"): ``pointwise``, ``depthwise`` and ``batch_norm_act``, the three a block is made of, and the two dense layers,
+``stem_conv`` (3x3, stride 2, 3 -> 32; weight gradient only) and ``deconv_pair`` (the ConvTranspose2d(k4, s2, p1) pair of
+the Fusion Deconv Head, or one of them), each a ``torch.autograd.Function`` over one forward and one backward call of the
+C ABI.  float32 CUDA tensors, NCHW; a tensor of another kind is an error, there is no other path.
 
 What an op keeps between forward and backward is what its backward reads: the raw input (and the weight, which lives on
 anyway), and for BatchNorm the fp64 ``(mean, invstd)`` pair of the batch.  The BatchNorm output is not kept: the backward
@@ -132,6 +133,133 @@ def depthwise(x, w, stride=1):
     """Depthwise K x K convolution (K 3, 5 or 7), padding K // 2, ``stride`` 1 or 2 (even planes), without bias:
     ``x`` [N,C,H,W], ``w`` [C,K,K] or [C,1,K,K]."""
     return _Depthwise.apply(x, w, stride)
+
+
+# ---------------------------------------------------------------------------------- stem: dense 3x3, stride 2, 3 -> 32
+def _stem_dims(x, w):
+    N, C, H, W = (int(v) for v in x.shape)
+    if C != 3 or tuple(w.shape) != (32, 3, 3, 3):
+        raise ValueError('the stem takes x [N, 3, H, W] and w [32, 3, 3, 3]')
+    if H % 2 or W % 2:
+        raise ValueError('the stem is defined for even H and W only')
+    return N, H, W
+
+
+def stem_forward(x, w):
+    x, w = _f32(x, 'x', 4), _f32(w, 'w', 4)
+    N, H, W = _stem_dims(x, w)
+    y = torch.empty((N, 32, H // 2, W // 2), dtype=torch.float32, device=x.device)
+    nv.check(nv.lib().lp_stem_forward(nv.dptr(x), nv.dptr(w), nv.dptr(y), N, H, W, nv.stream_ptr()), 'lp_stem_forward')
+    return y
+
+
+def stem_backward(grad_y, x):
+    """-> grad_w [32, 3, 3, 3]; there is no data gradient."""
+    grad_y, x = _f32(grad_y, 'grad_y', 4), _f32(x, 'x', 4)
+    N, C, H, W = (int(v) for v in x.shape)
+    if C != 3 or H % 2 or W % 2 or tuple(grad_y.shape) != (N, 32, H // 2, W // 2):
+        raise ValueError('grad_y and x do not belong to one stem convolution')
+    gw = torch.empty((32, 3, 3, 3), dtype=torch.float32, device=x.device)
+    L = nv.lib()
+    ws = _ws(L.lp_stem_backward_workspace_bytes(N, H, W), x.device)
+    nv.check(L.lp_stem_backward(nv.dptr(grad_y), nv.dptr(x), nv.dptr(gw), N, H, W, nv.dptr(ws), ws.numel(),
+                                nv.stream_ptr()), 'lp_stem_backward')
+    return gw
+
+
+class _StemConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w):
+        ctx.save_for_backward(x)
+        return stem_forward(x, w)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError('the stem has no data gradient in the library')
+        (x,) = ctx.saved_tensors
+        return None, stem_backward(grad_y, x) if ctx.needs_input_grad[1] else None
+
+
+def stem_conv(x, w):
+    """The stem: 3x3 convolution, stride 2, padding 1, without bias: ``x`` [N,3,H,W] (even H, W; it must not require a
+    gradient: the library has no data gradient for the image), ``w`` [32,3,3,3] -> [N,32,H/2,W/2]."""
+    if isinstance(x, torch.Tensor) and x.requires_grad:
+        raise ValueError('stem_conv has no gradient for x')
+    return _StemConv.apply(x, w)
+
+
+# ---------------------------------------------------------------------------------- ConvTranspose2d(k4, s2, p1) pair
+def _deconv_dims(xa, wa, xb, wb):
+    N, Ca, h, w = (int(v) for v in xa.shape)
+    if wa.dim() != 4 or int(wa.shape[0]) != Ca or tuple(wa.shape[2:]) != (4, 4):
+        raise ValueError('wa must be [%d, Cout, 4, 4]' % Ca)
+    Cout = int(wa.shape[1])
+    if (xb is None) != (wb is None):
+        raise ValueError('xb and wb are given together')
+    Cb = 0
+    if xb is not None:
+        Cb = int(xb.shape[1])
+        if tuple(xb.shape) != (N, Cb, h, w) or tuple(wb.shape) != (Cb, Cout, 4, 4) or Cb < 1:
+            raise ValueError('xb must be [%d, Cb, %d, %d] and wb [Cb, %d, 4, 4]' % (N, h, w, Cout))
+    return N, Ca, Cb, Cout, h, w
+
+
+def deconv_forward(xa, wa, xb=None, wb=None):
+    xa, wa = _f32(xa, 'xa', 4), _f32(wa, 'wa')
+    if xb is not None or wb is not None:
+        xb, wb = _f32(xb, 'xb', 4), _f32(wb, 'wb')
+    N, Ca, Cb, Cout, h, w = _deconv_dims(xa, wa, xb, wb)
+    y = torch.empty((N, Cout, 2 * h, 2 * w), dtype=torch.float32, device=xa.device)
+    L = nv.lib()
+    ws = _ws(L.lp_deconv_forward_workspace_bytes(Ca, Cb, Cout), xa.device)
+    nv.check(L.lp_deconv_forward(nv.dptr(xa), nv.dptr(wa), nv.dptr(xb), nv.dptr(wb), nv.dptr(y), N, Ca, Cb, Cout, h, w,
+                                 nv.dptr(ws), ws.numel(), nv.stream_ptr()), 'lp_deconv_forward')
+    return y
+
+
+def deconv_backward(grad_y, xa, wa, xb=None, wb=None, need_x=True, need_w=True):
+    """-> (grad_xa, grad_xb, grad_wa, grad_wb): the data-gradient pair is None without ``need_x``, the weight-gradient
+    pair without ``need_w``, and the ``b`` members without a second source."""
+    grad_y, xa, wa = _f32(grad_y, 'grad_y', 4), _f32(xa, 'xa', 4), _f32(wa, 'wa')
+    if xb is not None or wb is not None:
+        xb, wb = _f32(xb, 'xb', 4), _f32(wb, 'wb')
+    N, Ca, Cb, Cout, h, w = _deconv_dims(xa, wa, xb, wb)
+    if tuple(grad_y.shape) != (N, Cout, 2 * h, 2 * w):
+        raise ValueError('grad_y does not have the shape of the output')
+    if not (need_x or need_w):
+        return None, None, None, None
+    gxa = torch.empty_like(xa) if need_x else None
+    gxb = torch.empty_like(xb) if need_x and Cb else None
+    gwa = torch.empty_like(wa) if need_w else None
+    gwb = torch.empty_like(wb) if need_w and Cb else None
+    L = nv.lib()
+    ws = _ws(L.lp_deconv_backward_workspace_bytes(N, Ca, Cb, Cout, h, w, int(need_x), int(need_w)), xa.device)
+    nv.check(L.lp_deconv_backward(nv.dptr(grad_y), nv.dptr(xa), nv.dptr(wa), nv.dptr(xb), nv.dptr(wb), nv.dptr(gxa),
+                                  nv.dptr(gxb), nv.dptr(gwa), nv.dptr(gwb), N, Ca, Cb, Cout, h, w, nv.dptr(ws), ws.numel(),
+                                  nv.stream_ptr()), 'lp_deconv_backward')
+    return gxa, gxb, gwa, gwb
+
+
+class _DeconvPair(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xa, wa, xb, wb):
+        ctx.save_for_backward(xa, wa, xb, wb)
+        return deconv_forward(xa, wa, xb, wb)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        xa, wa, xb, wb = ctx.saved_tensors
+        nx, nw = ctx.needs_input_grad[0::2], ctx.needs_input_grad[1::2]
+        gxa, gxb, gwa, gwb = deconv_backward(grad_y, xa, wa, xb, wb, any(nx), any(nw))
+        return (gxa if nx[0] else None, gwa if nw[0] else None, gxb if nx[1] else None, gwb if nw[1] else None)
+
+
+def deconv_pair(xa, wa, xb=None, wb=None):
+    """``conv_transpose2d(xa, wa, stride 2, padding 1) + conv_transpose2d(xb, wb, stride 2, padding 1)``, kernel 4, without
+    bias: ``xa`` [N,Ca,h,w], ``wa`` [Ca,Cout,4,4], ``xb`` [N,Cb,h,w], ``wb`` [Cb,Cout,4,4] -> [N,Cout,2h,2w].  Without
+    ``xb`` / ``wb`` it is the single transposed convolution."""
+    return _DeconvPair.apply(xa, wa, xb, wb)
 
 
 # ---------------------------------------------------------------------------------- BatchNorm + act (+ residual)

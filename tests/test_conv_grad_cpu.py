@@ -1,0 +1,117 @@
+"""The C ABI of the stem and transposed-convolution calls without a device: the header declares the seven calls and
+_native.py binds them, the workspace sizes follow the header's formulas, and every refusal is answered with its documented
+code before anything is launched (the pointers below are made-up addresses that are never dereferenced)."""
+import ctypes as C
+import re
+
+import pytest
+
+import _conv_grad_check as K
+from litepose_amd import _native as nv
+
+CALLS = ['lp_stem_forward', 'lp_stem_backward_workspace_bytes', 'lp_stem_backward', 'lp_deconv_forward_workspace_bytes',
+         'lp_deconv_forward', 'lp_deconv_backward_workspace_bytes', 'lp_deconv_backward']
+P = [C.c_void_p(0x10000 + 0x1000 * i) for i in range(10)]      # 16-byte aligned addresses, never read
+ODD = C.c_void_p(0x20004)
+BIG = 1 << 40
+
+
+def test_header_declares_and_native_binds_the_seven_calls():
+    with open(K.HEADER) as f:
+        hdr = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+    L = nv.lib()
+    for name in CALLS:
+        assert re.search(r'\b%s\s*\(' % name, hdr), name
+        assert name in nv.EXPORTS and hasattr(L, name), name
+    assert K.macro('LP_DECONV_WGRAD_SLICE') % K.DECONV_TILE == 0 and K.macro('LP_STEM_WGRAD_SLICE') % K.STEM_TILE == 0
+
+
+def test_no_new_call_names_a_writable_pointer_d():
+    from test_poison_cpu import writable_device_calls
+    found = writable_device_calls()
+    assert len(found) == 20 and not set(CALLS) & found
+
+
+@pytest.mark.parametrize('shape', [(1, 2, 2), (3, 2, 2), (2, 10, 14), (2, 64, 64), (33, 64, 64), (64, 256, 256)])
+def test_stem_workspace_formula(shape):
+    n, H, W = shape
+    assert nv.lib().lp_stem_backward_workspace_bytes(n, H, W) == K.stem_slices(n, H, W) * 32 * 27 * 4
+
+
+@pytest.mark.parametrize('plane', [(3, 1, 1), (2, 5, 7), (2, 16, 16), (35, 8, 8), (64, 64, 64)])
+@pytest.mark.parametrize('ch', [(16, 16, 8), (5, 0, 3), (33, 7, 9)])
+def test_deconv_workspace_formula(ch, plane):
+    L = nv.lib()
+    (ca, cb, cout), (n, h, w) = ch, plane
+    wbytes = (ca + cb) * cout * 16 * 4
+    assert L.lp_deconv_forward_workspace_bytes(ca, cb, cout) == wbytes
+    s = K.deconv_slices(n, h, w)
+    for wx in (0, 1):
+        for ww in (0, 1):
+            assert L.lp_deconv_backward_workspace_bytes(n, ca, cb, cout, h, w, wx, ww) == wx * wbytes + ww * s * wbytes
+
+
+def test_stem_refusals():
+    L = nv.lib()
+    for H, W in ((6, 7), (7, 6), (5, 5)):
+        assert L.lp_stem_forward(P[0], P[1], P[2], 1, H, W, None) == K.LP_ERR_INVALID_ARG
+        assert L.lp_stem_backward(P[0], P[1], P[2], 1, H, W, P[3], BIG, None) == K.LP_ERR_INVALID_ARG
+        assert L.lp_stem_backward_workspace_bytes(1, H, W) == 0
+    assert L.lp_stem_forward(P[0], P[1], P[2], 0, 8, 8, None) == K.LP_ERR_INVALID_ARG
+    assert L.lp_stem_forward(P[0], P[1], None, 1, 8, 8, None) == K.LP_ERR_INVALID_ARG
+    assert L.lp_stem_forward(ODD, P[1], P[2], 1, 8, 8, None) == K.LP_ERR_INVALID_ARG
+    assert L.lp_stem_backward(P[0], ODD, P[2], 1, 8, 8, P[3], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert L.lp_stem_backward(P[0], P[1], None, 1, 8, 8, P[3], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert b'aligned' in L.lp_last_error() or b'null' in L.lp_last_error()
+    # N * (H/2) * (W/2) beyond 2^31 - 256
+    assert L.lp_stem_forward(P[0], P[1], P[2], 64, 16384, 16384, None) == K.LP_ERR_UNSUPPORTED
+    assert L.lp_stem_backward_workspace_bytes(64, 16384, 16384) == 0
+    need = L.lp_stem_backward_workspace_bytes(2, 64, 64)
+    assert L.lp_stem_backward(P[0], P[1], P[2], 2, 64, 64, P[3], need - 1, None) == K.LP_ERR_WORKSPACE
+    assert L.lp_stem_backward(P[0], P[1], P[2], 2, 64, 64, None, need, None) == K.LP_ERR_WORKSPACE
+    assert L.lp_stem_backward(P[0], P[1], P[2], 2, 64, 64, ODD, need, None) == K.LP_ERR_WORKSPACE
+
+
+def test_deconv_refusals():
+    L = nv.lib()
+    d = (2, 16, 16, 8, 5, 7)                                   # N, Ca, Cb, Cout, h, w
+    one = (2, 5, 0, 3, 5, 7)
+    fwd, bwd = L.lp_deconv_forward, L.lp_deconv_backward
+    # Cb = 0 with a b pointer, Cb > 0 without one
+    assert fwd(P[0], P[1], P[2], None, P[4], *one, P[5], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert fwd(P[0], P[1], None, P[3], P[4], *one, P[5], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert fwd(P[0], P[1], None, P[3], P[4], *d, P[5], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert bwd(P[0], P[1], P[2], P[3], None, P[5], None, P[7], None, *one, P[9], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert bwd(P[0], P[1], P[2], None, None, P[5], P[6], P[7], None, *one, P[9], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert bwd(P[0], P[1], P[2], None, None, P[5], None, P[7], P[8], *one, P[9], BIG, None) == K.LP_ERR_INVALID_ARG
+    # no output requested; half a pair
+    assert bwd(P[0], P[1], P[2], P[3], P[4], None, None, None, None, *d, P[9], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert bwd(P[0], P[1], P[2], P[3], P[4], P[5], None, P[7], P[8], *d, P[9], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert bwd(P[0], P[1], P[2], P[3], P[4], P[5], P[6], None, P[8], *d, P[9], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert L.lp_deconv_backward_workspace_bytes(*d, 0, 0) == 0
+    # an operand a requested gradient reads is missing
+    assert bwd(P[0], P[1], None, P[3], P[4], P[5], P[6], None, None, *d, P[9], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert bwd(P[0], None, P[2], P[3], P[4], None, None, P[7], P[8], *d, P[9], BIG, None) == K.LP_ERR_INVALID_ARG
+    # misaligned activations and gradients
+    assert fwd(ODD, P[1], P[2], P[3], P[4], *d, P[5], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert fwd(P[0], P[1], P[2], P[3], ODD, *d, P[5], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert bwd(ODD, P[1], P[2], P[3], P[4], P[5], P[6], P[7], P[8], *d, P[9], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert bwd(P[0], P[1], P[2], P[3], P[4], P[5], ODD, P[7], P[8], *d, P[9], BIG, None) == K.LP_ERR_INVALID_ARG
+    # sizes
+    assert fwd(P[0], P[1], P[2], P[3], P[4], 2, 0, 16, 8, 5, 7, P[5], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert fwd(P[0], P[1], P[2], P[3], P[4], 2, 16, -1, 8, 5, 7, P[5], BIG, None) == K.LP_ERR_INVALID_ARG
+    assert fwd(P[0], P[1], P[2], P[3], P[4], 2, 40000, 40000, 8, 5, 7, P[5], BIG, None) == K.LP_ERR_UNSUPPORTED
+    assert fwd(P[0], P[1], P[2], P[3], P[4], 64, 16, 16, 8, 16384, 16384, P[5], BIG, None) == K.LP_ERR_UNSUPPORTED
+    assert L.lp_deconv_forward_workspace_bytes(40000, 40000, 8) == 0
+    assert L.lp_deconv_backward_workspace_bytes(64, 16, 16, 8, 16384, 16384, 1, 1) == 0
+    # a workspace one byte short, absent, misaligned
+    need = L.lp_deconv_forward_workspace_bytes(16, 16, 8)
+    assert fwd(P[0], P[1], P[2], P[3], P[4], *d, P[5], need - 1, None) == K.LP_ERR_WORKSPACE
+    assert fwd(P[0], P[1], P[2], P[3], P[4], *d, ODD, need, None) == K.LP_ERR_WORKSPACE
+    for wx, ww in ((1, 1), (1, 0), (0, 1)):
+        need = L.lp_deconv_backward_workspace_bytes(*d, wx, ww)
+        args = (P[0], P[1], P[2], P[3], P[4], P[5] if wx else None, P[6] if wx else None, P[7] if ww else None,
+                P[8] if ww else None) + d
+        assert bwd(*args, P[9], need - 1, None) == K.LP_ERR_WORKSPACE
+        assert bwd(*args, None, need, None) == K.LP_ERR_WORKSPACE
+        assert bwd(*args, ODD, need, None) == K.LP_ERR_WORKSPACE

@@ -1,0 +1,84 @@
+"""The buffer contract of the stem and transposed-convolution calls (include/litepose_amd.h, "training-mode layers") with
+the poisoned and guarded buffers of tests/_poison.py, as tests/test_gpu_layer_buffers.py has it for the other layers: every
+call writes exactly the elements its header comment names -- whatever the outputs and the workspace held before (zeros,
+NaN, a huge finite value) the results are the same bits -- and nothing in the guards around outputs, inputs and a workspace
+of exactly ``*_workspace_bytes``; one byte less answers LP_ERR_WORKSPACE; the inputs come back unchanged.  Covers the
+nullable-output forms and the one-source form of lp_deconv_backward."""
+import pytest
+
+import _poison as po
+from litepose_amd import _native as nv
+from test_gpu_layer_buffers import LP_ERR_WORKSPACE, _contract, _g
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.mark.parametrize('shape', [(3, 2, 2), (2, 10, 14), (35, 16, 32)], ids=['2x2', '10x14', 'slices'])
+def test_stem_calls(shape):
+    L = nv.lib()
+    N, H, W = shape
+    x, w, dy = _g((N, 3, H, W), 21), _g((32, 3, 3, 3), 22, 0.3), _g((N, 32, H // 2, W // 2), 23)
+    s = nv.stream_ptr()
+
+    def fwd(A):
+        y = A.out((N, 32, H // 2, W // 2), what='y_out')
+        return L.lp_stem_forward(nv.dptr(A.inp(x, what='x')), nv.dptr(A.inp(w, what='w')), nv.dptr(y), N, H, W, s), dict(y=y)
+
+    def bwd(A):
+        gw = A.out((32, 3, 3, 3), what='grad_w_out')
+        need = L.lp_stem_backward_workspace_bytes(N, H, W)
+        assert need > 0
+        ws = A.ws(need)
+        args = (nv.dptr(A.inp(dy, what='grad_y')), nv.dptr(A.inp(x, what='x')), nv.dptr(gw), N, H, W, nv.dptr(ws))
+        assert L.lp_stem_backward(*args, need - 1, s) == LP_ERR_WORKSPACE
+        return L.lp_stem_backward(*args, need, s), dict(gw=gw)
+
+    _contract(fwd)
+    _contract(bwd)
+
+
+@pytest.mark.parametrize('want', ['both', 'x', 'w'])
+@pytest.mark.parametrize('shape', [(3, 16, 16, 8, 1, 1), (2, 33, 7, 9, 5, 7), (2, 5, 0, 3, 5, 7), (35, 24, 16, 24, 8, 8)],
+                         ids=['1x1', 'ragged-rows', 'one-source', 'slices'])
+def test_deconv_calls(shape, want):
+    L = nv.lib()
+    N, Ca, Cb, Cout, h, w = shape
+    xa, wa, dy = _g((N, Ca, h, w), 24), _g((Ca, Cout, 4, 4), 25, 0.3), _g((N, Cout, 2 * h, 2 * w), 26)
+    xb, wb = (_g((N, Cb, h, w), 27), _g((Cb, Cout, 4, 4), 28, 0.3)) if Cb else (None, None)
+    s = nv.stream_ptr()
+
+    def inp(A, t, what):
+        return None if t is None else nv.dptr(A.inp(t, what=what))
+
+    def fwd(A):
+        y = A.out((N, Cout, 2 * h, 2 * w), what='y_out')
+        need = L.lp_deconv_forward_workspace_bytes(Ca, Cb, Cout)
+        ws = A.ws(need)
+        args = (inp(A, xa, 'xa'), inp(A, wa, 'wa'), inp(A, xb, 'xb'), inp(A, wb, 'wb'), nv.dptr(y), N, Ca, Cb, Cout, h, w,
+                nv.dptr(ws))
+        assert L.lp_deconv_forward(*args, need - 1, s) == LP_ERR_WORKSPACE
+        return L.lp_deconv_forward(*args, need, s), dict(y=y)
+
+    def bwd(A):
+        wx, ww = want in ('both', 'x'), want in ('both', 'w')
+        gxa = A.out((N, Ca, h, w), what='grad_xa_out') if wx else None
+        gxb = A.out((N, Cb, h, w), what='grad_xb_out') if wx and Cb else None
+        gwa = A.out((Ca, Cout, 4, 4), what='grad_wa_out') if ww else None
+        gwb = A.out((Cb, Cout, 4, 4), what='grad_wb_out') if ww and Cb else None
+        need = L.lp_deconv_backward_workspace_bytes(N, Ca, Cb, Cout, h, w, int(wx), int(ww))
+        assert need > 0
+        ws = A.ws(need)
+        # the sources are read only for the weight gradients, the weights only for the data gradients
+        args = (nv.dptr(A.inp(dy, what='grad_y')), inp(A, xa, 'xa') if ww else None, inp(A, wa, 'wa') if wx else None,
+                inp(A, xb, 'xb') if ww else None, inp(A, wb, 'wb') if wx else None, nv.dptr(gxa), nv.dptr(gxb), nv.dptr(gwa),
+                nv.dptr(gwb), N, Ca, Cb, Cout, h, w, nv.dptr(ws))
+        assert L.lp_deconv_backward(*args, need - 1, s) == LP_ERR_WORKSPACE
+        outs = dict(gxa=gxa, gxb=gxb, gwa=gwa, gwb=gwb)
+        return L.lp_deconv_backward(*args, need, s), {k: v for k, v in outs.items() if v is not None}
+
+    if want == 'both':
+        _contract(fwd)
+    _contract(bwd)
+    A = po.Arena('N')
+    assert L.lp_deconv_backward(nv.dptr(dy), nv.dptr(xa), nv.dptr(wa), nv.dptr(xb), nv.dptr(wb), None, None, None, None, N, Ca,
+                                Cb, Cout, h, w, nv.dptr(A.ws(1 << 16)), 1 << 16, s) == -1

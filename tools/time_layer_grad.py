@@ -1,11 +1,13 @@
 #!/usr/bin/env python
 """Device time of the training-mode layers (GPU box): the measurement of DESIGN.md 4f.  Every distinct layer shape of an
-architecture (default LitePose-XS at 256) at batch 64: the library's forward and each backward kernel group (data gradient,
-weight gradient), and beside them torch's own forward and backward of the same op on the same tensors (aten's
-convolution_backward with one output asked for at a time; BatchNorm + activation through autograd).  HIP events, 10 warm-up
-calls and REPS repeats, medians, every row from one run.  The bytes are those a call must move (activations in and out once
-per pass over them: BatchNorm reads its input twice, its backward reads input and upstream twice), the FLOPs those of the
-weight-gradient GEMM.  The repeats re-read the same tensors: where they fit the Infinity Cache this is not an HBM figure.
+architecture (default LitePose-XS at 256) at batch 64 -- 1x1, depthwise, BatchNorm, the stem convolution (forward and
+weight gradient: it has no data gradient) and the transposed-convolution pairs: the library's forward and each backward
+kernel group (data gradient, weight gradient), and beside them torch's own forward and backward of the same op on the same
+tensors (aten's convolution_backward with one output asked for at a time; BatchNorm + activation through autograd).  HIP
+events, 10 warm-up calls and REPS repeats, medians, every row from one run.  The bytes are those a call must move
+(activations in and out once per pass over them: BatchNorm reads its input twice, its backward reads input and upstream
+twice), the FLOPs those of the weight-gradient GEMM (for the transposed-convolution pair, whose three passes are GEMMs of
+one size, of each pass).  The repeats re-read the same tensors: where they fit the Infinity Cache this is not an HBM figure.
 Last: one full do_train step (loss, backward, SGD) of the native module and of the backend='torch' module.
 
     python tools/time_layer_grad.py [REPS] [ARCH] [BATCH]
@@ -41,7 +43,7 @@ def layer_shapes(cfg, arch, res):
     """One forward of the torch-backend module at batch 1 on the CPU with its layer methods recording: the distinct
     (kind, ...) shapes in network order with how often each occurs."""
     m = pm.get_train_net(cfg, arch, backend='torch').eval()
-    seen, conv0, bn0 = {}, m._conv, m._bn
+    seen, conv0, bn0, up0 = {}, m._conv, m._bn, m._up_pair
 
     def note(key):
         seen[key] = seen.get(key, 0) + 1
@@ -52,13 +54,19 @@ def layer_shapes(cfg, arch, res):
             note(('pw', c.in_channels, c.out_channels, x.shape[2], x.shape[3]))
         elif g == c.in_channels and g > 1:
             note(('dw', c.in_channels, k, c.stride[0], x.shape[2], x.shape[3]))
+        else:
+            note(('stem', x.shape[2], x.shape[3]))
         return conv0(x, c)
+
+    def up_pair(refined, w_refined, raw, w_raw):
+        note(('deconv', refined.shape[1], raw.shape[1], w_refined.shape[1], refined.shape[2], refined.shape[3]))
+        return up0(refined, w_refined, raw, w_raw)
 
     def bn(x, b, act=None, residual=None):
         note(('bn', x.shape[1], x.shape[2], x.shape[3], act, residual is not None))
         return bn0(x, b, act, residual)
 
-    m._conv, m._bn = conv, bn
+    m._conv, m._bn, m._up_pair = conv, bn, up_pair
     with torch.no_grad():
         m(torch.zeros(1, 3, res, res))
     return list(seen.items())
@@ -86,6 +94,26 @@ def rows(shape, N, reps):
             ('fwd', nb, 0, lambda: F.dw_forward(x, wt, s), lambda: TF.conv2d(x, wt, None, s, k // 2, 1, c)),
             ('dX', nb, 0, lambda: F.dw_backward(dy, x, wt, s, True, False), lambda: back([True, False, False])),
             ('dW', nb, 2 * k * k * dy.numel(), lambda: F.dw_backward(dy, x, wt, s, False, True), lambda: back([False, True, False]))]
+    if kind == 'stem':
+        _, h, w = shape
+        x, wt, dy = r(N, 3, h, w), r(32, 3, 3, 3) * 0.1, r(N, 32, h // 2, w // 2)
+        nb = (x.numel() + dy.numel()) * 4
+        back = lambda: torch.ops.aten.convolution_backward(dy, x, wt, None, [2, 2], [1, 1], [1, 1], False, [0, 0], 1, [False, True, False])  # noqa: E731
+        return 'stem   3 ->   32  %3dx%-3d' % (h, w), [
+            ('fwd', nb, 0, lambda: F.stem_forward(x, wt), lambda: TF.conv2d(x, wt, None, 2, 1)),
+            ('dW', nb, 2 * 27 * dy.numel(), lambda: F.stem_backward(dy, x), back)]
+    if kind == 'deconv':
+        _, ca, cb, co, h, w = shape
+        xa, xb, wa, wb, dy = r(N, ca, h, w), r(N, cb, h, w), r(ca, co, 4, 4) * 0.1, r(cb, co, 4, 4) * 0.1, r(N, co, 2 * h, 2 * w)
+        nb = (xa.numel() + xb.numel() + dy.numel()) * 4
+        fl = 2 * 16 * (ca + cb) * co * N * h * w
+        back = lambda x, wt, mask: torch.ops.aten.convolution_backward(dy, x, wt, None, [2, 2], [1, 1], [1, 1], True, [0, 0], 1, mask)  # noqa: E731
+        both = lambda mask: (back(xa, wa, mask), back(xb, wb, mask))  # noqa: E731
+        return 'dc %3d+%-3d-> %3d  %3dx%-3d' % (ca, cb, co, h, w), [
+            ('fwd', nb, fl, lambda: F.deconv_forward(xa, wa, xb, wb),
+             lambda: TF.conv_transpose2d(xa, wa, None, 2, 1) + TF.conv_transpose2d(xb, wb, None, 2, 1)),
+            ('dX', nb, fl, lambda: F.deconv_backward(dy, xa, wa, xb, wb, True, False), lambda: both([True, False, False])),
+            ('dW', nb, fl, lambda: F.deconv_backward(dy, xa, wa, xb, wb, False, True), lambda: both([False, True, False]))]
     _, c, h, w, act, has_res = shape
     x, dy, res = r(N, c, h, w), r(N, c, h, w), r(N, c, h, w) if has_res else None
     ga, be, run = torch.rand(c, device='cuda') + 0.5, r(c), torch.stack([r(c) * 0.1, torch.rand(c, device='cuda') + 0.5])

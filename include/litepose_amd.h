@@ -868,6 +868,49 @@ int lp_deconv_backward(const float* d_grad_y, const float* d_xa, const float* d_
                        float* grad_xa_out, float* grad_xb_out, float* grad_wa_out, float* grad_wb_out, int N, int Ca,
                        int Cb, int Cout, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------ optimizers ---------
+ * torch.optim.Adam (no amsgrad, no maximize, L2 weight decay) and torch.optim.SGD (dampening 0) over a LIST of fp32 tensors:
+ * one call updates every tensor of a parameter group.  The arrays param_io, d_grad, exp_avg_io, exp_avg_sq_io, momentum_io
+ * and numel are HOST arrays of `count` entries (device pointers / element counts), read during the call and free to go
+ * afterwards.  The host packs pointers, lengths and the map from a workgroup to (tensor, block of LP_OPTIM_BLOCK_ELEMS
+ * elements) into by-value launch arguments of at most 4 KB: tensors in list order, each cut into blocks in order; an
+ * argument chunk closes when it holds LP_OPTIM_CHUNK_BLOCKS blocks, or LP_OPTIM_CHUNK_TENSORS tensors and the next block
+ * belongs to another tensor; each chunk is one launch.  No device-side pointer table, no memcpy, no allocation, no
+ * synchronisation, no atomics, no LDS; capturable in a hipGraph, and the rules of the training-mode layer calls hold.
+ * lp_optim_launches: the number of argument chunks = update launches of a call on tensors of these lengths (the same for
+ * both optimizers).  lp_optim_adam enqueues ONE more launch behind them, which advances the counters: a block of an update
+ * launch must not move a counter that another block of the call still reads, and a tensor may span launches.
+ * d_lr: a DEVICE fp64 scalar read when the launches run (a schedule changes it without a new capture); every other
+ * hyperparameter travels by value.  Every tensor pointer must be 4-byte aligned; a tensor whose pointers are all 16-byte
+ * aligned is updated with 16-byte loads and stores, any other one element by element (the same bits).
+ * Adam, per element, t = step_io[i] + 1 as the value stood BEFORE the call (every launch of the call sees that value):
+ *   g' = g + wd p (wd != 0);  m = b1 m + (1 - b1) g';  v = b2 v + ((1 - b2) g') g';
+ *   p = p - (lr / (1 - b1^t)) * (m / (sqrt(v) / sqrt(1 - b2^t) + eps))
+ *   lr / (1 - b1^t) and sqrt(1 - b2^t) in fp64 (the powers by squaring), rounded to fp32 once; the element math in fp32,
+ *   every operation rounded on its own.  step_io [count] fp32 DEVICE; after the call every step_io[i] is one higher.
+ *   Writes: every element of every param_io, exp_avg_io and exp_avg_sq_io tensor and of step_io.
+ * SGD, per element:
+ *   g' = g + wd p (wd != 0);  buf = mu buf + g' (mu != 0; a zero buffer gives torch's first step);
+ *   d = nesterov ? g' + mu buf : buf (mu != 0), g' otherwise;  p = p - lr d  -- with mu = 0 and wd = 0 that is p - lr * g,
+ *   the product and the difference rounded separately (lr rounded to fp32 first).
+ *   Writes: every element of every param_io tensor and, with a momentum, of every momentum_io tensor.
+ * Gradients are never written.
+ * LP_ERR_INVALID_ARG: count <= 0, a NULL array or entry, numel <= 0, a pointer that is not 4-byte aligned (d_lr: 8-byte),
+ * d_lr NULL, a beta outside [0, 1), eps < 0, momentum < 0, weight_decay < 0, nesterov with momentum == 0, momentum_io given
+ * with momentum == 0 or missing otherwise.  LP_ERR_UNSUPPORTED: a numel above 2^31 - 256.  Every refusal is answered
+ * before anything is launched, and no tensor pointer is dereferenced on the host.
+ * The writable pointers are DEVICE memory; like those of the layer calls they do not carry the d_ prefix (the census of
+ * writable calls keys on it); their contract test is tests/test_gpu_optim_buffers.py.                                  */
+#define LP_OPTIM_BLOCK_ELEMS 4096
+#define LP_OPTIM_CHUNK_TENSORS 64
+#define LP_OPTIM_CHUNK_BLOCKS 432
+int lp_optim_launches(int count, const int64_t* numel);
+int lp_optim_adam(int count, float* const* param_io, const float* const* d_grad, float* const* exp_avg_io,
+                  float* const* exp_avg_sq_io, const int64_t* numel, float* step_io, const double* d_lr, double beta1,
+                  double beta2, double eps, double weight_decay, void* stream);
+int lp_optim_sgd(int count, float* const* param_io, const float* const* d_grad, float* const* momentum_io,
+                 const int64_t* numel, const double* d_lr, double momentum, double weight_decay, int nesterov, void* stream);
+
 /* utils.transforms.get_final_preds (lib/utils/transforms.py:195-202,50-56): inverse
  * affine (rot 0) heatmap -> image coordinates, in place on x,y of d_ans.
  * h_center [2], h_scale [2] as returned by get_multi_scale_size, heatmap size (Wp,Hp).

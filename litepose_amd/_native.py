@@ -176,6 +176,11 @@ _SIGS = {
     'lp_deconv_forward': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     'lp_deconv_backward_workspace_bytes': (sz, [i32, i32, i32, i32, i32, i32, i32, i32]),
     'lp_deconv_backward': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    'lp_optim_launches': (i32, [i32, C.POINTER(i64)]),
+    'lp_optim_adam': (i32, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp, vp,
+                            C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+    'lp_optim_sgd': (i32, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp, C.c_double, C.c_double,
+                           i32, vp]),
     'lp_stream_abort_capture': (i32, [vp]),
     'lp_final_preds': (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                              i32, i32, vp]),

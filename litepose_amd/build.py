@@ -53,6 +53,8 @@ SOURCES = [
     ('vis_kernels.hip', NOPK),                             # integer raster; floats are only loaded, compared, truncated
     ('layer_kernels.hip', NOPK),                           # no hand-placed packed FMAs: fp32 MFMA, scalar FMAs, fp64 sums
     ('conv_grad_kernels.hip', NOPK),                       # likewise: fp32 MFMA from LDS patches
+    ('optim_api.cpp', []),
+    ('optim_kernels.hip', ['-ffp-contract=off'] + NOPK),   # Adam / SGD: every product and sum of the update rounds on its own
 ]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value',
           '-Wno-pass-failed']

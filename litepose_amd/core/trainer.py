@@ -32,7 +32,149 @@ def loss_epoch(model, labelled_set, cfg, batch_size=16, np_rng=None, py_rng=None
     return {k: [None if v is None else float(v) / count for v in vals] for k, vals in sums.items()}
 
 
-def do_train(cfg, model, data_loader, loss_factory, optimizer, epoch=0, teacher=None, logger=None):
+_KEYS = ('heatmaps', 'push', 'pull')
+
+
+def _flat(batch):
+    for part in batch:
+        for t in (part if isinstance(part, (list, tuple)) else [part]):
+            yield t
+
+
+class CapturedStep(object):
+    """One training step -- ``zero_grad`` (set to none), forward, loss, backward, ``optimizer.step()`` -- replayed as one
+    captured graph.  ``step(images, heatmaps, masks, joints)`` follows the convention of the inference engine's buffer sets
+    (DESIGN.md): a batch signature (shapes and dtypes of every tensor) runs eagerly at its first sight; at its second sight
+    the batch is copied into static buffers, the step is captured (a capture enqueues nothing) and replayed once -- that
+    replay IS the step; every later sight copies and replays.  A run through ``step`` therefore performs exactly the eager
+    loop's sequence of updates, and the library's calls give the same bits launched or replayed.
+
+    The loss terms never visit the host inside a step: slot ``k * NUM_STAGES + stage`` (k: heatmaps, push, pull) of a static
+    fp32 tensor holds the last batch mean, the same slot of an fp64 tensor the running sum of ``mean.double() * n``;
+    ``read()`` fetches both.  ``captures``, ``replays`` and ``eager_steps`` count what happened.
+
+    ``optimizer`` must be a ``litepose_amd.optim`` optimizer: its ``lr`` and step counts live on the device, torch's own
+    would be baked into the graph.  ``sync_hyperparameters()`` runs before every replay.  The model must be in training mode
+    and stay there.  After a step ``p.grad`` holds that step's gradient, as in the eager loop."""
+
+    def __init__(self, cfg, model, loss_factory, optimizer):
+        from .. import optim
+        if not isinstance(optimizer, (optim.Adam, optim.SGD)):
+            raise TypeError('CapturedStep needs a litepose_amd.optim optimizer (lr and step counts on the device), got %s'
+                            % type(optimizer).__name__)
+        if not model.training:
+            raise ValueError('CapturedStep: the model must be in training mode')
+        self.model, self.loss_factory, self.optimizer = model, loss_factory, optimizer
+        self.S = int(cfg.LOSS.NUM_STAGES)
+        self.captures = self.replays = self.eager_steps = 0
+        self._sights, self._captured = {}, {}
+        self._last = self._sums = None
+        self._active = [False] * (3 * self.S)
+        self._grads_of = None                      # the captured entry whose gradients p.grad holds (None: an eager step's)
+
+    def reset_meters(self):
+        """Zero the running sums (the start of an epoch)."""
+        if self._sums is not None:
+            self._sums.zero_()
+
+    def read(self):
+        """-> (last, sums): per slot the last batch mean and the running sum as Python floats, None where the term is off.
+        One host read."""
+        if self._last is None:
+            return [None] * (3 * self.S), [None] * (3 * self.S)
+        both = torch.cat([self._last.double(), self._sums]).tolist()
+        n = 3 * self.S
+        return ([v if a else None for v, a in zip(both[:n], self._active)],
+                [v if a else None for v, a in zip(both[n:], self._active)])
+
+    def _run(self, images, heatmaps, masks, joints):
+        n = int(images.shape[0])
+        self.optimizer.zero_grad(set_to_none=True)
+        outputs = self.model(images)
+        terms = self.loss_factory(outputs, heatmaps, masks, joints)
+        loss = 0
+        for idx in range(self.S):
+            for k, vals in enumerate(terms):
+                if vals[idx] is None:
+                    continue
+                v = vals[idx].mean(dim=0)
+                slot = k * self.S + idx
+                self._active[slot] = True
+                d = v.detach()
+                self._last[slot].copy_(d)
+                self._sums[slot].add_(d.double() * n)
+                loss = loss + v
+        loss.backward()
+        self.optimizer.step()
+
+    def step(self, images, heatmaps, masks, joints):
+        if not self.model.training:
+            raise ValueError('CapturedStep: the model must be in training mode')
+        batch = (images, heatmaps, masks, joints)
+        if self._last is None:
+            self._last = torch.zeros(3 * self.S, dtype=torch.float32, device=images.device)
+            self._sums = torch.zeros(3 * self.S, dtype=torch.float64, device=images.device)
+        sig = tuple((tuple(t.shape), t.dtype) for t in _flat(batch))
+        seen = self._sights.get(sig, 0)
+        self._sights[sig] = seen + 1
+        if seen == 0:
+            self._run(*batch)
+            self.eager_steps += 1
+            self._grads_of = None
+            return
+        cap = self._captured.get(sig)
+        if cap is None:
+            static = tuple([torch.empty_like(t) for t in part] if isinstance(part, (list, tuple)) else torch.empty_like(part)
+                           for part in batch)
+            cap = dict(static=static, graph=torch.cuda.CUDAGraph())
+            for dst, src in zip(_flat(static), _flat(batch)):
+                dst.copy_(src)
+            with torch.cuda.graph(cap['graph']):
+                self._run(*static)
+            cap['params'] = [p for g in self.optimizer.param_groups for p in g['params']]
+            cap['grads'] = [p.grad for p in cap['params']]
+            self._captured[sig] = cap
+            self.captures += 1
+        else:
+            for dst, src in zip(_flat(cap['static']), _flat(batch)):
+                dst.copy_(src)
+        self.optimizer.sync_hyperparameters()
+        cap['graph'].replay()
+        self.replays += 1
+        if self._grads_of is not cap:                  # an eager step (or another graph) left other tensors in p.grad
+            for p, g in zip(cap['params'], cap['grads']):
+                p.grad = g
+            self._grads_of = cap
+
+
+def _do_train_captured(cfg, model, data_loader, loss_factory, optimizer, epoch, logger, graph):
+    S = cfg.LOSS.NUM_STAGES
+    freq = getattr(cfg, 'PRINT_FREQ', 1)
+    model.train()
+    if isinstance(graph, CapturedStep):
+        stepper = graph
+        if stepper.model is not model or stepper.optimizer is not optimizer or stepper.loss_factory is not loss_factory:
+            raise ValueError('do_train: the CapturedStep was built for another model, loss factory or optimizer')
+    else:
+        stepper = CapturedStep(cfg, model, loss_factory, optimizer)
+    stepper.reset_meters()
+    count = 0
+    for i, (images, heatmaps, masks, joints) in enumerate(data_loader):
+        stepper.step(images, heatmaps, masks, joints)
+        count += int(images.shape[0])
+        if logger is not None and i % freq == 0:
+            last, sums = stepper.read()
+            logger.info('Epoch: [%d][%d]\t%s' % (epoch, i, '\t'.join(
+                'Stage%d-%s: %.3e (%.3e)' % (idx, key, last[k * S + idx], sums[k * S + idx] / count)
+                for k, key in enumerate(_KEYS) for idx in range(S) if last[k * S + idx] is not None)))
+    if count == 0:
+        raise ValueError('do_train: the data loader yielded no batch')
+    last, sums = stepper.read()
+    return {key: [None if last[k * S + idx] is None else (last[k * S + idx], sums[k * S + idx] / count) for idx in range(S)]
+            for k, key in enumerate(_KEYS)}
+
+
+def do_train(cfg, model, data_loader, loss_factory, optimizer, epoch=0, teacher=None, logger=None, graph=False):
     """One epoch of trainer.py:41-113 for a ``torch.nn.Module`` whose ``model(images)`` gives the list of stage outputs:
     per batch ``(images, heatmaps, masks, joints)`` of ``data_loader`` (device tensors, as ``LabelledSet.batches`` yields
     them) the total loss of :82-105 through ``loss_factory`` (``core.loss.MultiLossFactory``), ``optimizer.zero_grad()``,
@@ -47,8 +189,17 @@ def do_train(cfg, model, data_loader, loss_factory, optimizer, epoch=0, teacher=
     by the batch size as do_train's AverageMeter accumulates it; None where the term is off.  ``logger``: an object with
     ``info``; one line per ``cfg.PRINT_FREQ`` batches (every batch where ``cfg`` has no such key).
 
+    ``graph``: True, or a ``CapturedStep`` kept by the caller so that its graphs serve every epoch: each batch goes through
+    ``CapturedStep.step`` -- eager at the first sight of a batch signature, captured at the second, replayed from then on --
+    with a ``litepose_amd.optim`` optimizer; the same updates and the same returned values as the eager loop, without a
+    host read per step (one per logged line and one at the end).  The teacher stays eager-only (ValueError).
+
     Not here: tensorboard scalars, ``fp16_optimizer``, the supernet's random-resolution resize (:49-59), debug image dumps,
     batch and data timers."""
+    if graph:
+        if teacher is not None:
+            raise ValueError('do_train: a teacher is not supported with graph=True')
+        return _do_train_captured(cfg, model, data_loader, loss_factory, optimizer, epoch, logger, graph)
     S = cfg.LOSS.NUM_STAGES
     last = dict(heatmaps=[None] * S, push=[None] * S, pull=[None] * S)
     sums = dict(heatmaps=[0.0] * S, push=[0.0] * S, pull=[0.0] * S)

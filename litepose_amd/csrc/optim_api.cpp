@@ -1,0 +1,116 @@
+// C ABI of the optimizer updates (include/litepose_amd.h, "optimizers"): argument validation and the packing of a tensor
+// list into by-value argument chunks (optim.h); the kernels live in optim_kernels.hip.  Nothing here allocates, copies to
+// the device or synchronises: the host arrays are read while a chunk is packed and the chunk travels in the launch.
+#include <hip/hip_runtime.h>
+
+#include "../../include/litepose_amd.h"
+#include "optim.h"
+
+extern "C" void lp_set_error_(const char* msg);   // engine.cpp owns the thread-local slot
+
+namespace {
+int fail(int code, const char* msg) {
+    lp_set_error_(msg);
+    return code;
+}
+bool al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+int64_t blocks_of(int64_t n) { return (n + LP_OPTIM_BLOCK_ELEMS - 1) / LP_OPTIM_BLOCK_ELEMS; }
+
+int check_numel(int count, const int64_t* numel) {
+    if (count <= 0 || !numel) return fail(LP_ERR_INVALID_ARG, "count must be positive and numel given");
+    for (int i = 0; i < count; ++i)
+        if (numel[i] <= 0) return fail(LP_ERR_INVALID_ARG, "every numel must be positive");
+    for (int i = 0; i < count; ++i)
+        if (numel[i] > 0x7fffff00LL) return fail(LP_ERR_UNSUPPORTED, "a tensor may hold at most 2^31 - 256 elements");
+    return LP_OK;
+}
+
+// every array given, every entry non-NULL and 4-byte aligned; rows[k] == nullptr: the row is not part of the call
+int check_rows(int count, const float* const* const* rows, int nrows) {
+    for (int k = 0; k < nrows; ++k) {
+        if (!rows[k]) continue;
+        for (int i = 0; i < count; ++i) {
+            if (!rows[k][i]) return fail(LP_ERR_INVALID_ARG, "a NULL tensor pointer");
+            if (!al4(rows[k][i])) return fail(LP_ERR_INVALID_ARG, "tensor pointers must be 4-byte aligned");
+        }
+    }
+    return LP_OK;
+}
+
+// The chunking rule: tensors in list order, each cut into blocks of LP_OPTIM_BLOCK_ELEMS elements in order; a chunk closes
+// when it holds LP_OPTIM_CHUNK_BLOCKS blocks, or LP_OPTIM_CHUNK_TENSORS tensors and the next block belongs to another
+// one.  A tensor that crosses a chunk boundary is an entry of both chunks.  emit(chunk) is called per closed chunk.
+template <class Emit>
+int for_each_chunk(int count, const float* const* const* rows, int nrows, const int64_t* numel, Emit emit) {
+    lp::OptimChunk ck = {};
+    int launches = 0;
+    for (int i = 0; i < count; ++i) {
+        const int64_t nb = blocks_of(numel[i]);
+        int64_t b = 0;
+        while (b < nb) {
+            if (ck.tensors == LP_OPTIM_CHUNK_TENSORS || ck.blocks == LP_OPTIM_CHUNK_BLOCKS) {
+                emit(ck);
+                ++launches;
+                ck = lp::OptimChunk{};
+            }
+            if (ck.tensors == 0) ck.first = i;
+            const int t = ck.tensors++;
+            for (int k = 0; k < nrows; ++k) ck.ptr[k][t] = rows && rows[k] ? const_cast<float*>(rows[k][i]) : nullptr;
+            ck.numel[t] = (int32_t)numel[i];
+            while (b < nb && ck.blocks < LP_OPTIM_CHUNK_BLOCKS) ck.map[ck.blocks++] = (uint32_t)t << 24 | (uint32_t)b++;
+        }
+    }
+    if (ck.tensors) {
+        emit(ck);
+        ++launches;
+    }
+    return launches;
+}
+}  // namespace
+
+extern "C" {
+
+int lp_optim_launches(int count, const int64_t* numel) {
+    if (int rc = check_numel(count, numel)) return rc;
+    return for_each_chunk(count, nullptr, 0, numel, [](const lp::OptimChunk&) {});
+}
+
+int lp_optim_adam(int count, float* const* param_io, const float* const* d_grad, float* const* exp_avg_io,
+                  float* const* exp_avg_sq_io, const int64_t* numel, float* step_io, const double* d_lr, double beta1,
+                  double beta2, double eps, double weight_decay, void* stream) {
+    if (int rc = check_numel(count, numel)) return rc;
+    if (!param_io || !d_grad || !exp_avg_io || !exp_avg_sq_io || !step_io || !d_lr) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (!al4(step_io) || ((uintptr_t)d_lr & 7)) return fail(LP_ERR_INVALID_ARG, "step_io must be 4-byte, d_lr 8-byte aligned");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(LP_ERR_INVALID_ARG, "betas must lie in [0, 1)");
+    if (!(eps >= 0.0) || !(weight_decay >= 0.0)) return fail(LP_ERR_INVALID_ARG, "eps and weight_decay must not be negative");
+    const float* const* rows[4] = {param_io, d_grad, exp_avg_io, exp_avg_sq_io};
+    if (int rc = check_rows(count, rows, 4)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    for_each_chunk(count, rows, 4, numel, [&](const lp::OptimChunk& ck) {
+        lp::launch_adam_chunk(ck, step_io, d_lr, beta1, beta2, eps, weight_decay, s);
+    });
+    lp::launch_step_advance(step_io, count, s);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "optim_adam launch failed");
+    return LP_OK;
+}
+
+int lp_optim_sgd(int count, float* const* param_io, const float* const* d_grad, float* const* momentum_io, const int64_t* numel,
+                 const double* d_lr, double momentum, double weight_decay, int nesterov, void* stream) {
+    if (int rc = check_numel(count, numel)) return rc;
+    if (!param_io || !d_grad || !d_lr) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if ((uintptr_t)d_lr & 7) return fail(LP_ERR_INVALID_ARG, "d_lr must be 8-byte aligned");
+    if (!(momentum >= 0.0) || !(weight_decay >= 0.0)) return fail(LP_ERR_INVALID_ARG, "momentum and weight_decay must not be negative");
+    if (nesterov && momentum == 0.0) return fail(LP_ERR_INVALID_ARG, "nesterov needs a momentum");
+    if ((momentum == 0.0) != (momentum_io == nullptr))
+        return fail(LP_ERR_INVALID_ARG, "momentum_io must be given exactly when momentum is not zero");
+    const float* const* rows[3] = {param_io, d_grad, momentum_io};
+    if (int rc = check_rows(count, rows, 3)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    for_each_chunk(count, rows, 3, numel, [&](const lp::OptimChunk& ck) {
+        lp::launch_sgd_chunk(ck, momentum_io != nullptr, d_lr, momentum, weight_decay, nesterov, s);
+    });
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "optim_sgd launch failed");
+    return LP_OK;
+}
+
+}  // extern "C"

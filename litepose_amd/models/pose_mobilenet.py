@@ -258,8 +258,8 @@ class TrainableLitePose(torch.nn.Module):
     ``backend='native'``: every layer runs on ``litepose_amd.nn.functional`` -- the library's kernels, forward and
     backward: the 1x1 and depthwise convolutions, every BatchNorm (+ activation, + residual), the dense 3x3 stem
     convolution ``first.0.0`` (``stem_conv``) and the ``ConvTranspose2d`` pairs of the Fusion Deconv Head
-    (``deconv_pair``).  No sum in it is atomic: one step gives the same bits every time, for every parameter; only the
-    optimizer is torch's.  One exception: the library has no data gradient for the stem, so when the image itself requires
+    (``deconv_pair``).  No sum in it is atomic: one step gives the same bits every time, for every parameter; with
+    ``litepose_amd.optim`` the optimizer is the library's as well.  One exception: the library has no data gradient for the stem, so when the image itself requires
     a gradient ``first.0.0`` runs on torch's ``conv2d``.  float32 on the GPU.
     ``backend='torch'``: every layer on torch's ops: the same module on any device and dtype.
 

@@ -1,0 +1,105 @@
+"""The buffer contract of ``lp_optim_adam`` / ``lp_optim_sgd`` (include/litepose_amd.h, "optimizers") with the guarded
+buffers of tests/_poison.py.  The ``*_io`` tensors are read AND written, so they cannot be poisoned; what the contract says is
+checked this way instead: every tensor sits between guard bands at exactly its size (some at a 4- but not 16-byte aligned
+address, the element in front of them a guard too), every element of every ``*_io`` tensor and of ``step_io`` changes in a
+call whose inputs make every new value differ from the old one, the gradients and ``d_lr`` are left as they were, and no
+guard byte changes -- also where the tensor list ends exactly at an argument chunk's boundary (the last tensor's guards are
+the first thing a block past the end would hit)."""
+import ctypes as C
+
+import pytest
+import torch
+
+import _poison as po
+from litepose_amd import _native as nv
+
+pytestmark = pytest.mark.gpu
+E, T, B = 4096, 64, 432                     # LP_OPTIM_BLOCK_ELEMS, LP_OPTIM_CHUNK_TENSORS, LP_OPTIM_CHUNK_BLOCKS
+
+
+def _g(n, seed, scale=1.0, lo=0.0):
+    t = torch.randn(n, generator=torch.Generator().manual_seed(seed)) * scale
+    return (t.abs() + lo if lo else t).cuda()
+
+
+def _arr(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+class Guarded(object):
+    """A copy of ``t`` between guard bands; ``shift``: start one element past a 16-byte boundary, that element a guard."""
+
+    def __init__(self, t, shift, what):
+        el = t.element_size()
+        self.what, self.start = what, t.clone()
+        self.place = po.place((t.numel() + int(shift)) * el, 16, None)
+        full = self.place.view(t.dtype, (t.numel() + int(shift),))
+        self.lead = full[:int(shift)].view(torch.uint8)
+        self.lead.fill_(po.GUARD_BYTE)
+        self.view = full[int(shift):]
+        self.view.copy_(t)
+        assert self.view.data_ptr() % 16 == (el if shift else 0)
+
+    def check(self):
+        self.place.check_guards(self.what)
+        assert bool((self.lead == po.GUARD_BYTE).all()), '%s: the element in front of the tensor changed' % self.what
+
+    def untouched(self):
+        self.check()
+        assert po.bitwise_equal(self.view, self.start), '%s changed (first element %s)' % (
+            self.what, po.first_difference(self.view, self.start))
+
+    def all_written(self):
+        self.check()
+        same = (po.as_bits(self.view) == po.as_bits(self.start)).nonzero()
+        assert same.numel() == 0, '%s: element %d was not written' % (self.what, int(same[0]))
+        assert bool(torch.isfinite(self.view).all()), self.what
+
+
+def _run(lengths, which, shifts=(False, True, False)):
+    n = len(lengths)
+    sh = lambda i: shifts[i % len(shifts)]                              # noqa: E731
+    # |p| and g at least 0.5, v at least 0.01: every update moves every element of every tensor it writes
+    P = [Guarded(_g(k, 10 + i, lo=0.5), sh(i), 'param_io[%d]' % i) for i, k in enumerate(lengths)]
+    G = [Guarded(_g(k, 1000 + i, lo=0.5), sh(i + 1), 'grad[%d]' % i) for i, k in enumerate(lengths)]
+    M = [Guarded(_g(k, 2000 + i, 0.1, lo=0.05), sh(i), 'exp_avg_io / momentum_io[%d]' % i) for i, k in enumerate(lengths)]
+    V = [Guarded(_g(k, 3000 + i, 0.01, lo=0.01), sh(i),'exp_avg_sq_io[%d]' % i) for i, k in enumerate(lengths)]
+    lr = Guarded(torch.tensor([0.25], dtype=torch.float64, device='cuda'), False, 'lr')
+    steps = Guarded(torch.arange(n, dtype=torch.float32, device='cuda'), True, 'step_io')
+    ptr = lambda xs: _arr([x.view for x in xs])                         # noqa: E731
+    ne = (C.c_int64 * n)(*lengths)
+    L = nv.lib()
+    if which == 'adam':
+        rc = L.lp_optim_adam(n, ptr(P), ptr(G), ptr(M), ptr(V), ne, nv.dptr(steps.view), nv.dptr(lr.view), 0.9, 0.999,
+                             1e-8, 0.0, nv.stream_ptr())
+        written, kept = P + M + V, G + [lr]
+    else:
+        mom = which == 'sgd-momentum'
+        rc = L.lp_optim_sgd(n, ptr(P), ptr(G), ptr(M) if mom else None, ne, nv.dptr(lr.view), 0.9 if mom else 0.0, 0.0, 0,
+                            nv.stream_ptr())
+        written, kept = P + (M if mom else []), G + [lr, steps] + V + ([] if mom else M)
+    assert rc == 0, L.lp_last_error()
+    torch.cuda.synchronize()
+    for x in written:
+        x.all_written()
+    for x in kept:
+        x.untouched()
+    if which == 'adam':
+        steps.check()
+        assert torch.equal(steps.view, steps.start + 1)
+
+
+@pytest.mark.parametrize('which', ['adam', 'sgd-momentum', 'sgd-plain'])
+def test_every_io_element_is_written_and_nothing_else(which):
+    _run([1, 3, 27 * 32, E - 1, E, E + 1, 2 * E + 517, 5, 4], which)
+
+
+@pytest.mark.parametrize('which', ['adam', 'sgd-momentum'])
+def test_a_list_that_ends_at_a_chunk_boundary(which):
+    """T tensors fill a chunk's tensor slots exactly; T - 1 tiny tensors and one of B - (T - 1) blocks fill its block slots
+    exactly, the last block full to its last element."""
+    _run([3] * (T - 1) + [5], which)
+    lengths = [2] * (T - 1) + [E * (B - (T - 1))]
+    ne = (C.c_int64 * len(lengths))(*lengths)
+    assert nv.lib().lp_optim_launches(len(lengths), ne) == 1
+    _run(lengths, which, shifts=(False,))

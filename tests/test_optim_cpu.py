@@ -1,0 +1,268 @@
+"""The optimizer calls without a device: the header declares the three calls and _native.py binds them, none of them names
+a writable ``d_*`` pointer, ``lp_optim_launches`` follows the header's chunking rule, every refusal is answered with its
+documented code before anything is launched (the pointers below are made-up addresses that are never dereferenced), and
+``litepose_amd.optim`` exchanges ``state_dict``s with ``torch.optim.Adam`` / ``SGD`` in both directions on CPU parameters."""
+import ctypes as C
+import os
+import re
+
+import pytest
+import torch
+
+from litepose_amd import _native as nv, arch_zoo, config, optim
+from litepose_amd.models import pose_mobilenet as pm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, 'include', 'litepose_amd.h')
+CALLS = ['lp_optim_launches', 'lp_optim_adam', 'lp_optim_sgd']
+LP_ERR_INVALID_ARG, LP_ERR_UNSUPPORTED = -1, -8
+LR = C.c_void_p(0x90008)                      # an 8-byte aligned made-up address for d_lr
+STEP = C.c_void_p(0x91000)
+
+
+def macro(name):
+    with open(HEADER) as f:
+        return int(re.search(r'#define\s+%s\s+(\d+)' % name, f.read()).group(1))
+
+
+E, T, B = macro('LP_OPTIM_BLOCK_ELEMS'), macro('LP_OPTIM_CHUNK_TENSORS'), macro('LP_OPTIM_CHUNK_BLOCKS')
+
+
+def launches(numel):
+    """The header's rule: tensors in order, blocks of E elements in order; a chunk closes at B blocks, or at T tensors when
+    the next block belongs to another tensor; a tensor cut by a chunk boundary is an entry of both chunks."""
+    n = t = b = 0
+    for ne in numel:
+        nb = -(-ne // E)
+        while nb:
+            if t == T or b == B:
+                n, t, b = n + 1, 0, 0
+            take = min(nb, B - b)
+            t, b, nb = t + 1, b + take, nb - take
+    return n + (1 if t else 0)
+
+
+def _ptrs(n, base=0x100000, stride=0x1000):
+    return (C.c_void_p * n)(*[base + stride * i for i in range(n)])
+
+
+def _numel(vals):
+    return (C.c_int64 * len(vals))(*vals)
+
+
+def test_header_declares_and_native_binds_the_three_calls():
+    with open(HEADER) as f:
+        hdr = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+    L = nv.lib()
+    for name in CALLS:
+        assert re.search(r'\b%s\s*\(' % name, hdr), name
+        assert name in nv.EXPORTS and hasattr(L, name), name
+    assert E % 1024 == 0 and T <= 256 and 4 * 8 * T + 4 * T + 4 * B + 16 + 48 <= 4096
+
+
+def test_no_optimizer_call_names_a_writable_pointer_d():
+    from test_poison_cpu import writable_device_calls
+    found = writable_device_calls()
+    assert len(found) == 20 and not set(CALLS) & found
+
+
+@pytest.mark.parametrize('numel', [[1], [E + 1], [E], [3] * T, [3] * (T + 1), [E * B], [E * B + 1], [5] * (B + 1),
+                                   [E * (B - 1) + 1, 7, E * 3], [2 ** 31 - 256]],
+                         ids=['one', 'block+1', 'block', 'T-tensors', 'T+1-tensors', 'B-blocks', 'B-blocks+1', 'B+1-tensors',
+                              'straddle', 'largest'])
+def test_launch_count_follows_the_chunking_rule(numel):
+    want = launches(numel)
+    assert nv.lib().lp_optim_launches(len(numel), _numel(numel)) == want
+    if numel in ([1], [E], [3] * T, [E * B]):
+        assert want == 1
+    if numel in ([3] * (T + 1), [E * B + 1]):
+        assert want == 2
+
+
+@pytest.mark.parametrize('name', arch_zoo.names())
+def test_launch_count_of_every_zoo_architecture(name):
+    m = pm.get_train_net(config.get_cfg('coco'), arch_zoo.get(name), backend='torch')
+    numel = [p.numel() for p in m.parameters()]
+    got = nv.lib().lp_optim_launches(len(numel), _numel(numel))
+    assert got == launches(numel) and 1 <= got <= len(numel)
+    print('%s: %d tensors, %d elements, %d update launches' % (name, len(numel), sum(numel), got))
+
+
+def test_adam_refusals():
+    L = nv.lib()
+    n = 3
+    p, g, m, v, ne = _ptrs(n), _ptrs(n, 0x200000), _ptrs(n, 0x300000), _ptrs(n, 0x400000), _numel([5, 6, 7])
+    ok = dict(count=n, p=p, g=g, m=m, v=v, ne=ne, step=STEP, lr=LR, b1=0.9, b2=0.999, eps=1e-8, wd=0.0)
+
+    def call(**kw):
+        a = dict(ok, **kw)
+        return L.lp_optim_adam(a['count'], a['p'], a['g'], a['m'], a['v'], a['ne'], a['step'], a['lr'], a['b1'], a['b2'],
+                               a['eps'], a['wd'], None)
+
+    odd = _ptrs(n)
+    odd[1] = 0x100002
+    hole = _ptrs(n)
+    hole[2] = None
+    for kw in (dict(count=0), dict(count=-1), dict(p=None), dict(g=None), dict(m=None), dict(v=None), dict(ne=None),
+               dict(step=None), dict(lr=None), dict(p=hole), dict(g=hole), dict(m=hole), dict(v=hole), dict(p=odd),
+               dict(g=odd), dict(m=odd), dict(v=odd), dict(ne=_numel([5, 0, 7])), dict(ne=_numel([5, -3, 7])),
+               dict(b1=1.0), dict(b1=-0.1), dict(b2=1.0), dict(b2=-1e-9), dict(b1=float('nan')), dict(eps=-1e-8),
+               dict(wd=-0.1)):
+        assert call(**kw) == LP_ERR_INVALID_ARG, kw
+        assert L.lp_last_error()
+    assert call(ne=_numel([5, 2 ** 31 - 255, 7])) == LP_ERR_UNSUPPORTED
+    assert L.lp_optim_launches(0, ne) == LP_ERR_INVALID_ARG and L.lp_optim_launches(3, None) == LP_ERR_INVALID_ARG
+    assert L.lp_optim_launches(3, _numel([1, 0, 1])) == LP_ERR_INVALID_ARG
+    assert L.lp_optim_launches(1, _numel([2 ** 31 - 255])) == LP_ERR_UNSUPPORTED
+
+
+def test_sgd_refusals():
+    L = nv.lib()
+    n = 3
+    p, g, b, ne = _ptrs(n), _ptrs(n, 0x200000), _ptrs(n, 0x300000), _numel([5, 6, 7])
+    ok = dict(count=n, p=p, g=g, b=b, ne=ne, lr=LR, mu=0.9, wd=0.0, nesterov=0)
+
+    def call(**kw):
+        a = dict(ok, **kw)
+        return L.lp_optim_sgd(a['count'], a['p'], a['g'], a['b'], a['ne'], a['lr'], a['mu'], a['wd'], a['nesterov'], None)
+
+    odd = _ptrs(n)
+    odd[0] = 0x100001
+    hole = _ptrs(n)
+    hole[0] = None
+    for kw in (dict(count=0), dict(p=None), dict(g=None), dict(ne=None), dict(lr=None), dict(p=hole), dict(g=hole),
+               dict(b=hole), dict(p=odd), dict(g=odd), dict(b=odd), dict(ne=_numel([0, 6, 7])), dict(mu=-0.5), dict(wd=-1.0),
+               dict(mu=0.0, b=None, nesterov=1),            # nesterov without a momentum
+               dict(mu=0.0),                                # a buffer list although momentum == 0
+               dict(b=None)):                               # a momentum without a buffer list
+        assert call(**kw) == LP_ERR_INVALID_ARG, kw
+    assert call(ne=_numel([2 ** 31 - 255, 6, 7])) == LP_ERR_UNSUPPORTED
+
+
+# ------------------------------------------------------------------ state_dict interchange on CPU parameters
+SHAPES = [(5, 3), (7,), (2, 3, 4)]
+
+
+def _params(seed=0):
+    g = torch.Generator().manual_seed(seed)
+    return [torch.nn.Parameter(torch.randn(s, generator=g)) for s in SHAPES]
+
+
+def _torch_steps(opt, params, rounds, skip_last_of=None):
+    """``rounds`` steps on fixed random gradients; parameter ``skip_last_of`` has no gradient in the last round, so its
+    step count stays one behind."""
+    g = torch.Generator().manual_seed(9)
+    for r in range(rounds):
+        for i, p in enumerate(params):
+            p.grad = None if (r == rounds - 1 and i == skip_last_of) else torch.randn(p.shape, generator=g)
+        opt.step()
+
+
+def _same_state(a, b):
+    assert sorted(a['state']) == sorted(b['state'])
+    for k in a['state']:
+        assert sorted(a['state'][k]) == sorted(b['state'][k]), k
+        for name, v in a['state'][k].items():
+            w = b['state'][k][name]
+            if v is None or w is None:
+                assert v is None and w is None, (k, name)
+            else:
+                assert torch.equal(torch.as_tensor(v).float().cpu(), torch.as_tensor(w).float().cpu()), (k, name)
+    assert len(a['param_groups']) == len(b['param_groups'])
+    for ga, gb in zip(a['param_groups'], b['param_groups']):
+        assert ga['params'] == gb['params']
+        for key in ('lr', 'betas', 'eps', 'weight_decay', 'momentum', 'nesterov'):
+            if key in ga or key in gb:
+                assert tuple(ga[key]) == tuple(gb[key]) if key == 'betas' else ga[key] == gb[key], key
+
+
+def test_adam_state_dict_round_trip_with_torch():
+    params = _params()
+    ref = torch.optim.Adam(params, lr=3e-3, betas=(0.8, 0.95), eps=1e-6, weight_decay=0.01)
+    _torch_steps(ref, params, 3, skip_last_of=1)
+    sd = ref.state_dict()
+    assert [float(sd['state'][i]['step']) for i in range(3)] == [3.0, 2.0, 3.0]
+    mine = optim.Adam(params, lr=1.0)
+    mine.load_state_dict(sd)
+    assert mine.param_groups[0]['lr'] == 3e-3 and tuple(mine.param_groups[0]['betas']) == (0.8, 0.95)
+    got = mine.state_dict()
+    _same_state(got, sd)
+    for i in range(3):
+        st = got['state'][i]
+        assert sorted(st) == ['exp_avg', 'exp_avg_sq', 'step']
+        assert st['step'].dtype == torch.float32 and st['step'].dim() == 0 and st['exp_avg'].dtype == torch.float32
+    # the counts live in one array per group; a parameter's state is a view of it
+    steps = mine._steps(mine.param_groups[0])
+    assert steps.tolist() == [3.0, 2.0, 3.0] and mine.state[params[1]]['step'].data_ptr() == steps[1].data_ptr()
+    # a saved dict owns its tensors
+    got['state'][0]['exp_avg'].zero_()
+    assert bool(mine.state[params[0]]['exp_avg'].any())
+    # and back: torch's Adam loads it and goes on exactly as the optimizer it came from
+    a, b = _params(), _params()
+    for p, q, r in zip(a, b, params):
+        p.data.copy_(r.data)
+        q.data.copy_(r.data)
+    back, twin = torch.optim.Adam(a, lr=1.0), torch.optim.Adam(b, lr=1.0)
+    back.load_state_dict(mine.state_dict())
+    twin.load_state_dict(sd)
+    _torch_steps(back, a, 2)
+    _torch_steps(twin, b, 2)
+    for p, q in zip(a, b):
+        assert torch.equal(p, q)
+    _same_state(back.state_dict(), twin.state_dict())
+
+
+@pytest.mark.parametrize('momentum', [0.9, 0.0])
+def test_sgd_state_dict_round_trip_with_torch(momentum):
+    params = _params(1)
+    ref = torch.optim.SGD(params, lr=0.05, momentum=momentum, weight_decay=1e-4, nesterov=momentum != 0)
+    _torch_steps(ref, params, 2, skip_last_of=2)
+    sd = ref.state_dict()
+    mine = optim.SGD(params, lr=1.0)
+    mine.load_state_dict(sd)
+    assert mine.param_groups[0]['momentum'] == momentum and mine.param_groups[0]['lr'] == 0.05
+    _same_state(mine.state_dict(), sd)
+    a, b = _params(1), _params(1)
+    for p, q, r in zip(a, b, params):
+        p.data.copy_(r.data)
+        q.data.copy_(r.data)
+    back, twin = torch.optim.SGD(a, lr=1.0), torch.optim.SGD(b, lr=1.0)
+    back.load_state_dict(mine.state_dict())
+    twin.load_state_dict(sd)
+    _torch_steps(back, a, 2)
+    _torch_steps(twin, b, 2)
+    for p, q in zip(a, b):
+        assert torch.equal(p, q)
+
+
+def test_construction_refusals_and_cpu_step():
+    with pytest.raises(TypeError):
+        optim.Adam([torch.nn.Parameter(torch.zeros(3, dtype=torch.float64))])
+    with pytest.raises(TypeError):
+        optim.SGD([torch.nn.Parameter(torch.zeros(3, dtype=torch.bfloat16))], lr=0.1)
+    with pytest.raises(ValueError):
+        optim.Adam(_params(), betas=(0.9, 1.0))
+    with pytest.raises(ValueError):
+        optim.SGD(_params(), lr=0.1, nesterov=True)
+    p = _params()
+    opt = optim.Adam(p)
+    for q in p:
+        q.grad = torch.ones_like(q)
+    with pytest.raises(RuntimeError, match='GPU'):
+        opt.step()
+    assert isinstance(opt, torch.optim.Optimizer) and isinstance(optim.SGD(p, lr=0.1), torch.optim.Optimizer)
+
+
+def test_get_optimizer_follows_the_reference():
+    cfg = config.get_cfg()
+    model = torch.nn.Linear(3, 2)
+    cfg.TRAIN = config.CfgNode(OPTIMIZER='adam', LR=2e-3, MOMENTUM=0.9, WD=1e-4, NESTEROV=False)
+    o = optim.get_optimizer(cfg, model)
+    assert isinstance(o, optim.Adam) and o.param_groups[0]['lr'] == 2e-3 and o.param_groups[0]['weight_decay'] == 0
+    cfg.TRAIN.OPTIMIZER = 'sgd'
+    o = optim.get_optimizer(cfg, model)
+    assert isinstance(o, optim.SGD)
+    g = o.param_groups[0]
+    assert (g['lr'], g['momentum'], g['weight_decay'], g['nesterov']) == (2e-3, 0.9, 1e-4, False)
+    cfg.TRAIN.OPTIMIZER = 'rmsprop'
+    assert optim.get_optimizer(cfg, model) is None

@@ -54,8 +54,27 @@ class CapturedStep(object):
     ``read()`` fetches both.  ``captures``, ``replays`` and ``eager_steps`` count what happened.
 
     ``optimizer`` must be a ``litepose_amd.optim`` optimizer: its ``lr`` and step counts live on the device, torch's own
-    would be baked into the graph.  ``sync_hyperparameters()`` runs before every replay.  The model must be in training mode
-    and stay there.  After a step ``p.grad`` holds that step's gradient, as in the eager loop."""
+    would be baked into the graph.  ``sync_hyperparameters()`` runs at the top of every step.  The model must be in
+    training mode whenever ``step`` is called.  After a step ``p.grad`` holds that step's gradient, as in the eager loop.
+
+    A graph holds raw addresses.  What may happen between two steps, and what ``step`` does about it (DESIGN.md 4f has
+    the table with the test that pins each row):
+
+      nothing needed   a changed ``lr`` (a scheduler), ``model.load_state_dict()`` (in place), ``model.eval()`` ... a
+                       forward under ``no_grad`` ... ``model.train()``, ``optimizer.state_dict()``, another batch
+                       signature, a new epoch (``reset_meters``)
+      restores         ``p.grad`` after EVERY replay: ``optimizer.zero_grad()``, ``model.zero_grad()``, an eager step on
+                       the same optimizer or another graph's replay in between change nothing about it
+      invalidates      ``optimizer.load_state_dict()`` and ``optimizer.add_param_group()``: the optimizer's ``generation``
+                       has moved, ``step`` calls ``invalidate()`` itself
+      refuses          a changed betas / eps / weight_decay / momentum / nesterov: RuntimeError before anything is copied,
+                       run or replayed; call ``invalidate()`` and go on with the new value
+      the caller's     ``requires_grad_()`` on a parameter, or any other change of WHICH tensors a step touches: call
+                       ``invalidate()``
+
+    ``invalidate()`` drops every graph and forgets every sight (signatures start over: eager, then captured) and calls
+    ``optimizer.forget_captures()``; ``invalidations`` counts them, the other counters keep counting.  One ``CapturedStep``
+    per optimizer: a second one would see the first one's invalidations as events of its own."""
 
     def __init__(self, cfg, model, loss_factory, optimizer):
         from .. import optim
@@ -66,11 +85,21 @@ class CapturedStep(object):
             raise ValueError('CapturedStep: the model must be in training mode')
         self.model, self.loss_factory, self.optimizer = model, loss_factory, optimizer
         self.S = int(cfg.LOSS.NUM_STAGES)
-        self.captures = self.replays = self.eager_steps = 0
+        self.captures = self.replays = self.eager_steps = self.invalidations = 0
         self._sights, self._captured = {}, {}
         self._last = self._sums = None
         self._active = [False] * (3 * self.S)
-        self._grads_of = None                      # the captured entry whose gradients p.grad holds (None: an eager step's)
+        self._generation = optimizer.generation    # the optimizer's generation the sights and graphs belong to
+
+    def invalidate(self):
+        """Drop every graph and forget every sight: each signature runs eagerly at its next sight and is captured at the one
+        after, against the optimizer as it then is.  Also ``optimizer.forget_captures()``."""
+        if self._captured:
+            torch.cuda.synchronize()               # no graph is destroyed while a replay of it may still be running
+        self._sights, self._captured = {}, {}
+        self.optimizer.forget_captures()
+        self._generation = self.optimizer.generation
+        self.invalidations += 1
 
     def reset_meters(self):
         """Zero the running sums (the start of an epoch)."""
@@ -110,6 +139,9 @@ class CapturedStep(object):
     def step(self, images, heatmaps, masks, joints):
         if not self.model.training:
             raise ValueError('CapturedStep: the model must be in training mode')
+        if self.optimizer.generation != self._generation:    # load_state_dict / add_param_group: the graphs are stale
+            self.invalidate()
+        self.optimizer.sync_hyperparameters()                # refuses a by-value change here: nothing has been touched yet
         batch = (images, heatmaps, masks, joints)
         if self._last is None:
             self._last = torch.zeros(3 * self.S, dtype=torch.float32, device=images.device)
@@ -120,7 +152,6 @@ class CapturedStep(object):
         if seen == 0:
             self._run(*batch)
             self.eager_steps += 1
-            self._grads_of = None
             return
         cap = self._captured.get(sig)
         if cap is None:
@@ -138,13 +169,11 @@ class CapturedStep(object):
         else:
             for dst, src in zip(_flat(cap['static']), _flat(batch)):
                 dst.copy_(src)
-        self.optimizer.sync_hyperparameters()
         cap['graph'].replay()
         self.replays += 1
-        if self._grads_of is not cap:                  # an eager step (or another graph) left other tensors in p.grad
-            for p, g in zip(cap['params'], cap['grads']):
+        for p, g in zip(cap['params'], cap['grads']):  # whatever the caller, an eager step or another graph left in p.grad
+            if p.grad is not g:
                 p.grad = g
-            self._grads_of = cap
 
 
 def _do_train_captured(cfg, model, data_loader, loss_factory, optimizer, epoch, logger, graph):
@@ -192,7 +221,11 @@ def do_train(cfg, model, data_loader, loss_factory, optimizer, epoch=0, teacher=
     ``graph``: True, or a ``CapturedStep`` kept by the caller so that its graphs serve every epoch: each batch goes through
     ``CapturedStep.step`` -- eager at the first sight of a batch signature, captured at the second, replayed from then on --
     with a ``litepose_amd.optim`` optimizer; the same updates and the same returned values as the eager loop, without a
-    host read per step (one per logged line and one at the end).  The teacher stays eager-only (ValueError).
+    host read per step (one per logged line and one at the end).  The teacher stays eager-only (ValueError).  A kept
+    ``CapturedStep`` survives what a run does between steps and epochs -- a scheduler, validation in ``eval()`` mode,
+    ``zero_grad``, eager epochs on the same optimizer, ``model.load_state_dict``; it captures again by itself after
+    ``optimizer.load_state_dict`` / ``add_param_group``; it refuses a changed by-value hyperparameter before it touches
+    anything, until ``CapturedStep.invalidate()`` (its docstring lists the events).
 
     Not here: tensorboard scalars, ``fp16_optimizer``, the supernet's random-resolution resize (:49-59), debug image dumps,
     batch and data timers."""

@@ -5,7 +5,15 @@ of launches whose arguments carry the pointers.  ``lr`` is read from a device fp
 counts live in one device array per group, so a ``step()`` can sit inside a captured graph and a scheduler
 (``MultiStepLR`` writes ``param_groups[i]['lr']``) still takes effect: ``sync_hyperparameters()`` uploads the value when it
 has changed.  The other hyperparameters travel by value in the launch; changing one after a capture is refused at the next
-``sync_hyperparameters()``.
+``sync_hyperparameters()`` -- before anything is written -- until ``forget_captures()`` (``CapturedStep.invalidate()``
+calls it) has cleared the marks.
+
+A captured graph holds the addresses of the state tensors, of the ``lr`` scalars and of the step arrays.  ``generation``
+counts the events after which a graph captured earlier no longer describes the optimizer: ``load_state_dict()`` (every state
+tensor and device scalar is a new one), ``add_param_group()`` after construction (a group the graph does not update, without
+state yet) and ``forget_captures()``.  ``core.trainer.CapturedStep`` compares it before every step and captures again when it
+has moved.  Nothing else moves it: ``state_dict()``, ``zero_grad()``, a changed ``lr`` and ``sync_hyperparameters()`` leave
+every address where it was.
 
 ``state_dict()`` / ``load_state_dict()`` speak torch's format (per parameter ``step``, ``exp_avg``, ``exp_avg_sq`` or
 ``momentum_buffer``, plus ``param_groups``), in both directions with the torch optimizer of the same name on the same
@@ -26,16 +34,22 @@ class _NativeOptimizer(torch.optim.Optimizer):
     _SLOTS = ()                  # per-parameter state tensors shaped like the parameter
 
     def __init__(self, params, defaults):
+        self._constructed = False
         super().__init__(params, defaults)
         self._native = {}        # id(group) -> dict(steps=[n] fp32 | None, lr=0-dim fp64, lr_host, captured=by-value key | None)
+        self.generation = 0      # moves when a graph captured earlier no longer describes this optimizer (module docstring)
+        self._constructed = True
 
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
         for p in self.param_groups[-1]['params']:
-            if p.dtype != torch.float32:
-                raise TypeError('%s: float32 parameters only, got %s' % (type(self).__name__, p.dtype))
-            if p.layout != torch.strided:
-                raise TypeError('%s: dense parameters only, got %s' % (type(self).__name__, p.layout))
+            what = ('float32 parameters only, got %s' % p.dtype if p.dtype != torch.float32 else
+                    'dense parameters only, got %s' % p.layout if p.layout != torch.strided else None)
+            if what:
+                self.param_groups.pop()                  # a refused group is no group, and no event
+                raise TypeError('%s: %s' % (type(self).__name__, what))
+        if self._constructed:
+            self.generation += 1
 
     # ---- per-group device state ----
     def _group_native(self, group):
@@ -70,15 +84,25 @@ class _NativeOptimizer(torch.optim.Optimizer):
     def _by_value(self, group):
         return tuple(group[k] for k in self._BY_VALUE)
 
+    def forget_captures(self):
+        """Clear every group's mark of a captured ``step()`` and move ``generation``: the graphs that held the by-value
+        hyperparameters are the caller's to drop (``CapturedStep.invalidate()`` does both)."""
+        for ns in self._native.values():
+            ns['captured'] = None
+        self.generation += 1
+
     def sync_hyperparameters(self):
-        """Write every group's ``lr`` into its device scalar where the value has changed, and refuse a by-value
-        hyperparameter that differs from what a captured ``step()`` holds."""
+        """Refuse a by-value hyperparameter that differs from what a captured ``step()`` holds -- for every group, before
+        anything is written -- then write every group's ``lr`` into its device scalar where the value has changed."""
         for group in self.param_groups:
             ns = self._group_native(group)
             if ns['captured'] is not None and ns['captured'] != self._by_value(group):
                 raise RuntimeError('%s: %s changed after step() was captured (%r -> %r): these travel by value in the '
-                                   'captured launches; capture again' % (type(self).__name__, '/'.join(self._BY_VALUE),
-                                                                         ns['captured'], self._by_value(group)))
+                                   'captured launches; call CapturedStep.invalidate() (or forget_captures() on an optimizer '
+                                   'captured by hand) to capture again'
+                                   % (type(self).__name__, '/'.join(self._BY_VALUE), ns['captured'], self._by_value(group)))
+        for group in self.param_groups:
+            ns = self._group_native(group)
             lr = float(group['lr'])
             if lr != ns['lr_host']:
                 ns['lr'].fill_(lr)
@@ -143,8 +167,11 @@ class _NativeOptimizer(torch.optim.Optimizer):
         return sd
 
     def load_state_dict(self, state_dict):
+        """torch's loader, then the library's layout again.  Every state tensor, ``lr`` scalar and step array is a NEW
+        tensor afterwards and the marks of a captured ``step()`` are gone: ``generation`` moves."""
         super().load_state_dict(state_dict)
         self._native = {}
+        self.generation += 1
         for group in self.param_groups:
             steps = None
             for i, p in enumerate(group['params']):
@@ -244,6 +271,7 @@ class SGD(_NativeOptimizer):
     def load_state_dict(self, state_dict):                      # no step counts here
         torch.optim.Optimizer.load_state_dict(self, state_dict)
         self._native = {}
+        self.generation += 1
         for group in self.param_groups:
             for p in group['params']:
                 st = self.state.get(p)

@@ -266,3 +266,112 @@ def test_get_optimizer_follows_the_reference():
     assert (g['lr'], g['momentum'], g['weight_decay'], g['nesterov']) == (2e-3, 0.9, 1e-4, False)
     cfg.TRAIN.OPTIMIZER = 'rmsprop'
     assert optim.get_optimizer(cfg, model) is None
+
+
+# ------------------------------------------------------------------ generation: what a captured step must notice
+def _two_group_optimizer(which, seed=3):
+    """A library optimizer over two groups with state in every slot (loaded from torch's optimizer after two steps: a
+    ``step()`` of the library's own needs the GPU) -> (optimizer, params)."""
+    params = _params(seed)
+    groups = lambda: [dict(params=params[:2]), dict(params=params[2:], lr=0.02)]
+    if which == 'adam':
+        ref, mine = torch.optim.Adam(groups(), lr=0.01), optim.Adam(groups(), lr=0.01)
+    else:
+        ref, mine = torch.optim.SGD(groups(), lr=0.01, momentum=0.9), optim.SGD(groups(), lr=0.01, momentum=0.9)
+    _torch_steps(ref, params, 2)
+    assert mine.generation == 0                             # the groups of the constructor do not count
+    mine.load_state_dict(ref.state_dict())
+    assert mine.generation == 1
+    return mine, params
+
+
+def _mark_captured(opt):
+    """What ``step()`` records while a capture is under way: the by-value hyperparameters the launches hold."""
+    for g in opt.param_groups:
+        opt._group_native(g)['captured'] = opt._by_value(g)
+
+
+def _addresses(opt):
+    """The tensors a captured ``step()`` holds by address -> (list of tensors, kept alive by the caller, and their addresses)."""
+    held = []
+    for g in opt.param_groups:
+        ns = opt._group_native(g)
+        held.append(ns['lr'])
+        if ns['steps'] is not None:
+            held.append(ns['steps'])
+        for p in g['params']:
+            held.extend(opt.state[p][k] for k in opt._slots(g))
+    return held, [t.data_ptr() for t in held]
+
+
+@pytest.mark.parametrize('which', ['adam', 'sgd'])
+def test_generation_moves_on_three_events_and_on_nothing_else(which):
+    opt, params = _two_group_optimizer(which)
+    held, where = _addresses(opt)
+    start = opt.generation
+    # not on these: every address a captured step holds stays where it was
+    opt.state_dict()
+    for p in params:
+        p.grad = torch.ones_like(p)
+    opt.zero_grad()
+    opt.zero_grad(set_to_none=False)
+    opt.param_groups[0]['lr'] = 0.005
+    opt.sync_hyperparameters()
+    opt.sync_hyperparameters()
+    for g in opt.param_groups:                              # as a scheduler writes it
+        g['lr'] *= 0.5
+    opt.sync_hyperparameters()
+    assert opt.generation == start and _addresses(opt)[1] == where
+    assert [float(opt._group_native(g)['lr']) for g in opt.param_groups] == [0.0025, 0.01]
+    # on these three
+    opt.load_state_dict(opt.state_dict())
+    assert opt.generation == start + 1
+    extra = torch.nn.Parameter(torch.zeros(4))
+    opt.add_param_group(dict(params=[extra]))
+    assert opt.generation == start + 2 and len(opt.param_groups) == 3
+    opt.forget_captures()
+    assert opt.generation == start + 3
+    with pytest.raises(TypeError):                          # a refused group is no event ... and no group
+        opt.add_param_group(dict(params=[torch.nn.Parameter(torch.zeros(2, dtype=torch.float64))]))
+    assert opt.generation == start + 3 and len(opt.param_groups) == 3
+
+
+@pytest.mark.parametrize('which', ['adam', 'sgd'])
+def test_a_by_value_change_is_refused_while_the_marks_stand_and_before_any_write(which):
+    opt, _ = _two_group_optimizer(which)
+    _mark_captured(opt)
+    opt.sync_hyperparameters()                              # unchanged values pass
+    opt.param_groups[0]['lr'] = 0.5                         # a legal change in the first group ...
+    opt.param_groups[1]['weight_decay'] = 0.125             # ... and a refused one in the second
+    for _ in range(2):
+        with pytest.raises(RuntimeError, match=r'captured.*CapturedStep\.invalidate\(\)'):
+            opt.sync_hyperparameters()
+        assert float(opt._group_native(opt.param_groups[0])['lr']) == 0.01      # nothing was written
+    for p in opt.param_groups[0]['params']:
+        p.grad = torch.ones_like(p)
+    with pytest.raises(RuntimeError, match='captured'):     # the eager step() checks before it looks at a gradient
+        opt.step()
+    generation = opt.generation
+    opt.forget_captures()
+    assert opt.generation == generation + 1
+    assert all(opt._group_native(g)['captured'] is None for g in opt.param_groups)
+    opt.sync_hyperparameters()                              # the new values are accepted and the lr arrives
+    assert float(opt._group_native(opt.param_groups[0])['lr']) == 0.5
+
+
+@pytest.mark.parametrize('which', ['adam', 'sgd'])
+def test_load_state_dict_moves_every_address_and_the_generation(which):
+    """Why a captured step must start over after ``load_state_dict``: torch's loader hands over new state tensors and new
+    group dicts, and the device scalars are rebuilt -- every address a graph would hold is stale, with nothing to fault on.
+    The guarantee the captured step relies on is the generation."""
+    opt, _ = _two_group_optimizer(which)
+    _mark_captured(opt)
+    held, where = _addresses(opt)                           # ``held`` keeps the old tensors alive: no address can be reused
+    groups = list(opt.param_groups)
+    generation = opt.generation
+    opt.load_state_dict(opt.state_dict())
+    assert opt.generation == generation + 1
+    now = _addresses(opt)[1]
+    assert len(now) == len(where) and not set(now) & set(where)
+    assert all(g is not old for g, old in zip(opt.param_groups, groups))
+    assert all(opt._group_native(g)['captured'] is None for g in opt.param_groups)

@@ -788,7 +788,13 @@ int lp_bn_backward(const float* d_grad_y, const float* d_x, const float* d_gamma
  * lp_pw_backward: grad_x_out or grad_w_out may be NULL (not both): only the other gradient is computed, and the
  * workspace (lp_pw_backward_workspace_bytes with the matching want_x / want_w flags) holds only its share.  d_x is read
  * only for grad_w_out, d_w only for grad_x_out (each may be NULL when not read).
- * Writes: lp_pw_forward every element of y_out; lp_pw_backward every element of each output given.                     */
+ * Writes: lp_pw_forward every element of y_out; lp_pw_backward every element of each output given.
+ * lp_pw_tile_choice: host arithmetic only (no launch, no device): the tile of the fp32 MFMA 1x1 kernel that a 1x1 over
+ * Ca + Cb input channels picks when it has no bf16x3-split weights, as both calls above always do (forward: Ca = Cin,
+ * Cout; data gradient: Ca = Cout, Cout = Cin; Cb = 0, has_res = 0).  A wave owns 32 PXV pixels x 32 NB channels; returns
+ * NB * 16 + PXV (NB 1..3, PXV 1, 2 or 4), LP_ERR_INVALID_ARG for a non-positive size.  For tests and tools that must know
+ * which form a shape runs.                                                                                              */
+int lp_pw_tile_choice(int N, int Ca, int Cb, int Cout, int HW, int has_res);
 #define LP_PW_WGRAD_SLICE 1024
 size_t lp_pw_forward_workspace_bytes(int Cin, int Cout);
 int lp_pw_forward(const float* d_x, const float* d_w, float* y_out, int N, int Cin, int Cout, int HW, void* workspace,

@@ -91,6 +91,9 @@ void launch_pw(const float* inA, int Ca, const float* inB, int Cb,
                int N, int HW, int Cout, int act, hipStream_t s, const void* wsplit = nullptr, int pw3d_mode = 1);
 // wsplit: optional exact bf16x3 split of the same weights ([Cout/32][K/16][3][64 lanes] x 4 dwords) for
 // the compute-bound variant; only used for single-source layers with K % 16 == 0
+// the pw2_kernel<NB, PXV> launch_pw picks when it does not take the wsplit route (host arithmetic, no launch)
+struct PwTile { int NB, PXV; };
+PwTile pw_tile_choice(int N, int Ca, int Cb, int Cout, int HW, bool has_res);
 
 // fused depthwise(K7)+bias+ReLU6 -> 1x1 project + bias (+res); false = shape not supported
 bool launch_dwpw(const float* in, const float* wdw, const float* bdw, const float* wp, const float* bias,

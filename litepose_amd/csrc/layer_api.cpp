@@ -79,6 +79,12 @@ static int pw_check(int N, int Cin, int Cout, int HW) {
     return LP_OK;
 }
 
+int lp_pw_tile_choice(int N, int Ca, int Cb, int Cout, int HW, int has_res) {
+    if (N < 1 || Ca < 1 || Cb < 0 || Cout < 1 || HW < 1) return fail(LP_ERR_INVALID_ARG, "N, Ca, Cout and HW must be positive, Cb non-negative");
+    const lp::PwTile t = lp::pw_tile_choice(N, Ca, Cb, Cout, HW, has_res != 0);
+    return t.NB * 16 + t.PXV;
+}
+
 size_t lp_pw_forward_workspace_bytes(int Cin, int Cout) {
     if (Cin < 1 || Cout < 1 || Cin > 65535 || Cout > 65535) return 0;
     return (frag_floats(Cout, Cin) + bias_floats(Cout)) * sizeof(float);

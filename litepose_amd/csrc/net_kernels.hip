@@ -1094,39 +1094,46 @@ static void launch_pw2_t(const float* inA, int Ca, const float* inB, int Cb, con
                            NG, HW / PXV, HW, Cout, act);
 }
 
+// Tile choice of the fp32 MFMA 1x1 (pw2_kernel<NB, PXV>): a wave owns PXV*32 pixels x NB*32 channels.  PXV is as wide as
+// the plane size allows (16-byte loads/stores); NB in {1,2,3} minimises a small cost model fitted to a sweep on MI355X
+// (profiles/r01_pw_tile_sweep.txt):
+//   time ~ rounds(waves / (1024 SIMDs * occupancy)) * (occupancy_used * mfma_cycles + overhead)
+// Host arithmetic only: launch_pw's one source of the choice, and what lp_pw_tile_choice reports.
+PwTile pw_tile_choice(int N, int Ca, int Cb, int Cout, int HW, bool has_res) {
+    const long NP = (long)N * HW;
+    const int cblocks = (Cout + 31) / 32;
+    PwTile t{1, (HW % 4 == 0) ? 4 : (HW % 2 == 0 ? 2 : 1)};
+    const int PXV = t.PXV;
+    const long ptiles = (NP / PXV + 31) / 32;
+    const int KP = (Ca + Cb) / 2;
+    double best = 1e300;
+    for (int nb = 1; nb <= 3 && nb <= cblocks; ++nb) {
+        const long waves = ptiles * ((cblocks + nb - 1) / nb);
+        const int regs = nb * PXV * 16 * 2 + 32;                       // VGPR+AGPR estimate
+        const int occ = regs <= 128 ? 4 : (regs <= 168 ? 3 : (regs <= 256 ? 2 : 1));
+        const long slots = 1024L * occ;
+        const long rounds = (waves + slots - 1) / slots;
+        const double per_simd = (double)waves / 1024.0 / rounds;       // waves sharing a SIMD
+        const double used = per_simd < 1.0 ? 1.0 : (per_simd > occ ? occ : per_simd);
+        const double t_mfma = rounds * (used * (double)KP * nb * PXV * 64.0 + 8000.0);
+        // HBM term: the input is re-read once per channel group; ~2.3 B/cycle/SIMD at 5 TB/s
+        const double bytes = (double)NP * 4.0 * ((double)(Ca + Cb) * ((cblocks + nb - 1) / nb) +
+                                                 (double)Cout * (has_res ? 2 : 1));
+        const double t_mem = bytes / (1024.0 * 2.3);
+        const double tt = t_mfma > t_mem ? t_mfma : t_mem;
+        if (tt < best * 0.999) { best = tt; t.NB = nb; }
+    }
+    return t;
+}
+
 void launch_pw(const float* inA, int Ca, const float* inB, int Cb, const float* wp, const float* b,
                const float* res, float* out, int N, int HW, int Cout, int act, hipStream_t s,
                const void* wsplit, int pw3d_mode) {
     const long NP = (long)N * HW;
     const int cblocks = (Cout + 31) / 32;
-    // Tile choice: a wave owns PXV*32 pixels x NB*32 channels.  PXV is as wide as the plane
-    // size allows (16-byte loads/stores); NB in {1,2,3} minimises a small cost model fitted
-    // to a sweep on MI355X (profiles/r01_pw_tile_sweep.txt):
-    //   time ~ rounds(waves / (1024 SIMDs * occupancy)) * (occupancy_used * mfma_cycles + overhead)
-    int PXV = (HW % 4 == 0) ? 4 : (HW % 2 == 0 ? 2 : 1);
-    int NB = 1;
+    const PwTile tile = pw_tile_choice(N, Ca, Cb, Cout, HW, res != nullptr);
+    const int PXV = tile.PXV, NB = tile.NB;
     bool bound_mfma = false;
-    {
-        const long ptiles = (NP / PXV + 31) / 32;
-        const int KP = (Ca + Cb) / 2;
-        double best = 1e300;
-        for (int nb = 1; nb <= 3 && nb <= cblocks; ++nb) {
-            const long waves = ptiles * ((cblocks + nb - 1) / nb);
-            const int regs = nb * PXV * 16 * 2 + 32;                       // VGPR+AGPR estimate
-            const int occ = regs <= 128 ? 4 : (regs <= 168 ? 3 : (regs <= 256 ? 2 : 1));
-            const long slots = 1024L * occ;
-            const long rounds = (waves + slots - 1) / slots;
-            const double per_simd = (double)waves / 1024.0 / rounds;       // waves sharing a SIMD
-            const double used = per_simd < 1.0 ? 1.0 : (per_simd > occ ? occ : per_simd);
-            const double t_mfma = rounds * (used * (double)KP * nb * PXV * 64.0 + 8000.0);
-            // HBM term: the input is re-read once per channel group; ~2.3 B/cycle/SIMD at 5 TB/s
-            const double bytes = (double)NP * 4.0 * ((double)(Ca + Cb) * ((cblocks + nb - 1) / nb) +
-                                                     (double)Cout * (res ? 2 : 1));
-            const double t_mem = bytes / (1024.0 * 2.3);
-            const double t = t_mfma > t_mem ? t_mfma : t_mem;
-            if (t < best * 0.999) { best = t; NB = nb; }
-        }
-    }
     // compute-bound under fp32 MFMA -> exact bf16x3 split kernel (2.67x the matrix-core rate).
     // The choice depends on the LAYER SHAPE only (arithmetic intensity K*Cout/(K+Cout) in MAC per
     // element moved; fp32-MFMA balance ~ 31 FLOP/B), never on the batch size, so that a batched run

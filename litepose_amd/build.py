@@ -38,7 +38,10 @@ SOURCES = [
     ('stem_kernels.hip', []),
     ('bf16_kernels.hip', []),
     ('convk_kernels.hip', []),
-    ('calib_kernels.hip', []),
+    # no hand-placed packed FMAs: raw convolutions, fp64 statistics.  With the feature on, the NaN-keeping select of
+    # bn_apply_kernel<VEC> made the compiler pack `v - mean` into v_pk_add_f32 with neg_lo / neg_hi, a form the ISA scan
+    # below does not have on its cleared list and refuses
+    ('calib_kernels.hip', NOPK),
     ('ae_kernels.hip', ['-ffp-contract=off'] + NOPK),
     ('ae_mid_kernels.hip', ['-ffp-contract=off'] + NOPK),
     ('fast_api.cpp', []),

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(float* __restrict__ x, co
     const double cnt = (double)N * (double)HW;
     const double mean = sum / cnt;
     double var = sq / cnt - mean * mean;
-    var = var > 0.0 ? var : 0.0;
+    var = var < 0.0 ? 0.0 : var;                        // a NaN variance (a NaN or an Inf in the channel) stays NaN
     if (s == 0 && threadIdx.x == 0) {
         const double unb = cnt > 1.0 ? var * (cnt / (cnt - 1.0)) : var;
         bn[2 * C + c] = (float)((1.0 - momentum) * (double)bn[2 * C + c] + momentum * mean);
@@ -210,7 +210,10 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(float* __restrict__ x, co
     const long plane = (long)C * HW;
     long u = u0 + threadIdx.x;
     int n = (int)(u / units), i = (int)(u - (long)n * units);
-    auto f = [&](float v) { return fminf(fmaxf(((v - meanf) * istd) * ga + be, lo), hi); };
+    auto f = [&](float v) {                             // a NaN stays a NaN, as in bn_fwd_kernel (layer_kernels.hip)
+        const float z = ((v - meanf) * istd) * ga + be;
+        return z != z ? z : fminf(fmaxf(z, lo), hi);
+    };
     for (; u < u1; u += 256) {
         const long base = (long)c * HW + n * plane;
         if (VEC) {

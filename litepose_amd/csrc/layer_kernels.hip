@@ -30,9 +30,11 @@ typedef float f32x16_t __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ float bn_z(float v, float meanf, float istd, float ga, float be) {
     return fmaf((v - meanf) * istd, ga, be);
 }
-// act'(z) as torch has it: strict inequalities (ReLU: z > 0; ReLU6: 0 < z < 6)
+// act'(z) as torch has it: strict inequalities (ReLU: z > 0; ReLU6: 0 < z < 6), written as torch's backward writes them,
+// "closed where z <= 0 or z >= 6": a NaN z is on neither side of a kink and PASSES its gradient (threshold_backward,
+// hardtanh_backward), so that dbeta of a channel that went NaN is the sum of dy, as torch's, and a NaN dy there shows.
 __device__ __forceinline__ bool bn_pass(float z, int act) {
-    return act == ACT_NONE || (z > 0.f && (act != ACT_RELU6 || z < 6.f));
+    return act == ACT_NONE || (!(z <= 0.f) && (act != ACT_RELU6 || !(z >= 6.f)));
 }
 
 // the slice walk of bn_stats_kernel: unit u of the channel's N * units -> element offset, 256 units per step
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(256) void bn_fwd_kernel(const float* __restrict__ x
         const double cnt = (double)N * (double)HW;
         mean = sum / cnt;
         double var = sq / cnt - mean * mean;
-        var = var > 0.0 ? var : 0.0;
+        var = var < 0.0 ? 0.0 : var;                    // a NaN variance (a NaN or an Inf in the channel) stays NaN
         invstd = 1.0 / sqrt(var + eps);
         if (s == 0 && threadIdx.x == 0) {
             const double unb = cnt > 1.0 ? var * (cnt / (cnt - 1.0)) : var;
@@ -105,7 +107,12 @@ __global__ __launch_bounds__(256) void bn_fwd_kernel(const float* __restrict__ x
     const float ga = gamma[c], be = beta[c];
     const float lo = act == ACT_NONE ? -INFINITY : 0.f;
     const float hi = act == ACT_RELU6 ? 6.f : INFINITY;
-    auto f = [&](float v) { return fminf(fmaxf(bn_z(v, meanf, istd, ga, be), lo), hi); };
+    // fmaxf / fminf return the operand that is not a NaN: the clamp alone would turn a NaN z into 0 (ReLU, ReLU6) or -inf
+    // (none), where torch's relu, relu6 and batch_norm keep it.  Every other z takes the clamp it always took.
+    auto f = [&](float v) {
+        const float z = bn_z(v, meanf, istd, ga, be);
+        return z != z ? z : fminf(fmaxf(z, lo), hi);
+    };
     bn_walk<VEC>(N, C, HW, chunk, s, c, [&](long o) {
         if (VEC) {
             f32x4_t v = *reinterpret_cast<const f32x4_t*>(x + o);

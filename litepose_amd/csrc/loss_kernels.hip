@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const double* __restri
                     row += exp(-(d * d));
                 } else {
                     const double t = 1.0 - fabs(d);
-                    row += t > 0.0 ? t : 0.0;
+                    row += t < 0.0 ? 0.0 : t;                // a NaN gap stays in the sum, as torch.clamp(min=0) keeps it
                 }
             }
         }

@@ -53,6 +53,12 @@ __device__ __forceinline__ int xcd_contiguous_id(int id, int n) {
     return xcd * q + min(xcd, r) + slot;
 }
 
+// The bounds of ACT_NONE in the branch-free clamp fminf(fmaxf(v, lo), hi) of the planar 1x1 and depthwise launchers the
+// training layers call.  fmaxf / fminf are IEEE maxNum / minNum: they return the operand that is not a NaN, and a NaN only
+// when both are.  Against a NaN bound every v comes back as itself, a NaN v included; against -inf / +inf a NaN sum would
+// leave the layer as -inf, and a diverged training run would look finite.  The same instructions, another constant.
+#define ACT_NONE_BOUND __builtin_nanf("")
+
 __device__ __forceinline__ float apply_act(float v, int act) {
     if (act == ACT_RELU) return fmaxf(v, 0.f);
     if (act == ACT_RELU6) return fminf(fmaxf(v, 0.f), 6.f);
@@ -206,8 +212,8 @@ __global__ __launch_bounds__(256) void dw_kernel(const float* __restrict__ in,
     constexpr int QPR = G::QPR;                       // float4 staged per row
     constexpr int NQ = G::IH * QPR;                   // float4 per tile
     constexpr int NLD = (NQ + 63) / 64;               // float4 per lane
-    const float lo = act == ACT_NONE ? -INFINITY : 0.f;
-    const float hi = act == ACT_RELU6 ? 6.f : INFINITY;
+    const float lo = act == ACT_NONE ? ACT_NONE_BOUND : 0.f;
+    const float hi = act == ACT_RELU6 ? 6.f : (act == ACT_NONE ? ACT_NONE_BOUND : INFINITY);
     const int row = lane >> 2, strip = lane & 3;
 
     f32x4 pre[NLD];
@@ -438,8 +444,8 @@ __global__ __launch_bounds__(256) void dw_pair_kernel(const float* __restrict__ 
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-    const float lo = act == ACT_NONE ? -INFINITY : 0.f;
-    const float hi = act == ACT_RELU6 ? 6.f : INFINITY;
+    const float lo = act == ACT_NONE ? ACT_NONE_BOUND : 0.f;
+    const float hi = act == ACT_RELU6 ? 6.f : (act == ACT_NONE ? ACT_NONE_BOUND : INFINITY);
     // quad -> tile row: lane groups of ds_read_b128 then cover rows {0,1,8,9},{2,3,10,11},...
     const int row = (int)((0xFDCE5764B98A1320ull >> (4 * (lane >> 2))) & 15);
     const int strip = lane & 3;
@@ -538,8 +544,8 @@ __global__ __launch_bounds__(256) void dw_pair16_kernel(const float* __restrict_
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-    const float lo = act == ACT_NONE ? -INFINITY : 0.f;
-    const float hi = act == ACT_RELU6 ? 6.f : INFINITY;
+    const float lo = act == ACT_NONE ? ACT_NONE_BOUND : 0.f;
+    const float hi = act == ACT_RELU6 ? 6.f : (act == ACT_NONE ? ACT_NONE_BOUND : INFINITY);
     const int row = (int)((0xFDCE5764B98A1320ull >> (4 * (lane >> 2))) & 15);
     const int strip = lane & 3;
     const f32x2* wc2 = reinterpret_cast<const f32x2*>(wdup) + (long)c * K * K;
@@ -757,8 +763,8 @@ __global__ __launch_bounds__(256) void pw2_kernel(const float* __restrict__ inA,
     }
     if (!valid) return;
     // branch-free activation: clamp to [lo, hi]
-    const float lo = act == ACT_NONE ? -INFINITY : 0.f;
-    const float hi = act == ACT_RELU6 ? 6.f : INFINITY;
+    const float lo = act == ACT_NONE ? ACT_NONE_BOUND : 0.f;
+    const float hi = act == ACT_RELU6 ? 6.f : (act == ACT_NONE ? ACT_NONE_BOUND : INFINITY);
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
         const int cob = (cb0 + i) * 32 + 4 * half;

@@ -169,6 +169,9 @@ int lp_net_set_streams(lp_net* net, int k);
  *   "mbt"        tiled fused blocks: 0 off, 1 default (32-filter blocks + stride-2 blocks), 2 also the 16-filter
  *                blocks, 3 only the stride-2 blocks
  *   "mbt_s2"     stride-2 fused blocks (default 1)
+ *   "mbt_strip"  fp32: the stride-1 tiled blocks on planes 32 wide as 32-wide x 16-row strips, one workgroup per strip, bit-identical
+ *                to the 16x16 tiles (round 7; 0 off, 1 default: when images x ceil(H / 16) strips are at least one per CU of the
+ *                device, 2 always)
  *   "mbconv2"    16-filter blocks in mbconv2_kernel (default 1; 0: the unfused pw / dw_pair / pw chain)
  *   "mbtb"       bf16 storage: whole-block kernels (default 1; 0: one launch per op, what the per-launch parity tests run)
  *   "mbtb_s2"    bf16 storage: stride-2 whole-block kernel (default 1)

@@ -65,6 +65,7 @@ struct lp_net : lp_plan::Net {           // arch, tensors, storage and the plan:
     int opt_mb16_min = 48;                 // ... only for launches of at least this many images (one workgroup per image:
                                            //     a small batch leaves the chip empty; below it the pw3 / dw_pair16 / pw3 chain)
     int opt_mbt = 1, opt_mbt_s2 = 1;       // tiled fused blocks (mbtile_kernels.hip: launch_mbt)
+    int opt_mbt_strip = 1;                 // ... 32-wide planes as 32 x 16 strips (0 off, 1 when the strips fill the CUs, 2 always)
     int opt_mbconv2 = 1;                   // 16-filter blocks in mbconv2_kernel (0: the unfused chain)
     int opt_mbtb = 1, opt_mbtb_s2 = 1;     // bf16 storage: whole-block kernels
     int opt_pw3d = 1;                      // fp32: small launches of the bf16x3 1x1 take the deep-prefetch form (0 off, 2 always)
@@ -447,7 +448,8 @@ int rule_mbt(const Part& c, size_t i) {
     const float *Wt = c.Wt, *res = d.res >= 0 ? c.f(d.res) : nullptr;
     return ((o.ws_off && d.ws_off && d.wrow_off &&
              lp::launch_mbt(c.f(o.inA), Wt + o.ws_off, Wt + o.b_off, Wt + d.wrow_off, Wt + d.ws_off, Wt + d.b2_off, res,
-                            c.f(d.out), c.NB, o.Ca, o.Cout, d.Cout, pl.ih, pl.iw, d.K, d.S, c.s, n->opt_mbt, n->opt_mbt_s2)) ||
+                            c.f(d.out), c.NB, o.Ca, o.Cout, d.Cout, pl.ih, pl.iw, d.K, d.S, c.s, n->opt_mbt, n->opt_mbt_s2,
+                            n->opt_mbt_strip)) ||
             lp::launch_mbconv(c.f(o.inA), Wt + o.w_off, Wt + o.b_off, Wt + d.w_off, Wt + d.b_off, Wt + d.w2_off,
                               Wt + d.b2_off, res, c.f(d.out), c.NB, o.Ca, o.Cout, d.Cout, pl.ih, pl.iw, d.K, d.S, c.s,
                               d.wpair_off ? Wt + d.wpair_off : nullptr, o.ws_off ? Wt + o.ws_off : nullptr,
@@ -1006,6 +1008,7 @@ const std::vector<OptEntry>& lp_net::options() {
         {"mb16_min", 0, 65536, &lp_net::opt_mb16_min},
         {"mbt", 0, 3, &lp_net::opt_mbt},
         {"mbt_s2", 0, 1, &lp_net::opt_mbt_s2},
+        {"mbt_strip", 0, 2, &lp_net::opt_mbt_strip},
         {"mbconv2", 0, 1, &lp_net::opt_mbconv2},
         {"mbtb", 0, 1, &lp_net::opt_mbtb},
         {"mbtb_s2", 0, 1, &lp_net::opt_mbtb_s2},

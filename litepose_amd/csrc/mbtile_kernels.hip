@@ -22,6 +22,8 @@
 //     per workgroup by LDS-DMA, exactly as in mb16_kernel (same packed arrays: pack_pw's bf16x3 split, wrow)
 // Arithmetic: expand and depthwise are mbconv2_kernel's / mb16_kernel's bit for bit; the project sums the six
 // bf16x3 products per 16 channels in mb16_kernel's order (fp32-equivalent: dropped terms <= 3 * 2^-24).
+// Round 7: planes 32 wide run as 32-wide x 16-row strips (the overload mbt_kernel<CK, NMT, RES, 16> below, option
+// "mbt_strip"), bit-identical to the tiles.
 #include "kernels.h"
 #include "dw7.h"
 #include "split3.h"
@@ -275,6 +277,291 @@ __global__ __launch_bounds__(512, 2) void mbt_kernel(
                 for (int e = 0; e < 4; ++e) {
                     const int co = mt * 32 + 4 * half + e + 8 * q;
                     float v = acc[mt][4 * q + e] + bq[e];
+                    if (RES) v += rb[(long)co * HW];
+                    ob[(long)co * HW] = v;
+                }
+            }
+        }
+    }
+}
+
+// =====================================================================================
+// Strip form (round 7), planes with W == 32: one 8-wave workgroup owns a 32-wide x 16-row OUTPUT STRIP of an image
+// (overload mbt_kernel<CK, NMT, RES, 16>; launch_mbt takes it by option "mbt_strip").  On a 32 x 32 plane every 16 x 16
+// tile is a corner tile: 484 halo cells = 16 MFMA column groups per tile and chunk, of which 361 cells lie inside the
+// image.  A strip's halo is 22 rows of 32 in-image columns; the frame columns (-3..-1, 32..34) are never inside:
+//   * E tile [16 pairs][22 rows][42 cells][2 ch] (column c at cell c + 4; 21 sixteen-byte slots per row, 463 per pair),
+//     zeroed ONCE; the expand writes cells 4..35 of the rows inside the image and nothing else, the depthwise writes its
+//     result over cells 4..35 of the output rows inside the image: the frame and the rows outside stay zero for all chunks
+//   * expand: one column group = one halo ROW (32 cells).  Wave w expands tile rows 2w+3, 2w+4 (its own two project
+//     rows) and at most one of the six outer rows 0,1,2 / 19,20,21 (waves 0,1,2 / 7,4,5: the three rows a border strip
+//     has lie on three SIMDs); rows outside the image are skipped wave-uniformly: 19 + 19 groups per 32 x 32 image and
+//     chunk instead of 64, x fragments in 3 x CK x 12 registers, loaded as full 128-byte rows
+//   * depthwise: dw7_s1_2x4 with the 84-float row stride, two passes per wave (output rows 0-7, then 8-15).  In a pass
+//     lanes 0-31 / 32-63 hold row pairs {0,1} / {2,3} of BOTH channel pairs of the wave; the four 8-lane sets that a
+//     ds_read_b128 services together are (pair, row pair) x 8 strips, the two sets of a group from different pairs: the
+//     odd pair stride is what reaches the odd slots (one pair per pass, 8 row pairs x 8 strips, has every slot even and
+//     conflicts 4-way; tools/lds_model.py mbt_strip).  Pass 1 reads rows pass 0 writes, so both results are kept in
+//     registers and written after pass 1's reads (one wave, in-order LDS queue)
+//   * project / epilogue: wave w = output rows 2w, 2w+1 = two column groups of 32 pixels, acc[NMT][2]; stores and
+//     residual reads are full 128-byte rows
+// TWO barriers per chunk.  Who touches a cell of the E tile between which barriers (chunk c; B1 ends the expand, B2 the
+// depthwise):
+//     B2(c-1) .. B1(c)   project(c-1): wave w READS cells 4..35 of tile rows 2w+3, 2w+4, every pair
+//                        expand(c):    wave w WRITES cells 4..35 of tile rows 2w+3, 2w+4 and of its outer row, every pair
+//                        -> a wave writes only rows that it alone read since B2(c-1) (in order, after its own reads); the
+//                           outer rows are read by no project.  The tile form needed a third barrier here because its
+//                           cell groups were arbitrary halo cells that other waves' projects read
+//     B1(c) .. B2(c)     depthwise(c): wave w READS every row of pairs 2w, 2w+1 and WRITES rows 3..18 of the same two pairs
+//     weights: the stage of chunk c (expand slice / bias / filter rows of c+1, project slice of c) is requested after
+//     B1(c), when every wave is past expand(c) and project(c-1), and has landed at B2(c), before project(c) / expand(c+1)
+// Arithmetic: per output the tile form's, instruction for instruction (same six-product order per k-step, chunk order,
+// tap order, zero padding of the expanded tensor): bit-identical results.
+// =====================================================================================
+constexpr int MS_RS = 42;                                 // cells per strip row: column c at cell c + 4
+constexpr int MS_PAIR = 22 * MS_RS * 2 + 4;               // floats per channel pair: 463 sixteen-byte slots (odd)
+constexpr int MS_E_FLOATS = 16 * MS_PAIR;
+
+template <int CK, int NMT> struct MSW : MTW<CK, NMT> {
+    static constexpr size_t LDS_BYTES = (size_t)MS_E_FLOATS * 4 + (size_t)(MTW<CK, NMT>::NTOT + MTW<CK, NMT>::N4) * 16;
+};
+
+template <int CK, int NMT, bool RES, int ROWS>
+__global__ __launch_bounds__(512, 2) void mbt_kernel(
+    const float* __restrict__ x,        // [N, Cin, H, 32]
+    const u32x4* __restrict__ w1s, const float* __restrict__ b1f, const f32x4* __restrict__ wrow,
+    const u32x4* __restrict__ w2s, const float* __restrict__ b2f,    // as the tile form
+    float* __restrict__ out,            // [N, Cout, H, 32]
+    int Cexp, int Cout, int H, int stripsY, int xcd_remap) {
+    static_assert(ROWS == 16, "a strip is 16 output rows");
+    extern __shared__ __attribute__((aligned(16))) float E[];
+    LP_OWN_CU();                                                      // kernels.h
+    constexpr int Cin = CK * 16, W = 32;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int half = lane >> 5, pl = lane & 31;
+    const int unit = xcd_remap ? mt_xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int n = unit / stripsY;
+    const int y0 = (unit - n * stripsY) * 16;
+    const long HW = (long)H * W;
+    const int nchunks = Cexp >> 5, KS2 = Cexp >> 4;
+    using WG = MSW<CK, NMT>;
+    u32x4* W1 = reinterpret_cast<u32x4*>(E + MS_E_FLOATS);            // [CK][3][64]
+    u32x4* W2 = W1 + WG::N1;                                          // [NMT][2][3][64]
+    u32x4* WD = W2 + WG::N2 + WG::N3;                                 // [2 chunk parities][16 pairs][28]
+
+    // weight staging: the tile form's, element for element
+    u32x4 stg[WG::NLD];
+    auto stage_addr = [&](int c, int j, const u32x4*& src, u32x4*& dst) -> bool {
+        const int e0 = 64 * wave + 512 * j;
+        if (e0 >= WG::NTOT) return false;
+        const int ca = max(c, 0), cb = min(c + 1, nchunks - 1), dpar = (c + 1) & 1;
+        dst = W1 + e0;
+        if (e0 < WG::N1) src = w1s + (long)cb * WG::N1 + e0 + lane;
+        else if (e0 < WG::N1 + WG::N2) {
+            const int f0 = e0 - WG::N1, seg = f0 / 192, within = f0 - seg * 192;
+            src = w2s + ((long)(seg >> 1) * KS2 + 2 * ca + (seg & 1)) * 192 + within + lane;
+        } else if (e0 < WG::N1 + WG::N2 + WG::N3) {
+            src = reinterpret_cast<const u32x4*>(b1f) + (long)cb * 8 + min(lane, 7);
+        } else {
+            src = reinterpret_cast<const u32x4*>(wrow) + (long)cb * WG::N4 + (e0 - WG::N1 - WG::N2 - WG::N3) + lane;
+            dst += dpar * WG::N4;
+        }
+        return true;
+    };
+    auto stage_load = [&](int c) {
+#pragma unroll
+        for (int j = 0; j < WG::NLD; ++j) {
+            const u32x4* src;
+            u32x4* dst;
+            if (stage_addr(c, j, src, dst)) LP_STAGE_LOAD(stg[j], src, dst);
+        }
+    };
+    auto stage_store = [&](int c) {
+#pragma unroll
+        for (int j = 0; j < WG::NLD; ++j) {
+            const u32x4* src;
+            u32x4* dst;
+            if (stage_addr(c, j, src, dst)) LP_STAGE_STORE(stg[j], dst, lane);
+        }
+        LP_STAGE_DRAIN();
+    };
+    stage_load(-1);
+
+    // the E tile is zeroed once: frame columns, pads and the rows outside the image are never written again
+    {
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        for (int i = threadIdx.x; i < MS_E_FLOATS / 4; i += 512) reinterpret_cast<f32x4*>(E)[i] = z;
+    }
+
+    // ---- this wave's halo rows as bf16x3 B fragments, split ONCE per strip: tile rows 2w+3, 2w+4 and one outer row;
+    //      channels 16ks + 8*half + 0..7 of column pl.  gok: the row exists and lies inside the image (wave-uniform)
+    u32x4 xh[3][CK], xm[3][CK], xl[3][CK];
+    int trow[3];
+    bool gok[3];
+    trow[0] = 2 * wave + 3;
+    trow[1] = 2 * wave + 4;
+    trow[2] = wave < 3 ? wave : wave == 7 ? 19 : wave == 4 ? 20 : wave == 5 ? 21 : -1;
+#pragma unroll
+    for (int gi = 0; gi < 3; ++gi) {
+        const int yy = y0 - 3 + trow[gi];
+        gok[gi] = trow[gi] >= 0 && yy >= 0 && yy < H;
+#pragma unroll
+        for (int ks = 0; ks < CK; ++ks) xh[gi][ks] = xm[gi][ks] = xl[gi][ks] = u32x4{0u, 0u, 0u, 0u};
+        if (gok[gi]) {
+            const float* sp = x + ((long)n * Cin + 8 * half) * HW + (long)yy * W + pl;
+#pragma unroll
+            for (int ks = 0; ks < CK; ++ks) {
+                float v[8];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) v[c] = sp[(long)(ks * 16 + c) * HW];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const Split3 p3 = split3_pair(v[2 * j], v[2 * j + 1]);
+                    xh[gi][ks][j] = p3.h; xm[gi][ks][j] = p3.m; xl[gi][ks][j] = p3.l;
+                }
+            }
+        }
+    }
+    f32x16 acc[NMT][2];
+#pragma unroll
+    for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mt][g][r] = 0.f;
+
+    // depthwise geometry (tools/lds_model.py mbt_strip_lane): 8-lane set -> (pair of the wave, row pair of the pass)
+    const int dq = pl >> 2;
+    const int dwpair = (0x66 >> dq) & 1;
+    const int dwrp = ((0x96 >> dq) & 1) + 2 * half;                  // + 4 in the second pass
+    const int strip = (lane & 3) + 4 * ((dq >> 1) & 1);
+    const int dwoff = (2 * dwrp * MS_RS + strip * 4) * 2;            // first cell this lane reads (tile row 2rp)
+    const int dwout = ((2 * dwrp + 3) * MS_RS + 4 + strip * 4) * 2;  // its 2 x 4 output cells (second row: + MS_RS*2)
+    constexpr int PASS = 8 * MS_RS * 2;                              // floats between the passes' rows
+    // project geometry: this lane's MFMA column = output pixel (row 2w + g, column pl), g = 0, 1
+    const int pcell = ((2 * wave + 3) * MS_RS + pl + 4) * 2;
+
+    stage_store(-1);
+    __syncthreads();                                                 // the first stage has landed, the tile is zero
+    for (int ch = 0; ch < nchunks; ++ch) {
+        // ================= expand: E = relu6(W1[chunk] . x + b1) on this wave's rows inside the image ========
+        {
+            u32x4 a[CK][3];
+#pragma unroll
+            for (int ks = 0; ks < CK; ++ks)
+#pragma unroll
+                for (int t = 0; t < 3; ++t) a[ks][t] = W1[(ks * 3 + t) * 64 + lane];
+            const f32x4* bp = reinterpret_cast<const f32x4*>(W2 + WG::N2) + half * 4;
+            f32x4 bq[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) bq[q] = bp[q];
+#pragma unroll
+            for (int gi = 0; gi < 3; ++gi) {
+                if (!gok[gi]) continue;                              // wave-uniform
+                f32x16 d;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) d[r] = 0.f;
+#pragma unroll
+                for (int ks = 0; ks < CK; ++ks) d = mma6(a[ks], xh[gi][ks], xm[gi][ks], xl[gi][ks], d);
+                float* ec = E + (trow[gi] * MS_RS + pl + 4) * 2;
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; e += 2) {                 // registers 4q+e, 4q+e+1 = channels cc, cc+1
+                        const int cc = 4 * half + e + 8 * q;
+                        const float v0 = fminf(fmaxf(d[4 * q + e] + bq[q][e], 0.f), 6.f);
+                        const float v1 = fminf(fmaxf(d[4 * q + e + 1] + bq[q][e + 1], 0.f), 6.f);
+                        *reinterpret_cast<f32x2*>(ec + (cc >> 1) * MS_PAIR) = f32x2{v0, v1};
+                    }
+            }
+        }
+        __syncthreads();                                             // B1
+        stage_load(ch);
+        // ================= depthwise 7x7 + bias + relu6, in place: pairs 2w, 2w+1, two passes of 8 output rows ======
+        {
+            const int kp = wave * 2 + dwpair;
+            const f32x4* wl = reinterpret_cast<const f32x4*>(WD + (ch & 1) * WG::N4) + kp * 28;
+            float* ep = E + kp * MS_PAIR;
+            const f32x4 wbias = wl[3];                               // the pair's bias rides in the pad of filter row 0
+            const float b0 = wbias[2], b1 = wbias[3];
+            f32x4 o[2][4];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                f32x2 a0[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};   // output row 2rp
+                f32x2 a1[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};   // output row 2rp + 1
+                dw7_s1_2x4<MS_RS * 2>(ep + dwoff + p * PASS, wl, a0, a1);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    o[p][i >> 1][2 * (i & 1)] = fminf(fmaxf(a0[i][0] + b0, 0.f), 6.f);
+                    o[p][i >> 1][2 * (i & 1) + 1] = fminf(fmaxf(a0[i][1] + b1, 0.f), 6.f);
+                    o[p][2 + (i >> 1)][2 * (i & 1)] = fminf(fmaxf(a1[i][0] + b0, 0.f), 6.f);
+                    o[p][2 + (i >> 1)][2 * (i & 1) + 1] = fminf(fmaxf(a1[i][1] + b1, 0.f), 6.f);
+                }
+                // a pass's results exist before the next pass requests its rows: nothing else orders the FMAs, which are
+                // not memory operations, against the pinned requests of the second call (they sank below all 96, and spilled)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(o[p][k]) : : "memory");
+            }
+            // every lane's reads of both passes precede these writes (one wave, in-order LDS queue); a pair is read and
+            // written by this wave only.  Rows below the image keep their zeros -- by a select, not a branch: with the
+            // stores under a condition hipcc sinks the FMAs of both passes into it, below all 96 row reads, and spills
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const int oy = y0 + 2 * (dwrp + 4 * p);
+                float* op = ep + dwout + p * PASS;
+                *reinterpret_cast<f32x4*>(op) = oy < H ? o[p][0] : z;
+                *reinterpret_cast<f32x4*>(op + 4) = oy < H ? o[p][1] : z;
+                *reinterpret_cast<f32x4*>(op + MS_RS * 2) = oy + 1 < H ? o[p][2] : z;
+                *reinterpret_cast<f32x4*>(op + MS_RS * 2 + 4) = oy + 1 < H ? o[p][3] : z;
+            }
+        }
+        stage_store(ch);
+        __syncthreads();                                             // B2
+        // ================= project: acc += W2[:, chunk] . D[chunk][this wave's two rows] ================
+#pragma unroll
+        for (int ks2 = 0; ks2 < 2; ++ks2) {
+            u32x4 fh[2], fm[2], fl[2];
+#pragma unroll
+            for (int g = 0; g < 2; ++g)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const f32x2 v = *reinterpret_cast<const f32x2*>(E + (8 * ks2 + 4 * half + j) * MS_PAIR + pcell +
+                                                                    g * MS_RS * 2);
+                    const Split3 p3 = split3_pair(v[0], v[1]);
+                    fh[g][j] = p3.h; fm[g][j] = p3.m; fl[g][j] = p3.l;
+                }
+#pragma unroll
+            for (int mt = 0; mt < NMT; ++mt) {
+                const u32x4* wl = W2 + (mt * 2 + ks2) * 3 * 64 + lane;
+                u32x4 a[3];
+#pragma unroll
+                for (int t = 0; t < 3; ++t) a[t] = wl[t * 64];
+#pragma unroll
+                for (int g = 0; g < 2; ++g) acc[mt][g] = mma6(a, fh[g], fm[g], fl[g], acc[mt][g]);
+            }
+        }
+    }
+    // ================= epilogue: + bias (+ x), one 128-byte row per 32 lanes ==========================
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const int oy = y0 + 2 * wave + g;
+        if (oy >= H) continue;                                       // wave-uniform
+        const long o = (long)oy * W + pl;
+        float* ob = out + (long)n * Cout * HW + o;
+        const float* rb = x + (long)n * Cin * HW + o;                // RES: Cin == Cout
+#pragma unroll
+        for (int mt = 0; mt < NMT; ++mt) {
+            const f32x4* bp = reinterpret_cast<const f32x4*>(b2f + (mt * 2 + half) * 16);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (mt * 32 + 8 * q >= Cout) break;                  // wave-uniform: Cout is a multiple of 8
+                const f32x4 bq = bp[q];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int co = mt * 32 + 4 * half + e + 8 * q;
+                    float v = acc[mt][g][4 * q + e] + bq[e];
                     if (RES) v += rb[(long)co * HW];
                     ob[(long)co * HW] = v;
                 }
@@ -601,9 +888,45 @@ static void launch_mbt_t(const float* x, const void* w1s, const float* b1f, cons
                            (const f32x4*)wrow, (const u32x4*)w2s, b2f, out, Cexp, Cout, H, W, tilesX, tilesY, xcd);
 }
 
+template <int CK, int NMT>
+static void launch_mbt_strip_t(const float* x, const void* w1s, const float* b1f, const void* wrow, const void* w2s,
+                               const float* b2f, bool res, float* out, int N, int Cexp, int Cout, int H, int xcd,
+                               hipStream_t s) {
+    const size_t lds = MSW<CK, NMT>::LDS_BYTES;
+    static_assert(MSW<CK, NMT>::LDS_BYTES <= 160 * 1024, "the strip form's E tile and weight stage must fit the CU's LDS");
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mbt_kernel<CK, NMT, true, 16>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mbt_kernel<CK, NMT, false, 16>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr = true;
+    }
+    const int stripsY = (H + 15) / 16;
+    const dim3 grid(N * stripsY);
+    if (res)
+        LP_LAUNCH((mbt_kernel<CK, NMT, true, 16>), grid, dim3(512), lds, s, x, (const u32x4*)w1s, b1f,
+                           (const f32x4*)wrow, (const u32x4*)w2s, b2f, out, Cexp, Cout, H, stripsY, xcd);
+    else
+        LP_LAUNCH((mbt_kernel<CK, NMT, false, 16>), grid, dim3(512), lds, s, x, (const u32x4*)w1s, b1f,
+                           (const f32x4*)wrow, (const u32x4*)w2s, b2f, out, Cexp, Cout, H, stripsY, xcd);
+}
+
+// CUs of the current device: the default rule of option "mbt_strip" takes strips when they fill the chip in one round
+static int device_cu_count() {
+    static const int cus = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+            return 1 << 30;                                          // unknown: keep the tiles
+        return v;
+    }();
+    return cus;
+}
+
 bool launch_mbt(const float* x, const void* w1s, const float* b1f, const void* wrow, const void* w2s,
                 const float* b2f, const float* res, float* out, int N, int Cin, int Cexp, int Cout, int H, int W,
-                int K, int S, hipStream_t s, int mode, int mode_s2) {
+                int K, int S, hipStream_t s, int mode, int mode_s2, int mode_strip) {
     // mode = option "mbt" (the parity tests compare the paths): 0 = off (mbconv2_kernel / the unfused chain),
     // 1 (default) = the 32-filter blocks and up, 2 = also the 16-filter blocks (mbconv2_kernel's), 3 = only the
     // stride-2 blocks (mbt_s2_kernel; mode_s2 = option "mbt_s2" = 0 switches those off separately)
@@ -644,6 +967,23 @@ bool launch_mbt(const float* x, const void* w1s, const float* b1f, const void* w
         launch_mbt_t<CKV, NMTV>(x, w1s, b1f, wrow, w2s, b2f, res != nullptr, out, N, Cexp, Cout, H, W,     \
                                 xcd, s);                                                                   \
         return true;                                                                                       \
+    }
+    // mode_strip = option "mbt_strip": planes with W == 32 as 32 x 16 strips (mbt_kernel<CK, NMT, RES, 16>, bit-identical):
+    // 0 = never, 1 (default) = when the N * ceil(H / 16) strips are at least one per CU -- a smaller launch fills more CUs
+    // as twice as many tiles --, 2 = always.  A shape whose variant is not built keeps the tiles
+    if (W == 32 && mode_strip && (mode_strip == 2 || (long)N * ((H + 15) / 16) >= device_cu_count())) {
+#define LP_GOS(CKV, NMTV)                                                                                  \
+        if (ck == CKV && nmt == NMTV &&                                                                    \
+            !uses_scratch(res ? (const void*)mbt_kernel<CKV, NMTV, true, 16>                               \
+                              : (const void*)mbt_kernel<CKV, NMTV, false, 16>)) {                          \
+            launch_mbt_strip_t<CKV, NMTV>(x, w1s, b1f, wrow, w2s, b2f, res != nullptr, out, N, Cexp, Cout, H, xcd, s); \
+            return true;                                                                                   \
+        }
+        // built where the form fits the 256-register budget: 16- and 32-channel blocks of up to 32 filters (<2, 1> is
+        // the headline's stage 1).  <2, 2> needs 76 bytes of scratch per lane and CK = 3 holds 108 registers of x
+        // fragments: those shapes keep the tiles
+        LP_GOS(1, 1) LP_GOS(2, 1)
+#undef LP_GOS
     }
     LP_GO(1, 1) LP_GO(2, 1) LP_GO(2, 2) LP_GO(3, 1) LP_GO(3, 2)
 #undef LP_GO

@@ -115,6 +115,75 @@ def mbt():
     return {'depthwise rows as 48 ds_read_b128': total(ins)}
 
 
+# ------------------------------------------------------------------------------------------ mbt_kernel, strip form
+def mbt_strip_lane(lane):
+    """(pair of the wave, row pair of the pass, strip) of a depthwise lane of the strip form: the four 8-lane sets a
+    ds_read_b128 services together -- {0-3, 12-15} with {20-27}, {4-11} with {16-19, 28-31} -- are one channel pair, one
+    row pair and its eight 4-column strips each, and the two sets of a group belong to DIFFERENT pairs: the pair stride is
+    an odd slot count, row pairs and strips are even ones, so only the pair bit reaches the odd slots."""
+    dq = (lane & 31) >> 2
+    pair = (0x66 >> dq) & 1
+    rp = ((0x96 >> dq) & 1) + 2 * (lane >> 5)
+    strip = (lane & 3) + 4 * ((dq >> 1) & 1)
+    return pair, rp, strip
+
+
+def mbt_strip():
+    RS = 42                              # cells per row: column c at cell c + 4, 21 sixteen-byte slots
+    PAIR = 22 * RS * 2 + 4               # floats per channel pair: 463 slots (odd)
+    out = {}
+    ins = []
+    for p in range(2):                   # pass p: row pairs 4p .. 4p + 3 of both pairs of the wave
+        for R in range(8):
+            for q in range(6):
+                ad = []
+                for lane in range(64):
+                    pair, rp, strip = mbt_strip_lane(lane)
+                    ad.append((pair * PAIR + ((2 * (rp + 4 * p) + R) * RS + strip * 4) * 2 + 4 * q) * 4)
+                ins.append((ad, 16, groups_b128(), 64))
+    out['depthwise rows of both passes as 96 ds_read_b128'] = total(ins)
+    ins = []
+    for p in range(2):                   # the layout NOT built: a pass = one pair, lane = 8 row pairs x 8 strips
+        for R in range(8):
+            for q in range(6):
+                ad = [(p * PAIR + ((2 * (lane >> 3) + R) * RS + (lane & 7) * 4) * 2 + 4 * q) * 4 for lane in range(64)]
+                ins.append((ad, 16, groups_b128(), 64))
+    out['the same with one pair per pass (every slot even: not built)'] = total(ins)
+    ins = []
+    for p in range(2):
+        for k in range(4):
+            ad = []
+            for lane in range(64):
+                pair, rp, strip = mbt_strip_lane(lane)
+                cell = ((2 * (rp + 4 * p) + 3) * RS + 4 + strip * 4) * 2
+                ad.append((pair * PAIR + cell + [0, 4, RS * 2, RS * 2 + 4][k]) * 4)
+            ins.append((ad, 16, G8, 32))
+    out['depthwise result, 8 ds_write_b128'] = total(ins)
+    ins = []
+    for wave in range(8):
+        for ks2 in range(2):
+            for g in range(2):
+                for j in range(4):
+                    ad = []
+                    for lane in range(64):
+                        half, pl = lane >> 5, lane & 31
+                        cell = ((2 * wave + 3 + g) * RS + pl + 4) * 2
+                        ad.append(((8 * ks2 + 4 * half + j) * PAIR + cell) * 4)
+                    ins.append((ad, 8, G32, 64))
+    out['project operands of the 8 waves, 128 ds_read_b64'] = total(ins)
+    ins = []
+    for row in (0, 7, 21):               # any row: the lanes of a half write 32 consecutive cells of one pair
+        for k in range(8):               # registers (4q + e, 4q + e + 1), q < 4, e in (0, 2)
+            ad = []
+            for lane in range(64):
+                half, pl = lane >> 5, lane & 31
+                cc = 4 * half + 2 * (k & 1) + 8 * (k >> 1)
+                ad.append(((cc >> 1) * PAIR + (row * RS + pl + 4) * 2) * 4)
+            ins.append((ad, 8, G16, 32))
+    out['expand result of three rows, 24 ds_write_b64'] = total(ins)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ mbt_s2_kernel
 def mbt_s2():
     RS, ODD = 44, 22
@@ -205,7 +274,8 @@ def deconv4x3():
 
 
 if __name__ == '__main__':
-    for name, fn in (('mb16_kernel', mb16), ('mbt_kernel', mbt), ('mbt_s2_kernel', mbt_s2), ('mbtb_kernel', mbtb),
+    for name, fn in (('mb16_kernel', mb16), ('mbt_kernel', mbt), ('mbt_kernel, 32-wide strip form', mbt_strip),
+                     ('mbt_s2_kernel', mbt_s2), ('mbtb_kernel', mbtb),
                      ('deconv4x3_kernel', deconv4x3)):
         print(name)
         for k, (c, base) in fn().items():

@@ -799,6 +799,26 @@ int lp_bn_backward(const float* d_grad_y, const float* d_x, const float* d_gamma
  * which form a shape runs.                                                                                              */
 int lp_pw_tile_choice(int N, int Ca, int Cb, int Cout, int HW, int has_res);
 #define LP_PW_WGRAD_SLICE 1024
+
+/* lp_mbt_form: host arithmetic only (no launch; no device unless cus <= 0): the form in which the fp32 network runs a whole
+ * InvBottleneck of Cin -> Cexp -> Cout channels, depthwise K x K at stride S, on N planes of H x W (for a net: N = images
+ * of the launch, twice that under flip = 2), as the fused tiled kernels would take it.  has_res: the block adds its input.
+ * mode, mode_s2, mode_strip: the values of the lp_net_set_option switches "mbt", "mbt_s2", "mbt_strip" (defaults 1, 1, 1).
+ * cus: the CU count that the default rule of "mbt_strip" = 1 compares N * ceil(H / 16) with; <= 0 asks the current
+ * device (without one the rule keeps the tiles).  Returns LP_MBT_NONE (0: another kernel or the unfused chain runs the
+ * block), or  form + 16 CK + 256 NMT + 4096 RES  with form = LP_MBT_TILE (mbt_kernel on 16 x 16 output tiles, grid
+ * N ceil(W / 16) ceil(H / 16)), LP_MBT_STRIP (mbt_kernel on 32-wide x 16-row strips, W == 32, grid N ceil(H / 16)) or
+ * LP_MBT_S2 (mbt_s2_kernel, 16 x 8 output tiles); CK = Cin / 16 (1..3), NMT = ceil(Cout / 32) (1..2), RES = has_res:
+ * the template arguments of the kernel body.  This is the form BEFORE the launcher's check that the built kernel needs no
+ * scratch memory, which needs a device: a strip kernel that fails it runs as the tile form of the same CK, NMT and RES, a
+ * tile or stride-2 kernel that fails it is not taken at all.  LP_ERR_INVALID_ARG for a non-positive size.  For tests and
+ * tools that must know which form a shape runs.                                                                         */
+#define LP_MBT_NONE 0
+#define LP_MBT_TILE 1
+#define LP_MBT_STRIP 2
+#define LP_MBT_S2 3
+int lp_mbt_form(int N, int Cin, int Cexp, int Cout, int H, int W, int K, int S, int has_res, int mode, int mode_s2,
+                int mode_strip, int cus);
 size_t lp_pw_forward_workspace_bytes(int Cin, int Cout);
 int lp_pw_forward(const float* d_x, const float* d_w, float* y_out, int N, int Cin, int Cout, int HW, void* workspace,
                   size_t workspace_bytes, void* stream);

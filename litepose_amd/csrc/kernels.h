@@ -144,6 +144,16 @@ bool launch_mb16(const float* x, const Mb16Run& run, bool res, int N, int Cin, i
 bool launch_mbt(const float* x, const void* w1s, const float* b1f, const void* wrow, const void* w2s,
                 const float* b2f, const float* res, float* out, int N, int Cin, int Cexp, int Cout, int H, int W,
                 int K, int S, hipStream_t s, int mode = 1, int mode_s2 = 1, int mode_strip = 1);
+// Host arithmetic only: launch_mbt's one source of the form, and what lp_mbt_form reports.  kind: the kernel body
+// (MBT_TILE = mbt_kernel<CK, NMT, RES>, MBT_STRIP = mbt_kernel<CK, NMT, RES, 16>, MBT_S2 = mbt_s2_kernel<CK, NMT>), or
+// MBT_NONE: launch_mbt returns false.  has_res: the block adds its input (launch_mbt: res == x).  cus: the CU count the
+// default rule of mode_strip = 1 compares with; <= 0 asks the device.  The form is the one BEFORE the uses_scratch checks,
+// which need a device: launch_mbt turns a strip whose kernel needs scratch into the tile of the same CK, NMT, RES, and
+// refuses a tile or an s2 form that does.
+enum MbtKind { MBT_NONE = 0, MBT_TILE = 1, MBT_STRIP = 2, MBT_S2 = 3 };
+struct MbtForm { int kind = MBT_NONE, CK = 0, NMT = 0; bool RES = false; };
+MbtForm mbt_form(int N, int Cin, int Cexp, int Cout, int H, int W, int K, int S, bool has_res, int mode, int mode_s2,
+                 int mode_strip, int cus);
 
 // fused pair of ConvTranspose2d(k4,s2,p1) + add + folded BN + ReLU.
 // w [Ca+Cb][Cout][4][4] (BN scale folded), b [Cout].  in: [N,C,h,w] -> out [N,Cout,2h,2w]

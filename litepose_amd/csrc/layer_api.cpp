@@ -85,6 +85,15 @@ int lp_pw_tile_choice(int N, int Ca, int Cb, int Cout, int HW, int has_res) {
     return t.NB * 16 + t.PXV;
 }
 
+int lp_mbt_form(int N, int Cin, int Cexp, int Cout, int H, int W, int K, int S, int has_res, int mode, int mode_s2,
+                int mode_strip, int cus) {
+    if (N < 1 || Cin < 1 || Cexp < 1 || Cout < 1 || H < 1 || W < 1 || K < 1 || S < 1)
+        return fail(LP_ERR_INVALID_ARG, "N, Cin, Cexp, Cout, H, W, K and S must be positive");
+    const lp::MbtForm f = lp::mbt_form(N, Cin, Cexp, Cout, H, W, K, S, has_res != 0, mode, mode_s2, mode_strip, cus);
+    if (f.kind == lp::MBT_NONE) return LP_MBT_NONE;
+    return f.kind + 16 * f.CK + 256 * f.NMT + (f.RES ? 4096 : 0);
+}
+
 size_t lp_pw_forward_workspace_bytes(int Cin, int Cout) {
     if (Cin < 1 || Cout < 1 || Cin > 65535 || Cout > 65535) return 0;
     return (frag_floats(Cout, Cin) + bias_floats(Cout)) * sizeof(float);

@@ -924,64 +924,83 @@ static int device_cu_count() {
     return cus;
 }
 
-bool launch_mbt(const float* x, const void* w1s, const float* b1f, const void* wrow, const void* w2s,
-                const float* b2f, const float* res, float* out, int N, int Cin, int Cexp, int Cout, int H, int W,
-                int K, int S, hipStream_t s, int mode, int mode_s2, int mode_strip) {
+// Every shape rule of launch_mbt in one place (kernels.h: MbtForm); host arithmetic, no device unless cus <= 0.
+// The variants built: tile (CK, NMT) = (1, 1) (2, 1) (2, 2) (3, 1) (3, 2) -- a residual block has Cin == Cout, so (2, 2)
+// and (3, 1) can only be non-residual blocks --, strip (1, 1) (2, 1), s2 (1, 1) (1, 2) (2, 1) (2, 2).
+MbtForm mbt_form(int N, int Cin, int Cexp, int Cout, int H, int W, int K, int S, bool has_res, int mode, int mode_s2,
+                 int mode_strip, int cus) {
     // mode = option "mbt" (the parity tests compare the paths): 0 = off (mbconv2_kernel / the unfused chain),
     // 1 (default) = the 32-filter blocks and up, 2 = also the 16-filter blocks (mbconv2_kernel's), 3 = only the
     // stride-2 blocks (mbt_s2_kernel; mode_s2 = option "mbt_s2" = 0 switches those off separately)
-    if (mode == 0) return false;
+    const MbtForm none;
+    if (mode == 0) return none;
+    if (K == 7 && S == 2 && !has_res) {
+        if (!mode_s2) return none;
+        if ((Cin & 15) || Cin > 32 || (Cexp & 31) || (Cout & 7) || Cout > 64 || (H & 1) || (W & 1)) return none;
+        if (H < 16 || W < 16 || Cin < 16 || Cout < 8) return none;
+        // (2, 2) -- 32 -> 192 -> 48, the stage-3 entry block of XS / S -- sits exactly at the 256-register budget since
+        // the depthwise loop pins its LDS requests (dw7.h; it needed 20 bytes of scratch per lane before and stayed
+        // off the path: uses_scratch() in kernels.h)
+        return MbtForm{MBT_S2, Cin >> 4, (Cout + 31) >> 5, false};   // (1, 1) (1, 2) (2, 1) (2, 2): all built
+    }
+    if (K != 7 || S != 1) return none;
+    if ((Cin & 15) || Cin > 48 || (Cexp & 31) || (Cout & 7) || Cout > 64) return none;
+    if (has_res && Cin != Cout) return none;
+    if (H < 17 && W < 17) return none;                               // a single 16x16 plane: mb16_kernel
+    if (mode == 3) return none;                                      // 3 = the stride-2 blocks only (A/B hook)
+    if (mode == 1 && Cin < 32) return none;
+    if ((long)N * ((W + 15) / 16) * ((H + 15) / 16) > 0x7fffffffL) return none;
+    const int ck = Cin >> 4, nmt = (Cout + 31) >> 5;
+    // mode_strip = option "mbt_strip": planes with W == 32 as 32 x 16 strips (mbt_kernel<CK, NMT, RES, 16>, bit-identical):
+    // 0 = never, 1 (default) = when the N * ceil(H / 16) strips are at least one per CU -- a smaller launch fills more CUs
+    // as twice as many tiles --, 2 = always.  A shape whose variant is not built keeps the tiles
+    if (W == 32 && mode_strip &&
+        (mode_strip == 2 || (long)N * ((H + 15) / 16) >= (cus > 0 ? cus : device_cu_count()))) {
+        // built where the form fits the 256-register budget: 16- and 32-channel blocks of up to 32 filters (<2, 1> is
+        // the headline's stage 1).  <2, 2> needs 76 bytes of scratch per lane and CK = 3 holds 108 registers of x
+        // fragments: those shapes keep the tiles
+        if (nmt == 1 && (ck == 1 || ck == 2)) return MbtForm{MBT_STRIP, ck, nmt, has_res};
+    }
+    if (ck < 1 || nmt < 1 || nmt > 2 || (ck == 1 && nmt == 2)) return none;   // (1, 2) is not built
+    return MbtForm{MBT_TILE, ck, nmt, has_res};
+}
+
+bool launch_mbt(const float* x, const void* w1s, const float* b1f, const void* wrow, const void* w2s,
+                const float* b2f, const float* res, float* out, int N, int Cin, int Cexp, int Cout, int H, int W,
+                int K, int S, hipStream_t s, int mode, int mode_s2, int mode_strip) {
+    if (!w1s || !b1f || !wrow || !w2s || !b2f || (res && res != x)) return false;
+    const MbtForm f = mbt_form(N, Cin, Cexp, Cout, H, W, K, S, res != nullptr, mode, mode_s2, mode_strip, 0);
+    if (f.kind == MBT_NONE) return false;
     constexpr int xcd = 1;                                           // tiles dealt XCD-contiguously
-    if (K == 7 && S == 2 && !res && w1s && b1f && wrow && w2s && b2f) {
-        if (!mode_s2) return false;
-        if ((Cin & 15) || Cin > 32 || (Cexp & 31) || (Cout & 7) || Cout > 64 || (H & 1) || (W & 1)) return false;
-        if (H < 16 || W < 16) return false;
-        const int ck2 = Cin >> 4, nmt2 = (Cout + 31) >> 5;
+    if (f.kind == MBT_S2) {
         last_kernel_tag = "mbt_s2_kernel";
 #define LP_GO2(CKV, NMTV)                                                                                   \
-        if (ck2 == CKV && nmt2 == NMTV) {                                                                   \
+        if (f.CK == CKV && f.NMT == NMTV) {                                                                 \
             if (uses_scratch((const void*)mbt_s2_kernel<CKV, NMTV>)) return false;                          \
             launch_mbt_s2_t<CKV, NMTV>(x, w1s, b1f, wrow, w2s, b2f, out, N, Cexp, Cout, H, W, xcd, s);      \
             return true;                                                                                    \
         }
-        // (2, 2) -- 32 -> 192 -> 48, the stage-3 entry block of XS / S -- sits exactly at the 256-register budget since
-        // the depthwise loop pins its LDS requests (dw7.h; it needed 20 bytes of scratch per lane before and stayed
-        // off the path: uses_scratch() in kernels.h)
         LP_GO2(1, 1) LP_GO2(1, 2) LP_GO2(2, 1) LP_GO2(2, 2)
 #undef LP_GO2
         return false;
     }
-    if (K != 7 || S != 1 || !w1s || !b1f || !wrow || !w2s || !b2f) return false;
-    if ((Cin & 15) || Cin > 48 || (Cexp & 31) || (Cout & 7) || Cout > 64) return false;
-    if (res && (res != x || Cin != Cout)) return false;
-    if (H < 17 && W < 17) return false;                              // a single 16x16 plane: mb16_kernel
-    if (mode == 3) return false;                                     // 3 = the stride-2 blocks only (A/B hook)
-    if (mode == 1 && Cin < 32) return false;
-    if ((long)N * ((W + 15) / 16) * ((H + 15) / 16) > 0x7fffffffL) return false;
-    const int ck = Cin >> 4, nmt = (Cout + 31) >> 5;
     last_kernel_tag = "mbt_kernel";
 #define LP_GO(CKV, NMTV)                                                                                   \
-    if (ck == CKV && nmt == NMTV) {                                                                        \
+    if (f.CK == CKV && f.NMT == NMTV) {                                                                    \
         if (uses_scratch(res ? (const void*)mbt_kernel<CKV, NMTV, true> : (const void*)mbt_kernel<CKV, NMTV, false>)) \
             return false;                                                                                  \
         launch_mbt_t<CKV, NMTV>(x, w1s, b1f, wrow, w2s, b2f, res != nullptr, out, N, Cexp, Cout, H, W,     \
                                 xcd, s);                                                                   \
         return true;                                                                                       \
     }
-    // mode_strip = option "mbt_strip": planes with W == 32 as 32 x 16 strips (mbt_kernel<CK, NMT, RES, 16>, bit-identical):
-    // 0 = never, 1 (default) = when the N * ceil(H / 16) strips are at least one per CU -- a smaller launch fills more CUs
-    // as twice as many tiles --, 2 = always.  A shape whose variant is not built keeps the tiles
-    if (W == 32 && mode_strip && (mode_strip == 2 || (long)N * ((H + 15) / 16) >= device_cu_count())) {
+    if (f.kind == MBT_STRIP) {                                       // a strip kernel that needs scratch: the tiles
 #define LP_GOS(CKV, NMTV)                                                                                  \
-        if (ck == CKV && nmt == NMTV &&                                                                    \
+        if (f.CK == CKV && f.NMT == NMTV &&                                                                \
             !uses_scratch(res ? (const void*)mbt_kernel<CKV, NMTV, true, 16>                               \
                               : (const void*)mbt_kernel<CKV, NMTV, false, 16>)) {                          \
             launch_mbt_strip_t<CKV, NMTV>(x, w1s, b1f, wrow, w2s, b2f, res != nullptr, out, N, Cexp, Cout, H, xcd, s); \
             return true;                                                                                   \
         }
-        // built where the form fits the 256-register budget: 16- and 32-channel blocks of up to 32 filters (<2, 1> is
-        // the headline's stage 1).  <2, 2> needs 76 bytes of scratch per lane and CK = 3 holds 108 registers of x
-        // fragments: those shapes keep the tiles
         LP_GOS(1, 1) LP_GOS(2, 1)
 #undef LP_GOS
     }

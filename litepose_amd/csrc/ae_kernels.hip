@@ -1149,7 +1149,7 @@ bool launch_peaks_topk_walk(const float* mid, int N, int J, int h1, int w1, int 
     if ((double)thr > p.det_thr) thr = nextafterf(thr, -INFINITY);
     if (!(thr >= 0.f)) thr = 0.f;
     static_assert((size_t)16 * (TOPK_CAP / 16) * sizeof(u64) <= 64 * 1024,
-                  "above the default dynamic-LDS limit the launch needs hipFuncSetAttribute per device (ADVICE r05)");
+                  "above the default dynamic-LDS limit the launch needs kernel_allow_lds (kernels.h)");
 #define LP_PW(RV, WV)                                                                                    \
     hipLaunchKernelGGL((peaks_topk_walk_kernel<RV, WV>), dim3(N * J), dim3(WV * 64), lds, s, mid, J, h1, w1, T, p.M, \
                        thr, val_k, ind_k, tag_k)
@@ -1161,53 +1161,29 @@ bool launch_peaks_topk_walk(const float* mid, int N, int J, int h1, int w1, int 
 
 bool launch_peaks_topk(const float* det, const float* tag, int N, int J, int H, int W, int T,
                        const ParseParams& p, float* val_k, int* ind_k, float* tag_k, hipStream_t s, const float* mid) {
-    static bool attr_set = false;
+    // false means "shape not supported", so a refused LDS limit is not one: these kernels launch anyway and the launch
+    // error surfaces in the caller (kernel_allow_lds, kernels.h)
     const size_t lds = (size_t)TOPK_CAP * sizeof(u64);
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(peaks_topk_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(peaks_topk_fast_kernel<1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(peaks_topk_fast_kernel<2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(peaks_topk_fast_kernel<3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
     const int r = p.nms_k / 2;
     if ((W & 3) == 0 && p.M <= 64 && r >= 1 && r <= 3) {
-        const size_t lds2 = (size_t)TOPK_CAP * sizeof(u64);
-        static bool attr2 = false;
-        if (!attr2) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(peaks_topk_vec_kernel<1>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(peaks_topk_vec_kernel<2>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(peaks_topk_vec_kernel<3>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            attr2 = true;
-        }
-#define LP_PV(RV)                                                                                      \
-    hipLaunchKernelGGL((peaks_topk_vec_kernel<RV>), dim3(N * J), dim3(PK_THREADS), lds2, s, det, tag, J, \
-                       H, W, T, p.M, p.tag_per_joint, val_k, ind_k, tag_k, mid)
         if (!tag && (!mid || !p.tag_per_joint || (H & 1) || (W & 1))) return false;
-        if (r == 2) LP_PV(2);
-        else if (r == 1) LP_PV(1);
-        else LP_PV(3);
-#undef LP_PV
+        const auto kern = r == 2 ? peaks_topk_vec_kernel<2> : (r == 1 ? peaks_topk_vec_kernel<1> : peaks_topk_vec_kernel<3>);
+        (void)kernel_allow_lds(reinterpret_cast<const void*>(kern), lds);
+        hipLaunchKernelGGL(kern, dim3(N * J), dim3(PK_THREADS), lds, s, det, tag, J, H, W, T, p.M, p.tag_per_joint, val_k,
+                           ind_k, tag_k, mid);
         return true;
     }
     if (!tag) return false;                  // tags from mid: the vectorised kernel only
-#define LP_PK(RV)                                                                                     \
-    hipLaunchKernelGGL((peaks_topk_fast_kernel<RV>), dim3(N * J), dim3(PK_THREADS), lds, s, det, tag, J, \
-                       H, W, T, p.M, p.tag_per_joint, val_k, ind_k, tag_k)
-    if (r == 2) LP_PK(2);
-    else if (r == 1) LP_PK(1);
-    else if (r == 3) LP_PK(3);
-    else
-        hipLaunchKernelGGL(peaks_topk_kernel, dim3(N * J), dim3(256), lds, s, det, tag, J, H, W, T, p.M,
-                           r, p.tag_per_joint, val_k, ind_k, tag_k);
-#undef LP_PK
+    if (r >= 1 && r <= 3) {
+        const auto kern = r == 2 ? peaks_topk_fast_kernel<2> : (r == 1 ? peaks_topk_fast_kernel<1> : peaks_topk_fast_kernel<3>);
+        (void)kernel_allow_lds(reinterpret_cast<const void*>(kern), lds);
+        hipLaunchKernelGGL(kern, dim3(N * J), dim3(PK_THREADS), lds, s, det, tag, J, H, W, T, p.M, p.tag_per_joint, val_k,
+                           ind_k, tag_k);
+    } else {
+        (void)kernel_allow_lds(reinterpret_cast<const void*>(peaks_topk_kernel), lds);
+        hipLaunchKernelGGL(peaks_topk_kernel, dim3(N * J), dim3(256), lds, s, det, tag, J, H, W, T, p.M, r, p.tag_per_joint,
+                           val_k, ind_k, tag_k);
+    }
     return true;
 }
 

@@ -471,21 +471,10 @@ bool launch_peaks_topk_mid(const float* mid, int N, int J, int h1, int w1, int T
     if (r < 1 || r > 3 || p.M > 64 || W > PM_THREADS || T < 1 || T > 2 || !p.tag_per_joint) return false;
     const size_t lds = (size_t)TOPK_CAP * sizeof(u64) + (size_t)(PM_BR + 2 * r) * W * sizeof(float);
     if (lds > 150 * 1024) return false;
-#define LP_PM(RV)                                                                                        \
-    do {                                                                                                 \
-        static size_t attr_##RV = 0;                                                                     \
-        if (attr_##RV < lds) {                                                                           \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(peaks_topk_mid_kernel<RV>),          \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-            attr_##RV = lds;                                                                             \
-        }                                                                                                \
-        hipLaunchKernelGGL((peaks_topk_mid_kernel<RV>), dim3(N * J), dim3(PM_THREADS), lds, s, mid, J, h1, w1, T, \
-                           p.M, val_k, ind_k, tag_k);                                                    \
-    } while (0)
-    if (r == 2) LP_PM(2);
-    else if (r == 1) LP_PM(1);
-    else LP_PM(3);
-#undef LP_PM
+    // false means "shape not supported" here, so a refused LDS limit is not one: the launch error surfaces in the caller
+    const auto kern = r == 2 ? peaks_topk_mid_kernel<2> : (r == 1 ? peaks_topk_mid_kernel<1> : peaks_topk_mid_kernel<3>);
+    (void)kernel_allow_lds(reinterpret_cast<const void*>(kern), lds);
+    hipLaunchKernelGGL(kern, dim3(N * J), dim3(PM_THREADS), lds, s, mid, J, h1, w1, T, p.M, val_k, ind_k, tag_k);
     return true;
 }
 
@@ -499,12 +488,7 @@ void launch_adjust_scores_mid(const float* mid, int N, int J, int h1, int w1, in
 void launch_refine_mid(const float* mid, int N, int J, int h1, int w1, int T, int pcap, float* ans,
                        const int* count, const float* prev, const unsigned* miss, hipStream_t s) {
     const size_t lds = (size_t)4 * (RM_ROWS + 2) * (w1 + 2) * sizeof(float);
-    static size_t attr = 0;
-    if (attr < lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(refine_mid_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
-    }
+    (void)kernel_allow_lds(reinterpret_cast<const void*>(refine_mid_kernel), lds);     // no other form: launch anyway
     hipLaunchKernelGGL(refine_mid_kernel, dim3(J, N), dim3(RM_THREADS), lds, s, mid, J, h1, w1, T, pcap, ans, count,
                        prev, miss);
 }

@@ -16,6 +16,7 @@
 // (fmt16.h) with two entry points -- the bf16 one under its original name and template list, and an overload with a
 // leading lp::F16 (e.g. lp::mbtb_kernel<lp::F16, 1, 1, true>); NAME_fn<F, ...>() gives the launcher the entry point of F.
 #include "kernels.h"
+#include "fused_common.h"
 #include "fmt16.h"
 #include "split3.h"
 
@@ -23,16 +24,6 @@
 #include <cstdlib>
 
 namespace lp {
-
-namespace {
-
-__device__ __forceinline__ int xcd_id(int id, int n) {      // see xcd_contiguous_id (net_kernels.hip)
-    const int q = n >> 3, r = n & 7;
-    const int xcd = id & 7, slot = id >> 3;
-    return xcd * q + min(xcd, r) + slot;
-}
-
-}  // namespace
 
 // =====================================================================================
 // stem: conv 3x3 stride 2 pad 1, 3 -> 32, + bias + ReLU6 on the fp32 image (mirror-on-read for the
@@ -151,7 +142,7 @@ __device__ __forceinline__ void dwb_kernel_body(const u32x4* __restrict__ in, co
     extern __shared__ __attribute__((aligned(16))) f32x4 smem4[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = xcd_remap ? xcd_id(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int bid = xcd_remap ? xcd_contiguous_id(blockIdx.x, gridDim.x) : blockIdx.x;
     const int u0 = (bid * 4 + wave) * tpw;
     if (u0 >= units) return;                                   // wave-uniform
     const int u1 = min(units, u0 + tpw);
@@ -301,7 +292,7 @@ inline auto dwb_kernel_fn() {
 
 
 template <class F, int K, int S>
-static void launch_dwb_t(const void* in, const float* w, void* out, int N, int C, int H, int W, int act,
+static bool launch_dwb_t(const void* in, const float* w, void* out, int N, int C, int H, int W, int act,
                          hipStream_t s) {
     using G = DwbGeom<K, S>;
     const int OH = (H + 2 * (K / 2) - K) / S + 1, OW = (W + 2 * (K / 2) - K) / S + 1;
@@ -311,15 +302,11 @@ static void launch_dwb_t(const void* in, const float* w, void* out, int N, int C
     // units per wave: the next unit's loads fly under this unit's FMAs; keep >= ~8 waves per SIMD in the grid
     const int tpw = units >= 32768 ? 4 : (units >= 16384 ? 2 : 1);
     const unsigned grid = (unsigned)((units + 4L * tpw - 1) / (4L * tpw));
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)dwb_kernel_fn<F, K, S>(), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  4 * G::LDS_BYTES);
-        attr_done = true;
-    }
+    if (!kernel_ready((const void*)dwb_kernel_fn<F, K, S>(), 4 * G::LDS_BYTES)) return false;
     LP_LAUNCH((dwb_kernel_fn<F, K, S>()), dim3(grid), dim3(256), 4 * G::LDS_BYTES, s, (const u32x4*)in,
                        (const f32x4*)w, (u32x4*)out, C / 8, H, W, OH, OW, tilesX, tilesY, act, (int)units, tpw,
                        (xr && tilesX * tilesY > 4) ? 1 : 0);
+    return true;
 }
 
 bool launch_dwb(const void* in, const float* w, void* out, int N, int C, int H, int W, int K, int S, int act,
@@ -330,15 +317,14 @@ bool launch_dwb(const void* in, const float* w, void* out, int N, int C, int H, 
                                        : (S == 1 ? "dwb_kernel<3,1>" : "dwb_kernel<3,2>"));
 #define LP_DWB(KV, SV) \
     (f16 ? launch_dwb_t<F16, KV, SV>(in, w, out, N, C, H, W, act, s) : launch_dwb_t<Bf16, KV, SV>(in, w, out, N, C, H, W, act, s))
-    if (K == 7 && S == 1) LP_DWB(7, 1);
-    else if (K == 7 && S == 2) LP_DWB(7, 2);
-    else if (K == 5 && S == 1) LP_DWB(5, 1);
-    else if (K == 5 && S == 2) LP_DWB(5, 2);
-    else if (K == 3 && S == 1) LP_DWB(3, 1);
-    else if (K == 3 && S == 2) LP_DWB(3, 2);
-    else return false;
+    if (K == 7 && S == 1) return LP_DWB(7, 1);
+    if (K == 7 && S == 2) return LP_DWB(7, 2);
+    if (K == 5 && S == 1) return LP_DWB(5, 1);
+    if (K == 5 && S == 2) return LP_DWB(5, 2);
+    if (K == 3 && S == 1) return LP_DWB(3, 1);
+    if (K == 3 && S == 2) return LP_DWB(3, 2);
 #undef LP_DWB
-    return true;
+    return false;
 }
 
 // =====================================================================================
@@ -378,7 +364,7 @@ __device__ __forceinline__ void dwt_kernel_body(const u32x4* __restrict__ in, co
     unsigned* O = dwt_smem + G::LDS_IN / 4;                    // [4 tiles][256 px][4 dwords]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int unit = xcd_remap ? xcd_id(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int unit = xcd_remap ? xcd_contiguous_id(blockIdx.x, gridDim.x) : blockIdx.x;
     const int rq = unit / regsX;
     const int rx = unit - rq * regsX;
     const int nc = rq / regsY;                                 // n * C8 + octet
@@ -546,7 +532,7 @@ __device__ __forceinline__ void headb_kernel_body(
     unsigned* O = dwt_smem + G::LDS_IN / 4;                    // [2 octets of a k-step][4 tiles][256 px][4 dwords]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int unit = xcd_remap ? xcd_id(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int unit = xcd_remap ? xcd_contiguous_id(blockIdx.x, gridDim.x) : blockIdx.x;
     const int rq = unit / regsX;
     const int rx = unit - rq * regsX;
     const int n = rq / regsY;
@@ -713,17 +699,10 @@ bool launch_headb(const void* inA, int Ca, const void* inB, int Cb, const void* 
     if (units > 0x7fffffffL) return false;
     const int remap = regsX * regsY > 4 ? 1 : 0;
     const size_t lds = DwtGeom<5>::LDS_IN + 2 * DwtGeom<5>::LDS_OUT;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(headb_kernel_fn<Bf16>()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(headb_kernel_fn<F16>()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(headb_kernel_fn<Bf16, false>()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(headb_kernel_fn<F16, false>()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
     last_kernel_tag = "headb_kernel";
     const auto kern = dual ? (f16 ? headb_kernel_fn<F16>() : headb_kernel_fn<Bf16>())
                            : (f16 ? headb_kernel_fn<F16, false>() : headb_kernel_fn<Bf16, false>());
+    if (!kernel_ready(reinterpret_cast<const void*>(kern), lds)) return false;
     LP_LAUNCH(kern, dim3((unsigned)units), dim3(256), lds, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8,
               (const u32x4*)wtA, wbA, (const u32x4*)wtB, wbB, (const u32x4*)wf, out, H, W, regsX, regsY, Cout, remap);
     return true;
@@ -953,7 +932,7 @@ __device__ __forceinline__ void deconvb_kernel_body(const u32x4* __restrict__ in
                                                       int xcd_remap) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const int bid = xcd_remap ? xcd_id(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int bid = xcd_remap ? xcd_contiguous_id(blockIdx.x, gridDim.x) : blockIdx.x;
     const long px0 = ((long)bid * 4 + wave) * 32;
     if (px0 >= NP) return;
     const int half = lane >> 5, pl = lane & 31;

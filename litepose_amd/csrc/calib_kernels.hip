@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void stem_raw_kernel(const float* __restrict__
 
 // ConvTranspose2d(k4, s2, p1) of the refined source + the same of the raw source (inB may be null: Cb = 0), raw sum.
 // w [Ca+Cb][Cout][4][4].  One input cell per lane -> its 2x2 output cells, COT output channels per workgroup row.
-template <int COT>
+constexpr int COT = 8;
 __global__ __launch_bounds__(256) void deconv_raw_kernel(const float* __restrict__ inA, int Ca,
                                                          const float* __restrict__ inB, int Cb,
                                                          const float* __restrict__ w, float* __restrict__ out, int N,
@@ -242,10 +242,9 @@ void launch_stem_raw(const float* x, const float* w, float* out, int N, int H, i
 
 void launch_deconv_raw(const float* inA, int Ca, const float* inB, int Cb, const float* w, float* out, int N, int h,
                        int w_, int Cout, hipStream_t s) {
-    constexpr int COT = 8;
     const long total = (long)N * h * w_;
     dim3 grid((unsigned)((total + 255) / 256), (Cout + COT - 1) / COT), block(256);
-    LP_LAUNCH((deconv_raw_kernel<COT>), grid, block, 0, s, inA, Ca, inB, Cb, w, out, N, h, w_, Cout);
+    LP_LAUNCH(deconv_raw_kernel, grid, block, 0, s, inA, Ca, inB, Cb, w, out, N, h, w_, Cout);
 }
 
 size_t bn_partial_doubles(int N, int C, int HW) { return 2 * (size_t)C * bn_cut(N, C, HW).S; }

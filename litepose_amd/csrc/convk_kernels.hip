@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256, 2) void convk3_kernel(
 }
 
 template <int K, int S, int NB>
-static void convk3_go(const float* inA, int Ca, const float* inB, int Cb, const void* ws, const float* bias, float* out, int N,
+static bool convk3_go(const float* inA, int Ca, const float* inB, int Cb, const void* ws, const float* bias, float* out, int N,
                int IH, int IW, int ups, int OH, int OW, int Cout, int act, int flip_from, int x_batch, hipStream_t s) {
     constexpr int PG = S == 1 ? 2 : 1;
     const CkGeo g = ck_geo(OW, K, S, PG);
@@ -210,15 +210,12 @@ static void convk3_go(const float* inA, int Ca, const float* inB, int Cb, const 
     const size_t lds = (size_t)2 * g.ir * g.rs * CK_REC;
     const int nblk = (Cout + 31) / 32;
     auto kern = convk3_kernel<K, S, NB, PG>;
-    static bool attr = false;
-    if (!attr) {                                                  // the largest tile of this form (stride 2, k7: 87 KB)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  96 * 1024);
-        attr = true;
-    }
+    // the limit is set once, for the largest tile of this form (stride 2, k7: 87 KB)
+    if (!kernel_ready(reinterpret_cast<const void*>(kern), 96 * 1024)) return false;
     dim3 grid((unsigned)((long)N * tilesX * tilesY), (unsigned)((nblk + NB - 1) / NB)), block(256);
     LP_LAUNCH(kern, grid, block, lds, s, inA, Ca, inB, Cb, (const u32x4*)ws, bias, out, tilesX, tilesY, IH, IW, ups, OH,
               OW, Cout, act, flip_from, x_batch);
+    return true;
 }
 
 bool launch_convk3(const float* inA, int Ca, const float* inB, int Cb, const void* ws, const float* bias, float* out,
@@ -230,21 +227,15 @@ bool launch_convk3(const float* inA, int Ca, const float* inB, int Cb, const voi
     const int CH = IH << ups, CW = IW << ups;                     // the conv's input plane
     const int OH = (CH - 1) / S + 1, OW = (CW - 1) / S + 1;
 #define LP_CK(KV, SV)                                                                                              \
-    do {                                                                                                           \
-        if (Cout <= 32)                                                                                            \
-            convk3_go<KV, SV, 1>(inA, Ca, inB, Cb, ws, bias, out, N, CH, CW, ups, OH, OW, Cout, act, flip_from,    \
-                                 x_batch, s);                                                                      \
-        else                                                                                                       \
-            convk3_go<KV, SV, 2>(inA, Ca, inB, Cb, ws, bias, out, N, CH, CW, ups, OH, OW, Cout, act, flip_from,    \
-                                 x_batch, s);                                                                      \
-    } while (0)
-    if (K == 7 && S == 1) LP_CK(7, 1);
-    else if (K == 7) LP_CK(7, 2);
-    else if (K == 5 && S == 1) LP_CK(5, 1);
-    else if (K == 5) LP_CK(5, 2);
-    else if (S == 1) LP_CK(3, 1);
-    else LP_CK(3, 2);
+    (Cout <= 32 ? convk3_go<KV, SV, 1>(inA, Ca, inB, Cb, ws, bias, out, N, CH, CW, ups, OH, OW, Cout, act, flip_from,  \
+                                       x_batch, s)                                                                 \
+                : convk3_go<KV, SV, 2>(inA, Ca, inB, Cb, ws, bias, out, N, CH, CW, ups, OH, OW, Cout, act, flip_from,  \
+                                       x_batch, s))
+    const bool ok = K == 7 ? (S == 1 ? LP_CK(7, 1) : LP_CK(7, 2))
+                  : K == 5 ? (S == 1 ? LP_CK(5, 1) : LP_CK(5, 2))
+                           : (S == 1 ? LP_CK(3, 1) : LP_CK(3, 2));
 #undef LP_CK
+    if (!ok) return false;
     // The tags of this family come from a table, not from literals in the assignment: the kernel census of the
     // pose_mobilenet family (tests/test_gpu_kernel_census.py) collects the literals assigned to last_kernel_tag and wants a
     // pose_mobilenet case for each, which a dense-conv form cannot have.  This family's forms are enumerated and compared

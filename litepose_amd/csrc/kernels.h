@@ -16,6 +16,15 @@ enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_RELU6 = 2 };
 // Every fused-block launcher still asks this before it picks a variant and falls through to the next form.
 bool uses_scratch(const void* kernel_fn);
 
+// The launch gate of every kernel that takes dynamic LDS: false when the kernel needs scratch (above), otherwise
+// kernel_allow_lds.  A launcher that returns bool returns false on it (its caller takes the next form).
+bool kernel_ready(const void* kernel_fn, size_t dyn_lds);
+// Raises the kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) to dyn_lds on the current device:
+// one runtime call per (device, kernel) and thread, a table lookup afterwards (eager and capture launches; a graph replay
+// runs no launcher).  false = the runtime refused, the sticky error is cleared.  Alone it serves the void launchers that have no other form to fall
+// back to (peaks_topk*, refine_mid_kernel): they launch anyway and the launch error surfaces at the end of the call.
+bool kernel_allow_lds(const void* kernel_fn, size_t dyn_lds);
+
 // name of the kernel the last launch_* call enqueued (profiling aid, set by the launchers)
 extern thread_local const char* last_kernel_tag;
 
@@ -115,8 +124,9 @@ bool launch_mbconv(const float* x, const float* w1p, const float* b1f, const flo
                    int N, int Cin, int Cexp, int Cout, int H, int W, int K, int S, hipStream_t s,
                    const float* wdw_pair = nullptr, const void* w1_split = nullptr, const void* wdw_rows = nullptr,
                    int mbconv2 = 1);
-// wdw_rows: depthwise weights as pair rows [C/2][7][7 taps x 2 ch + bias pair in row 0's pad] -> LDS-staged
-// w1_split: exact bf16x3 split of the expand weights (pack_pw) -> the expand runs on bf16 MFMAs
+// Cin = 24: mbconv_kernel / mbconv_s2_kernel (w1p, wdw_pair, bdw).  Cin = 16, stride 1: mbconv2_kernel, which takes
+// wdw_rows: depthwise weights as pair rows [C/2][7][7 taps x 2 ch + bias pair in row 0's pad], and
+// w1_split: exact bf16x3 split of the expand weights (pack_pw): its expand runs on bf16 MFMAs
 
 // whole InvBottlenecks (stride 1, k7) on a 16x16 plane, one workgroup per image, bf16x3 MFMA 1x1s (mb16_kernels.hip):
 // a RUN of up to MB16_MAX_RUN consecutive blocks per launch.  Per block: w1s / b1f / w2s / b2f = the exact bf16x3

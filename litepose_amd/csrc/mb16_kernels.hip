@@ -40,6 +40,7 @@
 // for 32 cycles and a lone wave issues one VALU instruction per ~5 cycles, so at two waves per SIMD there is no idle
 // issue slot to win; profiles/r04_phase_mix.txt).
 #include "kernels.h"
+#include "fused_common.h"
 #include "dw7.h"
 #include "split3.h"
 
@@ -52,16 +53,8 @@ constexpr int M16_PAIR = 22 * M16_RS * 2 + 4;            // floats per channel p
                                                          // consecutive pairs start an ODD number of slots apart (see the
                                                          // depthwise lane mapping)
 constexpr int M16_LDS_FLOATS = 16 * M16_PAIR + 8;        // + the two cells strip 3 reads past the last row
-// weight stage behind the E chunk: [expand slice: CK k-steps][project slice: NMT blocks x 2 k-steps] x
-// 3 pieces x 64 lanes x 16 bytes, the expand bias of the chunk, then (double-buffered by chunk parity) the
-// depthwise filter rows of the chunk's 16 pairs [16][7 rows][7 taps x 2 ch, bias pair in row 0's pad]
-template <int CK, int NMT> struct M16W {
-    static constexpr int N1 = CK * 3 * 64, N2 = NMT * 2 * 3 * 64, N3 = 64, N4 = 16 * 28;  // u32x4 elements (N3: 8 used;
-                                                                            // every region a whole number of waves)
-    static constexpr int NTOT = N1 + N2 + N3 + N4;                          // what one staging pass moves
-    static constexpr int NLD = (NTOT + 511) / 512;
-    static constexpr size_t LDS_BYTES = (size_t)M16_LDS_FLOATS * 4 + (size_t)(NTOT + N4) * 16;
-};
+// weight stage behind the E chunk (fused_common.h): bf16x3 pieces, 512 threads
+template <int CK, int NMT> using M16W = StageLayout<CK, NMT, 3, 512, (size_t)M16_LDS_FLOATS * 4>;
 
 // bf16 piece (low / high half of a dword) -> the fp32 value it stands for
 __device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
@@ -353,19 +346,38 @@ bool uses_scratch(const void* kernel_fn) {
     return r;
 }
 
+bool kernel_allow_lds(const void* kernel_fn, size_t dyn_lds) {
+    // the same kind of cache, keyed by (device, kernel): the largest limit the runtime granted and the smallest it
+    // refused, so that neither is asked for twice
+    struct Entry { const void* fn; int dev; size_t granted, refused; };
+    static thread_local Entry tab[512];
+    static thread_local int ntab = 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
+    Entry* e = nullptr;
+    for (int i = 0; i < ntab && !e; ++i)
+        if (tab[i].fn == kernel_fn && tab[i].dev == dev) e = &tab[i];
+    if (e && dyn_lds <= e->granted) return true;
+    if (e && e->refused && dyn_lds >= e->refused) return false;
+    const bool ok = hipFuncSetAttribute(kernel_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds) == hipSuccess;
+    if (!ok) (void)hipGetLastError();
+    if (!e && ntab < 512) { e = &tab[ntab++]; *e = Entry{kernel_fn, dev, 0, 0}; }
+    if (e) (ok ? e->granted : e->refused) = dyn_lds;
+    return ok;
+}
+
+bool kernel_ready(const void* kernel_fn, size_t dyn_lds) {
+    return !uses_scratch(kernel_fn) && kernel_allow_lds(kernel_fn, dyn_lds);
+}
+
 template <int CK, int NMT>
-static void launch_mb16_t(const float* x, const Mb16Run& run, bool res, int N, int Cexp, int Cout, hipStream_t s) {
+static bool launch_mb16_t(const float* x, const Mb16Run& run, bool res, int N, int Cexp, int Cout, hipStream_t s) {
     const size_t lds = M16W<CK, NMT>::LDS_BYTES;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mb16_kernel<CK, NMT, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mb16_kernel<CK, NMT, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (!kernel_ready(res ? (const void*)mb16_kernel<CK, NMT, true> : (const void*)mb16_kernel<CK, NMT, false>, lds))
+        return false;
     if (res) LP_LAUNCH((mb16_kernel<CK, NMT, true>), dim3(N), dim3(512), lds, s, x, run, Cexp, Cout);
     else LP_LAUNCH((mb16_kernel<CK, NMT, false>), dim3(N), dim3(512), lds, s, x, run, Cexp, Cout);
+    return true;
 }
 
 bool mb16_supported(int Cin, int Cexp, int Cout, int H, int W, int K, int S, bool res) {
@@ -388,11 +400,8 @@ bool launch_mb16(const float* x, const Mb16Run& run, bool res, int N, int Cin, i
         if (!run.w1s[b] || !run.b1f[b] || !run.wrow[b] || !run.w2s[b] || !run.b2f[b] || !run.out[b]) return false;
     const int nmt = (Cout + 31) >> 5, ck = Cin >> 4;
     last_kernel_tag = "mb16_kernel";
-#define LP_GO(CKV, NMTV)                                                              \
-    if (ck == CKV && nmt == NMTV) {                                                   \
-        launch_mb16_t<CKV, NMTV>(x, run, res, N, Cexp, Cout, s);                      \
-        return true;                                                                  \
-    }
+#define LP_GO(CKV, NMTV) \
+    if (ck == CKV && nmt == NMTV) return launch_mb16_t<CKV, NMTV>(x, run, res, N, Cexp, Cout, s);
     LP_GO(3, 2) LP_GO(3, 3) LP_GO(3, 4) LP_GO(5, 3) LP_GO(6, 3)
 #undef LP_GO
     return false;

@@ -31,6 +31,7 @@
 // (fmt16.h) with two entry points -- the bf16 one under its original name and template list, and an overload with a
 // leading lp::F16 (e.g. lp::mbtb_kernel<lp::F16, 1, 1, true>); NAME_fn<F, ...>() gives the launcher the entry point of F.
 #include "kernels.h"
+#include "fused_common.h"
 #include "dw7.h"
 #include "fmt16.h"
 #include "split3.h"
@@ -122,18 +123,8 @@ constexpr int TB_DP = 264;                                // dwords per channel 
                                                           // two lane halves of a project read -- 32 banks apart)
 constexpr int TB_D_DWORDS = 16 * TB_DP;
 
-template <int CK, int NMT> struct TBW {
-    static constexpr int N1 = CK * 64, N2 = NMT * 2 * 64, N3 = 64, N4 = 16 * 28;   // u32x4 elements
-    static constexpr int NTOT = N1 + N2 + N3 + N4;
-    static constexpr int NLD = (NTOT + 511) / 512;
-    static constexpr size_t LDS_BYTES = (size_t)(TB_E_FLOATS + TB_D_DWORDS) * 4 + (size_t)(NTOT + N4) * 16;
-};
-
-__device__ __forceinline__ int tb_xcd_contiguous_id(int id, int n) {     // see net_kernels.hip
-    const int q = n >> 3, r = n & 7;
-    const int xcd = id & 7, slot = id >> 3;
-    return xcd * q + min(xcd, r) + slot;
-}
+// weight stage behind the E and D tiles (fused_common.h): one piece per fragment (16-bit weights), 512 threads
+template <int CK, int NMT> using TBW = StageLayout<CK, NMT, 1, 512, (size_t)(TB_E_FLOATS + TB_D_DWORDS) * 4>;
 
 }  // namespace
 
@@ -154,7 +145,7 @@ __device__ __forceinline__ void mbtb_kernel_body(
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5, pl = lane & 31;
-    const int unit = xcd_remap ? tb_xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int unit = xcd_remap ? xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int tq = unit / tilesX;
     const int tx = unit - tq * tilesX;
     const int n = tq / tilesY;
@@ -424,12 +415,7 @@ constexpr int SB_GPW = (SB_NG + 7) / 8;                   // groups per wave (4;
 constexpr int SB_DP = 136;                                // dwords per pair of the depthwise result (128 px + 8)
 constexpr int SB_D_DWORDS = 16 * SB_DP;
 
-template <int CK, int NMT> struct SBW {
-    static constexpr int N1 = CK * 64, N2 = NMT * 2 * 64, N3 = 64, N4 = 16 * 28;
-    static constexpr int NTOT = N1 + N2 + N3 + N4;
-    static constexpr int NLD = (NTOT + 511) / 512;
-    static constexpr size_t LDS_BYTES = (size_t)(SB_E_FLOATS + SB_D_DWORDS) * 4 + (size_t)(NTOT + N4) * 16;
-};
+template <int CK, int NMT> using SBW = StageLayout<CK, NMT, 1, 512, (size_t)(SB_E_FLOATS + SB_D_DWORDS) * 4>;
 }  // namespace
 
 template <class F, int CK, int NMT>
@@ -444,7 +430,7 @@ __device__ __forceinline__ void mbtb_s2_kernel_body(
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5, pl = lane & 31;
-    const int unit = xcd_remap ? tb_xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int unit = xcd_remap ? xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int tq = unit / tilesX;
     const int tx = unit - tq * tilesX;
     const int n = tq / tilesY;
@@ -708,12 +694,8 @@ constexpr int TQ_D_DWORDS = 8 * TB_DP;
 constexpr int TQ_NG = (TB_CELLS + 15) / 16;               // 31 groups of 16 halo cells
 constexpr int TQ_GPW = (TQ_NG + 3) / 4;                   // 8 per wave (wave 3: 7)
 
-template <int CK, int NMT> struct TQW {                    // CK = 16-channel k-steps of the block input (as TBW)
-    static constexpr int N1 = CK * 64, N2 = NMT * 2 * 64, N3 = 64, N4 = 16 * 28;   // u32x4 elements
-    static constexpr int NTOT = N1 + N2 + N3 + N4;
-    static constexpr int NLD = (NTOT + 255) / 256;
-    static constexpr size_t LDS_BYTES = (size_t)(TQ_E_FLOATS + TQ_D_DWORDS) * 4 + (size_t)(NTOT + N4) * 16;
-};
+// as TBW, staged by the 256 threads of a 4-wave workgroup
+template <int CK, int NMT> using TQW = StageLayout<CK, NMT, 1, 256, (size_t)(TQ_E_FLOATS + TQ_D_DWORDS) * 4>;
 }  // namespace
 
 template <class F, int CK, int NMT, bool RES>
@@ -729,7 +711,7 @@ __device__ __forceinline__ void mbtq_kernel_body(
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5, pl = lane & 31;                      // project / epilogue roles
     const int cn = lane & 15, cg = lane >> 4;                        // expand roles: cell of the group, octet / channel quad
-    const int unit = xcd_remap ? tb_xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int unit = xcd_remap ? xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int tq = unit / tilesX;
     const int tx = unit - tq * tilesX;
     const int n = tq / tilesY;
@@ -974,13 +956,8 @@ static bool launch_mbtq_t(const void* x, const void* w1, const float* b1f, const
                           const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int xcd,
                           hipStream_t s) {
     const void* fn = reinterpret_cast<const void*>(mbtq_kernel_fn<F, CK, NMT, RES>());
-    if (uses_scratch(fn)) return false;
     const size_t lds = TQW<CK, NMT>::LDS_BYTES;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (!kernel_ready(fn, lds)) return false;
     const int tilesX = (W + 15) / 16, tilesY = (H + 15) / 16;
     LP_LAUNCH((mbtq_kernel_fn<F, CK, NMT, RES>()), dim3(N * tilesX * tilesY), dim3(256), lds, s, (const u32x4*)x,
               (const u32x4*)w1, b1f, (const f32x4*)wrow, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp,
@@ -1015,13 +992,8 @@ namespace {
 constexpr int TD_RS = 14;                                 // dwords per E row: 11 cell pairs + 3 (bank spread of the row pairs)
 constexpr int TD_PS = 22 * TD_RS;                         // dwords per channel plane
 constexpr int TD_E_DWORDS = 32 * TD_PS;
-template <int CK, int NMT> struct TDW {
-    static constexpr int N1 = CK * 64, N2 = NMT * 2 * 64, N3 = 64, N4 = 16 * 28;   // u32x4 elements, as TBW; the depthwise biases
-                                                                                    // ride in the N3 segment (see stage_addr)
-    static constexpr int NTOT = N1 + N2 + N3 + N4;
-    static constexpr int NLD = (NTOT + 511) / 512;
-    static constexpr size_t LDS_BYTES = (size_t)(TD_E_DWORDS + TB_D_DWORDS) * 4 + (size_t)(NTOT + N4) * 16;
-};
+// as TBW; the depthwise biases ride in the N3 segment (see stage_addr)
+template <int CK, int NMT> using TDW = StageLayout<CK, NMT, 1, 512, (size_t)(TD_E_DWORDS + TB_D_DWORDS) * 4>;
 __device__ __forceinline__ float td_swap(float v) {      // lane 2i <-> lane 2i + 1
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
 }
@@ -1040,7 +1012,7 @@ __device__ __forceinline__ void mbtd_kernel_body(     // 4 waves per SIMD = two 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5, pl = lane & 31;
-    const int unit = xcd_remap ? tb_xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int unit = xcd_remap ? xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int tq = unit / tilesX;
     const int tx = unit - tq * tilesX;
     const int n = tq / tilesY;
@@ -1322,14 +1294,9 @@ static bool launch_mbtd_t(const void* x, const void* w1, const float* b1f, const
                           const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int xcd,
                           hipStream_t s) {
     const void* fn = reinterpret_cast<const void*>(mbtd_kernel_fn<F, CK, NMT, RES>());
-    if (uses_scratch(fn)) return false;
     const size_t lds = TDW<CK, NMT>::LDS_BYTES;
     static_assert(TDW<CK, NMT>::LDS_BYTES <= 80 * 1024, "two workgroups per CU");
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (!kernel_ready(fn, lds)) return false;
     const int tilesX = (W + 15) / 16, tilesY = (H + 15) / 16;
     LP_LAUNCH((mbtd_kernel_fn<F, CK, NMT, RES>()), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
               (const u32x4*)w1, b1f, (const u32x4*)wrow2, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp,
@@ -1342,13 +1309,8 @@ static bool launch_mbtb_s2_t(const void* x, const void* w1, const float* b1f, co
                              const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int xcd,
                              hipStream_t s) {
     const void* fn = reinterpret_cast<const void*>(mbtb_s2_kernel_fn<F, CK, NMT>());
-    if (uses_scratch(fn)) return false;
     const size_t lds = SBW<CK, NMT>::LDS_BYTES;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (!kernel_ready(fn, lds)) return false;
     const int OH = H / 2, OW = W / 2;
     const int tilesX = (OW + 15) / 16, tilesY = (OH + 7) / 8;
     LP_LAUNCH((mbtb_s2_kernel_fn<F, CK, NMT>()), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
@@ -1362,13 +1324,8 @@ static bool launch_mbtb_t(const void* x, const void* w1, const float* b1f, const
                           const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int xcd,
                           hipStream_t s) {
     const void* fn = reinterpret_cast<const void*>(mbtb_kernel_fn<F, CK, NMT, RES>());
-    if (uses_scratch(fn)) return false;
     const size_t lds = TBW<CK, NMT>::LDS_BYTES;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (!kernel_ready(fn, lds)) return false;
     const int tilesX = (W + 15) / 16, tilesY = (H + 15) / 16;
     LP_LAUNCH((mbtb_kernel_fn<F, CK, NMT, RES>()), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
                        (const u32x4*)w1, b1f, (const f32x4*)wrow, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp,
@@ -1423,9 +1380,10 @@ bool launch_mbtb(const void* x, const void* w1, const float* b1f, const void* wr
         (mode_q == 2 || (Cexp <= 160 && (long)N * ((W + 15) / 16) * ((H + 15) / 16) >= 1024))) {
         last_kernel_tag = "mbtq_kernel";
 #define LP_GOQ(CKV, NMTV)                                                                                   \
-        if (ck == CKV && nmt == NMTV)                                                                       \
-            return f16 ? launch_mbtq_t<F16, CKV, NMTV, true>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s) \
-                       : launch_mbtq_t<Bf16, CKV, NMTV, true>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s);
+        if (ck == CKV && nmt == NMTV &&                                                                     \
+            (f16 ? launch_mbtq_t<F16, CKV, NMTV, true>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s) \
+                 : launch_mbtq_t<Bf16, CKV, NMTV, true>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s))) \
+            return true;                               /* refused, as above: mbtb_kernel below */
         LP_GOQ(1, 1) LP_GOQ(2, 1)
 #undef LP_GOQ
     }

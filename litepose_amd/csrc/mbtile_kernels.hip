@@ -25,6 +25,7 @@
 // Round 7: planes 32 wide run as 32-wide x 16-row strips (the overload mbt_kernel<CK, NMT, RES, 16> below, option
 // "mbt_strip"), bit-identical to the tiles.
 #include "kernels.h"
+#include "fused_common.h"
 #include "dw7.h"
 #include "split3.h"
 
@@ -37,18 +38,8 @@ constexpr int MT_PAIR = 22 * MT_RS * 2 + 4;               // floats per channel 
 constexpr int MT_E_FLOATS = 16 * MT_PAIR;
 constexpr int MT_CELLS = 22 * 22;                         // halo cells the depthwise reads
 
-template <int CK, int NMT> struct MTW {
-    static constexpr int N1 = CK * 3 * 64, N2 = NMT * 2 * 3 * 64, N3 = 64, N4 = 16 * 28;   // u32x4 elements, as M16W
-    static constexpr int NTOT = N1 + N2 + N3 + N4;
-    static constexpr int NLD = (NTOT + 511) / 512;
-    static constexpr size_t LDS_BYTES = (size_t)MT_E_FLOATS * 4 + (size_t)(NTOT + N4) * 16;
-};
-
-__device__ __forceinline__ int mt_xcd_contiguous_id(int id, int n) {       // see net_kernels.hip
-    const int q = n >> 3, r = n & 7;
-    const int xcd = id & 7, slot = id >> 3;
-    return xcd * q + min(xcd, r) + slot;
-}
+// weight stage behind the E tile (fused_common.h): bf16x3 pieces, 512 threads, as mb16_kernel's
+template <int CK, int NMT> using MTW = StageLayout<CK, NMT, 3, 512, (size_t)MT_E_FLOATS * 4>;
 
 template <int CK, int NMT, bool RES>
 __global__ __launch_bounds__(512, 2) void mbt_kernel(
@@ -66,7 +57,7 @@ __global__ __launch_bounds__(512, 2) void mbt_kernel(
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5, pl = lane & 31;
-    const int unit = xcd_remap ? mt_xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int unit = xcd_remap ? xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int tq = unit / tilesX;
     const int tx = unit - tq * tilesX;
     const int n = tq / tilesY;
@@ -322,9 +313,7 @@ constexpr int MS_RS = 42;                                 // cells per strip row
 constexpr int MS_PAIR = 22 * MS_RS * 2 + 4;               // floats per channel pair: 463 sixteen-byte slots (odd)
 constexpr int MS_E_FLOATS = 16 * MS_PAIR;
 
-template <int CK, int NMT> struct MSW : MTW<CK, NMT> {
-    static constexpr size_t LDS_BYTES = (size_t)MS_E_FLOATS * 4 + (size_t)(MTW<CK, NMT>::NTOT + MTW<CK, NMT>::N4) * 16;
-};
+template <int CK, int NMT> using MSW = StageLayout<CK, NMT, 3, 512, (size_t)MS_E_FLOATS * 4>;   // MTW behind the strip's tile
 
 template <int CK, int NMT, bool RES, int ROWS>
 __global__ __launch_bounds__(512, 2) void mbt_kernel(
@@ -340,7 +329,7 @@ __global__ __launch_bounds__(512, 2) void mbt_kernel(
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5, pl = lane & 31;
-    const int unit = xcd_remap ? mt_xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int unit = xcd_remap ? xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int n = unit / stripsY;
     const int y0 = (unit - n * stripsY) * 16;
     const long HW = (long)H * W;
@@ -596,12 +585,7 @@ constexpr int S2_CELLS = S2_ROWS * S2_COLS;               // 777
 constexpr int S2_NG = (S2_CELLS + 31) / 32;               // 25 groups of 32 cells
 constexpr int S2_GPW = (S2_NG + 7) / 8;                   // groups per wave (4; only wave 0 has a fourth)
 
-template <int CK, int NMT> struct S2W {
-    static constexpr int N1 = CK * 3 * 64, N2 = NMT * 2 * 3 * 64, N3 = 64, N4 = 16 * 28;
-    static constexpr int NTOT = N1 + N2 + N3 + N4;
-    static constexpr int NLD = (NTOT + 511) / 512;
-    static constexpr size_t LDS_BYTES = (size_t)S2_E_FLOATS * 4 + (size_t)(NTOT + N4) * 16;
-};
+template <int CK, int NMT> using S2W = StageLayout<CK, NMT, 3, 512, (size_t)S2_E_FLOATS * 4>;
 
 template <int CK, int NMT>
 __global__ __launch_bounds__(512, 2) void mbt_s2_kernel(
@@ -619,7 +603,7 @@ __global__ __launch_bounds__(512, 2) void mbt_s2_kernel(
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5, pl = lane & 31;
-    const int unit = xcd_remap ? mt_xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int unit = xcd_remap ? xcd_contiguous_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int tq = unit / tilesX;
     const int tx = unit - tq * tilesX;
     const int n = tq / tilesY;
@@ -848,36 +832,26 @@ __global__ __launch_bounds__(512, 2) void mbt_s2_kernel(
 }
 
 template <int CK, int NMT>
-static void launch_mbt_s2_t(const float* x, const void* w1s, const float* b1f, const void* wrow, const void* w2s,
+static bool launch_mbt_s2_t(const float* x, const void* w1s, const float* b1f, const void* wrow, const void* w2s,
                             const float* b2f, float* out, int N, int Cexp, int Cout, int H, int W, int xcd,
                             hipStream_t s) {
     const size_t lds = S2W<CK, NMT>::LDS_BYTES;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mbt_s2_kernel<CK, NMT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (!kernel_ready((const void*)mbt_s2_kernel<CK, NMT>, lds)) return false;
     const int OH = H / 2, OW = W / 2;
     const int tilesX = (OW + 15) / 16, tilesY = (OH + 7) / 8;
     LP_LAUNCH((mbt_s2_kernel<CK, NMT>), dim3(N * tilesX * tilesY), dim3(512), lds, s, x, (const u32x4*)w1s,
                        b1f, (const f32x4*)wrow, (const u32x4*)w2s, b2f, out, Cexp, Cout, H, W, OH, OW, tilesX, tilesY,
                        xcd);
+    return true;
 }
 
 template <int CK, int NMT>
-static void launch_mbt_t(const float* x, const void* w1s, const float* b1f, const void* wrow, const void* w2s,
+static bool launch_mbt_t(const float* x, const void* w1s, const float* b1f, const void* wrow, const void* w2s,
                          const float* b2f, bool res, float* out, int N, int Cexp, int Cout, int H, int W,
                          int xcd, hipStream_t s) {
     const size_t lds = MTW<CK, NMT>::LDS_BYTES;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mbt_kernel<CK, NMT, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mbt_kernel<CK, NMT, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (!kernel_ready(res ? (const void*)mbt_kernel<CK, NMT, true> : (const void*)mbt_kernel<CK, NMT, false>, lds))
+        return false;
     const int tilesX = (W + 15) / 16, tilesY = (H + 15) / 16;
     const dim3 grid(N * tilesX * tilesY);
     if (res)
@@ -886,22 +860,17 @@ static void launch_mbt_t(const float* x, const void* w1s, const float* b1f, cons
     else
         LP_LAUNCH((mbt_kernel<CK, NMT, false>), grid, dim3(512), lds, s, x, (const u32x4*)w1s, b1f,
                            (const f32x4*)wrow, (const u32x4*)w2s, b2f, out, Cexp, Cout, H, W, tilesX, tilesY, xcd);
+    return true;
 }
 
 template <int CK, int NMT>
-static void launch_mbt_strip_t(const float* x, const void* w1s, const float* b1f, const void* wrow, const void* w2s,
+static bool launch_mbt_strip_t(const float* x, const void* w1s, const float* b1f, const void* wrow, const void* w2s,
                                const float* b2f, bool res, float* out, int N, int Cexp, int Cout, int H, int xcd,
                                hipStream_t s) {
     const size_t lds = MSW<CK, NMT>::LDS_BYTES;
     static_assert(MSW<CK, NMT>::LDS_BYTES <= 160 * 1024, "the strip form's E tile and weight stage must fit the CU's LDS");
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mbt_kernel<CK, NMT, true, 16>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mbt_kernel<CK, NMT, false, 16>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (!kernel_ready(res ? (const void*)mbt_kernel<CK, NMT, true, 16> : (const void*)mbt_kernel<CK, NMT, false, 16>, lds))
+        return false;
     const int stripsY = (H + 15) / 16;
     const dim3 grid(N * stripsY);
     if (res)
@@ -910,6 +879,7 @@ static void launch_mbt_strip_t(const float* x, const void* w1s, const float* b1f
     else
         LP_LAUNCH((mbt_kernel<CK, NMT, false, 16>), grid, dim3(512), lds, s, x, (const u32x4*)w1s, b1f,
                            (const f32x4*)wrow, (const u32x4*)w2s, b2f, out, Cexp, Cout, H, stripsY, xcd);
+    return true;
 }
 
 // CUs of the current device: the default rule of option "mbt_strip" takes strips when they fill the chip in one round
@@ -975,32 +945,21 @@ bool launch_mbt(const float* x, const void* w1s, const float* b1f, const void* w
     if (f.kind == MBT_S2) {
         last_kernel_tag = "mbt_s2_kernel";
 #define LP_GO2(CKV, NMTV)                                                                                   \
-        if (f.CK == CKV && f.NMT == NMTV) {                                                                 \
-            if (uses_scratch((const void*)mbt_s2_kernel<CKV, NMTV>)) return false;                          \
-            launch_mbt_s2_t<CKV, NMTV>(x, w1s, b1f, wrow, w2s, b2f, out, N, Cexp, Cout, H, W, xcd, s);      \
-            return true;                                                                                    \
-        }
+        if (f.CK == CKV && f.NMT == NMTV)                                                                   \
+            return launch_mbt_s2_t<CKV, NMTV>(x, w1s, b1f, wrow, w2s, b2f, out, N, Cexp, Cout, H, W, xcd, s);
         LP_GO2(1, 1) LP_GO2(1, 2) LP_GO2(2, 1) LP_GO2(2, 2)
 #undef LP_GO2
         return false;
     }
     last_kernel_tag = "mbt_kernel";
 #define LP_GO(CKV, NMTV)                                                                                   \
-    if (f.CK == CKV && f.NMT == NMTV) {                                                                    \
-        if (uses_scratch(res ? (const void*)mbt_kernel<CKV, NMTV, true> : (const void*)mbt_kernel<CKV, NMTV, false>)) \
-            return false;                                                                                  \
-        launch_mbt_t<CKV, NMTV>(x, w1s, b1f, wrow, w2s, b2f, res != nullptr, out, N, Cexp, Cout, H, W,     \
-                                xcd, s);                                                                   \
-        return true;                                                                                       \
-    }
+    if (f.CK == CKV && f.NMT == NMTV)                                                                      \
+        return launch_mbt_t<CKV, NMTV>(x, w1s, b1f, wrow, w2s, b2f, res != nullptr, out, N, Cexp, Cout, H, W, xcd, s);
     if (f.kind == MBT_STRIP) {                                       // a strip kernel that needs scratch: the tiles
 #define LP_GOS(CKV, NMTV)                                                                                  \
         if (f.CK == CKV && f.NMT == NMTV &&                                                                \
-            !uses_scratch(res ? (const void*)mbt_kernel<CKV, NMTV, true, 16>                               \
-                              : (const void*)mbt_kernel<CKV, NMTV, false, 16>)) {                          \
-            launch_mbt_strip_t<CKV, NMTV>(x, w1s, b1f, wrow, w2s, b2f, res != nullptr, out, N, Cexp, Cout, H, xcd, s); \
-            return true;                                                                                   \
-        }
+            launch_mbt_strip_t<CKV, NMTV>(x, w1s, b1f, wrow, w2s, b2f, res != nullptr, out, N, Cexp, Cout, H, xcd, s)) \
+            return true;
         LP_GOS(1, 1) LP_GOS(2, 1)
 #undef LP_GOS
     }

@@ -13,6 +13,7 @@
 // (InvBottleneck), :120-133 (SepConv2d); lib/models/pose_mobilenet.py:113-131,143-156
 // (Fusion Deconv Head).  BN is folded on the host (engine.cpp).
 #include "kernels.h"
+#include "fused_common.h"
 #include "split3.h"
 
 #include <cstdio>
@@ -39,19 +40,9 @@ void note_launch(const void* fn, dim3 grid, dim3 block, size_t lds) {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// tiles are dealt to workgroups XCD-contiguously (xcd_contiguous_id below); measured on every tiled kernel in rounds
+// tiles are dealt to workgroups XCD-contiguously (xcd_contiguous_id, fused_common.h); measured on every tiled kernel in rounds
 // 1-3, the hardware order never won
 static constexpr int xcd_remap_mode() { return 1; }
-
-// Workgroups are dealt to the 8 XCDs round-robin (id % 8) and every XCD has its own L2.  Tile kernels
-// whose neighbouring tiles share halo rows / cache lines therefore remap the hardware id so that
-// CONSECUTIVE logical tiles run on the SAME XCD (ids 8 apart, dispatched back to back) and their shared
-// lines are L2 hits instead of a second fabric fetch.  Bijection on [0, n).
-__device__ __forceinline__ int xcd_contiguous_id(int id, int n) {
-    const int q = n >> 3, r = n & 7;
-    const int xcd = id & 7, slot = id >> 3;
-    return xcd * q + min(xcd, r) + slot;
-}
 
 // The bounds of ACT_NONE in the branch-free clamp fminf(fmaxf(v, lo), hi) of the planar 1x1 and depthwise launchers the
 // training layers call.  fmaxf / fminf are IEEE maxNum / minNum: they return the operand that is not a NaN, and a NaN only
@@ -806,13 +797,14 @@ __global__ __launch_bounds__(256) void pw2_kernel(const float* __restrict__ inA,
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-template <int NB, int PXV, bool RES>
+template <int PXV, bool RES>
 __global__ __launch_bounds__(256) void pw3_kernel(const float* __restrict__ inA, int C,
                                                   const u32x4* __restrict__ wsp,   // [cb][ks][3][64] x4 dw
                                                   const float* __restrict__ bias,
                                                   const float* __restrict__ res,
                                                   float* __restrict__ out, long NG, int HWV, int HW,
                                                   int Cout, int act) {
+    constexpr int NB = 1;                                  // channel blocks of 32 per wave: most waves, shortest chains
     typedef typename PxVec<PXV>::type vec_t;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -938,10 +930,11 @@ __global__ __launch_bounds__(256) void pw3_kernel(const float* __restrict__ inA,
 // waves, shortest chain).  Same fragments, same six products per k-step in the same order, k-steps in the same order:
 // bit-identical to pw3_kernel (and so to mb16_kernel), which a GPU test asserts -- the parity protocol's P4 (a batched run
 // equals the per-image runs bit for bit) does not depend on which of the two a launch takes.
-template <int NB, int PXV, bool RES, int D>
+template <bool RES>
 __global__ __launch_bounds__(256) void pw3d_kernel(const float* __restrict__ inA, int C, const u32x4* __restrict__ wsp,
                                                    const float* __restrict__ bias, const float* __restrict__ res,
                                                    float* __restrict__ out, long NG, int HWV, int HW, int Cout, int act) {
+    constexpr int NB = 1, PXV = 1, D = 4;                  // one channel block, 32 pixels per wave, loads 4 k-steps ahead
     typedef typename PxVec<PXV>::type vec_t;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -1054,33 +1047,28 @@ __global__ __launch_bounds__(256) void pw3d_kernel(const float* __restrict__ inA
     }
 }
 
-template <int NB, int PXV, int D>
-static void launch_pw3d_t(const float* inA, int C, const void* wsp, const float* b, const float* res,
-                          float* out, long NP, int HW, int Cout, int act, hipStream_t s) {
-    const long NG = NP / PXV;
-    const int cblocks = (Cout + 31) / 32;
-    dim3 grid((unsigned)((NG + 127) / 128), (cblocks + NB - 1) / NB), block(256);
+// both bf16x3 forms: one workgroup = 4 waves x 32 pixel groups, one 32-channel block per wave (grid.y = the blocks)
+static void launch_pw3d(const float* inA, int C, const void* wsp, const float* b, const float* res,
+                        float* out, long NP, int HW, int Cout, int act, hipStream_t s) {
+    dim3 grid((unsigned)((NP + 127) / 128), (Cout + 31) / 32), block(256);
     last_kernel_tag = "pw3d_kernel";
     if (res)
-        LP_LAUNCH((pw3d_kernel<NB, PXV, true, D>), grid, block, 0, s, inA, C, (const u32x4*)wsp, b, res, out, NG, HW / PXV, HW,
-                  Cout, act);
+        LP_LAUNCH(pw3d_kernel<true>, grid, block, 0, s, inA, C, (const u32x4*)wsp, b, res, out, NP, HW, HW, Cout, act);
     else
-        LP_LAUNCH((pw3d_kernel<NB, PXV, false, D>), grid, block, 0, s, inA, C, (const u32x4*)wsp, b, res, out, NG, HW / PXV, HW,
-                  Cout, act);
+        LP_LAUNCH(pw3d_kernel<false>, grid, block, 0, s, inA, C, (const u32x4*)wsp, b, res, out, NP, HW, HW, Cout, act);
 }
 
-template <int NB, int PXV>
+template <int PXV>
 static void launch_pw3_t(const float* inA, int C, const void* wsp, const float* b, const float* res,
                          float* out, long NP, int HW, int Cout, int act, hipStream_t s) {
     const long NG = NP / PXV;
-    const int cblocks = (Cout + 31) / 32;
-    dim3 grid((unsigned)((NG + 127) / 128), (cblocks + NB - 1) / NB), block(256);
+    dim3 grid((unsigned)((NG + 127) / 128), (Cout + 31) / 32), block(256);
     last_kernel_tag = "pw3_kernel";
     if (res)
-        LP_LAUNCH((pw3_kernel<NB, PXV, true>), grid, block, 0, s, inA, C, (const u32x4*)wsp, b, res,
+        LP_LAUNCH((pw3_kernel<PXV, true>), grid, block, 0, s, inA, C, (const u32x4*)wsp, b, res,
                            out, NG, HW / PXV, HW, Cout, act);
     else
-        LP_LAUNCH((pw3_kernel<NB, PXV, false>), grid, block, 0, s, inA, C, (const u32x4*)wsp, b, res,
+        LP_LAUNCH((pw3_kernel<PXV, false>), grid, block, 0, s, inA, C, (const u32x4*)wsp, b, res,
                            out, NG, HW / PXV, HW, Cout, act);
 }
 
@@ -1153,12 +1141,12 @@ void launch_pw(const float* inA, int Ca, const float* inB, int Cb, const float* 
             // option "pw3d": small launches (<= 8192 pixels: 16 images of a 16x16 plane) take the deep-prefetch form, which is
             // bit-identical (1 = by that rule, 2 = always, 0 = never)
             if (pw3d_mode == 2 || (pw3d_mode == 1 && NP <= 8192)) {
-                launch_pw3d_t<1, 1, 4>(inA, Ca, wsplit, b, res, out, NP, HW, Cout, act, s);
+                launch_pw3d(inA, Ca, wsplit, b, res, out, NP, HW, Cout, act, s);
                 return;
             }
             const int pxv3 = (cblocks <= 3 || Ca < 64) ? 2 : 4;
-            if (pxv3 == 2) launch_pw3_t<1, 2>(inA, Ca, wsplit, b, res, out, NP, HW, Cout, act, s);
-            else launch_pw3_t<1, 4>(inA, Ca, wsplit, b, res, out, NP, HW, Cout, act, s);
+            if (pxv3 == 2) launch_pw3_t<2>(inA, Ca, wsplit, b, res, out, NP, HW, Cout, act, s);
+            else launch_pw3_t<4>(inA, Ca, wsplit, b, res, out, NP, HW, Cout, act, s);
             return;
         }
     }
@@ -1536,7 +1524,7 @@ __device__ __forceinline__ int quad_row_of_lane(int lane) {
     return (int)((0xFDCE5764B98A1320ull >> (4 * (lane >> 2))) & 15);
 }
 
-template <int K, int NB, bool ALLPF, bool DUAL>
+template <int NB, bool DUAL>
 __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__ inA, int Ca,
                                                        const float* __restrict__ inB, int Cb,
                                                        const float* __restrict__ wpairA,   // [Ca/2][K*K + 1][2] taps, bias
@@ -1544,6 +1532,7 @@ __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__
                                                        const float* __restrict__ wp,       // A frags [cblocks][C/2][64]
                                                        float* __restrict__ out, int H, int W, int tilesX, int tilesY,
                                                        int Cout, int xcd_remap) {
+    constexpr int K = 5;                                  // both heads of every published network: SepConv2d(k5)
     constexpr int HALO = K / 2;
     constexpr int IH = 16 + K - 1;                        // input rows per tile
     constexpr int QPR = 6;                                // float4 staged per row and channel: columns -4 .. 19
@@ -1588,14 +1577,10 @@ __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__
 #pragma unroll
         for (int kp = 0; kp < 32; ++kp)
             afr[i][kp] = wp[((long)min(i, cblocks - 1) * KP + min(kp, KP - 1)) * 64 + lane];
-    // ALLPF: ALL of this wave's channel pairs (<= 8) are requested up front; otherwise one pair ahead of the FMAs.
-    // Round 5: with the ring slab FOUR workgroups fit a CU (33 KB of LDS, 88 + 34 registers in the one-pair-ahead form;
-    // ALLPF needs 180 + 34: two per CU), and sixteen resident waves hide the loads better than eight waves with everything
-    // in flight: 0.300 -> 0.233 ms per forward (two launches), step 2.90 -> 2.85 ms, bit-identical (gpurun r5m; round 2's
-    // +9 % for ALLPF was measured at two workgroups per CU either way).  ALLPF = true is no longer instantiated.
-    constexpr int NPW = ALLPF ? 8 : 1;
-    f32x4 pre[NPW][2][NLD];
-    auto issue = [&](int cp, int u) {                      // channel pair cp of the concatenated sources -> slot u
+    // The halo tiles are requested ONE channel pair ahead of the FMAs: with the ring slab four workgroups fit a CU (33 KB of
+    // LDS, 88 + 34 registers), and sixteen resident waves hide the loads better than fewer waves with more in flight
+    f32x4 pre[2][NLD];
+    auto issue = [&](int cp) {                             // channel pair cp of the concatenated sources -> pre
         const int c = 2 * cp;
         const float* plane = (!DUAL || c < Ca) ? imgA + (long)c * HW : imgB + (long)(c - Ca) * HW;
 #pragma unroll
@@ -1604,16 +1589,10 @@ __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__
             for (int i = 0; i < NLD; ++i) {
                 f32x4 v = *reinterpret_cast<const f32x4*>(plane + h2 * HW + max(st_off[i], 0));
                 if (st_off[i] < 0) v = f32x4{0.f, 0.f, 0.f, 0.f};
-                pre[u][h2][i] = v;
+                pre[h2][i] = v;
             }
     };
-    if (ALLPF) {
-#pragma unroll
-        for (int u = 0; u < NPW; ++u)
-            if (wave + 4 * u < KP) issue(wave + 4 * u, u);
-    } else {
-        issue(wave, 0);
-    }
+    issue(wave);
     // Rounds: in round u wave w runs the depthwise of channel pair 4u + w and parks it in the slab; a workgroup barrier
     // later the four k-pairs of that round are complete for all 256 pixels.  Their 1x1 MFMAs are NOT issued as one
     // block at the end (a wave issues in order: 40 back-to-back 64-cycle MFMAs were a quarter of the kernel with the
@@ -1640,7 +1619,6 @@ __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__
         if (u >= NR) break;                                // workgroup-uniform
         const int cp = wave + 4 * u;
         const bool has = cp < KP;                          // wave-uniform
-        const int us = ALLPF ? u : 0;
         const int c = 2 * cp;
         f32x2 dacc[4];
         f32x2 dbias = {0.f, 0.f};
@@ -1650,14 +1628,14 @@ __global__ __launch_bounds__(256) void headfuse_kernel(const float* __restrict__
 #pragma unroll
             for (int i = 0; i < NLD; ++i)
                 if (st_lds[i] >= 0) {
-                    const f32x4 a = pre[us][0][i], b = pre[us][1][i];
+                    const f32x4 a = pre[0][i], b = pre[1][i];
                     tile[st_lds[i]] = f32x4{a[0], b[0], a[1], b[1]};
                     tile[st_lds[i] + 1] = f32x4{a[2], b[2], a[3], b[3]};
                 }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (!ALLPF && cp + 4 < KP) issue(cp + 4, 0);
+            if (cp + 4 < KP) issue(cp + 4);
             wc = (!DUAL || c < Ca) ? wpairA + (long)cp * (K * K + 1) * 2 : wpairB + (long)(cp - (Ca >> 1)) * (K * K + 1) * 2;
             dbias = f32x2{wc[2 * K * K], wc[2 * K * K + 1]};                                    // bias pair
 #pragma unroll
@@ -1742,7 +1720,7 @@ bool launch_headfuse(const float* inA, int Ca, const float* inB, int Cb, const f
     static_assert((16 * 256 + 4 * (16 + 5 - 1) * 13 * 4) * sizeof(float) <= 64 * 1024,
                   "33 KB: below the default dynamic-LDS limit, no per-device attribute call needed (ADVICE r05)");
     last_kernel_tag = "headfuse_kernel";
-#define LP_HF(NBV, DV) LP_LAUNCH((headfuse_kernel<5, NBV, false, DV>), dim3(grid), dim3(256), lds, s, inA, Ca, inB, Cb, \
+#define LP_HF(NBV, DV) LP_LAUNCH((headfuse_kernel<NBV, DV>), dim3(grid), dim3(256), lds, s, inA, Ca, inB, Cb, \
                                  wpairA, wpairB, wp, out, H, W, tilesX, tilesY, Cout, xcd_remap_mode())
     if (dual) { if (Cout <= 32) LP_HF(1, true); else LP_HF(2, true); }
     else { if (Cout <= 32) LP_HF(1, false); else LP_HF(2, false); }
@@ -1782,11 +1760,9 @@ __device__ __forceinline__ int mb2_row_of_lane(int lane) {
     return (int)((0xFDCE5764B98A1320ull >> (4 * (lane >> 2))) & 15);
 }
 
-template <bool RES, int KP1, bool X3, bool WL>
+template <bool RES>
 __global__ __launch_bounds__(256, 2) void mbconv_kernel(
     const float* __restrict__ x,        // [N, Cin, H, W]
-    const f32x4* __restrict__ wrow,     // WL: depthwise weights as pair rows [Cexp/2][7][7 taps x 2 ch, bias pair in row 0's pad]
-    const u32x4* __restrict__ w1s,      // X3: expand weights as bf16x3 A fragments [Cexp/32][Cin/16][3][64]
     const float* __restrict__ w1p,      // expand A frags [Cexp/32][Cin/2][64]
     const float* __restrict__ b1f,      // expand bias, D-frag order [Cexp/32][2][16]
     const float* __restrict__ wdwp,     // depthwise weights, channel-pair interleaved [Cexp/2][49][2]
@@ -1821,7 +1797,6 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(
     // ---- depthwise geometry --------------------------------------------------------------
     const int drow = mb2_row_of_lane(lane), strip = lane & 3;
     const float* e_lane = E + (drow * MB2_RS + strip * 4) * 2;   // + pair*MB2_PAIR + ky*MB2_RS*2
-    float* Wd = E + 16 * MB2_PAIR + wave * 448;                  // WL: [4 pairs][7 rows][16 floats] of this wave
 
     f32x16 acc[2][4];
 #pragma unroll
@@ -1834,9 +1809,8 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(
     // ---- the x halo tile of this wave's cell groups, loaded ONCE: every 32-channel chunk of the
     //      expand re-uses it (it used to be re-fetched per chunk: 3x the loads and their latency)
     constexpr int NGW = (NG + 3) / 4;                          // groups per wave (4)
-    constexpr int KS1 = X3 ? KP1 / 8 : 1;                      // X3: k-steps of 16 input channels
-    float xv[X3 ? 1 : NGW][X3 ? 1 : KP1];
-    u32x4 xh[X3 ? NGW : 1][KS1], xm[X3 ? NGW : 1][KS1], xl[X3 ? NGW : 1][KS1];
+    constexpr int KP1 = 12;                                    // input channel pairs: Cin = 24 (fp32 expand, 32x32x2 MFMAs)
+    float xv[NGW][KP1];
     bool xok[NGW];
 #pragma unroll
     for (int gi = 0; gi < NGW; ++gi) {
@@ -1845,59 +1819,20 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(
         const int hy = hp0 / NCOL, hx = 1 + hp0 - hy * NCOL;
         const int yy = y0 - 3 + hy, xx = x0 - 4 + hx;
         xok[gi] = g < NG && hp0 < CELLS && yy >= 0 && yy < H && xx >= 0 && xx < W;
-        if constexpr (X3) {
-            // bf16x3 B fragments: channels 16ks + 8*half + 0..7 of this halo cell, split ONCE per tile
-            const float* sp = xin + (long)(8 * half) * HW + (xok[gi] ? yy * W + xx : 0);
+        const float* sp = xin + (long)half * HW + (xok[gi] ? yy * W + xx : 0);
 #pragma unroll
-            for (int ks = 0; ks < KS1; ++ks) {
-                float v[8];
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const float t = sp[(long)(16 * ks + c) * HW];
-                    v[c] = xok[gi] ? t : 0.f;
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const Split3 p3 = split3_pair(v[2 * j], v[2 * j + 1]);
-                    xh[gi][ks][j] = p3.h; xm[gi][ks][j] = p3.m; xl[gi][ks][j] = p3.l;
-                }
-            }
-        } else {
-            const float* sp = xin + (long)half * HW + (xok[gi] ? yy * W + xx : 0);
-#pragma unroll
-            for (int kp = 0; kp < KP1; ++kp) {
-                const float t = sp[(long)(2 * kp) * HW];
-                xv[gi][kp] = xok[gi] ? t : 0.f;
-            }
+        for (int kp = 0; kp < KP1; ++kp) {
+            const float t = sp[(long)(2 * kp) * HW];
+            xv[gi][kp] = xok[gi] ? t : 0.f;
         }
     }
 
     for (int ch = 0; ch < nchunks; ++ch) {
-        // WL: the 49 x 2 depthwise weights (+ bias pair) of this wave's four channel pairs go through a
-        // wave-private LDS stage and are read back as broadcast VGPR operands: as SGPR operands every filter
-        // row cost one scalar-cache miss (s_load + s_waitcnt, 300-600 cycles; 100 per tile)
-        f32x4 wld[2];
-        if constexpr (WL) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int e = lane + 64 * j;
-                const int u = e / 28, r = e - u * 28;
-                if (e < 112) wld[j] = wrow[((long)(ch * 16 + wave + 4 * u)) * 28 + r];
-            }
-        }
         // ================= expand: E = relu6(W1[chunk] . x + b1) on the halo tile =========
         {
-            float a1[X3 ? 1 : KP1];
-            u32x4 a3[KS1][3];
-            if constexpr (X3) {
+            float a1[KP1];
 #pragma unroll
-                for (int ks = 0; ks < KS1; ++ks)
-#pragma unroll
-                    for (int t = 0; t < 3; ++t) a3[ks][t] = w1s[(((long)ch * KS1 + ks) * 3 + t) * 64 + lane];
-            } else {
-#pragma unroll
-                for (int kp = 0; kp < KP1; ++kp) a1[kp] = w1p[((long)ch * KP1 + kp) * 64 + lane];
-            }
+            for (int kp = 0; kp < KP1; ++kp) a1[kp] = w1p[((long)ch * KP1 + kp) * 64 + lane];
             const f32x4* bp = reinterpret_cast<const f32x4*>(b1f + ((long)ch * 2 + half) * 16);
             f32x4 b1v[4];
 #pragma unroll
@@ -1909,15 +1844,8 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(
                 f32x16 d;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) d[r] = 0.f;
-                if constexpr (X3) {
-                    // exact bf16x3 form: 6 bf16 MFMAs per 16 input channels instead of 8 fp32 ones (2.67x)
 #pragma unroll
-                    for (int ks = 0; ks < KS1; ++ks) d = mma6(a3[ks], xh[gi][ks], xm[gi][ks], xl[gi][ks], d);
-                } else {
-#pragma unroll
-                    for (int kp = 0; kp < KP1; ++kp)
-                        d = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[kp], xv[gi][kp], d, 0, 0, 0);
-                }
+                for (int kp = 0; kp < KP1; ++kp) d = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[kp], xv[gi][kp], d, 0, 0, 0);
                 const int hp = g * 32 + pl;
                 if (hp < CELLS) {
                     const int hy = hp / NCOL, hx = 1 + hp - hy * NCOL;
@@ -1932,11 +1860,6 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(
                     }
                 }
             }
-        }
-        if constexpr (WL) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                if (lane + 64 * j < 112) reinterpret_cast<f32x4*>(Wd)[lane + 64 * j] = wld[j];
         }
         __syncthreads();
         // ================= depthwise pairs -> permlane swap -> project MFMAs ================
@@ -1955,23 +1878,13 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(
                 f32x2 a4[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
                 // the next row's six ds_read_b128 are issued before this row's 28 packed FMAs
                 f32x4 rn[6], rc[6];
-                const f32x4* wl = reinterpret_cast<const f32x4*>(Wd) + u * 28;
-                f32x4 wr[4];                                        // WL: this row's taps (no second buffer: the
-                                                                    // kernel is register-bound, two waves per SIMD
-                                                                    // cover the ~100-cycle LDS latency)
 #pragma unroll
                 for (int q = 0; q < 6; ++q) rn[q] = *reinterpret_cast<const f32x4*>(ep + 4 * q);
                 keep_b128(rn[0]); keep_b128(rn[5]);                 // half-used outer slots stay ds_read_b128 (split3.h)
-                float wb0 = 0.f, wb1 = 0.f;
 #pragma unroll
                 for (int ky = 0; ky < 7; ++ky) {
 #pragma unroll
                     for (int q = 0; q < 6; ++q) rc[q] = rn[q];
-                    if constexpr (WL) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) wr[q] = wl[ky * 4 + q];
-                        if (ky == 0) { wb0 = wr[3][2]; wb1 = wr[3][3]; }
-                    }
                     if (ky < 6) {
 #pragma unroll
                         for (int q = 0; q < 6; ++q)
@@ -1986,14 +1899,12 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(
                     }
 #pragma unroll
                     for (int kx = 0; kx < 7; ++kx) {
-                        f32x2 w2;
-                        if constexpr (WL) w2 = f32x2{wr[kx >> 1][2 * (kx & 1)], wr[kx >> 1][2 * (kx & 1) + 1]};
-                        else w2 = wc[ky * 7 + kx];
+                        const f32x2 w2 = wc[ky * 7 + kx];           // wave-uniform: an SGPR pair
 #pragma unroll
                         for (int i = 0; i < 4; ++i) a4[i] = __builtin_elementwise_fma(P[1 + kx + i], w2, a4[i]);
                     }
                 }
-                const float b0 = WL ? wb0 : bdw[c], b1 = WL ? wb1 : bdw[c + 1];
+                const float b0 = bdw[c], b1 = bdw[c + 1];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     res2[0][i] = fminf(fmaxf(a4[i][0] + b0, 0.f), 6.f);
@@ -2076,7 +1987,7 @@ __device__ __forceinline__ int mb3_rp_of_quad(int q) {
     return (int)((0x6732673245104510ull >> (4 * q)) & 15);
 }
 
-template <bool RES, int KP1, int NBLK>
+template <bool RES>
 __global__ __launch_bounds__(256, 2) void mbconv2_kernel(
     const float* __restrict__ x,        // [N, Cin, H, W]
     const f32x4* __restrict__ wrow,     // depthwise filter rows [Cexp/2][7][7 taps x 2 ch, bias pair in row 0's pad]
@@ -2101,7 +2012,9 @@ __global__ __launch_bounds__(256, 2) void mbconv2_kernel(
     const int nchunks = Cexp >> 5;
 
     constexpr int NCOL = 22, CELLS = MB_ROWS * NCOL;
-    constexpr int NG = (CELLS + 31) / 32, NGW = (NG + 3) / 4, KS1 = KP1 / 8;
+    constexpr int NG = (CELLS + 31) / 32, NGW = (NG + 3) / 4;
+    constexpr int KS1 = 1;                                       // k-steps of 16 input channels: Cin = 16
+    constexpr int NBLK = 1;                                      // blocks of 16 filters: Cout <= 16
     // ---- depthwise geometry ------------------------------------------------------------------
     const int dwq = lane >> 2, strip = lane & 3;
     const int dwpair = (dwq >> 2) & 1;
@@ -2324,11 +2237,12 @@ __global__ __launch_bounds__(256, 2) void mbconv2_kernel(
 // B operands of the two 32-pixel halves, and the four waves' K-slices are summed through LDS.
 // The 6x expanded tensor of the block (the largest tensor of the network) never leaves the CU.
 // -------------------------------------------------------------------------------------
-template <int KP1, bool X3, bool WL>
 __global__ __launch_bounds__(256, 2) void mbconv_s2_kernel(
     const float* __restrict__ x,        // [N, Cin, H, W]
-    const f32x4* __restrict__ wrow,     // WL: depthwise weights as pair rows [Cexp/2][7][7 taps x 2 ch, bias pair in row 0's pad]
-    const u32x4* __restrict__ w1s,      // X3: expand weights as bf16x3 A fragments [Cexp/32][Cin/16][3][64]
+    const void*, const void*,           // two unused slots, always null: this kernel keeps more scalars live than there are
+                                        // SGPRs, and where its other arguments sit in the kernarg segment decides how their
+                                        // loads merge and which scalars spill to VGPR lanes -- without the slots the same
+                                        // vector work comes with six more lane moves
     const float* __restrict__ w1p,      // expand A frags [Cexp/32][Cin/2][64]
     const float* __restrict__ b1f,      // expand bias, D-frag order [Cexp/32][2][16]
     const float* __restrict__ wdwp,     // depthwise weights, channel-pair interleaved [Cexp/2][49][2]
@@ -2360,7 +2274,6 @@ __global__ __launch_bounds__(256, 2) void mbconv_s2_kernel(
     constexpr int NGW = (NG + 3) / 4;                          // groups per wave (4)
     const int orow = lane >> 3, ocol = lane & 7;               // this lane's output inside the tile
     const float* e_lane = E + ((2 * orow) * MB_RS + 2 * ocol) * 2;   // + pair*1056 + ky*48; taps at cells 1..7
-    float* Wd = E + 32 * MB_PLANE + wave * 448;                      // WL: [4 pairs][7 rows][16 floats] of this wave
 
     f32x16 acc[2];                                             // pixels 0-31 / 32-63 of the tile
 #pragma unroll
@@ -2369,9 +2282,8 @@ __global__ __launch_bounds__(256, 2) void mbconv_s2_kernel(
         for (int r = 0; r < 16; ++r) acc[h][r] = 0.f;
 
     // the x halo tile of this wave's cell groups, loaded once for all expand chunks
-    constexpr int KS1 = X3 ? KP1 / 8 : 1;                      // X3: k-steps of 16 input channels
-    float xv[X3 ? 1 : NGW][X3 ? 1 : KP1];
-    u32x4 xh[X3 ? NGW : 1][KS1], xm[X3 ? NGW : 1][KS1], xl[X3 ? NGW : 1][KS1];
+    constexpr int KP1 = 12;                                    // input channel pairs: Cin = 24 (fp32 expand, 32x32x2 MFMAs)
+    float xv[NGW][KP1];
     bool xok[NGW];
 #pragma unroll
     for (int gi = 0; gi < NGW; ++gi) {
@@ -2380,59 +2292,20 @@ __global__ __launch_bounds__(256, 2) void mbconv_s2_kernel(
         const int hy = hp0 / NCOL, hx = 1 + hp0 - hy * NCOL;
         const int yy = y0 - 3 + hy, xx = x0 - 4 + hx;
         xok[gi] = g < NG && hp0 < CELLS && yy >= 0 && yy < H && xx >= 0 && xx < W;
-        if constexpr (X3) {
-            // bf16x3 B fragments: channels 16ks + 8*half + 0..7 of this halo cell, split ONCE per tile
-            const float* sp = xin + (long)(8 * half) * HW + (xok[gi] ? yy * W + xx : 0);
+        const float* sp = xin + (long)half * HW + (xok[gi] ? yy * W + xx : 0);
 #pragma unroll
-            for (int ks = 0; ks < KS1; ++ks) {
-                float v[8];
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const float t = sp[(long)(16 * ks + c) * HW];
-                    v[c] = xok[gi] ? t : 0.f;
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const Split3 p3 = split3_pair(v[2 * j], v[2 * j + 1]);
-                    xh[gi][ks][j] = p3.h; xm[gi][ks][j] = p3.m; xl[gi][ks][j] = p3.l;
-                }
-            }
-        } else {
-            const float* sp = xin + (long)half * HW + (xok[gi] ? yy * W + xx : 0);
-#pragma unroll
-            for (int kp = 0; kp < KP1; ++kp) {
-                const float t = sp[(long)(2 * kp) * HW];
-                xv[gi][kp] = xok[gi] ? t : 0.f;
-            }
+        for (int kp = 0; kp < KP1; ++kp) {
+            const float t = sp[(long)(2 * kp) * HW];
+            xv[gi][kp] = xok[gi] ? t : 0.f;
         }
     }
 
     for (int ch = 0; ch < nchunks; ++ch) {
-        // WL: the 49 x 2 depthwise weights (+ bias pair) of this wave's four channel pairs go through a
-        // wave-private LDS stage and are read back as broadcast VGPR operands: as SGPR operands every filter
-        // row cost one scalar-cache miss (s_load + s_waitcnt, 300-600 cycles; 100 per tile)
-        f32x4 wld[2];
-        if constexpr (WL) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int e = lane + 64 * j;
-                const int u = e / 28, r = e - u * 28;
-                if (e < 112) wld[j] = wrow[((long)(ch * 16 + wave + 4 * u)) * 28 + r];
-            }
-        }
         // ================= expand: E = relu6(W1[chunk] . x + b1) on the halo tile =========
         {
-            float a1[X3 ? 1 : KP1];
-            u32x4 a3[KS1][3];
-            if constexpr (X3) {
+            float a1[KP1];
 #pragma unroll
-                for (int ks = 0; ks < KS1; ++ks)
-#pragma unroll
-                    for (int t = 0; t < 3; ++t) a3[ks][t] = w1s[(((long)ch * KS1 + ks) * 3 + t) * 64 + lane];
-            } else {
-#pragma unroll
-                for (int kp = 0; kp < KP1; ++kp) a1[kp] = w1p[((long)ch * KP1 + kp) * 64 + lane];
-            }
+            for (int kp = 0; kp < KP1; ++kp) a1[kp] = w1p[((long)ch * KP1 + kp) * 64 + lane];
             const f32x4* bp = reinterpret_cast<const f32x4*>(b1f + ((long)ch * 2 + half) * 16);
             f32x4 b1v[4];
 #pragma unroll
@@ -2444,15 +2317,8 @@ __global__ __launch_bounds__(256, 2) void mbconv_s2_kernel(
                 f32x16 d;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) d[r] = 0.f;
-                if constexpr (X3) {
-                    // exact bf16x3 form: 6 bf16 MFMAs per 16 input channels instead of 8 fp32 ones (2.67x)
 #pragma unroll
-                    for (int ks = 0; ks < KS1; ++ks) d = mma6(a3[ks], xh[gi][ks], xm[gi][ks], xl[gi][ks], d);
-                } else {
-#pragma unroll
-                    for (int kp = 0; kp < KP1; ++kp)
-                        d = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[kp], xv[gi][kp], d, 0, 0, 0);
-                }
+                for (int kp = 0; kp < KP1; ++kp) d = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[kp], xv[gi][kp], d, 0, 0, 0);
                 const int hp = g * 32 + pl;
                 if (hp < CELLS) {
                     const int hy = hp / NCOL, hx = 1 + hp - hy * NCOL;
@@ -2467,11 +2333,6 @@ __global__ __launch_bounds__(256, 2) void mbconv_s2_kernel(
                     }
                 }
             }
-        }
-        if constexpr (WL) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                if (lane + 64 * j < 112) reinterpret_cast<f32x4*>(Wd)[lane + 64 * j] = wld[j];
         }
         __syncthreads();
         // ================= stride-2 depthwise pairs -> permlane swap -> project MFMAs =========
@@ -2490,8 +2351,6 @@ __global__ __launch_bounds__(256, 2) void mbconv_s2_kernel(
                 const f32x2* wc = reinterpret_cast<const f32x2*>(wdwp) + (long)(c >> 1) * 49;
                 const float* ep = e_lane + kp * (2 * MB_PLANE);
                 f32x2 a = {0.f, 0.f};
-                const f32x4* wl = reinterpret_cast<const f32x4*>(Wd) + u * 28;
-                float wb0 = 0.f, wb1 = 0.f;
 #pragma unroll
                 for (int ky = 0; ky < 7; ++ky) {
                     f32x2 P[8];                                     // cells 0..7 of the row: (ch a, ch b)
@@ -2502,19 +2361,8 @@ __global__ __launch_bounds__(256, 2) void mbconv_s2_kernel(
                         P[2 * q] = f32x2{t[0], t[1]};
                         P[2 * q + 1] = f32x2{t[2], t[3]};
                     }
-                    f32x4 wr[4];
-                    if constexpr (WL) {
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) wr[q] = wl[ky * 4 + q];
-                        if (ky == 0) { wb0 = wr[3][2]; wb1 = wr[3][3]; }
-                    }
-#pragma unroll
-                    for (int kx = 0; kx < 7; ++kx) {
-                        f32x2 w2;
-                        if constexpr (WL) w2 = f32x2{wr[kx >> 1][2 * (kx & 1)], wr[kx >> 1][2 * (kx & 1) + 1]};
-                        else w2 = wc[ky * 7 + kx];
-                        a = __builtin_elementwise_fma(P[1 + kx], w2, a);
-                    }
+                    for (int kx = 0; kx < 7; ++kx) a = __builtin_elementwise_fma(P[1 + kx], wc[ky * 7 + kx], a);   // SGPR pair
                     if constexpr (pending) {
                         if (ky == 2) {
                             __builtin_amdgcn_sched_barrier(0);
@@ -2528,8 +2376,8 @@ __global__ __launch_bounds__(256, 2) void mbconv_s2_kernel(
                         }
                     }
                 }
-                res2[0] = fminf(fmaxf(a[0] + (WL ? wb0 : bdw[c]), 0.f), 6.f);
-                res2[1] = fminf(fmaxf(a[1] + (WL ? wb1 : bdw[c + 1]), 0.f), 6.f);
+                res2[0] = fminf(fmaxf(a[0] + bdw[c], 0.f), 6.f);
+                res2[1] = fminf(fmaxf(a[1] + bdw[c + 1], 0.f), 6.f);
             }
             // lanes 0-31 keep channel 2kp, lanes 32-63 receive channel 2kp+1 (and vice versa)
             const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(res2[0]), __float_as_uint(res2[1]),
@@ -2570,14 +2418,11 @@ __global__ __launch_bounds__(256, 2) void mbconv_s2_kernel(
     }
 }
 
-// Which variants of the three first-generation fused-block kernels are still launched (round 4 clean-up): the ones no
-// later kernel covers and that need no scratch --
-//   mbconv2_kernel<RES, 8, 1>              16-filter stride-1 blocks (stage 1 of XS / S)
-//   mbconv_kernel<RES, 12, false, false>   24-filter stride-1 blocks (stage 1 of M / L: Cin % 16 != 0, fp32 expand)
-//   mbconv_s2_kernel<12, false, false>     their stride-2 entry block
-// The 16- / 32-filter variants of mbconv_kernel and mbconv_s2_kernel, the LDS-tap (WL) forms and the 32-filter
-// mbconv2_kernel all spilled (20 - 460 bytes of scratch per lane) and were refused at run time since round 3
-// (DESIGN 5b); their blocks run in mbt_kernel / mbt_s2_kernel or as the unfused chain.  They are no longer built.
+// The three first-generation fused-block kernels serve the blocks no later kernel covers:
+//   mbconv2_kernel<RES>    16-channel stride-1 blocks of up to 16 filters (stage 1 of XS / S), bf16x3 expand
+//   mbconv_kernel<RES>     24-channel stride-1 blocks of up to 32 filters (stage 1 of M / L: Cin % 16 != 0, fp32 expand)
+//   mbconv_s2_kernel       the stride-2 entry block of those
+// Every other block shape runs in mbt_kernel / mbt_s2_kernel / mb16_kernel or as the unfused chain.
 static bool launch_mbconv_s2(const float* x, const float* w1p, const float* b1f, const float* wdwp, const float* bdw,
                              const float* w2p, const float* b2f, float* out, int N, int Cin, int Cexp, int Cout, int H,
                              int W, hipStream_t s) {
@@ -2588,16 +2433,9 @@ static bool launch_mbconv_s2(const float* x, const float* w1p, const float* b1f,
     const size_t lds = (size_t)(32 * MB_PLANE) * sizeof(float);
     dim3 grid(N * tilesX * tilesY), block(256);
     last_kernel_tag = "mbconv_s2_kernel";
-    if (uses_scratch(reinterpret_cast<const void*>(mbconv_s2_kernel<12, false, false>))) return false;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mbconv_s2_kernel<12, false, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
-    LP_LAUNCH((mbconv_s2_kernel<12, false, false>), grid, block, lds, s, x, (const f32x4*)nullptr,
-                       (const u32x4*)nullptr, w1p, b1f, wdwp, bdw, w2p, b2f, out, Cin, Cexp, Cout, H, W, OH, OW, tilesX,
-                       tilesY, xcd_remap_mode());
+    if (!kernel_ready(reinterpret_cast<const void*>(mbconv_s2_kernel), lds)) return false;
+    LP_LAUNCH(mbconv_s2_kernel, grid, block, lds, s, x, (const void*)nullptr, (const void*)nullptr, w1p, b1f, wdwp, bdw,
+              w2p, b2f, out, Cin, Cexp, Cout, H, W, OH, OW, tilesX, tilesY, xcd_remap_mode());
     return true;
 }
 
@@ -2619,40 +2457,18 @@ bool launch_mbconv(const float* x, const float* w1p, const float* b1f, const flo
         if (!mbconv2 || !wrow || !w1s || Cout > 16) return false;
         const size_t lds2 = (size_t)16 * MB3_PAIR * sizeof(float);
         last_kernel_tag = "mbconv2_kernel";
-#define LP_MB2(RESV)                                                                                       \
-        do {                                                                                               \
-            if (uses_scratch(reinterpret_cast<const void*>(mbconv2_kernel<RESV, 8, 1>))) return false;     \
-            static bool attr2_##RESV = false;                                                              \
-            if (!attr2_##RESV) {                                                                           \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mbconv2_kernel<RESV, 8, 1>),       \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);          \
-                attr2_##RESV = true;                                                                       \
-            }                                                                                              \
-            LP_LAUNCH((mbconv2_kernel<RESV, 8, 1>), grid, block, lds2, s, x, (const f32x4*)wrow,  \
-                               (const u32x4*)w1s, b1f, w2p, b2f, out, Cin, Cexp, Cout, H, W, tilesX, tilesY, \
-                               xcd_remap_mode());                                                          \
-        } while (0)
-        if (res) LP_MB2(true); else LP_MB2(false);
-#undef LP_MB2
+        const auto kern = res ? mbconv2_kernel<true> : mbconv2_kernel<false>;
+        if (!kernel_ready(reinterpret_cast<const void*>(kern), lds2)) return false;
+        LP_LAUNCH(kern, grid, block, lds2, s, x, (const f32x4*)wrow, (const u32x4*)w1s, b1f, w2p, b2f, out, Cin, Cexp,
+                  Cout, H, W, tilesX, tilesY, xcd_remap_mode());
         return true;
     }
     const size_t lds = (size_t)(16 * MB2_PAIR) * sizeof(float);
     last_kernel_tag = "mbconv_kernel";
-#define LP_MB(RESV)                                                                                        \
-    do {                                                                                                   \
-        if (uses_scratch(reinterpret_cast<const void*>(mbconv_kernel<RESV, 12, false, false>))) return false; \
-        static bool attr_##RESV = false;                                                                   \
-        if (!attr_##RESV) {                                                                                \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mbconv_kernel<RESV, 12, false, false>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-            attr_##RESV = true;                                                                            \
-        }                                                                                                  \
-        LP_LAUNCH((mbconv_kernel<RESV, 12, false, false>), grid, block, lds, s, x, (const f32x4*)nullptr, \
-                           (const u32x4*)nullptr, w1p, b1f, wdw_pair, bdw, w2p, b2f, out, Cin, Cexp, Cout, H, W, \
-                           tilesX, tilesY, xcd_remap_mode());                                              \
-    } while (0)
-    if (res) LP_MB(true); else LP_MB(false);
-#undef LP_MB
+    const auto kern = res ? mbconv_kernel<true> : mbconv_kernel<false>;
+    if (!kernel_ready(reinterpret_cast<const void*>(kern), lds)) return false;
+    LP_LAUNCH(kern, grid, block, lds, s, x, w1p, b1f, wdw_pair, bdw, w2p, b2f, out, Cin, Cexp, Cout, H, W, tilesX, tilesY,
+              xcd_remap_mode());
     return true;
 }
 
@@ -2664,7 +2480,8 @@ bool launch_mbconv(const float* x, const float* w1p, const float* b1f, const flo
 //   a=0: (dy= 0,ky=1) (dy=-1,ky=3)      a=1: (dy=+1,ky=0) (dy= 0,ky=2)   (same in x)
 // =====================================================================================
 // DUAL = false (plain head, pose_simplenet.py:133): ConvT(refined) alone -- the raw operand is absent at compile time
-template <int COT, bool DUAL>
+constexpr int COT = 8;                                    // output channels per workgroup row (grid.y) of deconv_pair_kernel
+template <bool DUAL>
 __global__ __launch_bounds__(256) void deconv_pair_kernel(const float* __restrict__ inA, int Ca,
                                                           const float* __restrict__ inB, int Cb,
                                                           const float* __restrict__ w,
@@ -3200,13 +3017,12 @@ void launch_deconv_mfma(const float* inA, int Ca, const float* inB, int Cb, cons
 
 void launch_deconv_pair(const float* inA, int Ca, const float* inB, int Cb, const float* w,
                         const float* b, float* out, int N, int h, int w_, int Cout, hipStream_t s) {
-    constexpr int COT = 8;
     const long total = (long)N * h * w_;
     dim3 grid((unsigned)((total + 255) / 256), (Cout + COT - 1) / COT), block(256);
     if (inB)
-        LP_LAUNCH((deconv_pair_kernel<COT, true>), grid, block, 0, s, inA, Ca, inB, Cb, w, b, out, N, h, w_, Cout);
+        LP_LAUNCH(deconv_pair_kernel<true>, grid, block, 0, s, inA, Ca, inB, Cb, w, b, out, N, h, w_, Cout);
     else                                                                   // plain head: the one-source form
-        LP_LAUNCH((deconv_pair_kernel<COT, false>), grid, block, 0, s, inA, Ca, inB, Cb, w, b, out, N, h, w_, Cout);
+        LP_LAUNCH(deconv_pair_kernel<false>, grid, block, 0, s, inA, Ca, inB, Cb, w, b, out, N, h, w_, Cout);
     last_kernel_tag = "deconv_pair_kernel";
 }
 

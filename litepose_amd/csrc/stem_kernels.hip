@@ -29,6 +29,7 @@
 //   * + bias, 64-byte row segments to HBM.
 // All three sums run in the order of the unfused kernels (stem_kernel, dwpw_kernel<3>): bit-identical, tested.
 #include "kernels.h"
+#include "fused_common.h"
 #include "fmt16.h"
 
 // tools/ubench/stem4_trace.hip defines this before including the file: per-wave time stamps at the phase boundaries
@@ -59,12 +60,6 @@ template <int C0> constexpr int s4_lds_floats() { return S4_ACT_FLOATS + S4_WA +
 
 constexpr int S4_NW = 8;                               // waves per workgroup
 constexpr int S4_NT = 64 * S4_NW;
-
-__device__ __forceinline__ int s4_xcd_contiguous_id(int id, int n) {        // see net_kernels.hip
-    const int q = n >> 3, r = n & 7;
-    const int xcd = id & 7, slot = id >> 3;
-    return xcd * q + min(xcd, r) + slot;
-}
 
 // BF16 (round 6): the stem of the bf16-storage network (valid.py:152-153 -> fp16util.py:87-91; oracle/net_ref.py bf16_plan) in
 // the same launch shape -- the weights are the bf16-ROUNDED folded weights (as fp32 values: products of bf16 values are exact
@@ -155,7 +150,7 @@ __device__ __forceinline__ void stem4_kernel_body(     // 6 waves per SIMD = thr
 
     {
         const int unit0 = blockIdx.x;
-        int unit = s4_xcd_contiguous_id(unit0, total_units);
+        int unit = xcd_contiguous_id(unit0, total_units);
         LP_STEM4_TRACE(0, unit0);
         const int tx = unit % tilesX;
         unit /= tilesX;
@@ -371,14 +366,9 @@ static bool launch_stem3_t(const float* x, const float* w0t, const float* b0, co
     if (total > 0x7fffffffL) return false;
     const size_t lds = (size_t)(c0 == 16 ? s4_lds_floats<16>() : s4_lds_floats<24>()) * sizeof(float);
     last_kernel_tag = "stem4_kernel";
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem4_fn<16, BF16, F>()), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  s4_lds_floats<16>() * 4);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem4_fn<24, BF16, F>()), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  s4_lds_floats<24>() * 4);
-        attr = true;
-    }
+    if (!kernel_ready(c0 == 16 ? reinterpret_cast<const void*>(stem4_fn<16, BF16, F>())
+                               : reinterpret_cast<const void*>(stem4_fn<24, BF16, F>()), lds))
+        return false;
     const int grid = (int)total;
     if (c0 == 16)
         LP_LAUNCH((stem4_fn<16, BF16, F>()), dim3((unsigned)grid), dim3(S4_NT), lds, s, x, w0t, b0, w1t, b1, w2t, b2, out, H,

@@ -51,7 +51,7 @@ ARCHS = {
     # published 24-channel blocks expand to 144).  stage 0: the stride-2 entry and two residual blocks at 1/4; stage 1: the
     # same pair at 1/8, where a plane's width can be 2 mod 4 (W = 272 -> 34)
     'mb24': build(24, [(24, 2, [[4, 7]] * 3), (24, 2, [[4, 7]] * 2), (48, 2, [[6, 7]]), (80, 1, [[6, 7]])], (16, 24, 24)),
-    # five stages, the first at stride 1: the NON-residual stride-1 24 -> 32 block (mbconv_kernel<false, ...>) at 1/2, a
+    # five stages, the first at stride 1: the NON-residual stride-1 24 -> 32 block (mbconv_kernel<false>) at 1/2, a
     # 32 -> 24 stride-2 entry with expand 3, stride-2 entries with 5x5 and 3x3 depthwise
     'five': build(24, [(32, 1, [[4, 7]]), (24, 2, [[3, 7], [4, 7]]), (32, 2, [[6, 5]]), (48, 2, [[6, 3]]), (80, 1, [[3, 5]])],
                   (16, 24, 24)),
@@ -106,7 +106,7 @@ ROWS = [
      'maps (two channel blocks), final.0 on a 16 x 16 plane'),
     ('odd_96x160', 'odd', 96, 160, 3, 2, {'_joints': 17}, _ODD16, set(), 'the same on non-square planes'),
     ('pair66_64', 'pair66', 64, 64, 3, 2, {}, {'deconv_pair_kernel', 'deconv4_kernel'}, set(),
-     'deconv_pair_kernel<8, true> on 34 + 32 channels, 40 filters'),
+     'deconv_pair_kernel<true> on 34 + 32 channels, 40 filters'),
     ('pair66_96x160', 'pair66', 96, 160, 3, 2, {}, {'deconv_pair_kernel'}, set(), 'the same on non-square planes'),
     ('wide72_64', 'wide72', 64, 64, 3, 2, {}, {'deconv_pair_kernel'}, set(),
      'deconv_pair_kernel on 80 + 48 = 128 channels, 72 filters; 16-bit storage refuses > 64 filters at finalize'),
@@ -115,7 +115,7 @@ ROWS = [
     ('plain_mfma_64', 'odd', 64, 64, 3, 2, {'_plain': 1}, {'deconv_mfma_kernel', 'pw2_kernel'}, set(),
      'pose_simplenet: deconv_mfma_kernel<false> on 18 and on 17 channels, one-source heads of 17 and 9 channels'),
     ('plain_pair_64', 'pair66', 64, 64, 3, 2, {'_plain': 1}, {'deconv_pair_kernel'}, set(),
-     'pose_simplenet: deconv_pair_kernel<8, false> on 34 channels, 40 filters'),
+     'pose_simplenet: deconv_pair_kernel<false> on 34 channels, 40 filters'),
     # ---- depthwise kernel sizes and expand ratios inside blocks
     ('ksize_256', 'ksize', 256, 256, 3, 2, {},
      {'dw_kernel<3,2>', 'dw_kernel<5,2>', 'dw_pair_kernel<3>', 'dw_pair_kernel<5>', 'dw_pair16_kernel<3>',

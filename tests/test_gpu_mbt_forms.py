@@ -129,7 +129,7 @@ of bounds; runs of the others were not possible in this work).  What each does a
   (e) waves 4 / 5 expanding rows 21 / 19 instead of 20 / 21: tile row 20 (image row y0 + 17) stays zero.  Every strip with
       18 rows or more below its top fails: h19 - h35, g51; so does the existing test at heights 32 and 48.  h17 and below
       pass: they have no such row.
-  (f) ``mt_xcd_contiguous_id`` without ``min(xcd, r)``: with a grid of 8 q + r, r != 0, several workgroups take one unit
+  (f) ``xcd_contiguous_id`` without ``min(xcd, r)``: with a grid of 8 q + r, r != 0, several workgroups take one unit
       and the last units are taken by none (grid 3: units 1 and 2).  The function serves both forms, so the bitwise
       partner is wrong too; the skipped units keep the FOREIGN images' results, which the block check and the oracle
       see: every row whose grid is no multiple of 8 fails (3, 4, 6, 9, 12, 18, 51).  The existing strip test runs both

@@ -426,7 +426,7 @@ CALIB_MEASURED = {'all_min': (1.87, 1.91), 'min_max': (1.77, 1.76)}
 
 @pytest.mark.parametrize('ci', range(len(CALIB)), ids=[c[0] for c in CALIB])
 def test_calibration_on_the_extreme_widths(ci):
-    """``calibrate`` (the unfused launches, stem_raw_kernel, deconv_raw_kernel<8>, bn_stats_kernel, bn_apply_kernel) on
+    """``calibrate`` (the unfused launches, stem_raw_kernel, deconv_raw_kernel, bn_stats_kernel, bn_apply_kernel) on
     8-channel layers and an 8-filter deconv, 96 x 160 (15-pixel deepest planes: the scalar path), two steps of N = 4:
     every running pair of every layer against sr.train_forward in float64.  The reference golden has no ``dist`` for
     these architectures, so the yardstick of a layer is the float32 restatement's own distance from float64

@@ -250,7 +250,7 @@ def test_no_kernel_uses_scratch():
     assert not bad, bad
     # what the default path of the headline configuration launches must be there at all
     for k in ('lp::mb16_kernel<5, 3, true>', 'lp::mb16_kernel<3, 2, true>', 'lp::mb16_kernel<3, 3, false>',
-              'lp::mbt_kernel<2, 1, true>', 'lp::mbt_s2_kernel<1, 1>', 'lp::mbconv2_kernel<true, 8, 1>',
+              'lp::mbt_kernel<2, 1, true>', 'lp::mbt_s2_kernel<1, 1>', 'lp::mbconv2_kernel<true>',
               # bf16 storage, S@448 / M@512 (BASELINE configs 4 / 5): the fused blocks of every stage
               'lp::mbtb_kernel<1, 1, true>', 'lp::mbtb_kernel<2, 1, true>', 'lp::mbtb_kernel<3, 2, true>',
               'lp::mbtb_kernel<3, 4, false>', 'lp::mbtb_kernel<5, 3, true>', 'lp::mbtb_kernel<5, 4, false>',

@@ -13,8 +13,8 @@
 // take an octet per wave and run its four channel pairs as v_pk_fma_f32 against SGPR weight pairs.
 // (The fp32 path keeps planar NCHW: its matrix-core operand is one f32 per lane; see net_kernels.hip.)
 // Round 7, fp16 storage (LP_STORAGE_F16): every kernel below is a __device__ body templated on the 16-bit format F
-// (fmt16.h) with two entry points -- the bf16 one under its original name and template list, and an overload with a
-// leading lp::F16 (e.g. lp::mbtb_kernel<lp::F16, 1, 1, true>); NAME_fn<F, ...>() gives the launcher the entry point of F.
+// (fmt16.h) under one __global__ template with F leading (lp::pwb_kernel<lp::Bf16, 1, 2, false, false>, the same list
+// after lp::F16); a launcher turns its `bool f16` into F with with_fmt.
 #include "kernels.h"
 #include "fused_common.h"
 #include "fmt16.h"
@@ -75,30 +75,19 @@ __device__ __forceinline__ void stemb_kernel_body(const float* __restrict__ x, c
     }
 }
 
-__global__ __launch_bounds__(256) void stemb_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                    const float* __restrict__ b, u32x4* __restrict__ out, int N,
-                                                    int H, int W, int flip_from, int x_batch) {
-    stemb_kernel_body<Bf16>(x, w, b, out, N, H, W, flip_from, x_batch);
-}
 template <class F>
 __global__ __launch_bounds__(256) void stemb_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                     const float* __restrict__ b, u32x4* __restrict__ out, int N,
                                                     int H, int W, int flip_from, int x_batch) {
     stemb_kernel_body<F>(x, w, b, out, N, H, W, flip_from, x_batch);
 }
-// the entry point of format F (bf16: the original function)
-template <class F>
-inline auto stemb_kernel_fn() {
-    if constexpr (F::is_f16) return &stemb_kernel<F>;
-    else return static_cast<decltype(&stemb_kernel<F16>)>(stemb_kernel);
-}
-
 
 void launch_stemb(const float* x, const float* w, const float* b, void* out, int N, int H, int W, int flip_from,
                   int x_batch, hipStream_t s, bool f16) {
     const long total = (long)N * (H / 2) * (W / 2);
-    LP_LAUNCH((f16 ? stemb_kernel_fn<F16>() : stemb_kernel_fn<Bf16>()), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, w, b, (u32x4*)out, N,
-                       H, W, flip_from, x_batch);
+    const auto kern = with_fmt(f16, [](auto F) { return &stemb_kernel<decltype(F)>; });
+    LP_LAUNCH(kern, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, w, b, (u32x4*)out, N, H, W, flip_from,
+              x_batch);
     last_kernel_tag = "stemb_kernel";
 }
 
@@ -271,25 +260,12 @@ __device__ __forceinline__ void dwb_kernel_body(const u32x4* __restrict__ in, co
     }
 }
 
-template <int K, int S>
-__global__ __launch_bounds__(256) void dwb_kernel(const u32x4* __restrict__ in, const f32x4* __restrict__ w,
-                                                  u32x4* __restrict__ out, int C8, int H, int W, int OH, int OW,
-                                                  int tilesX, int tilesY, int act, int units, int tpw, int xcd_remap) {
-    dwb_kernel_body<Bf16, K, S>(in, w, out, C8, H, W, OH, OW, tilesX, tilesY, act, units, tpw, xcd_remap);
-}
 template <class F, int K, int S>
 __global__ __launch_bounds__(256) void dwb_kernel(const u32x4* __restrict__ in, const f32x4* __restrict__ w,
                                                   u32x4* __restrict__ out, int C8, int H, int W, int OH, int OW,
                                                   int tilesX, int tilesY, int act, int units, int tpw, int xcd_remap) {
     dwb_kernel_body<F, K, S>(in, w, out, C8, H, W, OH, OW, tilesX, tilesY, act, units, tpw, xcd_remap);
 }
-// the entry point of format F (bf16: the original template)
-template <class F, int K, int S>
-inline auto dwb_kernel_fn() {
-    if constexpr (F::is_f16) return &dwb_kernel<F, K, S>;
-    else return &dwb_kernel<K, S>;
-}
-
 
 template <class F, int K, int S>
 static bool launch_dwb_t(const void* in, const float* w, void* out, int N, int C, int H, int W, int act,
@@ -302,8 +278,8 @@ static bool launch_dwb_t(const void* in, const float* w, void* out, int N, int C
     // units per wave: the next unit's loads fly under this unit's FMAs; keep >= ~8 waves per SIMD in the grid
     const int tpw = units >= 32768 ? 4 : (units >= 16384 ? 2 : 1);
     const unsigned grid = (unsigned)((units + 4L * tpw - 1) / (4L * tpw));
-    if (!kernel_ready((const void*)dwb_kernel_fn<F, K, S>(), 4 * G::LDS_BYTES)) return false;
-    LP_LAUNCH((dwb_kernel_fn<F, K, S>()), dim3(grid), dim3(256), 4 * G::LDS_BYTES, s, (const u32x4*)in,
+    if (!kernel_ready((const void*)&dwb_kernel<F, K, S>, 4 * G::LDS_BYTES)) return false;
+    LP_LAUNCH((dwb_kernel<F, K, S>), dim3(grid), dim3(256), 4 * G::LDS_BYTES, s, (const u32x4*)in,
                        (const f32x4*)w, (u32x4*)out, C / 8, H, W, OH, OW, tilesX, tilesY, act, (int)units, tpw,
                        (xr && tilesX * tilesY > 4) ? 1 : 0);
     return true;
@@ -316,7 +292,7 @@ bool launch_dwb(const void* in, const float* w, void* out, int N, int C, int H, 
                              : (K == 5 ? (S == 1 ? "dwb_kernel<5,1>" : "dwb_kernel<5,2>")
                                        : (S == 1 ? "dwb_kernel<3,1>" : "dwb_kernel<3,2>"));
 #define LP_DWB(KV, SV) \
-    (f16 ? launch_dwb_t<F16, KV, SV>(in, w, out, N, C, H, W, act, s) : launch_dwb_t<Bf16, KV, SV>(in, w, out, N, C, H, W, act, s))
+    with_fmt(f16, [&](auto F) { return launch_dwb_t<decltype(F), KV, SV>(in, w, out, N, C, H, W, act, s); })
     if (K == 7 && S == 1) return LP_DWB(7, 1);
     if (K == 7 && S == 2) return LP_DWB(7, 2);
     if (K == 5 && S == 1) return LP_DWB(5, 1);
@@ -455,25 +431,12 @@ __device__ __forceinline__ void dwt_kernel_body(const u32x4* __restrict__ in, co
     }
 }
 
-template <int K>
-__global__ __launch_bounds__(256) void dwt_kernel(
-    const u32x4* __restrict__ in, const u32x4* __restrict__ wt, const float* __restrict__ wb,
-    u32x4* __restrict__ out, int C8, int H, int W, int regsX, int regsY, int act, int xcd_remap) {
-    dwt_kernel_body<Bf16, K>(in, wt, wb, out, C8, H, W, regsX, regsY, act, xcd_remap);
-}
 template <class F, int K>
 __global__ __launch_bounds__(256) void dwt_kernel(
     const u32x4* __restrict__ in, const u32x4* __restrict__ wt, const float* __restrict__ wb,
     u32x4* __restrict__ out, int C8, int H, int W, int regsX, int regsY, int act, int xcd_remap) {
     dwt_kernel_body<F, K>(in, wt, wb, out, C8, H, W, regsX, regsY, act, xcd_remap);
 }
-// the entry point of format F (bf16: the original template)
-template <class F, int K>
-inline auto dwt_kernel_fn() {
-    if constexpr (F::is_f16) return &dwt_kernel<F, K>;
-    else return &dwt_kernel<K>;
-}
-
 
 bool launch_dwt(const void* in, const void* wt, const float* wb, void* out, int N, int C, int H, int W, int K, int act,
                 hipStream_t s, bool f16) {
@@ -487,15 +450,14 @@ bool launch_dwt(const void* in, const void* wt, const float* wb, void* out, int 
     if (units > 0x7fffffffL) return false;
     constexpr int xr = 1;                                            // tiles dealt XCD-contiguously
     const int remap = (xr && regsX * regsY > 4) ? 1 : 0;
-    if (K == 7) {
-        last_kernel_tag = "dwt_kernel<7>";
-        LP_LAUNCH((f16 ? dwt_kernel_fn<F16, 7>() : dwt_kernel_fn<Bf16, 7>()), dim3((unsigned)units), dim3(256), DwtGeom<7>::LDS_IN + DwtGeom<7>::LDS_OUT, s,
-                           (const u32x4*)in, (const u32x4*)wt, wb, (u32x4*)out, C / 8, H, W, regsX, regsY, act, remap);
-    } else {            // 5x5 (the two output heads): the same kernel, 5 MFMAs per channel and tile; NOT run on hardware
-        last_kernel_tag = "dwt_kernel<5>";
-        LP_LAUNCH((f16 ? dwt_kernel_fn<F16, 5>() : dwt_kernel_fn<Bf16, 5>()), dim3((unsigned)units), dim3(256), DwtGeom<5>::LDS_IN + DwtGeom<5>::LDS_OUT, s,
-                           (const u32x4*)in, (const u32x4*)wt, wb, (u32x4*)out, C / 8, H, W, regsX, regsY, act, remap);
-    }
+    // 5x5 (the two output heads): the same kernel, 5 MFMAs per channel and tile; NOT run on hardware
+    last_kernel_tag = K == 7 ? "dwt_kernel<7>" : "dwt_kernel<5>";
+    const auto kern = with_fmt(f16, [&](auto F) {
+        return K == 7 ? &dwt_kernel<decltype(F), 7> : &dwt_kernel<decltype(F), 5>;
+    });
+    const size_t lds = K == 7 ? DwtGeom<7>::LDS_IN + DwtGeom<7>::LDS_OUT : DwtGeom<5>::LDS_IN + DwtGeom<5>::LDS_OUT;
+    LP_LAUNCH(kern, dim3((unsigned)units), dim3(256), lds, s, (const u32x4*)in, (const u32x4*)wt, wb, (u32x4*)out, C / 8,
+              H, W, regsX, regsY, act, remap);
     return true;
 }
 
@@ -661,14 +623,7 @@ __device__ __forceinline__ void headb_kernel_body(
     }
 }
 
-__global__ __launch_bounds__(256, 2) void headb_kernel(
-    const u32x4* __restrict__ inA, int Ca8, const u32x4* __restrict__ inB, int Cb8,
-    const u32x4* __restrict__ wtA, const float* __restrict__ wbA, const u32x4* __restrict__ wtB,
-    const float* __restrict__ wbB, const u32x4* __restrict__ wf, float* __restrict__ out, int H, int W,
-    int regsX, int regsY, int Cout, int xcd_remap) {
-    headb_kernel_body<Bf16, true>(inA, Ca8, inB, Cb8, wtA, wbA, wtB, wbB, wf, out, H, W, regsX, regsY, Cout, xcd_remap);
-}
-template <class F, bool DUAL = true>
+template <class F, bool DUAL>
 __global__ __launch_bounds__(256, 2) void headb_kernel(
     const u32x4* __restrict__ inA, int Ca8, const u32x4* __restrict__ inB, int Cb8,
     const u32x4* __restrict__ wtA, const float* __restrict__ wbA, const u32x4* __restrict__ wtB,
@@ -676,14 +631,6 @@ __global__ __launch_bounds__(256, 2) void headb_kernel(
     int regsX, int regsY, int Cout, int xcd_remap) {
     headb_kernel_body<F, DUAL>(inA, Ca8, inB, Cb8, wtA, wbA, wtB, wbB, wf, out, H, W, regsX, regsY, Cout, xcd_remap);
 }
-// the entry point of format F (bf16, two sources: the original function; the one-source forms of both formats are
-// headb_kernel<F, false>)
-template <class F, bool DUAL = true>
-inline auto headb_kernel_fn() {
-    if constexpr (F::is_f16 || !DUAL) return &headb_kernel<F, DUAL>;
-    else return static_cast<decltype(&headb_kernel<F16>)>(headb_kernel);
-}
-
 
 bool launch_headb(const void* inA, int Ca, const void* inB, int Cb, const void* wtA, const float* wbA, const void* wtB,
                   const float* wbB, const void* wf, float* out, int N, int H, int W, int K, int Cout, hipStream_t s,
@@ -700,8 +647,9 @@ bool launch_headb(const void* inA, int Ca, const void* inB, int Cb, const void* 
     const int remap = regsX * regsY > 4 ? 1 : 0;
     const size_t lds = DwtGeom<5>::LDS_IN + 2 * DwtGeom<5>::LDS_OUT;
     last_kernel_tag = "headb_kernel";
-    const auto kern = dual ? (f16 ? headb_kernel_fn<F16>() : headb_kernel_fn<Bf16>())
-                           : (f16 ? headb_kernel_fn<F16, false>() : headb_kernel_fn<Bf16, false>());
+    const auto kern = with_fmt(f16, [&](auto F) {
+        return dual ? &headb_kernel<decltype(F), true> : &headb_kernel<decltype(F), false>;
+    });
     if (!kernel_ready(reinterpret_cast<const void*>(kern), lds)) return false;
     LP_LAUNCH(kern, dim3((unsigned)units), dim3(256), lds, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8,
               (const u32x4*)wtA, wbA, (const u32x4*)wtB, wbB, (const u32x4*)wf, out, H, W, regsX, regsY, Cout, remap);
@@ -855,13 +803,6 @@ __device__ __forceinline__ void pwb_kernel_body(const u32x4* __restrict__ inA, i
     }
 }
 
-template <int NB, int PXV, bool RES, bool OUTF32>
-__global__ __launch_bounds__(256, pwb_min_blocks(NB, PXV)) void pwb_kernel(
-    const u32x4* __restrict__ inA, int Ca8, const u32x4* __restrict__ inB, int Cb8, const u32x4* __restrict__ wf,
-    const float* __restrict__ bias, const uint2* __restrict__ res, void* __restrict__ outv, long NG, int HWV,
-    int HW, int Cout, int act) {
-    pwb_kernel_body<Bf16, NB, PXV, RES, OUTF32>(inA, Ca8, inB, Cb8, wf, bias, res, outv, NG, HWV, HW, Cout, act);
-}
 template <class F, int NB, int PXV, bool RES, bool OUTF32>
 __global__ __launch_bounds__(256, pwb_min_blocks(NB, PXV)) void pwb_kernel(
     const u32x4* __restrict__ inA, int Ca8, const u32x4* __restrict__ inB, int Cb8, const u32x4* __restrict__ wf,
@@ -869,13 +810,6 @@ __global__ __launch_bounds__(256, pwb_min_blocks(NB, PXV)) void pwb_kernel(
     int HW, int Cout, int act) {
     pwb_kernel_body<F, NB, PXV, RES, OUTF32>(inA, Ca8, inB, Cb8, wf, bias, res, outv, NG, HWV, HW, Cout, act);
 }
-// the entry point of format F (bf16: the original template)
-template <class F, int NB, int PXV, bool RES, bool OUTF32>
-inline auto pwb_kernel_fn() {
-    if constexpr (F::is_f16) return &pwb_kernel<F, NB, PXV, RES, OUTF32>;
-    else return &pwb_kernel<NB, PXV, RES, OUTF32>;
-}
-
 
 template <class F, int NB, int PXV>
 static void launch_pwb_t(const void* inA, int Ca, const void* inB, int Cb, const void* wf, const float* bias,
@@ -884,7 +818,7 @@ static void launch_pwb_t(const void* inA, int Ca, const void* inB, int Cb, const
     const int cblocks = (Cout + 31) / 32;
     dim3 grid((unsigned)((NG + 127) / 128), (cblocks + NB - 1) / NB), block(256);
 #define LP_PWB(RESV, F32V)                                                                                          \
-    LP_LAUNCH((pwb_kernel_fn<F, NB, PXV, RESV, F32V>()), grid, block, 0, s, (const u32x4*)inA, Ca / 8,              \
+    LP_LAUNCH((pwb_kernel<F, NB, PXV, RESV, F32V>), grid, block, 0, s, (const u32x4*)inA, Ca / 8,                   \
                        (const u32x4*)inB, Cb / 8, (const u32x4*)wf, bias, (const uint2*)res, out, NG, HW / PXV, HW, \
                        Cout, act)
     if (out_f32) LP_PWB(false, true);
@@ -905,9 +839,10 @@ bool launch_pwb(const void* inA, int Ca, const void* inB, int Cb, const void* wf
     if (PXV == 4 && ((NP / 4 + 31) / 32) * ((cblocks + NB - 1) / NB) < 2048) PXV = 2;
     if (PXV == 4 && NB >= 3) NB = 2;                              // 192 accumulator registers: one wave per SIMD
     last_kernel_tag = "pwb_kernel";
-#define LP_GO(NBV, PV)                                                                                                  \
-    (f16 ? launch_pwb_t<F16, NBV, PV>(inA, Ca, inB, Cb, wf, bias, res, out, NP, HW, Cout, act, out_f32, s)                  \
-         : launch_pwb_t<Bf16, NBV, PV>(inA, Ca, inB, Cb, wf, bias, res, out, NP, HW, Cout, act, out_f32, s))
+#define LP_GO(NBV, PV)                                                                                        \
+    with_fmt(f16, [&](auto F) {                                                                               \
+        launch_pwb_t<decltype(F), NBV, PV>(inA, Ca, inB, Cb, wf, bias, res, out, NP, HW, Cout, act, out_f32, s); \
+    })
     if (PXV == 4) { if (NB >= 2) LP_GO(2, 4); else LP_GO(1, 4); }
     else { if (NB >= 3) LP_GO(3, 2); else if (NB == 2) LP_GO(2, 2); else LP_GO(1, 2); }
 #undef LP_GO
@@ -1021,15 +956,7 @@ __device__ __forceinline__ void deconvb_kernel_body(const u32x4* __restrict__ in
     }
 }
 
-template <int NB>
-__global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconvb_kernel(const u32x4* __restrict__ inA, int Ca8,
-                                                      const u32x4* __restrict__ inB, int Cb8,
-                                                      const u32x4* __restrict__ wf, const float* __restrict__ bias,
-                                                      u32x4* __restrict__ out, long NP, int h, int w_, int Cout,
-                                                      int xcd_remap) {
-    deconvb_kernel_body<Bf16, NB, true>(inA, Ca8, inB, Cb8, wf, bias, out, NP, h, w_, Cout, xcd_remap);
-}
-template <class F, int NB, bool DUAL = true>
+template <class F, int NB, bool DUAL>
 __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconvb_kernel(const u32x4* __restrict__ inA, int Ca8,
                                                       const u32x4* __restrict__ inB, int Cb8,
                                                       const u32x4* __restrict__ wf, const float* __restrict__ bias,
@@ -1037,14 +964,6 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void deconvb_kernel(const u32
                                                       int xcd_remap) {
     deconvb_kernel_body<F, NB, DUAL>(inA, Ca8, inB, Cb8, wf, bias, out, NP, h, w_, Cout, xcd_remap);
 }
-// the entry point of format F (bf16, two sources: the original template; the one-source forms of both formats are
-// deconvb_kernel<F, NB, false>)
-template <class F, int NB, bool DUAL = true>
-inline auto deconvb_kernel_fn() {
-    if constexpr (F::is_f16 || !DUAL) return &deconvb_kernel<F, NB, DUAL>;
-    else return &deconvb_kernel<NB>;
-}
-
 
 bool launch_deconvb(const void* inA, int Ca, const void* inB, int Cb, const void* wf, const float* bias, void* out,
                     int N, int h, int w_, int Cout, hipStream_t s, bool f16) {
@@ -1055,11 +974,11 @@ bool launch_deconvb(const void* inA, int Ca, const void* inB, int Cb, const void
     // inB == nullptr: the one-source form (plain head, Cb = 0)
     const bool dual = inB != nullptr;
     if (!dual && Cb != 0) return false;
-    const auto kern = Cout <= 32
-        ? (dual ? (f16 ? deconvb_kernel_fn<F16, 1>() : deconvb_kernel_fn<Bf16, 1>())
-                : (f16 ? deconvb_kernel_fn<F16, 1, false>() : deconvb_kernel_fn<Bf16, 1, false>()))
-        : (dual ? (f16 ? deconvb_kernel_fn<F16, 2>() : deconvb_kernel_fn<Bf16, 2>())
-                : (f16 ? deconvb_kernel_fn<F16, 2, false>() : deconvb_kernel_fn<Bf16, 2, false>()));
+    const auto kern = with_fmt(f16, [&](auto F) {
+        using T = decltype(F);
+        return Cout <= 32 ? (dual ? &deconvb_kernel<T, 1, true> : &deconvb_kernel<T, 1, false>)
+                          : (dual ? &deconvb_kernel<T, 2, true> : &deconvb_kernel<T, 2, false>);
+    });
     LP_LAUNCH(kern, grid, block, 0, s, (const u32x4*)inA, Ca / 8, (const u32x4*)inB, Cb / 8, (const u32x4*)wf, bias,
               (u32x4*)out, NP, h, w_, Cout, xr);
     last_kernel_tag = "deconvb_kernel";
@@ -1085,27 +1004,16 @@ __device__ __forceinline__ void octet_to_planar_kernel_body(const u32x4* __restr
     }
 }
 
-__global__ __launch_bounds__(256) void octet_to_planar_kernel(const u32x4* __restrict__ in, float* __restrict__ out,
-                                                              long total, int C8, int HW) {
-    octet_to_planar_kernel_body<Bf16>(in, out, total, C8, HW);
-}
 template <class F>
 __global__ __launch_bounds__(256) void octet_to_planar_kernel(const u32x4* __restrict__ in, float* __restrict__ out,
                                                               long total, int C8, int HW) {
     octet_to_planar_kernel_body<F>(in, out, total, C8, HW);
 }
-// the entry point of format F (bf16: the original function)
-template <class F>
-inline auto octet_to_planar_kernel_fn() {
-    if constexpr (F::is_f16) return &octet_to_planar_kernel<F>;
-    else return static_cast<decltype(&octet_to_planar_kernel<F16>)>(octet_to_planar_kernel);
-}
-
 
 void launch_octet_to_planar(const void* in, float* out, int N, int C, int HW, hipStream_t s, bool f16) {
     const long total = (long)N * (C / 8) * HW;
-    LP_LAUNCH((f16 ? octet_to_planar_kernel_fn<F16>() : octet_to_planar_kernel_fn<Bf16>()), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                       (const u32x4*)in, out, total, C / 8, HW);
+    const auto kern = with_fmt(f16, [](auto F) { return &octet_to_planar_kernel<decltype(F)>; });
+    LP_LAUNCH(kern, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const u32x4*)in, out, total, C / 8, HW);
 }
 
 }  // namespace lp

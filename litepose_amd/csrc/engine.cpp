@@ -601,7 +601,7 @@ int64_t mbtb_launch_bytes(const Part& c, size_t i) {
     return 2ll * NB * (ipx * o.Ca + opx * pw.Cout * (pw.res >= 0 ? 2ll : 1ll));
 }
 
-// the whole stem in one launch (stem4_kernel<C0, true>; option "stem" = 0: the three launches of the parity tests)
+// the whole stem in one launch (stem4_kernel<Bf16 | F16, C0>; option "stem" = 0: the three launches of the parity tests)
 int rule_stem3b(const Part& c, size_t i) {
     const lp_net* n = c.n;
     const BOp& o = n->bops[i];

@@ -1,8 +1,11 @@
 // The two 16-bit storage formats of the reduced-precision network path (bf16_kernels.hip, mbtile_bf16.hip, the rounded
-// form of stem4_kernel).  Every kernel of that path is ONE __device__ body templated on a format F; the format-specific
-// parts are the five operations below, everything else (octet-planar records, fragment layouts, fp32 accumulation, bias /
-// activation / residual in fp32, one rounding where a tensor is stored) is shared.
-//   Bf16: v_cvt_pk_bf16_f32 (RNE), unpack = a shift, v_mfma_f32_*_bf16, v_dot2_f32_bf16.  The original entry points.
+// forms of stem4_kernel).  Every kernel of that path is ONE __device__ body and ONE __global__ template, both with the
+// format F as their leading template argument (lp::mbtb_kernel<lp::Bf16, 1, 1, true>, lp::mbtb_kernel<lp::F16, 1, 1, true>);
+// the format-specific parts are the five operations below, everything else (octet-planar records, fragment layouts, fp32
+// accumulation, bias / activation / residual in fp32, one rounding where a tensor is stored) is shared.  A launcher turns
+// its `bool f16` into F once, through with_fmt, so every form exists in both formats with the same template list
+// (tests/test_f16_cpu.py holds that against the build's resource report).
+//   Bf16: v_cvt_pk_bf16_f32 (RNE), unpack = a shift, v_mfma_f32_*_bf16, v_dot2_f32_bf16.
 //   F16:  IEEE half (what the reference's network_to_half runs in, fp16util.py:87-91): v_cvt_pk_f16_f32 (RNE, overflow to
 //         +-inf, subnormals KEPT: hipcc's default kernel mode has float_denorm_mode_16_64 = 3 and nothing here changes it),
 //         unpack = v_cvt_f32_f16, v_mfma_f32_*_f16, v_dot2c_f32_f16.  Never v_cvt_pkrtz_f16_f32: it rounds toward zero.
@@ -16,7 +19,6 @@ namespace lp {
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 
 struct Bf16 {
-    static constexpr bool is_f16 = false;
     __device__ static __forceinline__ unsigned pack(float lo, float hi) {     // RNE, lo in bits 0-15
         typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
         const f32x2 v = {lo, hi};
@@ -40,7 +42,6 @@ struct Bf16 {
 };
 
 struct F16 {
-    static constexpr bool is_f16 = true;
     __device__ static __forceinline__ unsigned pack(float lo, float hi) {     // RNE (v_cvt_pk_f16_f32), lo in bits 0-15
         typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
         const f32x2 v = {lo, hi};
@@ -66,5 +67,16 @@ struct F16 {
         return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b), acc, false);
     }
 };
+
+// fp32 storage: stem4_kernel's unrounded form (its planar fp32 output needs no pack)
+struct F32 {
+    __device__ static __forceinline__ float round(float v) { return v; }
+};
+
+// the one place a launcher's `bool f16` becomes a format: with_fmt(f16, [&](auto F) { ...<decltype(F), ...>... })
+template <class Fn>
+inline auto with_fmt(bool f16, Fn&& fn) {
+    return f16 ? fn(F16{}) : fn(Bf16{});
+}
 
 }  // namespace lp

@@ -209,8 +209,9 @@ void launch_bn_apply(float* x, const float* res, const double* part, float* bn, 
                      double momentum, double eps, hipStream_t s);
 
 // ---- network, 16-bit storage (octet-planar [N][C/8][HW][8] bf16 or fp16; bf16_kernels.hip, mbtile_bf16.hip) ----
-// Every launcher below takes the storage format last: f16 = false (default) runs the bf16 kernels, true their IEEE-half
-// forms (the same templates with a leading lp::F16 argument, fmt16.h): same shape rules, same refusals, same last_kernel_tag.
+// Every launcher below takes the storage format last: f16 = false (default) runs the kernels' lp::Bf16 instances, true their
+// lp::F16 (IEEE half) ones -- one template per kernel with the format as its leading argument, chosen by with_fmt
+// (fmt16.h): same template lists, same shape rules, same refusals, same last_kernel_tag.
 // The weight arrays hold values rounded to the launch's format (engine.cpp rne16).
 // stem on the fp32 image; w [32][27] fp32 (bf16-rounded values), b [32]
 void launch_stemb(const float* x, const float* w, const float* b, void* out, int N, int H, int W, int flip_from,

@@ -28,8 +28,8 @@
 //   * output: the D fragment gives a lane 4 channels (its half of an octet record) of its pixel: 8-byte stores, the
 //     two halves of a wave complete every record in the same instruction
 // Round 7, fp16 storage (LP_STORAGE_F16): every kernel below is a __device__ body templated on the 16-bit format F
-// (fmt16.h) with two entry points -- the bf16 one under its original name and template list, and an overload with a
-// leading lp::F16 (e.g. lp::mbtb_kernel<lp::F16, 1, 1, true>); NAME_fn<F, ...>() gives the launcher the entry point of F.
+// (fmt16.h) under one __global__ template with F leading (lp::mbtb_kernel<lp::Bf16, 1, 1, true>, the same list after
+// lp::F16); launch_mbtb turns its `bool f16` into F with with_fmt.
 #include "kernels.h"
 #include "fused_common.h"
 #include "dw7.h"
@@ -372,13 +372,6 @@ __device__ __forceinline__ void mbtb_kernel_body(
     LP_TR_END(0);
 }
 
-template <int CK, int NMT, bool RES>
-__global__ __launch_bounds__(512, 2) void mbtb_kernel(
-    const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
-    const f32x4* __restrict__ wrow, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
-    u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
-    mbtb_kernel_body<Bf16, CK, NMT, RES>(x, w1, b1f, wrow, w2, b2f, out, Ci8, Cexp, Co8, H, W, tilesX, tilesY, xcd_remap);
-}
 template <class F, int CK, int NMT, bool RES>
 __global__ __launch_bounds__(512, 2) void mbtb_kernel(
     const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
@@ -386,13 +379,6 @@ __global__ __launch_bounds__(512, 2) void mbtb_kernel(
     u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
     mbtb_kernel_body<F, CK, NMT, RES>(x, w1, b1f, wrow, w2, b2f, out, Ci8, Cexp, Co8, H, W, tilesX, tilesY, xcd_remap);
 }
-// the entry point of format F (bf16: the original template)
-template <class F, int CK, int NMT, bool RES>
-inline auto mbtb_kernel_fn() {
-    if constexpr (F::is_f16) return &mbtb_kernel<F, CK, NMT, RES>;
-    else return &mbtb_kernel<CK, NMT, RES>;
-}
-
 
 // =====================================================================================
 // Stride-2 form (the first block of a stage: 7x7 stride 2, no residual): mbt_s2_kernel's geometry (mbtile_kernels.hip)
@@ -633,14 +619,6 @@ __device__ __forceinline__ void mbtb_s2_kernel_body(
     }
 }
 
-template <int CK, int NMT>
-__global__ __launch_bounds__(512, 2) void mbtb_s2_kernel(
-    const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
-    const f32x4* __restrict__ wrow, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
-    u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int OH, int OW, int tilesX, int tilesY,
-    int xcd_remap) {
-    mbtb_s2_kernel_body<Bf16, CK, NMT>(x, w1, b1f, wrow, w2, b2f, out, Ci8, Cexp, Co8, H, W, OH, OW, tilesX, tilesY, xcd_remap);
-}
 template <class F, int CK, int NMT>
 __global__ __launch_bounds__(512, 2) void mbtb_s2_kernel(
     const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
@@ -649,14 +627,6 @@ __global__ __launch_bounds__(512, 2) void mbtb_s2_kernel(
     int xcd_remap) {
     mbtb_s2_kernel_body<F, CK, NMT>(x, w1, b1f, wrow, w2, b2f, out, Ci8, Cexp, Co8, H, W, OH, OW, tilesX, tilesY, xcd_remap);
 }
-// the entry point of format F (bf16: the original template)
-template <class F, int CK, int NMT>
-inline auto mbtb_s2_kernel_fn() {
-    if constexpr (F::is_f16) return &mbtb_s2_kernel<F, CK, NMT>;
-    else return &mbtb_s2_kernel<CK, NMT>;
-}
-
-
 
 // =====================================================================================
 // Round 6: mbtq_kernel -- mbtb_kernel's block on FOUR waves and 16-channel sub-chunks, so that TWO workgroups share a CU.
@@ -929,40 +899,12 @@ __device__ __forceinline__ void mbtq_kernel_body(
     LP_TR_END(1);
 }
 
-template <int CK, int NMT, bool RES>
-__global__ __launch_bounds__(256, 2) void mbtq_kernel(
-    const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
-    const f32x4* __restrict__ wrow, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
-    u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
-    mbtq_kernel_body<Bf16, CK, NMT, RES>(x, w1, b1f, wrow, w2, b2f, out, Ci8, Cexp, Co8, H, W, tilesX, tilesY, xcd_remap);
-}
 template <class F, int CK, int NMT, bool RES>
 __global__ __launch_bounds__(256, 2) void mbtq_kernel(
     const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
     const f32x4* __restrict__ wrow, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
     u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
     mbtq_kernel_body<F, CK, NMT, RES>(x, w1, b1f, wrow, w2, b2f, out, Ci8, Cexp, Co8, H, W, tilesX, tilesY, xcd_remap);
-}
-// the entry point of format F (bf16: the original template)
-template <class F, int CK, int NMT, bool RES>
-inline auto mbtq_kernel_fn() {
-    if constexpr (F::is_f16) return &mbtq_kernel<F, CK, NMT, RES>;
-    else return &mbtq_kernel<CK, NMT, RES>;
-}
-
-
-template <class F, int CK, int NMT, bool RES>
-static bool launch_mbtq_t(const void* x, const void* w1, const float* b1f, const void* wrow, const void* w2,
-                          const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int xcd,
-                          hipStream_t s) {
-    const void* fn = reinterpret_cast<const void*>(mbtq_kernel_fn<F, CK, NMT, RES>());
-    const size_t lds = TQW<CK, NMT>::LDS_BYTES;
-    if (!kernel_ready(fn, lds)) return false;
-    const int tilesX = (W + 15) / 16, tilesY = (H + 15) / 16;
-    LP_LAUNCH((mbtq_kernel_fn<F, CK, NMT, RES>()), dim3(N * tilesX * tilesY), dim3(256), lds, s, (const u32x4*)x,
-              (const u32x4*)w1, b1f, (const f32x4*)wrow, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp,
-              Cout / 8, H, W, tilesX, tilesY, xcd);
-    return true;
 }
 
 // =====================================================================================
@@ -1267,13 +1209,6 @@ __device__ __forceinline__ void mbtd_kernel_body(     // 4 waves per SIMD = two 
     LP_TR_END(0);
 }
 
-template <int CK, int NMT, bool RES>
-__global__ __launch_bounds__(512, 4) void mbtd_kernel(
-    const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
-    const u32x4* __restrict__ wrow2, const u32x4* __restrict__ w2, const float* __restrict__ b2f,
-    u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
-    mbtd_kernel_body<Bf16, CK, NMT, RES>(x, w1, b1f, wrow2, w2, b2f, out, Ci8, Cexp, Co8, H, W, tilesX, tilesY, xcd_remap);
-}
 template <class F, int CK, int NMT, bool RES>
 __global__ __launch_bounds__(512, 4) void mbtd_kernel(
     const u32x4* __restrict__ x, const u32x4* __restrict__ w1, const float* __restrict__ b1f,
@@ -1281,55 +1216,33 @@ __global__ __launch_bounds__(512, 4) void mbtd_kernel(
     u32x4* __restrict__ out, int Ci8, int Cexp, int Co8, int H, int W, int tilesX, int tilesY, int xcd_remap) {
     mbtd_kernel_body<F, CK, NMT, RES>(x, w1, b1f, wrow2, w2, b2f, out, Ci8, Cexp, Co8, H, W, tilesX, tilesY, xcd_remap);
 }
-// the entry point of format F (bf16: the original template)
-template <class F, int CK, int NMT, bool RES>
-inline auto mbtd_kernel_fn() {
-    if constexpr (F::is_f16) return &mbtd_kernel<F, CK, NMT, RES>;
-    else return &mbtd_kernel<CK, NMT, RES>;
-}
-
-
-template <class F, int CK, int NMT, bool RES>
-static bool launch_mbtd_t(const void* x, const void* w1, const float* b1f, const void* wrow2, const void* w2,
-                          const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int xcd,
-                          hipStream_t s) {
-    const void* fn = reinterpret_cast<const void*>(mbtd_kernel_fn<F, CK, NMT, RES>());
-    const size_t lds = TDW<CK, NMT>::LDS_BYTES;
-    static_assert(TDW<CK, NMT>::LDS_BYTES <= 80 * 1024, "two workgroups per CU");
-    if (!kernel_ready(fn, lds)) return false;
-    const int tilesX = (W + 15) / 16, tilesY = (H + 15) / 16;
-    LP_LAUNCH((mbtd_kernel_fn<F, CK, NMT, RES>()), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
-              (const u32x4*)w1, b1f, (const u32x4*)wrow2, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp,
-              Cout / 8, H, W, tilesX, tilesY, xcd);
-    return true;
-}
 
 template <class F, int CK, int NMT>
 static bool launch_mbtb_s2_t(const void* x, const void* w1, const float* b1f, const void* wrow, const void* w2,
                              const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int xcd,
                              hipStream_t s) {
-    const void* fn = reinterpret_cast<const void*>(mbtb_s2_kernel_fn<F, CK, NMT>());
     const size_t lds = SBW<CK, NMT>::LDS_BYTES;
-    if (!kernel_ready(fn, lds)) return false;
+    if (!kernel_ready(reinterpret_cast<const void*>(&mbtb_s2_kernel<F, CK, NMT>), lds)) return false;
     const int OH = H / 2, OW = W / 2;
     const int tilesX = (OW + 15) / 16, tilesY = (OH + 7) / 8;
-    LP_LAUNCH((mbtb_s2_kernel_fn<F, CK, NMT>()), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
-                       (const u32x4*)w1, b1f, (const f32x4*)wrow, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp,
-                       Cout / 8, H, W, OH, OW, tilesX, tilesY, xcd);
+    LP_LAUNCH((mbtb_s2_kernel<F, CK, NMT>), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
+              (const u32x4*)w1, b1f, (const f32x4*)wrow, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp, Cout / 8, H, W,
+              OH, OW, tilesX, tilesY, xcd);
     return true;
 }
 
-template <class F, int CK, int NMT, bool RES>
-static bool launch_mbtb_t(const void* x, const void* w1, const float* b1f, const void* wrow, const void* w2,
-                          const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W, int xcd,
-                          hipStream_t s) {
-    const void* fn = reinterpret_cast<const void*>(mbtb_kernel_fn<F, CK, NMT, RES>());
-    const size_t lds = TBW<CK, NMT>::LDS_BYTES;
-    if (!kernel_ready(fn, lds)) return false;
+// One stride-1 launch.  The three forms (mbtd, mbtq, mbtb) differ in the kernel, in the LDS of its StageLayout, in the block
+// size and in the type of the depthwise rows (WROW: fp32 tap rows; mbtd_kernel's are pairs in the storage format).
+template <class WROW>
+static bool launch_mbt16_s1(void (*kern)(const u32x4*, const u32x4*, const float*, const WROW*, const u32x4*, const float*,
+                                         u32x4*, int, int, int, int, int, int, int, int),
+                            size_t lds, int threads, const void* x, const void* w1, const float* b1f, const void* wrow,
+                            const void* w2, const float* b2f, void* out, int N, int Cin, int Cexp, int Cout, int H, int W,
+                            int xcd, hipStream_t s) {
+    if (!kernel_ready(reinterpret_cast<const void*>(kern), lds)) return false;
     const int tilesX = (W + 15) / 16, tilesY = (H + 15) / 16;
-    LP_LAUNCH((mbtb_kernel_fn<F, CK, NMT, RES>()), dim3(N * tilesX * tilesY), dim3(512), lds, s, (const u32x4*)x,
-                       (const u32x4*)w1, b1f, (const f32x4*)wrow, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp,
-                       Cout / 8, H, W, tilesX, tilesY, xcd);
+    LP_LAUNCH(kern, dim3(N * tilesX * tilesY), dim3(threads), lds, s, (const u32x4*)x, (const u32x4*)w1, b1f,
+              (const WROW*)wrow, (const u32x4*)w2, b2f, (u32x4*)out, Cin / 8, Cexp, Cout / 8, H, W, tilesX, tilesY, xcd);
     return true;
 }
 
@@ -1350,8 +1263,10 @@ bool launch_mbtb(const void* x, const void* w1, const float* b1f, const void* wr
         last_kernel_tag = "mbtb_s2_kernel";
 #define LP_GO2(CKV, NMTV)                                                                                   \
         if (ck == CKV && nmt == NMTV)                                                                       \
-            return f16 ? launch_mbtb_s2_t<F16, CKV, NMTV>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s)  \
-                       : launch_mbtb_s2_t<Bf16, CKV, NMTV>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s);
+            return with_fmt(f16, [&](auto F) {                                                              \
+                return launch_mbtb_s2_t<decltype(F), CKV, NMTV>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, \
+                                                                xcd, s);                                    \
+            });
         // the stage-entry blocks of search-XS / S / M / L
         LP_GO2(1, 1) LP_GO2(2, 1) LP_GO2(2, 2) LP_GO2(3, 3) LP_GO2(4, 3)
 #undef LP_GO2
@@ -1361,9 +1276,11 @@ bool launch_mbtb(const void* x, const void* w1, const float* b1f, const void* wr
     if (mode_d && wrow2 && res && ck <= 2 && nmt == 1) {
         last_kernel_tag = "mbtd_kernel";
 #define LP_GOD(CKV, NMTV)                                                                                   \
-        if (ck == CKV && nmt == NMTV &&                                                                     \
-            (f16 ? launch_mbtd_t<F16, CKV, NMTV, true>(x, w1, b1f, wrow2, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s)  \
-                 : launch_mbtd_t<Bf16, CKV, NMTV, true>(x, w1, b1f, wrow2, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s))) \
+        static_assert(TDW<CKV, NMTV>::LDS_BYTES <= 80 * 1024, "two workgroups per CU");                     \
+        if (ck == CKV && nmt == NMTV && with_fmt(f16, [&](auto F) {                                         \
+                return launch_mbt16_s1(&mbtd_kernel<decltype(F), CKV, NMTV, true>, TDW<CKV, NMTV>::LDS_BYTES, 512, x, w1, \
+                                       b1f, wrow2, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s);         \
+            }))                                                                                             \
             return true;                               /* a variant that needs scratch is refused: the forms below */
         // the residual blocks with up to 32 channels: two workgroups per CU.  Measured and not kept (gpurun r6, S@448 / M@512
         // b32): the same kernel for the wide blocks at ONE workgroup per CU (2 waves per SIMD, 138-223 registers) is 9-15 %
@@ -1380,9 +1297,10 @@ bool launch_mbtb(const void* x, const void* w1, const float* b1f, const void* wr
         (mode_q == 2 || (Cexp <= 160 && (long)N * ((W + 15) / 16) * ((H + 15) / 16) >= 1024))) {
         last_kernel_tag = "mbtq_kernel";
 #define LP_GOQ(CKV, NMTV)                                                                                   \
-        if (ck == CKV && nmt == NMTV &&                                                                     \
-            (f16 ? launch_mbtq_t<F16, CKV, NMTV, true>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s) \
-                 : launch_mbtq_t<Bf16, CKV, NMTV, true>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s))) \
+        if (ck == CKV && nmt == NMTV && with_fmt(f16, [&](auto F) {                                         \
+                return launch_mbt16_s1(&mbtq_kernel<decltype(F), CKV, NMTV, true>, TQW<CKV, NMTV>::LDS_BYTES, 256, x, w1, \
+                                       b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s);          \
+            }))                                                                                             \
             return true;                               /* refused, as above: mbtb_kernel below */
         LP_GOQ(1, 1) LP_GOQ(2, 1)
 #undef LP_GOQ
@@ -1390,8 +1308,10 @@ bool launch_mbtb(const void* x, const void* w1, const float* b1f, const void* wr
     last_kernel_tag = "mbtb_kernel";
 #define LP_GO(CKV, NMTV, RESV)                                                                              \
     if (ck == CKV && nmt == NMTV && (res != nullptr) == RESV)                                               \
-        return f16 ? launch_mbtb_t<F16, CKV, NMTV, RESV>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s)  \
-                   : launch_mbtb_t<Bf16, CKV, NMTV, RESV>(x, w1, b1f, wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s);
+        return with_fmt(f16, [&](auto F) {                                                                  \
+            return launch_mbt16_s1(&mbtb_kernel<decltype(F), CKV, NMTV, RESV>, TBW<CKV, NMTV>::LDS_BYTES, 512, x, w1, b1f, \
+                                   wrow, w2, b2f, out, N, Cin, Cexp, Cout, H, W, xcd, s);                   \
+        });
     // the stride-1 blocks of search-XS / S / M / L (arch_zoo): residual blocks, then the widening ones
     LP_GO(1, 1, true) LP_GO(2, 1, true) LP_GO(3, 2, true) LP_GO(4, 2, true) LP_GO(5, 3, true) LP_GO(6, 3, true)
     LP_GO(8, 4, true)     // (10, 5): the 160-channel blocks of search-L would spill 104 bytes per lane: unfused chain

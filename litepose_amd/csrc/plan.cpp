@@ -206,7 +206,7 @@ size_t push_pair_rows(Net& n, int npairs, int C, At at) {
     return off;
 }
 
-// the fused stem's copies of the three folded weight sets (stem3_kernel / stem4_kernel<C0, true>): conv tap-major
+// the fused stem's copies of the three folded weight sets (stem3_kernel / stem4_kernel<F, C0>): conv tap-major
 // [27][32], depthwise tap-major [9][32] (+ its bias [32] when with_b1), 1x1 input-major [32][c0] + bias [c0].
 // dw_at(c, t): arena offset of depthwise tap t of channel c (t = 9: its bias); rnd: the rounding of the 1x1 weights
 template <class At, class Rnd>
@@ -728,7 +728,7 @@ struct B16 {
     static void pw(Net& n, std::vector<const Tensor*> ws, const std::vector<double>* sc, const std::vector<double>* sh, BOp& o) {
         pack_pwb(n, std::move(ws), sc, sh, o);
     }
-    // stem4_kernel<C0, true> exists for c0 = 16 and 24: the SAME rounded folded weights in the fp32 stem's layouts
+    // stem4_kernel<Bf16 | F16, C0> exists for c0 = 16 and 24: the SAME rounded folded weights in the fp32 stem's layouts
     static void fused_stem(Net& n, BOp& st, const BOp& dw, const std::vector<double>& sc, const std::vector<double>& sh) {
         if (n.c0 != 16 && n.c0 != 24) return;
         pack_fused_stem(n, st, [&](int c, int t) { return dw.w_off + (size_t)((c >> 3) * 10 + t) * 8 + (c & 7); }, true, sc, sh,

@@ -32,6 +32,8 @@
 #include "fused_common.h"
 #include "fmt16.h"
 
+#include <type_traits>
+
 // tools/ubench/stem4_trace.hip defines this before including the file: per-wave time stamps at the phase boundaries
 #ifndef LP_STEM4_TRACE
 #define LP_STEM4_TRACE(i, unit)
@@ -66,7 +68,7 @@ constexpr int S4_NT = 64 * S4_NW;
 // in the fp32 MFMA / FMA chains), every tensor the unfused chain (stemb_kernel -> dwb_kernel<3,1> -> pwb_kernel) would have
 // STORED is rounded to bf16 at the same place (conv output, depthwise output, 1x1 output), and the output goes out as
 // octet-planar records [N][C0 / 8][OH * OW] x 16 B: 1.03 GB of HBM traffic per 64 images of S@448 become 0.26.
-template <class F, int C0, bool BF16>
+template <class F, int C0>
 __device__ __forceinline__ void stem4_kernel_body(     // 6 waves per SIMD = three workgroups per CU: <= 80 registers
     const float* __restrict__ x,        // [x_batch, 3, H, W]
     const float* __restrict__ w0t,      // conv weights, tap-major [27][32] (BN scale folded)
@@ -77,6 +79,7 @@ __device__ __forceinline__ void stem4_kernel_body(     // 6 waves per SIMD = thr
     const float* __restrict__ b2,       // [C0]
     float* __restrict__ out,            // [N, C0, H/2, W/2] fp32; BF16: [N][C0 / 8][H/2 * W/2] records of 8 bf16 channels
     int H, int W, int tilesX, int tilesY, int flip_from, int x_batch, int total_units) {
+    constexpr bool BF16 = !std::is_same<F, F32>::value;    // a 16-bit storage format: round where the chain stores, pack
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* const RA = lds;                             // input patch
     float* const C1 = lds + S4_PATCH;                  // [16][10][36] (+8), later d[16][8 x 32] at the plane heads
@@ -281,7 +284,7 @@ __device__ __forceinline__ void stem4_kernel_body(     // 6 waves per SIMD = thr
         }
         // ---- 5. + bias, store: D fragment (col = pixel lane & 15 of the group, rows 4 (lane >> 4) + r = filters) ---------
         const float* b2p = b2;
-        if (BF16) {
+        if constexpr (BF16) {                          // F32 has no pack
             // a lane holds channels 4 q4 .. 4 q4 + 3 of row block rb of its pixel = one HALF (8 bytes) of the record of octet
             // 2 rb + (q4 >> 1); the lanes of quarters q4, q4 ^ 1 complete every record within the same store instruction
             uint2* ob = reinterpret_cast<uint2*>(out);
@@ -330,32 +333,17 @@ __device__ __forceinline__ void stem4_kernel_body(     // 6 waves per SIMD = thr
     }
 }
 
-template <int C0, bool BF16>
-__global__ __launch_bounds__(S4_NT, 6) void stem4_kernel(
-    const float* __restrict__ x, const float* __restrict__ w0t, const float* __restrict__ b0,
-    const float* __restrict__ w1t, const float* __restrict__ b1, const float* __restrict__ w2t,
-    const float* __restrict__ b2, float* __restrict__ out, int H, int W, int tilesX, int tilesY, int flip_from,
-    int x_batch, int total_units) {
-    stem4_kernel_body<Bf16, C0, BF16>(x, w0t, b0, w1t, b1, w2t, b2, out, H, W, tilesX, tilesY, flip_from, x_batch, total_units);
-}
 template <class F, int C0>
 __global__ __launch_bounds__(S4_NT, 6) void stem4_kernel(
     const float* __restrict__ x, const float* __restrict__ w0t, const float* __restrict__ b0,
     const float* __restrict__ w1t, const float* __restrict__ b1, const float* __restrict__ w2t,
     const float* __restrict__ b2, float* __restrict__ out, int H, int W, int tilesX, int tilesY, int flip_from,
     int x_batch, int total_units) {
-    stem4_kernel_body<F, C0, true>(x, w0t, b0, w1t, b1, w2t, b2, out, H, W, tilesX, tilesY, flip_from, x_batch, total_units);
+    stem4_kernel_body<F, C0>(x, w0t, b0, w1t, b1, w2t, b2, out, H, W, tilesX, tilesY, flip_from, x_batch, total_units);
 }
 
-
-// the entry point of a rounding format (bf16: stem4_kernel<C0, true>; fp32 storage: <C0, false>)
-template <int C0, bool BF16, class F>
-inline auto stem4_fn() {
-    if constexpr (F::is_f16) return &stem4_kernel<F, C0>;
-    else return &stem4_kernel<C0, BF16>;
-}
-
-template <bool BF16, class F = Bf16>
+// F: the storage format of the network the stem feeds (fmt16.h: F32, Bf16 or F16)
+template <class F>
 static bool launch_stem3_t(const float* x, const float* w0t, const float* b0, const float* w1t, const float* b1,
                            const float* w2t, const float* b2, float* out, int N, int H, int W, int c0, int flip_from,
                            int x_batch, hipStream_t s) {
@@ -366,35 +354,28 @@ static bool launch_stem3_t(const float* x, const float* w0t, const float* b0, co
     if (total > 0x7fffffffL) return false;
     const size_t lds = (size_t)(c0 == 16 ? s4_lds_floats<16>() : s4_lds_floats<24>()) * sizeof(float);
     last_kernel_tag = "stem4_kernel";
-    if (!kernel_ready(c0 == 16 ? reinterpret_cast<const void*>(stem4_fn<16, BF16, F>())
-                               : reinterpret_cast<const void*>(stem4_fn<24, BF16, F>()), lds))
-        return false;
-    const int grid = (int)total;
-    if (c0 == 16)
-        LP_LAUNCH((stem4_fn<16, BF16, F>()), dim3((unsigned)grid), dim3(S4_NT), lds, s, x, w0t, b0, w1t, b1, w2t, b2, out, H,
-                  W, tilesX, tilesY, flip_from, x_batch, (int)total);
-    else
-        LP_LAUNCH((stem4_fn<24, BF16, F>()), dim3((unsigned)grid), dim3(S4_NT), lds, s, x, w0t, b0, w1t, b1, w2t, b2, out, H,
-                  W, tilesX, tilesY, flip_from, x_batch, (int)total);
+    const auto kern = c0 == 16 ? &stem4_kernel<F, 16> : &stem4_kernel<F, 24>;
+    if (!kernel_ready(reinterpret_cast<const void*>(kern), lds)) return false;
+    LP_LAUNCH(kern, dim3((unsigned)total), dim3(S4_NT), lds, s, x, w0t, b0, w1t, b1, w2t, b2, out, H, W, tilesX, tilesY,
+              flip_from, x_batch, (int)total);
     return true;
 }
 
 bool launch_stem3(const float* x, const float* w0t, const float* b0, const float* w1t, const float* b1,
                   const float* w2t, const float* b2, float* out, int N, int H, int W, int c0, int flip_from,
                   int x_batch, hipStream_t s) {
-    return launch_stem3_t<false>(x, w0t, b0, w1t, b1, w2t, b2, out, N, H, W, c0, flip_from, x_batch, s);
+    return launch_stem3_t<F32>(x, w0t, b0, w1t, b1, w2t, b2, out, N, H, W, c0, flip_from, x_batch, s);
 }
 
 // the 16-bit-storage stem in one launch: rounded weights in stem4_kernel's fp32 layouts, octet-planar records out
-// (f16: IEEE half storage, stem4_kernel<F16, C0>; otherwise bf16, stem4_kernel<C0, true>)
+// (stem4_kernel<Bf16, C0>; f16: IEEE half storage, stem4_kernel<F16, C0>)
 bool launch_stem3b(const float* x, const float* w0t, const float* b0, const float* w1t, const float* b1,
                    const float* w2t, const float* b2, void* out, int N, int H, int W, int c0, int flip_from,
                    int x_batch, hipStream_t s, bool f16) {
-    if (f16)
-        return launch_stem3_t<true, F16>(x, w0t, b0, w1t, b1, w2t, b2, reinterpret_cast<float*>(out), N, H, W, c0,
-                                         flip_from, x_batch, s);
-    return launch_stem3_t<true>(x, w0t, b0, w1t, b1, w2t, b2, reinterpret_cast<float*>(out), N, H, W, c0, flip_from,
-                                x_batch, s);
+    return with_fmt(f16, [&](auto F) {
+        return launch_stem3_t<decltype(F)>(x, w0t, b0, w1t, b1, w2t, b2, reinterpret_cast<float*>(out), N, H, W, c0,
+                                           flip_from, x_batch, s);
+    });
 }
 
 }  // namespace lp

@@ -55,7 +55,7 @@ def layerwise_report(m, arch, sd, x):
     expanded tensors of a block on the CU, so there would be nothing to compare them with; it has its own test
     below), and compare every launch with the emulated op on the device's own inputs.
     Returns [(name, max_abs_diff, worst_ulp_ratio, mismatch_fraction, is_head)]."""
-    # ... and option "stem" = 0: the fused stem (stem4_kernel<C0, true>, round 6) keeps the conv and depthwise outputs in LDS
+    # ... and option "stem" = 0: the fused stem (stem4_kernel<lp::Bf16, C0>, round 6) keeps the conv and depthwise outputs in LDS
     # ... and "headb" = 0: the fused head keeps both depthwise outputs in LDS (it is bit-identical to its three launches)
     outs = _with_option(m, 'headb', 0, lambda: _with_option(m, 'stem', 0, lambda: _with_option(
         m, 'mbtb', 0, lambda: [o.cpu() for o in m.forward_native(x.cuda(), 0)])))
@@ -177,7 +177,7 @@ def fused_inner(launch_names):
         if nm.endswith('.inv+dw+point_conv'):                     # mbtb / mbtb_s2 / mbtd / mbtq: a whole block
             p = nm[:-len('.inv+dw+point_conv')]
             out[p + '.point_conv'] = [p + '.inv', p + '.depth_conv']
-        elif nm == 'stem.conv3x3s2+dw3+pw':                       # stem4_kernel<C0, true>
+        elif nm == 'stem.conv3x3s2+dw3+pw':                       # stem4_kernel<lp::Bf16, C0>
             out['stem.pw'] = ['stem.conv3x3s2', 'stem.dw3']
         elif nm.endswith('.dw5+dw5+pw'):                          # headb_kernel
             h = nm.split('.')[1]

@@ -84,6 +84,51 @@ def test_library_host_code_rounds_to_half_only_from_float():
     assert b'__truncdfhf2' not in image
 
 
+FAMILIES_16 = ('stemb_kernel', 'dwb_kernel', 'dwt_kernel', 'pwb_kernel', 'deconvb_kernel', 'headb_kernel',
+               'octet_to_planar_kernel', 'mbtb_kernel', 'mbtb_s2_kernel', 'mbtq_kernel', 'mbtd_kernel')
+
+
+def _check_format_census(res):
+    """Every kernel of the 16-bit path is one template with the format leading (csrc/fmt16.h): the instances of a family
+    under lp::Bf16 and under lp::F16 have the same template lists, stem4_kernel has the same C0 under lp::F32 as well."""
+    forms = {}                                        # family -> format -> set of template lists after the format
+    for name in res:
+        base, _, args = name.partition('<')
+        if base.startswith('lp::') and base[4:] in FAMILIES_16 + ('stem4_kernel',):
+            fmt, _, rest = args.rstrip('>').partition(', ')
+            assert fmt in ('lp::F32', 'lp::Bf16', 'lp::F16'), '%s: no leading format argument' % name
+            forms.setdefault(base[4:], {}).setdefault(fmt, set()).add(rest)
+    for fam in FAMILIES_16:
+        by = forms.get(fam, {})
+        assert set(by) == {'lp::Bf16', 'lp::F16'}, (fam, sorted(by))
+        assert by['lp::Bf16'] == by['lp::F16'] and by['lp::Bf16'], (fam, sorted(by['lp::Bf16'] ^ by['lp::F16']))
+    stem = forms.get('stem4_kernel', {})
+    assert set(stem) == {'lp::F32', 'lp::Bf16', 'lp::F16'}, sorted(stem)
+    assert stem['lp::F32'] == stem['lp::Bf16'] == stem['lp::F16'] and stem['lp::F32'], stem
+    for fmt in ('lp::Bf16', 'lp::F16'):
+        n = sum(len(by[fmt]) for by in forms.values())
+        assert n == 53, (fmt, n)
+
+
+def test_every_16bit_kernel_is_built_in_both_formats_with_the_same_template_list():
+    import json
+    from litepose_amd import build as _b
+    path = os.path.join(_b.LIBDIR, 'kernel_resources.json')
+    if not os.path.exists(path):
+        pytest.skip('no kernel resource report (written by `python -m litepose_amd.build`)')
+    res = json.load(open(path))
+    _check_format_census(res)
+    # the check can fail: a form missing in one format, a stem missing in fp32, an instance without a format
+    for gone in ('lp::pwb_kernel<lp::F16, 1, 2, false, false>', 'lp::mbtd_kernel<lp::Bf16, 2, 1, true>',
+                 'lp::stem4_kernel<lp::F32, 24>', 'lp::headb_kernel<lp::F16, false>'):
+        less = dict(res)
+        del less[gone]
+        with pytest.raises(AssertionError):
+            _check_format_census(less)
+    with pytest.raises(AssertionError, match='no leading format'):
+        _check_format_census(dict(res, **{'lp::dwb_kernel<7, 1>': {}}))
+
+
 def test_f16_plan_names_match_the_bf16_plan_and_stored_tensors_are_half():
     from litepose_amd import arch_zoo
     arch = arch_zoo.get('search-XS')

@@ -306,7 +306,7 @@ def test_mbtq_two_workgroups_per_cu_bitwise_vs_mbtb(arch_name, R, N):
 @pytest.mark.parametrize('arch_name,H,W', [('search-S', 448, 448), ('search-XS', 96, 160), ('search-L', 128, 128),
                                            ('search-XS', 160, 96)])
 def test_bf16_fused_stem_vs_unfused_chain(arch_name, H, W):
-    """Round 6: the stem of the bf16-storage network in ONE launch (stem4_kernel<C0, true>: image -> conv3x3 s2 -> dw3x3 ->
+    """Round 6: the stem of the bf16-storage network in ONE launch (stem4_kernel<lp::Bf16, C0>: image -> conv3x3 s2 -> dw3x3 ->
     1x1 with the two 32-channel tensors in LDS, rounded to bf16 where stemb_kernel / dwb_kernel<3,1> / pwb_kernel store
     them; pose_mobilenet.py:36-41 under valid.py:152-153) against those three launches (option "stem" = 0) on the stem
     output: plain and mirrored pass (flip-TTA read), ragged tiles and image borders.  Same roundings, other fp32 summation

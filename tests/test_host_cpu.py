@@ -250,12 +250,13 @@ def test_no_kernel_uses_scratch():
     assert not bad, bad
     # what the default path of the headline configuration launches must be there at all
     for k in ('lp::mb16_kernel<5, 3, true>', 'lp::mb16_kernel<3, 2, true>', 'lp::mb16_kernel<3, 3, false>',
-              'lp::mbt_kernel<2, 1, true>', 'lp::mbt_s2_kernel<1, 1>', 'lp::mbconv2_kernel<true>',
-              # bf16 storage, S@448 / M@512 (BASELINE configs 4 / 5): the fused blocks of every stage
-              'lp::mbtb_kernel<1, 1, true>', 'lp::mbtb_kernel<2, 1, true>', 'lp::mbtb_kernel<3, 2, true>',
-              'lp::mbtb_kernel<3, 4, false>', 'lp::mbtb_kernel<5, 3, true>', 'lp::mbtb_kernel<5, 4, false>',
-              'lp::mbtb_kernel<8, 4, true>'):
+              'lp::mbt_kernel<2, 1, true>', 'lp::mbt_s2_kernel<1, 1>', 'lp::mbconv2_kernel<true>'):
         assert k in res, k
+    # 16-bit storage, S@448 / M@512 (BASELINE configs 4 / 5): the fused blocks of every stage, in both formats
+    for fmt in ('lp::Bf16', 'lp::F16'):
+        for form in ('1, 1, true', '2, 1, true', '3, 2, true', '3, 4, false', '5, 3, true', '5, 4, false', '8, 4, true'):
+            k = 'lp::mbtb_kernel<%s, %s>' % (fmt, form)
+            assert k in res, k
 
 
 def test_library_has_no_packed_fp32_with_op_sel_01():

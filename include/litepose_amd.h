@@ -940,6 +940,96 @@ int lp_optim_adam(int count, float* const* param_io, const float* const* d_grad,
 int lp_optim_sgd(int count, float* const* param_io, const float* const* d_grad, float* const* momentum_io,
                  const int64_t* numel, const double* d_lr, double momentum, double weight_decay, int nesterov, void* stream);
 
+/* ------------------------------------------------------------ supernet training -----------
+ * What a training step of the weight-sharing supernet adds to a step of the fixed network (lib/models/layers/
+ * super_layers.py, lib/core/trainer.py:49-59): the parameters of the sampled sub-network as slices of the supernet's, the
+ * gradients back in the full-size tensors, and the batch resized to a random resolution.  The rules of the training-mode
+ * layer calls hold: caller-owned buffers, no allocation, no synchronisation, no atomics, every sum in one order that
+ * depends on the shapes only (two calls give the same bits), capturable in a hipGraph.  Every refusal is answered before
+ * anything is launched and no device pointer is dereferenced on the host.  The writable pointers are DEVICE memory; they
+ * do not carry the d_ prefix (the census of writable calls keys on it); their contract test is
+ * tests/test_gpu_supertrain_buffers.py.
+ *
+ * lp_subnet_desc: one learnable tensor of the sampled sub-network, 64 bytes, no implicit padding (3 * 8 + 2 * 8 + 6 * 4).
+ * All offsets and sizes are in ELEMENTS (fp32).
+ *   src          the supernet's tensor (DEVICE)
+ *   lin_w, lin_b kind 2 with k < 7: the block's Linear5x5 / Linear3x3 weight [k*k, k*k] and bias [k*k] (DEVICE); else NULL
+ *   sub_offset   where the sliced tensor starts in the packed sub-network buffer
+ *   full_offset  where the full-size gradient of `src` starts in the packed full-gradient buffer
+ *   kind 0       the prefix slice [:rows, :cols] of a row-major [R, C] tensor with t trailing elements per cell
+ *                (SuperConv2d: t = 1, [:out, :in]; SuperConvTranspose2d: t = 16, [:in, :out, 4, 4]); packed [rows, cols, t]
+ *   kind 1       the prefix [:rows] of a vector of R elements (BatchNorm gamma / beta; a depthwise [c, 1, 5, 5] with
+ *                rows = c * 25); cols, C and t are ignored
+ *   kind 2       the depthwise window w[:rows, 0, l:r, l:r] of a [R, 1, 7, 7] tensor, l = 3 - k / 2, r = l + k, k = cols in
+ *                {7, 5, 3}; packed [rows, k, k].  k = 7 is the plain prefix.  k < 7 is followed by the window transform
+ *                (SuperInvBottleneck.forward): with crop[c][i] the flattened window (i = y * k + x),
+ *                  w'[c][o] = b[o] + crop[c][0] * L[o][0] + crop[c][1] * L[o][1] + ...   (i ascending)
+ *                evaluated left to right as written: the accumulator starts at b[o], every product is rounded, then the
+ *                sum is rounded (no fused multiply-add): k*k + 1 roundings of at most 2^-24 relative each on the path of a
+ *                term, |error| <= (k*k + 1) * 2^-24 * (|b| + sum |crop * L|) to first order.
+ * The table is sorted by sub_offset AND by full_offset (both ascending in index order, descriptor 0 at offset 0 of each),
+ * and every offset is a multiple of 64 elements (256 bytes).  A descriptor owns the elements from its offset to the next
+ * descriptor's (the last one: to the end of the buffer); what lies behind its tensor there is padding.  In the full-gradient
+ * buffer a kind 2 descriptor with k < 7 owns three tensors: the gradient of src at full_offset, of lin_w at full_offset +
+ * a64(R * 49), of lin_b at that + a64(k^4), with a64(n) = n rounded up to a multiple of 64.
+ * A malformed descriptor (unknown kind, a size < 1, rows > R, cols > C, t > 65536, k not 7 / 5 / 3, a NULL src, NULL lin_w
+ * / lin_b with k < 7) yields zeros for everything it owns and reads nothing.  A table that is not sorted, or whose offsets
+ * do not match the sizes, gives unspecified VALUES; no launch writes outside the buffers given or reads the packed buffers
+ * outside [0, sub_elems) (the src / lin pointers are the caller's).
+ *
+ * lp_subnet_gather: ONE launch.  sub_out[0, sub_elems) receives every sliced tensor at its sub_offset and 0.0f in the
+ *   padding.  16-byte loads and stores where the four elements are contiguous in src and src is 16-byte aligned, element
+ *   by element otherwise: the same bits.  Values are copied as bits (NaN payloads, Inf and denormals included); the window
+ *   transform propagates NaN / Inf by IEEE arithmetic.  Writes: every element of sub_out.
+ * lp_subnet_scatter_grad: TWO launches.  d_grad_sub[0, sub_elems) is the gradient of sub_out.  full_grad_out[0, full_elems)
+ *   receives, per descriptor, the gradient of the whole supernet tensor: the value inside the slice / window and literal
+ *   0.0f elsewhere and in the padding (there is no memset).  kind 2 with k < 7, g[c][o] the packed gradient:
+ *     gcrop[c][i] = g[c][0] * L[0][i] + g[c][1] * L[1][i] + ...  (o ascending, left to right, products rounded), scattered
+ *                   into the 7x7 centre
+ *     gL[o][i]    = sum_c g[c][o] * crop[c][i],  gb[o] = sum_c g[c][o]: the channels [0, rows) are cut into
+ *                   LP_SUBNET_SEGS = 8 segments of ceil(rows / 8) consecutive channels; a segment is summed from 0.0f in
+ *                   ascending channel order, the 8 partials (an empty segment is 0.0f) are added in ascending segment
+ *                   order, each operation rounded on its own.  This is the second launch.
+ *   crop is re-read from src and L from lin_w: the supernet's parameters must not change between the gather and the
+ *   scatter that belongs to it (the optimizer step comes after the backward).
+ *   Writes: every element of full_grad_out.
+ * LP_ERR_INVALID_ARG: a NULL pointer, count outside 1..LP_SUBNET_MAX_DESC, sub_elems / full_elems < 1, d_desc not 8-byte or
+ * a buffer not 16-byte aligned.  LP_ERR_UNSUPPORTED: sub_elems or full_elems above 2^31 - 256.                          */
+typedef struct lp_subnet_desc {
+    const float* src;
+    const float* lin_w;
+    const float* lin_b;
+    int64_t sub_offset, full_offset;
+    int32_t kind, rows, cols, R, C, t;
+} lp_subnet_desc;
+#define LP_SUBNET_MAX_DESC 1024
+#define LP_SUBNET_SEGS 8
+int lp_subnet_gather(const lp_subnet_desc* d_desc, int count, float* sub_out, int64_t sub_elems, void* stream);
+int lp_subnet_scatter_grad(const lp_subnet_desc* d_desc, int count, const float* d_grad_sub, int64_t sub_elems,
+                           float* full_grad_out, int64_t full_elems, void* stream);
+
+/* lib/core/trainer.py:49-59 for a whole batch: ONE launch.  Every resize is nearest (F.interpolate's default): output cell
+ * d of a line of `out` cells takes source cell min(d * in / out, in - 1), integer arithmetic (for every pair of sizes
+ * training meets -- 512 ... 16 to 1/2, 5/8, 3/4, 7/8 and 1 of it -- that is torch's float rule; tests/test_supertrain_cpu.py).
+ *   d_images [N,3,I,I] -> images_out [N,3,S,S]
+ *   per stage s < stages (1 or 2); the six pointer arrays are HOST arrays of `stages` DEVICE pointers, read during the call:
+ *     d_heatmaps[s] [N,J,R_s,R_s] -> heatmaps_out[s] [N,J,O_s,O_s],  O_s = S / 4 * 2^s,  R_s = h_res[s]
+ *     d_masks[s]    [N,R_s,R_s]   -> masks_out[s]    [N,O_s,O_s]
+ *     d_joints[s]   [N,M,J,2] int32 -> joints_out[s]: element 1 is copied; element 0, the flat index j of the joint's cell,
+ *                   becomes y * S + x with x = (j % B) * S / B, y = (j / B) * S / B in integers (floor modulus and floor
+ *                   division by B, the product divided toward zero, as torch evaluates the reference's expression).
+ *                   The modulus B and the multiplier S are those of the INPUT for every stage, the quarter-size one
+ *                   included: the reference's behaviour (it hard-codes B = 512), kept because the point is to reproduce its
+ *                   training.  For B and S divisible by 16 and 0 <= j < R_s^2 the result lies in [0, O_s^2).
+ * Writes: every element of every output.
+ * LP_ERR_INVALID_ARG: a NULL pointer or array entry, N, J, M < 1, stages not 1 or 2, B < 16 or not a multiple of 16, S < 8
+ * or not a multiple of 8 (every O_s is even), I != B, h_res[s] != B / 4 * 2^s, a float pointer not 16-byte or a joints pointer not 4-byte
+ * aligned.  LP_ERR_UNSUPPORTED: B or S above 16384, or a tensor of more than 2^31 - 256 elements.                         */
+int lp_train_resize(const float* d_images, float* images_out, int N, int I, int S, int B, int stages, int J, int M,
+                    const int32_t* h_res, const float* const* d_heatmaps, const float* const* d_masks,
+                    const int32_t* const* d_joints, float* const* heatmaps_out, float* const* masks_out,
+                    int32_t* const* joints_out, void* stream);
+
 /* utils.transforms.get_final_preds (lib/utils/transforms.py:195-202,50-56): inverse
  * affine (rot 0) heatmap -> image coordinates, in place on x,y of d_ans.
  * h_center [2], h_scale [2] as returned by get_multi_scale_size, heatmap size (Wp,Hp).

@@ -65,6 +65,13 @@ class LpImageDesc(C.Structure):
     _fields_ = [('offset', C.c_int64), ('H', C.c_int32), ('W', C.c_int32)]
 
 
+class LpSubnetDesc(C.Structure):
+    """lp_subnet_desc: one row (64 bytes) of the device descriptor table of lp_subnet_gather / lp_subnet_scatter_grad."""
+    _fields_ = [('src', C.c_void_p), ('lin_w', C.c_void_p), ('lin_b', C.c_void_p), ('sub_offset', C.c_int64),
+                ('full_offset', C.c_int64), ('kind', C.c_int32), ('rows', C.c_int32), ('cols', C.c_int32),
+                ('R', C.c_int32), ('C', C.c_int32), ('t', C.c_int32)]
+
+
 class LpScaleMid(C.Structure):
     """lp_scale_mid: one scale (16 bytes) of lp_tta_merge_scales."""
     _fields_ = [('mid', C.c_void_p), ('h1', C.c_int32), ('w1', C.c_int32)]
@@ -183,6 +190,10 @@ _SIGS = {
                             C.c_double, C.c_double, C.c_double, C.c_double, vp]),
     'lp_optim_sgd': (i32, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp, C.c_double, C.c_double,
                            i32, vp]),
+    'lp_subnet_gather': (i32, [vp, i32, vp, i64, vp]),
+    'lp_subnet_scatter_grad': (i32, [vp, i32, vp, i64, vp, i64, vp]),
+    'lp_train_resize': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp),
+                              C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]),
     'lp_stream_abort_capture': (i32, [vp]),
     'lp_final_preds': (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                              i32, i32, vp]),

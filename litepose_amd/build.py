@@ -58,6 +58,8 @@ SOURCES = [
     ('conv_grad_kernels.hip', NOPK),                       # likewise: fp32 MFMA from LDS patches
     ('optim_api.cpp', []),
     ('optim_kernels.hip', ['-ffp-contract=off'] + NOPK),   # Adam / SGD: every product and sum of the update rounds on its own
+    ('supertrain_api.cpp', []),
+    ('supertrain_kernels.hip', ['-ffp-contract=off'] + NOPK),  # the window transform and its gradients: products and sums round separately
 ]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value',
           '-Wno-pass-failed']

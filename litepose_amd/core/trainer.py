@@ -1,8 +1,11 @@
 """lib/core/trainer.py:do_train with the losses and their gradient on the device: ``loss_epoch``, the losses of a model over a
 labelled set, and ``do_train``, one epoch of loss, backward and optimizer step for a torch model."""
+import random
+
 import torch
 import torch.nn.functional as F
 
+from ..nn.functional import train_resize
 from .loss import MultiLossFactory
 
 
@@ -203,7 +206,17 @@ def _do_train_captured(cfg, model, data_loader, loss_factory, optimizer, epoch, 
             for k, key in enumerate(_KEYS)}
 
 
-def do_train(cfg, model, data_loader, loss_factory, optimizer, epoch=0, teacher=None, logger=None, graph=False):
+SUPERNET_NAMES = ('pose_supermobilenet', 'pose_superresnet')
+
+
+def random_resolution_size(cfg):
+    """trainer.py:50: ``256 + 64 * random.randint(0, 4)`` for the reference's input size 512, the same five fractions of
+    ``DATASET.INPUT_SIZE`` otherwise.  One draw from Python's ``random``."""
+    return (256 + 64 * random.randint(0, 4)) * int(cfg.DATASET.INPUT_SIZE) // 512
+
+
+def do_train(cfg, model, data_loader, loss_factory, optimizer, epoch=0, teacher=None, logger=None, graph=False,
+             random_resolution=None):
     """One epoch of trainer.py:41-113 for a ``torch.nn.Module`` whose ``model(images)`` gives the list of stage outputs:
     per batch ``(images, heatmaps, masks, joints)`` of ``data_loader`` (device tensors, as ``LabelledSet.batches`` yields
     them) the total loss of :82-105 through ``loss_factory`` (``core.loss.MultiLossFactory``), ``optimizer.zero_grad()``,
@@ -227,11 +240,23 @@ def do_train(cfg, model, data_loader, loss_factory, optimizer, epoch=0, teacher=
     ``optimizer.load_state_dict`` / ``add_param_group``; it refuses a changed by-value hyperparameter before it touches
     anything, until ``CapturedStep.invalidate()`` (its docstring lists the events).
 
-    Not here: tensorboard scalars, ``fp16_optimizer``, the supernet's random-resolution resize (:49-59), debug image dumps,
-    batch and data timers."""
+    ``random_resolution``: the supernet's random-resolution resize (:49-59).  None: as the reference, on iff
+    ``cfg.MODEL.NAME`` is ``pose_supermobilenet`` or ``pose_superresnet``.  Per step the size is drawn from Python's
+    ``random`` BEFORE the forward (``random_resolution_size``; a sampling supernet draws its architecture after it, the
+    reference's order), then ``nn.functional.train_resize`` resizes images, heatmaps, masks and joints in one library call
+    (the batch must be DATASET.INPUT_SIZE wide, the joints int32), then the step as otherwise.  With ``graph`` it raises
+    ValueError, and so does a model that samples an architecture per step
+    (``pose_supermobilenet.TrainableSuperLitePose``): every step has another signature.
+
+    Not here: tensorboard scalars, ``fp16_optimizer``, debug image dumps, batch and data timers."""
+    if random_resolution is None:
+        random_resolution = getattr(cfg.MODEL, 'NAME', None) in SUPERNET_NAMES
     if graph:
         if teacher is not None:
             raise ValueError('do_train: a teacher is not supported with graph=True')
+        if random_resolution or hasattr(model, 'arch_manager'):
+            raise ValueError('do_train: graph=True does not go with the random-resolution resize or a model that samples '
+                             'an architecture per step: every step has another signature')
         return _do_train_captured(cfg, model, data_loader, loss_factory, optimizer, epoch, logger, graph)
     S = cfg.LOSS.NUM_STAGES
     last = dict(heatmaps=[None] * S, push=[None] * S, pull=[None] * S)
@@ -241,6 +266,12 @@ def do_train(cfg, model, data_loader, loss_factory, optimizer, epoch=0, teacher=
     model.train()
     for i, (images, heatmaps, masks, joints) in enumerate(data_loader):
         n = int(images.shape[0])
+        if random_resolution:
+            size = random_resolution_size(cfg)
+            if size % 16:
+                raise ValueError('do_train: DATASET.INPUT_SIZE %s gives a training size %d that is not a multiple of 16'
+                                 % (cfg.DATASET.INPUT_SIZE, size))
+            images, heatmaps, masks, joints = train_resize(images, heatmaps, masks, joints, size, cfg.DATASET.INPUT_SIZE)
         t_heatmaps = None
         if teacher is not None:
             size = int(images.shape[-1]) // 4

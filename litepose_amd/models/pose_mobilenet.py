@@ -250,7 +250,75 @@ def _conv(cin, cout, k, stride=1, groups=1):
     return torch.nn.Conv2d(cin, cout, k, stride, k // 2, groups=groups, bias=False)
 
 
-class TrainableLitePose(torch.nn.Module):
+class LayerWalk(object):
+    """The layer walk of the trainable LitePose modules: ``walk(net, x)`` runs the network whose layers ``net`` holds
+    (``first``, ``stage``, ``deconv_refined`` / ``deconv_raw`` / ``deconv_bnrelu``, ``final_refined`` / ``final_raw``,
+    ``num_deconv_layers``) on the backend of ``self``.  A layer is anything with the attributes the walk reads: the torch
+    modules of ``TrainableLitePose``, or the per-step views of the supernet's tensors that
+    ``pose_supermobilenet.TrainableSuperLitePose`` builds."""
+
+    # ---- layers ----
+    def _conv(self, x, conv):
+        k, groups = conv.kernel_size[0], conv.groups
+        if self.backend == 'native' and k == 1 and groups == 1:
+            return F_.pointwise(x, conv.weight)
+        if self.backend == 'native' and groups == conv.in_channels == conv.out_channels and groups > 1:
+            return F_.depthwise(x, conv.weight, conv.stride[0])
+        if self.backend == 'native' and conv is self.first[0][0] and not x.requires_grad:
+            return F_.stem_conv(x, conv.weight)
+        return torch.nn.functional.conv2d(x, conv.weight, None, conv.stride, conv.padding, 1, groups)
+
+    def _up_pair(self, refined, w_refined, raw, w_raw):
+        if self.backend == 'native':
+            return F_.deconv_pair(refined, w_refined, raw, w_raw)
+        up = torch.nn.functional.conv_transpose2d
+        return up(refined, w_refined, None, 2, 1) + up(raw, w_raw, None, 2, 1)
+
+    def _bn(self, x, bn, act=None, residual=None):
+        if self.training:
+            bn.num_batches_tracked += 1
+        if self.backend == 'native':
+            return F_.batch_norm_act(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, act, residual, self.training,
+                                     bn.momentum, bn.eps)
+        y = torch.nn.functional.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, self.training,
+                                           bn.momentum, bn.eps)
+        if act == 'relu6':
+            y = torch.nn.functional.relu6(y)
+        elif act == 'relu':
+            y = torch.relu(y)
+        return y if residual is None else y + residual
+
+    def _block(self, x, blk):
+        y = self._bn(self._conv(x, blk.inv[0]), blk.inv[1], 'relu6')
+        y = self._bn(self._conv(y, blk.depth_conv[0]), blk.depth_conv[1], 'relu6')
+        return self._bn(self._conv(y, blk.point_conv[0]), blk.point_conv[1], None, x if blk.residual else None)
+
+    def _head(self, x, head):
+        c = head.conv
+        return self._conv(self._bn(self._conv(x, c[0]), c[1], 'relu'), c[3])
+
+    def walk(self, net, x):
+        f = net.first
+        x = self._bn(self._conv(x, f[0][0]), f[0][1], 'relu6')
+        x = self._bn(self._conv(x, f[1][0]), f[1][1], 'relu6')
+        x = self._bn(self._conv(x, f[2]), f[3])
+        feats = [x]
+        for blocks in net.stage:
+            for blk in blocks:
+                x = self._block(x, blk)
+            feats.append(x)
+        outputs = []
+        refined, raw = feats[-1], feats[-2]
+        for i in range(net.num_deconv_layers):
+            y = self._up_pair(refined, net.deconv_refined[i].weight, raw, net.deconv_raw[i].weight)
+            refined = self._bn(y, net.deconv_bnrelu[i][0], 'relu')
+            raw = feats[-i - 3]
+            if i > 0:
+                outputs.append(self._head(refined, net.final_refined[i - 1]) + self._head(raw, net.final_raw[i - 1]))
+        return outputs
+
+
+class TrainableLitePose(LayerWalk, torch.nn.Module):
     """LitePose as a ``torch.nn.Module`` whose parameters and buffers carry the names and shapes of ``LitePose.keys()``
     (``load_state_dict`` of a reference checkpoint and of ``LitePose.state_dict()`` both work) and whose ``forward`` returns
     the list of stage outputs, for ``core.trainer.do_train``.
@@ -323,65 +391,8 @@ class TrainableLitePose(torch.nn.Module):
         self.final_refined, self.final_raw = nn.ModuleList(f_refined), nn.ModuleList(f_raw)
         self.channel = channels
 
-    # ---- layers ----
-    def _conv(self, x, conv):
-        k, groups = conv.kernel_size[0], conv.groups
-        if self.backend == 'native' and k == 1 and groups == 1:
-            return F_.pointwise(x, conv.weight)
-        if self.backend == 'native' and groups == conv.in_channels == conv.out_channels and groups > 1:
-            return F_.depthwise(x, conv.weight, conv.stride[0])
-        if self.backend == 'native' and conv is self.first[0][0] and not x.requires_grad:
-            return F_.stem_conv(x, conv.weight)
-        return torch.nn.functional.conv2d(x, conv.weight, None, conv.stride, conv.padding, 1, groups)
-
-    def _up_pair(self, refined, w_refined, raw, w_raw):
-        if self.backend == 'native':
-            return F_.deconv_pair(refined, w_refined, raw, w_raw)
-        up = torch.nn.functional.conv_transpose2d
-        return up(refined, w_refined, None, 2, 1) + up(raw, w_raw, None, 2, 1)
-
-    def _bn(self, x, bn, act=None, residual=None):
-        if self.training:
-            bn.num_batches_tracked += 1
-        if self.backend == 'native':
-            return F_.batch_norm_act(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, act, residual, self.training,
-                                     bn.momentum, bn.eps)
-        y = torch.nn.functional.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, self.training,
-                                           bn.momentum, bn.eps)
-        if act == 'relu6':
-            y = torch.nn.functional.relu6(y)
-        elif act == 'relu':
-            y = torch.relu(y)
-        return y if residual is None else y + residual
-
-    def _block(self, x, blk):
-        y = self._bn(self._conv(x, blk.inv[0]), blk.inv[1], 'relu6')
-        y = self._bn(self._conv(y, blk.depth_conv[0]), blk.depth_conv[1], 'relu6')
-        return self._bn(self._conv(y, blk.point_conv[0]), blk.point_conv[1], None, x if blk.residual else None)
-
-    def _head(self, x, head):
-        c = head.conv
-        return self._conv(self._bn(self._conv(x, c[0]), c[1], 'relu'), c[3])
-
     def forward(self, x):
-        f = self.first
-        x = self._bn(self._conv(x, f[0][0]), f[0][1], 'relu6')
-        x = self._bn(self._conv(x, f[1][0]), f[1][1], 'relu6')
-        x = self._bn(self._conv(x, f[2]), f[3])
-        feats = [x]
-        for blocks in self.stage:
-            for blk in blocks:
-                x = self._block(x, blk)
-            feats.append(x)
-        outputs = []
-        refined, raw = feats[-1], feats[-2]
-        for i in range(self.num_deconv_layers):
-            y = self._up_pair(refined, self.deconv_refined[i].weight, raw, self.deconv_raw[i].weight)
-            refined = self._bn(y, self.deconv_bnrelu[i][0], 'relu')
-            raw = feats[-i - 3]
-            if i > 0:
-                outputs.append(self._head(refined, self.final_refined[i - 1]) + self._head(raw, self.final_raw[i - 1]))
-        return outputs
+        return self.walk(self, x)
 
     def to_engine(self, storage=None):
         """A ``LitePose`` inference handle loaded from this module's ``state_dict``: validation on the inference path."""

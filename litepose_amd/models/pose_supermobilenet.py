@@ -11,12 +11,14 @@ The result goes to ``PoseEngine(cfg, cfg_arch, state_dict)`` / ``pose_mobilenet`
 """
 import ctypes as C
 import random
+import types
 from collections import OrderedDict
 
 import torch
 import torch.nn.functional as F
 
 from .. import _native as nv
+from ..nn import functional as F_
 from . import pose_mobilenet
 
 INPUT_CHANNEL = 24
@@ -224,8 +226,9 @@ class SuperLitePose(object):
             raise nv.LitePoseNativeError('load_state_dict() has not been called')
 
     def forward(self, x):
-        raise NotImplementedError('the supernet itself is not run: slice it (sub_state_dict) or calibrate() a '
-                                  'sub-network and run that as pose_mobilenet')
+        raise NotImplementedError('this host-side supernet is not run: slice it (sub_state_dict) or calibrate() a '
+                                  'sub-network and run that as pose_mobilenet; the supernet that runs and trains is '
+                                  'get_train_net(cfg)')
 
     __call__ = forward
 
@@ -375,7 +378,218 @@ class SuperLitePose(object):
 
 
 def get_pose_net(cfg, is_train=False):
-    """pose_supermobilenet.py:199-218.  Initialising from a pre-trained backbone (is_train and INIT_WEIGHTS, with the
-    channel re-ordering that follows it) is a training feature and out of scope: weights arrive through
-    ``load_state_dict``."""
+    """pose_supermobilenet.py:199-218: the supernet as the evaluation side uses it; weights arrive through
+    ``load_state_dict``.  The training side -- the sampled forward, and the pre-trained initialisation with the channel
+    re-ordering that follows it (is_train and INIT_WEIGHTS) -- is ``get_train_net``."""
     return SuperLitePose(cfg)
+
+
+# ---- the trainable supernet -----------------------------------------------------------------------------------------
+def _layer(**kw):
+    return types.SimpleNamespace(**kw)
+
+
+class TrainableSuperLitePose(pose_mobilenet.LayerWalk, torch.nn.Module):
+    """The weight-sharing supernet as a ``torch.nn.Module`` (reference ``SuperLitePose``): its ``state_dict`` has exactly
+    the keys and shapes of ``SuperLitePose.keys()``, so ``SuperLitePose(cfg).load_state_dict(module.state_dict())`` hands a
+    trained supernet to calibration and search.
+
+    ``forward(x, cfg_arch=None)`` runs a sub-network whose parameters are slices of the supernet's
+    (layers/super_layers.py): ``cfg_arch``, or ``self.arch_manager.random_sample()`` -- which honours ``is_search`` /
+    ``search_arch`` -- left in ``last_arch``.  The layers are ``TrainableLitePose``'s walk on the sliced tensors.  BatchNorm
+    running statistics are prefix views of the supernet's buffers and move in place; only the two plain BatchNorms of the
+    stem advance ``num_batches_tracked`` (``SuperBatchNorm2d.forward`` bypasses the counter).  ``first.0`` and ``first.1``
+    are not sliced.  A parameter the sampled sub-network does not touch keeps ``grad is None``.
+
+    ``backend='native'``: the slices of every learnable tensor are gathered into one packed buffer by one library call and
+    their gradients come back as full-size tensors, zero outside the slice, from one more
+    (``nn.functional.subnet_params``); the descriptor table is built once per architecture, kept on the device, and
+    rebuilt when a parameter's ``data_ptr()`` has changed.  float32 on the GPU.
+    ``backend='torch'``: the same module on torch slicing, for any device and dtype."""
+
+    def __init__(self, cfg, backend='native'):
+        super().__init__()
+        if backend not in ('native', 'torch'):
+            raise ValueError("backend must be 'native' or 'torch'")
+        nn, conv = torch.nn, pose_mobilenet._conv
+        self.backend = backend
+        self._cfg = cfg
+        self._host = [SuperLitePose(cfg)]             # in a list: not a sub-module, never in the state_dict
+        host = self._host[0]
+        self.arch_manager = ArchManager(cfg)
+        self.last_arch = None
+        self.first = nn.Sequential(
+            nn.Sequential(conv(3, 32, 3, 2), nn.BatchNorm2d(32), nn.ReLU6()),
+            nn.Sequential(conv(32, 32, 3, 1, 32), nn.BatchNorm2d(32), nn.ReLU6()),
+            conv(32, INPUT_CHANNEL, 1), nn.BatchNorm2d(INPUT_CHANNEL))
+        stages = []
+        for blocks in host.stages:
+            mods = []
+            for b in blocks:
+                blk = nn.Module()
+                feat = b['feat']
+                blk.inv = nn.Sequential(conv(b['inp'], feat, 1), nn.BatchNorm2d(feat), nn.ReLU6())
+                blk.depth_conv = nn.Sequential(conv(feat, feat, 7, b['stride'], feat), nn.BatchNorm2d(feat), nn.ReLU6())
+                blk.point_conv = nn.Sequential(conv(feat, b['oup'], 1), nn.BatchNorm2d(b['oup']))
+                blk.Linear5x5, blk.Linear3x3 = nn.Linear(25, 25), nn.Linear(9, 9)
+                blk.stride, blk.residual = b['stride'], b['stride'] == 1 and b['inp'] == b['oup']
+                mods.append(blk)
+            stages.append(nn.Sequential(*mods))
+        self.stage = nn.ModuleList(stages)
+        up = lambda cin, cout: nn.ConvTranspose2d(cin, cout, 4, 2, 1, bias=False)  # noqa: E731
+        self.deconv_refined = nn.ModuleList([up(host._deconv_in(i)[0], host.filters[i]) for i in range(3)])
+        self.deconv_raw = nn.ModuleList([up(host._deconv_in(i)[1], host.filters[i]) for i in range(3)])
+        self.deconv_bnrelu = nn.ModuleList([nn.Sequential(nn.BatchNorm2d(f), nn.ReLU()) for f in host.filters])
+        self.num_deconv_layers = 3
+        self.final_channel = list(host.final_channel)
+        f_refined, f_raw = [], []
+        for i in range(1, 3):
+            for lst, c in ((f_refined, host.filters[i]), (f_raw, host.channel[-i - 3])):
+                head = nn.Module()
+                head.conv = nn.Sequential(conv(c, c, 5, 1, c), nn.BatchNorm2d(c), nn.ReLU(),
+                                          conv(c, self.final_channel[i - 1], 1))
+                lst.append(head)
+        self.final_refined, self.final_raw = nn.ModuleList(f_refined), nn.ModuleList(f_raw)
+        self._tables = {}
+
+    # ---- the sub-network: one description for the descriptor table, the torch slices and the per-step layers ----
+    def _assemble(self, plan, take):
+        """The layers of the sub-network ``plan`` for ``LayerWalk.walk``.  ``take(spec)`` hands out the sliced tensor of one
+        learnable tensor (``SubnetTable`` has the fields of ``spec``); the calls come in one fixed order."""
+        def pw(m, out, inn):
+            w = take(dict(param=m.weight, kind=0, rows=out, cols=inn, shape=(out, inn, 1, 1)))
+            return _layer(weight=w, kernel_size=(1, 1), groups=1, in_channels=inn, out_channels=out, stride=(1, 1),
+                          padding=(0, 0))
+
+        def dw(w, c, k, stride):
+            return _layer(weight=w, kernel_size=(k, k), groups=c, in_channels=c, out_channels=c, stride=(stride, stride),
+                          padding=(k // 2, k // 2))
+
+        def bn(m, c):
+            return _layer(weight=take(dict(param=m.weight, kind=1, rows=c, shape=(c,))),
+                          bias=take(dict(param=m.bias, kind=1, rows=c, shape=(c,))),
+                          running_mean=m.running_mean[:c], running_var=m.running_var[:c], momentum=m.momentum, eps=m.eps,
+                          num_batches_tracked=0)        # SuperBatchNorm2d does not count its batches
+
+        def up(m, inn, out):
+            return _layer(weight=take(dict(param=m.weight, kind=0, rows=inn, cols=out, shape=(inn, out, 4, 4))))
+
+        f = self.first
+        net = _layer(first=[f[0], f[1], pw(f[2], plan['c0'], 32), bn(f[3], plan['c0'])], stage=[],
+                     num_deconv_layers=3)
+        for s, blocks in enumerate(plan['stages']):
+            layers = []
+            for b, blk in enumerate(blocks):
+                m, mid, k = self.stage[s][b], blk['mid'], blk['k']
+                inv = [pw(m.inv[0], mid, blk['inp']), bn(m.inv[1], mid)]
+                lin = None if k == 7 else (m.Linear5x5 if k == 5 else m.Linear3x3)
+                w = take(dict(param=m.depth_conv[0].weight, kind=2, rows=mid, cols=k, shape=(mid, 1, k, k),
+                              lin_w=None if lin is None else lin.weight, lin_b=None if lin is None else lin.bias))
+                depth = [dw(w, mid, k, m.stride), bn(m.depth_conv[1], mid)]
+                point = [pw(m.point_conv[0], blk['oup'], mid), bn(m.point_conv[1], blk['oup'])]
+                layers.append(_layer(inv=inv, depth_conv=depth, point_conv=point, stride=m.stride, residual=m.residual))
+            net.stage.append(layers)
+        ch, fl = plan['channel'], plan['filters']
+        net.deconv_refined = [up(self.deconv_refined[i], ch[-1] if i == 0 else fl[i - 1], fl[i]) for i in range(3)]
+        net.deconv_raw = [up(self.deconv_raw[i], ch[-i - 2], fl[i]) for i in range(3)]
+        net.deconv_bnrelu = [[bn(self.deconv_bnrelu[i][0], fl[i])] for i in range(3)]
+        net.final_refined, net.final_raw = [], []
+        for i in range(1, 3):
+            for lst, mods, c in ((net.final_refined, self.final_refined, fl[i]), (net.final_raw, self.final_raw, ch[-i - 3])):
+                m = mods[i - 1].conv
+                w = take(dict(param=m[0].weight, kind=1, rows=c * 25, shape=(c, 1, 5, 5)))
+                lst.append(_layer(conv=[dw(w, c, 5, 1), bn(m[1], c), None, pw(m[3], self.final_channel[i - 1], c)]))
+        return net
+
+    @staticmethod
+    def _torch_slice(spec):
+        p, shape = spec['param'], spec['shape']
+        if spec['kind'] == 0:
+            return p[:spec['rows'], :spec['cols']]
+        if spec['kind'] == 1:
+            return p[:shape[0]]
+        k = spec['cols']
+        l, r = 3 - k // 2, 3 + k // 2 + 1
+        w = p[:spec['rows'], :, l:r, l:r]
+        if k != 7:                     # the window transform: Linear5x5 / Linear3x3 on the flattened centre crop
+            w = F.linear(w.reshape(shape[0], 1, -1), spec['lin_w'], spec['lin_b']).reshape(shape)
+        return w
+
+    def _table(self, cfg_arch, plan):
+        key = repr(plan)
+        table = self._tables.get(key)
+        device = self.first[2].weight.device
+        if table is None or table.device != device or table.stale():
+            specs = []
+            self._assemble(plan, specs.append)
+            table = self._tables[key] = F_.SubnetTable(specs, device)
+        return table
+
+    def forward(self, x, cfg_arch=None):
+        if cfg_arch is None:
+            cfg_arch = self.arch_manager.random_sample()
+            if cfg_arch is None:
+                raise ValueError('arch_manager.is_search is set without a search_arch')
+        self.last_arch = cfg_arch
+        plan = self._host[0]._sub_plan(cfg_arch)
+        if self.backend == 'native':
+            table = self._table(cfg_arch, plan)
+            views = iter(F_.subnet_params(table, *table.params))
+            net = self._assemble(plan, lambda spec: next(views))
+        else:
+            net = self._assemble(plan, self._torch_slice)
+        return self.walk(net, x)
+
+    # ---- initialisation from a pre-trained backbone (pose_supermobilenet.py:167-218) ----
+    @torch.no_grad()
+    def re_organize_weights(self):
+        """Re-order the channels between layers by importance -- the L1 norm of the weights the NEXT layer puts on them,
+        descending -- so that a prefix slice keeps the channels that matter most: the output of ``first.2`` / ``first.3``
+        by ``stage.0.0.inv``, and the output of every stage but the last by the first expansion of the next (every
+        block's ``point_conv`` and, behind the first block, the residual blocks' ``inv`` input follow).  Returns the list of
+        permutations, in that order."""
+        def reorder(t, dim, idx):
+            t.data = torch.index_select(t.data, dim, idx)
+
+        def reorder_bn(bn, idx):
+            for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+                reorder(t, 0, idx)
+
+        def importance(w):
+            return torch.sort(w.data.abs().sum(dim=(0, 2, 3)), dim=0, descending=True)[1]
+
+        perms = []
+        nxt = self.stage[0][0].inv[0].weight
+        idx = importance(nxt)
+        reorder(self.first[2].weight, 0, idx)
+        reorder_bn(self.first[3], idx)
+        reorder(nxt, 1, idx)
+        perms.append(idx)
+        for s in range(len(self.stage) - 1):
+            nxt = self.stage[s + 1][0].inv[0].weight
+            idx = importance(nxt)
+            reorder(nxt, 1, idx)
+            for b, blk in enumerate(self.stage[s]):
+                reorder_bn(blk.point_conv[1], idx)
+                reorder(blk.point_conv[0].weight, 0, idx)
+                if b > 0:
+                    reorder(blk.inv[0].weight, 1, idx)
+            perms.append(idx)
+        self._tables = {}
+        return perms
+
+
+def get_train_net(cfg, backend='native', init_from=None):
+    """The trainable counterpart of ``get_pose_net``: a ``TrainableSuperLitePose``.  ``init_from``: the state dict of a
+    pre-trained backbone (the reference's ``is_train and INIT_WEIGHTS`` path): its ``final*`` and ``deconv*`` tensors are
+    dropped, a ``module.`` prefix is stripped, the rest is loaded non-strictly and the channels are re-organised."""
+    model = TrainableSuperLitePose(cfg, backend)
+    if init_from is not None:
+        keep = OrderedDict()
+        for k, v in init_from.items():
+            if 'final' in k or 'deconv' in k:
+                continue
+            keep[k[7:] if 'module' in k else k] = v
+        model.load_state_dict(keep, strict=False)
+        model.re_organize_weights()
+    return model

@@ -331,3 +331,149 @@ def batch_norm_act(x, gamma, beta, running_mean, running_var, act=None, residual
         raise ValueError('act must be one of %s' % sorted(k for k in ACTS if k))
     return _BatchNormAct.apply(x, gamma, beta, residual, running_mean, running_var, act, bool(training), float(momentum),
                                float(eps))
+
+
+# ---------------------------------------------------------------------------------- supernet: sliced parameters
+def _a64(n):
+    return (int(n) + 63) // 64 * 64
+
+
+class SubnetTable(object):
+    """The descriptor table of one sampled sub-network (include/litepose_amd.h, lp_subnet_desc), on the device.
+
+    ``specs``: one dict per learnable tensor of the sub-network, in the order ``subnet_params`` returns them:
+    ``param`` (the supernet's tensor), ``kind`` 0 / 1 / 2, ``rows``, ``cols``, ``shape`` (of the sliced tensor) and, for a
+    window with k < 7, ``lin_w`` / ``lin_b``.  ``params`` is the list of supernet tensors the table reads -- every ``param``
+    and, behind its window, the ``lin_w`` / ``lin_b`` pair -- in the order ``subnet_params`` takes them.  The table holds raw
+    addresses: ``stale()`` tells whether a parameter's ``data_ptr()`` has changed since it was built."""
+
+    def __init__(self, specs, device):
+        rows, self.params, self.views, self.grads = [], [], [], []
+        sub = full = 0
+        for sp in specs:
+            p, kind = sp['param'], int(sp['kind'])
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError('supernet parameters must be contiguous float32 tensors')
+            d = nv.LpSubnetDesc(src=p.data_ptr(), sub_offset=sub, full_offset=full, kind=kind, rows=int(sp['rows']),
+                                cols=int(sp.get('cols', 0)), t=1)
+            shape = tuple(int(v) for v in sp['shape'])
+            numel = 1
+            for v in shape:
+                numel *= v
+            self.params.append(p)
+            self.grads.append((full, p.numel(), tuple(p.shape)))
+            span = p.numel()
+            if kind == 0:
+                d.R, d.C = int(p.shape[0]), int(p.shape[1])
+                d.t = p.numel() // (d.R * d.C)
+            elif kind == 1:
+                d.R = p.numel()
+            else:
+                d.R = int(p.shape[0])
+                if d.cols != 7:
+                    lw, lb = sp['lin_w'], sp['lin_b']
+                    kk = d.cols * d.cols
+                    if tuple(lw.shape) != (kk, kk) or tuple(lb.shape) != (kk,) or not lw.is_contiguous():
+                        raise ValueError('the window transform of a k x k window is [k*k, k*k] with a [k*k] bias')
+                    d.lin_w, d.lin_b = lw.data_ptr(), lb.data_ptr()
+                    off_l = full + _a64(p.numel())
+                    off_b = off_l + _a64(kk * kk)
+                    self.params += [lw, lb]
+                    self.grads += [(off_l, kk * kk, (kk, kk)), (off_b, kk, (kk,))]
+                    span = off_b + kk - full
+            self.views.append((sub, numel, shape))
+            rows.append(d)
+            sub += _a64(numel)
+            full += _a64(span)
+        self.count, self.sub_elems, self.full_elems = len(rows), sub, full
+        table = (nv.LpSubnetDesc * len(rows))(*rows)
+        self.table = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(device)
+        self.device = self.table.device
+        self._ptrs = tuple(p.data_ptr() for p in self.params)
+
+    def stale(self):
+        return self._ptrs != tuple(p.data_ptr() for p in self.params)
+
+
+class _SubnetParams(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, *full_params):
+        if len(full_params) != len(table.params) or any(a.data_ptr() != b for a, b in zip(full_params, table._ptrs)):
+            raise ValueError('subnet_params: the parameters are not the ones the table was built from')
+        sub = torch.empty(table.sub_elems, dtype=torch.float32, device=table.device)
+        nv.check(nv.lib().lp_subnet_gather(nv.dptr(table.table), table.count, nv.dptr(sub), table.sub_elems,
+                                           nv.stream_ptr()), 'lp_subnet_gather')
+        ctx.table = table
+        return tuple(sub[o:o + n].view(shape) for o, n, shape in table.views)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        table = ctx.table
+        if table.stale():
+            raise RuntimeError('subnet_params: a parameter moved between the forward and the backward')
+        gsub = torch.empty(table.sub_elems, dtype=torch.float32, device=table.device)
+        dst, src = [], []
+        for (o, n, shape), g in zip(table.views, grads):
+            if g is None:
+                gsub[o:o + n].zero_()
+            else:
+                dst.append(gsub[o:o + n].view(shape))
+                src.append(g)
+        torch._foreach_copy_(dst, src)
+        full = torch.empty(table.full_elems, dtype=torch.float32, device=table.device)
+        nv.check(nv.lib().lp_subnet_scatter_grad(nv.dptr(table.table), table.count, nv.dptr(gsub), table.sub_elems,
+                                                 nv.dptr(full), table.full_elems, nv.stream_ptr()),
+                 'lp_subnet_scatter_grad')
+        return (None,) + tuple(full[o:o + n].view(shape) if need else None
+                               for (o, n, shape), need in zip(table.grads, ctx.needs_input_grad[1:]))
+
+
+def subnet_params(descs, *full_params):
+    """The learnable tensors of a sampled sub-network as slices of the supernet's ``full_params``: ``descs`` is the
+    ``SubnetTable`` built from them (``full_params`` must be ``descs.params``, passed so that autograd sees them).  Forward:
+    ONE ``lp_subnet_gather`` into one packed buffer; returns a view of it per tensor, in the table's order.  Backward: the
+    upstream gradients are packed (one multi-tensor copy) and ONE ``lp_subnet_scatter_grad`` writes one packed buffer that
+    holds the full-size gradient of every parameter -- zero outside its slice -- of which the returned gradients are
+    views.  The parameters must not change between forward and backward."""
+    return _SubnetParams.apply(descs, *full_params)
+
+
+def train_resize(images, heatmaps, masks, joints, size, base):
+    """The supernet's random-resolution resize of a batch (lib/core/trainer.py:49-59), one ``lp_train_resize`` call:
+    ``images`` [N,3,base,base] -> [N,3,size,size]; per stage s ``heatmaps[s]`` [N,J,R,R] and ``masks[s]`` [N,R,R]
+    (R = base / 4 * 2^s) -> size / 4 * 2^s, nearest; ``joints[s]`` int32 [N,M,J,2]: the flat cell index is remapped as the
+    reference does it (modulus ``base``, multiplier ``size`` for every stage).  -> (images, heatmaps, masks, joints), new
+    tensors."""
+    images = _f32(images, 'images', 4)
+    stages = len(heatmaps)
+    if len(masks) != stages or len(joints) != stages:
+        raise ValueError('heatmaps, masks and joints are lists of one tensor per stage')
+    N, c, I = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    size, base = int(size), int(base)
+    if c != 3 or int(images.shape[3]) != I:
+        raise ValueError('images must be [N, 3, I, I]')
+    heatmaps = [_f32(h, 'heatmaps', 4) for h in heatmaps]
+    masks = [_f32(m, 'masks', 3) for m in masks]
+    res, J, M = [], None, None
+    for h, m, j in zip(heatmaps, masks, joints):
+        R = int(h.shape[2])
+        if not isinstance(j, torch.Tensor) or j.dtype != torch.int32 or not j.is_cuda or j.dim() != 4 or j.shape[3] != 2:
+            raise ValueError('joints must be int32 CUDA tensors [N, M, J, 2]')
+        J, M = int(h.shape[1]) if J is None else J, int(j.shape[1]) if M is None else M
+        if tuple(h.shape) != (N, J, R, R) or tuple(m.shape) != (N, R, R) or tuple(j.shape) != (N, M, J, 2):
+            raise ValueError('heatmaps [N,J,R,R], masks [N,R,R] and joints [N,M,J,2] of a stage do not belong together')
+        res.append(R)
+    joints = [j.detach().contiguous() for j in joints]
+    dev = images.device
+    if size < 8 or size % 8:
+        raise ValueError('size must be a positive multiple of 8')
+    images_o = torch.empty((N, 3, size, size), dtype=torch.float32, device=dev)
+    heat_o = [torch.empty((N, J, (size // 4) << s, (size // 4) << s), dtype=torch.float32, device=dev)
+              for s in range(stages)]
+    mask_o = [torch.empty((N, (size // 4) << s, (size // 4) << s), dtype=torch.float32, device=dev) for s in range(stages)]
+    joint_o = [torch.empty_like(j) for j in joints]
+    arr = lambda ts: (nv.vp * max(len(ts), 1))(*[t.data_ptr() for t in ts])  # noqa: E731
+    nv.check(nv.lib().lp_train_resize(nv.dptr(images), nv.dptr(images_o), N, I, size, base, stages, J or 0, M or 0,
+                                      (nv.C.c_int32 * max(stages, 1))(*res), arr(heatmaps), arr(masks), arr(joints),
+                                      arr(heat_o), arr(mask_o), arr(joint_o), nv.stream_ptr()), 'lp_train_resize')
+    return images_o, heat_o, mask_o, joint_o

@@ -1,0 +1,198 @@
+"""Buffer contract of the supernet-training calls (include/litepose_amd.h, "supernet training") with tests/_poison.py:
+lp_subnet_gather, lp_subnet_scatter_grad and lp_train_resize write every element of every output whatever the buffers
+held before (Z, N and H runs agree bitwise), keep off the guards, leave their inputs alone, and answer every documented
+refusal before anything is written."""
+import ctypes as C
+
+import pytest
+import torch
+
+import _poison as po
+import _supertrain_ref as st
+from litepose_amd import _native as nv
+from litepose_amd.nn import functional as F_
+
+pytestmark = pytest.mark.gpu
+
+
+def _codes():
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'litepose_amd.h')) as f:
+        src = f.read()
+    return {k: int(v) for k, v in re.findall(r'(LP_ERR_\w+)\s*=\s*(-\d+)', src)}
+
+
+CODES = _codes()
+MID = 48
+
+
+def _subnet(arena):
+    g = torch.Generator().manual_seed(9)
+    rn = lambda *s: arena.inp(torch.randn(*s, generator=g).cuda())  # noqa: E731
+    pw, dw7, gamma, dw5, L5, b5, up, dw3, L3, b3 = (rn(32, 144, 1, 1), rn(144, 1, 7, 7), rn(144), rn(144, 1, 7, 7),
+                                                    rn(25, 25), rn(25), rn(40, 24, 4, 4), rn(144, 1, 7, 7), rn(9, 9), rn(9))
+    specs = [dict(param=pw, kind=0, rows=24, cols=32, shape=(24, 32, 1, 1)),
+             dict(param=dw7, kind=2, rows=MID, cols=7, shape=(MID, 1, 7, 7), lin_w=None, lin_b=None),
+             dict(param=gamma, kind=1, rows=MID - 1, shape=(MID - 1,)),               # a length that is no multiple of 4
+             dict(param=dw5, kind=2, rows=MID, cols=5, shape=(MID, 1, 5, 5), lin_w=L5, lin_b=b5),
+             dict(param=up, kind=0, rows=16, cols=8, shape=(16, 8, 4, 4)),
+             dict(param=dw3, kind=2, rows=MID, cols=3, shape=(MID, 1, 3, 3), lin_w=L3, lin_b=b3)]
+    return F_.SubnetTable(specs, 'cuda')
+
+
+def _run_subnet(pattern):
+    arena = po.Arena(pattern)
+    table = _subnet(arena)
+    desc = arena.inp(table.table, what='d_desc')
+    # sizes that end inside a group of four: the tail stores are element by element
+    sub_elems, full_elems = table.sub_elems - 61, table.full_elems - 53
+    sub = arena.out((sub_elems,), what='sub_out')
+    L = nv.lib()
+    nv.check(L.lp_subnet_gather(nv.dptr(desc), table.count, nv.dptr(sub), sub_elems, nv.stream_ptr()), 'lp_subnet_gather')
+    gsub = arena.inp(torch.randn(sub_elems, generator=torch.Generator().manual_seed(2)).cuda(), what='d_grad_sub')
+    full = arena.out((full_elems,), what='full_grad_out')
+    nv.check(L.lp_subnet_scatter_grad(nv.dptr(desc), table.count, nv.dptr(gsub), sub_elems, nv.dptr(full), full_elems,
+                                      nv.stream_ptr()), 'lp_subnet_scatter_grad')
+    arena.check()
+    return sub.clone(), full.clone()
+
+
+@pytest.fixture(scope='module')
+def subnet_ref():
+    return _run_subnet('Z')
+
+
+@pytest.mark.parametrize('pattern', ['N', 'H'])
+def test_subnet_calls_write_everything_and_nothing_else(subnet_ref, pattern):
+    got = _run_subnet(pattern)
+    for name, a, b in zip(('sub_out', 'full_grad_out'), got, subnet_ref):
+        assert po.still_poisoned(a, b, pattern) == [], name
+        assert po.bitwise_equal(a, b), (name, po.first_difference(a, b))
+
+
+def test_a_malformed_descriptor_yields_zeros(subnet_ref):
+    arena = po.Arena('N')
+    table = _subnet(arena)
+    rows = (nv.LpSubnetDesc * table.count).from_buffer_copy(bytes(table.table.cpu().numpy()))
+    rows[0].rows = 33                                     # more rows than the tensor has
+    rows[3].lin_b = None                                  # a k = 5 window without its bias
+    desc = arena.inp(torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8).cuda())
+    sub, full = arena.out((table.sub_elems,)), arena.out((table.full_elems,))
+    L = nv.lib()
+    nv.check(L.lp_subnet_gather(nv.dptr(desc), table.count, nv.dptr(sub), table.sub_elems, nv.stream_ptr()))
+    gsub = arena.inp(torch.ones(table.sub_elems).cuda())
+    nv.check(L.lp_subnet_scatter_grad(nv.dptr(desc), table.count, nv.dptr(gsub), table.sub_elems, nv.dptr(full),
+                                      table.full_elems, nv.stream_ptr()))
+    arena.check()
+    ref_sub, ref_full = subnet_ref
+    for i in (0, 3):
+        o, n, _ = table.views[i]
+        assert not bool(sub[o:o + n].any())
+    o1 = table.views[1][0]
+    assert po.bitwise_equal(sub[o1:o1 + 64], ref_sub[o1:o1 + 64])
+    f3, f4 = rows[3].full_offset, rows[4].full_offset
+    assert not bool(full[f3:f4].any()) and not bool(full[:rows[1].full_offset].any())
+    assert bool(torch.isfinite(full).all())
+
+
+def test_subnet_refusals_come_before_any_write():
+    arena = po.Arena('N')
+    table = _subnet(arena)
+    desc = arena.inp(table.table)
+    sub, full = arena.out((table.sub_elems,)), arena.out((table.full_elems,))
+    gsub = arena.inp(torch.ones(table.sub_elems).cuda())
+    L, s = nv.lib(), nv.stream_ptr()
+    d, n, e, fe = nv.dptr(desc), table.count, table.sub_elems, table.full_elems
+    off = lambda t, b: C.c_void_p(t.data_ptr() + b)  # noqa: E731
+    bad = CODES['LP_ERR_INVALID_ARG']
+    assert L.lp_subnet_gather(None, n, nv.dptr(sub), e, s) == bad
+    assert L.lp_subnet_gather(d, 0, nv.dptr(sub), e, s) == bad
+    assert L.lp_subnet_gather(d, 1025, nv.dptr(sub), e, s) == bad
+    assert L.lp_subnet_gather(d, n, None, e, s) == bad
+    assert L.lp_subnet_gather(d, n, nv.dptr(sub), 0, s) == bad
+    assert L.lp_subnet_gather(d, n, off(sub, 4), e - 1, s) == bad
+    assert L.lp_subnet_gather(off(desc, 4), n, nv.dptr(sub), e, s) == bad
+    assert L.lp_subnet_gather(d, n, nv.dptr(sub), 1 << 31, s) == CODES['LP_ERR_UNSUPPORTED']
+    assert L.lp_subnet_scatter_grad(d, n, None, e, nv.dptr(full), fe, s) == bad
+    assert L.lp_subnet_scatter_grad(d, n, nv.dptr(gsub), e, None, fe, s) == bad
+    assert L.lp_subnet_scatter_grad(d, n, nv.dptr(gsub), e, nv.dptr(full), 0, s) == bad
+    assert L.lp_subnet_scatter_grad(d, n, off(gsub, 8), e - 2, nv.dptr(full), fe, s) == bad
+    assert L.lp_subnet_scatter_grad(d, n, nv.dptr(gsub), e, off(full, 4), fe - 1, s) == bad
+    assert L.lp_subnet_scatter_grad(d, n, nv.dptr(gsub), e, nv.dptr(full), 1 << 31, s) == CODES['LP_ERR_UNSUPPORTED']
+    assert b'full_elems' in L.lp_last_error()
+    arena.check()
+    assert bool(torch.isnan(sub).all()) and bool(torch.isnan(full).all())
+
+
+# ------------------------------------------------------------------ lp_train_resize
+N, J, M, BASE, SIZE = 2, 3, 2, 64, 40
+
+
+def _resize_args(arena, stages=2):
+    images, heat, mask, joints = st.make_batch(BASE, N, J, M)
+    d_images = arena.inp(images.cuda(), what='d_images')
+    d_heat = [arena.inp(h.cuda(), what='d_heatmaps') for h in heat[:stages]]
+    d_mask = [arena.inp(m.cuda(), what='d_masks') for m in mask[:stages]]
+    d_joints = [arena.inp(j.int().cuda(), 4, what='d_joints') for j in joints[:stages]]
+    outs = dict(images=arena.out((N, 3, SIZE, SIZE), what='images_out'),
+                heat=[arena.out((N, J, SIZE // 4 << s, SIZE // 4 << s), what='heatmaps_out') for s in range(stages)],
+                mask=[arena.out((N, SIZE // 4 << s, SIZE // 4 << s), what='masks_out') for s in range(stages)],
+                joints=[arena.out((N, M, J, 2), torch.int32, 4, what='joints_out') for s in range(stages)])
+    arr = lambda ts: (nv.vp * len(ts))(*[t.data_ptr() for t in ts])  # noqa: E731
+    res = (C.c_int32 * stages)(*[BASE // 4 << s for s in range(stages)])
+    args = [nv.dptr(d_images), nv.dptr(outs['images']), N, BASE, SIZE, BASE, stages, J, M, res, arr(d_heat), arr(d_mask),
+            arr(d_joints), arr(outs['heat']), arr(outs['mask']), arr(outs['joints']), nv.stream_ptr()]
+    return args, outs
+
+
+def _flat(outs):
+    return [outs['images']] + outs['heat'] + outs['mask'] + outs['joints']
+
+
+def _run_resize(pattern, stages=2):
+    arena = po.Arena(pattern)
+    args, outs = _resize_args(arena, stages)
+    nv.check(nv.lib().lp_train_resize(*args), 'lp_train_resize')
+    arena.check()
+    return [t.clone() for t in _flat(outs)]
+
+
+@pytest.mark.parametrize('stages', [1, 2])
+def test_train_resize_writes_everything_and_nothing_else(stages):
+    ref = _run_resize('Z', stages)
+    for pattern in ('N', 'H'):
+        got = _run_resize(pattern, stages)
+        for i, (a, b) in enumerate(zip(got, ref)):
+            assert po.still_poisoned(a, b, pattern) == [], (pattern, i)
+            assert po.bitwise_equal(a, b), (pattern, i, po.first_difference(a, b))
+
+
+def test_train_resize_refusals_come_before_any_write():
+    arena = po.Arena('H')
+    args, outs = _resize_args(arena)
+    L = nv.lib()
+    bad = CODES['LP_ERR_INVALID_ARG']
+
+    def call(**change):
+        a = list(args)
+        for k, v in change.items():
+            a[int(k[1:])] = v
+        return L.lp_train_resize(*a)
+
+    assert call(a0=None) == bad and call(a1=None) == bad and call(a9=None) == bad and call(a13=None) == bad
+    assert call(a2=0) == bad and call(a7=0) == bad and call(a8=0) == bad
+    assert call(a6=0) == bad and call(a6=3) == bad
+    assert call(a4=36) == bad and call(a4=0) == bad                    # S: a positive multiple of 8
+    assert call(a3=48) == bad                                          # I != B
+    assert call(a5=72, a3=72) == bad                                   # B: a multiple of 16
+    assert call(a9=(C.c_int32 * 2)(16, 16)) == bad                     # R_1 is not B / 4 * 2
+    assert call(a13=(nv.vp * 2)(outs['heat'][0].data_ptr(), 0)) == bad
+    assert call(a1=C.c_void_p(outs['images'].data_ptr() + 4)) == bad
+    assert call(a15=(nv.vp * 2)(outs['joints'][0].data_ptr() + 2, outs['joints'][1].data_ptr())) == bad
+    assert call(a4=32768, a5=32768, a3=32768, a9=(C.c_int32 * 2)(8192, 16384)) == CODES['LP_ERR_UNSUPPORTED']
+    arena.check()
+    p = po.poison_bits(torch.float32, 'H')
+    for t in _flat(outs):
+        assert bool((po.as_bits(t) == po.poison_bits(t.dtype, 'H')).all())
+    assert p == 0x7F7F7F7F

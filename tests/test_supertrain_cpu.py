@@ -1,0 +1,259 @@
+"""Supernet training without a GPU: ``pose_supermobilenet.get_train_net(cfg, backend='torch')`` on the CPU against the
+real reference's training step (tests/golden/golden_supertrain.npz, written by tests/golden/gen_golden_supertrain.py), the
+sampling order of ``do_train``, the channel re-ordering, the integer rules of ``lp_train_resize`` and the header.
+
+The gradient yardstick is the rule of tests/test_gpu_train_net.py on the golden's sampled elements: per tensor
+e = |g - g64|_2 / |g64|_2 may not exceed FOUR times the largest e the reference's own fp32 shows for a tensor of its kind
+(pw, dw, gamma, beta, stem, deconv, and linear for the window transforms)."""
+import json
+import os
+import random
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import _supernet_ref as sr
+import _supertrain_ref as st
+from litepose_amd import config
+from litepose_amd.core import trainer
+from litepose_amd.models import pose_supermobilenet as psm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def make_cfg(input_size=512):
+    cfg = config.get_cfg()
+    cfg.MODEL.NAME = 'pose_supermobilenet'
+    cfg.MODEL.EXTRA.NUM_DECONV_FILTERS = list(sr.FILTERS)
+    cfg.DATASET.INPUT_SIZE = input_size
+    return cfg
+
+
+@pytest.fixture(scope='module')
+def golden():
+    return st.load()
+
+
+@pytest.fixture(autouse=True)
+def one_thread():
+    """As the generator ran the reference: torch's CPU convolutions split their sums by the thread count, and the fp32
+    yardstick of the golden is the single-threaded order."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    yield
+    torch.set_num_threads(n)
+
+
+def rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.linalg.norm(a - b) / np.linalg.norm(b))
+
+
+def split(golden, tag, arch, name):
+    """{key: sampled elements} of the concatenated golden vector ``name``."""
+    shapes, idx, out, at = sr.state_dict_shapes(), st.slices(arch), {}, 0
+    for k in golden[tag + '_keys']:
+        n = st.sample(shapes[str(k)], idx[str(k)]).size
+        out[str(k)] = golden['%s_%s' % (tag, name)][at:at + n]
+        at += n
+    assert at == golden['%s_%s' % (tag, name)].size
+    return out
+
+
+def pools(golden, tag, arch):
+    shapes = sr.state_dict_shapes()
+    g32, g64 = split(golden, tag, arch, 'g32'), split(golden, tag, arch, 'g64')
+    p = {}
+    for k in g64:
+        kind = st.kind_of(k, shapes[k])
+        p[kind] = max(p.get(kind, 0.0), rel(g32[k], g64[k]))
+    return p, g64
+
+
+def check_step(golden, tag, arch, grads, outs, label):
+    """The 4-times rule for the gradients ``grads`` {key: full-size tensor} and the outputs."""
+    shapes, idx = sr.state_dict_shapes(), st.slices(arch)
+    p, g64 = pools(golden, tag, arch)
+    assert sorted(p) == (['beta', 'deconv', 'dw', 'gamma', 'linear', 'pw', 'stem'] if tag == 'mixed'
+                         else ['beta', 'deconv', 'dw', 'gamma', 'pw', 'stem'])
+    worst = {}
+    for k, ref in g64.items():
+        kind = st.kind_of(k, shapes[k])
+        e = rel(grads[k].detach().cpu().numpy().reshape(-1)[st.sample(shapes[k], idx[k])], ref)
+        worst[kind] = max(worst.get(kind, 0.0), e / p[kind])
+    pool_out = max(rel(golden['%s_out%d_32' % (tag, s)], golden['%s_out%d_64' % (tag, s)]) for s in range(2))
+    worst['output'] = max(rel(outs[s].detach().cpu().numpy().reshape(-1)[::st.STRIDE], golden['%s_out%d_64' % (tag, s)])
+                          for s in range(2)) / pool_out
+    for kind in sorted(worst):
+        print('%s %s %-7s largest e / (largest reference e of the kind) = %.3f' % (label, tag, kind, worst[kind]))
+    assert all(v <= 4 for v in worst.values()), worst
+
+
+def run_step(model, arch, device='cpu'):
+    model.load_state_dict(sr.make_state_dict(sr.SEED))
+    model.train()
+    for p in model.parameters():
+        p.grad = None
+    x, ups = st.step_inputs(model.final_channel)
+    outs = model(torch.from_numpy(x).to(device), arch)
+    torch.autograd.backward(outs, [torch.from_numpy(u).to(device) for u in ups])
+    return outs
+
+
+# ------------------------------------------------------------------ sampling
+def test_sample_sequence_is_the_reference_order(golden):
+    cfg = make_cfg(512)
+    am = psm.ArchManager(cfg)
+    random.seed(st.SEED_SAMPLE)
+    sizes, archs = [], []
+    for _ in range(3):
+        sizes.append(trainer.random_resolution_size(cfg))         # drawn before the forward ...
+        archs.append(am.random_sample())                           # ... which draws the architecture
+    assert sizes == [int(v) for v in golden['seq_sizes']]
+    assert archs == json.loads(str(golden['seq_archs']))
+    random.seed(int(golden['arch_random_seed']))
+    assert am.random_sample() == json.loads(str(golden['arch_random']))
+    random.seed(st.SEED_SAMPLE)
+    assert [trainer.random_resolution_size(make_cfg(128)) for _ in range(1)] == [sizes[0] // 4]
+
+
+def test_forward_samples_and_honours_search_arch():
+    m = psm.get_train_net(make_cfg(), backend='torch').eval()
+    x = torch.zeros(1, 3, 64, 64)
+    random.seed(3)
+    want = psm.ArchManager(make_cfg()).random_sample()
+    random.seed(3)
+    with torch.no_grad():
+        m(x)
+    assert m.last_arch == want
+    m.arch_manager.is_search, m.arch_manager.search_arch = True, sr.mixed_arch()
+    with torch.no_grad():
+        outs = m(x)
+    assert m.last_arch == sr.mixed_arch() and [tuple(o.shape) for o in outs] == [(1, 28, 16, 16), (1, 14, 32, 32)]
+    with pytest.raises(ValueError):
+        m(x, dict(sr.mixed_arch(), input_channel=12))
+    with pytest.raises(ValueError):
+        psm.get_train_net(make_cfg(), backend='triton')
+
+
+# ------------------------------------------------------------------ the module
+def test_state_dict_is_the_supernets():
+    cfg = make_cfg()
+    m = psm.get_train_net(cfg, backend='torch')
+    assert [(k, tuple(v.shape)) for k, v in m.state_dict().items()] == psm.SuperLitePose(cfg).keys()
+    host = psm.SuperLitePose(cfg).load_state_dict(m.state_dict())
+    assert all(torch.equal(v, m.state_dict()[k]) for k, v in host.state_dict().items())
+
+
+@pytest.mark.parametrize('which', [0, 1])
+def test_torch_backend_step_against_the_reference(golden, which):
+    tag, arch = st.step_archs(golden)[which]
+    m = psm.get_train_net(make_cfg(), backend='torch')
+    before = sr.make_state_dict(sr.SEED)
+    outs = run_step(m, arch)
+    params = dict(m.named_parameters())
+    # exactly the golden's parameters have no gradient, and every gradient is exactly zero outside its slice
+    assert [k for k, p in params.items() if p.grad is None] == [str(k) for k in golden[tag + '_none']]
+    idx = st.slices(arch)
+    for k in golden[tag + '_keys']:
+        g = params[str(k)].grad.numpy()
+        inside = st.inside_mask(g.shape, idx[str(k)])
+        assert not g[~inside].any() and g[inside].any(), k
+    check_step(golden, tag, arch, {k: p.grad for k, p in params.items()}, outs, 'torch/cpu')
+    # running statistics: the prefix moved in place, the rest did not; only the stem's BatchNorms count their batches
+    after = m.state_dict()
+    moved = dict(sr.bn_layers(arch))
+    run, at = golden[tag + '_run32'], 0
+    for q in ('running_mean', 'running_var'):
+        for p, c in sr.bn_layers(arch):
+            s = sr.sample_index(c)
+            assert np.allclose(after[p + '.' + q][:c].numpy()[s], run[at:at + s.size], rtol=1e-4, atol=1e-6), (p, q)
+            at += s.size
+    for k, v in after.items():
+        p, q = k.rsplit('.', 1)
+        if q in ('running_mean', 'running_var'):
+            c = moved.get(p, 0)
+            assert torch.equal(v[c:], before[k][c:]) and (c == 0 or not torch.equal(v[:c], before[k][:c])), k
+        elif q == 'num_batches_tracked':
+            assert int(v) == (1 if p in ('first.0.1', 'first.1.1') else 0), k
+    assert [int(after[p + '.num_batches_tracked']) for p, _ in sr.bn_layers(arch)] == [int(v) for v in golden[tag + '_nbt']]
+
+
+def test_re_organize_weights_and_init_from(golden):
+    cfg = make_cfg()
+    sd = sr.make_state_dict(sr.SEED)
+    m = psm.get_train_net(cfg, backend='torch')
+    m.load_state_dict(sd)
+    perms = m.re_organize_weights()
+    assert len(perms) == 4
+    for i, p in enumerate(perms):
+        assert np.array_equal(p.numpy(), golden['perm_%d' % i]), i
+    p0 = perms[0]
+    assert torch.equal(m.first[3].weight, sd['first.3.weight'][p0])
+    assert torch.equal(m.stage[0][0].inv[0].weight, sd['stage.0.0.inv.0.weight'][:, p0])
+    assert torch.equal(m.stage[0][2].inv[0].weight, sd['stage.0.2.inv.0.weight'][:, perms[1]])
+    # init_from: final* / deconv* dropped, `module.` stripped, the rest loaded and re-organised
+    torch.manual_seed(0)
+    init = psm.get_train_net(cfg, backend='torch', init_from={'module.' + k: v for k, v in sd.items()})
+    got = init.state_dict()
+    for k, v in m.state_dict().items():
+        if k.startswith(('final', 'deconv')):
+            assert not torch.equal(got[k], sd[k]) or k.endswith('num_batches_tracked') or 'running' in k, k
+        else:
+            assert torch.equal(got[k], v), k
+
+
+# ------------------------------------------------------------------ the integer rules of lp_train_resize
+SIZES = (512, 256, 128, 64, 32, 16)
+
+
+def test_integer_nearest_index_is_torchs_rule():
+    for inn in SIZES:
+        for num, den in st.FRACTIONS:
+            out = inn * num // den
+            line = torch.arange(inn, dtype=torch.float32).reshape(1, 1, 1, inn)
+            want = F.interpolate(line, size=(1, out))[0, 0, 0].long().numpy()
+            assert np.array_equal(st.nearest_index(out, inn), want), (inn, out)
+
+
+@pytest.mark.parametrize('base', [512, 128])
+def test_remapped_joints_stay_inside_the_resized_plane(base):
+    for num, den in st.FRACTIONS:
+        size = base * num // den
+        assert size % 16 == 0
+        for s in range(2):
+            R, O = base // 4 << s, size // 4 << s
+            j = np.arange(R * R)
+            got = st.remap_joint(j, size, base)
+            assert got.min() >= 0 and got.max() < O * O, (base, size, s)
+            t = torch.from_numpy(j).reshape(1, 1, -1, 1).repeat(1, 1, 1, 2)
+            ref = st.resize_ref(torch.zeros(1, 3, 4, 4), [torch.zeros(1, 1, 4, 4)], [torch.zeros(1, 4, 4)], [t], size, base)
+            assert np.array_equal(ref[3][0][0, 0, :, 0].numpy(), got)
+
+
+def test_do_train_refuses_a_graph_with_the_resize():
+    cfg = make_cfg(128)
+    with pytest.raises(ValueError, match='graph=True'):
+        trainer.do_train(cfg, None, [], None, None, graph=True)
+    cfg.MODEL.NAME = 'pose_mobilenet'
+    with pytest.raises(ValueError, match='graph=True'):
+        trainer.do_train(cfg, psm.get_train_net(make_cfg(), backend='torch'), [], None, None, graph=True)
+
+
+# ------------------------------------------------------------------ the header
+def test_header_declares_the_three_calls_without_a_writable_d_parameter():
+    import test_poison_cpu as pc
+    with open(os.path.join(ROOT, 'include', 'litepose_amd.h')) as f:
+        src = pc._COMMENT.sub(' ', f.read())
+    protos = dict(pc._PROTO.findall(src))
+    for name in ('lp_subnet_gather', 'lp_subnet_scatter_grad', 'lp_train_resize'):
+        assert name in protos, name
+        assert name not in pc.writable_device_calls(), name
+        assert re.search(r'\w+_out\b', protos[name]), name
+    from litepose_amd import _native
+    assert {'lp_subnet_gather', 'lp_subnet_scatter_grad', 'lp_train_resize'} <= set(_native.EXPORTS)
+    import ctypes
+    assert ctypes.sizeof(_native.LpSubnetDesc) == 64

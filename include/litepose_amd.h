@@ -178,9 +178,9 @@ int lp_net_set_streams(lp_net* net, int k);
  *   "pw3d"       fp32: small launches (<= 8192 pixels) of the bf16x3 1x1 as pw3d_kernel: loads four k-steps ahead, 32 pixels per
  *                wave, bit-identical to pw3_kernel (round 6; 0 off, 1 by that rule, 2 always)
  *   "mbtd"       bf16 storage: residual stride-1 blocks with <= 32 channels as mbtd_kernel: expanded tile in bf16, depthwise on
- *                v_dot2_f32_bf16, two 8-wave workgroups per CU (round 6; 0 off, 1 default)
- *   "mbtq"       bf16 storage: residual stride-1 blocks with <= 32 input channels as 4-wave workgroups, two per CU (round 6;
- *                1 = default: expanded width <= 160 and >= 1024 tiles, 2: whenever the shape fits, 0: the 8-wave kernel)
+ *                v_dot2_f32_bf16, two 8-wave workgroups per CU (round 6; 0: mbtb_kernel, 1 default).  The key of the 4-wave
+ *                form that this one superseded is gone with its kernel: like any key not listed here it answers
+ *                LP_ERR_UNKNOWN_KEY, from both calls
  *   "headb"      bf16 storage: an output head (both 5x5 depthwise convs + the dual-source 1x1) in one launch, bit-identical to the
  *                three launches it replaces (round 6; default 1; needs "dwt" = 2 and <= 32 output filters); with
  *                lp_arch.plain_head = 1 the one-source head (one 5x5 depthwise + the 1x1), bit-identical to its two launches

@@ -70,7 +70,6 @@ struct lp_net : lp_plan::Net {           // arch, tensors, storage and the plan:
     int opt_mbtb = 1, opt_mbtb_s2 = 1;     // bf16 storage: whole-block kernels
     int opt_pw3d = 1;                      // fp32: small launches of the bf16x3 1x1 take the deep-prefetch form (0 off, 2 always)
     int opt_mbtd = 1;                      // bf16: the small residual blocks as bf16-E / dot2 workgroups, two per CU (0 off)
-    int opt_mbtq = 1;                      // ... the small residual blocks as 4-wave workgroups, two per CU (0 off, 2 always)
     int opt_headb = 1;                     // bf16 storage: an output head (dw5 + dw5 + 1x1; plain head: dw5 + 1x1) in one launch
     int opt_headfuse = 1;                  // fp32: an output head in one launch, headfuse_kernel (0: the unfused chain)
     int opt_dwt = 2;                       // bf16 storage: matrix-core depthwise (0 never, 1 7x7, 2 + the heads' 5x5)
@@ -587,7 +586,7 @@ int rule_mbtb(const Part& c, size_t i) {
     const float* Wt = c.Wt;
     return lp::launch_mbtb(c.buf[o.inA], Wt + o.w_off, Wt + o.b_off, Wt + dw.wrow_off, Wt + pw.w_off, Wt + pw.b_off,
                            pw.res >= 0 ? c.buf[pw.res] : nullptr, c.buf[pw.out], c.NB, o.Ca, o.Cout, pw.Cout, pl.ih, pl.iw,
-                           dw.K, dw.S, c.s, n->opt_mbtb, n->opt_mbtb_s2, n->opt_mbtq,
+                           dw.K, dw.S, c.s, n->opt_mbtb, n->opt_mbtb_s2,
                            dw.wrow2_off ? Wt + dw.wrow2_off : nullptr, n->opt_mbtd, c.f16) ? 3 : 0;
 }
 
@@ -1012,7 +1011,6 @@ const std::vector<OptEntry>& lp_net::options() {
         {"mbconv2", 0, 1, &lp_net::opt_mbconv2},
         {"mbtb", 0, 1, &lp_net::opt_mbtb},
         {"mbtb_s2", 0, 1, &lp_net::opt_mbtb_s2},
-        {"mbtq", 0, 2, &lp_net::opt_mbtq},
         {"mbtd", 0, 1, &lp_net::opt_mbtd},
         {"pw3d", 0, 2, &lp_net::opt_pw3d},
         {"headb", 0, 1, &lp_net::opt_headb},

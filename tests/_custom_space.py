@@ -28,7 +28,7 @@ from oracle import spec
 
 # every fused block kernel built for 7x7 depthwise blocks only
 FUSED_K7 = {'mb16_kernel', 'mbt_kernel', 'mbt_s2_kernel', 'mbconv_kernel', 'mbconv2_kernel', 'mbconv_s2_kernel',
-            'mbtb_kernel', 'mbtb_s2_kernel', 'mbtd_kernel', 'mbtq_kernel'}
+            'mbtb_kernel', 'mbtb_s2_kernel', 'mbtd_kernel'}
 
 
 def _st(channel, stride, blocks):
@@ -73,8 +73,8 @@ ARCHS = {
     # and one 7x7 residual block that shows the batch gate passed
     'gate5': build(16, [(16, 2, [[1, 3]]), (32, 2, [[3, 3]]), (48, 2, [[3, 5]]),
                         (80, 1, [[6, 5], [6, 5], [6, 5], [6, 7]])], (16, 24, 24)),
-    # 5x5 / 3x3 residual blocks of 16 channels at 1/2 (five stages, the first at stride 1): mbtd_kernel's / mbtq_kernel's
-    # channel shape; one 7x7 residual block shows the tile-count gate passed
+    # 5x5 / 3x3 residual blocks of 16 channels at 1/2 (five stages, the first at stride 1): mbtd_kernel's channel
+    # shape; one 7x7 residual block shows that kernel launched in the same forward
     'gateq': build(16, [(16, 1, [[6, 5], [6, 5], [6, 3], [6, 7]]), (24, 2, [[3, 5]]), (32, 2, [[3, 3]]), (48, 2, [[3, 3]]),
                         (80, 1, [[1, 5]])], (16, 24, 24)),
 }
@@ -131,10 +131,7 @@ ROWS = [
     ('gate5_nb48', 'gate5', 256, 256, 24, 2, {'_storages': ('f32',)}, {'mb16_kernel', 'dw_pair16_kernel<5>'}, set(),
      'a launch of 48 images (opt_mb16_min) on 16 x 16 planes: mb16_kernel takes the 7x7 block, never the 5x5 ones'),
     ('gateq_1024', 'gateq', 128, 128, 32, 2, {'_storages': ('bf16',)}, set(), {'mbtd_kernel', 'dwb_kernel<5,1>', 'dwb_kernel<3,1>'},
-     '64 images x 16 tiles = 1024 tiles: mbtd_kernel (asked before mbtq_kernel) takes the 7x7 block, never the others'),
-    ('gateq_1024_mbtd0', 'gateq', 128, 128, 32, 2, {'_storages': ('bf16',), 'mbtd': 0}, set(),
-     {'mbtq_kernel', 'dwb_kernel<5,1>', 'dwb_kernel<3,1>'},
-     'the same with option "mbtd" = 0: mbtq_kernel takes the 7x7 block'),
+     '64 images x 16 tiles = 1024 tiles, a full-size launch: mbtd_kernel takes the 7x7 block, never the 5x5 / 3x3 ones'),
 ]
 
 # row id -> the shapes it is there for: (tag the fp32 forward must launch on the shape, or None) + launch_key's shape
@@ -177,7 +174,6 @@ TARGET = {
     'gate5_nb48': [('dw_pair16_kernel<5>', 48, 288, 80, 5, 1, False), ('dw_pair16_kernel<5>', 80, 480, 80, 5, 1, True),
                    ('mb16_kernel', 80, 480, 80, 7, 1, True)],
     'gateq_1024': [(None, 16, 96, 16, 5, 1, True), (None, 16, 96, 16, 3, 1, True), (None, 16, 96, 16, 7, 1, True)],
-    'gateq_1024_mbtd0': [(None, 16, 96, 16, 5, 1, True), (None, 16, 96, 16, 3, 1, True), (None, 16, 96, 16, 7, 1, True)],
 }
 
 # row id -> {launch-name prefix: tags none of its launches may carry}: the far side of a gate

@@ -174,7 +174,7 @@ def fused_inner(launch_names):
     """{stored output: [tensors the launch keeps on the CU]} of the fused bf16 launches among ``launch_names``."""
     out = {}
     for nm in launch_names:
-        if nm.endswith('.inv+dw+point_conv'):                     # mbtb / mbtb_s2 / mbtd / mbtq: a whole block
+        if nm.endswith('.inv+dw+point_conv'):                     # mbtb / mbtb_s2 / mbtd: a whole block
             p = nm[:-len('.inv+dw+point_conv')]
             out[p + '.point_conv'] = [p + '.inv', p + '.depth_conv']
         elif nm == 'stem.conv3x3s2+dw3+pw':                       # stem4_kernel<lp::Bf16, C0>

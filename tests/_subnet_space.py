@@ -24,7 +24,8 @@ builds from it.  A width VECTOR is ``(input_channel, deconv 0, deconv 1, deconv 
     256 x 256 and deconv4x3_kernel on every larger one, the stage-3 / stage-4 depthwise is dw_pair16_kernel on
     16 x 16 planes only -- so every vector runs in both size classes: a trunk vector that ran at 256 again at 320, the
     others again at 256, and every deconv vector at 288 x 288 (18 x 18 deepest planes), N = 1, flip = 0.
-``GATE_ROWS`` are the rows on both sides of the two batch gates (see test_gpu_subnet_census.py)."""
+``GATE_ROWS`` are the rows on both sides of the batch gate, ``OPTION_ROWS`` the rows of forms that an option selects (see
+test_gpu_subnet_census.py)."""
 import functools
 import itertools
 
@@ -242,15 +243,20 @@ TRUNK = [r for r in ROWS if r[0].startswith('t')]
 DECONV = [r for r in ROWS if r[0].startswith('d')]
 SECOND = [r for r in ROWS if r[0].startswith('e')]
 
-# (id, vector, storage, H, W, N, flip, options, the gated tag, whether this side launches it): the two batch gates, each
-# on a search-space shape no published architecture has (see test_gpu_subnet_census.py: test_batch_gate_both_sides)
+# (id, vector, storage, H, W, N, flip, options, the gated tag, whether this side launches it): the batch gate on a
+# search-space shape no published architecture has (see test_gpu_subnet_census.py: test_batch_gate_both_sides)
 GATE_ROWS = [
     # mb16_kernel<3, 2>: the 48 -> 40 channel stage-4 entry block on 16 x 16 planes, a launch of >= 48 images
     ('mb16_c48_40_nb46', (16, 48, 16, 24, 24, 16, 48, 40), 'f32', 256, 256, 23, 2, {}, 'mb16_kernel', False),
     ('mb16_c48_40_nb48', (16, 48, 16, 24, 24, 16, 48, 40), 'f32', 256, 256, 24, 2, {}, 'mb16_kernel', True),
-    # mbtq_kernel<1, 1>: the 8-channel residual blocks of stage 1 (Cexp = 48), 16 tiles per image on 64 x 64 planes
-    ('mbtq_c8_992', (16, 16, 48, 32, 8, 16, 24, 40), 'bf16', 256, 256, 31, 2, {'mbtd': 0}, 'mbtq_kernel', False),
-    ('mbtq_c8_1024', (16, 16, 48, 32, 8, 16, 24, 40), 'bf16', 256, 256, 32, 2, {'mbtd': 0}, 'mbtq_kernel', True),
+]
+
+# the same layout, the last field always True: a form that only an option selects, on a search-space shape no published
+# architecture has (test_gpu_subnet_census.py: test_option_row_launches_its_form)
+OPTION_ROWS = [
+    # mbtb_kernel<1, 1, true>: the 8-channel residual blocks of stage 1 (Cexp = 48: half a 16-channel MFMA group), which
+    # mbtd_kernel takes by default; 32 x 32 planes = 2 x 2 tiles per image
+    ('mbtb_c8_mbtd0', (16, 16, 48, 32, 8, 16, 24, 40), 'bf16', 128, 128, 3, 2, {'mbtd': 0}, 'mbtb_kernel', True),
 ]
 
 

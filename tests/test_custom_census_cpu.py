@@ -13,7 +13,7 @@ from test_kernel_census_cpu import source_tags
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'golden_custom.npz')
-OPTION_KEYS = {'mb16', 'mb16_run', 'mb16_min', 'mbt', 'mbt_s2', 'mbconv2', 'mbtb', 'mbtb_s2', 'mbtq', 'mbtd', 'pw3d',
+OPTION_KEYS = {'mb16', 'mb16_run', 'mb16_min', 'mbt', 'mbt_s2', 'mbconv2', 'mbtb', 'mbtb_s2', 'mbtd', 'pw3d',
                'headb', 'dwt', 'stem'}
 
 

@@ -85,7 +85,7 @@ def test_library_host_code_rounds_to_half_only_from_float():
 
 
 FAMILIES_16 = ('stemb_kernel', 'dwb_kernel', 'dwt_kernel', 'pwb_kernel', 'deconvb_kernel', 'headb_kernel',
-               'octet_to_planar_kernel', 'mbtb_kernel', 'mbtb_s2_kernel', 'mbtq_kernel', 'mbtd_kernel')
+               'octet_to_planar_kernel', 'mbtb_kernel', 'mbtb_s2_kernel', 'mbtd_kernel')
 
 
 def _check_format_census(res):
@@ -107,7 +107,7 @@ def _check_format_census(res):
     assert stem['lp::F32'] == stem['lp::Bf16'] == stem['lp::F16'] and stem['lp::F32'], stem
     for fmt in ('lp::Bf16', 'lp::F16'):
         n = sum(len(by[fmt]) for by in forms.values())
-        assert n == 53, (fmt, n)
+        assert n == 51, (fmt, n)
 
 
 def test_every_16bit_kernel_is_built_in_both_formats_with_the_same_template_list():

@@ -51,12 +51,12 @@ CASES = [
     ('mb16_nb48_flip', 'search-XS', 'f32', 256, 256, 24, 2, {}, {'mb16_kernel'}),
     ('mb16_nb47', 'search-XS', 'f32', 256, 256, 47, 0, {}, {'dw_pair16_kernel<7>'}),
     ('mb16_nb48', 'search-XS', 'f32', 256, 256, 48, 0, {}, {'mb16_kernel'}),
-    # mbtq_kernel (bf16): residual blocks of <= 32 channels on grids of N * tiles >= 1024 16x16 tiles; mbtd_kernel is
-    # checked first and takes the same blocks.  XS@512: stage 1 on 128x128 planes = 64 tiles per image
-    ('mbtq_960_default', 'search-XS', 'bf16', 512, 512, 15, 0, {}, {'mbtd_kernel'}),
-    ('mbtq_1024_default', 'search-XS', 'bf16', 512, 512, 8, 2, {}, {'mbtd_kernel'}),
-    ('mbtq_960_mbtd0', 'search-XS', 'bf16', 512, 512, 15, 0, {'mbtd': 0}, {'mbtb_kernel'}),
-    ('mbtq_1024_mbtd0', 'search-XS', 'bf16', 512, 512, 8, 2, {'mbtd': 0}, {'mbtq_kernel'}),
+    # the residual blocks of <= 32 channels (bf16) have no batch gate: mbtd_kernel by default, mbtb_kernel with option
+    # "mbtd" = 0, on either side of 1024 16x16 tiles per launch (where a form since removed used to take over from
+    # mbtb_kernel).  XS@512: stage 1 on 128x128 planes = 64 tiles per image
+    ('mbtd_960_default', 'search-XS', 'bf16', 512, 512, 15, 0, {}, {'mbtd_kernel'}),
+    ('mbtd_1024_default', 'search-XS', 'bf16', 512, 512, 8, 2, {}, {'mbtd_kernel'}),
+    ('mbtb_960_mbtd0', 'search-XS', 'bf16', 512, 512, 15, 0, {'mbtd': 0}, {'mbtb_kernel'}),
     # mbconv_s2_kernel's gate (24-channel stride-2 entry block, output plane >= 1024 pixels) on both sides: search-L's
     # entry block expands to 144 channels, which the kernel refuses (Cexp % 32), so both sides take the unfused chain
     ('mbconv_s2_896', 'search-L', 'f32', 112, 128, 2, 0, {}, {'dw_kernel<7,2>'}),
@@ -92,7 +92,6 @@ CASES = [
     ('opt_dwt1', 'search-M', 'bf16', 256, 256, 2, 0, {'dwt': 1, 'mbtb': 0}, {'dwt_kernel<7>', 'dwb_kernel<5,1>'}),
     ('opt_mbtb0', 'search-S', 'bf16', 224, 224, 3, 0, {'mbtb': 0}, {'pwb_kernel', 'dwb_kernel<7,2>'}),
     ('opt_mbtb_s2_0', 'search-S', 'bf16', 224, 224, 3, 0, {'mbtb_s2': 0}, {'dwb_kernel<7,2>'}),
-    ('opt_mbtq2', 'search-S', 'bf16', 224, 224, 3, 0, {'mbtq': 2, 'mbtd': 0}, {'mbtq_kernel'}),
 ]
 
 # kernel tag -> why no CASES row reaches it (the option value or shape that would).  CASES holds published architectures

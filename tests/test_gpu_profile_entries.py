@@ -66,7 +66,7 @@ UNFUSED = {'f32': {'mbt': 0, 'mbt_s2': 0, 'mbconv2': 0, 'mb16': 0, 'headfuse': 0
            'f16': {'mbtb': 0, 'mbtb_s2': 0, 'headb': 0, 'stem': 0}}
 
 _RUN = re.compile(r'^stage\.\d+\.\d+-\d+\.')
-_MBT16 = ('mbtb_kernel', 'mbtb_s2_kernel', 'mbtd_kernel', 'mbtq_kernel')
+_MBT16 = ('mbtb_kernel', 'mbtb_s2_kernel', 'mbtd_kernel')
 
 # (rule or switch case of csrc/engine.cpp, fp32 storage?, predicate(name, tag)): what the golden file must reach
 RULES = [
@@ -89,7 +89,7 @@ RULES = [
     ('f32 OP_DWPW: dwpw_kernel', True, lambda n, t: n.endswith('.depth_conv+point_conv') and t.startswith('dwpw_kernel')),
     ('f32 OP_DWPW: depthwise half', True, lambda n, t: n.endswith('.depth_conv') and t.startswith('dw_')),
     ('f32 OP_DWPW: 1x1 half', True, lambda n, t: n.endswith('.point_conv') and t.startswith('pw')),
-    ('rule_mbtb: stride 1', False, lambda n, t: n.endswith('+dw+point_conv') and t in ('mbtb_kernel', 'mbtd_kernel', 'mbtq_kernel')),
+    ('rule_mbtb: stride 1', False, lambda n, t: n.endswith('+dw+point_conv') and t in ('mbtb_kernel', 'mbtd_kernel')),
     ('rule_mbtb: stride 2', False, lambda n, t: n.endswith('+dw+point_conv') and t == 'mbtb_s2_kernel'),
     ('rule_stem3b', False, lambda n, t: n == 'stem.conv3x3s2+dw3+pw'),
     ('rule_headb: two sources', False, lambda n, t: t == 'headb_kernel' and n.endswith('.dw5+dw5+pw')),

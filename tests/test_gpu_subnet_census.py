@@ -5,9 +5,9 @@ with synthetic weights (oracle.synth.make_state_dict).
 
 Tests: every row in fp32 (check_fp32: all block taps and both outputs, every image and the mirrored half); every row in
 bf16 and the trunk rows plus sixteen deconv rows in f16 (check_bf16 / check_f16, their own criteria); both sides of the
-two batch gates on a shape no published architecture has; batched == per-image and flip modes, bitwise; closure of the
-launch keys of 32 real draws over the rows; BatchNorm calibration on the two extreme architectures.  Every row test
-prints its tags, its worst fraction of the bound and its wall time.
+batch gate, and the form an option selects, on shapes no published architecture has; batched == per-image and flip
+modes, bitwise; closure of the launch keys of 32 real draws over the rows; BatchNorm calibration on the two extreme
+architectures.  Every row test prints its tags, its worst fraction of the bound and its wall time.
 
 Measured on an MI355X, every test passing.  Columns: input size, N, flip; the worst fp32 block tap and the worst fp32
 output as fractions of TAP_REL / NET_ATOL; the worst bf16 and f16 criterion as a fraction of its bound (check_bf16 /
@@ -152,8 +152,7 @@ Worst of all rows: taps 0.215 (t06), outputs 0.080 (t03), bf16 1.000 (t10, t13, 
 t13, d04).
   * REFUSED is empty: neither storage refuses a row or a draw.
   * Gate rows: mb16_c48_40_nb46 0.136 of the bound without mb16_kernel (the entry block runs as pw3_kernel +
-    dw_pair16_kernel<7> + pw2_kernel), mb16_c48_40_nb48 0.137 with it; mbtq_c8_992 0.992 without mbtq_kernel,
-    mbtq_c8_1024 1.000 with it.
+    dw_pair16_kernel<7> + pw2_kernel), mb16_c48_40_nb48 0.137 with it.
   * The 32 draws produce 357 launch keys (storage included), 0 unreached, 0 refused builds; the rows produce 820.
   * Calibration: CALIB_MEASURED below.
   * No row launches a tag that NOT_REACHED in test_gpu_kernel_census.py lists (dw_pair16_kernel<5>, mbconv_kernel,
@@ -189,8 +188,8 @@ ROWS16 = sp.TRUNK + DECONV16            # bf16 AND f16; bf16 runs every row (the
 REFUSED = {
 }
 
-# the shape at which a GATE_ROWS row must launch its gated form: (Cin, Cexp, Cout, K, stride, residual)
-GATE_SHAPE = {'mb16_kernel': (48, 288, 40, 7, 1, False), 'mbtq_kernel': (8, 48, 8, 7, 1, True)}
+# the shape at which a GATE_ROWS / OPTION_ROWS row must launch its form: (Cin, Cexp, Cout, K, stride, residual)
+GATE_SHAPE = {'mb16_kernel': (48, 288, 40, 7, 1, False), 'mbtb_kernel': (8, 48, 8, 7, 1, True)}
 
 # stem 16, 24, 24, 24; stage widths (8, 16, 24, 40), (24, 64, 96, 80), (32, 16, 96, 120), (16, 64, 72, 160)
 INVARIANCE_ROWS = ('t00', 't07', 't11', 't14')
@@ -307,22 +306,11 @@ def test_row_16bit_vs_emulation(rid, storage):
         _same_deconv_forms_as_256(rid, vec, storage, launches)
 
 
-@pytest.mark.parametrize('gid', [g[0] for g in sp.GATE_ROWS])
-def test_batch_gate_both_sides(gid):
-    """The two batch-gated forms on a search-space shape no published architecture has, one row on each side.
-      * mb16_kernel: ``NB >= opt_mb16_min`` (48) and ``mb16_supported``: ``H == 16 && W == 16 && K == 7 && S == 1``,
-        ``!(Cout & 7) && !(res && Cin != Cout) && !(Cin & 15) && !(Cexp & 31)`` and (Cin / 16, ceil(Cout / 32)) one of
-        (3, 2) (3, 3) (3, 4) (5, 3) (6, 3).  In the space that is stage 4 at 256 x 256: the 80-channel residual blocks and
-        the 48 -> 80 entry (search-XS), the 48 -> 120 entry (search-S), and two shapes no published architecture has,
-        the 48 -> 40 and the 96 -> 80 entry.  The rows take 48 -> 40 (mb16_kernel<3, 2>); N = 24 / 23 with flip = 2.
-      * mbtq_kernel: ``res && ck <= 2 && nmt == 1 && Cexp <= 160 && N * tiles >= 1024``: residual blocks of 8, 16 or
-        24 channels.  No published architecture has 8-channel blocks (Cexp = 48: half a 16-channel MFMA group).
-        mbtd_kernel is asked first and takes the same blocks (``mode_d && wrow2 && res && ck <= 2 && nmt == 1``), so, as
-        in the kernel census, the rows switch it off (option "mbtd" = 0); stage 1 on 64 x 64 planes is 16 tiles per
-        image: N = 32 / 31 with flip = 2."""
+def _keyed_row(row):
+    """A GATE_ROWS / OPTION_ROWS row: the forward launches its tag at GATE_SHAPE exactly when the row says so, and every
+    image is compared like a census row's."""
     from _net_check import NET_ATOL, TAP_REL, check_bf16, check_fp32, launch_key
-    row = {g[0]: g for g in sp.GATE_ROWS}[gid]
-    _, vec, storage, H, W, N, flip, options, tag, launched = row
+    gid, vec, storage, H, W, N, flip, options, tag, launched = row
     t0 = time.time()
     res = _forward(vec, storage, H, W, N, flip, options)
     assert not isinstance(res, str), (gid, res)
@@ -339,6 +327,26 @@ def test_batch_gate_both_sides(gid):
         crit = max(r[2] for r in rows.values())
     print('%s: worst criterion %.3f of its bound; %.1f s; tags %s'
           % (gid, crit, time.time() - t0, ' '.join(sorted({t for _, t in launches}))))
+
+
+@pytest.mark.parametrize('gid', [g[0] for g in sp.GATE_ROWS])
+def test_batch_gate_both_sides(gid):
+    """The batch-gated form on a search-space shape no published architecture has, one row on each side.
+      * mb16_kernel: ``NB >= opt_mb16_min`` (48) and ``mb16_supported``: ``H == 16 && W == 16 && K == 7 && S == 1``,
+        ``!(Cout & 7) && !(res && Cin != Cout) && !(Cin & 15) && !(Cexp & 31)`` and (Cin / 16, ceil(Cout / 32)) one of
+        (3, 2) (3, 3) (3, 4) (5, 3) (6, 3).  In the space that is stage 4 at 256 x 256: the 80-channel residual blocks and
+        the 48 -> 80 entry (search-XS), the 48 -> 120 entry (search-S), and two shapes no published architecture has,
+        the 48 -> 40 and the 96 -> 80 entry.  The rows take 48 -> 40 (mb16_kernel<3, 2>); N = 24 / 23 with flip = 2."""
+    _keyed_row({g[0]: g for g in sp.GATE_ROWS}[gid])
+
+
+@pytest.mark.parametrize('oid', [o[0] for o in sp.OPTION_ROWS])
+def test_option_row_launches_its_form(oid):
+    """mbtb_kernel<1, 1, true> on the 8-channel residual blocks of stage 1 (Cexp = 48: half a 16-channel MFMA group; no
+    published architecture has them): mbtd_kernel is asked first and takes every residual block of up to 32 channels
+    (``mode_d && wrow2 && res && ck <= 2 && nmt == 1``), so the row switches it off (option "mbtd" = 0).  No batch gate
+    is involved: three images, mirrored, on 32 x 32 stage-1 planes."""
+    _keyed_row({o[0]: o for o in sp.OPTION_ROWS}[oid])
 
 
 @pytest.mark.parametrize('storage', ['bf16', 'f16'])

@@ -42,7 +42,7 @@ def test_sources_name_the_forms():
     tags = source_tags()
     # the dispatcher's families: a parser that finds far fewer has stopped reading the sources
     assert len(tags) >= 27, sorted(tags)
-    for t in ('mb16_kernel', 'mbtq_kernel', 'mbconv_s2_kernel', 'dwb_kernel<7,2>', 'dw_pair16_kernel<7>'):
+    for t in ('mb16_kernel', 'mbtd_kernel', 'mbconv_s2_kernel', 'dwb_kernel<7,2>', 'dw_pair16_kernel<7>'):
         assert t in tags, t
 
 
@@ -65,7 +65,7 @@ def test_cases_table_is_well_formed():
     cases, _ = _census()
     ids = [c[0] for c in cases]
     assert len(ids) == len(set(ids))
-    keys = {'mb16', 'mb16_run', 'mb16_min', 'mbt', 'mbt_s2', 'mbconv2', 'mbtb', 'mbtb_s2', 'mbtq', 'mbtd', 'pw3d',
+    keys = {'mb16', 'mb16_run', 'mb16_min', 'mbt', 'mbt_s2', 'mbconv2', 'mbtb', 'mbtb_s2', 'mbtd', 'pw3d',
             'headb', 'dwt', 'stem'}
     for cid, arch, storage, H, W, N, flip, options, expect in cases:
         assert arch in arch_zoo.names(), cid

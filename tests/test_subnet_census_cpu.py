@@ -85,7 +85,7 @@ def test_every_row_is_a_vector_random_sample_can_return_and_derive_accepts():
     w = sp.widths()
     m = psm.get_pose_net(sp._cfg())
     m.load_state_dict(sr.make_state_dict(sr.SEED), strict=True)
-    for row in list(sp.ROWS) + list(sp.GATE_ROWS):
+    for row in list(sp.ROWS) + list(sp.GATE_ROWS) + list(sp.OPTION_ROWS):
         v = row[1]
         assert len(v) == len(w) and all(c in ws for c, ws in zip(v, w)), row[0]
         arch = sp.row_arch(row)

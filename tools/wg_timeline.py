@@ -89,7 +89,7 @@ c0 = cus[0]
 o = np.argsort(start[cu == c0])
 print('first CU: start-end (us):', ' '.join('%.1f-%.1f' % (a_, b_) for a_, b_ in zip(start[cu == c0][o][:14], end[cu == c0][o][:14])))
 names = ['prologue', 'depthwise', 'drain+bar', 'project', 'expand', 'barrier', 'epilogue']
-wv = w[w[:, :, 7] > 0]                                             # waves that ran (mbtq: 4 per workgroup)
+wv = w[w[:, :, 7] > 0]                                             # waves that ran
 tiles = wv[:, 7].sum()
 print('per wave and TILE, ticks (%.0f waves, %.2f tiles per wave): ' % (len(wv), wv[:, 7].mean())
       + ' '.join('%s %.0f' % (n, wv[:, k].sum() / tiles) for k, n in enumerate(names))

@@ -783,6 +783,39 @@ int lp_bn_backward(const float* d_grad_y, const float* d_x, const float* d_gamma
                    float* grad_x_out, float* grad_gamma_out, float* grad_beta_out, int N, int C, int HW, int act,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* Synchronised BatchNorm: the statistics of W ranks' batches taken together (torch.nn.SyncBatchNorm).  Each pass is two
+ * calls with ONE all-gather of the caller's between them; the library does no communication.  Same rules, size limits
+ * and error codes as lp_bn_forward / lp_bn_backward; the fp64 rows and stats must be 8-byte aligned; W in
+ * 1 .. LP_BN_SYNC_MAX_WORLD and rank in [0, W), else LP_ERR_INVALID_ARG before any pointer is looked at.  All rows fp64:
+ *   forward row  [2C + 2] = sum[C] | sumsq[C] | count | 0         backward row [2C] = sum_g[C] | sum_gxhat[C]
+ *   sync stat    [2C + 2] = mean[C] | invstd[C] | total count | 0 (the count rides along: the backward reads it on the device)
+ * lp_bn_sync_stats: this rank's forward row, count = N * HW, from the per-workgroup partials of lp_bn_forward added in
+ *   index order.  Writes: every element of row_out [2C + 2].  Workspace: lp_bn_workspace_bytes(N, C, HW).
+ * lp_bn_sync_forward: d_rows [W][2C + 2], the rows of all ranks in rank order.  Every sum adds the W rows in rank order
+ *   starting from 0.0, the cell count is the sum of the rows' counts; mean, the clamped biased variance, invstd, the
+ *   running update (unbiased over the total count) and y are lp_bn_forward's training-mode expressions, so every rank
+ *   that is given the same d_rows holds the same bits of stat_out and running_io, and W = 1 gives lp_bn_forward's bits.
+ *   Writes: every element of y_out [N,C,HW], of stat_out [2C + 2] (sync stat) and of running_io [2,C].
+ * lp_bn_sync_backward_stats: this rank's backward row, xhat on the GLOBAL pair of d_stat (the sync stat; its first 2C
+ *   doubles are read).  Writes: every element of row_out [2C].  Workspace: lp_bn_workspace_bytes(N, C, HW).
+ * lp_bn_sync_backward: d_rows [W][2C] in rank order; grad_x is lp_bn_backward's expression with sum(g), sum(g * xhat) the
+ *   rank-order sums of all rows and n the total count of d_stat; grad_gamma / grad_beta are this rank's OWN row,
+ *   d_rows[rank], rounded once, as torch.nn.SyncBatchNorm leaves them: the average of the parameter gradients over the
+ *   ranks makes them global.  Writes: every element of grad_x_out [N,C,HW], grad_gamma_out [C], grad_beta_out [C].
+ * Contract test: tests/test_gpu_sync_bn_buffers.py.                                                                   */
+#define LP_BN_SYNC_MAX_WORLD 64
+int lp_bn_sync_stats(const float* d_x, int N, int C, int HW, double* row_out, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int lp_bn_sync_forward(const float* d_x, const float* d_gamma, const float* d_beta, float* running_io, const float* d_res,
+                       float* y_out, double* stat_out, const double* d_rows, int W, int N, int C, int HW, int act,
+                       double momentum, double eps, void* stream);
+int lp_bn_sync_backward_stats(const float* d_grad_y, const float* d_x, const float* d_gamma, const float* d_beta,
+                              const double* d_stat, int N, int C, int HW, int act, double* row_out, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int lp_bn_sync_backward(const float* d_grad_y, const float* d_x, const float* d_gamma, const float* d_beta,
+                        const double* d_stat, const double* d_rows, int W, int rank, int N, int C, int HW, int act,
+                        float* grad_x_out, float* grad_gamma_out, float* grad_beta_out, void* stream);
+
 /* Pointwise 1x1 without bias: y[n][co][p] = sum_ci w[co][ci] x[n][ci][p]; d_x [N,Cin,HW], d_w [Cout,Cin], y_out [N,Cout,HW].
  * The forward and the data gradient (the same kernel on the transposed weight) run on v_mfma_f32_32x32x2_f32 from A
  * fragments a device kernel packs into the workspace; the weight gradient grad_w[co][ci] = sum_{n,p} grad_y[n][co][p] *

@@ -168,6 +168,10 @@ _SIGS = {
     'lp_bn_workspace_bytes': (sz, [i32, i32, i32]),
     'lp_bn_forward': (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_double, C.c_double, vp, sz, vp]),
     'lp_bn_backward': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+    'lp_bn_sync_stats': (i32, [vp, i32, i32, i32, vp, vp, sz, vp]),
+    'lp_bn_sync_forward': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_double, C.c_double, vp]),
+    'lp_bn_sync_backward_stats': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
+    'lp_bn_sync_backward': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     'lp_pw_tile_choice': (i32, [i32, i32, i32, i32, i32, i32]),
     'lp_mbt_form': (i32, [i32] * 13),
     'lp_pw_forward_workspace_bytes': (sz, [i32, i32]),

@@ -215,8 +215,18 @@ def random_resolution_size(cfg):
     return (256 + 64 * random.randint(0, 4)) * int(cfg.DATASET.INPUT_SIZE) // 512
 
 
+def _bucket(model, group):
+    """The model's GradBucket for ``group``: built once per (model, group) and kept on the model."""
+    from ..parallel import GradBucket
+    kept = getattr(model, '_grad_bucket', None)
+    if kept is None or kept[0] is not group:
+        kept = (group, GradBucket(model.parameters(), group))
+        model._grad_bucket = kept
+    return kept[1]
+
+
 def do_train(cfg, model, data_loader, loss_factory, optimizer, epoch=0, teacher=None, logger=None, graph=False,
-             random_resolution=None):
+             random_resolution=None, group=None):
     """One epoch of trainer.py:41-113 for a ``torch.nn.Module`` whose ``model(images)`` gives the list of stage outputs:
     per batch ``(images, heatmaps, masks, joints)`` of ``data_loader`` (device tensors, as ``LabelledSet.batches`` yields
     them) the total loss of :82-105 through ``loss_factory`` (``core.loss.MultiLossFactory``), ``optimizer.zero_grad()``,
@@ -248,9 +258,34 @@ def do_train(cfg, model, data_loader, loss_factory, optimizer, epoch=0, teacher=
     ValueError, and so does a model that samples an architecture per step
     (``pose_supermobilenet.TrainableSuperLitePose``): every step has another signature.
 
+    ``group``: a ``torch.distributed`` process group: data-parallel training, the reference's ``DistributedDataParallel``
+    (dist_train.py:271, :283).  ``data_loader`` yields THIS rank's part of every batch (``LabelledSet.batches(shard=(rank,
+    world))``), and every rank runs the same number of steps.  Per step ``bucket.zero_grad()`` replaces
+    ``optimizer.zero_grad()`` and ``bucket.all_reduce_mean()`` sits between ``loss.backward()`` and ``optimizer.step()``: one
+    all-reduce of one flat buffer (``parallel.GradBucket``, built once per (model, group) and kept on the model), after
+    which every rank steps with the same gradient -- the mean over the ranks of the rank's own batch-mean loss gradient,
+    as DDP.  Start the ranks equal (``parallel.broadcast_state``); for BatchNorm statistics over all ranks' images call
+    ``models.pose_mobilenet.convert_sync_batchnorm`` first (``MODEL.SYNC_BN``).  The returned meters are the rank's own,
+    as in the reference.  Three combinations raise ValueError before anything runs:
+      * ``graph`` with a group: the gloo path goes through the host and cannot be captured, and a capture of an RCCL
+        collective has never been run here;
+      * a ``teacher`` with a group;
+      * a model that samples an architecture per step with a group: every rank would have to draw the same architecture.
+
     Not here: tensorboard scalars, ``fp16_optimizer``, debug image dumps, batch and data timers."""
     if random_resolution is None:
         random_resolution = getattr(cfg.MODEL, 'NAME', None) in SUPERNET_NAMES
+    bucket = None
+    if group is not None:
+        if graph:
+            raise ValueError('do_train: graph=True is not supported with a process group: the collectives of a step '
+                             'are not captured')
+        if teacher is not None:
+            raise ValueError('do_train: a teacher is not supported with a process group')
+        if hasattr(model, 'arch_manager'):
+            raise ValueError('do_train: a model that samples an architecture per step is not supported with a process '
+                             'group: every rank would have to draw the same architecture')
+        bucket = _bucket(model, group)
     if graph:
         if teacher is not None:
             raise ValueError('do_train: a teacher is not supported with graph=True')
@@ -295,8 +330,13 @@ def do_train(cfg, model, data_loader, loss_factory, optimizer, epoch=0, teacher=
                 loss = loss + v
                 if key == 'heatmaps' and t_terms is not None:
                     loss = loss + t_terms[0][idx].mean(dim=0)
-        optimizer.zero_grad()
-        loss.backward()
+        if bucket is None:
+            optimizer.zero_grad()
+            loss.backward()
+        else:
+            bucket.zero_grad()
+            loss.backward()
+            bucket.all_reduce_mean()
         optimizer.step()
         count += n
         if logger is not None and i % freq == 0:

@@ -427,6 +427,20 @@ void launch_bn_fwd(const float* x, const float* res, const double* part, const f
 // two launches: the per-workgroup (sum g, sum g * xhat) partials -> part (bn_partial_doubles), then dx, dgamma, dbeta
 void launch_bn_bwd(const float* dy, const float* x, const float* gamma, const float* beta, const double* stat, double* part,
                    float* dx, float* dgamma, float* dbeta, int N, int C, int HW, int act, hipStream_t s);
+// synchronised BatchNorm (lp_bn_sync_*): a rank's partials -> one fp64 row, the ranks' rows [W][.] in rank order -> the layer.
+// part [C][S] pairs (S = bn_cut(N, C, HW).S) -> row = firsts[C] | seconds[C] (| cnt | 0 with tail), index order
+void launch_bn_row(const double* part, int S, int C, double cnt, bool tail, double* row, hipStream_t s);
+// rows [W][2C + 2] = sum | sumsq | count | 0; writes y, stat = mean[C] | invstd[C] | total count | 0, moves running
+void launch_bn_sync_fwd(const float* x, const float* res, const double* rows, int W, const float* gamma, const float* beta,
+                        float* running, float* y, double* stat, int N, int C, int HW, int act, double momentum, double eps,
+                        hipStream_t s);
+// bn_bwd_stats_kernel on the global pair of stat -> part (bn_partial_doubles) -> row [2C] = sum g | sum g * xhat
+void launch_bn_sync_bwd_stats(const float* dy, const float* x, const float* gamma, const float* beta, const double* stat,
+                              double* part, double* row, int N, int C, int HW, int act, hipStream_t s);
+// rows [W][2C]; dx from the rank-order sums over n = stat[2C], dgamma / dbeta from rows[rank]
+void launch_bn_sync_bwd(const float* dy, const float* x, const float* gamma, const float* beta, const double* stat,
+                        const double* rows, int W, int rank, float* dx, float* dgamma, float* dbeta, int N, int C, int HW,
+                        int act, hipStream_t s);
 // w [Cout][Cin] (transpose: its transpose) -> launch_pw's A fragments [ceil(M/32)][(K+1)/2][64] and ceil(M/32) * 32 zeros
 void launch_pw_pack(const float* w, int Cout, int Cin, bool transpose, float* wp, float* zb, hipStream_t s);
 // w [C][K*K] -> launch_dw's wdup [C][K*K][2] and C zeros

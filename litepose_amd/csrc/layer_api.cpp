@@ -72,6 +72,73 @@ int lp_bn_backward(const float* d_grad_y, const float* d_x, const float* d_gamma
     return LP_OK;
 }
 
+// ---- synchronised BatchNorm: the two halves of each pass, a collective of the caller's between them ----
+static int sync_check(int N, int C, int HW, int act, int W, int rank) {
+    if (int rc = bn_check(N, C, HW, act)) return rc;
+    if (W < 1 || W > LP_BN_SYNC_MAX_WORLD) return fail(LP_ERR_INVALID_ARG, "W must lie in 1 .. LP_BN_SYNC_MAX_WORLD");
+    if (rank < 0 || rank >= W) return fail(LP_ERR_INVALID_ARG, "rank must lie in [0, W)");
+    return LP_OK;
+}
+static bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+
+int lp_bn_sync_stats(const float* d_x, int N, int C, int HW, double* row_out, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+    if (int rc = bn_check(N, C, HW, 0)) return rc;
+    if (!d_x || !row_out) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (!al16(d_x) || !al8(row_out)) return fail(LP_ERR_INVALID_ARG, "x must be 16-byte, row_out 8-byte aligned");
+    if (!workspace || workspace_bytes < lp_bn_workspace_bytes(N, C, HW)) return fail(LP_ERR_WORKSPACE, "bn workspace too small");
+    if (!al16(workspace)) return fail(LP_ERR_WORKSPACE, "bn workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    lp::launch_bn_stats(d_x, (double*)workspace, N, C, HW, s);
+    lp::launch_bn_row((const double*)workspace, lp::bn_cut(N, C, HW).S, C, (double)N * (double)HW, true, row_out, s);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "bn_sync_stats launch failed");
+    return LP_OK;
+}
+
+int lp_bn_sync_forward(const float* d_x, const float* d_gamma, const float* d_beta, float* running_io, const float* d_res,
+                       float* y_out, double* stat_out, const double* d_rows, int W, int N, int C, int HW, int act,
+                       double momentum, double eps, void* stream) {
+    if (int rc = sync_check(N, C, HW, act, W, 0)) return rc;
+    if (!d_x || !d_gamma || !d_beta || !running_io || !y_out || !stat_out || !d_rows)
+        return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (!(eps >= 0.0) || !(momentum >= 0.0 && momentum <= 1.0)) return fail(LP_ERR_INVALID_ARG, "eps >= 0, momentum in [0, 1]");
+    if (!al16(d_x) || !al16(y_out) || !al16(d_res) || !al8(stat_out) || !al8(d_rows))
+        return fail(LP_ERR_INVALID_ARG, "x, res and y must be 16-byte, stat_out and rows 8-byte aligned");
+    lp::launch_bn_sync_fwd(d_x, d_res, d_rows, W, d_gamma, d_beta, running_io, y_out, stat_out, N, C, HW, act, momentum, eps,
+                           (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "bn_sync_forward launch failed");
+    return LP_OK;
+}
+
+int lp_bn_sync_backward_stats(const float* d_grad_y, const float* d_x, const float* d_gamma, const float* d_beta,
+                              const double* d_stat, int N, int C, int HW, int act, double* row_out, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    if (int rc = bn_check(N, C, HW, act)) return rc;
+    if (!d_grad_y || !d_x || !d_gamma || !d_beta || !d_stat || !row_out) return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (!al16(d_grad_y) || !al16(d_x) || !al8(d_stat) || !al8(row_out))
+        return fail(LP_ERR_INVALID_ARG, "grad_y and x must be 16-byte, stat and row_out 8-byte aligned");
+    if (!workspace || workspace_bytes < lp_bn_workspace_bytes(N, C, HW)) return fail(LP_ERR_WORKSPACE, "bn workspace too small");
+    if (!al16(workspace)) return fail(LP_ERR_WORKSPACE, "bn workspace must be 16-byte aligned");
+    lp::launch_bn_sync_bwd_stats(d_grad_y, d_x, d_gamma, d_beta, d_stat, (double*)workspace, row_out, N, C, HW, act,
+                                 (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "bn_sync_backward_stats launch failed");
+    return LP_OK;
+}
+
+int lp_bn_sync_backward(const float* d_grad_y, const float* d_x, const float* d_gamma, const float* d_beta,
+                        const double* d_stat, const double* d_rows, int W, int rank, int N, int C, int HW, int act,
+                        float* grad_x_out, float* grad_gamma_out, float* grad_beta_out, void* stream) {
+    if (int rc = sync_check(N, C, HW, act, W, rank)) return rc;
+    if (!d_grad_y || !d_x || !d_gamma || !d_beta || !d_stat || !d_rows || !grad_x_out || !grad_gamma_out || !grad_beta_out)
+        return fail(LP_ERR_INVALID_ARG, "null argument");
+    if (!al16(d_grad_y) || !al16(d_x) || !al16(grad_x_out) || !al8(d_stat) || !al8(d_rows))
+        return fail(LP_ERR_INVALID_ARG, "grad_y, x and grad_x must be 16-byte, stat and rows 8-byte aligned");
+    lp::launch_bn_sync_bwd(d_grad_y, d_x, d_gamma, d_beta, d_stat, d_rows, W, rank, grad_x_out, grad_gamma_out,
+                           grad_beta_out, N, C, HW, act, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "bn_sync_backward launch failed");
+    return LP_OK;
+}
+
 static int pw_check(int N, int Cin, int Cout, int HW) {
     if (N < 1 || Cin < 1 || Cout < 1 || HW < 1) return fail(LP_ERR_INVALID_ARG, "N, Cin, Cout and HW must be positive");
     if (Cin > 65535 || Cout > 65535 || big((long long)N * HW) || big((long long)Cin * HW) || big((long long)Cout * HW))

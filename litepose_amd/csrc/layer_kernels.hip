@@ -6,6 +6,12 @@
 //   BatchNorm (+ act, + residual)   bn_stats_kernel (calib_kernels.hip) -> bn_fwd_kernel, out of place: the raw input
 //                                   survives, the channel's (mean, invstd) pair is kept in fp64 for the backward
 //                                   bn_bwd_stats_kernel -> bn_bwd_apply_kernel: the twins of that pair
+//   the same, synchronised over W ranks (lp_bn_sync_*): a collective of the caller's between the two halves of a pass --
+//                                   bn_stats_kernel -> bn_row_kernel (this rank's partials -> one fp64 row) | all-gather |
+//                                   bn_sync_fwd_kernel (the W rows added in rank order by every workgroup alike);
+//                                   bn_bwd_stats_kernel -> bn_row_kernel | all-gather | bn_sync_bwd_kernel.  The plain and
+//                                   the synchronised kernels share their bodies (bn_moments, bn_keep, bn_fwd_slice,
+//                                   bn_bwd_slice): W = 1 gives the plain kernels' bits
 //   1x1                             forward and data gradient are launch_pw on A fragments packed on the device
 //                                   (pw_pack_kernel: W, or W^T for the data gradient); the weight gradient is
 //                                   pw_wgrad_kernel, a GEMM over the N * HW pixels on v_mfma_f32_32x32x2_f32, cut into
@@ -68,41 +74,32 @@ __device__ __forceinline__ double2 bn_block_sum(double a, double b) {
     return double2{(wv[0].x + wv[1].x) + (wv[2].x + wv[3].x), (wv[0].y + wv[1].y) + (wv[2].y + wv[3].y)};
 }
 
-// y = act(z(x)) (+ res).  TRAIN: the batch's statistics from the partials of bn_stats_kernel, combined in index order by
-// every workgroup alike; slice 0 of a channel writes stat = [mean | invstd] x C (fp64) and moves the running pair
-// (running = [mean | var] x C) as bn_apply_kernel does.  !TRAIN: the running pair is the statistics, nothing but y is written.
-// Roundings of y: 3 (bn_z) + 1 with a residual, on the fp32 (meanf, istd).
-template <bool VEC, bool TRAIN>
-__global__ __launch_bounds__(256) void bn_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
-                                                     const double2* __restrict__ part, const float* __restrict__ gamma,
-                                                     const float* __restrict__ beta, float* __restrict__ running,
-                                                     float* __restrict__ y, double* __restrict__ stat, int N, int C, int HW,
-                                                     int chunk, int act, double momentum, double eps) {
-    const int s = blockIdx.x, c = blockIdx.y, S = gridDim.x;
-    double mean, invstd;
-    if (TRAIN) {
-        double sum = 0.0, sq = 0.0;
-        for (int i = 0; i < S; ++i) {
-            const double2 d = part[(long)c * S + i];
-            sum += d.x;
-            sq += d.y;
-        }
-        const double cnt = (double)N * (double)HW;
-        mean = sum / cnt;
-        double var = sq / cnt - mean * mean;
-        var = var < 0.0 ? 0.0 : var;                    // a NaN variance (a NaN or an Inf in the channel) stays NaN
-        invstd = 1.0 / sqrt(var + eps);
-        if (s == 0 && threadIdx.x == 0) {
-            const double unb = cnt > 1.0 ? var * (cnt / (cnt - 1.0)) : var;
-            running[c] = (float)((1.0 - momentum) * (double)running[c] + momentum * mean);
-            running[C + c] = (float)((1.0 - momentum) * (double)running[C + c] + momentum * unb);
-            stat[c] = mean;
-            stat[C + c] = invstd;
-        }
-    } else {
-        mean = (double)running[c];
-        invstd = 1.0 / sqrt((double)running[C + c] + eps);
-    }
+// mean, the clamped biased variance and invstd of a channel from its (sum, sum of squares) over cnt cells: THE expression of
+// bn_fwd_kernel and bn_sync_fwd_kernel
+__device__ __forceinline__ void bn_moments(double sum, double sq, double cnt, double eps, double& mean, double& var,
+                                           double& invstd) {
+    mean = sum / cnt;
+    var = sq / cnt - mean * mean;
+    var = var < 0.0 ? 0.0 : var;                        // a NaN variance (a NaN or an Inf in the channel) stays NaN
+    invstd = 1.0 / sqrt(var + eps);
+}
+
+// one thread per channel: the kept fp64 pair and the running pair moved by `momentum` with the unbiased variance over cnt
+__device__ __forceinline__ void bn_keep(float* __restrict__ running, double* __restrict__ stat, int C, int c, double mean,
+                                        double var, double invstd, double cnt, double momentum) {
+    const double unb = cnt > 1.0 ? var * (cnt / (cnt - 1.0)) : var;
+    running[c] = (float)((1.0 - momentum) * (double)running[c] + momentum * mean);
+    running[C + c] = (float)((1.0 - momentum) * (double)running[C + c] + momentum * unb);
+    stat[c] = mean;
+    stat[C + c] = invstd;
+}
+
+// slice s of channel c: y = act(z(x)) (+ res) on the fp32 (meanf, istd).  Roundings of y: 3 (bn_z) + 1 with a residual
+template <bool VEC>
+__device__ __forceinline__ void bn_fwd_slice(const float* __restrict__ x, const float* __restrict__ res,
+                                             const float* __restrict__ gamma, const float* __restrict__ beta,
+                                             float* __restrict__ y, int N, int C, int HW, int chunk, int s, int c, int act,
+                                             double mean, double invstd) {
     const float meanf = (float)mean, istd = (float)invstd;
     const float ga = gamma[c], be = beta[c];
     const float lo = act == ACT_NONE ? -INFINITY : 0.f;
@@ -125,6 +122,88 @@ __global__ __launch_bounds__(256) void bn_fwd_kernel(const float* __restrict__ x
             y[o] = v;
         }
     });
+}
+
+// y = act(z(x)) (+ res).  TRAIN: the batch's statistics from the partials of bn_stats_kernel, combined in index order by
+// every workgroup alike; slice 0 of a channel writes stat = [mean | invstd] x C (fp64) and moves the running pair
+// (running = [mean | var] x C) as bn_apply_kernel does.  !TRAIN: the running pair is the statistics, nothing but y is written.
+template <bool VEC, bool TRAIN>
+__global__ __launch_bounds__(256) void bn_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
+                                                     const double2* __restrict__ part, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, float* __restrict__ running,
+                                                     float* __restrict__ y, double* __restrict__ stat, int N, int C, int HW,
+                                                     int chunk, int act, double momentum, double eps) {
+    const int s = blockIdx.x, c = blockIdx.y, S = gridDim.x;
+    double mean, invstd;
+    if (TRAIN) {
+        double sum = 0.0, sq = 0.0;
+        for (int i = 0; i < S; ++i) {
+            const double2 d = part[(long)c * S + i];
+            sum += d.x;
+            sq += d.y;
+        }
+        const double cnt = (double)N * (double)HW;
+        double var;
+        bn_moments(sum, sq, cnt, eps, mean, var, invstd);
+        if (s == 0 && threadIdx.x == 0) bn_keep(running, stat, C, c, mean, var, invstd, cnt, momentum);
+    } else {
+        mean = (double)running[c];
+        invstd = 1.0 / sqrt((double)running[C + c] + eps);
+    }
+    bn_fwd_slice<VEC>(x, res, gamma, beta, y, N, C, HW, chunk, s, c, act, mean, invstd);
+}
+
+// The synchronised forward: rows [W][2C + 2] = sum[C] | sumsq[C] | count | 0 of every rank, in rank order.  Every workgroup
+// adds the W rows in rank order from 0.0 (W = 1: 0.0 + s == s, the plain kernel's bits), the cell count is the sum of the
+// rows' counts; from there on bn_fwd_kernel<., true>'s own expressions.  Slice 0 of a channel keeps stat = mean[C] |
+// invstd[C] | total count | 0 (channel 0 writes the tail) and moves the running pair.
+template <bool VEC>
+__global__ __launch_bounds__(256) void bn_sync_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
+                                                          const double* __restrict__ rows, int W,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          float* __restrict__ running, float* __restrict__ y,
+                                                          double* __restrict__ stat, int N, int C, int HW, int chunk, int act,
+                                                          double momentum, double eps) {
+    const int s = blockIdx.x, c = blockIdx.y;
+    const int RL = 2 * C + 2;
+    double sum = 0.0, sq = 0.0, cnt = 0.0;
+    for (int r = 0; r < W; ++r) {
+        const double* row = rows + (long)r * RL;
+        sum += row[c];
+        sq += row[C + c];
+        cnt += row[2 * C];
+    }
+    double mean, var, invstd;
+    bn_moments(sum, sq, cnt, eps, mean, var, invstd);
+    if (s == 0 && threadIdx.x == 0) {
+        bn_keep(running, stat, C, c, mean, var, invstd, cnt, momentum);
+        if (c == 0) {
+            stat[2 * C] = cnt;
+            stat[2 * C + 1] = 0.0;
+        }
+    }
+    bn_fwd_slice<VEC>(x, res, gamma, beta, y, N, C, HW, chunk, s, c, act, mean, invstd);
+}
+
+// part [C][S] pairs -> one row: row[c] = the channel's S first members, row[C + c] its S second members, each added in
+// index order from 0.0 (the order bn_fwd_kernel / bn_bwd_apply_kernel use); tail: row[2C] = cnt, row[2C + 1] = 0.
+// One thread per channel: S <= 64 dependent adds
+__global__ __launch_bounds__(256) void bn_row_kernel(const double2* __restrict__ part, int S, int C, double cnt, int tail,
+                                                     double* __restrict__ row) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double a = 0.0, b = 0.0;
+    for (int i = 0; i < S; ++i) {
+        const double2 d = part[(long)c * S + i];
+        a += d.x;
+        b += d.y;
+    }
+    row[c] = a;
+    row[C + c] = b;
+    if (tail && c == 0) {
+        row[2 * C] = cnt;
+        row[2 * C + 1] = 0.0;
+    }
 }
 
 // g = dy * act'(z), xhat = (x - mean) * invstd in fp64 from the kept pair: per-channel partial (sum g, sum g * xhat) in
@@ -157,28 +236,13 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_kernel(const float* __restri
     if (threadIdx.x == 0) part[(long)c * S + s] = t;
 }
 
-// dx = gamma * invstd * (g - sum(g) / n - xhat * sum(g * xhat) / n), evaluated in fp64 on the fp32 inputs and the kept
-// fp64 pair and rounded ONCE; slice 0 of a channel writes dgamma = sum(g * xhat) and dbeta = sum(g), one rounding each.
-// The partials are combined in index order by every workgroup alike -- the twin of bn_fwd_kernel.
+// slice s of channel c: dx = gamma * invstd * (g - sum(g) / n - xhat * sum(g * xhat) / n), evaluated in fp64 on the fp32
+// inputs and the kept fp64 pair and rounded ONCE; (sg, sgx) = (sum g, sum g * xhat) over the cnt cells of the channel
 template <bool VEC>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           const double* __restrict__ stat, const double2* __restrict__ part,
-                                                           float* __restrict__ dx, float* __restrict__ dgamma,
-                                                           float* __restrict__ dbeta, int N, int C, int HW, int chunk,
-                                                           int act) {
-    const int s = blockIdx.x, c = blockIdx.y, S = gridDim.x;
-    double sg = 0.0, sgx = 0.0;
-    for (int i = 0; i < S; ++i) {
-        const double2 d = part[(long)c * S + i];
-        sg += d.x;
-        sgx += d.y;
-    }
-    if (s == 0 && threadIdx.x == 0) {
-        dgamma[c] = (float)sgx;
-        dbeta[c] = (float)sg;
-    }
-    const double cnt = (double)N * (double)HW;
+__device__ __forceinline__ void bn_bwd_slice(const float* __restrict__ dy, const float* __restrict__ x,
+                                             const float* __restrict__ gamma, const float* __restrict__ beta,
+                                             const double* __restrict__ stat, float* __restrict__ dx, int N, int C, int HW,
+                                             int chunk, int s, int c, int act, double sg, double sgx, double cnt) {
     const double mg = sg / cnt, mgx = sgx / cnt;
     const double mean = stat[c], invstd = stat[C + c];
     const float meanf = (float)mean, istd = (float)invstd;
@@ -199,6 +263,55 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
             dx[o] = one(x[o], dy[o]);
         }
     });
+}
+
+// dx by bn_bwd_slice; slice 0 of a channel writes dgamma = sum(g * xhat) and dbeta = sum(g), one rounding each.
+// The partials are combined in index order by every workgroup alike -- the twin of bn_fwd_kernel.
+template <bool VEC>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           const double* __restrict__ stat, const double2* __restrict__ part,
+                                                           float* __restrict__ dx, float* __restrict__ dgamma,
+                                                           float* __restrict__ dbeta, int N, int C, int HW, int chunk,
+                                                           int act) {
+    const int s = blockIdx.x, c = blockIdx.y, S = gridDim.x;
+    double sg = 0.0, sgx = 0.0;
+    for (int i = 0; i < S; ++i) {
+        const double2 d = part[(long)c * S + i];
+        sg += d.x;
+        sgx += d.y;
+    }
+    if (s == 0 && threadIdx.x == 0) {
+        dgamma[c] = (float)sgx;
+        dbeta[c] = (float)sg;
+    }
+    const double cnt = (double)N * (double)HW;
+    bn_bwd_slice<VEC>(dy, x, gamma, beta, stat, dx, N, C, HW, chunk, s, c, act, sg, sgx, cnt);
+}
+
+// The synchronised backward: rows [W][2C] = sum_g[C] | sum_gxhat[C] of every rank, added in rank order from 0.0 by every
+// workgroup alike; n is the total count the forward kept in stat[2C].  dgamma / dbeta are THIS rank's row, rounded once
+// (torch.nn.SyncBatchNorm's convention: averaging the parameter gradients over the ranks makes them global).
+template <bool VEC>
+__global__ __launch_bounds__(256) void bn_sync_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          const double* __restrict__ stat, const double* __restrict__ rows,
+                                                          int W, int rank, float* __restrict__ dx, float* __restrict__ dgamma,
+                                                          float* __restrict__ dbeta, int N, int C, int HW, int chunk,
+                                                          int act) {
+    const int s = blockIdx.x, c = blockIdx.y;
+    double sg = 0.0, sgx = 0.0;
+    for (int r = 0; r < W; ++r) {
+        const double* row = rows + (long)r * 2 * C;
+        sg += row[c];
+        sgx += row[C + c];
+    }
+    if (s == 0 && threadIdx.x == 0) {
+        const double* own = rows + (long)rank * 2 * C;
+        dgamma[c] = (float)own[C + c];
+        dbeta[c] = (float)own[c];
+    }
+    bn_bwd_slice<VEC>(dy, x, gamma, beta, stat, dx, N, C, HW, chunk, s, c, act, sg, sgx, stat[2 * C]);
 }
 
 void launch_bn_fwd(const float* x, const float* res, const double* part, const float* gamma, const float* beta,
@@ -227,6 +340,47 @@ void launch_bn_bwd(const float* dy, const float* x, const float* gamma, const fl
         LP_LAUNCH(bn_bwd_apply_kernel<false>, grid, block, 0, s, dy, x, gamma, beta, stat, (const double2*)part, dx, dgamma,
                   dbeta, N, C, HW, k.chunk, act);
     }
+}
+
+void launch_bn_row(const double* part, int S, int C, double cnt, bool tail, double* row, hipStream_t s) {
+    LP_LAUNCH(bn_row_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const double2*)part, S, C, cnt, tail ? 1 : 0, row);
+}
+
+void launch_bn_sync_fwd(const float* x, const float* res, const double* rows, int W, const float* gamma, const float* beta,
+                        float* running, float* y, double* stat, int N, int C, int HW, int act, double momentum, double eps,
+                        hipStream_t s) {
+    const BnCut k = bn_cut(N, C, HW);
+    dim3 grid(k.S, C), block(256);
+    if (k.vec)
+        LP_LAUNCH(bn_sync_fwd_kernel<true>, grid, block, 0, s, x, res, rows, W, gamma, beta, running, y, stat, N, C, HW,
+                  k.chunk, act, momentum, eps);
+    else
+        LP_LAUNCH(bn_sync_fwd_kernel<false>, grid, block, 0, s, x, res, rows, W, gamma, beta, running, y, stat, N, C, HW,
+                  k.chunk, act, momentum, eps);
+}
+
+void launch_bn_sync_bwd_stats(const float* dy, const float* x, const float* gamma, const float* beta, const double* stat,
+                              double* part, double* row, int N, int C, int HW, int act, hipStream_t s) {
+    const BnCut k = bn_cut(N, C, HW);
+    dim3 grid(k.S, C), block(256);
+    if (k.vec)
+        LP_LAUNCH(bn_bwd_stats_kernel<true>, grid, block, 0, s, dy, x, gamma, beta, stat, (double2*)part, N, C, HW, k.chunk, act);
+    else
+        LP_LAUNCH(bn_bwd_stats_kernel<false>, grid, block, 0, s, dy, x, gamma, beta, stat, (double2*)part, N, C, HW, k.chunk, act);
+    launch_bn_row(part, k.S, C, 0.0, false, row, s);
+}
+
+void launch_bn_sync_bwd(const float* dy, const float* x, const float* gamma, const float* beta, const double* stat,
+                        const double* rows, int W, int rank, float* dx, float* dgamma, float* dbeta, int N, int C, int HW,
+                        int act, hipStream_t s) {
+    const BnCut k = bn_cut(N, C, HW);
+    dim3 grid(k.S, C), block(256);
+    if (k.vec)
+        LP_LAUNCH(bn_sync_bwd_kernel<true>, grid, block, 0, s, dy, x, gamma, beta, stat, rows, W, rank, dx, dgamma, dbeta, N,
+                  C, HW, k.chunk, act);
+    else
+        LP_LAUNCH(bn_sync_bwd_kernel<false>, grid, block, 0, s, dy, x, gamma, beta, stat, rows, W, rank, dx, dgamma, dbeta, N,
+                  C, HW, k.chunk, act);
 }
 
 // ====================================================================================== packing on the device

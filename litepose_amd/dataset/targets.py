@@ -171,15 +171,30 @@ class LabelledSet(CalibrationSet):
             masks.append(target_masks(self.mask_src, _upload(msk, self.device), B, R))
         return heats, masks, jts
 
-    def batches(self, input_size, output_sizes, batch_size, np_rng=None, py_rng=None, **aug):
+    def batches(self, input_size, output_sizes, batch_size, np_rng=None, py_rng=None, shard=None, **aug):
         """The set in order, ``batch_size`` images at a time -> ``(images, [heatmaps], [masks], [joints])`` on the device,
-        the lists indexed by output size.  ``aug``: the keyword parameters of ``draw_sample``."""
+        the lists indexed by output size.  ``aug``: the keyword parameters of ``draw_sample``.
+
+        ``shard=(rank, world)``: this rank's contiguous part of every batch (``parallel.shard_range``), for data-parallel
+        training: every rank walks the same batches, so the ranks meet in every collective of every step.  A batch with
+        fewer images than ranks raises ValueError (a rank without a part would miss the step's collectives).  The random
+        streams are drawn for the rank's own images only: give every rank its own ``np_rng`` / ``py_rng``."""
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError('batch_size must be positive')
+        if shard is not None:
+            from ..parallel import shard_range
+            rank, world = (int(v) for v in shard)
+            if not 0 <= rank < world:
+                raise ValueError('shard must be (rank, world) with 0 <= rank < world')
         output_sizes = [int(o) for o in output_sizes]
         for lo in range(0, len(self), batch_size):
             rows = list(range(lo, min(lo + batch_size, len(self))))
+            if shard is not None:
+                if len(rows) < world:
+                    raise ValueError('a batch of %d images cannot be sharded over %d ranks' % (len(rows), world))
+                a, b = shard_range(len(rows), rank, world)
+                rows = rows[a:b]
             img, tables, first = self.describe_labelled(rows, input_size, output_sizes, np_rng, py_rng, **aug)
             images = self.augment(img, input_size)
             heats, masks, jts = self.targets(rows, tables, first, output_sizes)

@@ -257,6 +257,8 @@ class LayerWalk(object):
     modules of ``TrainableLitePose``, or the per-step views of the supernet's tensors that
     ``pose_supermobilenet.TrainableSuperLitePose`` builds."""
 
+    sync_bn_group = None        # convert_sync_batchnorm sets the instance's: the process group of its BatchNorm statistics
+
     # ---- layers ----
     def _conv(self, x, conv):
         k, groups = conv.kernel_size[0], conv.groups
@@ -279,7 +281,7 @@ class LayerWalk(object):
             bn.num_batches_tracked += 1
         if self.backend == 'native':
             return F_.batch_norm_act(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, act, residual, self.training,
-                                     bn.momentum, bn.eps)
+                                     bn.momentum, bn.eps, self.sync_bn_group)
         y = torch.nn.functional.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, self.training,
                                            bn.momentum, bn.eps)
         if act == 'relu6':
@@ -399,6 +401,29 @@ class TrainableLitePose(LayerWalk, torch.nn.Module):
         net = LitePose(self._cfg, cfg_arch=self._cfg_arch, storage=storage)
         net.load_state_dict(self.state_dict())
         return net
+
+
+def convert_sync_batchnorm(model, group=None):
+    """The counterpart of ``nn.SyncBatchNorm.convert_sync_batchnorm`` (dist_train.py:260, ``MODEL.SYNC_BN``) for a native
+    ``TrainableLitePose``: from now on every BatchNorm of a training-mode forward takes its statistics over the batches of
+    all ranks of ``group`` (``nn.functional.batch_norm_act(group=...)``; two all-gathers of one fp64 row per layer and
+    step).  ``group=None``: the default process group as it is at this call.  Returns ``model``; its modules, parameters
+    and ``state_dict`` are unchanged (the group is a plain attribute, ``model.sync_bn_group``), eval mode is unchanged.
+
+    ``backend='torch'`` raises ValueError: those layers are torch's own, use ``torch.nn.SyncBatchNorm.
+    convert_sync_batchnorm`` on them."""
+    import torch.distributed as dist
+    if not isinstance(model, LayerWalk) or not isinstance(model, torch.nn.Module):
+        raise TypeError('convert_sync_batchnorm takes a TrainableLitePose, got %s' % type(model).__name__)
+    if model.backend != 'native':
+        raise ValueError("convert_sync_batchnorm is for backend='native'; a backend='torch' module holds torch's own "
+                         'BatchNorm2d layers: use torch.nn.SyncBatchNorm.convert_sync_batchnorm')
+    if group is None:
+        if not dist.is_initialized():
+            raise RuntimeError('convert_sync_batchnorm: group=None needs an initialised default process group')
+        group = dist.group.WORLD
+    model.sync_bn_group = group
+    return model
 
 
 def get_train_net(cfg, cfg_arch, backend='native'):

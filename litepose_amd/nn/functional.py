@@ -322,13 +322,120 @@ class _BatchNormAct(torch.autograd.Function):
         return gx, gg, gb, (grad_y if ctx.has_res else None), None, None, None, None, None, None
 
 
+# ---- synchronised over a process group: two calls per pass, one all-gather of a [2C (+ 2)] fp64 row between them
+SYNC_MAX_WORLD = 64                  # LP_BN_SYNC_MAX_WORLD
+_force_sync = False                  # tools/time_train_step.py: take the synchronised path at world size 1 too
+
+
+def bn_sync_stats(x):
+    """-> this rank's forward row, float64 [2C + 2] = sum | sumsq | count | 0."""
+    x = _f32(x, 'x', 4)
+    N, C, H, W = (int(v) for v in x.shape)
+    row = torch.empty(2 * C + 2, dtype=torch.float64, device=x.device)
+    L = nv.lib()
+    ws = _ws(L.lp_bn_workspace_bytes(N, C, H * W), x.device)
+    nv.check(L.lp_bn_sync_stats(nv.dptr(x), N, C, H * W, nv.dptr(row), nv.dptr(ws), ws.numel(), nv.stream_ptr()),
+             'lp_bn_sync_stats')
+    return row
+
+
+def bn_sync_forward(x, gamma, beta, running, rows, act=None, residual=None, momentum=0.1, eps=1e-5):
+    """``rows``: float64 [W, 2C + 2], the forward rows of all ranks in rank order.
+    -> (y, stat): stat float64 [2C + 2] = mean | invstd | total count | 0; ``running`` [2, C] is moved in place."""
+    x, gamma, beta = _f32(x, 'x', 4), _f32(gamma, 'gamma', 1), _f32(beta, 'beta', 1)
+    N, C, H, W = (int(v) for v in x.shape)
+    if gamma.numel() != C or beta.numel() != C or tuple(running.shape) != (2, C) or running.dtype != torch.float32:
+        raise ValueError('gamma, beta must be [C] and running float32 [2, C]')
+    if rows.dim() != 2 or rows.shape[1] != 2 * C + 2 or rows.dtype != torch.float64 or not rows.is_contiguous():
+        raise ValueError('rows must be contiguous float64 [W, 2C + 2]')
+    if residual is not None:
+        residual = _f32(residual, 'residual', 4)
+        if residual.shape != x.shape:
+            raise ValueError('residual must have the shape of x')
+    y = torch.empty_like(x)
+    stat = torch.empty(2 * C + 2, dtype=torch.float64, device=x.device)
+    nv.check(nv.lib().lp_bn_sync_forward(nv.dptr(x), nv.dptr(gamma), nv.dptr(beta), nv.dptr(running), nv.dptr(residual),
+                                         nv.dptr(y), nv.dptr(stat), nv.dptr(rows), int(rows.shape[0]), N, C, H * W,
+                                         ACTS[act], float(momentum), float(eps), nv.stream_ptr()), 'lp_bn_sync_forward')
+    return y, stat
+
+
+def bn_sync_backward_stats(grad_y, x, gamma, beta, stat, act=None):
+    """-> this rank's backward row, float64 [2C] = sum g | sum g * xhat, xhat on the global pair of ``stat``."""
+    grad_y, x, gamma, beta = _f32(grad_y, 'grad_y', 4), _f32(x, 'x', 4), _f32(gamma, 'gamma', 1), _f32(beta, 'beta', 1)
+    N, C, H, W = (int(v) for v in x.shape)
+    if grad_y.shape != x.shape or tuple(stat.shape) != (2 * C + 2,) or stat.dtype != torch.float64:
+        raise ValueError('grad_y must have the shape of x, stat must be float64 [2C + 2]')
+    row = torch.empty(2 * C, dtype=torch.float64, device=x.device)
+    L = nv.lib()
+    ws = _ws(L.lp_bn_workspace_bytes(N, C, H * W), x.device)
+    nv.check(L.lp_bn_sync_backward_stats(nv.dptr(grad_y), nv.dptr(x), nv.dptr(gamma), nv.dptr(beta), nv.dptr(stat), N, C,
+                                         H * W, ACTS[act], nv.dptr(row), nv.dptr(ws), ws.numel(), nv.stream_ptr()),
+             'lp_bn_sync_backward_stats')
+    return row
+
+
+def bn_sync_backward(grad_y, x, gamma, beta, stat, rows, rank, act=None):
+    """``rows``: float64 [W, 2C], the backward rows of all ranks in rank order -> (grad_x, grad_gamma, grad_beta);
+    grad_gamma / grad_beta are rank ``rank``'s own share (average the parameter gradients over the ranks)."""
+    grad_y, x, gamma, beta = _f32(grad_y, 'grad_y', 4), _f32(x, 'x', 4), _f32(gamma, 'gamma', 1), _f32(beta, 'beta', 1)
+    N, C, H, W = (int(v) for v in x.shape)
+    if grad_y.shape != x.shape or tuple(stat.shape) != (2 * C + 2,) or stat.dtype != torch.float64:
+        raise ValueError('grad_y must have the shape of x, stat must be float64 [2C + 2]')
+    if rows.dim() != 2 or rows.shape[1] != 2 * C or rows.dtype != torch.float64 or not rows.is_contiguous():
+        raise ValueError('rows must be contiguous float64 [W, 2C]')
+    gx, gg, gb = torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(beta)
+    nv.check(nv.lib().lp_bn_sync_backward(nv.dptr(grad_y), nv.dptr(x), nv.dptr(gamma), nv.dptr(beta), nv.dptr(stat),
+                                          nv.dptr(rows), int(rows.shape[0]), int(rank), N, C, H * W, ACTS[act],
+                                          nv.dptr(gx), nv.dptr(gg), nv.dptr(gb), nv.stream_ptr()), 'lp_bn_sync_backward')
+    return gx, gg, gb
+
+
+class _SyncBatchNormAct(torch.autograd.Function):
+    """Training mode over a process group: per pass one row kernel pair, ONE all-gather, one apply kernel."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, running_mean, running_var, act, momentum, eps, group):
+        from ..parallel import all_gather_rows, group_rank
+        running = torch.stack([running_mean.detach(), running_var.detach()]).float().contiguous()
+        rows = all_gather_rows(bn_sync_stats(x), group)
+        y, stat = bn_sync_forward(x, gamma, beta, running, rows, act, residual, momentum, eps)
+        running_mean.copy_(running[0])
+        running_var.copy_(running[1])
+        ctx.save_for_backward(x, gamma, beta, stat)
+        ctx.act, ctx.has_res, ctx.group, ctx.rank = act, residual is not None, group, group_rank(group)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        from ..parallel import all_gather_rows
+        x, gamma, beta, stat = ctx.saved_tensors
+        rows = all_gather_rows(bn_sync_backward_stats(grad_y, x, gamma, beta, stat, ctx.act), ctx.group)
+        gx, gg, gb = bn_sync_backward(grad_y, x, gamma, beta, stat, rows, ctx.rank, ctx.act)
+        return gx, gg, gb, (grad_y if ctx.has_res else None), None, None, None, None, None, None
+
+
 def batch_norm_act(x, gamma, beta, running_mean, running_var, act=None, residual=None, training=True, momentum=0.1,
-                   eps=1e-5):
+                   eps=1e-5, group=None):
     """``act(batch_norm(x)) (+ residual)``, ``act`` None / 'relu' / 'relu6'.  Training mode normalises with the batch's
     statistics and moves ``running_mean`` / ``running_var`` in place (the unbiased variance, as torch); eval mode
-    normalises with the running pair, and a backward through it raises ``NotImplementedError``."""
+    normalises with the running pair, and a backward through it raises ``NotImplementedError``.
+
+    ``group``: a ``torch.distributed`` process group.  In training mode with more than one rank the statistics are those of
+    all ranks' batches together (``torch.nn.SyncBatchNorm``): ``lp_bn_sync_stats``, one all-gather of the [2C + 2] fp64 row,
+    ``lp_bn_sync_forward``; the backward likewise with one all-gather of the [2C] row.  Every rank ends with the same bits
+    in ``running_mean`` / ``running_var``; ``gamma`` / ``beta`` receive this rank's share of their gradient.  ``None``, a
+    group of one, or eval mode: the calls above, unchanged."""
     if act not in ACTS:
         raise ValueError('act must be one of %s' % sorted(k for k in ACTS if k))
+    if training and group is not None:
+        from ..parallel import group_size
+        world = group_size(group)
+        if world > SYNC_MAX_WORLD:
+            raise ValueError('a synchronised batch_norm_act takes at most %d ranks' % SYNC_MAX_WORLD)
+        if world > 1 or _force_sync:
+            return _SyncBatchNormAct.apply(x, gamma, beta, residual, running_mean, running_var, act, float(momentum),
+                                           float(eps), group)
     return _BatchNormAct.apply(x, gamma, beta, residual, running_mean, running_var, act, bool(training), float(momentum),
                                float(eps))
 

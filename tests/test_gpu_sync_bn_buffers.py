@@ -1,0 +1,82 @@
+"""The buffer contract of the four synchronised BatchNorm calls (include/litepose_amd.h, "training-mode layers":
+lp_bn_sync_stats / _forward / _backward_stats / _backward) with the poisoned and guarded buffers of tests/_poison.py,
+in the style of tests/test_gpu_layer_buffers.py: whatever the outputs and the workspace held before (zeros, NaN, a huge
+finite value) the results are the same bits -- every element of every output is written; no guard around an output, an
+input or a workspace of exactly lp_bn_workspace_bytes is touched; the inputs are left as they were; one byte less of
+workspace answers LP_ERR_WORKSPACE."""
+import pytest
+import torch
+
+import _poison as po
+from litepose_amd import _native as nv
+from test_gpu_layer_buffers import _contract, _g
+
+pytestmark = pytest.mark.gpu
+LP_ERR_WORKSPACE = -6
+W, RANK = 3, 1
+
+
+@pytest.mark.parametrize('with_res', [False, True], ids=['plain', 'res'])
+@pytest.mark.parametrize('shape', [(3, 3, 35), (2, 32, 1024), (2, 8, 4096)], ids=['scalar', 'vec', 'sliced'])
+def test_sync_batch_norm_calls(shape, with_res):
+    L = nv.lib()
+    N, Cc, HW = shape
+    x, gamma, beta, res, dy = _g((N, Cc, HW), 7), _g((Cc,), 8) + 1, _g((Cc,), 9), _g((N, Cc, HW), 10), _g((N, Cc, HW), 11)
+    running0 = torch.stack([_g((Cc,), 12, 0.2), _g((Cc,), 13, 0.1).abs() + 1])
+    need = L.lp_bn_workspace_bytes(N, Cc, HW)
+    assert (need // (16 * Cc) > 1) == (shape == (2, 8, 4096))
+    s = nv.stream_ptr()
+    kept = {}
+
+    def stats(A):
+        row = A.out((2 * Cc + 2,), torch.float64, what='row_out')
+        ws = A.ws(need)
+        args = (nv.dptr(A.inp(x, what='x')), N, Cc, HW, nv.dptr(row), nv.dptr(ws))
+        assert L.lp_bn_sync_stats(*args, need - 1, s) == LP_ERR_WORKSPACE
+        return L.lp_bn_sync_stats(*args, need, s), dict(row=row)
+
+    def fwd(A):
+        y = A.out((N, Cc, HW), what='y_out')
+        stat = A.out((2 * Cc + 2,), torch.float64, what='stat_out')
+        rp, running = po.wrap_input(running0, 256, 'Z')               # in / out: its own guards, checked below
+        rc = L.lp_bn_sync_forward(nv.dptr(A.inp(x, what='x')), nv.dptr(A.inp(gamma, what='gamma')),
+                                  nv.dptr(A.inp(beta, what='beta')), nv.dptr(running),
+                                  nv.dptr(A.inp(res, what='res')) if with_res else None, nv.dptr(y), nv.dptr(stat),
+                                  nv.dptr(A.inp(kept['rows'], what='rows')), W, N, Cc, HW, 2, 0.1, 1e-5, s)
+        torch.cuda.synchronize()
+        rp.check_guards('running_io')
+        kept['stat'] = stat.clone()
+        return rc, dict(y=y, stat=stat, running=running)
+
+    def bstats(A):
+        row = A.out((2 * Cc,), torch.float64, what='row_out')
+        ws = A.ws(need)
+        args = (nv.dptr(A.inp(dy, what='grad_y')), nv.dptr(A.inp(x, what='x')), nv.dptr(A.inp(gamma, what='gamma')),
+                nv.dptr(A.inp(beta, what='beta')), nv.dptr(A.inp(kept['stat'], what='stat')), N, Cc, HW, 2, nv.dptr(row),
+                nv.dptr(ws))
+        assert L.lp_bn_sync_backward_stats(*args, need - 1, s) == LP_ERR_WORKSPACE
+        return L.lp_bn_sync_backward_stats(*args, need, s), dict(row=row)
+
+    def bwd(A):
+        gx = A.out((N, Cc, HW), what='grad_x_out')
+        gg, gb = A.out((Cc,), what='grad_gamma_out'), A.out((Cc,), what='grad_beta_out')
+        rc = L.lp_bn_sync_backward(nv.dptr(A.inp(dy, what='grad_y')), nv.dptr(A.inp(x, what='x')),
+                                   nv.dptr(A.inp(gamma, what='gamma')), nv.dptr(A.inp(beta, what='beta')),
+                                   nv.dptr(A.inp(kept['stat'], what='stat')), nv.dptr(A.inp(kept['brows'], what='rows')), W,
+                                   RANK, N, Cc, HW, 2, nv.dptr(gx), nv.dptr(gg), nv.dptr(gb), s)
+        return rc, dict(gx=gx, gg=gg, gb=gb)
+
+    _contract(stats)
+    # the rows of W ranks: this rank's own between two made-up neighbours (other counts, other sums)
+    A = po.Arena('Z')
+    rc, out = stats(A)
+    assert rc == 0
+    own = out['row'].clone()
+    kept['rows'] = torch.stack([own * 0.5, own, own * 1.25]).contiguous()
+    _contract(fwd)
+    _contract(bstats)
+    rc, out = bstats(po.Arena('Z'))
+    assert rc == 0
+    own = out['row'].clone()
+    kept['brows'] = torch.stack([own * -0.5, own, own * 2.0]).contiguous()
+    _contract(bwd)

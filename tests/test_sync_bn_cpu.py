@@ -1,0 +1,172 @@
+"""Data-parallel training, the parts that need no GPU: the four lp_bn_sync_* calls are declared, bound and exported and
+refuse bad arguments before they look at a pointer (every pointer is NULL here); convert_sync_batchnorm and do_train
+refuse what they document; GradBucket's views alias its flat buffer."""
+import os
+import re
+
+import pytest
+import torch
+
+from litepose_amd import _native as nv, config
+from litepose_amd.models import pose_mobilenet as pm
+from litepose_amd.parallel import GradBucket, all_gather_rows, broadcast_state
+
+import _train_net_case as TC
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, 'include', 'litepose_amd.h')
+CALLS = ['lp_bn_sync_stats', 'lp_bn_sync_forward', 'lp_bn_sync_backward_stats', 'lp_bn_sync_backward']
+LP_ERR_INVALID_ARG, LP_ERR_UNSUPPORTED = -1, -8
+
+
+def _header():
+    with open(HEADER) as f:
+        return re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+
+
+def test_header_declares_and_native_binds_the_four_calls():
+    hdr = _header()
+    L = nv.lib()
+    for name in CALLS:
+        m = re.search(r'\b%s\s*\(([^;{]*?)\)\s*;' % name, hdr, re.S)
+        assert m, name
+        for param in m.group(1).split(','):
+            # a writable pointer carries no d_ prefix (the census of tests/test_poison_cpu.py keys on it)
+            if re.search(r'\*\s*d_\w+\s*$', param):
+                assert re.search(r'\bconst\b', param), (name, param)
+        assert name in nv.EXPORTS and hasattr(L, name), name
+        assert len(nv._SIGS[name][1]) == len(m.group(1).split(',')), name
+    assert int(re.search(r'#define\s+LP_BN_SYNC_MAX_WORLD\s+(\d+)', hdr).group(1)) == 64
+
+
+def test_no_sync_call_names_a_writable_pointer_d():
+    from test_poison_cpu import writable_device_calls
+    assert not set(CALLS) & writable_device_calls()
+
+
+def _stats(N=2, C=3, HW=5):
+    return nv.lib().lp_bn_sync_stats(None, N, C, HW, None, None, 0, None)
+
+
+def _forward(W=2, N=2, C=3, HW=5, act=0):
+    return nv.lib().lp_bn_sync_forward(None, None, None, None, None, None, None, None, W, N, C, HW, act, 0.1, 1e-5, None)
+
+
+def _bstats(N=2, C=3, HW=5, act=0):
+    return nv.lib().lp_bn_sync_backward_stats(None, None, None, None, None, N, C, HW, act, None, None, 0, None)
+
+
+def _backward(W=2, rank=0, N=2, C=3, HW=5, act=0):
+    return nv.lib().lp_bn_sync_backward(None, None, None, None, None, None, W, rank, N, C, HW, act, None, None, None, None)
+
+
+def _refused(rc, code, word):
+    assert rc == code, (rc, nv.lib().lp_last_error())
+    assert word in nv.lib().lp_last_error().decode(), nv.lib().lp_last_error()
+
+
+@pytest.mark.parametrize('call', [_stats, _forward, _bstats, _backward], ids=CALLS)
+def test_sizes_are_refused_as_bn_check_refuses_them(call):
+    for bad in (dict(N=0), dict(C=0), dict(HW=0), dict(N=-1)):
+        _refused(call(**bad), LP_ERR_INVALID_ARG, 'positive')
+    for big in (dict(C=65536), dict(N=1 << 20, HW=1 << 11), dict(C=1 << 15, HW=1 << 16)):
+        _refused(call(**big), LP_ERR_UNSUPPORTED, '2^31')
+    if call is not _stats:
+        for act in (-1, 3):
+            _refused(call(act=act), LP_ERR_INVALID_ARG, 'act')
+    # sizes in range: the NULL pointers themselves are the next refusal -- nothing was dereferenced on the way
+    _refused(call(), LP_ERR_INVALID_ARG, 'null')
+
+
+def test_world_size_and_rank_are_refused_before_any_pointer_is_read():
+    for W in (0, -1, 65, 1 << 20):
+        _refused(_forward(W=W), LP_ERR_INVALID_ARG, 'W must')
+        _refused(_backward(W=W, rank=0), LP_ERR_INVALID_ARG, 'W must')
+    for W, rank in ((1, 1), (2, 2), (64, 64), (2, -1), (64, 1 << 20)):
+        _refused(_backward(W=W, rank=rank), LP_ERR_INVALID_ARG, 'rank')
+    for W, rank in ((1, 0), (64, 63)):
+        _refused(_forward(W=W), LP_ERR_INVALID_ARG, 'null')
+        _refused(_backward(W=W, rank=rank), LP_ERR_INVALID_ARG, 'null')
+
+
+def test_convert_sync_batchnorm_marks_a_native_module_and_refuses_a_torch_one():
+    cfg = config.get_cfg()
+    group = object()                                        # whatever torch.distributed hands out: only passed on
+    m = pm.get_train_net(cfg, TC.ARCH)
+    before = {k: v.clone() for k, v in m.state_dict().items()}
+    assert getattr(m, 'sync_bn_group', None) is None
+    assert pm.convert_sync_batchnorm(m, group) is m and m.sync_bn_group is group
+    after = m.state_dict()
+    assert list(after) == list(before) and all(torch.equal(after[k], before[k]) for k in before)
+    with pytest.raises(ValueError, match='convert_sync_batchnorm'):
+        pm.convert_sync_batchnorm(pm.get_train_net(cfg, TC.ARCH, backend='torch'), group)
+    with pytest.raises(TypeError):
+        pm.convert_sync_batchnorm(torch.nn.BatchNorm2d(3), group)
+    with pytest.raises(RuntimeError, match='process group'):
+        pm.convert_sync_batchnorm(pm.get_train_net(cfg, TC.ARCH))       # group=None: no default group here
+
+
+def test_do_train_refuses_three_combinations_with_a_group():
+    from litepose_amd.core.trainer import do_train
+    cfg = config.get_cfg()
+    group = object()
+    model = torch.nn.Linear(2, 2)
+    opt = torch.optim.SGD(model.parameters(), lr=0.1)
+
+    def loader():
+        raise AssertionError('the refusal comes before the first batch')
+        yield
+
+    with pytest.raises(ValueError, match='graph'):
+        do_train(cfg, model, loader(), None, opt, graph=True, group=group)
+    with pytest.raises(ValueError, match='teacher'):
+        do_train(cfg, model, loader(), None, opt, teacher=lambda x: x, group=group)
+    sampling = torch.nn.Linear(2, 2)
+    sampling.arch_manager = object()
+    with pytest.raises(ValueError, match='architecture'):
+        do_train(cfg, sampling, loader(), None, torch.optim.SGD(sampling.parameters(), lr=0.1), group=group)
+    assert not hasattr(model, '_grad_bucket') and not hasattr(sampling, '_grad_bucket')
+
+
+def test_grad_bucket_views_alias_the_flat_buffer():
+    g = torch.Generator().manual_seed(5)
+    shapes = [(3, 5), (7,), (2, 1, 3, 3), (1,), (4, 4)]
+    params = [torch.randn(s, generator=g).requires_grad_() for s in shapes]
+    frozen = torch.randn(6, generator=g)                    # requires no gradient: not in the bucket
+    b = GradBucket(params[:2] + [frozen] + params[2:])
+    assert b.params == params and b.flat.dtype == torch.float32
+    off = 0
+    for p, o in zip(params, b.offsets):
+        assert o == off and o % 4 == 0
+        off += (p.numel() + 3) // 4 * 4
+    assert b.flat.numel() == off
+    b.flat.fill_(7.0)
+    b.zero_grad()
+    assert not bool(b.flat.any())
+    for p, o in zip(params, b.offsets):
+        assert p.grad.shape == p.shape and p.grad.data_ptr() == b.flat.data_ptr() + 4 * o
+    assert frozen.grad is None
+    # autograd accumulates into the views in place: the flat buffer holds the gradients, the padding stays zero
+    sum((p * (i + 1)).sum() for i, p in enumerate(params)).backward()
+    kept = [p.grad for p in params]
+    want = torch.zeros_like(b.flat)
+    for i, (p, o) in enumerate(zip(params, b.offsets)):
+        assert p.grad.data_ptr() == b.flat.data_ptr() + 4 * o
+        want[o:o + p.numel()] = i + 1
+    assert torch.equal(b.flat, want)
+    b.all_reduce_mean()                                     # no process group: one rank, nothing moves
+    assert torch.equal(b.flat, want)
+    b.zero_grad()
+    assert all(p.grad is k for p, k in zip(params, kept)) and not bool(b.flat.any())
+    with pytest.raises(ValueError):
+        GradBucket([frozen])
+
+
+def test_one_rank_needs_no_collective():
+    row = torch.arange(8, dtype=torch.float64)
+    rows = all_gather_rows(row)
+    assert rows.shape == (1, 8) and torch.equal(rows[0], row)
+    m = torch.nn.BatchNorm2d(3)
+    before = {k: v.clone() for k, v in m.state_dict().items()}
+    broadcast_state(m)
+    assert all(torch.equal(v, before[k]) for k, v in m.state_dict().items())

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Wall time of one whole native training step (GPU box): the measurement of DESIGN.md 4f, "the captured step".
 
-    python tools/time_train_step.py [REPS] [ARCH] [BATCHES...] [--optimizer-only]
+    python tools/time_train_step.py [REPS] [ARCH] [BATCHES...] [--optimizer-only] [--sync-bn]
 
 For ARCH (default search-XS at its own resolution) and every batch size (default 16 64), medians of REPS whole steps after
 10 warm-ups, each step timed on the host from its first call to a device synchronisation behind it:
@@ -14,7 +14,12 @@ and the optimizer call alone on the module's parameter list with gradients in pl
 the library's, the library's launch count, and the bytes a step must move (4 streams of the parameter set read and 3
 written for Adam, 3 and 2 for SGD with momentum) over the time -- the parameter set of search-XS fits the Infinity Cache,
 so that figure is not an HBM rate.  Rows the tree cannot run (a commit without litepose_amd.optim) are reported as such,
-so the same file runs on an older tree."""
+so the same file runs on an older tree.
+
+--sync-bn (the measurement of DESIGN.md 4h) replaces the step rows by two alternating pairs of the eager loop on the
+library's Adam: the plain step, and the data-parallel step forced through a process group of ONE rank (gloo) -- the
+synchronised BatchNorm calls and the gradient bucket without any collective: what the extra launches of every BatchNorm
+cost, not what a collective costs."""
 import os
 import sys
 import time
@@ -110,6 +115,37 @@ def step_rows(cfg, arch, res, N, reps):
         print('batch %3d  the library rows: this tree has no litepose_amd.optim' % N, flush=True)
 
 
+def sync_rows(cfg, arch, res, N, reps):
+    import tempfile
+    import torch.distributed as dist
+    from litepose_amd.nn import functional as F_
+    if lp_optim is None or not hasattr(pm, 'convert_sync_batchnorm'):
+        print('batch %3d  the synchronised rows: this tree has no data-parallel training' % N, flush=True)
+        return
+    if not dist.is_initialized():
+        rendezvous = tempfile.NamedTemporaryFile(delete=False)
+        rendezvous.close()
+        dist.init_process_group('gloo', init_method='file://' + rendezvous.name, rank=0, world_size=1)
+    batch = batch_of(cfg, res, N)
+    fac = MultiLossFactory(cfg)
+    for _ in range(2):
+        for label, sync in (('eager, plain BatchNorm', False), ('eager, sync path, group of one', True)):
+            m = module(cfg, arch)
+            opt = lp_optim.Adam(m.parameters(), lr=1e-4)
+            F_._force_sync = sync
+            try:
+                if sync:
+                    pm.convert_sync_batchnorm(m)
+                    med, lo, hi = wall(lambda: trainer.do_train(cfg, m, [batch], fac, opt, group=dist.group.WORLD), reps)
+                else:
+                    med, lo, hi = wall(lambda: trainer.do_train(cfg, m, [batch], fac, opt), reps)
+            finally:
+                F_._force_sync = False
+            bns = sum(isinstance(x, torch.nn.BatchNorm2d) for x in m.modules())
+            print('batch %3d  %-34s %8.2f ms  (min %.2f, max %.2f)  %d BatchNorms' % (N, label, med, lo, hi, bns), flush=True)
+            del m, opt
+
+
 def optimizer_rows(cfg, arch, reps):
     m = module(cfg, arch)
     params = list(m.parameters())
@@ -144,12 +180,16 @@ def optimizer_rows(cfg, arch, reps):
             print('  %-38s not taken: %s' % (label, str(e).splitlines()[0][:160]), flush=True)
 
 
-def main(reps, name, batches, optimizer_only):
+def main(reps, name, batches, optimizer_only, sync_bn=False):
     cfg, arch = config.get_cfg(), arch_zoo.load_arch(name)
     res = int(arch['img_size'])
     print('whole training steps of %s at %d' % (name, res))
     print('command: python tools/time_train_step.py %d %s %s   (%d warm-ups, medians of %d steps, host clock with a '
           'synchronisation behind every step)' % (reps, name, ' '.join(str(b) for b in batches), WARMUP, reps), flush=True)
+    if sync_bn:
+        for N in batches:
+            sync_rows(cfg, arch, res, N, reps)
+        return
     if not optimizer_only:
         for N in batches:
             step_rows(cfg, arch, res, N, reps)
@@ -159,4 +199,4 @@ def main(reps, name, batches, optimizer_only):
 if __name__ == '__main__':
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
     main(int(args[0]) if args else 30, args[1] if len(args) > 1 else 'search-XS',
-         [int(a) for a in args[2:]] or [16, 64], '--optimizer-only' in sys.argv)
+         [int(a) for a in args[2:]] or [16, 64], '--optimizer-only' in sys.argv, '--sync-bn' in sys.argv)

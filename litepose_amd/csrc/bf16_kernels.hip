@@ -14,7 +14,10 @@
 // (The fp32 path keeps planar NCHW: its matrix-core operand is one f32 per lane; see net_kernels.hip.)
 // Round 7, fp16 storage (LP_STORAGE_F16): every kernel below is a __device__ body templated on the 16-bit format F
 // (fmt16.h) under one __global__ template with F leading (lp::pwb_kernel<lp::Bf16, 1, 2, false, false>, the same list
-// after lp::F16); a launcher turns its `bool f16` into F with with_fmt.
+// after lp::F16); a launcher turns its `bool f16` into F with with_fmt.  The body / wrapper pair stays: written into its
+// __global__ template a body compiles to other code (tried on all eleven of the 16-bit path: registers renumbered,
+// operands and waits moved in 60 of the 62 kernels of this file, every mbtb / mbtb_s2 / mbtd / stem4 kernel), so folding
+// one is a change to measure, not a tidy-up.
 #include "kernels.h"
 #include "fused_common.h"
 #include "fmt16.h"

@@ -82,12 +82,11 @@ __global__ __launch_bounds__(512, 2) void mb16_kernel(
     u32x4* W2 = W1 + WG::N1;                                          // [NMT][2][3][64]
     u32x4* WD = W2 + WG::N2 + WG::N3;                                 // [2 chunk parities][16 pairs][28]
 
-    // weight staging (kernels.h: LP_STAGE_*): wave w moves elements [64w + 512j, +64) of [expand slice of chunk g+1 |
-    // project slice of chunk g | expand bias of chunk g+1 | depthwise rows of chunk g+1 -> buffer (g+1)&1], g counting the
-    // chunks of the whole run: the first chunk of the next block is staged under the last depthwise of this one.  Every
-    // region is a whole number of 64-element wave transfers, so the source region is wave-uniform.  stage_load(g) at the
-    // top of the depthwise phase (nobody reads these regions then) requests the data into stg[], stage_store(g) writes it
-    // to LDS in front of the barrier that ends the phase.
+    // weight stage (fused_common.h: layout, protocol, LP_STAGE_*) with this kernel's own chunk map -- the standard one with
+    // g counting the chunks of the whole run, so that the first chunk of the next block is staged under the last depthwise of
+    // this one -- and its own copy of the two loops (stage_load = stage_issue, stage_store = stage_land): the CK = 6 variant
+    // sits at the register budget, and its code depends on how deep these lambdas nest.  Calling the shared loops, or
+    // writing stage_load's loop into stage_now, gives <6, 3, *> another register allocation (235 -> 234, waits moved).
     constexpr bool PIPE = CK < 6;                                    // (the 96-channel variant sits at the register budget)
     u32x4 stg[WG::NLD];
     auto stage_addr = [&](int g, int j, const u32x4*& src, u32x4*& dst) -> bool {

@@ -29,7 +29,7 @@
 //     two halves of a wave complete every record in the same instruction
 // Round 7, fp16 storage (LP_STORAGE_F16): every kernel below is a __device__ body templated on the 16-bit format F
 // (fmt16.h) under one __global__ template with F leading (lp::mbtb_kernel<lp::Bf16, 1, 1, true>, the same list after
-// lp::F16); launch_mbtb turns its `bool f16` into F with with_fmt.
+// lp::F16); launch_mbtb turns its `bool f16` into F with with_fmt (why the pair stays: bf16_kernels.hip).
 #include "kernels.h"
 #include "fused_common.h"
 #include "dw7.h"
@@ -159,46 +159,12 @@ __device__ __forceinline__ void mbtb_kernel_body(
     u32x4* W2 = W1 + WG::N1;                                          // [NMT][2][64]
     u32x4* WD = W2 + WG::N2 + WG::N3;                                 // [2 chunk parities][16 pairs][28]
 
-    // weight staging (mbt_kernel's scheme; kernels.h: LP_STAGE_*): wave w moves elements [64w + 512j, +64) of [expand slice of
-    // chunk c+1 | project slices of chunk c | expand bias of chunk c+1 | depthwise rows of chunk c+1 -> buffer (c+1)&1];
-    // issued at the top of the depthwise phase, drained by the workgroup barrier that ends it
-    u32x4 stg[WG::NLD];                                               // staging registers (kernels.h: LP_STAGE_*)
-    auto stage_addr = [&](int c, int j, const u32x4*& src, u32x4*& dst) -> bool {
-        const int e0 = 64 * wave + 512 * j;                          // wave-uniform; every segment is 64 elements
-        if (e0 >= WG::NTOT) return false;
-        const int ca = max(c, 0), cb = min(c + 1, nchunks - 1), dpar = (c + 1) & 1;
-                dst = W1 + e0;
-        if (e0 < WG::N1) src = w1 + (long)cb * WG::N1 + e0 + lane;
-        else if (e0 < WG::N1 + WG::N2) {
-            const int seg = (e0 - WG::N1) >> 6;              // (filter block, k-step of the chunk)
-            const int ks = min(2 * ca + (seg & 1), KS2 - 1); // the half chunk's second k-step is never used
-            src = w2 + ((long)(seg >> 1) * KS2 + ks) * 64 + lane;
-        } else if (e0 < WG::N1 + WG::N2 + WG::N3) {
-            src = reinterpret_cast<const u32x4*>(b1f) + (long)cb * 8 + min(lane, 7);
-        } else {
-            src = reinterpret_cast<const u32x4*>(wrow) + (long)cb * WG::N4 + (e0 - WG::N1 - WG::N2 - WG::N3) + lane;
-            dst += dpar * WG::N4;
-        }
-        return true;
+    // weight stage (fused_common.h): the standard chunk map, the project's last k-step clamped (half chunk)
+    u32x4 stg[WG::NLD];
+    auto stage_addr = [&](int c, int j, const u32x4*& src, u32x4*& dst) {
+        return stage_chunk_addr<WG, true>(wave, lane, j, c, nchunks, KS2, w1, w2, b1f, wrow, W1, src, dst);
     };
-    auto stage_load = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < WG::NLD; ++j) {
-            const u32x4* src;
-            u32x4* dst;
-            if (stage_addr(c, j, src, dst)) LP_STAGE_LOAD(stg[j], src, dst);
-        }
-    };
-    auto stage_store = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < WG::NLD; ++j) {
-            const u32x4* src;
-            u32x4* dst;
-            if (stage_addr(c, j, src, dst)) LP_STAGE_STORE(stg[j], dst, lane);
-        }
-        LP_STAGE_DRAIN();
-    };
-    stage_load(-1);
+    stage_issue<WG>(stg, -1, stage_addr);
 
     // ---- the x halo tile: wave w owns cell groups w and w + 8 (32 cells each, 484 in all); the record of octet
     //      2ks + half of halo cell hp IS the B fragment of k-step ks.  Cells outside the image and octets beyond the
@@ -275,7 +241,7 @@ __device__ __forceinline__ void mbtb_kernel_body(
         }
     };
 
-    stage_store(-1);
+    stage_land<WG>(stg, -1, lane, stage_addr);
     __syncthreads();                                                 // the first stage has landed
     expand();
     __syncthreads();
@@ -283,7 +249,7 @@ __device__ __forceinline__ void mbtb_kernel_body(
     for (int ch = 0; ch < nchunks; ++ch) {
         // weights of the next two 1x1 slices (this chunk's project, the next chunk's expand), the next chunk's bias
         // and filter rows: requested now, parked in LDS by the barrier that ends the depthwise
-        stage_load(ch);
+        stage_issue<WG>(stg, ch, stage_addr);
         // ================= depthwise 7x7 + bias + relu6 + round: pairs 2w, 2w+1 in ONE pass ==================
         {
             const int kp = wave * 2 + dwpair;
@@ -309,7 +275,7 @@ __device__ __forceinline__ void mbtb_kernel_body(
             *reinterpret_cast<u32x4*>(dp + (16 - slot)) = o1;
         }
         LP_TR(1);
-        stage_store(ch);
+        stage_land<WG>(stg, ch, lane, stage_addr);
         __syncthreads();                     // D complete, every wave is done reading E, the staged weights have landed
         LP_TR(2);
         // ================= project: acc += W2[:, chunk] . D[chunk][this wave's 32 px] ================
@@ -431,43 +397,12 @@ __device__ __forceinline__ void mbtb_s2_kernel_body(
     u32x4* W2 = W1 + WG::N1;
     u32x4* WD = W2 + WG::N2 + WG::N3;
 
-    u32x4 stg[WG::NLD];                                               // staging registers (kernels.h: LP_STAGE_*)
-    auto stage_addr = [&](int c, int j, const u32x4*& src, u32x4*& dst) -> bool {
-        const int e0 = 64 * wave + 512 * j;                          // wave-uniform; every segment is 64 elements
-        if (e0 >= WG::NTOT) return false;
-        const int ca = max(c, 0), cb = min(c + 1, nchunks - 1), dpar = (c + 1) & 1;
-                dst = W1 + e0;
-        if (e0 < WG::N1) src = w1 + (long)cb * WG::N1 + e0 + lane;
-        else if (e0 < WG::N1 + WG::N2) {
-            const int seg = (e0 - WG::N1) >> 6;
-            const int ks = min(2 * ca + (seg & 1), KS2 - 1);
-            src = w2 + ((long)(seg >> 1) * KS2 + ks) * 64 + lane;
-        } else if (e0 < WG::N1 + WG::N2 + WG::N3) {
-            src = reinterpret_cast<const u32x4*>(b1f) + (long)cb * 8 + min(lane, 7);
-        } else {
-            src = reinterpret_cast<const u32x4*>(wrow) + (long)cb * WG::N4 + (e0 - WG::N1 - WG::N2 - WG::N3) + lane;
-            dst += dpar * WG::N4;
-        }
-        return true;
+    // weight stage (fused_common.h): mbtb_kernel's
+    u32x4 stg[WG::NLD];
+    auto stage_addr = [&](int c, int j, const u32x4*& src, u32x4*& dst) {
+        return stage_chunk_addr<WG, true>(wave, lane, j, c, nchunks, KS2, w1, w2, b1f, wrow, W1, src, dst);
     };
-    auto stage_load = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < WG::NLD; ++j) {
-            const u32x4* src;
-            u32x4* dst;
-            if (stage_addr(c, j, src, dst)) LP_STAGE_LOAD(stg[j], src, dst);
-        }
-    };
-    auto stage_store = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < WG::NLD; ++j) {
-            const u32x4* src;
-            u32x4* dst;
-            if (stage_addr(c, j, src, dst)) LP_STAGE_STORE(stg[j], dst, lane);
-        }
-        LP_STAGE_DRAIN();
-    };
-    stage_load(-1);
+    stage_issue<WG>(stg, -1, stage_addr);
 
     // ---- the x halo tile: wave w owns cell groups w, w + 8, w + 16 (and 24: wave 0); records = B fragments --------
     u32x4 xb[SB_GPW][CK];
@@ -539,12 +474,12 @@ __device__ __forceinline__ void mbtb_s2_kernel_body(
         }
     };
 
-    stage_store(-1);
+    stage_land<WG>(stg, -1, lane, stage_addr);
     __syncthreads();                                                 // the first stage has landed
     expand();
     __syncthreads();
     for (int ch = 0; ch < nchunks; ++ch) {
-        stage_load(ch);
+        stage_issue<WG>(stg, ch, stage_addr);
         // ================= depthwise 7x7 stride 2 + bias + relu6 + round: pairs 2w, 2w+1 in ONE pass ===========
         {
             const int kp = wave * 2 + dpair;
@@ -564,7 +499,7 @@ __device__ __forceinline__ void mbtb_s2_kernel_body(
             *reinterpret_cast<uint2*>(dp) = d0;
             *reinterpret_cast<uint2*>(dp + 16) = d1;
         }
-        stage_store(ch);
+        stage_land<WG>(stg, ch, lane, stage_addr);
         __syncthreads();                     // D complete, every wave is done reading E, the staged weights have landed
         // ================= project: acc += W2[:, 16-ch half pks of the chunk] . D[those ch][px tile pt] ========
         if (2 * ch + pks < KS2) {                                    // wave-uniform; false only in a half chunk
@@ -691,6 +626,8 @@ __device__ __forceinline__ void mbtd_kernel_body(     // 4 waves per SIMD = two 
     u32x4* WD = W2 + WG::N2 + WG::N3;                                 // [2 chunk parities][16 pairs][28]
     const u32x4* bdw = wrow2 + (long)nchunks * WG::N4;                // depthwise biases [chunk][32 fp32] behind the taps
 
+    // weight stage (fused_common.h): the standard chunk map (stage_chunk_addr<WG, true>) with this kernel's own N3 transfer.
+    // Written out: delegating the three shared regions to the standard function costs 20-60 instructions per instantiation
     u32x4 stg[WG::NLD];
     auto stage_addr = [&](int c, int j, const u32x4*& src, u32x4*& dst) -> bool {
         const int e0 = 64 * wave + 512 * j;
@@ -715,24 +652,7 @@ __device__ __forceinline__ void mbtd_kernel_body(     // 4 waves per SIMD = two 
         }
         return true;
     };
-    auto stage_load = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < WG::NLD; ++j) {
-            const u32x4* src;
-            u32x4* dst;
-            if (stage_addr(c, j, src, dst)) LP_STAGE_LOAD(stg[j], src, dst);
-        }
-    };
-    auto stage_store = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < WG::NLD; ++j) {
-            const u32x4* src;
-            u32x4* dst;
-            if (stage_addr(c, j, src, dst)) LP_STAGE_STORE(stg[j], dst, lane);
-        }
-        LP_STAGE_DRAIN();
-    };
-    stage_load(-1);
+    stage_issue<WG>(stg, -1, stage_addr);
 
     u32x4 xb[2][CK];
     bool xok[2], ein[2];
@@ -809,13 +729,13 @@ __device__ __forceinline__ void mbtd_kernel_body(     // 4 waves per SIMD = two 
         }
     };
 
-    stage_store(-1);
+    stage_land<WG>(stg, -1, lane, stage_addr);
     __syncthreads();
     expand();
     __syncthreads();
     LP_TR(0);
     for (int ch = 0; ch < nchunks; ++ch) {
-        stage_load(ch);
+        stage_issue<WG>(stg, ch, stage_addr);
         // ================= depthwise 7x7 (dot2 on cell pairs) + bias + relu6 + round: pairs 2w, 2w+1 in ONE pass ==========
         {
             const int kp = wave * 2 + dwpair;
@@ -870,7 +790,7 @@ __device__ __forceinline__ void mbtd_kernel_body(     // 4 waves per SIMD = two 
             *reinterpret_cast<u32x4*>(dp + (16 - slot)) = o1;
         }
         LP_TR(1);
-        stage_store(ch);
+        stage_land<WG>(stg, ch, lane, stage_addr);
         __syncthreads();
         LP_TR(2);
 #pragma unroll

@@ -70,45 +70,12 @@ __global__ __launch_bounds__(512, 2) void mbt_kernel(
     u32x4* W2 = W1 + WG::N1;                                          // [NMT][2][3][64]
     u32x4* WD = W2 + WG::N2 + WG::N3;                                 // [2 chunk parities][16 pairs][28]
 
-    // weight staging, identical to mb16_kernel (kernels.h: LP_STAGE_*): wave w moves elements [64w + 512j, +64) of [expand slice
-    // of chunk c+1 | project slice of chunk c | expand bias of chunk c+1 | depthwise rows of chunk c+1 -> buffer
-    // (c+1)&1]; issued at the top of the depthwise phase, drained by the workgroup barrier that ends it
-    u32x4 stg[WG::NLD];                                               // staging registers (kernels.h: LP_STAGE_*)
-    auto stage_addr = [&](int c, int j, const u32x4*& src, u32x4*& dst) -> bool {
-        const int e0 = 64 * wave + 512 * j;                          // wave-uniform; every segment is 64 elements
-        if (e0 >= WG::NTOT) return false;
-        const int ca = max(c, 0), cb = min(c + 1, nchunks - 1), dpar = (c + 1) & 1;
-                dst = W1 + e0;
-        if (e0 < WG::N1) src = w1s + (long)cb * WG::N1 + e0 + lane;
-        else if (e0 < WG::N1 + WG::N2) {
-            const int f0 = e0 - WG::N1, seg = f0 / 192, within = f0 - seg * 192;
-            src = w2s + ((long)(seg >> 1) * KS2 + 2 * ca + (seg & 1)) * 192 + within + lane;
-        } else if (e0 < WG::N1 + WG::N2 + WG::N3) {
-            src = reinterpret_cast<const u32x4*>(b1f) + (long)cb * 8 + min(lane, 7);
-        } else {
-            src = reinterpret_cast<const u32x4*>(wrow) + (long)cb * WG::N4 + (e0 - WG::N1 - WG::N2 - WG::N3) + lane;
-            dst += dpar * WG::N4;
-        }
-        return true;
+    // weight stage (fused_common.h): the standard chunk map
+    u32x4 stg[WG::NLD];
+    auto stage_addr = [&](int c, int j, const u32x4*& src, u32x4*& dst) {
+        return stage_chunk_addr<WG, false>(wave, lane, j, c, nchunks, KS2, w1s, w2s, b1f, wrow, W1, src, dst);
     };
-    auto stage_load = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < WG::NLD; ++j) {
-            const u32x4* src;
-            u32x4* dst;
-            if (stage_addr(c, j, src, dst)) LP_STAGE_LOAD(stg[j], src, dst);
-        }
-    };
-    auto stage_store = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < WG::NLD; ++j) {
-            const u32x4* src;
-            u32x4* dst;
-            if (stage_addr(c, j, src, dst)) LP_STAGE_STORE(stg[j], dst, lane);
-        }
-        LP_STAGE_DRAIN();
-    };
-    stage_load(-1);
+    stage_issue<WG>(stg, -1, stage_addr);
 
     // ---- the x halo tile as bf16x3 B fragments: wave w owns cell groups w and w + 8 (32 cells each, 484 in all);
     //      channels 16ks + 8*half + 0..7 of halo cell hp, split ONCE per tile.  Cells outside the image are zero
@@ -157,7 +124,7 @@ __global__ __launch_bounds__(512, 2) void mbt_kernel(
     const int prow = 2 * wave + (pl >> 4), pcol = pl & 15;
     const int pcell = ((prow + 3) * MT_RS + pcol + 4) * 2;
 
-    stage_store(-1);
+    stage_land<WG>(stg, -1, lane, stage_addr);
     __syncthreads();                                                 // the first stage has landed
     for (int ch = 0; ch < nchunks; ++ch) {
         // ================= expand MFMAs of this wave's two cell groups (registers only) =====================
@@ -202,7 +169,7 @@ __global__ __launch_bounds__(512, 2) void mbt_kernel(
         __syncthreads();
         // weights of the next two 1x1 slices (this chunk's project, the next chunk's expand), the next chunk's bias
         // and filter rows: requested now, parked in LDS by the barrier that ends the depthwise
-        stage_load(ch);
+        stage_issue<WG>(stg, ch, stage_addr);
         // ================= depthwise 7x7 + bias + relu6, in place: pairs 2w, 2w+1 in ONE pass =================
         {
             const int kp = wave * 2 + dwpair;
@@ -229,7 +196,7 @@ __global__ __launch_bounds__(512, 2) void mbt_kernel(
             *reinterpret_cast<f32x4*>(ep + dwout + MT_RS * 2) = o10;
             *reinterpret_cast<f32x4*>(ep + dwout + MT_RS * 2 + 4) = o11;
         }
-        stage_store(ch);
+        stage_land<WG>(stg, ch, lane, stage_addr);
         __syncthreads();
         // ================= project: acc += W2[:, chunk] . D[chunk][this wave's 32 px] ================
 #pragma unroll
@@ -339,43 +306,12 @@ __global__ __launch_bounds__(512, 2) void mbt_kernel(
     u32x4* W2 = W1 + WG::N1;                                          // [NMT][2][3][64]
     u32x4* WD = W2 + WG::N2 + WG::N3;                                 // [2 chunk parities][16 pairs][28]
 
-    // weight staging: the tile form's, element for element
+    // weight stage (fused_common.h): the standard chunk map
     u32x4 stg[WG::NLD];
-    auto stage_addr = [&](int c, int j, const u32x4*& src, u32x4*& dst) -> bool {
-        const int e0 = 64 * wave + 512 * j;
-        if (e0 >= WG::NTOT) return false;
-        const int ca = max(c, 0), cb = min(c + 1, nchunks - 1), dpar = (c + 1) & 1;
-        dst = W1 + e0;
-        if (e0 < WG::N1) src = w1s + (long)cb * WG::N1 + e0 + lane;
-        else if (e0 < WG::N1 + WG::N2) {
-            const int f0 = e0 - WG::N1, seg = f0 / 192, within = f0 - seg * 192;
-            src = w2s + ((long)(seg >> 1) * KS2 + 2 * ca + (seg & 1)) * 192 + within + lane;
-        } else if (e0 < WG::N1 + WG::N2 + WG::N3) {
-            src = reinterpret_cast<const u32x4*>(b1f) + (long)cb * 8 + min(lane, 7);
-        } else {
-            src = reinterpret_cast<const u32x4*>(wrow) + (long)cb * WG::N4 + (e0 - WG::N1 - WG::N2 - WG::N3) + lane;
-            dst += dpar * WG::N4;
-        }
-        return true;
+    auto stage_addr = [&](int c, int j, const u32x4*& src, u32x4*& dst) {
+        return stage_chunk_addr<WG, false>(wave, lane, j, c, nchunks, KS2, w1s, w2s, b1f, wrow, W1, src, dst);
     };
-    auto stage_load = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < WG::NLD; ++j) {
-            const u32x4* src;
-            u32x4* dst;
-            if (stage_addr(c, j, src, dst)) LP_STAGE_LOAD(stg[j], src, dst);
-        }
-    };
-    auto stage_store = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < WG::NLD; ++j) {
-            const u32x4* src;
-            u32x4* dst;
-            if (stage_addr(c, j, src, dst)) LP_STAGE_STORE(stg[j], dst, lane);
-        }
-        LP_STAGE_DRAIN();
-    };
-    stage_load(-1);
+    stage_issue<WG>(stg, -1, stage_addr);
 
     // the E tile is zeroed once: frame columns, pads and the rows outside the image are never written again
     {
@@ -431,7 +367,7 @@ __global__ __launch_bounds__(512, 2) void mbt_kernel(
     // project geometry: this lane's MFMA column = output pixel (row 2w + g, column pl), g = 0, 1
     const int pcell = ((2 * wave + 3) * MS_RS + pl + 4) * 2;
 
-    stage_store(-1);
+    stage_land<WG>(stg, -1, lane, stage_addr);
     __syncthreads();                                                 // the first stage has landed, the tile is zero
     for (int ch = 0; ch < nchunks; ++ch) {
         // ================= expand: E = relu6(W1[chunk] . x + b1) on this wave's rows inside the image ========
@@ -466,7 +402,7 @@ __global__ __launch_bounds__(512, 2) void mbt_kernel(
             }
         }
         __syncthreads();                                             // B1
-        stage_load(ch);
+        stage_issue<WG>(stg, ch, stage_addr);
         // ================= depthwise 7x7 + bias + relu6, in place: pairs 2w, 2w+1, two passes of 8 output rows ======
         {
             const int kp = wave * 2 + dwpair;
@@ -506,7 +442,7 @@ __global__ __launch_bounds__(512, 2) void mbt_kernel(
                 *reinterpret_cast<f32x4*>(op + MS_RS * 2 + 4) = oy + 1 < H ? o[p][3] : z;
             }
         }
-        stage_store(ch);
+        stage_land<WG>(stg, ch, lane, stage_addr);
         __syncthreads();                                             // B2
         // ================= project: acc += W2[:, chunk] . D[chunk][this wave's two rows] ================
 #pragma unroll
@@ -617,42 +553,12 @@ __global__ __launch_bounds__(512, 2) void mbt_s2_kernel(
     u32x4* W2 = W1 + WG::N1;
     u32x4* WD = W2 + WG::N2 + WG::N3;
 
-    u32x4 stg[WG::NLD];                                               // staging registers (kernels.h: LP_STAGE_*)
-    auto stage_addr = [&](int c, int j, const u32x4*& src, u32x4*& dst) -> bool {
-        const int e0 = 64 * wave + 512 * j;                          // wave-uniform; every segment is 64 elements
-        if (e0 >= WG::NTOT) return false;
-        const int ca = max(c, 0), cb = min(c + 1, nchunks - 1), dpar = (c + 1) & 1;
-                dst = W1 + e0;
-        if (e0 < WG::N1) src = w1s + (long)cb * WG::N1 + e0 + lane;
-        else if (e0 < WG::N1 + WG::N2) {
-            const int f0 = e0 - WG::N1, seg = f0 / 192, within = f0 - seg * 192;
-            src = w2s + ((long)(seg >> 1) * KS2 + 2 * ca + (seg & 1)) * 192 + within + lane;
-        } else if (e0 < WG::N1 + WG::N2 + WG::N3) {
-            src = reinterpret_cast<const u32x4*>(b1f) + (long)cb * 8 + min(lane, 7);
-        } else {
-            src = reinterpret_cast<const u32x4*>(wrow) + (long)cb * WG::N4 + (e0 - WG::N1 - WG::N2 - WG::N3) + lane;
-            dst += dpar * WG::N4;
-        }
-        return true;
+    // weight stage (fused_common.h): the standard chunk map
+    u32x4 stg[WG::NLD];
+    auto stage_addr = [&](int c, int j, const u32x4*& src, u32x4*& dst) {
+        return stage_chunk_addr<WG, false>(wave, lane, j, c, nchunks, KS2, w1s, w2s, b1f, wrow, W1, src, dst);
     };
-    auto stage_load = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < WG::NLD; ++j) {
-            const u32x4* src;
-            u32x4* dst;
-            if (stage_addr(c, j, src, dst)) LP_STAGE_LOAD(stg[j], src, dst);
-        }
-    };
-    auto stage_store = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < WG::NLD; ++j) {
-            const u32x4* src;
-            u32x4* dst;
-            if (stage_addr(c, j, src, dst)) LP_STAGE_STORE(stg[j], dst, lane);
-        }
-        LP_STAGE_DRAIN();
-    };
-    stage_load(-1);
+    stage_issue<WG>(stg, -1, stage_addr);
 
     // ---- the x halo tile as bf16x3 B fragments: wave w owns cell groups w, w + 8, w + 16 (and 24: wave 0) --------
     u32x4 xh[S2_GPW][CK], xm[S2_GPW][CK], xl[S2_GPW][CK];
@@ -697,7 +603,7 @@ __global__ __launch_bounds__(512, 2) void mbt_s2_kernel(
     const int pt = wave & 3, pks = wave >> 2;
     const int ppx = pt * 32 + pl;
 
-    stage_store(-1);
+    stage_land<WG>(stg, -1, lane, stage_addr);
     __syncthreads();                                                 // the first stage has landed
     for (int ch = 0; ch < nchunks; ++ch) {
         // every wave is past the project of the previous chunk (it read D out of these planes)
@@ -745,10 +651,10 @@ __global__ __launch_bounds__(512, 2) void mbt_s2_kernel(
             }
         }
         __syncthreads();
-        // (this kernel sits at the 256-register budget: no room to keep staging registers across the depthwise, so each
-        // transfer is written to LDS as soon as it has arrived)
+        // (this kernel sits at the 256-register budget: no room to keep staging registers across the depthwise, so the
+        // regstage flavour writes each transfer to LDS as soon as it has arrived)
 #ifndef LP_NO_LDS_DMA
-        stage_load(ch);
+        stage_issue<WG>(stg, ch, stage_addr);
 #else
 #pragma unroll
         for (int j = 0; j < WG::NLD; ++j) {

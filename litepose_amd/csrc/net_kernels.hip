@@ -1226,7 +1226,7 @@ __global__ __launch_bounds__(256) void dwpw_kernel(const float* __restrict__ in,
     // the fetched registers are right after the load AND right before their use while the output is still wrong: the add
     // itself lost its operand -- hipcc had built it as v_pk_add_f32 op_sel:[0,1], the gfx950 packed-fp32 form that returns
     // src0 + 0 in lanes 48-63 next to a bf16-MFMA wave on the same SIMD (tools/ubench/pk_vs_mfma.hip).  LDS-DMA, the first
-    // suspect, was a bystander and stays the default weight staging of the fused blocks (kernels.h LP_STAGE_LOAD).  The
+    // suspect, was a bystander and stays the default weight staging of the fused blocks (fused_common.h: stage_issue).  The
     // scalar form stays: it is no slower, keeps 16 registers free, and makes hipcc emit a plain v_pk_add_f32.
     f32x4 bfr[NB][4];
 #pragma unroll

@@ -664,30 +664,57 @@ def test_diagnostic_variants_are_bit_identical_and_log_nothing_on_a_quiet_gpu():
     assert r.returncode == 0 and 'DIAG OK' in r.stdout, r.stdout[-3000:]
 
 
+_REGSTAGE_BODY = r'''
+import hashlib, sys, torch
+sys.path.insert(0, 'tests')
+from oracle import synth
+from litepose_amd import arch_zoo, config
+from litepose_amd.models import pose_mobilenet
+from _net_check import _model, profiled_forward, set_options
+x = synth.make_images(4, 256, seed=43).cuda()
+sha = lambda outs: [hashlib.sha1(t.cpu().numpy().tobytes()).hexdigest() for t in outs]
+arch = arch_zoo.get('search-XS')
+m = pose_mobilenet.get_pose_net(config.get_cfg(), cfg_arch=arch)
+m.load_state_dict(synth.make_state_dict(arch), strict=True)
+print('SUM', sha(m.forward_native(x, 2)))
+# every staged family: the run asserts that the kernels it is there for were launched (any of a group)
+for storage, options, wanted in (
+        ('f32', {'mb16_min': 1, 'mbt_strip': 2}, [('mb16_kernel',), ('mbt_kernel',), ('mbt_s2_kernel',)]),
+        ('bf16', {}, [('mbtb_kernel', 'mbtd_kernel'), ('mbtb_s2_kernel',)]),
+        ('f16', {}, [('mbtb_kernel', 'mbtd_kernel'), ('mbtb_s2_kernel',)])):
+    m = _model('search-XS', storage=storage)[0]
+    set_options(m, options)
+    outs, prof = profiled_forward(m, x, 2)
+    tags = {tag for _, tag in prof}
+    for group in wanted:
+        assert tags & set(group), (storage, group, sorted(tags))
+    print('SUM', storage, sha(outs))
+'''
+
+
 def test_regstage_flavour_is_bit_identical():
     """lib/liblitepose_amd_regstage.so (python -m litepose_amd.build --flavour regstage: the fused block kernels stage their
     weights through registers instead of LDS-DMA and claim whole CUs; the A/B of DESIGN 5b) computes the same bits as the
-    library."""
+    library: search-XS, 4 images at 256 x 256 (planes 64, 32 and 16 wide), one child process per flavour.  The default fp32
+    forward launches neither mb16_kernel (4 images < "mb16_min") nor a 16-bit kernel, so each child also runs fp32 with
+    "mb16_min" = 1 and "mbt_strip" = 2 (mb16_kernel, mbt_kernel as tiles and strips, mbt_s2_kernel), bf16 and fp16 storage
+    (mbtb_kernel / mbtd_kernel, mbtb_s2_kernel), and asserts from the profile that those kernels ran: the register arm of
+    all seven weight stages (fused_common.h) is compared with the LDS-DMA arm."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     from litepose_amd import build as _b
     _b.build(flavour='regstage', verbose=False)      # up to date after __graft_entry__.build(); never a silent skip
-    code = ("import torch, hashlib; from oracle import synth; from litepose_amd import arch_zoo, config; "
-            "from litepose_amd.models import pose_mobilenet; arch = arch_zoo.get('search-XS'); "
-            "m = pose_mobilenet.get_pose_net(config.get_cfg(), cfg_arch=arch); "
-            "m.load_state_dict(synth.make_state_dict(arch), strict=True); "
-            "o = m.forward_native(synth.make_images(4, 256, seed=43).cuda(), 2); "
-            "print('SUM', [hashlib.sha1(t.cpu().numpy().tobytes()).hexdigest() for t in o])")
     outs = []
     for fl in ('', 'regstage'):
         env = dict(os.environ, LP_NATIVE_FLAVOUR=fl)
         if not fl:
             env.pop('LP_NATIVE_FLAVOUR')
-        r = subprocess.run([sys.executable, '-c', code], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                           text=True, timeout=600)
+        r = subprocess.run([sys.executable, '-c', _REGSTAGE_BODY], cwd=root, env=env, stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, text=True, timeout=600)
         assert r.returncode == 0, r.stdout[-2000:]
-        outs.append([l for l in r.stdout.splitlines() if l.startswith('SUM')][-1])
+        outs.append([l for l in r.stdout.splitlines() if l.startswith('SUM')])
+        assert len(outs[-1]) == 4, r.stdout[-2000:]
     assert outs[0] == outs[1]
 
 

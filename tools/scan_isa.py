@@ -12,7 +12,7 @@ the instructions the library must not contain (tests/test_host_cpu.py
     entry per reproducer row).  Anything else -- the known-bad forms, and forms nobody has tested, e.g. a future hipcc
     emitting v_pk_fma_f32 op_sel:[0,0,1] -- is reported under 'pk_unverified' and fails the build / the CPU test;
   * LDS-DMA (global_load_lds_* / buffer_load_* ... lds): reported per kernel; only the fused block kernels stage
-    their weights that way (kernels.h LP_STAGE_LOAD; cleared by the regstage A/B of round 4).
+    their weights that way (fused_common.h LP_STAGE_LOAD; cleared by the regstage A/B of round 4).
 
 The scan never touches the library: llvm-objcopy writes its (unused) output copy into the temporary directory
 (round 4's call had no output operand, so objcopy re-laid the .so out in place: VERDICT r04 weak #9).

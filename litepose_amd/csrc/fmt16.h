@@ -6,9 +6,9 @@
 // its `bool f16` into F once, through with_fmt, so every form exists in both formats with the same template list
 // (tests/test_f16_cpu.py holds that against the build's resource report).
 //   Bf16: v_cvt_pk_bf16_f32 (RNE), unpack = a shift, v_mfma_f32_*_bf16, v_dot2_f32_bf16.
-//   F16:  IEEE half (what the reference's network_to_half runs in, fp16util.py:87-91): v_cvt_pk_f16_f32 (RNE, overflow to
-//         +-inf, subnormals KEPT: hipcc's default kernel mode has float_denorm_mode_16_64 = 3 and nothing here changes it),
-//         unpack = v_cvt_f32_f16, v_mfma_f32_*_f16, v_dot2c_f32_f16.  Never v_cvt_pkrtz_f16_f32: it rounds toward zero.
+//   F16:  IEEE half (the reference's network_to_half, fp16util.py:87-91): v_cvt_pk_f16_f32 (RNE, overflow to +-inf; never
+//         v_cvt_pkrtz_f16_f32: toward zero), unpack = v_cvt_f32_f16, v_mfma_f32_*_f16, v_dot2c_f32_f16.  Subnormals KEPT by all
+//         four, the dot2's operands included (measured: tests/test_gpu_f16_range.py): float_denorm_mode_16_64 = 3, never set.
 // Products of two 16-bit values of either format are exact in fp32 (8 + 8 or 11 + 11 significant bits; an fp16 subnormal
 // product is >= 2^-48, a normal fp32), so the MFMA and FMA chains keep the emulation's arithmetic.
 #pragma once

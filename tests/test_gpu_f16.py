@@ -9,32 +9,22 @@ The protocol of tests/test_gpu_bf16.py at fp16 ulps (2^-10 relative), against te
   (4) batched == per-image, flip=2 == flip=0 + flip=1, bitwise;
   (5) the AE stage on the device's fp16-path maps bit-exact against the reference-semantics parser;
   (6) the kernel census rows of bf16 storage again under fp16: the same forms, the same checks;
-  (7) folded weights in the fp16 SUBNORMAL range survive (no flush anywhere);
-  (8) the engine end to end at BASELINE config 4's shape: records at least as close to the fp32 pipeline as bf16's.
+  (7) folded weights in the fp16 SUBNORMAL range survive one 1x1 and one 7x7 depthwise, one launch per op;
+  (8) the range edges through EVERY 16-bit kernel form, the fused ones included -- subnormal weights, inputs and inner
+      tensors, and stores past 65504 -- with a derived bound: tests/_f16_range.py (the rows and the bound),
+      tests/test_f16_range_cpu.py (coverage and preconditions), tests/test_gpu_f16_range.py (the device);
+  (9) the engine end to end at BASELINE config 4's shape: records at least as close to the fp32 pipeline as bf16's.
 """
 import numpy as np
 import pytest
 import torch
 
 import _f16_ref
+from _f16_range import ACC_REL, F16_ULP_REL, ulp16          # noqa: F401  (the unit of every bound here)
 from _net_check import HEAD_ATOL, _model, _with_option, fused_inner, profiled_forward, set_options
 from oracle import group_ref, inference_ref, net_ref, synth
 
 pytestmark = pytest.mark.gpu
-
-F16_ULP_REL = 2.0 ** -10
-ACC_REL = 2.0 ** -20          # of an element's term magnitude sum: the fp32 accumulation allowance (see ulp16)
-
-
-def ulp16(exp, mag):
-    """The unit of the per-launch bound: one fp16 ulp of the emulated value (2^-10 relative, at least the subnormal
-    spacing 2^-24) plus 2^-20 of the sum of the magnitudes of the terms the element adds (tests/_f16_ref.py, absolute
-    plan).  The second term is the fp32 accumulation error of two summation orders (the device's MFMA / FMA order, the
-    CPU's): invisible at bf16 resolution, at fp16 resolution it shows where the terms cancel -- measured: an output of
-    1.3e-3 from terms of magnitude sum 44.8 (2.9e-6 apart, 3 fp16 ulps of the value) in 1-2 of 800 k elements of a 7x7
-    depthwise.  Everywhere else it is far below the ulp (an output of 1 from terms of magnitude 10: 1e-5 against 1e-3)."""
-    return torch.clamp(exp.abs() * F16_ULP_REL, min=2.0 ** -24) + ACC_REL * mag
-
 
 def layerwise_report(m, arch, sd, x):
     """tests/_net_check.py's layerwise_report at fp16: one launch per op ("mbtb" = "stem" = "headb" = 0), every launch
@@ -347,7 +337,7 @@ def test_f16_subnormal_folded_weights_are_kept():
     assert kern.get(dw) == 'dwt_kernel<7>' and kern.get('stage.1.0.inv') == 'pwb_kernel', kern
 
 
-# ------------------------------------------------------------------ (8) end to end at BASELINE config 4's shape
+# ------------------------------------------------------------------ (9) end to end at BASELINE config 4's shape
 def s448_parity(storage, B=8):
     """bench.py's config-4 workload (search-S 448x448, seeded synthetic scenes, head_gain 0.25) at a reduced batch through
     PoseEngine(storage=...), then bench.parity_check on every image: the records against the reference-semantics parser

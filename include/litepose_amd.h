@@ -930,6 +930,49 @@ int lp_deconv_backward(const float* d_grad_y, const float* d_xa, const float* d_
                        float* grad_xa_out, float* grad_xb_out, float* grad_wa_out, float* grad_wb_out, int N, int Ca,
                        int Cb, int Cout, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The dense K x K convolution of pose_resnet (convbnrelu, FusedMBConv's expand, UpConv, the output convolutions): K in
+ * {3, 5, 7}, stride S in {1, 2}, padding K / 2, over up to two channel-concatenated sources, optionally biased:
+ *   y[n][co][oy][ox] = bias[co] + sum over source s in (a, b), ci, ky, kx of
+ *                      w_s[co][ci][ky][kx] * X_s[n][ci][S oy - K/2 + ky][S ox - K/2 + kx]
+ * d_xa [N,Ca,H,W], d_xb [N,Cb,H,W], d_wa [Cout,Ca,K,K], d_wb [Cout,Cb,K,K], d_bias [Cout] or NULL.  H, W: the source plane.
+ * ups = 0: X_s = x_s.  ups = 1 (UpConv): X_s is the nearest x2 upsample X[y][x] = x[y >> 1][x >> 1], a (2H, 2W) plane.  X_s is
+ * zero outside its plane: the padding applies to the upsampled plane.  y_out [N,Cout,OH,OW], OH = ((H << ups) - 1) / S + 1.
+ * Cb = 0 is the one-source form: d_xb / d_wb are then not read.  Any Ca, Cout >= 1, Cb >= 0.
+ * Refused before any launch, outputs untouched: a dimension < 1, Cb > 0 without d_xb / d_wb, ups with S = 2, a null required
+ * pointer (LP_ERR_INVALID_ARG); K not in {3, 5, 7}, S not in {1, 2}, S = 2 on a plane with an odd side, channels > 65535,
+ * H, W > 16384, a tensor or a weight of more than 2^31 - 256 elements (LP_ERR_UNSUPPORTED); a short or misaligned workspace
+ * (LP_ERR_WORKSPACE).  lp_conv_workspace_bytes covers the forward and any backward of the shape (0: a refused shape).
+ *   forward          a pack launch turns the weights into the exact bf16x3 fragments of convk3_kernel (the network's own
+ *                    dense convolution), then that kernel: per output K^2 (Ca + Cb) terms, channels in groups of 16
+ *                    ascending, taps row-major, fp32 accumulation; the split drops products below 2^-16 of a term
+ *   data gradient    grad_x_s[n][ci][iy][ix] = sum over (co, ky, kx) of w_s[co][ci][ky][kx] * grad_y[n][co][oy][ox] where
+ *                    S oy - K/2 + ky = iy (and ox likewise): the same kernel on grad_y with the flipped, transposed weights,
+ *                    one launch per source.  S = 2: grad_y is first spread over the input plane with zeros between (exact
+ *                    zero products), a gather with no scatter.  ups: each cell is the sum of the 2x2 gradients of the
+ *                    upsampled plane, (a + b) + (c + d)
+ *   weight gradient  grad_w_s[co][ci][ky][kx] = sum over (n, oy, ox) of grad_y[n][co][oy][ox] * X_s[n][ci][..][..]: a GEMM on
+ *                    v_mfma_f32_32x32x2_f32 whose reduction runs over the output pixels, taken in tiles of 8 x 16 pixels
+ *                    (unit = n * tiles + tile, tiles = ceil(OH / 8) * ceil(OW / 16), a tile at the plane's edge counts all
+ *                    its 128 pixels) and cut into slices of LP_CONV_WGRAD_SLICE pixels (8 tiles; the last slice may be
+ *                    shorter); fp32 partials [slices][Cout * Ca * K^2 | Cout * Cb * K^2], added in index order in fp64,
+ *                    rounded once.  A tap that only ever meets padding is exactly zero.  1024: the deepest planes of the
+ *                    network (N = 16, 16 x 16) still give 4 slices per (32 output channels, channel group), and a wave runs
+ *                    8 x 64 MFMAs per 16-register partial
+ *   bias gradient    grad_bias[co] = sum over (n, oy, ox) of grad_y: fp64 partials of a fixed cut, added in index order
+ * lp_conv_backward: a NULL output is not computed; with only weight / bias outputs no data-gradient launch runs, and vice
+ * versa.  grad_xb_out / grad_wb_out must be NULL with Cb = 0.  The data gradients read d_wa / d_wb, the weight gradients
+ * d_xa / d_xb (each may be NULL when not read); passing no output is an error.
+ * Writes: lp_conv_forward every element of y_out; lp_conv_backward every element of each output given.                 */
+#define LP_CONV_WGRAD_SLICE 1024
+size_t lp_conv_workspace_bytes(int N, int Ca, int Cb, int Cout, int H, int W, int K, int S, int ups);
+int lp_conv_forward(const float* d_xa, const float* d_wa, const float* d_xb, const float* d_wb, const float* d_bias,
+                    float* y_out, int N, int Ca, int Cb, int Cout, int H, int W, int K, int S, int ups, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int lp_conv_backward(const float* d_grad_y, const float* d_xa, const float* d_wa, const float* d_xb, const float* d_wb,
+                     float* grad_xa_out, float* grad_xb_out, float* grad_wa_out, float* grad_wb_out, float* grad_bias_out,
+                     int N, int Ca, int Cb, int Cout, int H, int W, int K, int S, int ups, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------ optimizers ---------
  * torch.optim.Adam (no amsgrad, no maximize, L2 weight decay) and torch.optim.SGD (dampening 0) over a LIST of fp32 tensors:
  * one call updates every tensor of a parameter group.  The arrays param_io, d_grad, exp_avg_io, exp_avg_sq_io, momentum_io

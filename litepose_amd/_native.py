@@ -189,6 +189,9 @@ _SIGS = {
     'lp_deconv_forward': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     'lp_deconv_backward_workspace_bytes': (sz, [i32, i32, i32, i32, i32, i32, i32, i32]),
     'lp_deconv_backward': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    'lp_conv_workspace_bytes': (sz, [i32] * 9),
+    'lp_conv_forward': (i32, [vp, vp, vp, vp, vp, vp] + [i32] * 9 + [vp, sz, vp]),
+    'lp_conv_backward': (i32, [vp] * 10 + [i32] * 9 + [vp, sz, vp]),
     'lp_optim_launches': (i32, [i32, C.POINTER(i64)]),
     'lp_optim_adam': (i32, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp, vp,
                             C.c_double, C.c_double, C.c_double, C.c_double, vp]),

@@ -56,6 +56,7 @@ SOURCES = [
     ('vis_kernels.hip', NOPK),                             # integer raster; floats are only loaded, compared, truncated
     ('layer_kernels.hip', NOPK),                           # no hand-placed packed FMAs: fp32 MFMA, scalar FMAs, fp64 sums
     ('conv_grad_kernels.hip', NOPK),                       # likewise: fp32 MFMA from LDS patches
+    ('dense_grad_kernels.hip', NOPK),                      # likewise; its pack kernel splits into bf16 pieces with integer ops
     ('optim_api.cpp', []),
     ('optim_kernels.hip', ['-ffp-contract=off'] + NOPK),   # Adam / SGD: every product and sum of the update rounds on its own
     ('supertrain_api.cpp', []),

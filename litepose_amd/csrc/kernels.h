@@ -454,4 +454,24 @@ void launch_deconv_backward(const float* dy, const float* xa, const float* xb, c
 int stem_wgrad_slices(int N, int H, int W);
 void launch_stem_wgrad(const float* dy, const float* x, float* part, float* dw, int N, int H, int W, hipStream_t s);
 
+// ---- the dense K x K convolution as a training layer (dense_grad_kernels.hip; lp_conv_*, layer_api.cpp) ----
+// plain weights -> launch_convk3's A fragments ws (convk_pack_bytes(M, Kt, K) bytes) and bout: ceil(M / 32) * 32 floats = bias
+// (may be null: zeros).  !transpose: wa [Cout][Ca][K][K] | wb [Cout][Cb][K][K] (wb null with Cb = 0), M = Cout rows, Kt =
+// Ca + Cb.  transpose: the data gradient's weights of ONE source wa [Cout][Ca][K][K]: M = Ca rows, Kt = Cout, taps flipped
+size_t convk_pack_bytes(int M, int Kt, int K);
+void launch_convk_pack(const float* wa, int Ca, const float* wb, int Cb, int Cout, int K, bool transpose, const float* bias,
+                       void* ws, float* bout, hipStream_t s);
+// z [planes][2 OH][2 OW] = dy [planes][OH][OW] at the even cells, zeros elsewhere (the stride-2 data gradient's operand)
+void launch_dilate2(const float* dy, float* z, long planes, int OH, int OW, hipStream_t s);
+// gx [planes][H][W] = the 2x2 cell sums of g [planes][2H][2W], one fixed order (the gradient of a nearest x2 upsample)
+void launch_pool2(const float* g, float* gx, long planes, int H, int W, hipStream_t s);
+// gwa [Cout][Ca][K][K] (and gwb, null with Cb = 0) from dy [N,Cout,OH,OW] and the sources [N,Ca|Cb,H,W] (read through a nearest
+// x2 upsample when ups); part: conv_wgrad_slices(N, OH, OW) * Cout * (Ca + Cb) * K * K floats
+int conv_wgrad_slices(int N, int OH, int OW);
+void launch_conv_wgrad(const float* dy, const float* xa, const float* xb, float* part, float* gwa, float* gwb, int N, int Ca,
+                       int Cb, int Cout, int H, int W, int K, int S, int ups, hipStream_t s);
+// gbias [Cout] = per-channel sum of dy [N,Cout,HW]; part: Cout * conv_bias_slices(N, HW) doubles
+int conv_bias_slices(int N, int HW);
+void launch_conv_bias_grad(const float* dy, double* part, float* gbias, int N, int Cout, int HW, hipStream_t s);
+
 }  // namespace lp

@@ -1,6 +1,8 @@
 // C ABI of the training-mode layers (include/litepose_amd.h, "training-mode layers"): argument validation and workspace
 // carving; the kernels live in layer_kernels.hip, the 1x1 and depthwise forwards are the network's own launch_pw / launch_dw.
 // The stem and the ConvTranspose2d pair: backward in conv_grad_kernels.hip, forwards the raw forms of calib_kernels.hip.
+// The dense K x K convolution (lp_conv_*): packing, weight and bias gradients in dense_grad_kernels.hip; its forward and its
+// data gradient are the network's launch_convk3 (convk_kernels.hip).
 #include <hip/hip_runtime.h>
 
 #include "../../include/litepose_amd.h"
@@ -381,6 +383,144 @@ int lp_deconv_backward(const float* d_grad_y, const float* d_xa, const float* d_
     lp::launch_deconv_backward(d_grad_y, d_xa, d_xb, wp, grad_xa_out, grad_xb_out, ws, grad_wa_out, grad_wb_out, N, Ca, Cb,
                                Cout, h, w, (hipStream_t)s);
     if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "deconv_backward launch failed");
+    return LP_OK;
+}
+
+// ---- the dense K x K convolution (dense_grad_kernels.hip; the forward and the data gradient run convk3_kernel) ----
+namespace {
+size_t a16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// the regions of a conv workspace, in bytes, in the order they are carved
+struct ConvWs {
+    size_t pack_f, bias_f;                          // forward: A fragments, bias (or zeros)
+    size_t pack_x, bias_x, dil, up, part, bpart;    // backward: per-source A fragments, zeros, spread dY, upsampled dX, partials
+    size_t total;
+};
+
+int conv_refusal(int N, int Ca, int Cb, int Cout, int H, int W, int K, int S, int ups, const char** msg) {
+    *msg = "";
+    if (N < 1 || Ca < 1 || Cb < 0 || Cout < 1 || H < 1 || W < 1) {
+        *msg = "N, Ca, Cout, H and W must be positive, Cb non-negative";
+        return LP_ERR_INVALID_ARG;
+    }
+    if (K != 3 && K != 5 && K != 7) {
+        *msg = "K must be 3, 5 or 7";
+        return LP_ERR_UNSUPPORTED;
+    }
+    if (S != 1 && S != 2) {
+        *msg = "S must be 1 or 2";
+        return LP_ERR_UNSUPPORTED;
+    }
+    if (ups != 0 && ups != 1) {
+        *msg = "ups must be 0 or 1";
+        return LP_ERR_INVALID_ARG;
+    }
+    if (ups && S == 2) {
+        *msg = "ups goes with S = 1 only";
+        return LP_ERR_INVALID_ARG;
+    }
+    if (S == 2 && ((H | W) & 1)) {
+        *msg = "S = 2 is defined for even H and W only";
+        return LP_ERR_UNSUPPORTED;
+    }
+    const long long Ct = (long long)Ca + Cb, CH = (long long)H << ups, CW = (long long)W << ups;
+    const long long OH = (CH - 1) / S + 1, OW = (CW - 1) / S + 1;
+    if (Ct > 65535 || Cout > 65535 || H > 16384 || W > 16384 || big((long long)N * Ct * CH * CW) ||
+        big((long long)N * Cout * CH * CW) || big(Cout * Ct * K * K) || big((long long)N * ((OH + 7) / 8) * ((OW + 15) / 16) * 128)) {
+        *msg = "channels <= 65535, H, W <= 16384, N * C * (convolved plane) and Cout * (Ca + Cb) * K * K at most 2^31 - 256";
+        return LP_ERR_UNSUPPORTED;
+    }
+    return LP_OK;
+}
+
+ConvWs conv_ws(int N, int Ca, int Cb, int Cout, int H, int W, int K, int S, int ups) {
+    ConvWs w;
+    const int Ct = Ca + Cb, Mx = Ca > Cb ? Ca : Cb;
+    const int CH = H << ups, CW = W << ups, OH = (CH - 1) / S + 1, OW = (CW - 1) / S + 1;
+    w.pack_f = lp::convk_pack_bytes(Cout, Ct, K);
+    w.bias_f = a16(bias_floats(Cout) * sizeof(float));
+    w.pack_x = lp::convk_pack_bytes(Mx, Cout, K);
+    w.bias_x = a16(bias_floats(Mx) * sizeof(float));
+    w.dil = S == 2 ? a16((size_t)N * Cout * H * W * sizeof(float)) : 0;
+    w.up = ups ? a16((size_t)N * Mx * CH * CW * sizeof(float)) : 0;
+    w.part = a16((size_t)lp::conv_wgrad_slices(N, OH, OW) * Cout * Ct * K * K * sizeof(float));
+    w.bpart = a16((size_t)Cout * lp::conv_bias_slices(N, OH * OW) * sizeof(double));
+    const size_t f = w.pack_f + w.bias_f, b = w.pack_x + w.bias_x + w.dil + w.up + w.part + w.bpart;
+    w.total = f > b ? f : b;
+    return w;
+}
+}  // namespace
+
+size_t lp_conv_workspace_bytes(int N, int Ca, int Cb, int Cout, int H, int W, int K, int S, int ups) {
+    const char* msg;
+    if (conv_refusal(N, Ca, Cb, Cout, H, W, K, S, ups, &msg)) return 0;
+    return conv_ws(N, Ca, Cb, Cout, H, W, K, S, ups).total;
+}
+
+int lp_conv_forward(const float* d_xa, const float* d_wa, const float* d_xb, const float* d_wb, const float* d_bias,
+                    float* y_out, int N, int Ca, int Cb, int Cout, int H, int W, int K, int S, int ups, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    const char* msg;
+    if (int rc = conv_refusal(N, Ca, Cb, Cout, H, W, K, S, ups, &msg)) return fail(rc, msg);
+    if (!d_xa || !d_wa || !y_out) return fail(LP_ERR_INVALID_ARG, "null argument (d_xa, d_wa, y_out)");
+    if (Cb && (!d_xb || !d_wb)) return fail(LP_ERR_INVALID_ARG, "Cb > 0 needs d_xb and d_wb");
+    const ConvWs cw = conv_ws(N, Ca, Cb, Cout, H, W, K, S, ups);
+    if (!workspace || workspace_bytes < cw.total) return fail(LP_ERR_WORKSPACE, "conv workspace too small");
+    if (!al16(workspace)) return fail(LP_ERR_WORKSPACE, "conv workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* bias = (float*)(ws + cw.pack_f);
+    lp::launch_convk_pack(d_wa, Ca, Cb ? d_wb : nullptr, Cb, Cout, K, false, d_bias, ws, bias, s);
+    if (!lp::launch_convk3(d_xa, Ca, Cb ? d_xb : nullptr, Cb, ws, bias, y_out, N, H, W, K, S, ups, Cout, lp::ACT_NONE, N, N, s))
+        return fail(LP_ERR_HIP, "conv_forward: the convk3 launch was refused");
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "conv_forward launch failed");
+    return LP_OK;
+}
+
+int lp_conv_backward(const float* d_grad_y, const float* d_xa, const float* d_wa, const float* d_xb, const float* d_wb,
+                     float* grad_xa_out, float* grad_xb_out, float* grad_wa_out, float* grad_wb_out, float* grad_bias_out,
+                     int N, int Ca, int Cb, int Cout, int H, int W, int K, int S, int ups, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    const char* msg;
+    if (int rc = conv_refusal(N, Ca, Cb, Cout, H, W, K, S, ups, &msg)) return fail(rc, msg);
+    if (!d_grad_y) return fail(LP_ERR_INVALID_ARG, "null argument (d_grad_y)");
+    if (!grad_xa_out && !grad_xb_out && !grad_wa_out && !grad_wb_out && !grad_bias_out)
+        return fail(LP_ERR_INVALID_ARG, "no output requested");
+    if (!Cb && (grad_xb_out || grad_wb_out)) return fail(LP_ERR_INVALID_ARG, "grad_xb_out and grad_wb_out are NULL with Cb = 0");
+    if ((grad_xa_out && !d_wa) || (grad_xb_out && !d_wb)) return fail(LP_ERR_INVALID_ARG, "a data gradient needs its d_wa / d_wb");
+    const bool want_w = grad_wa_out || grad_wb_out;
+    if (want_w && (!d_xa || (Cb && !d_xb))) return fail(LP_ERR_INVALID_ARG, "the weight gradients need d_xa (and d_xb with Cb > 0)");
+    const ConvWs cw = conv_ws(N, Ca, Cb, Cout, H, W, K, S, ups);
+    if (!workspace || workspace_bytes < cw.total) return fail(LP_ERR_WORKSPACE, "conv workspace too small");
+    if (!al16(workspace)) return fail(LP_ERR_WORKSPACE, "conv workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* zb = (float*)(ws + cw.pack_x);
+    float* dil = (float*)(ws + cw.pack_x + cw.bias_x);
+    float* up = (float*)(ws + cw.pack_x + cw.bias_x + cw.dil);
+    float* part = (float*)(ws + cw.pack_x + cw.bias_x + cw.dil + cw.up);
+    double* bpart = (double*)(ws + cw.pack_x + cw.bias_x + cw.dil + cw.up + cw.part);
+    const int CH = H << ups, CW = W << ups, OH = (CH - 1) / S + 1, OW = (CW - 1) / S + 1;
+    if (grad_xa_out || grad_xb_out) {
+        // the stride-1 launch on dY (S = 2: on dY spread over the input plane) with the flipped, transposed weights
+        const float* g = d_grad_y;
+        if (S == 2) {
+            lp::launch_dilate2(d_grad_y, dil, (long)N * Cout, OH, OW, s);
+            g = dil;
+        }
+        for (int src = 0; src < 2; ++src) {
+            float* gx = src ? grad_xb_out : grad_xa_out;
+            if (!gx) continue;
+            const int Cs = src ? Cb : Ca;
+            lp::launch_convk_pack(src ? d_wb : d_wa, Cs, nullptr, 0, Cout, K, true, nullptr, ws, zb, s);
+            if (!lp::launch_convk3(g, Cout, nullptr, 0, ws, zb, ups ? up : gx, N, CH, CW, K, 1, 0, Cs, lp::ACT_NONE, N, N, s))
+                return fail(LP_ERR_HIP, "conv_backward: the convk3 launch was refused");
+            if (ups) lp::launch_pool2(up, gx, (long)N * Cs, H, W, s);
+        }
+    }
+    if (want_w) lp::launch_conv_wgrad(d_grad_y, d_xa, d_xb, part, grad_wa_out, grad_wb_out, N, Ca, Cb, Cout, H, W, K, S, ups, s);
+    if (grad_bias_out) lp::launch_conv_bias_grad(d_grad_y, bpart, grad_bias_out, N, Cout, OH * OW, s);
+    if (hipGetLastError() != hipSuccess) return fail(LP_ERR_HIP, "conv_backward launch failed");
     return LP_OK;
 }
 

@@ -2,7 +2,9 @@
 layers"): ``pointwise``, ``depthwise`` and ``batch_norm_act``, the three a block is made of, and the two dense layers,
 ``stem_conv`` (3x3, stride 2, 3 -> 32; weight gradient only) and ``deconv_pair`` (the ConvTranspose2d(k4, s2, p1) pair of
 the Fusion Deconv Head, or one of them), each a ``torch.autograd.Function`` over one forward and one backward call of the
-C ABI.  float32 CUDA tensors, NCHW; a tensor of another kind is an error, there is no other path.
+C ABI; and ``dense_conv``, the dense K x K convolution of the pose_resnet family (K 3 / 5 / 7, stride 1 / 2, one or two
+sources, optionally through a nearest x2 upsample, optionally biased) with every gradient.  float32 CUDA tensors, NCHW; a
+tensor of another kind is an error, there is no other path.
 
 What an op keeps between forward and backward is what its backward reads: the raw input (and the weight, which lives on
 anyway), and for BatchNorm the fp64 ``(mean, invstd)`` pair of the batch.  The BatchNorm output is not kept: the backward
@@ -260,6 +262,93 @@ def deconv_pair(xa, wa, xb=None, wb=None):
     bias: ``xa`` [N,Ca,h,w], ``wa`` [Ca,Cout,4,4], ``xb`` [N,Cb,h,w], ``wb`` [Cb,Cout,4,4] -> [N,Cout,2h,2w].  Without
     ``xb`` / ``wb`` it is the single transposed convolution."""
     return _DeconvPair.apply(xa, wa, xb, wb)
+
+
+# ---------------------------------------------------------------------------------- dense K x K convolution
+def _conv_dims(xa, wa, xb, wb, bias, stride, upsample):
+    N, Ca, H, W = (int(v) for v in xa.shape)
+    if wa.dim() != 4 or int(wa.shape[1]) != Ca or wa.shape[2] != wa.shape[3]:
+        raise ValueError('wa must be [Cout, %d, K, K]' % Ca)
+    Cout, K = int(wa.shape[0]), int(wa.shape[2])
+    if (xb is None) != (wb is None):
+        raise ValueError('xb and wb are given together')
+    Cb = 0
+    if xb is not None:
+        Cb = int(xb.shape[1])
+        if tuple(xb.shape) != (N, Cb, H, W) or tuple(wb.shape) != (Cout, Cb, K, K) or Cb < 1:
+            raise ValueError('xb must be [%d, Cb, %d, %d] and wb [%d, Cb, %d, %d]' % (N, H, W, Cout, K, K))
+    if bias is not None and tuple(bias.shape) != (Cout,):
+        raise ValueError('bias must be [%d]' % Cout)
+    S, ups = int(stride), int(bool(upsample))
+    OH, OW = ((H << ups) - 1) // max(S, 1) + 1, ((W << ups) - 1) // max(S, 1) + 1
+    return N, Ca, Cb, Cout, H, W, K, S, ups, OH, OW
+
+
+def _conv_ws(L, dims, device):
+    nbytes = L.lp_conv_workspace_bytes(*dims)
+    return _ws(nbytes, device)
+
+
+def conv_forward(xa, wa, xb=None, wb=None, bias=None, stride=1, upsample=False):
+    xa, wa = _f32(xa, 'xa', 4), _f32(wa, 'wa')
+    if xb is not None or wb is not None:
+        xb, wb = _f32(xb, 'xb', 4), _f32(wb, 'wb')
+    if bias is not None:
+        bias = _f32(bias, 'bias', 1)
+    N, Ca, Cb, Cout, H, W, K, S, ups, OH, OW = _conv_dims(xa, wa, xb, wb, bias, stride, upsample)
+    y = torch.empty((N, Cout, OH, OW), dtype=torch.float32, device=xa.device)
+    L = nv.lib()
+    ws = _conv_ws(L, (N, Ca, Cb, Cout, H, W, K, S, ups), xa.device)
+    nv.check(L.lp_conv_forward(nv.dptr(xa), nv.dptr(wa), nv.dptr(xb), nv.dptr(wb), nv.dptr(bias), nv.dptr(y), N, Ca, Cb,
+                               Cout, H, W, K, S, ups, nv.dptr(ws), ws.numel(), nv.stream_ptr()), 'lp_conv_forward')
+    return y
+
+
+def conv_backward(grad_y, xa, wa, xb=None, wb=None, stride=1, upsample=False, need=(True, True, True, True, False)):
+    """``need`` = which of (grad_xa, grad_wa, grad_xb, grad_wb, grad_bias) to compute -> that 5-tuple, None where not
+    asked for (the ``b`` members also without a second source)."""
+    grad_y, xa, wa = _f32(grad_y, 'grad_y', 4), _f32(xa, 'xa', 4), _f32(wa, 'wa')
+    if xb is not None or wb is not None:
+        xb, wb = _f32(xb, 'xb', 4), _f32(wb, 'wb')
+    N, Ca, Cb, Cout, H, W, K, S, ups, OH, OW = _conv_dims(xa, wa, xb, wb, None, stride, upsample)
+    if tuple(grad_y.shape) != (N, Cout, OH, OW):
+        raise ValueError('grad_y does not have the shape of the output')
+    nxa, nwa, nxb, nwb, nb = (bool(v) for v in need)
+    nxb, nwb = nxb and Cb > 0, nwb and Cb > 0
+    if not (nxa or nwa or nxb or nwb or nb):
+        return None, None, None, None, None
+    gxa = torch.empty_like(xa) if nxa else None
+    gwa = torch.empty_like(wa) if nwa else None
+    gxb = torch.empty_like(xb) if nxb else None
+    gwb = torch.empty_like(wb) if nwb else None
+    gb = torch.empty((Cout,), dtype=torch.float32, device=xa.device) if nb else None
+    L = nv.lib()
+    ws = _conv_ws(L, (N, Ca, Cb, Cout, H, W, K, S, ups), xa.device)
+    nv.check(L.lp_conv_backward(nv.dptr(grad_y), nv.dptr(xa), nv.dptr(wa), nv.dptr(xb), nv.dptr(wb), nv.dptr(gxa),
+                                nv.dptr(gxb), nv.dptr(gwa), nv.dptr(gwb), nv.dptr(gb), N, Ca, Cb, Cout, H, W, K, S, ups,
+                                nv.dptr(ws), ws.numel(), nv.stream_ptr()), 'lp_conv_backward')
+    return gxa, gwa, gxb, gwb, gb
+
+
+class _DenseConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xa, wa, xb, wb, bias, stride, upsample):
+        ctx.save_for_backward(xa, wa, xb, wb)
+        ctx.stride, ctx.upsample = stride, upsample
+        return conv_forward(xa, wa, xb, wb, bias, stride, upsample)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        xa, wa, xb, wb = ctx.saved_tensors
+        return conv_backward(grad_y, xa, wa, xb, wb, ctx.stride, ctx.upsample, ctx.needs_input_grad[:5]) + (None, None)
+
+
+def dense_conv(xa, wa, xb=None, wb=None, bias=None, stride=1, upsample=False):
+    """Dense K x K convolution (K 3, 5 or 7), padding K // 2, ``stride`` 1 or 2 (even planes), over one source or two
+    channel-concatenated ones: ``conv2d(U(xa), wa) + conv2d(U(xb), wb) + bias`` with ``U`` the nearest x2 upsample when
+    ``upsample`` (stride 1 only), else the identity.  ``xa`` [N,Ca,H,W], ``wa`` [Cout,Ca,K,K], ``xb`` [N,Cb,H,W], ``wb``
+    [Cout,Cb,K,K], ``bias`` [Cout] -> [N,Cout,OH,OW].  Every input that requires a gradient gets one, and only those."""
+    return _DenseConv.apply(xa, wa, xb, wb, bias, int(stride), bool(upsample))
 
 
 # ---------------------------------------------------------------------------------- BatchNorm + act (+ residual)

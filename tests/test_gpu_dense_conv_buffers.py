@@ -1,0 +1,140 @@
+"""The buffer contract of the dense convolution calls lp_conv_forward / lp_conv_backward (include/litepose_amd.h) with the
+poisoned and guarded buffers of tests/_poison.py, as tests/test_gpu_conv_grad_buffers.py has it for the stem and the
+transposed convolutions: every call writes exactly the elements its header comment names -- whatever the outputs and the
+workspace held before (zeros, NaN, a huge finite value) the results are the same bits -- and nothing in the guards around
+outputs, inputs and a workspace of exactly ``lp_conv_workspace_bytes``; one byte less answers LP_ERR_WORKSPACE; the inputs
+come back unchanged; NULL outputs are skipped, and the operands they alone read may be NULL; every refusal leaves the
+poison where it was."""
+import pytest
+import torch
+
+import _dense_conv_check as K
+import _poison as po
+from litepose_amd import _native as nv
+from test_gpu_layer_buffers import LP_ERR_WORKSPACE, _contract, _g
+
+pytestmark = pytest.mark.gpu
+
+# N, Ca, Cb, Cout, H, W, K, S, ups
+SHAPES = [(3, 16, 8, 8, 1, 1, 7, 1, 0), (2, 33, 7, 9, 5, 7, 5, 1, 1), (2, 5, 0, 3, 6, 10, 3, 2, 0), (2, 24, 32, 28, 6, 10, 7, 2, 0),
+          (19, 3, 0, 32, 8, 16, 3, 1, 0)]
+IDS = ['1x1-k7', 'ragged-ups-k5', 'one-source-s2-k3', 'pair-s2-k7', 'slices-k3']
+WANTS = {'all': (1, 1, 1, 1, 1), 'x': (1, 0, 1, 0, 0), 'w': (0, 1, 0, 1, 0), 'xa': (1, 0, 0, 0, 0), 'wb-bias': (0, 0, 0, 1, 1)}
+
+
+def _tensors(shape):
+    N, Ca, Cb, Cout, H, W, k, S, ups = shape
+    oh, ow = K.out_plane(H, W, S, ups)
+    xa, wa, dy = _g((N, Ca, H, W), 31), _g((Cout, Ca, k, k), 32, 0.3), _g((N, Cout, oh, ow), 33)
+    xb, wb = (_g((N, Cb, H, W), 34), _g((Cout, Cb, k, k), 35, 0.3)) if Cb else (None, None)
+    return xa, wa, xb, wb, _g((Cout,), 36), dy, oh, ow
+
+
+def _inp(A, t, what):
+    return None if t is None else nv.dptr(A.inp(t, what=what))
+
+
+@pytest.mark.parametrize('want', sorted(WANTS))
+@pytest.mark.parametrize('shape', SHAPES, ids=IDS)
+def test_conv_calls(shape, want):
+    L = nv.lib()
+    N, Ca, Cb, Cout, H, W, k, S, ups = shape
+    xa, wa, xb, wb, bias, dy, oh, ow = _tensors(shape)
+    s = nv.stream_ptr()
+    need = L.lp_conv_workspace_bytes(*shape)
+    assert need > 0
+
+    def fwd(with_bias):
+        def run(A):
+            y = A.out((N, Cout, oh, ow), what='y_out')
+            ws = A.ws(need)
+            args = (_inp(A, xa, 'xa'), _inp(A, wa, 'wa'), _inp(A, xb, 'xb'), _inp(A, wb, 'wb'),
+                    _inp(A, bias, 'bias') if with_bias else None, nv.dptr(y), *shape, nv.dptr(ws))
+            assert L.lp_conv_forward(*args, need - 1, s) == LP_ERR_WORKSPACE
+            return L.lp_conv_forward(*args, need, s), dict(y=y)
+        return run
+
+    def bwd(A):
+        nxa, nwa, nxb, nwb, nb = WANTS[want]
+        nxb, nwb = nxb and Cb, nwb and Cb
+        assert nxa or nwa or nxb or nwb or nb
+        outs = dict(gxa=A.out((N, Ca, H, W), what='grad_xa_out') if nxa else None,
+                    gxb=A.out((N, Cb, H, W), what='grad_xb_out') if nxb else None,
+                    gwa=A.out((Cout, Ca, k, k), what='grad_wa_out') if nwa else None,
+                    gwb=A.out((Cout, Cb, k, k), what='grad_wb_out') if nwb else None,
+                    gb=A.out((Cout,), what='grad_bias_out') if nb else None)
+        ws = A.ws(need)
+        # the sources are read only for the weight gradients, a weight only for its source's data gradient
+        ww = nwa or nwb
+        args = (nv.dptr(A.inp(dy, what='grad_y')), _inp(A, xa, 'xa') if ww else None, _inp(A, wa, 'wa') if nxa else None,
+                _inp(A, xb, 'xb') if ww else None, _inp(A, wb, 'wb') if nxb else None, nv.dptr(outs['gxa']),
+                nv.dptr(outs['gxb']), nv.dptr(outs['gwa']), nv.dptr(outs['gwb']), nv.dptr(outs['gb']), *shape, nv.dptr(ws))
+        assert L.lp_conv_backward(*args, need - 1, s) == LP_ERR_WORKSPACE
+        return L.lp_conv_backward(*args, need, s), {k_: v for k_, v in outs.items() if v is not None}
+
+    if want == 'all':
+        _contract(fwd(True))
+        _contract(fwd(False))
+    _contract(bwd)
+
+
+def test_a_requested_subset_is_the_same_bits_as_the_full_call():
+    """each output of a call that asks for one gradient only equals that output of the call that asks for all"""
+    L = nv.lib()
+    shape = (2, 33, 7, 9, 5, 7, 5, 1, 1)
+    N, Ca, Cb, Cout, H, W, k, S, ups = shape
+    xa, wa, xb, wb, bias, dy, oh, ow = _tensors(shape)
+    need = L.lp_conv_workspace_bytes(*shape)
+    ws = torch.empty(need, dtype=torch.uint8, device='cuda')
+    shapes = [(N, Ca, H, W), (N, Cb, H, W), (Cout, Ca, k, k), (Cout, Cb, k, k), (Cout,)]
+
+    def call(mask):
+        outs = [torch.empty(sh, device='cuda') if m else None for sh, m in zip(shapes, mask)]
+        rc = L.lp_conv_backward(nv.dptr(dy), nv.dptr(xa), nv.dptr(wa), nv.dptr(xb), nv.dptr(wb), *[nv.dptr(o) for o in outs],
+                                *shape, nv.dptr(ws), need, nv.stream_ptr())
+        assert rc == 0, L.lp_last_error()
+        return outs
+
+    full = call((1, 1, 1, 1, 1))
+    for i in range(5):
+        one = call(tuple(int(j == i) for j in range(5)))
+        assert po.bitwise_equal(one[i], full[i]), i
+
+
+def test_refusals_leave_the_poison_in_place():
+    L = nv.lib()
+    good = (2, 16, 8, 12, 6, 10)
+    s = nv.stream_ptr()
+    # dims, K, S, ups, drop xb, short workspace -> code
+    cases = [(good, 4, 1, 0, False, False, K.LP_ERR_UNSUPPORTED), (good, 9, 1, 0, False, False, K.LP_ERR_UNSUPPORTED),
+             (good, 3, 3, 0, False, False, K.LP_ERR_UNSUPPORTED), (good, 3, 0, 0, False, False, K.LP_ERR_UNSUPPORTED),
+             (good, 3, 2, 1, False, False, K.LP_ERR_INVALID_ARG), ((2, 16, 8, 12, 5, 10), 3, 2, 0, False, False, K.LP_ERR_UNSUPPORTED),
+             ((2, 16, 8, 12, 6, 7), 5, 2, 0, False, False, K.LP_ERR_UNSUPPORTED), (good, 3, 1, 0, True, False, K.LP_ERR_INVALID_ARG),
+             ((0, 16, 8, 12, 6, 10), 3, 1, 0, False, False, K.LP_ERR_INVALID_ARG),
+             ((2, 16, 8, 0, 6, 10), 3, 1, 0, False, False, K.LP_ERR_INVALID_ARG), (good, 7, 1, 1, False, True, K.LP_ERR_WORKSPACE),
+             (good, 7, 2, 0, False, True, K.LP_ERR_WORKSPACE)]
+    N, Ca, Cb, Cout, H, W = good
+    big = 1 << 22                                                 # more than any shape above needs
+    xa, xb, dy = _g((N, Ca, 2 * H, 2 * W), 41), _g((N, Cb, 2 * H, 2 * W), 42), _g((N, Cout, 2 * H, 2 * W), 43)
+    wa, wb, bias = _g((Cout, Ca, 9, 9), 44), _g((Cout, Cb, 9, 9), 45), _g((Cout,), 46)
+    for dims, k, S, ups, drop, short, code in cases:
+        for pat in ('N', 'H'):
+            A = po.Arena(pat)
+            outs = [A.out(t.shape, what=w) for t, w in ((dy, 'y_out'), (xa, 'grad_xa_out'), (xb, 'grad_xb_out'),
+                                                        (wa, 'grad_wa_out'), (wb, 'grad_wb_out'), (bias, 'grad_bias_out'))]
+            ws = A.ws(big)
+            need = L.lp_conv_workspace_bytes(*dims, k, S, ups)
+            assert (need == 0) == (not short and not drop) and need < big
+            nbytes = need - 1 if short else big
+            xbp = None if drop else nv.dptr(xb)
+            rc = L.lp_conv_forward(nv.dptr(xa), nv.dptr(wa), xbp, nv.dptr(wb), nv.dptr(bias), nv.dptr(outs[0]), *dims, k, S, ups,
+                                   nv.dptr(ws), nbytes, s)
+            assert rc == code, (dims, k, S, ups, rc, L.lp_last_error())
+            rc = L.lp_conv_backward(nv.dptr(dy), nv.dptr(xa), nv.dptr(wa), xbp, nv.dptr(wb), *[nv.dptr(o) for o in outs[1:]],
+                                    *dims, k, S, ups, nv.dptr(ws), nbytes, s)
+            assert rc == code, (dims, k, S, ups, rc, L.lp_last_error())
+            A.check()
+            bits = po.poison_bits(torch.float32, pat)
+            for o in outs:
+                assert bool((po.as_bits(o) == bits).all())
+            assert bool((ws == po.pattern_byte(pat)).all())

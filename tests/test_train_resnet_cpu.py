@@ -1,0 +1,223 @@
+"""``pose_resnet.get_train_net`` and the lp_conv_* calls without a device.
+
+The module's state dict is the reference's (names, shapes, registration order: tests/_resnet_ref.py, pinned to the real
+module by gen_golden_resnet.py); ``backend='torch'`` in eval mode is the restatement's forward bit for bit, and in fp64 in
+train mode it reproduces the golden step of the REAL module (tests/golden/gen_golden_resnet_train.py): outputs and running
+pairs to rtol 1e-12, gradients -- stored rounded to fp32 -- to 2^-24 of their 2-norm more.  The C ABI: the three calls are
+declared, bound with matching parameter counts and exported, and every refusal is answered with its documented code and a
+message that names the argument, before anything is launched (the pointers are made-up addresses, never dereferenced)."""
+import ctypes as C
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import _dense_conv_check as K
+import _resnet_ref as rr
+import _resnet_train_case as RC
+from _conv_grad_check import HEADER
+from litepose_amd import _native as nv
+from litepose_amd.models import pose_mobilenet as pm
+from litepose_amd.models import pose_resnet as pr
+
+CALLS = ['lp_conv_workspace_bytes', 'lp_conv_forward', 'lp_conv_backward']
+P = [C.c_void_p(0x10000 + 0x1000 * i) for i in range(12)]      # 16-byte aligned addresses, never read
+ODD = C.c_void_p(0x20004)
+BIG = 1 << 40
+
+
+@pytest.fixture(scope='module')
+def cfg():
+    return RC.cfg()
+
+
+@pytest.fixture(scope='module')
+def case():
+    return RC.load()
+
+
+# ------------------------------------------------------------------ the module
+@pytest.mark.parametrize('width', [1.0, 0.5, 0.25])
+def test_state_dict_is_the_references(cfg, width):
+    m = pr.get_train_net(cfg, backend='torch', width_mult=width)
+    assert isinstance(m, torch.nn.Module) and isinstance(m, pm.LayerWalk) and isinstance(m, pr.TrainablePoseResNet)
+    want = rr.state_dict_shapes(cfg, rr.width_table(width))
+    got = m.state_dict()
+    assert list(got.keys()) == list(want.keys())
+    for k, shp in want.items():
+        assert tuple(got[k].shape) == shp, k
+    params = [k for k, _ in m.named_parameters()]
+    assert params == [k for k in want if not k.endswith(('running_mean', 'running_var', 'num_batches_tracked'))]
+
+
+def test_backend_is_checked(cfg):
+    with pytest.raises(ValueError):
+        pr.get_train_net(cfg, backend='triton')
+
+
+@pytest.mark.parametrize('width', [1.0, 0.25])
+def test_eval_forward_is_the_restatements(cfg, width):
+    table = rr.width_table(width)
+    sd = rr.make_state_dict(cfg, 77, table=table)
+    m = pr.get_train_net(cfg, backend='torch', width_mult=width).eval()
+    m.load_state_dict(sd)
+    x = torch.randn(2, 3, 64, 96, generator=torch.Generator().manual_seed(5))
+    with torch.no_grad():
+        got, want = m(x), rr.forward(x, sd, cfg, table=table)
+    assert len(got) == 2
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+
+
+def test_fp64_training_step_reproduces_the_golden_step(cfg, case):
+    m = pr.get_train_net(cfg, backend='torch', width_mult=RC.WIDTH)
+    m.load_state_dict(RC.state(cfg))
+    m.double().train()
+    outs = m(torch.from_numpy(case['x']).double())
+    torch.autograd.backward(outs, [torch.from_numpy(case['up%d' % s]).double() for s in range(2)])
+    for s in range(2):
+        np.testing.assert_allclose(outs[s].detach().numpy(), case['out%d_64' % s], rtol=1e-12, atol=0)
+    sd = m.state_dict()
+    for k in case['buffers']:
+        np.testing.assert_allclose(sd[k].numpy(), case['run_64'][k], rtol=1e-12, atol=0, err_msg=k)
+    assert all(int(v) == 1 for k, v in sd.items() if k.endswith('num_batches_tracked'))
+    assert RC.GRAD_STORED_F32 and case['grad_64'][case['params'][0]].dtype == np.float32
+    for k, p in m.named_parameters():
+        g, f = p.grad.numpy(), case['grad_64'][k].astype(np.float64)
+        # the stored gradient is this one rounded to fp32: 2^-24 of its 2-norm, plus the rtol of the fp64 step itself
+        assert np.linalg.norm(g - f) <= (RC.GRAD_ROUNDING + 1e-12) * np.linalg.norm(g), k
+    # the stored e32 is the reference's fp32 error of a real gradient: small, and positive wherever a product is rounded
+    e = np.array([case['e32'][k] for k in case['params']])
+    assert e.shape == (len(case['params']),) and float(e.max()) < 1e-4
+    kinds = {RC.kind_of(k, case['shapes'][k]) for k in case['params']}
+    assert kinds == set(RC.KINDS)
+
+
+def test_init_from_drops_the_head(cfg):
+    sd = rr.make_state_dict(cfg, 9)
+    fresh = pr.get_train_net(cfg, backend='torch')
+    before = {k: v.clone() for k, v in fresh.state_dict().items()}
+    torch.manual_seed(0)
+    a = pr.get_train_net(cfg, backend='torch')
+    torch.manual_seed(0)
+    b = pr.get_train_net(cfg, backend='torch', init_from=sd)
+    head, body = 0, 0
+    for k, v in b.state_dict().items():
+        if 'deconv' in k or 'final' in k:
+            assert torch.equal(v, a.state_dict()[k]), k      # as initialised: the checkpoint's tensor was dropped
+            head += 1
+        else:
+            assert torch.equal(v, sd[k]), k
+            body += 1
+    assert head and body and before.keys() == b.state_dict().keys()
+    # a checkpoint with keys the module does not know still loads (non-strict, as the reference)
+    pr.get_train_net(cfg, backend='torch', init_from=dict(sd, **{'extra.weight': torch.zeros(1)}))
+
+
+def test_to_engine_refuses_other_widths(cfg):
+    with pytest.raises(ValueError):
+        pr.get_train_net(cfg, backend='torch', width_mult=0.5).to_engine()
+
+
+def test_convert_sync_batchnorm_accepts_the_native_module(cfg):
+    m = pr.get_train_net(cfg, backend='native', width_mult=0.25)
+    group = object()
+    assert pm.convert_sync_batchnorm(m, group) is m and m.sync_bn_group is group
+    with pytest.raises(ValueError):
+        pm.convert_sync_batchnorm(pr.get_train_net(cfg, backend='torch', width_mult=0.25), group)
+
+
+# ------------------------------------------------------------------ the C ABI
+def _params(hdr, name):
+    m = re.search(r'\b%s\s*\(([^;{]*?)\)\s*;' % name, hdr, re.S)
+    assert m, name
+    return [' '.join(p.split()) for p in m.group(1).split(',')]
+
+
+def test_header_declares_and_native_binds_the_three_calls():
+    with open(HEADER) as f:
+        hdr = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+    L = nv.lib()
+    for name in CALLS:
+        prm = _params(hdr, name)
+        assert name in nv.EXPORTS and hasattr(L, name), name
+        assert len(prm) == len(nv._SIGS[name][1]), (name, len(prm))
+        for p in prm:                                       # inputs const d_*, writable pointers never d_*
+            if re.search(r'\*\s*d_\w+$', p):
+                assert p.startswith('const float*'), p
+    assert K.macro('LP_CONV_WGRAD_SLICE') % K.CONV_TILE == 0
+    from test_poison_cpu import writable_device_calls
+    assert not set(CALLS) & writable_device_calls()
+
+
+D = (2, 16, 8, 12, 6, 10)                                   # N, Ca, Cb, Cout, H, W
+
+
+def _fwd(dims, k, s, ups, ws=None, nbytes=BIG, xa=P[0], xb=P[2], wb=P[3], y=P[5]):
+    return nv.lib().lp_conv_forward(xa, P[1], xb, wb, P[4], y, *dims, k, s, ups, P[9] if ws is None else ws, nbytes, None)
+
+
+def _bwd(dims, k, s, ups, outs=(P[5], P[6], P[7], P[8], P[10]), ws=None, nbytes=BIG, dy=P[0], xa=P[1], wa=P[2], xb=P[3],
+         wb=P[4]):
+    return nv.lib().lp_conv_backward(dy, xa, wa, xb, wb, *outs, *dims, k, s, ups, P[9] if ws is None else ws, nbytes, None)
+
+
+def _refused(rc, code, word):
+    err = nv.lib().lp_last_error().decode()
+    assert rc == code, (rc, code, err)
+    assert word in err, (word, err)
+
+
+def test_conv_refusals():
+    L = nv.lib()
+    for call in (_fwd, _bwd):
+        for k in (1, 2, 4, 9):
+            _refused(call(D, k, 1, 0), K.LP_ERR_UNSUPPORTED, 'K ')
+            assert L.lp_conv_workspace_bytes(*D, k, 1, 0) == 0
+        for s in (0, 3):
+            _refused(call(D, 3, s, 0), K.LP_ERR_UNSUPPORTED, 'S ')
+        _refused(call(D, 3, 2, 1), K.LP_ERR_INVALID_ARG, 'ups')
+        for h, w in ((5, 10), (6, 7)):
+            _refused(call((2, 16, 8, 12, h, w), 3, 2, 0), K.LP_ERR_UNSUPPORTED, 'even')
+        for bad in ((0, 16, 8, 12, 6, 10), (2, 0, 8, 12, 6, 10), (2, 16, -1, 12, 6, 10), (2, 16, 8, 0, 6, 10),
+                    (2, 16, 8, 12, 0, 10), (2, 16, 8, 12, 6, 0)):
+            _refused(call(bad, 3, 1, 0), K.LP_ERR_INVALID_ARG, 'positive')
+            assert L.lp_conv_workspace_bytes(*bad, 3, 1, 0) == 0
+        _refused(call((2, 40000, 40000, 8, 6, 10), 3, 1, 0), K.LP_ERR_UNSUPPORTED, '65535')
+        _refused(call((64, 16, 8, 12, 16384, 16384), 3, 1, 0), K.LP_ERR_UNSUPPORTED, '2^31')
+    # Cb > 0 without its operands
+    _refused(_fwd(D, 3, 1, 0, xb=None), K.LP_ERR_INVALID_ARG, 'd_xb')
+    _refused(_fwd(D, 3, 1, 0, wb=None), K.LP_ERR_INVALID_ARG, 'd_wb')
+    _refused(_fwd(D, 3, 1, 0, xa=None), K.LP_ERR_INVALID_ARG, 'd_xa')
+    _refused(_fwd(D, 3, 1, 0, y=None), K.LP_ERR_INVALID_ARG, 'y_out')
+    _refused(_bwd(D, 3, 1, 0, xb=None), K.LP_ERR_INVALID_ARG, 'd_xb')
+    _refused(_bwd(D, 3, 1, 0, wb=None), K.LP_ERR_INVALID_ARG, 'd_wb')
+    _refused(_bwd(D, 3, 1, 0, wa=None), K.LP_ERR_INVALID_ARG, 'd_wa')
+    _refused(_bwd(D, 3, 1, 0, xa=None), K.LP_ERR_INVALID_ARG, 'd_xa')
+    _refused(_bwd(D, 3, 1, 0, dy=None), K.LP_ERR_INVALID_ARG, 'd_grad_y')
+    _refused(_bwd(D, 3, 1, 0, outs=(None,) * 5), K.LP_ERR_INVALID_ARG, 'no output')
+    one = (2, 5, 0, 3, 6, 10)
+    _refused(_bwd(one, 3, 1, 0, outs=(P[5], P[6], None, None, None)), K.LP_ERR_INVALID_ARG, 'Cb = 0')
+    _refused(_bwd(one, 3, 1, 0, outs=(None, None, P[7], P[8], None)), K.LP_ERR_INVALID_ARG, 'Cb = 0')
+    # operands that the requested outputs do not read may be NULL: the next refusal is the workspace's
+    _refused(_bwd(D, 3, 1, 0, outs=(P[5], P[6], None, None, None), xa=None, xb=None, nbytes=0), K.LP_ERR_WORKSPACE, 'workspace')
+    _refused(_bwd(D, 3, 1, 0, outs=(None, None, P[7], P[8], P[10]), wa=None, wb=None, nbytes=0), K.LP_ERR_WORKSPACE, 'workspace')
+    # a workspace one byte short, absent, misaligned
+    for k, s, ups in ((3, 1, 0), (7, 2, 0), (5, 1, 1)):
+        need = L.lp_conv_workspace_bytes(*D, k, s, ups)
+        assert need > 0 and need % 16 == 0
+        for call in (_fwd, _bwd):
+            _refused(call(D, k, s, ups, nbytes=need - 1), K.LP_ERR_WORKSPACE, 'workspace')
+            _refused(call(D, k, s, ups, ws=ODD, nbytes=need), K.LP_ERR_WORKSPACE, 'aligned')
+        _refused(L.lp_conv_forward(P[0], P[1], P[2], P[3], P[4], P[5], *D, k, s, ups, None, need, None), K.LP_ERR_WORKSPACE,
+                 'workspace')
+
+
+@pytest.mark.parametrize('form', [(3, 1, 0), (7, 2, 0), (5, 1, 1)])
+def test_workspace_covers_the_partials(form):
+    """the weight-gradient partials alone: slices * Cout * (Ca + Cb) * K^2 floats (the header's slicing rule)"""
+    k, s, ups = form
+    n, ca, cb, cout, h, w = D
+    oh, ow = K.out_plane(h, w, s, ups)
+    assert nv.lib().lp_conv_workspace_bytes(*D, k, s, ups) >= K.conv_slices(n, oh, ow) * cout * (ca + cb) * k * k * 4

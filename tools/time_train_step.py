@@ -19,7 +19,12 @@ so the same file runs on an older tree.
 --sync-bn (the measurement of DESIGN.md 4h) replaces the step rows by two alternating pairs of the eager loop on the
 library's Adam: the plain step, and the data-parallel step forced through a process group of ONE rank (gloo) -- the
 synchronised BatchNorm calls and the gradient bucket without any collective: what the extra launches of every BatchNorm
-cost, not what a collective costs."""
+cost, not what a collective costs.
+
+ARCH = pose_resnet (the measurement of DESIGN.md 4f, "pose_resnet"): the network of resnet.yaml at 256 (deconv kernels 3,
+filters 16 / 24 / 24), one whole eager step on the library's Adam for ``backend='native'`` against ``backend='torch'``
+(torch's convolutions: MIOpen) in the same process, the two rows alternating after warm-up; then ``dense_conv`` forward /
+dX / dW alone (HIP events) against ``torch.nn.functional.conv2d`` plus autograd at the layer shapes of that step."""
 import os
 import sys
 import time
@@ -180,7 +185,105 @@ def optimizer_rows(cfg, arch, reps):
             print('  %-38s not taken: %s' % (label, str(e).splitlines()[0][:160]), flush=True)
 
 
+def resnet_cfg(res=256):
+    cfg = config.get_cfg()
+    cfg.MODEL.NAME = 'pose_resnet'
+    cfg.DATASET.INPUT_SIZE, cfg.DATASET.OUTPUT_SIZE = res, [res // 4, res // 2]
+    cfg.MODEL.EXTRA.NUM_DECONV_KERNELS, cfg.MODEL.EXTRA.NUM_DECONV_FILTERS = [3, 3, 3], [16, 24, 24]
+    return cfg
+
+
+# name, Ca, Cb, Cout, plane of the source, K, S, upsample: the layer shapes of a step at 256
+RESNET_LAYERS = [('stage entry k7 s2 16->64', 16, 0, 64, 128, 7, 2, False), ('k7 s1 32->128', 32, 0, 128, 32, 7, 1, False),
+                 ('k5 48->192', 48, 0, 192, 16, 5, 1, False), ('k3 80->320', 80, 0, 320, 16, 3, 1, False),
+                 ('UpConv pair 80+48->16', 80, 48, 16, 16, 3, 1, True), ('head pair 24+32->28', 24, 32, 28, 64, 3, 1, False)]
+
+
+def resnet_step_rows(cfg, N, reps):
+    from litepose_amd.models import pose_resnet as pr
+    batch = batch_of(cfg, int(cfg.DATASET.INPUT_SIZE), N)
+    fac = MultiLossFactory(cfg)
+    runs = {}
+    for backend in ('native', 'torch'):
+        torch.manual_seed(0)
+        m = pr.get_train_net(cfg, backend=backend).cuda().train()
+        opt = lp_optim.Adam(m.parameters(), lr=1e-4)
+        runs[backend] = (m, opt, [])
+        for _ in range(WARMUP):
+            trainer.do_train(cfg, m, [batch], fac, opt)
+    torch.cuda.synchronize()
+    for _ in range(reps):                                    # the two rows alternate: both see the same machine
+        for backend in ('native', 'torch'):
+            m, opt, t = runs[backend]
+            t0 = time.perf_counter()
+            trainer.do_train(cfg, m, [batch], fac, opt)
+            torch.cuda.synchronize()
+            t.append((time.perf_counter() - t0) * 1e3)
+    for backend in ('native', 'torch'):
+        t = runs[backend][2]
+        print('batch %3d  eager step, backend=%-7s %8.2f ms  (min %.2f, max %.2f)' % (N, backend, np.median(t), min(t), max(t)),
+              flush=True)
+
+
+def resnet_layer_rows(N, reps):
+    from litepose_amd.nn import functional as F_
+    tf = torch.nn.functional
+    g = torch.Generator(device='cuda').manual_seed(5)
+    rnd = lambda *shape: torch.randn(shape, device='cuda', generator=g)  # noqa: E731
+    print('dense_conv alone at N = %d (HIP events, medians of %d, the two sides alternating): library / torch, ms' % (N, reps))
+    for name, ca, cb, cout, hw, k, s, ups in RESNET_LAYERS:
+        xa, wa = rnd(N, ca, hw, hw), rnd(cout, ca, k, k) * 0.1
+        xb, wb = (rnd(N, cb, hw, hw), rnd(cout, cb, k, k) * 0.1) if cb else (None, None)
+        up = (lambda t: tf.interpolate(t, scale_factor=2)) if ups else (lambda t: t)
+
+        def torch_fwd(xa=xa, wa=wa, xb=xb, wb=wb):
+            y = tf.conv2d(up(xa), wa, None, s, k // 2)
+            return y if xb is None else y + tf.conv2d(up(xb), wb, None, s, k // 2)
+
+        dy = torch.randn_like(torch_fwd())
+
+        def torch_grad(data):
+            """autograd's backward alone, towards the sources (data) or towards the weights, through a graph built once"""
+            ins = [None if t is None else t.clone().requires_grad_(data == (i % 2 == 0)) for i, t in enumerate((xa, wa, xb, wb))]
+            y = torch_fwd(*ins)
+            wrt = [t for t in ins if t is not None and t.requires_grad]
+            return lambda: torch.autograd.grad(y, wrt, dy, retain_graph=True)
+
+        need_x = (True, False, cb > 0, False, False)
+        need_w = (False, True, False, cb > 0, False)
+        sides = [('forward', lambda: F_.conv_forward(xa, wa, xb, wb, None, s, ups), lambda: torch_fwd()),
+                 ('dX', lambda: F_.conv_backward(dy, xa, wa, xb, wb, s, ups, need_x), torch_grad(True)),
+                 ('dW', lambda: F_.conv_backward(dy, xa, wa, xb, wb, s, ups, need_w), torch_grad(False))]
+        cells = []
+        for what, mine, theirs in sides:
+            with torch.no_grad() if what == 'forward' else torch.enable_grad():
+                for _ in range(WARMUP):
+                    mine(), theirs()
+                torch.cuda.synchronize()
+                tm, tt = [], []
+                for _ in range(reps):
+                    for fn, acc in ((mine, tm), (theirs, tt)):
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record()
+                        fn()
+                        b.record()
+                        acc.append((a, b))
+                torch.cuda.synchronize()
+            cells.append('%s %7.3f / %7.3f' % (what, np.median([a.elapsed_time(b) for a, b in tm]),
+                                             np.median([a.elapsed_time(b) for a, b in tt])))
+        print('  %-26s %s' % (name, '   '.join(cells)), flush=True)
+
+
 def main(reps, name, batches, optimizer_only, sync_bn=False):
+    if name == 'pose_resnet':
+        cfg = resnet_cfg()
+        print('whole training steps of pose_resnet at %d' % cfg.DATASET.INPUT_SIZE)
+        print('command: python tools/time_train_step.py %d pose_resnet %s   (%d warm-ups, medians of %d steps, host clock '
+              'with a synchronisation behind every step)' % (reps, ' '.join(str(b) for b in batches), WARMUP, reps), flush=True)
+        for N in batches:
+            resnet_step_rows(cfg, N, reps)
+        resnet_layer_rows(batches[0], reps)
+        return
     cfg, arch = config.get_cfg(), arch_zoo.load_arch(name)
     res = int(arch['img_size'])
     print('whole training steps of %s at %d' % (name, res))
@@ -199,4 +302,4 @@ def main(reps, name, batches, optimizer_only, sync_bn=False):
 if __name__ == '__main__':
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
     main(int(args[0]) if args else 30, args[1] if len(args) > 1 else 'search-XS',
-         [int(a) for a in args[2:]] or [16, 64], '--optimizer-only' in sys.argv, '--sync-bn' in sys.argv)
+         [int(a) for a in args[2:]] or ([16] if len(args) > 1 and args[1] == 'pose_resnet' else [16, 64]), '--optimizer-only' in sys.argv, '--sync-bn' in sys.argv)

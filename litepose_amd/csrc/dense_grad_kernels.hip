@@ -10,7 +10,8 @@
 //                     w[co][ci][K-1-ky][K-1-kx] -> rows ci, reduction over co), one launch per source.
 //                     stride 2: dY is first spread over the input plane (dilate2_kernel: Z[2oy][2ox] = dY[oy][ox], zeros
 //                     elsewhere), so that the stride-1 launch is the gather over the taps of each cell's parity; the zero
-//                     products are exact.  ups: the launch writes the gradient of the upsampled plane into the workspace,
+//                     products are exact for finite operands (a non-finite weight tap poisons its whole input channel
+//                     through them and through the staged halo: a known deviation).  ups: the launch writes the gradient of the upsampled plane into the workspace,
 //                     pool2_kernel sums each 2x2 cell as (a + b) + (c + d)
 //   weight gradient   dW_s[co][ci][ky][kx] = sum over (n, oy, ox) of dY[n][co][oy][ox] * X_s[n][ci][S oy - K/2 + ky][S ox - K/2 + kx]
 //                     on v_mfma_f32_32x32x2_f32 (A[row = l & 31][k = l >> 5], B[k = l >> 5][col = l & 31], D register i of
@@ -18,9 +19,12 @@
 //                     CG input channels, reduction over the output pixels in tiles of 8 x 16 (unit = n * tiles + tile).  Per
 //                     tile the haloed input patch of the channel group (zeros outside the plane and beyond Ct, read
 //                     through the upsample when ups) and the 32 x 128 block of dY are staged in LDS; a wave owns NCB column
-//                     blocks of 32 and walks all 128 pixels.  Slices of LP_CONV_WGRAD_SLICE pixels -> fp32 partials
-//                     [slices][ Cout*Ca*K*K | Cout*Cb*K*K ] -> slice_sum_kernel (fp64, index order, one rounding).  A term
-//                     that meets padding is an exact zero product: a tap that only ever meets padding comes out exactly zero
+//                     blocks of 32 and walks all 128 pixels; a pixel of the tile outside the output plane is SELECTED
+//                     away (its partner is a real input cell wherever that cell lies in the plane, and 0 * NaN is a NaN).
+//                     Slices of LP_CONV_WGRAD_SLICE pixels -> fp32 partials [slices][ Cout*Ca*K*K | Cout*Cb*K*K ] ->
+//                     slice_sum_kernel (fp64, index order, one rounding).  A term that meets padding is a product with a
+//                     staged zero -- an exact zero for finite operands, so that a tap that only ever meets padding comes
+//                     out exactly zero; a non-finite dY at such a pixel poisons the tap, as torch's own padding does
 //   bias gradient     per-channel sum of dY: fp64 partials of a fixed cut [Cout][SB], fixed tree per workgroup, added in
 //                     index order, one rounding (the scheme of bn_bwd_stats_kernel)
 #include "../../include/litepose_amd.h"
@@ -201,6 +205,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict
             dys[row * WYS + p] = ok ? v : 0.f;
         }
         __syncthreads();
+        // A pixel of the tile outside the plane contributes nothing, by selection: its staged dY is zero, but its B operand
+        // is a real input cell wherever that cell lies in the plane, and 0 * NaN is a NaN.  The row limit of this lane's
+        // half (zero for a column beyond the group) and the tile-uniform column limit:
+        int ly[NCB];
+#pragma unroll
+        for (int j = 0; j < NCB; ++j) ly[j] = cok[j] ? OH - oy0 - 2 * half : 0;
+        const int lx = OW - ox0;
 #pragma unroll
         for (int e = 0; e < 64; ++e) {
             const int pix = (e & 31) + 64 * (e >> 5);              // + 32 half: in ap / bp
@@ -209,7 +220,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict
 #pragma unroll
             for (int j = 0; j < NCB; ++j) {
                 const float b = bp[j][boff];
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, cok[j] ? b : 0.f, acc[j], 0, 0, 0);
+                const bool in = (pix >> 4) < ly[j] && (pix & 15) < lx;
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, in ? b : 0.f, acc[j], 0, 0, 0);
             }
         }
         __syncthreads();

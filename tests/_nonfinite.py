@@ -21,15 +21,18 @@ wrongly read value by zero has a larger one, since 0 * NaN is NaN.
 Two allowances, both on the side of MORE non-finite outputs and both only for outputs whose sum holds a product of the site
 with a zero that stands for padding: torch's own convolutions multiply their padding, so between the cone (summed tap by tap
 over the cells a tap really meets) and torch's mask a kernel may go either way (``torch_conv``); and four kernels multiply a
-zero-filled halo where torch does not -- a known deviation, named in HALO_KERNELS, counted in LEAKS and held as strict
-expected failures in tests/test_gpu_nonfinite_layers.py (``halo_products``).
+zero-filled halo where torch does not, as does the dense convolution's data gradient, which also multiplies the zeros of a
+dilated grad_y at stride 2 -- known deviations, named in HALO_KERNELS, counted in LEAKS and held as strict expected failures
+in tests/test_gpu_nonfinite_layers.py and tests/test_gpu_nonfinite_conv.py (``halo_products``).
 
 For the linear ops the cone is derived a second way (``indicator_cone``): the same op on the 0/1 indicator of the site with
 all-ones partners, exact integer arithmetic in fp64; tests/test_nonfinite_cpu.py holds the two routes to each other for every
 case, operand, site and value the GPU files use.
 
 Cases are rows of the existing tables (tests/test_gpu_train_forms.py, test_gpu_layer_grad.py, test_gpu_conv_grad.py): for
-each component of a form key (tests/_train_forms.py) the smallest row that has it (``pick``)."""
+each component of a form key (tests/_train_forms.py) the smallest row that has it (``pick``).  The dense K x K convolution
+has a table of its own (``CONV_PLANES`` and its neighbours), and the synchronised BatchNorm rows are named in
+tests/test_gpu_nonfinite_layers.py."""
 import math
 
 import torch
@@ -177,11 +180,56 @@ def ref_deconv(ins):
     return out
 
 
+def _up(t, ups):
+    return TF.interpolate(t, scale_factor=2, mode='nearest') if ups else t
+
+
+def _conv_operands(ins):
+    """the fp64 leaves of a dense convolution; without a bias a zero one stands in, so that its gradient -- the sum of
+    grad_y, which the library hands out with or without a bias -- comes from the same autograd call"""
+    xa, wa, xb, wb = _w(ins['xa']), _w(ins['wa']), _w(ins.get('xb')), _w(ins.get('wb'))
+    b = _w(ins['bias']) if ins.get('bias') is not None else torch.zeros(wa.shape[0], dtype=torch.float64, requires_grad=True)
+    return xa, wa, xb, wb, b
+
+
+def _conv_outputs(y, leaves, ins):
+    xa, wa, xb, wb, b = leaves
+    two = xb is not None
+    g = _grads(y, (xa, wa, xb, wb, b) if two else (xa, wa, b), ins['dy'])
+    out = dict(y=y.detach(), gxa=g[0], gwa=g[1], gb=g[-1])
+    if two:
+        out.update(gxb=g[2], gwb=g[3])
+    return out
+
+
+def ref_conv(ins, k, s, ups):
+    """The dense K x K convolution of tests/_dense_conv_check.py (``reference``: nearest x2 upsample when ups, conv2d of
+    stride s and padding k // 2 over one or two sources, bias), summed tap by tap over the cells a tap really meets, as the
+    other convolutions here are: torch's own conv2d -- ``reference`` itself, which is this op's ``torch_conv`` -- multiplies
+    its padding in the forward and in the weight gradient (tests/test_nonfinite_cpu.py holds the two to each other on finite
+    data and pins the difference).  -> y, gxa, gwa, gb (the sum of grad_y, with or without a bias), gxb, gwb with two sources"""
+    leaves = xa, wa, xb, wb, b = _conv_operands(ins)
+    H, W = xa.shape[2] << ups, xa.shape[3] << ups
+    OH, OW = (H - 1) // s + 1, (W - 1) // s + 1
+    ua, ub = _up(xa, ups), (None if xb is None else _up(xb, ups))
+    y = b.view(1, -1, 1, 1).expand(xa.shape[0], wa.shape[0], OH, OW).clone()
+    for ky, kx, (orow, ocol), (irow, icol) in _taps(k, H, W, OH, OW, s, k // 2):
+        t = torch.einsum('oc,nchw->nohw', wa[:, :, ky, kx], ua[:, :, irow, icol])
+        if ub is not None:
+            t = t + torch.einsum('oc,nchw->nohw', wb[:, :, ky, kx], ub[:, :, irow, icol])
+        y[:, :, orow, ocol] += t
+    return _conv_outputs(y, leaves, ins)
+
+
 def torch_conv(kind, ins, **kw):
     """The same ops by torch's own convolutions plus autograd: what the tap-wise sums restate, WITH the multiplied padding.
     Its non-finite mask is the widest a kernel may have: one that materialises its halo as zeros and multiplies it, as torch
     does, poisons these outputs as torch does; one that selects does not.  Both are accepted (``compare``, ``Wb``)."""
     two = ins.get('xb') is not None
+    if kind == 'conv':
+        from _dense_conv_check import reference
+        leaves = _conv_operands(ins)
+        return _conv_outputs(reference(*leaves, kw['s'], kw['ups']), leaves, ins)
     if kind == 'deconv':
         xa, wa, xb, wb = _w(ins['xa']), _w(ins['wa']), _w(ins.get('xb')), _w(ins.get('wb'))
         y = TF.conv_transpose2d(xa, wa, None, 2, 1)
@@ -238,6 +286,11 @@ HALO_KERNELS = {
     ('deconv', 'wa'): ('y', 'deconv_raw_kernel, csrc/calib_kernels.hip'),
     ('deconv', 'wb'): ('y', 'deconv_raw_kernel, csrc/calib_kernels.hip'),
     ('deconv', 'dy'): ('gwa, gwb', 'deconv_wgrad_kernel, csrc/conv_grad_kernels.hip'),
+    # the dense convolution's data gradient is convk3_kernel's stride-1 launch over grad_y (stride 2: over grad_y spread
+    # over the input plane by dilate2_kernel) with the flipped, transposed weights: a weight tap meets the staged halo at
+    # the border and, at stride 2, the dilation's zeros at the cells of the other parities
+    ('conv', 'wa'): ('gxa', 'convk3_kernel over dilate2_kernel, csrc/convk_kernels.hip, csrc/dense_grad_kernels.hip'),
+    ('conv', 'wb'): ('gxb', 'convk3_kernel over dilate2_kernel, csrc/convk_kernels.hip, csrc/dense_grad_kernels.hip'),
 }
 LEAKS = {}                           # what -> outputs poisoned beyond cone and torch's mask, filled by ``compare``
 
@@ -245,7 +298,8 @@ LEAKS = {}                           # what -> outputs poisoned beyond cone and 
 def halo_products(kind, row, operand, idx, shapes):
     """Outputs whose sum, in a kernel that stages a zero-filled halo of the PARTNER operand and multiplies it, holds a
     product of the site with such a zero -- beyond what torch's own convolutions already show (torch_conv).  0 * NaN is a
-    NaN: a kernel may poison these outputs or not, as it may where torch does.  Three cases, read off the tilings:
+    NaN: a kernel may poison these outputs or not, as it may where torch does.  Four cases, read off the tilings:
+      dense convolution data gradient, site in a weight tap: the whole input channel of the tap (below);
       depthwise and stem weight gradient, site in x: every tap whose stride parity the cell matches, whether or not the
         output cell it pairs with lies in the plane (grad_y's halo);
       transposed pair forward, site in a weight tap: the outputs that tap reaches from the one-cell halo of the input;
@@ -280,10 +334,31 @@ def halo_products(kind, row, operand, idx, shapes):
                     for b in [t for t in range(4) if (idx[3] + 1 - t) % 2 == 0]:
                         m[:, idx[1], a, b] = True
                 out[key] = m
+    if kind == 'conv' and operand in ('wa', 'wb'):
+        # dense convolution data gradient, site in a weight tap [co][ci][ky][kx]: a stride-1 convolution applies every tap
+        # at every cell of its output, to a cell of the plane, of the halo or -- at stride 2 -- to a zero of the dilation;
+        # so the tap is a factor of one product in every cell of input channel ci, in every image, and the 2x2 sums behind
+        # the upsample keep that.  (dilated_data_gradient below is that formulation in torch.)
+        key = 'gxa' if operand == 'wa' else 'gxb'
+        m = torch.zeros(shapes[key], dtype=torch.bool)
+        m[:, idx[1]] = True
+        out[key] = m
     return out
 
 
-LINEAR = {'pw': ref_pw, 'dw': ref_dw, 'stem': ref_stem, 'deconv': ref_deconv}
+def dilated_data_gradient(dy, w, s, ups):
+    """The data gradient of a dense convolution the way lp_conv_backward forms it, in torch on whatever dtype the tensors
+    share: grad_y spread over the input plane (stride 2: at the even cells, zeros elsewhere), a stride-1 conv2d with the
+    flipped, transposed weights and padding K / 2, then the 2x2 sums behind a nearest x2 upsample."""
+    z = dy
+    if s == 2:
+        z = torch.zeros(dy.shape[:2] + (2 * dy.shape[2], 2 * dy.shape[3]), dtype=dy.dtype)
+        z[:, :, ::2, ::2] = dy
+    g = TF.conv2d(z, w.flip(2, 3).transpose(0, 1), None, 1, w.shape[-1] // 2)
+    return 4 * TF.avg_pool2d(g, 2) if ups else g
+
+
+LINEAR = {'pw': ref_pw, 'dw': ref_dw, 'stem': ref_stem, 'deconv': ref_deconv, 'conv': ref_conv}
 
 
 def indicator_cone(ref, ins, operand, idx, **kw):
@@ -369,6 +444,12 @@ def linear_inputs(kind, row):
     elif kind == 'stem':
         n, H, W = row
         ins = dict(x=rand((n, 3, H, W), 31), w=rand((32, 3, 3, 3), 32, 0.3), dy=rand((n, 32, H // 2, W // 2), 33))
+    elif kind == 'conv':
+        ca, cb, co, n, h, w, k, s, ups, bias = row
+        ins = dict(xa=rand((n, ca, h, w), 61), wa=rand((co, ca, k, k), 62, 0.3),
+                   dy=rand((n, co, ((h << ups) - 1) // s + 1, ((w << ups) - 1) // s + 1), 65))
+        ins['xb'], ins['wb'] = (rand((n, cb, h, w), 63), rand((co, cb, k, k), 64, 0.3)) if cb else (None, None)
+        ins['bias'] = rand((co,), 66) if bias else None
     else:
         ca, cb, co, n, h, w = row
         ins = dict(xa=rand((n, ca, h, w), 41), wa=rand((ca, co, 4, 4), 42, 0.3), dy=rand((n, co, 2 * h, 2 * w), 45))
@@ -379,7 +460,16 @@ def linear_inputs(kind, row):
 
 
 def linear_kw(kind, row):
+    if kind == 'conv':
+        return dict(k=row[6], s=row[7], ups=row[8])
     return dict(k=row[0], s=row[1]) if kind == 'dw' else {}
+
+
+def convk3_tile(ow, s):
+    """convk3_kernel's output tile (rows, columns) on a plane ow wide: 32 columns, or 16 on planes at most 16 wide; a wave
+    owns two pixel groups of 32 cells at stride 1 and one at stride 2 (ck_geo, csrc/convk_kernels.hip)"""
+    tw = 16 if ow <= 16 else 32
+    return (4 * (2 if s == 1 else 1) * (32 // tw), tw)
 
 
 def linear_sites(kind, row, operand, shape):
@@ -397,6 +487,21 @@ def linear_sites(kind, row, operand, shape):
         return sites(shape, t, ragged=bool(c % 4))
     if kind == 'stem':
         return sites(shape) if operand == 'w' else sites(shape, [(16, 32)] if operand == 'x' else [(8, 16)])
+    if kind == 'conv':
+        ca, cb, co, n, h, w, k, s, ups, _ = row
+        if operand == 'bias':
+            return sites(shape)
+        if operand in ('wa', 'wb'):      # [Cout][C][K][K]: the corner and edge taps are the ones that meet padding
+            return sites(shape, ragged=bool(shape[1] % 16))
+        ow = ((w << ups) - 1) // s + 1
+        if operand == 'dy':
+            # the weight gradient's 8 x 16 pixels, and the tile of the data gradient's stride-1 launch over the (dilated)
+            # plane, in grad_y's coordinates
+            th, tw = convk3_tile(w << ups, 1)
+            return sites(shape, [(8, 16), (th // s, tw // s)], ragged=bool(co % 32))
+        # the weight gradient's tile and the forward's, in the source's coordinates
+        th, tw = convk3_tile(ow, s)
+        return sites(shape, [(8 * s >> ups, 16 * s >> ups), (th * s >> ups, tw * s >> ups)], ragged=bool(shape[1] % 16))
     ca, cb, co = row[:3]
     if operand in ('wa', 'wb'):
         return sites(shape, ragged=bool(co % 8))
@@ -427,6 +532,9 @@ def _numel(kind, row):
     if kind == 'stem':
         n, H, W = row
         return n * 8 * H * W
+    if kind == 'conv':
+        ca, cb, co, n, h, w, k, s, ups, _ = row
+        return n * max(ca + cb, co) * (h << ups) * (w << ups)
     ca, cb, co, n, h, w = row
     return n * max(ca + cb, 4 * co) * h * w
 
@@ -449,10 +557,42 @@ def pick(kind, rows, forms):
 
 _rows = {}
 
+# The dense K x K convolution: rows (ca, cb, cout, n, h, w, k, s, ups, bias), the smallest shapes that select each thing that
+# can go wrong.  What each component is there for:
+#   forms     every K of {3, 5, 7} (one weight-gradient load form and column cut each) with every (stride, upsample)
+#   channels  (5, 0, 3)   one source
+#             (33, 7, 9)  two sources, ragged against the 16-channel k-step and the 32-row block; Ct = 40 crosses several
+#                         channel groups of the weight gradient (14 / 10 / 10 per workgroup), the source boundary inside one
+#             (3, 0, 40)  two 32-row blocks of Cout, the second ragged
+#   planes    stride 1: (2, 5, 7) one partly filled 8 x 16 tile of the weight gradient -- pixels of the tile outside the plane;
+#             (2, 8, 16) exactly one full tile, the control: the same sites, and no pixel outside the plane exists;
+#             (1, 11, 21) 2 x 2 tiles, the last row and column partly filled, and convk3's 32-wide form
+#             stride 2: (2, 6, 10) -> 3 x 5, (1, 18, 36) -> 9 x 18, the 32-wide form of the data gradient
+#             through the upsample: (2, 3, 5) -> 6 x 10, (1, 6, 11) -> 12 x 22
+# Not the full product: every K meets every (stride, upsample) on every plane of that form, and the channel sets and the bias
+# rotate so that every component meets every component of another kind (tests/test_nonfinite_cpu.py asserts it).
+CONV_KS = (3, 5, 7)
+CONV_FORMS = ((1, 0), (1, 1), (2, 0))
+CONV_CH = ((5, 0, 3), (33, 7, 9), (3, 0, 40))
+CONV_PLANES = {(1, 0): ((2, 5, 7), (2, 8, 16), (1, 11, 21)), (1, 1): ((2, 3, 5), (1, 6, 11)), (2, 0): ((2, 6, 10), (1, 18, 36))}
+
+
+def conv_rows():
+    out = []
+    for ki, k in enumerate(CONV_KS):
+        for fi, form in enumerate(CONV_FORMS):
+            for pi, plane in enumerate(CONV_PLANES[form]):
+                out.append(CONV_CH[(ki + fi + pi) % 3] + plane + (k,) + form + ((ki + pi) % 2 == 0,))
+    return out
+
 
 def rows(kind):
-    """the cases of ``kind`` ('pw', 'dw', 'bn', 'deconv', 'stem'): rows of the existing tables, chosen by ``pick``"""
+    """the cases of ``kind``: 'pw', 'dw', 'bn', 'deconv', 'stem' are rows of the existing tables, chosen by ``pick``; 'conv'
+    is the table above"""
     if kind in _rows:
+        return _rows[kind]
+    if kind == 'conv':
+        _rows[kind] = conv_rows()
         return _rows[kind]
     import _train_forms as FM
     import test_gpu_conv_grad as CG

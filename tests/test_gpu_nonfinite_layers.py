@@ -27,6 +27,10 @@ What the tests found in the parent's kernels (each failed there and passes now; 
   (_nonfinite.torch_conv); torch's batch_norm associates an infinite gamma differently from its own definition
   (_nonfinite.ref_bn follows the definition, as the kernel does).
 
+Synchronised BatchNorm (F.bn_sync_*, the ranks simulated as tests/test_gpu_sync_bn.py does) has rows of its own below, against
+ref_bn over the concatenated batch: its kernels share bn_moments, bn_fwd_slice and bn_pass with the plain ones, and the rows
+passed on the first run.  The dense K x K convolution: tests/test_gpu_nonfinite_conv.py.
+
 Sensitivity, on MI355X: scratch builds with one wrong edit each (not committed), against this file and against the files the
 suite had for the same kernels (tests/test_gpu_layer_grad.py and tests/test_gpu_train_forms.py, -k of the layer kind).
   edit                                                   the files before      this file
@@ -229,6 +233,97 @@ def test_batch_norm_act_through_autograd_keeps_a_nan_for_good():
         bn(x.cpu().double())
         for mine, theirs in ((d['rm'], bn.running_mean), (d['rv'], bn.running_var)):
             assert torch.isnan(mine).cpu().tolist() == torch.isnan(theirs).tolist() == [False, False, True, False]
+
+
+# ------------------------------------------------------------------ synchronised BatchNorm
+# The ranks are simulated in one process exactly as tests/test_gpu_sync_bn.py does it: every shard's row, the rows stacked in
+# rank order, the second half of each pass per shard, every shard its own allocation.  The truth is ref_bn over the
+# concatenated batch in training mode.  Rows of that file's table, named directly (MIN_PLANE is a rule of ``pick``):
+# (per-rank N, C, H, W, act, residual)
+SYNC_CASES = [((3, 1, 2), 5, 3, 5, 'relu6', True),          # uneven ranks, the scalar walk
+              ((2, 2), 16, 16, 16, 'relu6', True),
+              ((2, 3), 8, 33, 33, 'relu6', True),           # several slices per channel
+              ((3, 1, 2), 5, 3, 5, None, False)]
+SYNC_IDS = ['%s-c%d-%dx%d-%s-%s' % ('+'.join(map(str, c[0])), c[1], c[2], c[3], c[4] or 'none', 'res' if c[5] else 'plain')
+            for c in SYNC_CASES]
+
+
+def dev_bn_sync(d, ns, act):
+    """-> the outputs of dev_bn over the concatenated batch -- y and grad_x concatenated in rank order, the kept and the
+    running pair of rank 0 (every rank's are the same bits: asserted here, NaNs included), grad_gamma / grad_beta the fp64
+    sum of the ranks' shares -- and the ranks' shares themselves"""
+    c = d['x'].shape[1]
+    xs, dys = [v.clone() for v in d['x'].split(list(ns))], [v.clone() for v in d['dy'].split(list(ns))]
+    ress = [v.clone() for v in d['res'].split(list(ns))] if d['res'] is not None else [None] * len(ns)
+    running0 = torch.stack([d['rm'], d['rv']]).contiguous()
+    rows = torch.stack([F.bn_sync_stats(v) for v in xs])
+    ys, stats, runs = [], [], []
+    for v, r in zip(xs, ress):
+        running = running0.clone()
+        y, stat = F.bn_sync_forward(v, d['gamma'], d['beta'], running, rows, act, r, NF.MOM, NF.EPS)
+        ys.append(y), stats.append(stat), runs.append(running)
+    brows = torch.stack([F.bn_sync_backward_stats(g, v, d['gamma'], d['beta'], s, act) for g, v, s in zip(dys, xs, stats)])
+    grads = [F.bn_sync_backward(g, v, d['gamma'], d['beta'], s, brows, rank, act)
+             for rank, (g, v, s) in enumerate(zip(dys, xs, stats))]
+    for stat, running in zip(stats[1:], runs[1:]):
+        assert NF.bitwise(stat, stats[0]) and NF.bitwise(running, runs[0]), 'the ranks hold different statistics'
+    out = dict(y=torch.cat(ys), mean=stats[0][:c], invstd=stats[0][c:2 * c], rm=runs[0][0], rv=runs[0][1],
+               gx=torch.cat([g[0] for g in grads]), gg=sum(g[1].double() for g in grads), gb=sum(g[2].double() for g in grads))
+    return out, [(g[1], g[2]) for g in grads]
+
+
+def _sync_todo(ins, ns):
+    n, c, h, w = ins['x'].shape
+    mid = len(ns) // 2                                        # a rank that is neither the first nor, with three, the last
+    xs = [('first', (0, 0, 0, 0)), ('last', (n - 1, c - 1, h - 1, w - 1)), ('rank %d' % mid, (sum(ns[:mid]), c // 2, h // 2, w // 2))]
+    todo = [('x', site, v) for site, v in NF.plan(xs)]
+    for operand in ('gamma', 'beta', 'res', 'dy'):
+        if ins[operand] is not None:
+            todo += [(operand, site, v) for site, v in NF.plan(NF.sites(ins[operand].shape)[:2])]
+    return todo
+
+
+@pytest.mark.parametrize('case', SYNC_CASES, ids=SYNC_IDS)
+def test_sync_batch_norm(case):
+    """A NaN in one rank's x: the channel's y and grad_x are NaN on every rank, mean, invstd and the running pair are NaN
+    with the same bits on every rank, every rank's grad_gamma of the channel is NaN, and every other channel keeps the clean
+    call's bits.  grad_beta follows the truth: the sum of what the gate lets through, and torch's gate passes a NaN z, so
+    every rank's share stays the finite sum of its grad_y (tests/test_nonfinite_cpu.py pins that of torch)."""
+    t0 = time.time()
+    ns, c, h, w, act, with_res = case
+    ins = NF.bn_inputs((sum(ns), c, h, w), with_res)
+    R, (O, _) = NF.ref_bn(ins, act, True), dev_bn_sync(_cuda(ins), ns, act)
+    todo = _sync_todo(ins, ns)
+    for operand, (name, idx), vname in todo:
+        bad = dict(ins)
+        bad[operand] = NF.inject(ins[operand], idx, NF.VALUES[vname])
+        Rb = NF.ref_bn(bad, act, True)
+        Ob, shares = dev_bn_sync(_cuda(bad), ns, act)
+        what = 'sync bn %s %s %s at %s %s %s:' % (SYNC_IDS[SYNC_CASES.index(case)], act, operand, name, idx, vname)
+        NF.compare_all(what, O, Ob, R, Rb, NF.VALUES[vname], vname == 'nan' or operand in ('x', 'res'))
+        if operand == 'x':
+            ch = idx[1]
+            assert bool(torch.isnan(Rb['gg'][ch])) and bool(torch.isfinite(Rb['gb'][ch]))
+            for rank, (gg, gb) in enumerate(shares):
+                assert bool(torch.isnan(gg[ch])) and bool(torch.isfinite(gb[ch])), (what, rank)
+                assert bool(torch.isfinite(gg[:ch]).all()) and bool(torch.isfinite(gg[ch + 1:]).all()), (what, rank)
+    print('sync bn %s: %d injected runs, %.2f s' % (SYNC_IDS[SYNC_CASES.index(case)], len(todo), time.time() - t0))
+
+
+@pytest.mark.parametrize('act, with_res', [('relu6', True), (None, False)], ids=['relu6-res', 'none-plain'])
+def test_sync_batch_norm_of_one_rank_has_the_masks_of_the_plain_calls(act, with_res):
+    row = (6, 5, 3, 5)
+    ins = NF.bn_inputs(row, with_res)
+    for operand, (name, idx), vname in _sync_todo(ins, (6,)):
+        bad = dict(ins)
+        bad[operand] = NF.inject(ins[operand], idx, NF.VALUES[vname])
+        d = _cuda(bad)
+        plain, (sync, _) = dev_bn(d, act, True), dev_bn_sync(d, (6,), act)
+        for k in plain:
+            a, b = plain[k].double(), sync[k].double()
+            assert torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(torch.isinf(a), torch.isinf(b)), (operand, name, vname, k)
+            fin = torch.isfinite(a)
+            assert torch.equal(a[fin], b[fin]), (operand, name, vname, k)
 
 
 # ------------------------------------------------------------------ what the allowance let through

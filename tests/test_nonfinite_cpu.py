@@ -109,8 +109,48 @@ def test_the_two_routes_agree_stem(row):
     _routes('stem', row)
 
 
+@pytest.mark.parametrize('row', NF.rows('conv'), ids=_id)
+def test_the_two_routes_agree_dense_conv(row):
+    _routes('conv', row)
+
+
+def test_the_dense_conv_rows_cover_every_form():
+    """every K meets every (stride, upsample) on every plane of that form; every channel set and both bias settings meet
+    every K, every form and every plane; the leak's row and its control are among them"""
+    rows = NF.rows('conv')
+    assert len(rows) == len(set(rows))
+    comps = lambda r: dict(ch=r[:3], plane=r[3:6], k=r[6], form=r[7:9], bias=r[9])     # noqa: E731
+    for k in NF.CONV_KS:
+        for form in NF.CONV_FORMS:
+            assert {r[3:6] for r in rows if r[6] == k and r[7:9] == form} == set(NF.CONV_PLANES[form])
+    met = {((a, ca[a]), (b, ca[b])) for ca in map(comps, rows) for a in ca for b in ca if a != b}
+    values = dict(ch=NF.CONV_CH, k=NF.CONV_KS, form=NF.CONV_FORMS, bias=(True, False),
+                  plane=[p for f in NF.CONV_FORMS for p in NF.CONV_PLANES[f]])
+    for a in values:
+        for b in values:
+            for va in values[a]:
+                for vb in values[b]:
+                    if a == b or ('plane' in (a, b) and 'form' in (a, b)):
+                        continue                             # a plane belongs to one form
+                    assert ((a, va), (b, vb)) in met, (a, va, b, vb)
+    assert (5, 0, 3, 2, 5, 7, 3, 1, 0, True) in rows
+    assert any(r[3:9] == (2, 8, 16, 3, 1, 0) for r in rows)
+    # what the channel sets are there for (csrc/dense_grad_kernels.hip: WgCut, 32-row blocks; convk3's 16-channel k-step)
+    assert NF.CONV_CH[0][1] == 0 and NF.CONV_CH[1][1] > 0 and NF.CONV_CH[2][2] > 32 and NF.CONV_CH[2][2] % 32
+    ca, cb, _ = NF.CONV_CH[1]
+    for cg in (14, 10):
+        assert (ca + cb + cg - 1) // cg >= 3 and ca % cg and (ca + cb) % 16
+    # the planes: a partly filled tile, one full tile, 2 x 2 tiles with a ragged last row and column and a plane wider than 16
+    s1 = NF.CONV_PLANES[(1, 0)]
+    assert s1[0][1] < 8 and s1[0][2] < 16 and s1[1][1:] == (8, 16) and 8 < s1[2][1] < 16 < s1[2][2] < 32
+    assert all(h % 2 == 0 and w % 2 == 0 for _, h, w in NF.CONV_PLANES[(2, 0)])
+    assert NF.CONV_PLANES[(2, 0)][1][2] // 2 > 16 and 2 * NF.CONV_PLANES[(1, 1)][1][2] > 16
+
+
 @pytest.mark.parametrize('kind,row', [('dw', (7, 2, 8, 1, 6, 10)), ('dw', (3, 1, 6, 2, 7, 7)), ('stem', (2, 10, 14)),
-                                      ('deconv', (33, 7, 9, 2, 5, 7))], ids=['dw7s2', 'dw3s1', 'stem', 'deconv'])
+                                      ('deconv', (33, 7, 9, 2, 5, 7)), ('conv', (33, 7, 9, 2, 5, 7, 5, 1, 0, True)),
+                                      ('conv', (5, 0, 3, 2, 6, 10, 3, 2, 0, False)), ('conv', (33, 7, 9, 2, 3, 5, 7, 1, 1, True))],
+                         ids=['dw7s2', 'dw3s1', 'stem', 'deconv', 'conv5s1', 'conv3s2', 'conv7ups'])
 def test_the_tap_wise_sums_are_torchs_convolutions_without_the_multiplied_padding(kind, row):
     """On finite data the restatement is torch's own convolution up to the order of the sums.  With a NaN in the first
     weight tap torch's conv2d poisons every border output the tap meets only as padding: wider than the cone."""
@@ -119,12 +159,86 @@ def test_the_tap_wise_sums_are_torchs_convolutions_without_the_multiplied_paddin
     for k in mine:
         assert torch.allclose(mine[k], theirs[k], rtol=1e-12, atol=1e-13), k
     # the weight gradient of a transposed convolution pads grad_y; a convolution's forward pads x
-    operand, out = ('xa', 'gwa') if kind == 'deconv' else ('w', 'y')
+    operand, out = ('xa', 'gwa') if kind == 'deconv' else ('wa', 'y') if kind == 'conv' else ('w', 'y')
     bad = dict(ins)
     bad[operand] = NF.inject(ins[operand], (0, 0, 0, 0), NF.NAN)
     a, b = torch.isnan(NF.LINEAR[kind](bad, **kw)[out]), torch.isnan(NF.torch_conv(kind, bad, **kw)[out])
     assert bool((b | ~a).all()) and int(b.sum()) > int(a.sum())
     assert torch.equal(a, NF.indicator_cone(NF.LINEAR[kind], ins, operand, (0, 0, 0, 0), **kw)[out])
+
+
+@pytest.mark.parametrize('row', NF.rows('conv'), ids=_id)
+def test_the_mask_of_the_dense_data_gradient_is_the_dilated_formulations(row):
+    """halo_products' mask for a site in a weight tap -- the tap's whole input channel -- is what torch marks when it forms
+    the data gradient the way the library does (_nonfinite.dilated_data_gradient); on finite data that formulation is the
+    data gradient.  It holds the cone, and at stride 2, where a tap meets the cells of one parity only, it is far wider."""
+    ins, kw = NF.linear_inputs('conv', row), NF.linear_kw('conv', row)
+    clean = NF.ref_conv(ins, **kw)
+    for operand, key in (('wa', 'gxa'), ('wb', 'gxb')):
+        if ins[operand] is None:
+            continue
+        g = NF.dilated_data_gradient(ins['dy'].double(), ins[operand].double(), kw['s'], kw['ups'])
+        assert torch.allclose(g, clean[key], rtol=1e-12, atol=1e-13)
+        shapes = {k: v.shape for k, v in clean.items()}
+        for (name, idx), vname in NF.plan(NF.linear_sites('conv', row, operand, ins[operand].shape)):
+            bad = NF.inject(ins[operand], idx, NF.VALUES[vname])
+            theirs = NF.cone(NF.dilated_data_gradient(ins['dy'].double(), bad.double(), kw['s'], kw['ups']), NF.VALUES[vname])
+            mine = NF.halo_products('conv', row, operand, idx, shapes)
+            assert set(mine) == {key} and torch.equal(mine[key], theirs), (operand, name, vname)
+            truth = NF.indicator_cone(NF.ref_conv, ins, operand, idx, **kw)[key]
+            assert bool((theirs | ~truth).all())
+            if kw['s'] == 2 and name == 'first':
+                assert 4 * int(truth.sum()) <= int(theirs.sum())
+
+
+# ------------------------------------------------------------------ the partly filled tile of the dense weight gradient
+def _tiled_weight_gradient(x, dy, k, s, select):
+    """A weight gradient that walks ALL 128 pixels of every 8 x 16 tile of the output plane: a pixel outside the plane has a
+    zero grad_y, and its partner is the input cell it would read wherever that cell lies in the plane (zero outside it).
+    select: the partner of such a pixel is selected away instead."""
+    N, C, H, W = x.shape
+    OH, OW = dy.shape[2:]
+    TH, TW = -(-OH // 8) * 8, -(-OW // 16) * 16
+    p = k // 2
+    xp = torch.zeros((N, C, (TH - 1) * s + k, (TW - 1) * s + k), dtype=torch.float64)
+    xp[:, :, p:p + H, p:p + W] = x[:, :, :xp.shape[2] - p, :xp.shape[3] - p]
+    dyp = torch.zeros((N, dy.shape[1], TH, TW), dtype=torch.float64)
+    dyp[:, :, :OH, :OW] = dy
+    inside = torch.zeros((TH, TW), dtype=torch.bool)
+    inside[:OH, :OW] = True
+    gw = torch.zeros((dy.shape[1], C, k, k), dtype=torch.float64)
+    for ky in range(k):
+        for kx in range(k):
+            b = xp[:, :, ky:ky + (TH - 1) * s + 1:s, kx:kx + (TW - 1) * s + 1:s]
+            if select:
+                b = torch.where(inside, b, torch.zeros((), dtype=torch.float64))
+            gw[:, :, ky, kx] = torch.einsum('nohw,nchw->oc', dyp, b)
+    return gw.float()
+
+
+@pytest.mark.parametrize('k,s,plane,leaks', [(3, 1, (2, 5, 7), True), (5, 1, (2, 5, 7), True), (3, 2, (2, 6, 10), True),
+                                             (3, 1, (2, 8, 16), False)], ids=['k3', 'k5', 'k3s2', 'full-tile'])
+def test_the_rows_see_a_partly_filled_tile_removed_by_a_multiplication(k, s, plane, leaks):
+    """conv_wgrad_kernel before it selected: fed to ``compare`` in place of a device result, the scheme fails at the 'edge'
+    site of xa on every plane that does not fill its 8 x 16 tiles, beyond torch's own mask, and passes on the full tile;
+    with the select it passes everywhere.  On finite data the two are the same bits."""
+    row = (5, 0, 3) + plane + (k, s, 0, True)
+    ins, kw = NF.linear_inputs('conv', row), NF.linear_kw('conv', row)
+    name, idx = [s_ for s_ in NF.linear_sites('conv', row, 'xa', ins['xa'].shape) if s_[0] == 'edge'][0]
+    bad = dict(ins)
+    bad['xa'] = NF.inject(ins['xa'], idx, NF.NAN)
+    R, Rb, Wb = NF.ref_conv(ins, **kw)['gwa'], NF.ref_conv(bad, **kw)['gwa'], NF.torch_conv('conv', bad, **kw)['gwa']
+    assert torch.equal(torch.isnan(Rb), torch.isnan(Wb))          # torch pads x, not grad_y: no allowance here
+    run = lambda t, select: _tiled_weight_gradient(t['xa'], t['dy'], k, s, select)     # noqa: E731
+    assert NF.bitwise(run(ins, False), run(ins, True))
+    assert torch.allclose(run(ins, True).double(), R, rtol=1e-6, atol=1e-6)
+    NF.compare('selected gwa', run(ins, True), run(bad, True), R, Rb, NF.NAN, True, Wb)
+    if leaks:
+        with pytest.raises(AssertionError, match='outside it poisoned'):
+            NF.compare('multiplied gwa', run(ins, False), run(bad, False), R, Rb, NF.NAN, True, Wb)
+        assert int(torch.isnan(run(bad, False)).sum()) > int(torch.isnan(Rb).sum())
+    else:
+        NF.compare('multiplied gwa', run(ins, False), run(bad, False), R, Rb, NF.NAN, True, Wb)
 
 
 def test_every_kernel_size_and_stride_is_among_the_rows_held_here():

@@ -6,6 +6,7 @@ emulation (the fused-output yardstick).
 
 A plain module, not a conftest: the tests import it by name (tests/ is on sys.path under pytest)."""
 import re
+import time
 
 import torch
 
@@ -136,8 +137,18 @@ def check_fp32(m, arch, sd, x, flip, outs, chunk=8, tap_images=None, head=None, 
     the batch, the mirrored half (flip=2) against the oracle on torch.flip(x, [3]).  The oracle runs ``chunk`` images at a
     time so that the host memory of its taps stays bounded; taps are compared on the first ``tap_images`` images of each
     half (None: all).  ``head``: the oracle's HeadCfg when it is not the default; ``forward``: the oracle of another head
-    form with net_ref.forward's signature (tests/_simplenet_ref.py).  Returns (worst scaled tap error, its name, worst
-    output error)."""
+    form with net_ref.forward's signature (tests/_simplenet_ref.py).
+
+    Then the unit check of tests/_fp32_units.py on at most three images of the device batch -- the first, the first of
+    the mirrored half (flip=2) and the last: every unit in float64 on the DEVICE's own input taps, P (per element,
+    ``e <= c_max u B``) and R (``rms(e / B) <= m rms(|ref32 - ref| / B)``) asserted per unit and image.  With another
+    ``forward`` than net_ref.forward (pose_simplenet) the stem and the blocks are checked and the deconv and output-head
+    units are skipped.
+
+    Returns (worst scaled tap error, its name, worst output error, worst P as a fraction of c_max, worst R as a fraction
+    of m)."""
+    import _fp32_units as fu
+    t_all = time.time()
     d = spec.derive(arch, head)
     N = x.shape[0]
     halves = [(0, x)] if flip == 0 else ([(0, torch.flip(x, [3]))] if flip == 1 else [(0, x), (N, torch.flip(x, [3]))])
@@ -166,7 +177,14 @@ def check_fp32(m, arch, sd, x, flip, outs, chunk=8, tap_images=None, head=None, 
                 if rel > worst_tap:
                     worst_tap, worst_name = rel, nm
                 assert rel < TAP_REL, (nm, base + c0, rel)
-    return worst_tap, worst_name, worst_out
+    xin = x if flip == 0 else (torch.flip(x, [3]) if flip == 1 else torch.cat([x, torch.flip(x, [3])]))
+    images = sorted({0, xin.shape[0] - 1} | ({N} if flip == 2 else set()))
+    t0 = time.time()
+    rows = fu.check_device(m, sd, arch, xin, outs, images, head, heads=forward is net_ref.forward)
+    worst_p, worst_r = max(v[0] for v in rows.values()), max(v[1] for v in rows.values())
+    print('check_fp32 units: %d units x %d images of %d x %d in %.1f s (of %.1f s): P %.3f of c_max, R %.3f of m'
+          % (len(rows), len(images), x.shape[2], x.shape[3], time.time() - t0, time.time() - t_all, worst_p, worst_r))
+    return worst_tap, worst_name, worst_out, worst_p, worst_r
 
 
 # ------------------------------------------------------------------ bf16 against the emulation

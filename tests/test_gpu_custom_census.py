@@ -210,8 +210,8 @@ def test_row_fp32_vs_oracle(rid):
     m, arch, sd, head, plain, x, outs, launches = res
     tags = _check_launches(row, 'f32', arch, head, launches, row[7])
     big = N > 16                                        # the gate rows: taps on the first chunk of each half
-    worst_tap, name, worst_out = check_fp32(m, arch, sd, x, flip, outs, chunk=8, tap_images=8 if big else None, head=head,
-                                            forward=snr.forward if plain else net_ref.forward)
+    worst_tap, name, worst_out, unit_p, unit_r = check_fp32(m, arch, sd, x, flip, outs, chunk=8, tap_images=8 if big else None,
+                                                            head=head, forward=snr.forward if plain else net_ref.forward)
     g = _golden()
     gid = cs.golden_id(row)
     for k in range(2):
@@ -220,8 +220,9 @@ def test_row_fp32_vs_oracle(rid):
         assert tuple(got.shape) == tuple(g[key + '_shape'][1:]), (rid, k, got.shape)
         err = float(np.abs(got.reshape(-1)[::13] - g[key + '_sample']).max())
         assert err <= NET_ATOL, ('image 0 against the reference module', rid, k, err)
-    print('%s f32 %dx%d N=%d flip=%d: taps %.3f of the bound (%s), outputs %.3f; %.1f s; tags %s'
-          % (rid, H, W, N, flip, worst_tap / TAP_REL, name, worst_out / NET_ATOL, time.time() - t0, ' '.join(sorted(tags))))
+    print('%s f32 %dx%d N=%d flip=%d: taps %.3f of the bound (%s), outputs %.3f; units P %.3f of c_max, R %.3f of m; %.1f s; '
+          'tags %s' % (rid, H, W, N, flip, worst_tap / TAP_REL, name, worst_out / NET_ATOL, unit_p, unit_r, time.time() - t0,
+                       ' '.join(sorted(tags))))
 
 
 @pytest.mark.parametrize('rid,storage', CASES16, ids=['%s-%s' % c for c in CASES16])

@@ -49,8 +49,9 @@ def test_deconv_taps_and_outputs_vs_oracle(arch_name, H, W, N):
     _expect_x3(arch, H, W, launches)
     outs = [o.clone() for o in m.forward_native(x.cuda(), 2)]
     torch.cuda.synchronize()
-    worst_tap, worst_name, worst_out = check_fp32(m, arch, sd, x, 2, outs, chunk=2)
-    print('%s %dx%d b%d: worst tap %.3g (%s), worst output %.3g' % (arch_name, H, W, N, worst_tap, worst_name, worst_out))
+    worst_tap, worst_name, worst_out, unit_p, unit_r = check_fp32(m, arch, sd, x, 2, outs, chunk=2)
+    print('%s %dx%d b%d: worst tap %.3g (%s), worst output %.3g; units: P %.3f of c_max, R %.3f of m'
+          % (arch_name, H, W, N, worst_tap, worst_name, worst_out, unit_p, unit_r))
     assert worst_tap < TAP_REL and worst_out <= NET_ATOL
 
 

@@ -7,7 +7,11 @@ launch; every tag in the sources is either expected by some row or listed in ``N
 
 Per row, one profiled forward (the whole batch in one launch per op) and then the comparison of EVERY image of the
 batch (flip=2: the mirrored half against the oracle on torch.flip(x, [3])):
-  * fp32: the block taps scaled by their magnitude (< 2e-5) and both outputs at 2e-5 against net_ref.forward;
+  * fp32: the block taps scaled by their magnitude (< 2e-5) and both outputs at 2e-5 against net_ref.forward; then, on
+    three images, every unit of the net in float64 on the device's own input taps, per element (P) and per tap (R):
+    tests/_fp32_units.py.  Measured over the fp32 rows: P at most 0.732 of c_max (prune_s_native_f32), R at most 0.142
+    of m; the unit check costs a row 0.1 to 1.5 s (the three slowest: m512_b2_f32_flip 0.2 -> 1.7 s, s448_b4_f32_flip
+    0.1 -> 1.2 s of comparison time, xs256_b64_f32_flip 0.6 -> 1.3 s);
   * bf16: every launch against net_ref.bf16_plan fed the device's own inputs (<= 1 bf16 ulp, < 2 % of the elements
     differing, heads within 2e-5); the output of a fused launch against the emulation chained through the tensors it
     never stores (tests/_net_check.py: check_bf16).
@@ -135,6 +139,7 @@ def _case_by_id():
 
 _MODELS = {}
 RESULTS = {}              # case id -> (tags, worst criterion): the table of test_census_covers_production_launches
+UNITS = {}                # fp32 case id -> (worst P as a fraction of c_max, worst R as a fraction of m): tests/_fp32_units.py
 
 
 def _net(arch_name, storage):
@@ -159,6 +164,7 @@ def _run_case(case, compare):
             # bench-size batches: the taps of the first chunk of each half, every image's outputs
             worst = check_fp32(m, arch, sd, x, flip, outs, chunk=8, tap_images=8 if N > 16 else None)
             crit = worst[0] / 2e-5
+            UNITS[cid] = worst[3:5]
         else:
             rows = check_bf16(m, arch, sd, x, flip, outs, [n for n, _ in launches], chunk=8)
             crit = max(r[2] for r in rows.values())
@@ -174,7 +180,8 @@ def test_kernel_form_vs_reference(cid):
     launches, crit = _run_case(case, compare=True)
     tags = {t for _, t in launches}
     RESULTS[cid] = (tags, crit)
-    print('%s: %d launches, worst criterion %.3f of its bound; tags %s' % (cid, len(launches), crit, sorted(tags)))
+    units = '; units P %.3f of c_max, R %.3f of m' % UNITS[cid] if cid in UNITS else ''
+    print('%s: %d launches, worst criterion %.3f of its bound%s; tags %s' % (cid, len(launches), crit, units, sorted(tags)))
     missing = set(case[8]) - tags
     assert not missing, ('expected forms not launched', sorted(missing), sorted(tags))
 

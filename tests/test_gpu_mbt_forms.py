@@ -8,8 +8,10 @@ Per row (rows that share a net, an input and options share the forwards):
     x ceil(h / 16) for a tile (N' = 2 N under flip = 2; profile(launches=True)): the two forms differ in nothing else, and
     a strip kernel refused for scratch memory would show as the tile grid;
   * oracle: check_fp32 -- every block tap at TAP_REL, both outputs at NET_ATOL, every image and the mirrored half;
-  * the block alone in fp64 (BatchNorm folded in fp64) on the DEVICE's input tap against the device's output tap, bound
-    TAP_REL x max(1, max |ref|): the drift of the layers in front is out of the comparison;
+  * the block alone in fp64 (tests/_fp32_units.py: BatchNorm folded in fp64 and rounded once to fp32, as the device plan
+    does) on the DEVICE's input tap against the device's output tap, bound TAP_REL x max(1, max |ref|): the drift of the
+    layers in front is out of the comparison; and per image P (every element within c_max u B) and R (the tap's
+    rms(e / B) within m times that of the block in plain fp32 torch), printed as fractions of c_max and m;
   * bitwise: the other form (option "mbt_strip" 2 <-> 0) on the row's images gives the same bits in every tap and both
     outputs.  Order: the other form on the row's images, the other form on FOREIGN images (another seed), then the
     row's form on the row's images -- so the planes hold foreign data when the form under test starts, and a strip, tile
@@ -105,7 +107,9 @@ NET_ATOL; "other form": the grid of the bitwise partner, "same" where the other 
   k3_tile_ck2    272x512   2 2  tile <2,1,T>    32-> 96->32  17x32    16  0.011  0.045  0.022  grid 8
   k8_tile_ck2    272x512   2 2  tile <2,1,T>    32->256->32  17x32    16  0.014  0.045  0.022  grid 8
 Worst of all rows: blk 0.027 (t17_48_56), taps 0.060, outputs 0.036 of their bounds: a block error of 1e-6 of the tap's
-magnitude would show.  No row is refused (REFUSED is empty: an 8-filter last stage, one-row planes and odd plane heights
+magnitude would show.  The per-element columns added since (not in the table above): P at most 0.439 of c_max, R at most
+0.106 of m over the 85 rows (tests/_fp32_units.py: c_max 0.75, m 13), and check_fp32's unit check of the whole net on
+three images of every group.  No row is refused (REFUSED is empty: an 8-filter last stage, one-row planes and odd plane heights
 all run).  Wall time: this file 6.7 s (85 tests in one process; the slowest 1.1 s, g51 with 17 images; the default rule
 with 256 + 255 images 0.5 s).
 
@@ -142,10 +146,10 @@ import time
 
 import pytest
 import torch
-import torch.nn.functional as F
 
+import _fp32_units as fu
 import _mbt_space as ms
-from oracle import net_ref, spec, synth
+from oracle import spec, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -221,25 +225,6 @@ def _group(r):
     return g
 
 
-def _fold64(sd, p, conv, bn):
-    w = sd['%s.%s.weight' % (p, conv)].double()
-    s = sd['%s.%s.weight' % (p, bn)].double() / torch.sqrt(sd['%s.%s.running_var' % (p, bn)].double() + net_ref.BN_EPS)
-    b = sd['%s.%s.bias' % (p, bn)].double() - sd['%s.%s.running_mean' % (p, bn)].double() * s
-    return w * s.view(-1, 1, 1, 1), b
-
-
-def _block64(x, sd, p, blk):
-    """The InvBottleneck ``p`` in fp64 with BatchNorm folded in fp64."""
-    x = x.double()
-    w, b = _fold64(sd, p, 'inv.0', 'inv.1')
-    y = torch.clamp(F.conv2d(x, w, b), 0.0, 6.0)
-    w, b = _fold64(sd, p, 'depth_conv.0', 'depth_conv.1')
-    y = torch.clamp(F.conv2d(y, w, b, blk['stride'], blk['k'] // 2, 1, blk['feat']), 0.0, 6.0)
-    w, b = _fold64(sd, p, 'point_conv.0', 'point_conv.1')
-    y = F.conv2d(y, w, b)
-    return y + x if blk['residual'] else y
-
-
 @pytest.mark.parametrize('rid', [r[0] for r in ms.ROWS])
 def test_row(rid):
     from _net_check import NET_ATOL, TAP_REL
@@ -266,10 +251,12 @@ def test_row(rid):
     src = 'stage.%d.%d' % ((s, b - 1) if b else (s - 1, len(d['stages'][s - 1]) - 1))
     xin = g['taps'][src].view(nb, cin, h, w).cpu()
     got = g['taps']['stage.%d.%d' % (s, b)].view(nb, cout, h, w).cpu()
-    ref = _block64(xin, g['sd'], 'stage.%d.%d' % (s, b), blk)
+    ref, B, ref32 = fu.block_fn(g['sd'], 'stage.%d.%d' % (s, b), blk)(xin)
     bound = TAP_REL * max(1.0, float(ref.abs().max()))
     err = float((got.double() - ref).abs().max())
     frac = err / bound
+    pr = [fu.measure(got[n:n + 1], ref[n:n + 1], B[n:n + 1], ref32[n:n + 1]) for n in range(nb)]
+    unit_p, unit_r = max(v[0] for v in pr) / fu.C_MAX['block'], max(v[1] for v in pr) / fu.M
     # ---- bitwise against the other form
     o_outs, o_taps, o_prof = g['other']
     diff = [k for k in g['taps'] if not torch.equal(g['taps'][k], o_taps[k])]
@@ -277,11 +264,13 @@ def test_row(rid):
     ohit = [p for p in o_prof if p[0].split('|')[0] == launch]
     distinct = ohit[0][5][0] != hit[0][5][0]
     ora = g['oracle']
-    print('%-14s %dx%d N=%d f=%d %-5s<%d,%d,%s> %2d->%3d->%2d plane %2dx%2d grid %3d  blk %.3f  taps %s outs %s  other form %s  %.2f s (group %.2f s)'
-          % (rid, H, W, N, flip, key[0], key[1], key[2], 'FT'[key[3]], cin, cexp, cout, h, w, hit[0][5][0], frac,
+    print('%-14s %dx%d N=%d f=%d %-5s<%d,%d,%s> %2d->%3d->%2d plane %2dx%2d grid %3d  blk %.3f  P %.3f R %.3f  taps %s outs %s  other form %s  %.2f s (group %.2f s)'
+          % (rid, H, W, N, flip, key[0], key[1], key[2], 'FT'[key[3]], cin, cexp, cout, h, w, hit[0][5][0], frac, unit_p, unit_r,
              '%.3f' % (ora[0] / TAP_REL) if ora else 'FAIL', '%.3f' % (ora[2] / NET_ATOL) if ora else 'FAIL',
              'grid %d' % ohit[0][5][0] if distinct else 'same', time.time() - t0, g['wall']))
     assert err <= bound, ('the block alone against fp64', rid, err, bound, frac)
+    assert unit_p <= 1.0, ('P: an element of the block beyond c_max u B', rid, unit_p)
+    assert unit_r <= 1.0, ('R: the block beyond m times the fp32 reference', rid, unit_r)
     if g['err'] is not None:
         raise g['err']
     assert not diff and all(same), ('not bit-identical to the other form', rid, diff, same)

@@ -15,7 +15,12 @@ Per row, on the device (one profiled forward):
     ``torch.flip(x, [3])``;
   * the profile's launch names == the derived list, its tags == the derived <K,S> forms;
   * batched == per-image, flip = 2 == an explicit flip, flip = 1 == the flipped input: ``torch.equal``;
-  * the worst criterion as a fraction of its bound, per row and per <K,S>/NB form (printed; run with -s).
+  * the worst criterion as a fraction of its bound, per row and per <K,S>/NB form (printed; run with -s);
+  * every k x k launch as a single-convolution unit of tests/_fp32_units.py on the DEVICE's own input taps, on the first
+    image, the first of the mirrored half and the last: P, every element within c_max u B with B = conv(|x|, |w|) + |b|,
+    and R, rms(e / B) within m times that of the reference's fp32 op on the same input (class 'dense': c_max 17, m 21,
+    from tests/test_fp32_units_cpu.py).  Measured: P at most 0.395 of c_max (first.0 of A_16x1024), R at most 0.157
+    of m (deconv.0 of w1.5_upk7); the worst of each <K,S>/NB form lies between 0.19 and 0.40 / 0.05 and 0.16.
 
 What pins the restatement on these tables: tests/golden/gen_golden_resnet.py asserts it bit-identical to the REAL
 module for ``width_mult`` 0.5 / 1.5 and for filters [20, 12, 10] (rows w0.5, w1.5, f20).  The real module cannot build
@@ -325,6 +330,7 @@ def cpu_headroom(row):
 
 # ------------------------------------------------------------------ on the device
 _FORM_WORST = {}
+_UNIT_WORST = {}              # form -> (worst P as a fraction of c_max, worst R as a fraction of m)
 
 
 def _launch_of_tap(row):
@@ -334,6 +340,81 @@ def _launch_of_tap(row):
         if l[1] > 1 and not nm.startswith('final.'):
             m.setdefault(nm, l)
     return m
+
+
+def dense_units(row, sd):
+    """Every k x k launch of the row as a single-convolution unit of tests/_fp32_units.py: [(launch, inputs, out, fn)],
+    ``inputs`` tap names ('x' = the image), ``out`` a tap name or ('out', I), ``fn(*inputs) -> (ref, B, ref32)`` with
+    the weights folded as the device plan folds them (float64, one rounding to fp32; a deconv's BatchNorm scale in both
+    weight sets, a head's two biases added in float64) and ref32 the reference's own fp32 ops on the same inputs."""
+    import torch.nn.functional as F
+    import _fp32_units as fu
+    d = rr.derive(row_cfg(row), row[1])
+    by_name = {l[0]: l for l in launches(row)}
+    out = []
+
+    def unit(name, ins, dst, ws, b, stride, ups, act, f32):
+        w = torch.cat(ws, 1)
+
+        def fn(*xs):
+            xs = [F.interpolate(t, scale_factor=2) if ups else t for t in xs]
+            ref, B = fu.conv_unit(torch.cat(xs, 1), w, b, stride, w.shape[2] // 2)
+            ref = ref if act is None else torch.clamp(ref, 0.0, act)
+            with torch.no_grad():
+                return ref, B, f32(*xs)
+        out.append((by_name[name], ins, dst, fn))
+
+    def cbr(name, src, dst, conv, bn, stride):
+        w, b = fu.fold(sd, conv + '.weight', bn)
+        unit(name, [src], dst, [w], b, stride, 0, 6.0, lambda x: rr._convbnrelu6(x, sd, conv, bn, stride))
+
+    cbr('first.0', 'x', 'first.0', 'first.0.0', 'first.0.1', 2)
+    cbr('first.1', 'first.0', 'first', 'first.1.0', 'first.1.1', 1)
+    prev, ends = 'first', ['first']
+    for s, blocks in enumerate(d['stages']):
+        for b, blk in enumerate(blocks):
+            p = 'stage.%d.%d' % (s, b)
+            cbr(p + '.inv', prev, p + '.inv', p + '.inv.0', p + '.inv.1', blk['stride'])
+            prev = p
+        ends.append(prev)
+    refined, raw = ends[-1], ends[-2]
+    for i in range(len(d['deconv'])):
+        bn = 'deconv_bnrelu.%d.0' % i
+        kr, kw = 'deconv_refined.%d.conv.weight' % i, 'deconv_raw.%d.conv.weight' % i
+        wr, sh = fu.fold(sd, kr, bn)
+        ww, _ = fu.fold(sd, kw, bn)
+        pad = wr.shape[2] // 2
+        unit('deconv.%d' % i, [refined, raw], 'deconv.%d' % i, [wr, ww], sh, 1, 1, float('inf'),
+             lambda a, c, kr=kr, kw=kw, bn=bn, pad=pad: F.relu(rr._bn(
+                 F.conv2d(a, sd[kr], None, 1, pad) + F.conv2d(c, sd[kw], None, 1, pad), sd, bn)))
+        refined, raw = 'deconv.%d' % i, ends[-i - 3]
+        if i > 0:
+            j = i - 1
+            wr, _ = fu.fold(sd, 'final_refined.%d.weight' % j, None)
+            ww, _ = fu.fold(sd, 'final_raw.%d.weight' % j, None)
+            bias = (sd['final_refined.%d.bias' % j].double() + sd['final_raw.%d.bias' % j].double()).float().double()
+            unit('final.%d' % j, [refined, raw], ('out', j), [wr, ww], bias, 1, 0, None,
+                 lambda a, c, j=j: F.conv2d(a, sd['final_refined.%d.weight' % j], sd['final_refined.%d.bias' % j], 1, 1)
+                 + F.conv2d(c, sd['final_raw.%d.weight' % j], sd['final_raw.%d.bias' % j], 1, 1))
+    return out
+
+
+def check_dense_units(row, sd, xin, taps, outs, images):
+    """P and R of tests/_fp32_units.py (kind 'dense') for every k x k launch on the device's own input taps
+    (``taps``: name -> (N', C, h, w) on the host), for the images ``images`` of the device batch.  Returns
+    {launch name: (worst P as a fraction of c_max, worst R as a fraction of m)}; asserts both."""
+    import _fp32_units as fu
+    rows = {}
+    units = dense_units(row, sd)
+    for n in images:
+        for launch, ins, dst, fn in units:
+            ref, B, ref32 = fn(*[xin[n:n + 1] if k == 'x' else taps[k][n:n + 1] for k in ins])
+            got = outs[dst[1]][n:n + 1].cpu() if isinstance(dst, tuple) else taps[dst][n:n + 1]
+            assert got.shape == ref.shape, (launch[0], got.shape, ref.shape)
+            pf, rf = fu.check(got, ref, B, ref32, 'dense', (row[0], launch[0], 'image', n))
+            old = rows.get(launch[0], (0.0, 0.0))
+            rows[launch[0]] = (max(old[0], pf), max(old[1], rf))
+    return rows
 
 
 @pytest.mark.gpu
@@ -347,6 +428,7 @@ def test_row_vs_fp64_names_and_bitwise(cid):
     x = make_input(row)
     xd = x.cuda()
     lst = launches(row)
+    by_launch = {l[0]: l for l in lst}
 
     # ---- one profiled forward: names and tags
     outs, prof = profiled_forward(m, xd, flip)
@@ -394,6 +476,20 @@ def test_row_vs_fp64_names_and_bitwise(cid):
     print('census %-14s N=%d flip=%d %4dx%-4d worst %.3f of the bound at %s' % (cid, N, flip, H, W, worst[0], worst[1]))
     assert not bad, bad[:8]
 
+    # ---- every k x k launch as a single-convolution unit on the device's own input: P and R (tests/_fp32_units.py), on
+    #      the first image, the first of the mirrored half and the last
+    xin = x if flip == 0 else torch.cat([x, torch.flip(x, [3])])
+    full = {nm: dev_taps[nm].view((-1,) + tuple(t64[nm].shape[1:])) for nm in names}
+    images = sorted({0, xin.shape[0] - 1} | ({N} if flip == 2 else set()))
+    urows = check_dense_units(row, sd, xin, full, outs, images)
+    for nm, (pf, rf) in urows.items():
+        key = 'form<%d,%d>/NB%d' % (by_launch[nm][1], by_launch[nm][2], geometry(by_launch[nm])['NB'])
+        old = _UNIT_WORST.get(key, (0.0, 0.0))
+        _UNIT_WORST[key] = (max(old[0], pf), max(old[1], rf))
+    wp, wr = max(urows.items(), key=lambda kv: kv[1][0]), max(urows.items(), key=lambda kv: kv[1][1])
+    print('units  %-14s %d launches x %d images: P %.3f of c_max at %s, R %.3f of m at %s'
+          % (cid, len(urows), len(images), wp[1][0], wp[0], wr[1][1], wr[0]))
+
     # ---- bitwise: batched == per-image, flip = 2 == an explicit flip, flip = 1 == the flipped input
     xf = torch.flip(xd, [3]).contiguous()
     plain = [o.clone() for o in m.forward_native(xd, 0)]
@@ -419,7 +515,8 @@ def test_worst_fraction_per_form():
         print('census: no row ran in this process, nothing to summarise')
         return
     for key in sorted(_FORM_WORST):
-        print('census form %-16s worst %.3f of the bound at %s' % ((key,) + _FORM_WORST[key]))
+        print('census form %-16s worst %.3f of the bound at %s; unit P %.3f of c_max, R %.3f of m'
+              % ((key,) + _FORM_WORST[key] + _UNIT_WORST.get(key, (float('nan'), float('nan')))))
     want = {'form<%d,%d>/NB%d' % (k, s, nb) for k in (3, 5, 7) for s in (1, 2) for nb in (1, 2)}
     got = set(_FORM_WORST)
     # the finals are compared as outputs, every other launch through its own tap: all twelve forms are reached

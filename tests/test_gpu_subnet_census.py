@@ -269,10 +269,10 @@ def test_row_fp32_vs_oracle(rid):
     assert not isinstance(res, str), ('fp32 refuses nothing', rid, res)
     m, arch, sd, x, outs, launches = res
     LAUNCHES[(rid, 'f32')] = launches
-    worst_tap, name, worst_out = check_fp32(m, arch, sd, x, flip, outs)
-    print('%s f32 %dx%d N=%d flip=%d: taps %.3f of the bound (%s), outputs %.3f; %.1f s; tags %s'
-          % (rid, H, W, N, flip, worst_tap / TAP_REL, name, worst_out / NET_ATOL, time.time() - t0,
-             ' '.join(sorted({t for _, t in launches}))))
+    worst_tap, name, worst_out, unit_p, unit_r = check_fp32(m, arch, sd, x, flip, outs)
+    print('%s f32 %dx%d N=%d flip=%d: taps %.3f of the bound (%s), outputs %.3f; units P %.3f of c_max, R %.3f of m; %.1f s; '
+          'tags %s' % (rid, H, W, N, flip, worst_tap / TAP_REL, name, worst_out / NET_ATOL, unit_p, unit_r, time.time() - t0,
+                       ' '.join(sorted({t for _, t in launches}))))
     if rid.startswith('d'):
         _same_deconv_forms_as_256(rid, vec, 'f32', launches)
 
@@ -325,8 +325,9 @@ def _keyed_row(row):
     else:
         rows = check_bf16(m, arch, sd, x, flip, outs, [n for n, _ in launches], chunk=8)
         crit = max(r[2] for r in rows.values())
-    print('%s: worst criterion %.3f of its bound; %.1f s; tags %s'
-          % (gid, crit, time.time() - t0, ' '.join(sorted({t for _, t in launches}))))
+    units = '; units P %.3f of c_max, R %.3f of m' % worst[3:5] if storage == 'f32' else ''
+    print('%s: worst criterion %.3f of its bound%s; %.1f s; tags %s'
+          % (gid, crit, units, time.time() - t0, ' '.join(sorted({t for _, t in launches}))))
 
 
 @pytest.mark.parametrize('gid', [g[0] for g in sp.GATE_ROWS])
